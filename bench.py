@@ -1,14 +1,25 @@
 """Throughput bench of the siamese point-cloud ReID hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--pairs B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--pairs B] [--full]
+                    [--dump-outputs DIR]
 
 One step = one pass of the hot path (siamese_forward + match_forward_inference)
 over one batch of B synthetic pairs that is already resident in HBM.  Every rank (one process
 per GPU, RCCL only for the barrier / max-reduce of the timing) runs its own independent shard of
 pairs -- the path has no data-path collective -- so scaling is weak and `value` is the whole-job
-pairs/s.  Prints ONE JSON line on rank 0 (see the task contract) carrying `roofline` for the
-dominant kernel and, at N=1, `cpu_baseline` (the torch restatement oracle/model_oracle.py, which
-is pinned to the reference by tests/golden, timed on this box's host cores on a bounded sample).
+pairs/s.  Prints ONE JSON line on rank 0 (see the task contract).
+
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, unit,
+higher_is_better, dtype, ms_per_step, ...): nothing else.  `--full` adds everything else the
+bench measures: `roofline` for the dominant kernel (its own profiled passes, the clock probe),
+the deviation from the f32 path, the graph-vs-eager pilot, the guard sentinel's cost, and for the
+default run the companion workloads (`also`) and, at N=1, `cpu_baseline` (the torch restatement
+oracle/model_oracle.py, which is pinned to the reference by tests/golden, timed on the host's
+cores on a bounded sample).
+
+`--dump-outputs DIR` writes what the timed path returned in its last timed step (rank 0's shard)
+as DIR/<name>.npy in float32: inputs and weights are seeded, so two builds run with the same
+arguments can be compared output for output.
 """
 import argparse
 import copy
@@ -221,7 +232,7 @@ def train_bench(args, desc, n, bl, pairs, rank, world, steps=None, warmup=None):
     """training throughput (reported separately from the inference metric): pairs/s of
     Trainer.step = ReIDNet.train_step forward + backward, ONE flat-bucket gradient all-reduce over RCCL, gradient
     clipping and AdamW with the cyclic schedule, on a fixed synthetic batch already resident in HBM"""
-    from pcr_amd import shard, train, train_ops
+    from pcr_amd import shard, train
     from pcr_amd import testing as T
     steps = steps or args.steps
     warmup = args.warmup if warmup is None else warmup
@@ -250,10 +261,19 @@ def train_bench(args, desc, n, bl, pairs, rank, world, steps=None, warmup=None):
     prewarm()
     # (a pilot of both ways like the inference lines' was tried: an eager step AFTER a replay runs on the trainer's own
     # stream with autograd's cross-stream synchronisation and measures 13 ms against 10.3 -- not a fair pilot; eager stays)
-    dt, out = shard.timed(lambda: tr.step(data)["loss"].detach(), steps, warmup,
+    dt, out = shard.timed(lambda: train_outputs(tr.step(data)), steps, warmup,
                           sync=torch.cuda.synchronize, device="cuda")
-    assert torch.isfinite(out).all()
+    assert torch.isfinite(out["loss"]).all()
+    keep_outputs(out)
     per_rank = [t / steps * 1e3 for t in shard.LAST_RANK_SECONDS]
+    graphed = tr.graph
+    if not args.full:
+        line = None
+        if rank == 0:
+            line = train_line(desc, n, bl, pairs, world, steps, warmup, dt, per_rank, tr, graphed)
+        del model, tr, data
+        torch.cuda.empty_cache()
+        return line
     # per-launch device times of one more step (events on the launch stream): the dominant TRAINING launch.  EVERY rank
     # runs that step (it contains the gradient all-reduce: rank 0 alone would wait for the others forever); only rank
     # 0 records it
@@ -261,7 +281,6 @@ def train_bench(args, desc, n, bl, pairs, rank, world, steps=None, warmup=None):
     clk = clock_probe() if rank == 0 else None
     if rank == 0:
         engine.PROFILE = []
-    graphed = tr.graph
     tr.graph = False             # (the per-launch events need the launches themselves: this one step runs eager)
     tr.step(data)
     torch.cuda.synchronize()
@@ -297,26 +316,39 @@ def train_bench(args, desc, n, bl, pairs, rank, world, steps=None, warmup=None):
                          "(events on the launch stream), the rest (norms, attention core, reductions, packing, AdamW) is in "
                          "ms_per_step only")
         add_clock(roof, clk)
-        line = {
-            "metric": "siamese training pairs/sec @%d pts" % n, "value": world * pairs * steps / dt,
-            "unit": "pairs/s", "n_gpus": world, "steps": steps, "warmup": warmup,
-            "ms_per_step": dt / steps * 1e3, "per_rank_ms_per_step": per_rank, "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None,
-            "dtype": {"f32": "f32",
-                      "bf16x3": "f32 forward; split bf16 (three bf16 MFMAs per product) for the gradient products of the "
-                                "128 x 128 grouped-MLP layers and of the fused attention chains",
-                      "bf16x3_all": "f32; split bf16 for the fused attention chains (forward too) and the gradient "
-                                    "products of the 128 x 128 grouped-MLP layers"}[train_ops.TRAIN_PRECISION],
-            "data": "synthetic (randn clouds, seeded random-init weights)",
-            "config": {"workload": "pt128_train: %s" % desc, "pairs_per_gpu_per_step": pairs, "points": n,
-                       "backbone_list": bl, "parallelism": "data parallel x%d, one %d-byte gradient bucket per step"
-                       % (world, tr.bucket.nbytes()), "rccl_ranks": world,
-                       "launch": "hipgraph: forward + backward replayed from one HIP graph, exchange + update eager"
-                       if graphed else "eager (one launch per node)"},
-            "roofline": roof}
+        line = train_line(desc, n, bl, pairs, world, steps, warmup, dt, per_rank, tr, graphed)
+        line["roofline"] = roof
     del model, tr, data
     torch.cuda.empty_cache()
     return line
+
+
+def train_outputs(out):
+    """what a caller of Trainer.step receives, as tensors without autograd history (the loss and the gradient norm)"""
+    got = {"loss": out["loss"].detach()}
+    if out.get("grad_norm") is not None:
+        got["grad_norm"] = out["grad_norm"].detach()
+    return got
+
+
+def train_line(desc, n, bl, pairs, world, steps, warmup, dt, per_rank, tr, graphed):
+    from pcr_amd import train_ops
+    return {
+        "metric": "siamese training pairs/sec @%d pts" % n, "value": world * pairs * steps / dt,
+        "unit": "pairs/s", "n_gpus": world, "steps": steps, "warmup": warmup,
+        "ms_per_step": dt / steps * 1e3, "per_rank_ms_per_step": per_rank, "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None,
+        "dtype": {"f32": "f32",
+                  "bf16x3": "f32 forward; split bf16 (three bf16 MFMAs per product) for the gradient products of the "
+                            "128 x 128 grouped-MLP layers and of the fused attention chains",
+                  "bf16x3_all": "f32; split bf16 for the fused attention chains (forward too) and the gradient "
+                                "products of the 128 x 128 grouped-MLP layers"}[train_ops.TRAIN_PRECISION],
+        "data": "synthetic (randn clouds, seeded random-init weights)",
+        "config": {"workload": "pt128_train: %s" % desc, "pairs_per_gpu_per_step": pairs, "points": n,
+                   "backbone_list": bl, "parallelism": "data parallel x%d, one %d-byte gradient bucket per step"
+                   % (world, tr.bucket.nbytes()), "rccl_ranks": world,
+                   "launch": "hipgraph: forward + backward replayed from one HIP graph, exchange + update eager"
+                   if graphed else "eager (one launch per node)"}}
 
 
 def clock_probe(iters=20000):
@@ -345,17 +377,43 @@ def clock_probe(iters=20000):
 _PREWARMED = False
 
 
+LAST_OUTPUTS = {}            # name -> host tensor: what the timed path returned in its last timed step (--dump-outputs)
+DUMP_LIMIT = 64 << 20        # bytes of all the dumped arrays together
+
+
+def keep_outputs(out):
+    LAST_OUTPUTS.clear()
+    for name, t in (out.items() if isinstance(out, dict) else (("logits", out),)):
+        t = t.detach().cpu()
+        LAST_OUTPUTS[name] = t if t.dtype == torch.float64 else t.float()
+
+
+def dump_outputs(outdir, outputs):
+    """outputs -> <outdir>/<name>.npy.  An array larger than its share of DUMP_LIMIT is written as a fixed, seeded sample
+    of its flattened elements (same indices on every run of the same shape)."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    share = DUMP_LIMIT // max(1, len(outputs))
+    for name, t in outputs.items():
+        a = t.numpy()
+        if a.nbytes > share:
+            idx = np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False)
+            a = a.reshape(-1)[np.sort(idx)]
+        np.save(os.path.join(outdir, name + ".npy"), a)
+
+
 LAST_PILOT = {}              # {"eager_ms": .., "hipgraph_ms": ..} of the last graph_step() (both go into the record)
 
 
-def graph_step(fn):
+def graph_step(fn, with_pilot=True):
     """fn (a forward pass over resident inputs, no host round trip inside) captured ONCE into a HIP graph and replayed:
     -> (callable returning fn's output tensor, "hipgraph") or (fn, "eager: <why>").  Same launches, same bits -- the
     replay is checked against an eager call before it is used -- but the step no longer depends on how fast this box's
     host can issue ~25 launches and their tensor allocations (a loaded host of the pool: 6.7 ms eager against 5.1).
     The mode is FIXED, never picked by a race: PCR_BENCH_GRAPH=1 (the default) times the replay, PCR_BENCH_GRAPH=0 the
     eager loop; an untimed three-step pilot of BOTH ways is recorded beside the result (LAST_PILOT -> config.eager_ms /
-    config.hipgraph_ms) so that lines of either mode stay comparable."""
+    config.hipgraph_ms) so that lines of either mode stay comparable.  with_pilot=False (a plain bench run) skips the
+    pilot: LAST_PILOT stays empty."""
     LAST_PILOT.clear()
     want_graph = os.environ.get("PCR_BENCH_GRAPH", "1") != "0"
 
@@ -374,7 +432,11 @@ def graph_step(fn):
             ref = None
             for _ in range(2):                      # lazy plans, LDS attributes, allocator pools: all set up eagerly
                 ref = fn()
-            LAST_PILOT["eager_ms"] = pilot(fn)      # (BEFORE the capture: the first eager calls after one are not the steady state)
+            if with_pilot:
+                # (BEFORE the capture: the first eager calls after one are not the steady state)
+                LAST_PILOT["eager_ms"] = pilot(fn)
+            elif not want_graph:
+                return fn, "eager: PCR_BENCH_GRAPH=0"
             torch.cuda.synchronize()
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, capture_error_mode="thread_local"):   # (other threads -- RCCL's watchdog -- may call HIP meanwhile)
@@ -388,7 +450,8 @@ def graph_step(fn):
             g.replay()
             return out
         run._graph = g
-        LAST_PILOT["hipgraph_ms"] = pilot(run)
+        if with_pilot:
+            LAST_PILOT["hipgraph_ms"] = pilot(run)
         if not want_graph:
             del run, g
             return fn, "eager: PCR_BENCH_GRAPH=0"
@@ -597,52 +660,60 @@ def measure(workload, args, rank, world, pairs=None, cloud_kind=None, skip_repea
     # deviations go into config.guard
     guard = (model.calibrate_precision(s1, s2, max_pairs=int(s1.shape[0]))
              if (engine.GUARD and engine.PRECISION == "bf16x3") else None)
-    step_fn, launch_mode = graph_step(lambda: hot_path(model, s1, s2))
+    step_fn, launch_mode = graph_step(lambda: hot_path(model, s1, s2), with_pilot=args.full)
     pilot_ms = {k: round(v, 4) for k, v in LAST_PILOT.items()}
     with torch.no_grad():
         dt, out = shard.timed(step_fn, steps, warmup, sync=torch.cuda.synchronize, device="cuda")
     assert torch.isfinite(out).all()
     out = out.clone()
+    keep_outputs(out)
     del step_fn
     per_rank = [t / steps * 1e3 for t in shard.LAST_RANK_SECONDS]      # every rank's own time (the max is ms_per_step)
     rec = None
     if rank == 0:
-        clk = clock_probe()
-        roof, _ = roofline_of(model, s1, s2, workload, pairs)
-        add_clock(roof, clk)
-        add_sustained(roof)
-        with torch.no_grad(), engine.precision("f32"):
-            ref = hot_path(model, s1, s2)
+        if args.full:
+            clk = clock_probe()
+            roof, _ = roofline_of(model, s1, s2, workload, pairs)
+            add_clock(roof, clk)
+            add_sustained(roof)
+        else:
+            # a plain run: ONE profiled eager pass, only for what `dtype` names (the dominant launch's arithmetic)
+            roof = roofline_object(profile_kernels(model, s1, s2, reps=1, detail=True))
         rec = dict(value=world * pairs * steps / dt, unit="pairs/s", steps=steps, warmup=warmup,
                    ms_per_step=dt / steps * 1e3, per_rank_ms_per_step=per_rank,
                    # the arithmetic the workload's dominant matrix launch ran in (PointNet / DGCNN: their encoder GEMMs
                    # are f32-input MFMA whatever the mode; only their matching attention follows it)
                    dtype=(roof.get("kernel_arithmetic") if roof["bound"] == "mfma" and roof.get("kernel_arithmetic")
                           else PREC_INFO[engine.PRECISION][0]),
-                   max_abs_dlogit_vs_f32_path=float((out - ref).abs().max()),
                    data="synthetic (%s clouds, seeded random-init weights with non-trivial BN statistics)" % cloud_kind,
                    config={"workload": "%s: %s" % (workload, desc), "pairs_per_gpu_per_step": pairs, "points": n,
                            "backbone_list": bl, "parallelism": "independent pair shards x%d" % world,
                            "rccl_ranks": world,
                            "precision": precision_text(engine.PRECISION), "precision_tag": engine.PRECISION,
-                           "launch": launch_mode, **pilot_ms},
-                   roofline=roof)
+                           "launch": launch_mode, **pilot_ms})
         if guard is not None:
             rec["config"]["guard"] = {"level": guard["level"], "bound": guard["bound"],
                                       "dlogit": {str(k): float("%.2e" % v) for k, v in guard["dlogit"].items()}}
+        if kind == "ssg":
+            rec["config"]["skip_repeats"] = bool(skip_repeats)
+    if rank == 0 and args.full:
+        with torch.no_grad(), engine.precision("f32"):
+            ref = hot_path(model, s1, s2)
+        rec["max_abs_dlogit_vs_f32_path"] = float((out - ref).abs().max())
+        rec["roofline"] = roof
+        if guard is not None:
             sen = sentinel_cost(model, s1, s2, rec["ms_per_step"])
             if sen:
                 rec["config"]["guard"]["sentinel"] = sen
         if kind == "ssg":
             rec["config"]["fill"] = ssg_fill(model, s1)
-            rec["config"]["skip_repeats"] = bool(skip_repeats)
         else:
             rec["config"]["fill"] = "kNN groups: every one of the K rows is a genuine neighbour (fill 1.0)"
-        if args.detail:
-            det = profile_kernels(model, s1, s2, detail=True)
-            for k, v in sorted(det.items(), key=lambda kv: -kv[1][0]):
-                print("%-52s %8.3f ms x%d  %7.2f TFLOP/s  %7.1f GB/s(alg)" % (
-                    k, v[0], v[1], v[2] / (v[0] * 1e-3) / 1e12, v[3] / (v[0] * 1e-3) / 1e9), file=sys.stderr)
+    if rank == 0 and args.detail:
+        det = profile_kernels(model, s1, s2, detail=True)
+        for k, v in sorted(det.items(), key=lambda kv: -kv[1][0]):
+            print("%-52s %8.3f ms x%d  %7.2f TFLOP/s  %7.1f GB/s(alg)" % (
+                k, v[0], v[1], v[2] / (v[0] * 1e-3) / 1e12, v[3] / (v[0] * 1e-3) / 1e9), file=sys.stderr)
     del model, s1, s2
     torch.cuda.empty_cache()
     return rec, sd
@@ -686,17 +757,15 @@ def gallery_bench(args, desc, n, bl, pairs, rank, world, steps=None, warmup=None
         return model.match_gallery(h, xyz, combos)
     prewarm()
     guard = model.calibrate_precision(clouds[:G], clouds[G:]) if (engine.GUARD and engine.PRECISION == "bf16x3") else None
-    step_fn, launch_mode = graph_step(step)
+    step_fn, launch_mode = graph_step(step, with_pilot=args.full)
     pilot_ms = {k: round(v, 4) for k, v in LAST_PILOT.items()}
     with torch.no_grad():
         dt, out = shard.timed(step_fn, steps, warmup, sync=torch.cuda.synchronize, device="cuda")
     assert torch.isfinite(out).all() and out.numel() == P
+    keep_outputs({"scores": out})
     del step_fn
     line = None
     if rank == 0:
-        clk = clock_probe()
-        roof, _ = roofline_of(None, None, None, "gallery128", P, fn=step)
-        add_clock(roof, clk)
         line = {"metric": "siamese pair-comparisons/sec @%d pts (gallery: every object encoded once)" % n,
                 "value": world * P * steps / dt, "unit": "pairs/s", "n_gpus": world, "steps": steps,
                 "warmup": warmup, "ms_per_step": dt / steps * 1e3, "higher_is_better": True,
@@ -704,12 +773,16 @@ def gallery_bench(args, desc, n, bl, pairs, rank, world, steps=None, warmup=None
                 "data": "synthetic (randn clouds, seeded random-init weights with non-trivial BN statistics)",
                 "config": {"workload": "gallery128: %s" % desc, "precision": precision_text(engine.PRECISION), "pairs_per_gpu_per_step": P, "objects_per_gpu_per_step": 2 * G,
                            "points": n, "backbone_list": bl, "parallelism": "independent galleries x%d" % world,
-                           "rccl_ranks": world, "launch": launch_mode, "precision_tag": engine.PRECISION, **pilot_ms},
-                "roofline": roof}
+                           "rccl_ranks": world, "launch": launch_mode, "precision_tag": engine.PRECISION, **pilot_ms}}
         if guard is not None:
             line["config"]["guard"] = {"level": guard["level"], "bound": guard["bound"],
                                        "dlogit": {str(k): float("%.2e" % v) for k, v in guard["dlogit"].items()}}
-        if cpu and world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            clk = clock_probe()
+            roof, _ = roofline_of(None, None, None, "gallery128", P, fn=step)
+            add_clock(roof, clk)
+            line["roofline"] = roof
+        if args.full and cpu and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = gallery_cpu_baseline(sd, n, bl, G)
     del model, clouds, combos
     torch.cuda.empty_cache()
@@ -783,7 +856,8 @@ def compact_line(full):
     line = {k: full[k] for k in keep if k in full}
     line["data"] = str(line.get("data", ""))[:110]
     line["config"] = compact_config(full.get("config", {}))
-    line["roofline"] = compact_roofline(full.get("roofline"))
+    if "roofline" in full:                          # (--full)
+        line["roofline"] = compact_roofline(full["roofline"])
     if "cpu_baseline" in full:
         cb = dict(full["cpu_baseline"])
         cb["sample"] = str(cb.get("sample", ""))[:80]
@@ -918,6 +992,12 @@ def dry_run(args):
         dist.destroy_process_group()
 
 
+def write_outputs(args, rank):
+    """--dump-outputs: rank 0 writes its shard's outputs of the last timed step (before any companion runs)"""
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, LAST_OUTPUTS)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -931,8 +1011,13 @@ def main():
     ap.add_argument("--clouds", default=None, choices=["box", "dup", "crop", "randn"], help="synthetic cloud distribution")
     ap.add_argument("--full-groups", action="store_true",
                     help="SSG: evaluate all K rows of every ball-query group (no duplicate-row skipping)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-also", action="store_true", help="skip the companion measurements of the default run")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: roofline, f32-path deviation, graph/eager pilot, "
+                         "guard sentinel cost, and (default run) the companion workloads and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last timed step as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-also", action="store_true", help="--full: skip the companion measurements of the default run")
     ap.add_argument("--detail", action="store_true", help="also print per-launch device times (stderr)")
     ap.add_argument("--dry-run", action="store_true", help="CPU/gloo rehearsal of the launch + timing protocol")
     args = ap.parse_args()
@@ -964,13 +1049,19 @@ def main():
 
     desc, kind, n, bl, dpairs = WORKLOADS[args.workload]
     if kind == "pt_train":
-        return finish(train_bench(args, desc, n, bl, args.pairs or dpairs, rank, world), rank)
+        line = train_bench(args, desc, n, bl, args.pairs or dpairs, rank, world)
+        write_outputs(args, rank)
+        return finish(line, rank)
     if kind == "gallery":
-        return finish(gallery_bench(args, desc, n, bl, args.pairs or dpairs, rank, world), rank)
+        line = gallery_bench(args, desc, n, bl, args.pairs or dpairs, rank, world)
+        write_outputs(args, rank)
+        return finish(line, rank)
 
     rec, sd = measure(args.workload, args, rank, world, pairs=args.pairs or None, cloud_kind=args.clouds,
                       skip_repeats=not args.full_groups)
-    default_run = (args.workload == "pt1024" and not args.pairs and not args.clouds and not args.full_groups)
+    write_outputs(args, rank)
+    default_run = (args.full and args.workload == "pt1024" and not args.pairs and not args.clouds
+                   and not args.full_groups)
     also = []
     if default_run and world > 1 and not args.no_also:
         # N > 1: the inference headline has no collective at all, so a scaling run would never exercise the gradient
@@ -1027,12 +1118,14 @@ def main():
             "value": rec["value"], "unit": "pairs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": rec["ms_per_step"], "per_rank_ms_per_step": rec["per_rank_ms_per_step"],
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": rec["dtype"], "max_abs_dlogit_vs_f32_path": rec["max_abs_dlogit_vs_f32_path"],
-            "data": rec["data"], "config": rec["config"], "roofline": rec["roofline"],
+            "dtype": rec["dtype"], "data": rec["data"], "config": rec["config"],
         }
+        for k in ("max_abs_dlogit_vs_f32_path", "roofline"):          # (--full)
+            if k in rec:
+                line[k] = rec[k]
         if also:
             line["also"] = also
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args.workload, sd)
         emit(line)
     if shard.is_dist():

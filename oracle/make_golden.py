@@ -171,6 +171,16 @@ def gen_pointnet():
     rec = dict(h1=_np(h1), h2=_np(h2), logits=_np(logits),
                enc_max=_np(feat.max(dim=2)[0]), enc_mean=_np(feat.mean(dim=2)),
                meta=np.array(json.dumps(dict(pairs=2, n=256, kind="randn", input_seed=1, weight_seed=0))))
+    # the same pass in float64 ("f64:" keys): the f32 stages above carry the rounding of this host's BLAS kernels through
+    # the 1024-channel encoder (up to ~6e-5 on enc_max against the float64 pass), another host's kernels round otherwise
+    m64 = model.double()
+    d1, d2 = s1.double(), s2.double()
+    with torch.no_grad(), contextlib.redirect_stdout(io.StringIO()):
+        xyz1, xyz2, h1, h2 = m64.siamese_forward(d1, d2)
+        _, feat = m64.backbone(torch.cat([d1, d2], 0).permute(0, 2, 1), m64.backbone_list)
+        logits = m64.match_forward_inference(h1, h2, xyz1, xyz2)
+    rec.update({"f64:h1": _np(h1), "f64:h2": _np(h2), "f64:logits": _np(logits),
+                "f64:enc_max": _np(feat.max(dim=2)[0]), "f64:enc_mean": _np(feat.mean(dim=2))})
     np.savez_compressed(os.path.join(GOLD, "pointnet_n256_randn.npz"), **rec)
     with open(os.path.join(GOLD, "pointnet_manifest.json"), "w") as f:
         json.dump(manifest, f)
@@ -648,8 +658,53 @@ def gen_pairs():
     np.savez_compressed(os.path.join(GOLD, "pairs_toy.npz"), **rec)
 
 
+# the reference config files tests/test_config.py builds models from (paths under configs_reid/)
+REF_CONFIGS = (
+    "reid_nuscenes_pts/num_point_ablation_test/pts_point-transformer_r_nus_det_400e_1024pts.py",
+    "reid_nuscenes_pts/testing_pts_pointnet_r_nus_det_500e.py",
+    "reid_waymo_pts/testing_pts_dgcnn_r_waymo_det_400e.py",
+    "reid_waymo_pts/testing_pts_point-transformer_baseline-orig_r_waymo_det_400e.py",
+    "_base_/reidentifiers/reid_pts_point-transformer-1.5M_point-cat.py",
+    "_base_/reidentifiers/reid_pts_point-transformer-7M_point-cat.py",
+    "reid_nuscenes_pts/testing_pts_point-transformer_baseline_r_nus_det_500e.py",
+    "reid_nuscenes_pts/testing_pts_point-transformer_baseline-stnet_r_nus_det_500e.py",
+)
+
+
+def gen_ref_configs():
+    """tests/golden/ref_configs.json: the reference's point-cloud ReID configs as the project's loader (pcr_amd/config.py)
+    merges them -- the `model` and `data` sections of REF_CONFIGS -- and, for every file under reid_nuscenes_pts /
+    reid_waymo_pts, whether it loads ("ok") or names a base file that does not exist ("missing: <file>").  Values only:
+    no config file is copied."""
+    from pcr_amd.config import Config
+    base = os.path.join(ref_loader.REF_ROOT, "configs_reid")
+    rec = {"configs": {}, "load": {}}
+    for rel in REF_CONFIGS:
+        d = Config.fromfile(os.path.join(base, rel)).to_dict()
+        rec["configs"][rel] = {k: d[k] for k in ("model", "data") if k in d}
+    for sub in ("reid_nuscenes_pts", "reid_waymo_pts"):
+        for d, _, files in sorted(os.walk(os.path.join(base, sub))):
+            for f in sorted(files):
+                if f.endswith(".py"):
+                    rel = os.path.relpath(os.path.join(d, f), base)
+                    try:
+                        Config.fromfile(os.path.join(d, f))
+                        rec["load"][rel] = "ok"
+                    except FileNotFoundError as e:
+                        rec["load"][rel] = "missing: %s" % os.path.basename(str(e.filename or e))
+    with open(os.path.join(GOLD, "ref_configs.json"), "w") as f:
+        json.dump(rec, f, indent=1, sort_keys=True)
+        f.write("\n")
+
+
 if __name__ == "__main__":
     os.makedirs(GOLD, exist_ok=True)
+    if "--only-pointnet" in sys.argv:
+        gen_pointnet()
+        sys.exit(0)
+    if "--only-ref-configs" in sys.argv:
+        gen_ref_configs()
+        sys.exit(0)
     if "--only-pairs" in sys.argv:
         gen_pairs()
         sys.exit(0)
@@ -699,3 +754,4 @@ if __name__ == "__main__":
     gen_eval_metric()
     gen_eval_tables()
     gen_pairs()
+    gen_ref_configs()

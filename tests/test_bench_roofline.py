@@ -111,16 +111,17 @@ def test_bench_quotes_pmc_only_from_a_profile_of_the_same_mode_and_arithmetic(tm
 
 
 def test_graph_step_falls_back_to_the_eager_callable(monkeypatch):
-    """bench.graph_step is an optimisation of the measurement: without a device to capture on (this box), or with
+    """bench.graph_step is an optimisation of the measurement: without a device to capture on, or with
     PCR_BENCH_GRAPH=0, it must hand back the callable it was given and say why; the mode is fixed by the environment,
     never by which way a pilot ran faster"""
     import inspect
+    import torch
     calls = []
 
     def fn():
         calls.append(1)
-        import torch
         return torch.zeros(3)
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)     # (no device, also on a machine with a GPU)
     got, mode = bench.graph_step(fn)
     assert got is fn and mode.startswith("eager"), mode
     monkeypatch.setenv("PCR_BENCH_GRAPH", "0")
@@ -253,3 +254,34 @@ def test_the_sustained_rate_is_informational_and_leaves_peak_and_frac_alone():
                   {"bound": "mfma", "kernel_arithmetic": "f32", "achieved": 1.0}):
         bench.add_sustained(other)
         assert "sustained_bf16" not in other
+
+
+def test_dump_outputs_writes_every_array_within_the_limit(tmp_path, monkeypatch):
+    """--dump-outputs: one <name>.npy per output in float32 / float64; an output above its share of the limit is a fixed,
+    seeded sample (the same elements on every run), so that two builds can be compared output for output"""
+    import numpy as np
+    import torch
+    bench.keep_outputs({"logits": torch.arange(6, dtype=torch.float32).view(6, 1),
+                        "norm": torch.tensor(2.0, dtype=torch.float64)})
+    assert bench.LAST_OUTPUTS["logits"].dtype == torch.float32 and bench.LAST_OUTPUTS["norm"].dtype == torch.float64
+    bench.dump_outputs(str(tmp_path / "a"), bench.LAST_OUTPUTS)
+    assert np.array_equal(np.load(tmp_path / "a" / "logits.npy"), np.arange(6, dtype=np.float32).reshape(6, 1))
+    assert np.load(tmp_path / "a" / "norm.npy").dtype == np.float64
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 4096)
+    big = {"scores": torch.randn(10000, generator=torch.Generator().manual_seed(1))}
+    bench.keep_outputs(big)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), bench.LAST_OUTPUTS)
+    b, c = np.load(tmp_path / "b" / "scores.npy"), np.load(tmp_path / "c" / "scores.npy")
+    assert b.nbytes <= 4096 and np.array_equal(b, c) and np.isin(b, big["scores"].numpy()).all()
+
+
+def test_a_plain_run_only_times_and_full_keeps_the_rest():
+    """a plain `bench.py` run sets up, warms up, times and prints; the companions, the CPU baseline, the roofline passes and
+    the f32 comparison belong to `--full`"""
+    import inspect
+    src = inspect.getsource(bench.main)
+    assert '"--full"' in src and '"--dump-outputs"' in src
+    assert "default_run = (args.full and" in src and "if args.full and world == 1 and not args.no_cpu_baseline" in src
+    msrc = inspect.getsource(bench.measure)
+    assert "if rank == 0 and args.full:" in msrc and "with_pilot=args.full" in msrc

@@ -1,5 +1,6 @@
-"""CPU: the mmcv-free config loader (pcr_amd/config.py) on its own fixture tree and, when the
-reference is present (dev container only), on the reference's configs_reid files, unchanged."""
+"""CPU: the mmcv-free config loader (pcr_amd/config.py) on its own fixture tree, and the reference's configs_reid files
+as that loader merges them (tests/golden/ref_configs.json, recorded by oracle/make_golden.py gen_ref_configs)."""
+import json
 import os
 
 import pytest
@@ -8,7 +9,13 @@ from conftest import GOLDEN
 from pcr_amd.config import Config
 
 MINI = os.path.join(GOLDEN, "configs_mini")
-REF = "/root/reference/configs_reid"
+with open(os.path.join(GOLDEN, "ref_configs.json")) as _f:
+    REF = json.load(_f)
+
+
+def ref_config(rel):
+    """one reference config file (path under configs_reid/) as recorded: its merged `model` and `data` sections"""
+    return Config(REF["configs"][rel])
 
 
 def test_base_merge_rules():
@@ -37,26 +44,23 @@ def test_merge_from_dict():
     assert cfg.model.backbone.conv_out == 32 and cfg.seed == 1 and cfg.model.backbone.type == "Pointnet_Backbone"
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree only exists in the dev container")
 def test_reference_configs_load_unchanged_and_build():
     from mmdet3d.models import build_model
     from pcr_amd import testing as T
-    cfg = Config.fromfile(os.path.join(
-        REF, "reid_nuscenes_pts/num_point_ablation_test/pts_point-transformer_r_nus_det_400e_1024pts.py"))
+    cfg = ref_config("reid_nuscenes_pts/num_point_ablation_test/pts_point-transformer_r_nus_det_400e_1024pts.py")
     assert cfg.model.backbone_list == [1024, 512, 256] and cfg.model.eval_only is True
     assert cfg.data.val.subsample_sparse == 1024 and cfg.data.val_samples_per_gpu == 512
     assert cfg.model.losses_to_use.match is True and cfg.model.losses_to_use.kl is False
     model = build_model(cfg.model)
     assert T.manifest_of(model) == T.load_manifest(os.path.join(GOLDEN, "pt_manifest.json"))
-    cfg = Config.fromfile(os.path.join(REF, "reid_nuscenes_pts/testing_pts_pointnet_r_nus_det_500e.py"))
+    cfg = ref_config("reid_nuscenes_pts/testing_pts_pointnet_r_nus_det_500e.py")
     model = build_model(cfg.model)
     assert T.manifest_of(model) == T.load_manifest(os.path.join(GOLDEN, "pointnet_manifest.json"))
-    cfg = Config.fromfile(os.path.join(REF, "reid_waymo_pts/testing_pts_dgcnn_r_waymo_det_400e.py"))
+    cfg = ref_config("reid_waymo_pts/testing_pts_dgcnn_r_waymo_det_400e.py")
     assert cfg.model.backbone.type == "dgcnn" and cfg.model.use_dgcnn is True
     model = build_model(cfg.model)
     assert T.manifest_of(model) == T.load_manifest(os.path.join(GOLDEN, "dgcnn_manifest.json"))
-    cfg = Config.fromfile(os.path.join(
-        REF, "reid_waymo_pts/testing_pts_point-transformer_baseline-orig_r_waymo_det_400e.py"))
+    cfg = ref_config("reid_waymo_pts/testing_pts_point-transformer_baseline-orig_r_waymo_det_400e.py")
     assert cfg.model.match_type == "xcorr" and cfg.model.local_stage1.type == "local_self_attention"
     model = build_model(cfg.model)
     assert T.manifest_of(model) == T.load_manifest(os.path.join(GOLDEN, "pt_xcorr_manifest.json"))
@@ -65,32 +69,25 @@ def test_reference_configs_load_unchanged_and_build():
     # reid_1.5M_point-transformer-point-cat-lin-xcorr_fp.py -- so the reidentifier files they mean are loaded directly)
     for cfg_file, man in (("_base_/reidentifiers/reid_pts_point-transformer-1.5M_point-cat.py", "pt15m"),
                           ("_base_/reidentifiers/reid_pts_point-transformer-7M_point-cat.py", "pt7m")):
-        cfg = Config.fromfile(os.path.join(REF, cfg_file))
-        with pytest.raises(FileNotFoundError):
-            Config.fromfile(os.path.join(REF, "reid_waymo_pts/testing_pts_1.5M_point-transformer_r_waymo_det_800e.py"))
+        cfg = ref_config(cfg_file)
+        assert REF["load"]["reid_waymo_pts/testing_pts_1.5M_point-transformer_r_waymo_det_800e.py"].startswith(
+            "missing: reid_1.5M_point-transformer-point-cat-lin-xcorr_fp.py")
         assert cfg.model.backbone.mul in (2, 4)
         model = build_model(cfg.model)
         assert T.manifest_of(model) == T.load_manifest(os.path.join(GOLDEN, man + "_manifest.json")), cfg_file
-    cfg = Config.fromfile(os.path.join(REF, "reid_nuscenes_pts/testing_pts_point-transformer_baseline_r_nus_det_500e.py"))
+    cfg = ref_config("reid_nuscenes_pts/testing_pts_point-transformer_baseline_r_nus_det_500e.py")
     assert cfg.model.match_type == "concat" and cfg.model.pool_type == "max"
     model = build_model(cfg.model)              # (incl. the config's 105 M-parameter shape_head, never evaluated)
     man = [m for m in T.manifest_of(model) if not m[0].startswith("shape_head.")]
     assert man == T.load_manifest(os.path.join(GOLDEN, "pt_baseline_manifest.json"))
     del model
-    cfg = Config.fromfile(os.path.join(REF, "reid_nuscenes_pts/testing_pts_point-transformer_baseline-stnet_r_nus_det_500e.py"))
+    cfg = ref_config("reid_nuscenes_pts/testing_pts_point-transformer_baseline-stnet_r_nus_det_500e.py")
     assert cfg.model.match_type == "xcorr-baseline"
     build_model(cfg.model)
     # every point-cloud ReID config of the reference parses
-    n, broken = 0, []
-    for sub in ("reid_nuscenes_pts", "reid_waymo_pts"):
-        for d, _, files in os.walk(os.path.join(REF, sub)):
-            for f in files:
-                if f.endswith(".py"):
-                    try:
-                        Config.fromfile(os.path.join(d, f))
-                        n += 1
-                    except FileNotFoundError:      # a few reference configs name bases that do not exist
-                        broken.append(f)
+    n = sum(v == "ok" for v in REF["load"].values())
+    broken = [k for k, v in REF["load"].items() if v.startswith("missing: ")]   # a few name bases that do not exist
+    assert n + len(broken) == len(REF["load"])
     assert n > 80 and len(broken) <= 10, (n, broken)    # 8 misplaced files in the reference itself
 
 

@@ -81,7 +81,7 @@ def test_bench_runs_two_ranks_on_the_gpu(workload):
                PCR_BENCH_TEST_SAME_DEVICE="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2",
-           "--steps", "2", "--warmup", "1", "--workload", workload, "--pairs", "32", "--no-cpu-baseline"]
+           "--steps", "2", "--warmup", "1", "--workload", workload, "--pairs", "32", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -108,7 +108,7 @@ def test_default_two_rank_run_carries_the_training_companion():
                PCR_BENCH_TEST_SAME_DEVICE="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2",
-           "--steps", "2", "--warmup", "2"]
+           "--steps", "2", "--warmup", "2", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     last = r.stdout.strip().splitlines()[-1]

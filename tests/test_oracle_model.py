@@ -76,15 +76,18 @@ def test_pt_baseline_concat_oracle_matches_reference_golden():
 
 
 def test_pointnet_oracle_matches_reference_golden():
+    """in float64 against the reference's float64 pass ("f64:" keys): in f32 the 1024-channel encoder carries the rounding
+    of the host's BLAS kernels (the f32 golden and the f64 pass differ by ~6e-5 on enc_max), which differs by CPU"""
     g = load_golden("pointnet_n256_randn")
     m = g["meta"]
     s1, s2 = T.synthetic_pairs(m["pairs"], m["n"], m["input_seed"], m["kind"])
+    sd = {k: v.double() if v.is_floating_point() else v for k, v in _sd("pointnet").items()}
     st = {}
     with torch.no_grad():
-        logits = MO.pointnet_pairs(_sd("pointnet"), s1, s2, stages=st)
+        logits = MO.pointnet_pairs(sd, s1.double(), s2.double(), stages=st)
     for k in ("h1", "h2", "enc_max", "enc_mean"):
-        assert np.abs(st[k].numpy() - g[k]).max() < 5e-5, k
-    assert np.abs(logits.numpy() - g["logits"]).max() < TOL
+        assert np.abs(st[k].numpy() - g["f64:" + k]).max() < 5e-5, k
+    assert np.abs(logits.numpy() - g["f64:logits"]).max() < TOL
 
 
 @pytest.mark.parametrize("knn", ["pinned_order", "reference_formula"])

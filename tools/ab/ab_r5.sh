@@ -8,7 +8,7 @@ mkdir -p gpurun_out/ab
 P='import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d["roofline"]; print(sys.argv[1], d["config"]["workload"][:7], "step %.3f ms" % d["ms_per_step"], "dominant %.3f ms" % (r.get("avg_launch_ms") or 0), r.get("per_kernel_ms"))'
 for rep in 1 2 3; do
   for wl in pt1024 pt4096; do
-    PCR_LIB_TAG=r5 PCR_SA_CLAIMS=0 python bench.py --workload $wl --steps 20 --warmup 3 --no-also --no-cpu-baseline 2>/dev/null | python -c "$P" r5
-    python bench.py --workload $wl --steps 20 --warmup 3 --no-also --no-cpu-baseline 2>/dev/null | python -c "$P" HEAD
+    PCR_LIB_TAG=r5 PCR_SA_CLAIMS=0 python bench.py --workload $wl --steps 20 --warmup 3 --full --no-also --no-cpu-baseline 2>/dev/null | python -c "$P" r5
+    python bench.py --workload $wl --steps 20 --warmup 3 --full --no-also --no-cpu-baseline 2>/dev/null | python -c "$P" HEAD
   done
 done

@@ -7,7 +7,7 @@ WLS=${@:-pt1024}
 P='import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d["roofline"]; print("%-6s" % sys.argv[1], d["config"]["workload"][:7], "step %.3f ms" % d["ms_per_step"], "dominant %.3f ms" % (r.get("avg_launch_ms") or 0), "dlogit %.2e" % (d.get("max_abs_dlogit_vs_f32_path") or 0), r.get("per_kernel_ms"))'
 for rep in 1 2 3; do
   for wl in $WLS; do
-    PCR_LIB_TAG=$TAG python bench.py --workload $wl --steps 20 --warmup 3 --no-also --no-cpu-baseline 2>/dev/null | python -c "$P" $TAG
-    python bench.py --workload $wl --steps 20 --warmup 3 --no-also --no-cpu-baseline 2>/dev/null | python -c "$P" HEAD
+    PCR_LIB_TAG=$TAG python bench.py --workload $wl --steps 20 --warmup 3 --full --no-also --no-cpu-baseline 2>/dev/null | python -c "$P" $TAG
+    python bench.py --workload $wl --steps 20 --warmup 3 --full --no-also --no-cpu-baseline 2>/dev/null | python -c "$P" HEAD
   done
 done

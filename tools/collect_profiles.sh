@@ -7,7 +7,7 @@ TAG=$1; WLS=$2
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/prof_$TAG; mkdir -p $OUT
 for W in $WLS; do
-  ARGS="--workload $W --steps 5 --warmup 2 --no-cpu-baseline --no-also"
+  ARGS="--workload $W --steps 5 --warmup 2 --full --no-cpu-baseline --no-also"
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${W}_stats -o t -- python3 bench.py $ARGS > $OUT/${W}_bench.json 2> $OUT/${W}_stats.err
   cp $OUT/${W}_stats/t_kernel_stats.csv $OUT/${TAG}_${W}_kernel_stats.csv
   if [ "$W" != "pt128_train" ]; then

@@ -4,7 +4,7 @@ set -u
 W=${1:-pt1024}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/pmc_$W; mkdir -p $OUT
-ARGS="--workload $W --steps 3 --warmup 2 --no-cpu-baseline --no-also"
+ARGS="--workload $W --steps 3 --warmup 2 --full --no-cpu-baseline --no-also"
 rocprofv3 --kernel-trace --pmc SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d $OUT/a -o t -- python3 bench.py $ARGS > /dev/null 2> $OUT/a.err
 rocprofv3 --kernel-trace --pmc SQ_ACTIVE_INST_VALU SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_ANY SQ_WAVE_CYCLES SQ_ACTIVE_INST_ANY SQ_BUSY_CYCLES --output-format csv -d $OUT/b -o t -- python3 bench.py $ARGS > /dev/null 2> $OUT/b.err
 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_INSTS_SALU SQ_VALU_MFMA_COEXEC_CYCLES SQ_ACTIVE_INST_VALU2 --output-format csv -d $OUT/c -o t -- python3 bench.py $ARGS > /dev/null 2> $OUT/c.err

@@ -1560,6 +1560,345 @@ void attn_apply_stream64_kernel(AttnArgs a) {
 #undef PCR_AMARK
 #undef PCR_ANEXT
 }
+
+// ---- the same wave-autonomous form at d = c1 = cout = 128 (SA3's self-attention: q_pos, residual, no trailing conv) --------
+// A wave owns a 32-token block from the feature load to the store and chains Q -> message -> FFN0 -> FFN1 through its
+// registers exactly as attn_apply_stream64_kernel does (same operand orders, same LayerNorm / normaliser arithmetic).  What
+// differs is where the weights come from: the three images are 512 KB (Wq 256 -> 128, FFN0 256 -> 256, FFN1 256 -> 128, bf16
+// hi / lo), far beyond LDS.  They are streamed, in the order the phases consume them, as 16 chunks of 32 KB through a
+// two-slot LDS ring that the waves of a persistent workgroup share: every wave runs the same phase on its own block, so one
+// barrier per chunk is the only synchronisation, and the L2 weight traffic is divided by the waves per workgroup (the tile
+// kernel re-reads all 512 KB per 32-token tile).  Chunk k + 1 is fetched into registers (eight 16-byte pieces per thread)
+// while chunk k is on the matrix core and written to the other slot before the barrier; the stream is the same for every
+// block, so the last chunk's fetch is the next block's first.  Each chunk is 48 MFMAs per wave (Q: four steps x four cout
+// blocks, FFN0: two steps x eight, FFN1: four steps x four).
+// Registers: FFN0's input [x ; msg] is 16 steps x 8 (hi / lo) and its accumulators 8 x 16 -- more than two waves per SIMD
+// hold -- so the kernel runs ONE wave per SIMD with the whole 512-register file (four waves per workgroup, one workgroup
+// per CU; tools/kres.py: 256 VGPRs + 210 AGPRs, no scratch) instead of chunking FFN0 by hidden channels.  x's operands
+// from the Q phase are kept for FFN0 (the same steps), the f32 features are re-read for the residual under FFN1, and
+// FFN1's operands are converted chunk by chunk.  The per-cloud matrix M (64 KB bf16 image) is read per wave from global
+// memory / L2 one step ahead of its MFMAs.
+// NH: heads (1, 2, 4), a template argument so the normaliser's head sums unroll.
+// one 16-channel step (ls) of a ring chunk against NB cout blocks, four blocks at a time: 8 ds_read_b128 feed 12 MFMAs; the
+// compiler barrier keeps the next group's reads from being hoisted over this group's (a chunk's reads all at once are
+// 128 registers)
+template <int NB>
+__device__ __forceinline__ void ap128_step(f32x16 (&acc)[NB], const bf16x8 *wb, int ls, const bf16x8 &bh, const bf16x8 &bl) {
+#pragma unroll
+  for (int c0 = 0; c0 < NB; c0 += 4) {
+    bf16x8 wh[4], wl[4];
+#pragma unroll
+    for (int cb = 0; cb < 4; cb++) {
+      wh[cb] = wb[((ls * NB + c0 + cb) * 2) * 64];
+      wl[cb] = wb[((ls * NB + c0 + cb) * 2 + 1) * 64];
+    }
+#pragma unroll
+    for (int cb = 0; cb < 4; cb++) acc[c0 + cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh[cb], bh, acc[c0 + cb], 0, 0, 0);
+#pragma unroll
+    for (int cb = 0; cb < 4; cb++) acc[c0 + cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh[cb], bl, acc[c0 + cb], 0, 0, 0);
+#pragma unroll
+    for (int cb = 0; cb < 4; cb++) acc[c0 + cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl[cb], bh, acc[c0 + cb], 0, 0, 0);
+    asm volatile("" ::: "memory");
+  }
+}
+constexpr int kAp128Waves = 4, kAp128ChunkU = 2048, kAp128Chunks = 16;   // chunk: 2048 16-byte units
+constexpr size_t kAp128Lds = (size_t)2 * kAp128ChunkU * 16 + (640 + 4 * 128 + kAp128Waves * 128) * sizeof(float);
+template <int NH>
+__global__ __launch_bounds__(64 * kAp128Waves) __attribute__((amdgpu_waves_per_eu(1, 1)))
+void attn_apply_stream128_kernel(AttnArgs a) {
+  constexpr int D = 128, ND = 4, SD = 8, GPH = 8 / NH;   // d_model, its 32-channel blocks, 16-channel steps; steps per head
+  constexpr int NPC = kAp128ChunkU / (64 * kAp128Waves);  // pieces per thread and chunk
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const pcr_attn_params &p = a.p;
+  f32x4 *s_ring = reinterpret_cast<f32x4 *>(smem);                    // [2 slots][2048 units]
+  // (the constants lie past 64 KB, beyond a ds_read's 16-bit offset field: with the offset a compile-time constant every
+  // read there got an address register of its own, hoisted out of the item loop -- 300 spilled registers.  Laundered, it
+  // is one base register plus immediate offsets.)
+  int coff = 2 * kAp128ChunkU * 4;
+  asm volatile("" : "+s"(coff));
+  float *s_c = smem + coff;                                           // bq | ln1 g | ln1 b | ln2 g | ln2 b : 5 x 128
+  f32x4 *s_p0 = reinterpret_cast<f32x4 *>(s_c + 640);                 // [128] {w0x, w0y, w0z, b0}
+  float *s_ks = s_c + 640 + 4 * 128;                                  // [waves][128] key sums of the wave's current cloud
+  const int tid = threadIdx.x, lane = tid & 63, j = lane & 31, h = lane >> 5;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  // the weight stream: chunks 0-3 Wq (steps 4k .. 4k + 3), 4-11 FFN0 (steps 2 (k - 4) ..), 12-15 FFN1 (steps 4 (k - 12) ..);
+  // buffer loads (one lane-offset register, the chunk offset scalar: 64-bit addresses per chunk and piece were hoisted out
+  // of the item loop and spilled)
+  const __amdgpu_buffer_rsrc_t rwq = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.wq), 0, 4 * kAp128ChunkU * 16, 0x00020000),
+                               rw0 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.wmlp0), 0, 8 * kAp128ChunkU * 16, 0x00020000),
+                               rw2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.wmlp2), 0, 4 * kAp128ChunkU * 16, 0x00020000);
+  f32x4 stg[NPC];
+  auto fetch = [&](int k) __attribute__((always_inline)) {
+    k %= kAp128Chunks;
+    const __amdgpu_buffer_rsrc_t r = k < 4 ? rwq : (k < 12 ? rw0 : rw2);
+    const int kk = k < 4 ? k : (k < 12 ? k - 4 : k - 12);
+#pragma unroll
+    for (int u = 0; u < NPC; u++)
+      stg[u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, tid * 16, (kk * kAp128ChunkU + u * 64 * kAp128Waves) * 16, 0));
+    asm volatile("" ::: "memory");   // (issued here, ahead of the chunk's MFMAs; they land at the commit)
+  };
+  auto commit = [&](int k) __attribute__((always_inline)) {
+    f32x4 *dst = s_ring + (k & 1) * kAp128ChunkU + tid;
+#pragma unroll
+    for (int u = 0; u < NPC; u++) dst[u * 64 * kAp128Waves] = stg[u];
+    __syncthreads();
+  };
+  for (int e = tid; e < D; e += 64 * kAp128Waves) {
+    s_c[e] = p.bq[e];
+    s_c[128 + e] = p.ln1_g[e];
+    s_c[256 + e] = p.ln1_b[e];
+    s_c[384 + e] = p.ln2_g[e];
+    s_c[512 + e] = p.ln2_b[e];
+    s_p0[e] = f32x4{p.pos0_w[3 * e], p.pos0_w[3 * e + 1], p.pos0_w[3 * e + 2], p.pos0_b[e]};
+  }
+  fetch(0);
+  commit(0);
+  const int nblk = p.Lq >> 5;
+  const long nitem = (long)p.B * nblk;
+  const float skf = (float)p.Sk;
+  float *ksw = s_ks + wave * 128;
+  auto cvec = [&](const float *base, int cb, int g) __attribute__((always_inline)) {
+    return *reinterpret_cast<const f32x4 *>(base + 32 * cb + 8 * g + 4 * h);
+  };
+  auto to_ops = [&](const f32x16 &acc, int G, bf16x8 &oh, bf16x8 &ol) __attribute__((always_inline)) {
+    float v[8];
+#pragma unroll
+    for (int e = 0; e < 8; e++) v[e] = acc[8 * G + e];
+    bf_split8(v, oh, ol, true);
+  };
+  // LayerNorm over the 128 channels of a token (two passes, eps inside the sqrt: tile_layernorm's arithmetic)
+  auto layernorm = [&](f32x16 (&v)[ND], const float *gam, const float *bet) __attribute__((always_inline)) {
+    float sm = 0.f;
+#pragma unroll
+    for (int cb = 0; cb < ND; cb++)
+#pragma unroll
+      for (int r = 0; r < 16; r++) sm += v[cb][r];
+    sm += __shfl_xor(sm, 32, 64);
+    const float mean = sm / (float)D;
+    float vr = 0.f;
+#pragma unroll
+    for (int cb = 0; cb < ND; cb++)
+#pragma unroll
+      for (int r = 0; r < 16; r++) {
+        const float dlt = v[cb][r] - mean;
+        vr += dlt * dlt;
+      }
+    vr += __shfl_xor(vr, 32, 64);
+    const float inv = 1.0f / sqrtf(vr / (float)D + 1e-5f);
+#pragma unroll
+    for (int cb = 0; cb < ND; cb++)
+#pragma unroll
+      for (int g = 0; g < 4; g++) {
+        const f32x4 gv = cvec(gam, cb, g), bv = cvec(bet, cb, g);
+#pragma unroll
+        for (int qq = 0; qq < 4; qq++) v[cb][4 * g + qq] = (v[cb][4 * g + qq] - mean) * inv * gv[qq] + bv[qq];
+      }
+  };
+  // rounds of kAp128Waves items (cloud, block), one per wave; every wave of the workgroup takes part in every round (the
+  // ring's barriers), a wave past the last item runs the last item again and stores nothing
+  for (long it0 = (long)blockIdx.x * kAp128Waves; it0 < nitem; it0 += (long)gridDim.x * kAp128Waves) {
+    const long item = it0 + wave;
+    const bool live = item < nitem;
+    const long it = live ? item : nitem - 1;
+    const long b = it / nblk;
+    const int blk = (int)(it - b * nblk);
+    const size_t bq_ = p.q_index ? (size_t)p.q_index[b] : (size_t)b;
+    const size_t kb_ = p.kv_index ? (size_t)p.kv_index[b] : (size_t)b;
+    const float *kvp = p.kv + kb_ * ((size_t)D * D + D);
+    const int t = blk * 32 + j;
+    const __amdgpu_buffer_rsrc_t rfeat = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<float *>(p.feat_q + bq_ * D * p.Lq), 0, D * p.Lq * 4, 0x00020000);
+    const int vo = (4 * h * p.Lq + t) * 4;
+    // lane (t, h): element e of its 64 feature values is channel 16 (e >> 3) + bf_kpos(h, e & 7) -- B-operand order of the
+    // eight x steps, and the order of the final accumulators (residual, store)
+    auto load_x = [&](float (&xf)[64]) __attribute__((always_inline)) {
+#pragma unroll
+      for (int e = 0; e < 64; e++) {
+        const int ch = 16 * (e >> 3) + bf_kpos(0, e & 7);   // + 4 h: in the lane offset
+        xf[e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rfeat, vo, ch * p.Lq * 4, 0));
+      }
+    };
+    ksw[lane] = kvp[(size_t)D * D + lane];
+    ksw[64 + lane] = kvp[(size_t)D * D + 64 + lane];
+    // B operands: steps 0-7 x (kept through FFN0, whose input starts with the same x), 8-15 the position hidden layer
+    // (Q) / the message (FFN0)
+    bf16x8 bh[16], bl[16];
+    {
+      float xf[64];
+      load_x(xf);
+      const float *xyz = p.xyz_q + (bq_ * p.Lq + t) * 3;
+      const float px = xyz[0], py = xyz[1], pz = xyz[2];
+#pragma unroll
+      for (int s2 = 0; s2 < SD; s2++) {
+        float hv[8];
+#pragma unroll
+        for (int e = 0; e < 8; e++) {
+          const f32x4 w = s_p0[16 * s2 + bf_kpos(0, e) + 4 * h];
+          const float v = w[0] * px + w[1] * py + w[2] * pz + w[3];
+          hv[e] = relu_i(v);
+        }
+        bf_split8(hv, bh[SD + s2], bl[SD + s2], true);
+      }
+#pragma unroll
+      for (int e = 0; e < 64; e++) asm volatile("" : "+v"(xf[e]));   // (the loads land here: see attn_kv_stream64_kernel)
+#pragma unroll
+      for (int s2 = 0; s2 < SD; s2++) {
+        float xv[8];
+#pragma unroll
+        for (int e = 0; e < 8; e++) xv[e] = xf[8 * s2 + e];
+        bf_split8(xv, bh[s2], bl[s2], true);
+      }
+    }
+    // ---- Q = elu(Wq [x ; h] + bq) + 1: chunks 0-3 (the bias seeds the accumulators, as in the tile kernel)
+    f32x16 q[ND];
+#pragma unroll
+    for (int cb = 0; cb < ND; cb++)
+#pragma unroll
+      for (int g = 0; g < 4; g++) {
+        const f32x4 bqv = cvec(s_c, cb, g);
+#pragma unroll
+        for (int qq = 0; qq < 4; qq++) q[cb][4 * g + qq] = bqv[qq];
+      }
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      fetch(k + 1);
+      const bf16x8 *wb = reinterpret_cast<const bf16x8 *>(s_ring + (k & 1) * kAp128ChunkU) + lane;
+#pragma unroll
+      for (int ls = 0; ls < 4; ls++) ap128_step<ND>(q, wb, ls, bh[4 * k + ls], bl[4 * k + ls]);
+      commit(k + 1);
+    }
+    // z[head][token] = Q_head . ksum_head: partial sums per 16-channel group gi = 2 cb + G, then per head (GPH groups), then
+    // over the partner lane.  (The key-sum strip was written before the ring's barriers.)
+    float zg[SD];
+#pragma unroll
+    for (int cb = 0; cb < ND; cb++)
+#pragma unroll
+      for (int g = 0; g < 4; g++) {
+        const f32x4 ksv = cvec(ksw, cb, g);
+        float zz = 0.f;
+#pragma unroll
+        for (int qq = 0; qq < 4; qq++) {
+          const float v = elu1(q[cb][4 * g + qq]);
+          q[cb][4 * g + qq] = v;
+          zz += v * ksv[qq];
+        }
+        if ((g & 1) == 0) zg[2 * cb + (g >> 1)] = zz;
+        else zg[2 * cb + (g >> 1)] += zz;
+      }
+    float zs[NH];
+#pragma unroll
+    for (int hd = 0; hd < NH; hd++) {
+      float z = zg[hd * GPH];
+#pragma unroll
+      for (int gi = 1; gi < GPH; gi++) z += zg[hd * GPH + gi];
+      z += __shfl_xor(z, 32, 64);
+      zs[hd] = (1.0f / (z + 1e-6f)) * skf;
+    }
+#pragma unroll
+    for (int cb = 0; cb < ND; cb++)
+#pragma unroll
+      for (int r = 0; r < 16; r++) q[cb][r] *= zs[(2 * cb + (r >> 3)) / GPH];
+    // ---- message = M Q' (M: the cloud's bf16 image [8 steps][4 cout blocks][hi, lo][64], read from global memory / L2
+    // one step ahead of its MFMAs), written over the hidden layer's operands
+    {
+      bf16x8 ch_[SD], cl_[SD];
+#pragma unroll
+      for (int cb = 0; cb < ND; cb++)
+#pragma unroll
+        for (int G = 0; G < 2; G++) to_ops(q[cb], G, ch_[2 * cb + G], cl_[2 * cb + G]);
+#pragma unroll
+      for (int cb = 0; cb < ND; cb++)
+#pragma unroll
+        for (int r = 0; r < 16; r++) q[cb][r] = 0.f;   // (q becomes the message accumulator)
+      const bf16x8 *mb = reinterpret_cast<const bf16x8 *>(kvp) + lane;
+      bf16x8 mh[2][ND], ml[2][ND];
+#pragma unroll
+      for (int cb = 0; cb < ND; cb++) {
+        mh[0][cb] = mb[(cb * 2) * 64];
+        ml[0][cb] = mb[(cb * 2 + 1) * 64];
+      }
+#pragma unroll
+      for (int s2 = 0; s2 < SD; s2++) {
+        const int c = s2 & 1;
+        if (s2 + 1 < SD) {
+#pragma unroll
+          for (int cb = 0; cb < ND; cb++) {
+            mh[c ^ 1][cb] = mb[(((s2 + 1) * ND + cb) * 2) * 64];
+            ml[c ^ 1][cb] = mb[(((s2 + 1) * ND + cb) * 2 + 1) * 64];
+          }
+        }
+        asm volatile("" ::: "memory");
+#pragma unroll
+        for (int cb = 0; cb < ND; cb++) q[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(mh[c][cb], ch_[s2], q[cb], 0, 0, 0);
+#pragma unroll
+        for (int cb = 0; cb < ND; cb++) q[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(mh[c][cb], cl_[s2], q[cb], 0, 0, 0);
+#pragma unroll
+        for (int cb = 0; cb < ND; cb++) q[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ml[c][cb], ch_[s2], q[cb], 0, 0, 0);
+      }
+    }
+    layernorm(q, s_c + 128, s_c + 256);
+    // ---- FFN0: relu(W0 [x ; msg]) (256 couts): chunks 4-11
+#pragma unroll
+    for (int cb = 0; cb < ND; cb++)
+#pragma unroll
+      for (int G = 0; G < 2; G++) to_ops(q[cb], G, bh[SD + 2 * cb + G], bl[SD + 2 * cb + G]);
+    f32x16 f[2 * ND];
+#pragma unroll
+    for (int cb = 0; cb < 2 * ND; cb++)
+#pragma unroll
+      for (int r = 0; r < 16; r++) f[cb][r] = 0.f;
+#pragma unroll
+    for (int k = 4; k < 12; k++) {
+      fetch(k + 1);
+      const bf16x8 *wb = reinterpret_cast<const bf16x8 *>(s_ring + (k & 1) * kAp128ChunkU) + lane;
+#pragma unroll
+      for (int ls = 0; ls < 2; ls++) ap128_step<2 * ND>(f, wb, ls, bh[2 * (k - 4) + ls], bl[2 * (k - 4) + ls]);
+      commit(k + 1);
+    }
+    // the residual's features, re-read (L2) under FFN1
+    float xf[64];
+    load_x(xf);
+    // ---- FFN1 (128 couts): chunks 12-15 (the last one's fetch is the next block's chunk 0); chunk k takes the hidden
+    // channels of FFN0 blocks 2 (k - 12), 2 (k - 12) + 1, converted when it starts
+    f32x16 o[ND];
+#pragma unroll
+    for (int cb = 0; cb < ND; cb++)
+#pragma unroll
+      for (int r = 0; r < 16; r++) o[cb][r] = 0.f;
+#pragma unroll
+    for (int k = 12; k < 16; k++) {
+      fetch(k + 1);
+      bf16x8 oh[4], ol[4];
+#pragma unroll
+      for (int i = 0; i < 2; i++) {
+        f32x16 &fc = f[2 * (k - 12) + i];
+#pragma unroll
+        for (int r = 0; r < 16; r++) fc[r] = relu_i(fc[r]);
+#pragma unroll
+        for (int G = 0; G < 2; G++) to_ops(fc, G, oh[2 * i + G], ol[2 * i + G]);
+      }
+      const bf16x8 *wb = reinterpret_cast<const bf16x8 *>(s_ring + (k & 1) * kAp128ChunkU) + lane;
+#pragma unroll
+      for (int ls = 0; ls < 4; ls++) ap128_step<ND>(o, wb, ls, oh[ls], ol[ls]);
+      commit(k + 1);
+    }
+    layernorm(o, s_c + 384, s_c + 512);
+#pragma unroll
+    for (int cb = 0; cb < ND; cb++)
+#pragma unroll
+      for (int r = 0; r < 16; r++) o[cb][r] += xf[16 * cb + r];
+    if (live) {
+      const __amdgpu_buffer_rsrc_t rout =
+          __builtin_amdgcn_make_buffer_rsrc(p.out + (size_t)b * D * p.Lq, 0, D * p.Lq * 4, 0x00020000);
+#pragma unroll
+      for (int e = 0; e < 16 * ND; e++) {
+        const int ch = 16 * (e >> 3) + bf_kpos(0, e & 7);
+        const float v = o[e >> 4][e & 15];   // (a copy: __builtin_bit_cast of a vector ELEMENT reads element 0)
+        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rout, vo, ch * p.Lq * 4, 0);
+      }
+    }
+  }
+}
 #endif
 
 }  // namespace
@@ -1751,6 +2090,31 @@ static int attn_apply_launch(const pcr_attn_params *pp, pcr_stream_t stream) {
   const size_t aps_lds = (size_t)((aps_c1s + (p.q_pos ? 2 * aps_nd : 0)) * aps_nd * 128 + (aps_c1s + 2 * aps_nd) * aps_nd * 256 +
                                   aps_nd * (p.cout >> 5) * 512) * 16 +
                          (size_t)(448 + 256 + 64 * kApsWaves) * sizeof(float);
+  static const int no_s128 = pcr_tune_int("PCR_ATTN_NO_STREAM128");   // diagnostics: these shapes back to the tile kernel
+  if (p.d == 128 && p.c1 == 128 && p.cout == 128 && !p.cfinal && p.q_pos && p.residual && (p.Lq & 31) == 0 && p.Lq >= 256 &&
+      (p.nhead == 1 || p.nhead == 2 || p.nhead == 4) && !no_s128) {
+    // SA3's self-attention (d_model 128): the wave-autonomous form with the weights streamed through an LDS ring
+    // (shape-only choice); persistent, one workgroup of four waves per CU.  Query sets of >= 256 tokens only, the kv
+    // kernel's split-projection rule: at Lq = 32 (the Point-Transformer @128) its other rounding took one case of
+    // tests/test_gpu_precision.py's margin sweep from under 5e-5 to 5.4e-5
+    const long nitem = (long)p.B * (p.Lq >> 5);
+    const long nwg = (nitem + kAp128Waves - 1) / kAp128Waves;
+    static const int ncu = [] {
+      hipDeviceProp_t pr;
+      int dev = 0;
+      if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&pr, dev) != hipSuccess) return 256;
+      return pr.multiProcessorCount > 0 ? pr.multiProcessorCount : 256;
+    }();
+    const dim3 gg((unsigned)(nwg < ncu ? nwg : ncu)), bb(64 * kAp128Waves);
+    static bool ok128 = allow_big_lds(attn_apply_stream128_kernel<1>) && allow_big_lds(attn_apply_stream128_kernel<2>) &&
+                        allow_big_lds(attn_apply_stream128_kernel<4>);
+    (void)ok128;
+    if (p.nhead == 1) hipLaunchKernelGGL((attn_apply_stream128_kernel<1>), gg, bb, kAp128Lds, st, a);
+    else if (p.nhead == 2) hipLaunchKernelGGL((attn_apply_stream128_kernel<2>), gg, bb, kAp128Lds, st, a);
+    else hipLaunchKernelGGL((attn_apply_stream128_kernel<4>), gg, bb, kAp128Lds, st, a);
+    PCR_CHECK_LAUNCH();
+    return PCR_OK;
+  }
   if (p.d == 32 && p.c1 == 32 && p.cout == 32 && !p.cfinal && (p.Lq & 31) == 0 && (p.nhead == 1 || p.nhead == 2)) {
     // the SA1 self-attention (d_model 32): the same kernel with one 32-channel block
     const long nitem = (long)p.B * (p.Lq >> 5);

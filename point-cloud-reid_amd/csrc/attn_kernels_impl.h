@@ -19,6 +19,7 @@ constexpr int kAPrec = PCR_ATTN_PREC;
 struct AttnArgs {
   pcr_attn_params p;
   int dbg;   // diagnostics (trace builds): 256 = stamp the shader clock
+  int wpc;   // attn_kv_stream128_kernel: waves per cloud (1, 2, 4), a function of Sk only
 };
 
 // shader-clock stamps of the wave-autonomous kv kernel (trace builds only: -DPCR_SA_TRACE_BUILD, PCR_ATTN_TRACE=<file>);
@@ -1581,9 +1582,13 @@ void attn_apply_stream64_kernel(AttnArgs a) {
 // NH: heads (1, 2, 4), a template argument so the normaliser's head sums unroll.
 // one 16-channel step (ls) of a ring chunk against NB cout blocks, four blocks at a time: 8 ds_read_b128 feed 12 MFMAs; the
 // compiler barrier keeps the next group's reads from being hoisted over this group's (a chunk's reads all at once are
-// 128 registers)
-template <int NB>
+// 128 registers).  TRANS: the activations are the A operand (Y^T = X^T W^T: lane (cout, h) holds tokens 8 g + 4 h + q,
+// attn_kv_stream128_kernel); the weight image serves both roles unchanged.
+template <int NB, bool TRANS = false>
 __device__ __forceinline__ void ap128_step(f32x16 (&acc)[NB], const bf16x8 *wb, int ls, const bf16x8 &bh, const bf16x8 &bl) {
+  auto mm = [](const bf16x8 &w, const bf16x8 &x, const f32x16 &c) __attribute__((always_inline)) {
+    return TRANS ? __builtin_amdgcn_mfma_f32_32x32x16_bf16(x, w, c, 0, 0, 0) : __builtin_amdgcn_mfma_f32_32x32x16_bf16(w, x, c, 0, 0, 0);
+  };
 #pragma unroll
   for (int c0 = 0; c0 < NB; c0 += 4) {
     bf16x8 wh[4], wl[4];
@@ -1593,21 +1598,35 @@ __device__ __forceinline__ void ap128_step(f32x16 (&acc)[NB], const bf16x8 *wb, 
       wl[cb] = wb[((ls * NB + c0 + cb) * 2 + 1) * 64];
     }
 #pragma unroll
-    for (int cb = 0; cb < 4; cb++) acc[c0 + cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh[cb], bh, acc[c0 + cb], 0, 0, 0);
+    for (int cb = 0; cb < 4; cb++) acc[c0 + cb] = mm(wh[cb], bh, acc[c0 + cb]);
 #pragma unroll
-    for (int cb = 0; cb < 4; cb++) acc[c0 + cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh[cb], bl, acc[c0 + cb], 0, 0, 0);
+    for (int cb = 0; cb < 4; cb++) acc[c0 + cb] = mm(wh[cb], bl, acc[c0 + cb]);
 #pragma unroll
-    for (int cb = 0; cb < 4; cb++) acc[c0 + cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl[cb], bh, acc[c0 + cb], 0, 0, 0);
+    for (int cb = 0; cb < 4; cb++) acc[c0 + cb] = mm(wl[cb], bh, acc[c0 + cb]);
     asm volatile("" ::: "memory");
   }
 }
 constexpr int kAp128Waves = 4, kAp128ChunkU = 2048, kAp128Chunks = 16;   // chunk: 2048 16-byte units
+constexpr int kAp128Npc = kAp128ChunkU / (64 * kAp128Waves);             // 16-byte pieces per thread and chunk
+// the weight ring of the d = 128 stream kernels: chunk kk of the image behind r is fetched into registers (buffer loads: one
+// lane-offset register, the chunk offset scalar) ahead of its use, then committed to slot k & 1 with the one barrier per chunk
+__device__ __forceinline__ void ring128_fetch(f32x4 (&stg)[kAp128Npc], __amdgpu_buffer_rsrc_t r, int kk, int tid) {
+#pragma unroll
+  for (int u = 0; u < kAp128Npc; u++)
+    stg[u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, tid * 16, (kk * kAp128ChunkU + u * 64 * kAp128Waves) * 16, 0));
+  asm volatile("" ::: "memory");   // (issued here, ahead of the chunk's MFMAs; they land at the commit)
+}
+__device__ __forceinline__ void ring128_commit(f32x4 *s_ring, const f32x4 (&stg)[kAp128Npc], int k, int tid) {
+  f32x4 *dst = s_ring + (k & 1) * kAp128ChunkU + tid;
+#pragma unroll
+  for (int u = 0; u < kAp128Npc; u++) dst[u * 64 * kAp128Waves] = stg[u];
+  __syncthreads();
+}
 constexpr size_t kAp128Lds = (size_t)2 * kAp128ChunkU * 16 + (640 + 4 * 128 + kAp128Waves * 128) * sizeof(float);
 template <int NH>
 __global__ __launch_bounds__(64 * kAp128Waves) __attribute__((amdgpu_waves_per_eu(1, 1)))
 void attn_apply_stream128_kernel(AttnArgs a) {
   constexpr int D = 128, ND = 4, SD = 8, GPH = 8 / NH;   // d_model, its 32-channel blocks, 16-channel steps; steps per head
-  constexpr int NPC = kAp128ChunkU / (64 * kAp128Waves);  // pieces per thread and chunk
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const pcr_attn_params &p = a.p;
   f32x4 *s_ring = reinterpret_cast<f32x4 *>(smem);                    // [2 slots][2048 units]
@@ -1622,27 +1641,16 @@ void attn_apply_stream128_kernel(AttnArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, j = lane & 31, h = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   // the weight stream: chunks 0-3 Wq (steps 4k .. 4k + 3), 4-11 FFN0 (steps 2 (k - 4) ..), 12-15 FFN1 (steps 4 (k - 12) ..);
-  // buffer loads (one lane-offset register, the chunk offset scalar: 64-bit addresses per chunk and piece were hoisted out
-  // of the item loop and spilled)
+  // buffer loads (64-bit addresses per chunk and piece were hoisted out of the item loop and spilled)
   const __amdgpu_buffer_rsrc_t rwq = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.wq), 0, 4 * kAp128ChunkU * 16, 0x00020000),
                                rw0 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.wmlp0), 0, 8 * kAp128ChunkU * 16, 0x00020000),
                                rw2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.wmlp2), 0, 4 * kAp128ChunkU * 16, 0x00020000);
-  f32x4 stg[NPC];
+  f32x4 stg[kAp128Npc];
   auto fetch = [&](int k) __attribute__((always_inline)) {
     k %= kAp128Chunks;
-    const __amdgpu_buffer_rsrc_t r = k < 4 ? rwq : (k < 12 ? rw0 : rw2);
-    const int kk = k < 4 ? k : (k < 12 ? k - 4 : k - 12);
-#pragma unroll
-    for (int u = 0; u < NPC; u++)
-      stg[u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, tid * 16, (kk * kAp128ChunkU + u * 64 * kAp128Waves) * 16, 0));
-    asm volatile("" ::: "memory");   // (issued here, ahead of the chunk's MFMAs; they land at the commit)
+    ring128_fetch(stg, k < 4 ? rwq : (k < 12 ? rw0 : rw2), k < 4 ? k : (k < 12 ? k - 4 : k - 12), tid);
   };
-  auto commit = [&](int k) __attribute__((always_inline)) {
-    f32x4 *dst = s_ring + (k & 1) * kAp128ChunkU + tid;
-#pragma unroll
-    for (int u = 0; u < NPC; u++) dst[u * 64 * kAp128Waves] = stg[u];
-    __syncthreads();
-  };
+  auto commit = [&](int k) __attribute__((always_inline)) { ring128_commit(s_ring, stg, k, tid); };
   for (int e = tid; e < D; e += 64 * kAp128Waves) {
     s_c[e] = p.bq[e];
     s_c[128 + e] = p.ln1_g[e];
@@ -1899,6 +1907,247 @@ void attn_apply_stream128_kernel(AttnArgs a) {
     }
   }
 }
+
+// ---- the kv half at d = c2 = 128 (SA3's self-attention, key sets of >= 256 tokens): attn_kv_stream64_kernel's form with
+// attn_apply_stream128_kernel's weight ring.  A wave owns a 32-token block from the feature load to its KV MFMAs: lane
+// (t, h) holds the 128 feature and 128 position-hidden channels of token t in the K order of the bf16 image (16 steps,
+// 128 registers as hi / lo operands), the fused K / V projection runs TRANSPOSED (Y^T = [x ; h]^T W^T, all eight cout blocks
+// at once: 128 accumulator registers) so that after elu + 1 / the 1 / Sk scale its accumulators are the operands of
+// KV += K V^T as they stand (f32, same-head 32 x 32 tiles only, accumulated transposed as in the ONEW form: lane = dd,
+// register r <-> v).  The 256 KB image wkv_bf streams as 8 chunks of 32 KB (two steps x eight cout blocks, 48 MFMAs per
+// wave) through the two-slot ring; the stream is the same for every block, so the last chunk's fetch is the next block's
+// first.  The next block's features are requested right after the last chunk's barrier (vector loads retire in order:
+// before it, the ring's wait would sit out their HBM round trip) and land under the KV MFMAs.
+// A cloud takes wpc = 1 / 2 / 4 waves of a workgroup (attn_kv128_wpc: Sk only); with wpc > 1 its waves add their KV tiles and
+// key sums through LDS in wave order, then every wave holds the same sums and folds its share of the output blocks.  The
+// merge fold M[o][dd] = sum_{v in head(dd)} Wm[o][v] KV[dd][v] takes the KV tile registers as the A operand and the f32
+// merge rows from L2 as B (lane (o, h) then holds the 16-byte units of the bf16 image of M), then the key sums follow:
+// the image attn_kv_fold_mfma writes in this unit.  One wave per SIMD (four per workgroup, one workgroup per CU).
+// NH: heads (2, 4); nhead = 1 needs 16 KV tiles (256 registers) and stays on the tile kernel.
+__host__ __device__ constexpr int attn_kv128_wpc(int nblk) { return nblk >= 32 ? 4 : (nblk >= 16 ? 2 : 1); }
+constexpr size_t kKv128Lds0 = (size_t)2 * kAp128ChunkU * 16 + 128 * 16 + 256 * 4;   // ring + position MLP + biases
+template <int NH>
+__global__ __launch_bounds__(64 * kAp128Waves) __attribute__((amdgpu_waves_per_eu(1, 1)))
+void attn_kv_stream128_kernel(AttnArgs a) {
+  constexpr int D = 128, SD = 8, TPH = 4 / NH, NKV = NH * TPH * TPH;   // steps of x / of h; 32-blocks per head; KV tiles
+  constexpr int KVU = NKV * 16 + 4;                                     // reduction floats per lane: KV tiles + key sums
+  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const pcr_attn_params &p = a.p;
+  f32x4 *s_ring = reinterpret_cast<f32x4 *>(smem);                    // [2 slots][2048 units]
+  int coff = 2 * kAp128ChunkU * 4;                                     // (past 64 KB: laundered, see the apply kernel)
+  asm volatile("" : "+s"(coff));
+  f32x4 *s_p0 = reinterpret_cast<f32x4 *>(smem + coff);                // [128] {w0x, w0y, w0z, b0}
+  float *s_bkv = smem + coff + 4 * D;                                  // [256] K / V biases
+  float *s_red = s_bkv + 2 * D;                                        // [clouds per round][KVU][64] (wpc > 1)
+  const int tid = threadIdx.x, lane = tid & 63, j = lane & 31, h = lane >> 5;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.wkv_bf), 0, 8 * kAp128ChunkU * 16, 0x00020000);
+  f32x4 stg[kAp128Npc];
+  auto fetch = [&](int k) __attribute__((always_inline)) { ring128_fetch(stg, rw, k & 7, tid); };
+  auto commit = [&](int k) __attribute__((always_inline)) { ring128_commit(s_ring, stg, k, tid); };
+  for (int e = tid; e < D; e += 64 * kAp128Waves) s_p0[e] = f32x4{p.pos0_w[3 * e], p.pos0_w[3 * e + 1], p.pos0_w[3 * e + 2], p.pos0_b[e]};
+  for (int e = tid; e < 2 * D; e += 64 * kAp128Waves) s_bkv[e] = p.bkv[e];
+  fetch(0);
+  commit(0);
+  const int Sk = p.Sk, nblk = Sk >> 5;
+  const int wpc = a.wpc, cpg = kAp128Waves / wpc;
+  const int cslot = wave / wpc, wsub = wave - cslot * wpc;
+  const int nper = (nblk + wpc - 1) / wpc;                            // block rounds per cloud: the same for every wave
+  const long cstep = (long)gridDim.x * cpg;
+  const float inv_sk = 1.0f / (float)Sk;
+  // features (element e: channel 16 (e >> 3) + bf_kpos(h, e & 7)) and position of token t of block blk of cloud b
+  float xf[64], pxyz[3];
+  auto issue = [&](long bq, int blk) __attribute__((always_inline)) {
+    const __amdgpu_buffer_rsrc_t rfeat =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.feat_k + (size_t)bq * D * Sk), 0, D * Sk * 4, 0x00020000);
+    const int t = blk * 32 + j, vo = (4 * h * Sk + t) * 4;
+#pragma unroll
+    for (int e = 0; e < 64; e++) {
+      const int ch = 16 * (e >> 3) + bf_kpos(0, e & 7);   // + 4 h: in the lane offset
+      xf[e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rfeat, vo, ch * Sk * 4, 0));
+    }
+    const __amdgpu_buffer_rsrc_t rxyz =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.xyz_k + (size_t)bq * Sk * 3), 0, Sk * 12, 0x00020000);
+#pragma unroll
+    for (int c = 0; c < 3; c++) pxyz[c] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rxyz, t * 12, c * 4, 0));
+    asm volatile("" ::: "memory");
+  };
+  if ((long)blockIdx.x * cpg + cslot < p.B && wsub < nblk) issue((long)blockIdx.x * cpg + cslot, wsub);
+  // rounds of cpg clouds per workgroup; every wave takes part in every ring barrier (a wave without a block in a round
+  // fetches and commits and skips the MFMAs)
+  for (long c0 = (long)blockIdx.x * cpg; c0 < p.B; c0 += cstep) {
+    const long b = c0 + cslot;
+    const bool live = b < p.B;
+    f32x16 kv[NKV];
+#pragma unroll
+    for (int i = 0; i < NKV; i++)
+#pragma unroll
+      for (int r = 0; r < 16; r++) kv[i][r] = 0.f;
+    float ks[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int it = 0; it < nper; it++) {
+      const int blk = wsub + it * wpc;
+      const bool has = live && blk < nblk;
+      const bool last = it + 1 == nper;
+      const long bn = last ? b + cstep : b;                           // this wave's next block
+      const int blkn = last ? wsub : blk + wpc;
+      const bool hasn = bn < p.B && blkn < nblk;
+      // A operands: steps 0-7 the features, converted here; steps 8-15 the position-hidden channels 16 s2 + bf_kpos(h, .),
+      // computed by the chunk that takes them (all sixteen steps at once are 128 registers: spilled)
+      bf16x8 bh[SD], bl[SD];
+      if (has) {
+#pragma unroll
+        for (int s2 = 0; s2 < SD; s2++) {
+          float xv[8];
+#pragma unroll
+          for (int e = 0; e < 8; e++) xv[e] = xf[8 * s2 + e];
+          bf_split8(xv, bh[s2], bl[s2], true);
+        }
+      }
+      f32x16 acc[8];
+#pragma unroll
+      for (int cb = 0; cb < 8; cb++)
+#pragma unroll
+        for (int r = 0; r < 16; r++) acc[cb][r] = 0.f;   // (the bias joins in the epilogue)
+#pragma unroll
+      for (int k = 0; k < 8; k++) {
+        fetch(k + 1);
+        if (has) {
+          const bf16x8 *wb = reinterpret_cast<const bf16x8 *>(s_ring + (k & 1) * kAp128ChunkU) + lane;
+#pragma unroll
+          for (int ls = 0; ls < 2; ls++) {
+            if (k < 4) {
+              ap128_step<8, true>(acc, wb, ls, bh[2 * k + ls], bl[2 * k + ls]);
+            } else {
+              const int s2 = 2 * k + ls - SD;
+              float hv[8];
+#pragma unroll
+              for (int e = 0; e < 8; e++) {
+                const f32x4 w = s_p0[16 * s2 + bf_kpos(0, e) + 4 * h];
+                const float v = w[0] * pxyz[0] + w[1] * pxyz[1] + w[2] * pxyz[2] + w[3];
+                hv[e] = relu_i(v);
+              }
+              bf16x8 hh, hl;
+              bf_split8(hv, hh, hl, true);
+              ap128_step<8, true>(acc, wb, ls, hh, hl);
+            }
+          }
+        }
+        commit(k + 1);
+      }
+      if (hasn) issue(bn, blkn);
+      else {
+#pragma unroll
+        for (int e = 0; e < 64; e++) xf[e] = 0.f;   // (defined on both paths: not live through the chunks)
+        pxyz[0] = pxyz[1] = pxyz[2] = 0.f;
+      }
+      if (has) {
+        float bias[8];   // (from LDS here: eight registers through the chunks were what spilled)
+#pragma unroll
+        for (int cb = 0; cb < 8; cb++) bias[cb] = s_bkv[cb * 32 + j];
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+#pragma unroll
+          for (int cb = 0; cb < 4; cb++) {
+            acc[cb][r] = elu1(acc[cb][r] + bias[cb]);
+            ks[cb] += acc[cb][r];
+            acc[4 + cb][r] = (acc[4 + cb][r] + bias[4 + cb]) * inv_sk;
+          }
+        }
+        // KV^T tile (v block jb, dd block ib): lane (dd, h), register r <-> v = 32 jb + 8 g + 4 h + q
+#pragma unroll
+        for (int i = 0; i < NKV; i++) {
+          const int hd = i / (TPH * TPH), ib = hd * TPH + (i % (TPH * TPH)) / TPH, jb = hd * TPH + i % TPH;
+#pragma unroll
+          for (int r = 0; r < 16; r++) kv[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(acc[4 + jb][r], acc[ib][r], kv[i], 0, 0, 0);
+        }
+      }
+    }
+#pragma unroll
+    for (int cb = 0; cb < 4; cb++) ks[cb] += __shfl_xor(ks[cb], 32, 64);
+    if (wpc > 1) {
+      // the cloud's waves add their tiles and key sums in wave order (lane-major: conflict-free, no layout change), then
+      // all of them read the sums back
+      int ln = lane;
+      asm volatile("" : "+v"(ln));   // (the lane offsets of the cold phases are computed where used: hoisted, they spilled)
+      float *red = s_red + (size_t)cslot * KVU * 64 + ln;
+      for (int round = 0; round < wpc; round++) {
+        if (wsub == round) {
+#pragma unroll
+          for (int i = 0; i < NKV; i++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+              float *dst = red + (i * 16 + r) * 64;
+              *dst = round == 0 ? kv[i][r] : *dst + kv[i][r];
+            }
+#pragma unroll
+          for (int cb = 0; cb < 4; cb++) {
+            float *dst = red + (NKV * 16 + cb) * 64;
+            *dst = round == 0 ? ks[cb] : *dst + ks[cb];
+          }
+        }
+        __syncthreads();
+      }
+#pragma unroll
+      for (int i = 0; i < NKV; i++)
+#pragma unroll
+        for (int r = 0; r < 16; r++) kv[i][r] = red[(i * 16 + r) * 64];
+#pragma unroll
+      for (int cb = 0; cb < 4; cb++) ks[cb] = red[(NKV * 16 + cb) * 64];
+      // (the next round writes these areas after at least eight ring barriers)
+    }
+    if (live) {
+      // (buffer loads / stores throughout: 64-bit lane addresses were what spilled)
+      int ln = lane;
+      asm volatile("" : "+v"(ln));
+      const int j = ln & 31, h = ln >> 5;
+      const __amdgpu_buffer_rsrc_t rkv =
+          __builtin_amdgcn_make_buffer_rsrc(p.kv + (size_t)b * ((size_t)D * D + D), 0, (D * D + D) * 4, 0x00020000);
+      const __amdgpu_buffer_rsrc_t rwm = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.wmerge), 0, D * D * 4, 0x00020000);
+      for (int ob = wsub; ob < 4; ob += wpc) {
+        const int wrow = ((ob * 32 + j) * D + 4 * h) * 4;
+#pragma unroll
+        for (int hd = 0; hd < NH; hd++) {
+          f32x4 w[TPH][4];   // Wm[o][32 jb + 8 g + 4 h + q] of the head's v blocks
+#pragma unroll
+          for (int jj = 0; jj < TPH; jj++)
+#pragma unroll
+            for (int g = 0; g < 4; g++)
+              w[jj][g] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rwm, wrow, ((hd * TPH + jj) * 32 + 8 * g) * 4, 0));
+#pragma unroll
+          for (int dl = 0; dl < TPH; dl++) {
+            const int db = hd * TPH + dl;
+            f32x16 m;
+#pragma unroll
+            for (int r = 0; r < 16; r++) m[r] = 0.f;
+#pragma unroll
+            for (int jj = 0; jj < TPH; jj++) {
+              const int i = hd * TPH * TPH + dl * TPH + jj;
+#pragma unroll
+              for (int r = 0; r < 16; r++) m = __builtin_amdgcn_mfma_f32_32x32x2f32(kv[i][r], w[jj][r >> 2][r & 3], m, 0, 0, 0);
+            }
+#pragma unroll
+            for (int G = 0; G < 2; G++) {
+              float v[8];
+#pragma unroll
+              for (int e = 0; e < 8; e++) v[e] = m[8 * G + e];
+              bf16x8 hi, lo;
+              bf_split8(v, hi, lo, true);
+              const int unit = (((db * 2 + G) * (D >> 5) + ob) * 2) * 64 + h * 32 + j;
+              __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, hi), rkv, unit * 16, 0, 0);
+              __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, lo), rkv, (unit + 64) * 16, 0, 0);
+            }
+          }
+        }
+      }
+      if (wsub == 0 && h == 0) {
+#pragma unroll
+        for (int cb = 0; cb < 4; cb++)
+          __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, ks[cb]), rkv, (D * D + cb * 32 + j) * 4, 0, 0);
+      }
+    }
+  }
+}
 #endif
 
 }  // namespace
@@ -1943,6 +2192,7 @@ static int attn_kv_narrow(const pcr_attn_params *pp, pcr_stream_t stream) {
   AttnArgs a;
   a.p = *pp;
   a.dbg = 0;
+  a.wpc = 0;
   const int d = pp->d;
   if (pp->c2 < pp->d) return PCR_ERR_INVALID;   // the in-place K/V projection needs 2d <= c2 + d rows
   const int tb = d <= 64 ? 2 : 1, RP = 32 * tb + 1;
@@ -2040,6 +2290,33 @@ static int attn_kv_narrow(const pcr_attn_params *pp, pcr_stream_t stream) {
     PCR_CHECK_LAUNCH();
     return PCR_OK;
   }
+  static const int no_kv128 = pcr_tune_int("PCR_ATTN_NO_KV128");   // diagnostics: these shapes back to the tile kernel
+  if (ns == 1 && d == 128 && pp->c2 == 128 && pp->wkv_bf && (pp->Sk & 31) == 0 && pp->Sk >= 256 &&
+      (pp->nhead == 2 || pp->nhead == 4) && !no_kv128) {
+    // SA3's self-attention (d_model 128): the wave-autonomous form with the weights streamed through an LDS ring
+    // (shape-only choice, the split-projection rule below: key sets of >= 256 tokens); persistent, one workgroup of four
+    // waves per CU
+    pcr_note_arith(PCR_PREC_BF16X3);   // (the projection; the KV accumulation and the fold are f32)
+    a.wpc = attn_kv128_wpc(pp->Sk >> 5);
+    static const int wpc_t = pcr_tune_int("PCR_ATTN_KV128_WPC");   // diagnostics: 1 / 2 / 4 waves per cloud
+    if (wpc_t == 1 || wpc_t == 2 || wpc_t == 4) a.wpc = wpc_t;
+    const int cpg = kAp128Waves / a.wpc;
+    const size_t lds_s = kKv128Lds0 + (a.wpc > 1 ? (size_t)cpg * (16 * (16 / pp->nhead) + 4) * 64 * sizeof(float) : 0);
+    const long nwg = ((long)pp->B + cpg - 1) / cpg;
+    static const int ncu = [] {
+      hipDeviceProp_t pr;
+      int dev = 0;
+      if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&pr, dev) != hipSuccess) return 256;
+      return pr.multiProcessorCount > 0 ? pr.multiProcessorCount : 256;
+    }();
+    const dim3 gg((unsigned)(nwg < ncu ? nwg : ncu)), bb(64 * kAp128Waves);
+    static bool ok128 = allow_big_lds(attn_kv_stream128_kernel<2>) && allow_big_lds(attn_kv_stream128_kernel<4>);
+    (void)ok128;
+    if (pp->nhead == 2) hipLaunchKernelGGL((attn_kv_stream128_kernel<2>), gg, bb, lds_s, st, a);
+    else hipLaunchKernelGGL((attn_kv_stream128_kernel<4>), gg, bb, lds_s, st, a);
+    PCR_CHECK_LAUNCH();
+    return PCR_OK;
+  }
 #endif
   pcr_note_arith(PCR_PREC_F32);   // the tile kernel projects in f32 in both units (only the form of M differs)
   if (d == 32) hipLaunchKernelGGL((attn_kv_kernel<2, 1, 2, 1>), g, blk, lds, st, a);        // 2d = 64: two cout blocks
@@ -2072,6 +2349,7 @@ static int attn_apply_launch(const pcr_attn_params *pp, pcr_stream_t stream) {
   AttnArgs a;
   a.p = p;
   a.dbg = 0;
+  a.wpc = 0;
   // (round 6, measured and dropped: 64-token tiles for d = 128 -- half the weight traffic from L2, half the waves per CU:
   // pt1024's attn_apply[d=128] 0.455 -> 0.518 ms, profiles/r06_inproc_ab.txt)
   const int tb = p.d <= 32 ? 4 : (p.d <= 64 ? 2 : 1), T = 32 * tb, RP = T + 1;
@@ -2262,6 +2540,7 @@ PCR_EXPORT int pcr_attn_kv_f32(const pcr_attn_params *pp, pcr_stream_t stream) {
     AttnArgs a;
     a.p = *pp;
     a.dbg = 0;
+    a.wpc = 0;
     if (!pp->wkv_wide || !pp->bkv_wide || !pp->wmerge_packed || pp->B > 65535) return PCR_ERR_INVALID;
     pcr_note_arith(PCR_PREC_F32);
     const int dh = d / pp->nhead;

@@ -2201,9 +2201,6 @@ static int attn_kv_narrow(const pcr_attn_params *pp, pcr_stream_t stream) {
   if (lds2 > lds) lds = lds2;
   lds = (lds + kThreads) * sizeof(float);
   if (lds > (size_t)kMaxDynLds) return PCR_ERR_INVALID;
-  static bool ok = allow_big_lds(attn_kv_kernel<2, 1, 2, 1>) && allow_big_lds(attn_kv_kernel_o3<2, 1, 1, 1>) &&
-                   allow_big_lds(attn_kv_kernel_o3<1, 2, 1, 4>) && allow_big_lds(attn_kv_kernel<1, 2, 0, 4>);
-  (void)ok;
   const int ntile = (pp->Sk + 32 * tb - 1) / (32 * tb);
   int ns = pp->kv_splits > 1 ? pp->kv_splits : 1;
   if (ns > 1 && (!pp->kv_part || ns > 64)) return PCR_ERR_INVALID;
@@ -2219,11 +2216,6 @@ static int attn_kv_narrow(const pcr_attn_params *pp, pcr_stream_t stream) {
     const bool bf = bfk;
     const bool wide = pp->c2 == 128;
     pcr_note_arith(bf ? PCR_PREC_BF16X3 : PCR_PREC_F32);   // (the projection; the KV accumulation and the fold are f32)
-    static bool oks = allow_big_lds(attn_kv_stream64_kernel<true, false>) && allow_big_lds(attn_kv_stream64_kernel<false, false>) &&
-                      allow_big_lds(attn_kv_stream64_kernel<true, kBfUnit>) && allow_big_lds(attn_kv_stream64_kernel<false, kBfUnit>) &&
-                      allow_big_lds(attn_kv_stream64_kernel<true, kBfUnit, kBfUnit ? 8 : 4>) &&
-                      allow_big_lds(attn_kv_stream64_kernel<false, kBfUnit, kBfUnit ? 8 : 4>);
-    (void)oks;
     const int nblk = pp->Sk >> 5;
     const int minw = wide ? 4 : 2;
     int wpc2 = 1;
@@ -2237,40 +2229,31 @@ static int attn_kv_narrow(const pcr_attn_params *pp, pcr_stream_t stream) {
     const size_t wu = bf ? (size_t)((wide ? 8 : 4) + 4) * 512 : 4096;
     const size_t lds_s = (wu * 4 + 256 + 128 + 64 * 65 + (onew ? (size_t)0 : (size_t)cpg * (64 * 65 + 64))) * sizeof(float);
     const long rounds = ((long)pp->B + cpg - 1) / cpg;
-    static const int ncu = [] {
-      hipDeviceProp_t pr;
-      int dev = 0;
-      if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&pr, dev) != hipSuccess) return 256;
-      return pr.multiProcessorCount > 0 ? pr.multiProcessorCount : 256;
-    }();
-    const int gs = (int)(rounds < ncu ? rounds : ncu);        // persistent: one workgroup per CU
+    const int gs = (int)(rounds < pcr_cu_count() ? rounds : pcr_cu_count());        // persistent: one workgroup per CU
     const dim3 gg(gs), bb(64 * kKvsWaves);
+    const bool mh = pp->nhead >= 2;
     if (bf && wide) {
-      if (pp->nhead >= 2) hipLaunchKernelGGL((attn_kv_stream64_kernel<true, kBfUnit, kBfUnit ? 8 : 4>), gg, bb, lds_s, st, a);
-      else hipLaunchKernelGGL((attn_kv_stream64_kernel<false, kBfUnit, kBfUnit ? 8 : 4>), gg, bb, lds_s, st, a);
-    } else if (bf) {
-      static const char *atrace = pcr_tune_str("PCR_ATTN_TRACE");
-      if (atrace) a.dbg |= 256;
-      if (onew) {
-        static bool oko = allow_big_lds(attn_kv_stream64_kernel<true, kBfUnit, 4, kBfUnit>) &&
-                          allow_big_lds(attn_kv_stream64_kernel<false, kBfUnit, 4, kBfUnit>);
-        (void)oko;
-        if (pp->nhead >= 2) hipLaunchKernelGGL((attn_kv_stream64_kernel<true, kBfUnit, 4, kBfUnit>), gg, bb, lds_s, st, a);
-        else hipLaunchKernelGGL((attn_kv_stream64_kernel<false, kBfUnit, 4, kBfUnit>), gg, bb, lds_s, st, a);
-      } else if (pp->nhead >= 2) hipLaunchKernelGGL((attn_kv_stream64_kernel<true, kBfUnit>), gg, bb, lds_s, st, a);
-      else hipLaunchKernelGGL((attn_kv_stream64_kernel<false, kBfUnit>), gg, bb, lds_s, st, a);
-      if (atrace) attn_dump_trace(atrace, "kv64", gs, (int)pp->B, pp->Sk);
-    } else {
-      if (pp->nhead >= 2) hipLaunchKernelGGL((attn_kv_stream64_kernel<true, false>), gg, bb, lds_s, st, a);
-      else hipLaunchKernelGGL((attn_kv_stream64_kernel<false, false>), gg, bb, lds_s, st, a);
+      constexpr int W = kBfUnit ? 8 : 4;
+      return mh ? pcr_launch_lds<attn_kv_stream64_kernel<true, kBfUnit, W>>(gg, bb, lds_s, st, a)
+                : pcr_launch_lds<attn_kv_stream64_kernel<false, kBfUnit, W>>(gg, bb, lds_s, st, a);
     }
-    PCR_CHECK_LAUNCH();
-    return PCR_OK;
+    if (!bf)
+      return mh ? pcr_launch_lds<attn_kv_stream64_kernel<true, false>>(gg, bb, lds_s, st, a)
+                : pcr_launch_lds<attn_kv_stream64_kernel<false, false>>(gg, bb, lds_s, st, a);
+    static const char *atrace = pcr_tune_str("PCR_ATTN_TRACE");
+    if (atrace) a.dbg |= 256;
+    int rc;
+    if (onew)
+      rc = mh ? pcr_launch_lds<attn_kv_stream64_kernel<true, kBfUnit, 4, kBfUnit>>(gg, bb, lds_s, st, a)
+              : pcr_launch_lds<attn_kv_stream64_kernel<false, kBfUnit, 4, kBfUnit>>(gg, bb, lds_s, st, a);
+    else
+      rc = mh ? pcr_launch_lds<attn_kv_stream64_kernel<true, kBfUnit>>(gg, bb, lds_s, st, a)
+              : pcr_launch_lds<attn_kv_stream64_kernel<false, kBfUnit>>(gg, bb, lds_s, st, a);
+    if (atrace) attn_dump_trace(atrace, "kv64", gs, (int)pp->B, pp->Sk);
+    return rc;
   }
 #if PCR_ATTN_PREC != 0
   if (ns == 1 && d == 32 && pp->c2 == 32 && pp->wkv_bf && (pp->Sk & 31) == 0 && pp->nhead >= 1 && 32 % pp->nhead == 0) {
-    static bool ok32 = allow_big_lds(attn_kv_stream32_kernel);
-    (void)ok32;
     pcr_note_arith(PCR_PREC_BF16X3);
     const int nblk = pp->Sk >> 5;
     int wpc2 = 1;
@@ -2279,16 +2262,8 @@ static int attn_kv_narrow(const pcr_attn_params *pp, pcr_stream_t stream) {
     const int cpg = kKvsWaves / wpc2;
     const size_t lds_s = (size_t)(4096 + 128 + 64 + 32 * 33 + cpg * (32 * 33 + 32)) * sizeof(float);
     const long rounds = ((long)pp->B + cpg - 1) / cpg;
-    static const int ncu = [] {
-      hipDeviceProp_t pr;
-      int dev = 0;
-      if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&pr, dev) != hipSuccess) return 256;
-      return pr.multiProcessorCount > 0 ? pr.multiProcessorCount : 256;
-    }();
-    const long cap = 2L * ncu;                                // (small footprint: two workgroups per CU)
-    hipLaunchKernelGGL(attn_kv_stream32_kernel, dim3((unsigned)(rounds < cap ? rounds : cap)), dim3(64 * kKvsWaves), lds_s, st, a);
-    PCR_CHECK_LAUNCH();
-    return PCR_OK;
+    const long cap = 2L * pcr_cu_count();                                // (small footprint: two workgroups per CU)
+    return pcr_launch_lds<attn_kv_stream32_kernel>(dim3((unsigned)(rounds < cap ? rounds : cap)), dim3(64 * kKvsWaves), lds_s, st, a);
   }
   static const int no_kv128 = pcr_tune_int("PCR_ATTN_NO_KV128");   // diagnostics: these shapes back to the tile kernel
   if (ns == 1 && d == 128 && pp->c2 == 128 && pp->wkv_bf && (pp->Sk & 31) == 0 && pp->Sk >= 256 &&
@@ -2303,45 +2278,38 @@ static int attn_kv_narrow(const pcr_attn_params *pp, pcr_stream_t stream) {
     const int cpg = kAp128Waves / a.wpc;
     const size_t lds_s = kKv128Lds0 + (a.wpc > 1 ? (size_t)cpg * (16 * (16 / pp->nhead) + 4) * 64 * sizeof(float) : 0);
     const long nwg = ((long)pp->B + cpg - 1) / cpg;
-    static const int ncu = [] {
-      hipDeviceProp_t pr;
-      int dev = 0;
-      if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&pr, dev) != hipSuccess) return 256;
-      return pr.multiProcessorCount > 0 ? pr.multiProcessorCount : 256;
-    }();
-    const dim3 gg((unsigned)(nwg < ncu ? nwg : ncu)), bb(64 * kAp128Waves);
-    static bool ok128 = allow_big_lds(attn_kv_stream128_kernel<2>) && allow_big_lds(attn_kv_stream128_kernel<4>);
-    (void)ok128;
-    if (pp->nhead == 2) hipLaunchKernelGGL((attn_kv_stream128_kernel<2>), gg, bb, lds_s, st, a);
-    else hipLaunchKernelGGL((attn_kv_stream128_kernel<4>), gg, bb, lds_s, st, a);
-    PCR_CHECK_LAUNCH();
-    return PCR_OK;
+    const dim3 gg((unsigned)(nwg < pcr_cu_count() ? nwg : pcr_cu_count())), bb(64 * kAp128Waves);
+    return pp->nhead == 2 ? pcr_launch_lds<attn_kv_stream128_kernel<2>>(gg, bb, lds_s, st, a)
+                          : pcr_launch_lds<attn_kv_stream128_kernel<4>>(gg, bb, lds_s, st, a);
   }
 #endif
   pcr_note_arith(PCR_PREC_F32);   // the tile kernel projects in f32 in both units (only the form of M differs)
-  if (d == 32) hipLaunchKernelGGL((attn_kv_kernel<2, 1, 2, 1>), g, blk, lds, st, a);        // 2d = 64: two cout blocks
-  else if (d == 64) hipLaunchKernelGGL((attn_kv_kernel_o3<2, 1, 1, 1>), g, blk, lds, st, a);   // four, one per wave
+  int rc;
+  if (d == 32) rc = pcr_launch_lds<attn_kv_kernel<2, 1, 2, 1>>(g, blk, lds, st, a);        // 2d = 64: two cout blocks
+  else if (d == 64) rc = pcr_launch_lds<attn_kv_kernel_o3<2, 1, 1, 1>>(g, blk, lds, st, a);   // four, one per wave
   else if (d == 128) {
     // eight cout blocks, two rounds.  NOT the three-workgroups-per-CU form: this shape's fold buffer (d (d + 1) floats =
     // 66 KB) allows two workgroups per CU whatever the registers say, and held to a third of the register file the body
     // spilled 93 registers inside its tile loop for nothing (round 5, tools/kres.py)
-    static bool ok2 = allow_big_lds(attn_kv_kernel_o2<1, 2, 1, 4>) && allow_big_lds(attn_kv_kernel_o2<1, 2, 1, 4, true>);
-    (void)ok2;
     // (split-bf16 projection for key sets of >= 256 tokens -- a shape-only rule: the KV state is a mean over the key
     // tokens, so the projection's rounding averages out with their number; at Sk = 32 (the Point-Transformer @128) the
     // guard's sweep of tests/test_gpu_precision.py went from 4.5e-5 to 5.2e-5 with it, for 0.014 ms)
-    if (kBfUnit && pp->wkv_bf && pp->Sk >= 256) hipLaunchKernelGGL((attn_kv_kernel_o2<1, 2, 1, 4, true>), g, blk, lds, st, a);
-    else hipLaunchKernelGGL((attn_kv_kernel_o2<1, 2, 1, 4>), g, blk, lds, st, a);
+    if (kBfUnit && pp->wkv_bf && pp->Sk >= 256) rc = pcr_launch_lds<attn_kv_kernel_o2<1, 2, 1, 4, true>>(g, blk, lds, st, a);
+    else rc = pcr_launch_lds<attn_kv_kernel_o2<1, 2, 1, 4>>(g, blk, lds, st, a);
   }
-  else hipLaunchKernelGGL((attn_kv_kernel<1, 2, 0, 4>), g, blk, lds, st, a);                // d = 96: generic shape
-  PCR_CHECK_LAUNCH();
-  if (ns > 1) {
-    static bool okf = allow_big_lds(attn_kv_fold_kernel);
-    (void)okf;
-    hipLaunchKernelGGL(attn_kv_fold_kernel, dim3(pp->B), blk, ((size_t)d * (d + 1) + d) * sizeof(float), st, a);
-    PCR_CHECK_LAUNCH();
-  }
-  return PCR_OK;
+  else rc = pcr_launch_lds<attn_kv_kernel<1, 2, 0, 4>>(g, blk, lds, st, a);                // d = 96: generic shape
+  if (rc != PCR_OK || ns == 1) return rc;
+  return pcr_launch_lds<attn_kv_fold_kernel>(dim3(pp->B), blk, ((size_t)d * (d + 1) + d) * sizeof(float), st, a);
+}
+
+// the d = 64 wave-autonomous apply form (attn_apply_stream64_kernel), shapes: (c1 = 64 | 32 | < 16 with the padded
+// mlp[0] image) x (cout = 64 [+ cov_final 128] | cout = 128 | cout = 32 + cov_final 64)
+static bool aps64_shape(const pcr_attn_params &p) {
+  const bool aps_in = p.c1 == 64 || ((p.c1 == 32 || (p.c1 < 16 && p.wmlp0_bf_xpad)) && !p.q_pos && !p.residual);
+  const bool aps_out = (p.cout == 64 && (p.cfinal == 0 || p.cfinal == 128) && p.c1 >= 32) ||
+                       (p.cout == 128 && !p.cfinal && !p.residual && p.c1 == 64) ||
+                       (p.cout == 32 && p.cfinal == 64 && !p.residual && p.c1 < 16);
+  return p.d == 64 && aps_in && aps_out && (p.Lq & 31) == 0 && (p.nhead == 1 || p.nhead == 2 || p.nhead == 4);
 }
 
 static int attn_apply_launch(const pcr_attn_params *pp, pcr_stream_t stream) {
@@ -2377,126 +2345,67 @@ static int attn_apply_launch(const pcr_attn_params *pp, pcr_stream_t stream) {
     // tests/test_gpu_precision.py's margin sweep from under 5e-5 to 5.4e-5
     const long nitem = (long)p.B * (p.Lq >> 5);
     const long nwg = (nitem + kAp128Waves - 1) / kAp128Waves;
-    static const int ncu = [] {
-      hipDeviceProp_t pr;
-      int dev = 0;
-      if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&pr, dev) != hipSuccess) return 256;
-      return pr.multiProcessorCount > 0 ? pr.multiProcessorCount : 256;
-    }();
-    const dim3 gg((unsigned)(nwg < ncu ? nwg : ncu)), bb(64 * kAp128Waves);
-    static bool ok128 = allow_big_lds(attn_apply_stream128_kernel<1>) && allow_big_lds(attn_apply_stream128_kernel<2>) &&
-                        allow_big_lds(attn_apply_stream128_kernel<4>);
-    (void)ok128;
-    if (p.nhead == 1) hipLaunchKernelGGL((attn_apply_stream128_kernel<1>), gg, bb, kAp128Lds, st, a);
-    else if (p.nhead == 2) hipLaunchKernelGGL((attn_apply_stream128_kernel<2>), gg, bb, kAp128Lds, st, a);
-    else hipLaunchKernelGGL((attn_apply_stream128_kernel<4>), gg, bb, kAp128Lds, st, a);
-    PCR_CHECK_LAUNCH();
-    return PCR_OK;
+    const dim3 gg((unsigned)(nwg < pcr_cu_count() ? nwg : pcr_cu_count())), bb(64 * kAp128Waves);
+    if (p.nhead == 1) return pcr_launch_lds<attn_apply_stream128_kernel<1>>(gg, bb, kAp128Lds, st, a);
+    if (p.nhead == 2) return pcr_launch_lds<attn_apply_stream128_kernel<2>>(gg, bb, kAp128Lds, st, a);
+    return pcr_launch_lds<attn_apply_stream128_kernel<4>>(gg, bb, kAp128Lds, st, a);
   }
   if (p.d == 32 && p.c1 == 32 && p.cout == 32 && !p.cfinal && (p.Lq & 31) == 0 && (p.nhead == 1 || p.nhead == 2)) {
     // the SA1 self-attention (d_model 32): the same kernel with one 32-channel block
     const long nitem = (long)p.B * (p.Lq >> 5);
     const long nwg = (nitem + kApsWaves - 1) / kApsWaves;
-    static const int ncu = [] {
-      hipDeviceProp_t pr;
-      int dev = 0;
-      if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&pr, dev) != hipSuccess) return 256;
-      return pr.multiProcessorCount > 0 ? pr.multiProcessorCount : 256;
-    }();
-    const dim3 gg((unsigned)(nwg < ncu ? nwg : ncu)), bb(64 * kApsWaves);
-    static bool ok32 = allow_big_lds(attn_apply_stream64_kernel<true, 2, 0, 1, 1>) && allow_big_lds(attn_apply_stream64_kernel<false, 2, 0, 1, 1>);
-    (void)ok32;
-    if (p.q_pos) hipLaunchKernelGGL((attn_apply_stream64_kernel<true, 2, 0, 1, 1>), gg, bb, aps_lds, st, a);
-    else hipLaunchKernelGGL((attn_apply_stream64_kernel<false, 2, 0, 1, 1>), gg, bb, aps_lds, st, a);
-    PCR_CHECK_LAUNCH();
-    return PCR_OK;
+    const dim3 gg((unsigned)(nwg < pcr_cu_count() ? nwg : pcr_cu_count())), bb(64 * kApsWaves);
+    return p.q_pos ? pcr_launch_lds<attn_apply_stream64_kernel<true, 2, 0, 1, 1>>(gg, bb, aps_lds, st, a)
+                   : pcr_launch_lds<attn_apply_stream64_kernel<false, 2, 0, 1, 1>>(gg, bb, aps_lds, st, a);
   }
-  // shapes: (c1 = 64 | 32 | < 16 with the padded mlp[0] image) x (cout = 64 [+ cov_final 128] | cout = 128 | cout = 32 + cov_final 64)
-  const bool aps_in = p.c1 == 64 || ((p.c1 == 32 || (p.c1 < 16 && pp->wmlp0_bf_xpad)) && !p.q_pos && !p.residual);
-  const bool aps_out = (p.cout == 64 && (p.cfinal == 0 || p.cfinal == 128) && p.c1 >= 32) ||
-                       (p.cout == 128 && !p.cfinal && !p.residual && p.c1 == 64) ||
-                       (p.cout == 32 && p.cfinal == 64 && !p.residual && p.c1 < 16);
-  if (p.d == 64 && aps_in && aps_out &&
-      (p.Lq & 31) == 0 && (p.nhead == 1 || p.nhead == 2 || p.nhead == 4) && aps_lds <= (size_t)kMaxDynLds) {
+  if (aps64_shape(p) && aps_lds <= (size_t)kMaxDynLds) {
     // wave-autonomous form (shape-only choice)
-    const int c1s = aps_c1s, sq = c1s + (p.q_pos ? 4 : 0), s0 = c1s + 4;
     const int nob = p.cout >> 5;
-    const size_t lds_s = (size_t)(sq * 256 + s0 * 512 + nob * 1024) * 16 + (size_t)(448 + 256 + 64 * kApsWaves) * sizeof(float);
     const long nitem = (long)p.B * (p.Lq >> 5);
     const long nwg = (nitem + kApsWaves - 1) / kApsWaves;
-    static const int ncu = [] {
-      hipDeviceProp_t pr;
-      int dev = 0;
-      if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&pr, dev) != hipSuccess) return 256;
-      return pr.multiProcessorCount > 0 ? pr.multiProcessorCount : 256;
-    }();
-    const dim3 gg((unsigned)(nwg < ncu ? nwg : ncu)), bb(64 * kApsWaves);
-#define PCR_APS(QP, C1Sv, CFv)                                                            \
-  do {                                                                                    \
-    static bool oks = allow_big_lds(attn_apply_stream64_kernel<QP, C1Sv, CFv>);           \
-    (void)oks;                                                                            \
-    hipLaunchKernelGGL((attn_apply_stream64_kernel<QP, C1Sv, CFv>), gg, bb, lds_s, st, a); \
-  } while (0)
+    const dim3 gg((unsigned)(nwg < pcr_cu_count() ? nwg : pcr_cu_count())), bb(64 * kApsWaves);
     const bool cf = p.cfinal != 0;
     static const char *aptrace = pcr_tune_str("PCR_ATTN_TRACE");
     if (aptrace) a.dbg = 256;
     if (pp->pool_out) {
       // pooled output (pcr_attn_apply_pool_ok said yes): whole clouds per wave
-      static bool okp = allow_big_lds(attn_apply_stream64_kernel<false, 4, 0, 2, 2, true>);
-      (void)okp;
       const long nwgp = ((long)p.B + kApsWaves - 1) / kApsWaves;
-      const dim3 ggp((unsigned)(nwgp < ncu ? nwgp : ncu));
-      hipLaunchKernelGGL((attn_apply_stream64_kernel<false, 4, 0, 2, 2, true>), ggp, bb, lds_s, st, a);
-      PCR_CHECK_LAUNCH();
-      return PCR_OK;
+      const dim3 ggp((unsigned)(nwgp < pcr_cu_count() ? nwgp : pcr_cu_count()));
+      return pcr_launch_lds<attn_apply_stream64_kernel<false, 4, 0, 2, 2, true>>(ggp, bb, aps_lds, st, a);
     }
-    if (nob == 4) {
-      static bool ok4 = allow_big_lds(attn_apply_stream64_kernel<true, 4, 0, 4>) && allow_big_lds(attn_apply_stream64_kernel<false, 4, 0, 4>);
-      (void)ok4;
-      if (p.q_pos) hipLaunchKernelGGL((attn_apply_stream64_kernel<true, 4, 0, 4>), gg, bb, lds_s, st, a);
-      else hipLaunchKernelGGL((attn_apply_stream64_kernel<false, 4, 0, 4>), gg, bb, lds_s, st, a);
-    } else if (p.c1 < 16) {
-      static bool ok1 = allow_big_lds(attn_apply_stream64_kernel<false, 1, 2, 1>);
-      (void)ok1;
-      hipLaunchKernelGGL((attn_apply_stream64_kernel<false, 1, 2, 1>), gg, bb, lds_s, st, a);
-    } else if (p.c1 == 32) { if (cf) PCR_APS(false, 2, 4); else PCR_APS(false, 2, 0); }
-    else if (p.q_pos) { if (cf) PCR_APS(true, 4, 4); else PCR_APS(true, 4, 0); }
-    else { if (cf) PCR_APS(false, 4, 4); else PCR_APS(false, 4, 0); }
-#undef PCR_APS
+    int rc;
+    if (nob == 4)
+      rc = p.q_pos ? pcr_launch_lds<attn_apply_stream64_kernel<true, 4, 0, 4>>(gg, bb, aps_lds, st, a)
+                   : pcr_launch_lds<attn_apply_stream64_kernel<false, 4, 0, 4>>(gg, bb, aps_lds, st, a);
+    else if (p.c1 < 16) rc = pcr_launch_lds<attn_apply_stream64_kernel<false, 1, 2, 1>>(gg, bb, aps_lds, st, a);
+    else if (p.c1 == 32)
+      rc = cf ? pcr_launch_lds<attn_apply_stream64_kernel<false, 2, 4>>(gg, bb, aps_lds, st, a)
+              : pcr_launch_lds<attn_apply_stream64_kernel<false, 2, 0>>(gg, bb, aps_lds, st, a);
+    else if (p.q_pos)
+      rc = cf ? pcr_launch_lds<attn_apply_stream64_kernel<true, 4, 4>>(gg, bb, aps_lds, st, a)
+              : pcr_launch_lds<attn_apply_stream64_kernel<true, 4, 0>>(gg, bb, aps_lds, st, a);
+    else
+      rc = cf ? pcr_launch_lds<attn_apply_stream64_kernel<false, 4, 4>>(gg, bb, aps_lds, st, a)
+              : pcr_launch_lds<attn_apply_stream64_kernel<false, 4, 0>>(gg, bb, aps_lds, st, a);
     if (aptrace) attn_dump_trace(aptrace, "apply64", (int)gg.x, (int)p.B, p.Lq);
-    PCR_CHECK_LAUNCH();
-    return PCR_OK;
+    return rc;
   }
 #endif
   const bool wide = 2 * p.d > 128 || p.cout > 128 || p.cfinal > 128;   // some layer has > 4 cout blocks
-#define PCR_APPLY(TBv, NRv)                                                          \
-  do {                                                                               \
-    static bool ok = allow_big_lds(attn_apply_kernel<TBv, NRv>);                     \
-    (void)ok;                                                                        \
-    hipLaunchKernelGGL((attn_apply_kernel<TBv, NRv>), g, blk, lds, st, a);           \
-  } while (0)
-  if (tb == 4) {
-    if (wide) PCR_APPLY(4, 2);
-    else PCR_APPLY(4, 1);
-  } else if (tb == 2) {
-    if (wide) PCR_APPLY(2, 2);
-    else PCR_APPLY(2, 1);
-  } else {
-    // cout blocks of the widest layer: up to 8 -> two rounds per wave, up to 16 -> four, up to 32 (d_model 512) -> eight
-    int widest = 2 * p.d > p.cout ? 2 * p.d : p.cout;
-    if (p.cfinal > widest) widest = p.cfinal;
+  if (tb == 4)
+    return wide ? pcr_launch_lds<attn_apply_kernel<4, 2>>(g, blk, lds, st, a) : pcr_launch_lds<attn_apply_kernel<4, 1>>(g, blk, lds, st, a);
+  if (tb == 2)
+    return wide ? pcr_launch_lds<attn_apply_kernel<2, 2>>(g, blk, lds, st, a) : pcr_launch_lds<attn_apply_kernel<2, 1>>(g, blk, lds, st, a);
+  // cout blocks of the widest layer: up to 8 -> two rounds per wave, up to 16 -> four, up to 32 (d_model 512) -> eight
+  int widest = 2 * p.d > p.cout ? 2 * p.d : p.cout;
+  if (p.cfinal > widest) widest = p.cfinal;
 #if PCR_ATTN_PREC == 0
-    if (widest > 512) PCR_APPLY(1, 8);
-    else if (widest > 256) PCR_APPLY(1, 4);
-    else PCR_APPLY(1, 2);
+  if (widest > 512) return pcr_launch_lds<attn_apply_kernel<1, 8>>(g, blk, lds, st, a);
+  if (widest > 256) return pcr_launch_lds<attn_apply_kernel<1, 4>>(g, blk, lds, st, a);
 #else
-    if (widest > 256) return PCR_ERR_INVALID;
-    PCR_APPLY(1, 2);
+  if (widest > 256) return PCR_ERR_INVALID;
 #endif
-  }
-#undef PCR_APPLY
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  return pcr_launch_lds<attn_apply_kernel<1, 2>>(g, blk, lds, st, a);
 }
 
 #if PCR_ATTN_PREC == 1
@@ -2548,13 +2457,9 @@ PCR_EXPORT int pcr_attn_kv_f32(const pcr_attn_params *pp, pcr_stream_t stream) {
     const size_t lds2 = (size_t)dh * 65 * sizeof(float);
     if (lds2 > lds) lds = lds2;
     if (lds > (size_t)kMaxDynLds) return PCR_ERR_INVALID;
-    static bool okw = allow_big_lds(attn_kv_wide_kernel<2>) && allow_big_lds(attn_kv_wide_kernel<3>);
-    (void)okw;
     dim3 g(d / 64, pp->B), blk(kThreads);
-    if (64 + dh <= 256) hipLaunchKernelGGL((attn_kv_wide_kernel<2>), g, blk, lds, pcr_s(stream), a);
-    else hipLaunchKernelGGL((attn_kv_wide_kernel<3>), g, blk, lds, pcr_s(stream), a);
-    PCR_CHECK_LAUNCH();
-    return PCR_OK;
+    if (64 + dh <= 256) return pcr_launch_lds<attn_kv_wide_kernel<2>>(g, blk, lds, pcr_s(stream), a);
+    return pcr_launch_lds<attn_kv_wide_kernel<3>>(g, blk, lds, pcr_s(stream), a);
   }
   pcr_attn_params q;
   if (attn_bf(*pp, q)) return pcr_attn_kv_bf3(&q, stream);
@@ -2563,8 +2468,7 @@ PCR_EXPORT int pcr_attn_kv_f32(const pcr_attn_params *pp, pcr_stream_t stream) {
 
 static bool attn_pool_ok(const pcr_attn_params &p) {
   pcr_attn_params q;
-  return p.d == 64 && p.c1 == 64 && p.cout == 64 && !p.cfinal && !p.q_pos && (p.Lq & 31) == 0 &&
-         (p.nhead == 1 || p.nhead == 2 || p.nhead == 4) && attn_bf(p, q);
+  return aps64_shape(p) && p.c1 == 64 && p.cout == 64 && !p.cfinal && !p.q_pos && attn_bf(p, q);
 }
 
 PCR_EXPORT int pcr_attn_apply_pool_ok(const pcr_attn_params *pp) {

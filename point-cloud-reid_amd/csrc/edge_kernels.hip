@@ -502,21 +502,14 @@ PCR_EXPORT int pcr_local_attn_f32(const float *qkv, const int *idx, float *msg, 
   if (dh & (dh - 1)) return PCR_ERR_INVALID;
   const size_t lds32 = ((size_t)N * 32 * 2 + 32 * 33 + 32 * K) * 4;
   if (dh == 32 && lds32 <= 72 * 1024 && !pcr_tune_str("PCR_LOCAL_NO_LDS")) {
-    static bool big = hipFuncSetAttribute(reinterpret_cast<const void *>(local_attn_lds_kernel<32>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess;
-    (void)big;
-    hipLaunchKernelGGL(local_attn_lds_kernel<32>, dim3(nhead, B), dim3(kEdgeThreads), lds32, pcr_s(stream), qkv, idx,
-                       msg, N, C, K, eps);
-    PCR_CHECK_LAUNCH();
-    return PCR_OK;
+    return pcr_launch_lds<local_attn_lds_kernel<32>>(dim3(nhead, B), dim3(kEdgeThreads), lds32, pcr_s(stream), qkv, idx,
+                                                     msg, N, C, K, eps);
   }
   const dim3 g((N + 31) / 32, B), blk(kEdgeThreads);
   const size_t lds = (size_t)C * 33 * 4;
-  if (dh == 32) hipLaunchKernelGGL(local_attn_kernel<32>, g, blk, lds, pcr_s(stream), qkv, idx, msg, N, C, K, dh, eps);
-  else if (dh == 16) hipLaunchKernelGGL(local_attn_kernel<16>, g, blk, lds, pcr_s(stream), qkv, idx, msg, N, C, K, dh, eps);
-  else hipLaunchKernelGGL(local_attn_kernel<0>, g, blk, lds, pcr_s(stream), qkv, idx, msg, N, C, K, dh, eps);
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  if (dh == 32) return pcr_launch<local_attn_kernel<32>>(g, blk, lds, pcr_s(stream), qkv, idx, msg, N, C, K, dh, eps);
+  if (dh == 16) return pcr_launch<local_attn_kernel<16>>(g, blk, lds, pcr_s(stream), qkv, idx, msg, N, C, K, dh, eps);
+  return pcr_launch<local_attn_kernel<0>>(g, blk, lds, pcr_s(stream), qkv, idx, msg, N, C, K, dh, eps);
 }
 
 PCR_EXPORT int pcr_knn_feat_f32(const float *x, float *xx_ws, int *idx, int B, int C, int N, int K, long x_bstride,
@@ -526,32 +519,23 @@ PCR_EXPORT int pcr_knn_feat_f32(const float *x, float *xx_ws, int *idx, int B, i
     return PCR_ERR_INVALID;
   if (x_bstride <= 0) x_bstride = (long)C * N;
   hipStream_t st = pcr_s(stream);
-  hipLaunchKernelGGL(feat_sqnorm_kernel, dim3((N + 255) / 256, B), dim3(256), 0, st, x, xx_ws, C, N, x_bstride);
+  const int rc = pcr_launch<feat_sqnorm_kernel>(dim3((N + 255) / 256, B), dim3(256), 0, st, x, xx_ws, C, N, x_bstride);
+  if (rc != PCR_OK) return rc;
   const int T = N <= 64 ? 1 : N <= 128 ? 2 : N <= 256 ? 4 : N <= 512 ? 8 : N <= 1024 ? 16 : 32;
   const int QT = N <= 1024 ? 32 : 16;
   const int C2 = (C + 1) / 2;
   const size_t lds = (size_t)(2 * C2 * 32 + 32) * 4 + (size_t)QT * 64 * T * 4 + (size_t)(kKnnThreads / 64) * kSelCap * 8;
   if (lds > 160 * 1024) return PCR_ERR_INVALID;
   const dim3 g((N + QT - 1) / QT, B), blk(kKnnThreads);
-#define PCR_KNNF(TT)                                                                                              \
-  do {                                                                                                            \
-    static bool big = hipFuncSetAttribute(reinterpret_cast<const void *>(knn_feat_kernel<TT>),                    \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess;  \
-    (void)big;                                                                                                    \
-    hipLaunchKernelGGL((knn_feat_kernel<TT>), g, blk, lds, st, x, (const float *)xx_ws, idx, C, N, K, QT,         \
-                       x_bstride);                                                                                \
-  } while (0)
+  const float *xx = xx_ws;
   switch (T) {
-    case 1: PCR_KNNF(1); break;
-    case 2: PCR_KNNF(2); break;
-    case 4: PCR_KNNF(4); break;
-    case 8: PCR_KNNF(8); break;
-    case 16: PCR_KNNF(16); break;
-    default: PCR_KNNF(32); break;
+    case 1: return pcr_launch_lds<knn_feat_kernel<1>>(g, blk, lds, st, x, xx, idx, C, N, K, QT, x_bstride);
+    case 2: return pcr_launch_lds<knn_feat_kernel<2>>(g, blk, lds, st, x, xx, idx, C, N, K, QT, x_bstride);
+    case 4: return pcr_launch_lds<knn_feat_kernel<4>>(g, blk, lds, st, x, xx, idx, C, N, K, QT, x_bstride);
+    case 8: return pcr_launch_lds<knn_feat_kernel<8>>(g, blk, lds, st, x, xx, idx, C, N, K, QT, x_bstride);
+    case 16: return pcr_launch_lds<knn_feat_kernel<16>>(g, blk, lds, st, x, xx, idx, C, N, K, QT, x_bstride);
+    default: return pcr_launch_lds<knn_feat_kernel<32>>(g, blk, lds, st, x, xx, idx, C, N, K, QT, x_bstride);
   }
-#undef PCR_KNNF
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
 }
 
 PCR_EXPORT int pcr_edge_max_f32(const float *ta, const float *tb, const int *idx, const float *shift, float slope,
@@ -567,23 +551,13 @@ PCR_EXPORT int pcr_edge_max_f32(const float *ta, const float *tb, const int *idx
     // below: 0.72 and 1.55, but 1.52 against 1.69 at N = 1024, where it stays.
     static const int cs_env = pcr_tune_int("PCR_EDGE_CS");
     const int cs = cs_env ? cs_env : (N <= 128 ? 32 : 16);
-#define PCR_EDGE_LDS(CS_)                                                                                         \
-  do {                                                                                                            \
-    static bool big = hipFuncSetAttribute(reinterpret_cast<const void *>(edge_max_lds_kernel<CS_>),               \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess;  \
-    (void)big;                                                                                                    \
-    hipLaunchKernelGGL(edge_max_lds_kernel<CS_>, dim3((Co + CS_ - 1) / CS_, B), dim3(kEdgeThreads),               \
-                       (size_t)(N * CS_ + CS_ * 33 + 32 * K) * 4, pcr_s(stream), a);                              \
-  } while (0)
-    if (cs == 64 && N <= 512) PCR_EDGE_LDS(64);
-    else if (cs == 16 || N > 512) PCR_EDGE_LDS(16);
-    else PCR_EDGE_LDS(32);
-#undef PCR_EDGE_LDS
-    PCR_CHECK_LAUNCH();
-    return PCR_OK;
+    const int w = (cs == 64 && N <= 512) ? 64 : ((cs == 16 || N > 512) ? 16 : 32);
+    const dim3 g((Co + w - 1) / w, B), blk(kEdgeThreads);
+    const size_t lds = (size_t)(N * w + w * 33 + 32 * K) * 4;
+    if (w == 64) return pcr_launch_lds<edge_max_lds_kernel<64>>(g, blk, lds, pcr_s(stream), a);
+    if (w == 16) return pcr_launch_lds<edge_max_lds_kernel<16>>(g, blk, lds, pcr_s(stream), a);
+    return pcr_launch_lds<edge_max_lds_kernel<32>>(g, blk, lds, pcr_s(stream), a);
   }
   const size_t lds = (size_t)(32 * K + Co * 33) * 4;
-  hipLaunchKernelGGL(edge_max_kernel, dim3((N + 31) / 32, B), dim3(kEdgeThreads), lds, pcr_s(stream), a);
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  return pcr_launch<edge_max_kernel>(dim3((N + 31) / 32, B), dim3(kEdgeThreads), lds, pcr_s(stream), a);
 }

@@ -618,17 +618,11 @@ template <bool MAXE>
 static int dense_rw_launch(const DenseArgs &a, int B, hipStream_t st) {
   const int KB = ceil8(a.cin) / 8;
   const dim3 g((ceil32(a.cout) + 127) / 128, B);
-#define PCR_DRW(KBv)                                                                                       \
-  do {                                                                                                     \
-    const size_t lds = ((size_t)8 * KBv * 65 + 256) * sizeof(float);                                       \
-    hipLaunchKernelGGL((dense_rw_kernel<KBv, MAXE>), g, dim3(kThreads), lds, st, a, B);                    \
-  } while (0)
-  if (KB <= 4) PCR_DRW(4);
-  else if (KB <= 8) PCR_DRW(8);
-  else PCR_DRW(16);
-#undef PCR_DRW
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  const int kb = KB <= 4 ? 4 : (KB <= 8 ? 8 : 16);
+  const size_t lds = ((size_t)8 * kb * 65 + 256) * sizeof(float);
+  if (kb == 4) return pcr_launch<dense_rw_kernel<4, MAXE>>(g, dim3(kThreads), lds, st, a, B);
+  if (kb == 8) return pcr_launch<dense_rw_kernel<8, MAXE>>(g, dim3(kThreads), lds, st, a, B);
+  return pcr_launch<dense_rw_kernel<16, MAXE>>(g, dim3(kThreads), lds, st, a, B);
 }
 
 // ---- the wide per-point layers on the bf16 matrix core (round 4): PointNet's 1x1 convs, DGCNN's conv5 and the LinearRes
@@ -1235,17 +1229,13 @@ PCR_EXPORT int pcr_pool_head_f32(const pcr_head_params *pp, pcr_stream_t stream)
       !p.w1 || !p.w2 || !p.gn1_g || !p.gn1_b || !p.gn2_g || !p.gn2_b || !p.w_out || !p.b_out || !p.logits)
     return PCR_ERR_INVALID;
   if (p.P == 0) return PCR_OK;
-  hipLaunchKernelGGL(pool_head_kernel, dim3(p.P), dim3(kThreads), 0, pcr_s(stream), p);
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  return pcr_launch<pool_head_kernel>(dim3(p.P), dim3(kThreads), 0, pcr_s(stream), p);
 }
 
 PCR_EXPORT int pcr_pool_both_f32(const float *x, float *out, int B, int C, int L, pcr_stream_t stream) {
   if (!x || !out || B < 0 || C < 1 || L < 1) return PCR_ERR_INVALID;
   if (B == 0) return PCR_OK;
-  hipLaunchKernelGGL(pool_both_kernel, dim3(B), dim3(kThreads), 0, pcr_s(stream), x, out, C, L);
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  return pcr_launch<pool_both_kernel>(dim3(B), dim3(kThreads), 0, pcr_s(stream), x, out, C, L);
 }
 
 static int dense_launch(const float *x, const float *wp, long w_bstride, const float *scale, const float *shift,
@@ -1261,35 +1251,37 @@ static int dense_launch(const float *x, const float *wp, long w_bstride, const f
   if (cin >= 2 * kChunk && cin % kChunk == 0 && cout % 256 == 0 && !x_pm && !w_bstride && L > 32 &&
       !pcr_tune_str("PCR_DENSE_NO_CHUNK")) {
     const size_t ldsc = ((size_t)kChunk * 65 + 512) * sizeof(float);
-    static bool okc = allow_big_lds(dense_kernel<2, true, true>) && allow_big_lds(dense_kernel<2, false, true>);
-    (void)okc;
     const dim3 gc((L + 63) / 64, B, cout / 256);
-    if (gn_gs) hipLaunchKernelGGL((dense_kernel<2, true, true>), gc, dim3(kThreads), ldsc, pcr_s(stream), a);
-    else hipLaunchKernelGGL((dense_kernel<2, false, true>), gc, dim3(kThreads), ldsc, pcr_s(stream), a);
-    PCR_CHECK_LAUNCH();
-    return PCR_OK;
+    return gn_gs ? pcr_launch_lds<dense_kernel<2, true, true>>(gc, dim3(kThreads), ldsc, pcr_s(stream), a)
+                 : pcr_launch_lds<dense_kernel<2, false, true>>(gc, dim3(kThreads), ldsc, pcr_s(stream), a);
   }
   const int tb = ((size_t)cinP * 65 * 4 <= 72 * 1024 && L > 32) ? 2 : 1;
   size_t lds = ((size_t)cinP * (32 * tb + 1) + 512) * sizeof(float);
   if (lds > (size_t)kMaxDynLds) return PCR_ERR_INVALID;
-  static bool ok = allow_big_lds(dense_kernel<1, false>) && allow_big_lds(dense_kernel<2, false>);
-  (void)ok;
-  dim3 g((L + 32 * tb - 1) / (32 * tb), B, (ceil32(cout) + 255) / 256);
-  if (gn_gs) {
-    static bool okg = allow_big_lds(dense_kernel<1, true>) && allow_big_lds(dense_kernel<2, true>);
-    (void)okg;
-    if (tb == 2) hipLaunchKernelGGL((dense_kernel<2, true>), g, dim3(kThreads), lds, pcr_s(stream), a);
-    else hipLaunchKernelGGL((dense_kernel<1, true>), g, dim3(kThreads), lds, pcr_s(stream), a);
-  } else if (tb == 2) hipLaunchKernelGGL((dense_kernel<2, false>), g, dim3(kThreads), lds, pcr_s(stream), a);
-  else hipLaunchKernelGGL((dense_kernel<1, false>), g, dim3(kThreads), lds, pcr_s(stream), a);
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  const dim3 g((L + 32 * tb - 1) / (32 * tb), B, (ceil32(cout) + 255) / 256), b(kThreads);
+  const hipStream_t st = pcr_s(stream);
+  if (gn_gs)
+    return tb == 2 ? pcr_launch_lds<dense_kernel<2, true>>(g, b, lds, st, a) : pcr_launch_lds<dense_kernel<1, true>>(g, b, lds, st, a);
+  return tb == 2 ? pcr_launch_lds<dense_kernel<2, false>>(g, b, lds, st, a) : pcr_launch_lds<dense_kernel<1, false>>(g, b, lds, st, a);
 }
 
 // bf16 forms: cin a multiple of 64 (chunks of 256 / 128 / 64 channels), cout a multiple of 32, channel-major x, shared
 // weights.  pcr_dense_prec_ok tells a caller whether a shape is covered (else it keeps the f32 launch).
 PCR_EXPORT int pcr_dense_prec_ok(int cin, int cout, int L) {
   return cin >= 64 && cin % 64 == 0 && cout >= 32 && cout % 32 == 0 && L >= 1;
+}
+
+// the bf16 forms' fan-out over their template shapes
+template <bool GN, int NS>
+static int dense_bf_pc_go(int cin, dim3 g, size_t lds, hipStream_t st, const DenseArgs &a) {
+  if (cin == 1024) return pcr_launch_lds<dense_bf_pc_kernel<GN, NS, 8>>(g, dim3(kPcThreads), lds, st, a);
+  if (cin == 512) return pcr_launch_lds<dense_bf_pc_kernel<GN, NS, 4>>(g, dim3(kPcThreads), lds, st, a);
+  return pcr_launch_lds<dense_bf_pc_kernel<GN, NS, 2>>(g, dim3(kPcThreads), lds, st, a);
+}
+template <bool GN, int NS>
+static int dense_bf_go(bool wide, dim3 g, size_t lds, hipStream_t st, const DenseArgs &a, int KC) {
+  return wide ? pcr_launch_lds<dense_bf_kernel<GN, NS, 2>>(g, dim3(kThreads), lds, st, a, KC)
+              : pcr_launch_lds<dense_bf_kernel<GN, NS, 1>>(g, dim3(kThreads), lds, st, a, KC);
 }
 
 static int dense_bf_launch(const float *x, const float *wp_bf, const float *scale, const float *shift, float *y, int B,
@@ -1309,45 +1301,20 @@ static int dense_bf_launch(const float *x, const float *wp_bf, const float *scal
     const long tiles = (long)B * (L / kPcT), nzw = (ceil32(cout) + 255) / 256;
     if (((tiles + 7) / 8) * 8 * nzw > 0x7FFFFFFFl) return PCR_ERR_INVALID;
     a.w_bstride = tiles;
-#define PCR_DPC1(GNv, NSv, NCHv)                                                                  \
-  do {                                                                                            \
-    static bool ok = allow_big_lds(dense_bf_pc_kernel<GNv, NSv, NCHv>);                           \
-    (void)ok;                                                                                     \
-    hipLaunchKernelGGL((dense_bf_pc_kernel<GNv, NSv, NCHv>), dim3((unsigned)(((tiles + 7) / 8) * 8 * nzw)), dim3(kPcThreads), ldsp, pcr_s(stream), a); \
-  } while (0)
-#define PCR_DPC(GNv, NSv)                  \
-  do {                                     \
-    if (cin == 1024) PCR_DPC1(GNv, NSv, 8); \
-    else if (cin == 512) PCR_DPC1(GNv, NSv, 4); \
-    else PCR_DPC1(GNv, NSv, 2);            \
-  } while (0)
-    if (precision == PCR_PREC_BF16X3) { if (gn_gs) PCR_DPC(true, 3); else PCR_DPC(false, 3); }
-    else { if (gn_gs) PCR_DPC(true, 1); else PCR_DPC(false, 1); }
-#undef PCR_DPC1
-#undef PCR_DPC
-    PCR_CHECK_LAUNCH();
-    return PCR_OK;
+    const dim3 gp((unsigned)(((tiles + 7) / 8) * 8 * nzw));
+    const hipStream_t st = pcr_s(stream);
+    if (precision == PCR_PREC_BF16X3)
+      return gn_gs ? dense_bf_pc_go<true, 3>(cin, gp, ldsp, st, a) : dense_bf_pc_go<false, 3>(cin, gp, ldsp, st, a);
+    return gn_gs ? dense_bf_pc_go<true, 1>(cin, gp, ldsp, st, a) : dense_bf_pc_go<false, 1>(cin, gp, ldsp, st, a);
   }
   const int KC = cin % 256 == 0 ? 256 : (cin % 128 == 0 ? 128 : 64);
   const size_t lds = ((size_t)KC * 64 + 512) * sizeof(float);
   const dim3 g((L + 63) / 64, B, (cout + 255) / 256);
   const bool wide = cout > 128;      // more than four cout blocks in a workgroup's window: two rounds per wave
-#define PCR_DBF(GNv, NSv, NRv)                                                                    \
-  do {                                                                                            \
-    static bool ok = allow_big_lds(dense_bf_kernel<GNv, NSv, NRv>);                               \
-    (void)ok;                                                                                     \
-    hipLaunchKernelGGL((dense_bf_kernel<GNv, NSv, NRv>), g, dim3(kThreads), lds, pcr_s(stream), a, KC); \
-  } while (0)
-  if (precision == PCR_PREC_BF16X3) {
-    if (gn_gs) { if (wide) PCR_DBF(true, 3, 2); else PCR_DBF(true, 3, 1); }
-    else { if (wide) PCR_DBF(false, 3, 2); else PCR_DBF(false, 3, 1); }
-  } else {
-    if (gn_gs) { if (wide) PCR_DBF(true, 1, 2); else PCR_DBF(true, 1, 1); }
-    else { if (wide) PCR_DBF(false, 1, 2); else PCR_DBF(false, 1, 1); }
-  }
-#undef PCR_DBF
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  const hipStream_t st = pcr_s(stream);
+  if (precision == PCR_PREC_BF16X3)
+    return gn_gs ? dense_bf_go<true, 3>(wide, g, lds, st, a, KC) : dense_bf_go<false, 3>(wide, g, lds, st, a, KC);
+  return gn_gs ? dense_bf_go<true, 1>(wide, g, lds, st, a, KC) : dense_bf_go<false, 1>(wide, g, lds, st, a, KC);
 }
 
 PCR_EXPORT int pcr_dense_prec_f32(const float *x, const float *wp_bf, const float *scale, const float *shift, float *y,
@@ -1374,31 +1341,24 @@ PCR_EXPORT int pcr_dense_xpm_prec_f32(const float *x, const float *wp_bf, const 
   DenseArgs a{x, wp_bf, scale, shift, y, cin, cout, L, act, 0, 1, 0, nullptr};
   const int ncb = (cout + 31) / 32;
   const size_t lds = (size_t)(cin / 16) * ncb * 2048 + (size_t)64 * ncb * sizeof(float);
-  static const int ncu = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        n < 1)
-      n = 256;
-    return n;
-  }();
   long wgs = (items + kDpsWaves - 1) / kDpsWaves;
-  const long resident = (long)ncu * (lds <= (size_t)78 * 1024 ? 2 : 1);
+  const long resident = (long)pcr_cu_count() * (lds <= (size_t)78 * 1024 ? 2 : 1);
   if (wgs > resident) wgs = resident;
-#define PCR_DPS(NCBv, LOv)                                                                                  \
-  do {                                                                                                      \
-    static bool ok = allow_big_lds(dense_pm_stream_kernel<NCBv, LOv>);                                      \
-    (void)ok;                                                                                               \
-    hipLaunchKernelGGL((dense_pm_stream_kernel<NCBv, LOv>), dim3((unsigned)wgs), dim3(64 * kDpsWaves), lds, \
-                       pcr_s(stream), a, B);                                                                \
-  } while (0)
+  const dim3 g((unsigned)wgs), b(64 * kDpsWaves);
+  const hipStream_t st = pcr_s(stream);
+  int rc;
   if (precision == PCR_PREC_BF16X3) {
-    if (ncb == 1) PCR_DPS(1, true); else if (ncb == 2) PCR_DPS(2, true); else if (ncb == 3) PCR_DPS(3, true); else PCR_DPS(4, true);
+    if (ncb == 1) rc = pcr_launch_lds<dense_pm_stream_kernel<1, true>>(g, b, lds, st, a, B);
+    else if (ncb == 2) rc = pcr_launch_lds<dense_pm_stream_kernel<2, true>>(g, b, lds, st, a, B);
+    else if (ncb == 3) rc = pcr_launch_lds<dense_pm_stream_kernel<3, true>>(g, b, lds, st, a, B);
+    else rc = pcr_launch_lds<dense_pm_stream_kernel<4, true>>(g, b, lds, st, a, B);
   } else {
-    if (ncb == 1) PCR_DPS(1, false); else if (ncb == 2) PCR_DPS(2, false); else if (ncb == 3) PCR_DPS(3, false); else PCR_DPS(4, false);
+    if (ncb == 1) rc = pcr_launch_lds<dense_pm_stream_kernel<1, false>>(g, b, lds, st, a, B);
+    else if (ncb == 2) rc = pcr_launch_lds<dense_pm_stream_kernel<2, false>>(g, b, lds, st, a, B);
+    else if (ncb == 3) rc = pcr_launch_lds<dense_pm_stream_kernel<3, false>>(g, b, lds, st, a, B);
+    else rc = pcr_launch_lds<dense_pm_stream_kernel<4, false>>(g, b, lds, st, a, B);
   }
-#undef PCR_DPS
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  return rc;
 }
 
 PCR_EXPORT int pcr_dense_gn_prec_f32(const float *x, const float *wp_bf, const float *gamma, const float *beta,
@@ -1441,29 +1401,23 @@ PCR_EXPORT int pcr_pack_bmm_f32(const float *t, float *wp_per_cloud, int B, int 
   size_t total = (size_t)ceil8(k) * ceil32(k) * B;
   size_t blocks = (total + 255) / 256;
   if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(pack_bmm_kernel, dim3((unsigned)blocks), dim3(256), 0, pcr_s(stream), t, wp_per_cloud, B, k);
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  return pcr_launch<pack_bmm_kernel>(dim3((unsigned)blocks), dim3(256), 0, pcr_s(stream), t, wp_per_cloud, B, k);
 }
 
 PCR_EXPORT int pcr_channel_max_f32(const float *x, float *out, int B, int C, int L, int window, pcr_stream_t stream) {
   if (!x || !out || B < 0 || C < 1 || L < 1 || window < 1 || window > C) return PCR_ERR_INVALID;
   if (B == 0) return PCR_OK;
   if (B > 65535) return PCR_ERR_INVALID;
-  hipLaunchKernelGGL(channel_max_kernel, dim3((L + kThreads - 1) / kThreads, B), dim3(kThreads), 0, pcr_s(stream), x, out,
-                     C, L, window, C / window);
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  return pcr_launch<channel_max_kernel>(dim3((L + kThreads - 1) / kThreads, B), dim3(kThreads), 0, pcr_s(stream), x, out,
+                                        C, L, window, C / window);
 }
 
 PCR_EXPORT int pcr_max_over_l_f32(const float *x, float *out, int B, int C, int L, pcr_stream_t stream) {
   if (!x || !out || B < 0 || C < 1 || L < 1) return PCR_ERR_INVALID;
   if (B == 0) return PCR_OK;
   size_t rows = (size_t)B * C;
-  hipLaunchKernelGGL(max_over_l_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(kThreads), 0, pcr_s(stream), x, out,
-                     B, C, L);
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  return pcr_launch<max_over_l_kernel>(dim3((unsigned)((rows + 3) / 4)), dim3(kThreads), 0, pcr_s(stream), x, out,
+                                       B, C, L);
 }
 
 PCR_EXPORT int pcr_dense_max_ok(int cin, int cout, int L) {
@@ -1479,11 +1433,7 @@ PCR_EXPORT int pcr_dense_max_f32(const float *x, const float *wp, const float *s
   DenseArgs a{x, wp, scale, shift, out, cin, cout, L, act, 0, 0, 0, nullptr};
   if (dense_rw_ok(cin, cout, L) && !pcr_tune_str("PCR_DENSE_NO_RW")) return dense_rw_launch<true>(a, B, pcr_s(stream));
   const size_t lds = ((size_t)ceil8(cin) * 65 + 512) * sizeof(float);
-  static bool ok = allow_big_lds(dense_max_kernel);
-  (void)ok;
-  hipLaunchKernelGGL(dense_max_kernel, dim3(1, B, (ceil32(cout) + 255) / 256), dim3(kThreads), lds, pcr_s(stream), a, B);
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  return pcr_launch_lds<dense_max_kernel>(dim3(1, B, (ceil32(cout) + 255) / 256), dim3(kThreads), lds, pcr_s(stream), a, B);
 }
 
 PCR_EXPORT int pcr_groupnorm_f32(const float *x, const float *gamma, const float *beta, const float *res, float *y,
@@ -1493,8 +1443,6 @@ PCR_EXPORT int pcr_groupnorm_f32(const float *x, const float *gamma, const float
   if (B == 0) return PCR_OK;
   if (B > 65535) return PCR_ERR_INVALID;
   GnArgs a{x, gamma, beta, res, y, C, L, groups, relu};
-  hipLaunchKernelGGL(groupnorm_kernel, dim3((L + kThreads - 1) / kThreads, groups, B), dim3(kThreads), 0,
-                     pcr_s(stream), a);
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  return pcr_launch<groupnorm_kernel>(dim3((L + kThreads - 1) / kThreads, groups, B), dim3(kThreads), 0,
+                                      pcr_s(stream), a);
 }

@@ -106,10 +106,8 @@ PCR_EXPORT int pcr_grad_sumsq_f32(const pcr_opt_tensor *tab, const int *chunk_te
                                   int n_chunks, double *part, pcr_stream_t stream) {
   if (!tab || !chunk_tensor || !chunk_first || !part || n_chunks < 0) return PCR_ERR_INVALID;
   if (n_chunks == 0) return PCR_OK;
-  hipLaunchKernelGGL(grad_sumsq_kernel, dim3(n_chunks), dim3(kThreads), 0, pcr_s(stream),
-                     reinterpret_cast<const OptTensor *>(tab), chunk_tensor, chunk_first, part);
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  return pcr_launch<grad_sumsq_kernel>(dim3(n_chunks), dim3(kThreads), 0, pcr_s(stream),
+                                       reinterpret_cast<const OptTensor *>(tab), chunk_tensor, chunk_first, part);
 }
 
 PCR_EXPORT int pcr_adamw_step_f32(const pcr_opt_tensor *tab, const int *chunk_tensor, const int *chunk_first,
@@ -117,9 +115,7 @@ PCR_EXPORT int pcr_adamw_step_f32(const pcr_opt_tensor *tab, const int *chunk_te
                                   pcr_stream_t stream) {
   if (!tab || !chunk_tensor || !chunk_first || n_chunks < 0) return PCR_ERR_INVALID;
   if (n_chunks == 0) return PCR_OK;
-  hipLaunchKernelGGL(adamw_step_kernel, dim3(n_chunks), dim3(kThreads), 0, pcr_s(stream),
-                     reinterpret_cast<const OptTensor *>(tab), chunk_tensor, chunk_first, n_chunks, part, max_norm,
-                     grad_norm);
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  return pcr_launch<adamw_step_kernel>(dim3(n_chunks), dim3(kThreads), 0, pcr_s(stream),
+                                       reinterpret_cast<const OptTensor *>(tab), chunk_tensor, chunk_first, n_chunks, part, max_norm,
+                                       grad_norm);
 }

@@ -7,14 +7,44 @@
 
 #define PCR_EXPORT extern "C" __attribute__((visibility("default")))
 
-#define PCR_CHECK_LAUNCH()                        \
-  do {                                            \
-    if (hipGetLastError() != hipSuccess) return PCR_ERR_LAUNCH; \
-  } while (0)
-
 static inline hipStream_t pcr_s(pcr_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
 constexpr int kWave = 64;
+constexpr int kMaxDynLds = 160 * 1024;
+
+// ---- launch helpers (host) ----------------------------------------------------------------------------------------
+// The current device's compute-unit count, queried once (256 if the query fails): the grid cap of the persistent kernels.
+static inline int pcr_cu_count() {
+  static const int ncu = [] {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+        n < 1)
+      return 256;
+    return n;
+  }();
+  return ncu;
+}
+
+// Launches KERN; PCR_OK, or PCR_ERR_LAUNCH if the runtime reports an error.
+template <auto KERN, class... Args>
+static inline int pcr_launch(dim3 grid, dim3 block, size_t lds, hipStream_t st, Args... args) {
+  hipLaunchKernelGGL(KERN, grid, block, lds, st, args...);
+  return hipGetLastError() == hipSuccess ? PCR_OK : PCR_ERR_LAUNCH;
+}
+
+// Dynamic LDS beyond the default 64 KiB: KERN is opted in to kMaxDynLds once per process.  pcr_launch_lds does it at the
+// kernel's first launch; only a dispatcher whose occupancy query must see the opt-in calls it directly.
+template <auto KERN>
+static inline void allow_big_lds() {
+  static const bool opted = hipFuncSetAttribute(reinterpret_cast<const void *>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                kMaxDynLds) == hipSuccess;
+  (void)opted;
+}
+template <auto KERN, class... Args>
+static inline int pcr_launch_lds(dim3 grid, dim3 block, size_t lds, hipStream_t st, Args... args) {
+  allow_big_lds<KERN>();
+  return pcr_launch<KERN>(grid, block, lds, st, args...);
+}
 
 // Diagnostics for bench.py's roofline object: the arithmetic (PCR_PREC_*) of the matrix phases of the model launch the
 // calling thread issued last (pcr_last_launch_arith, probe_kernels.hip).  Every dispatcher of section B notes what the

@@ -658,44 +658,32 @@ int fps_launch(bool dist, const float *data, float *temp, int *idx, int B, int N
   while ((2 << logb) <= N && logb < 10) logb++;  // block = min(1024, 2^floor(log2 N))
   int block = 1 << logb;
   if (!dist && N <= 1024 && M > 1) {
-    const size_t lds_wave = 0;
-    dim3 gw(B), bw(64);
-#define PCR_FPS_WAVE(PPv) hipLaunchKernelGGL((fps_wave_kernel<PPv>), gw, bw, lds_wave, st, data, temp, idx, N, M, block, logb)
-    if (N <= 128) PCR_FPS_WAVE(1);
-    else if (N <= 256) PCR_FPS_WAVE(2);
-    else if (N <= 512) PCR_FPS_WAVE(4);
-    else PCR_FPS_WAVE(8);
-#undef PCR_FPS_WAVE
-    PCR_CHECK_LAUNCH();
-    return PCR_OK;
+    const dim3 gw(B), bw(64);
+    if (N <= 128) return pcr_launch<fps_wave_kernel<1>>(gw, bw, 0, st, data, temp, idx, N, M, block, logb);
+    if (N <= 256) return pcr_launch<fps_wave_kernel<2>>(gw, bw, 0, st, data, temp, idx, N, M, block, logb);
+    if (N <= 512) return pcr_launch<fps_wave_kernel<4>>(gw, bw, 0, st, data, temp, idx, N, M, block, logb);
+    return pcr_launch<fps_wave_kernel<8>>(gw, bw, 0, st, data, temp, idx, N, M, block, logb);
   }
   if (!dist && N <= 4096 && M > 1) {
     const size_t lds_fast = 64 + (size_t)3 * N * sizeof(float);
-    dim3 gf(B);
-#define PCR_FPS_FAST(P, T) hipLaunchKernelGGL((fps_fast_kernel<P, T>), gf, dim3(T), lds_fast, st, data, temp, idx, N, M, block, logb)
-    if (N <= 256) PCR_FPS_FAST(1, 256);
-    else if (N <= 512) PCR_FPS_FAST(2, 256);
-    else if (N <= 1024) PCR_FPS_FAST(4, 256);
-    else if (N <= 2048) PCR_FPS_FAST(8, 256);
-    else PCR_FPS_FAST(16, 256);
-#undef PCR_FPS_FAST
-    PCR_CHECK_LAUNCH();
-    return PCR_OK;
+    const dim3 gf(B), bf(256);
+    if (N <= 256) return pcr_launch<fps_fast_kernel<1, 256>>(gf, bf, lds_fast, st, data, temp, idx, N, M, block, logb);
+    if (N <= 512) return pcr_launch<fps_fast_kernel<2, 256>>(gf, bf, lds_fast, st, data, temp, idx, N, M, block, logb);
+    if (N <= 1024) return pcr_launch<fps_fast_kernel<4, 256>>(gf, bf, lds_fast, st, data, temp, idx, N, M, block, logb);
+    if (N <= 2048) return pcr_launch<fps_fast_kernel<8, 256>>(gf, bf, lds_fast, st, data, temp, idx, N, M, block, logb);
+    return pcr_launch<fps_fast_kernel<16, 256>>(gf, bf, lds_fast, st, data, temp, idx, N, M, block, logb);
   }
   int threads = block < 64 ? 64 : block;
   bool reg = N <= kFpsPpt * block;
   int stage = (!dist && N <= kFpsLdsPts) ? 1 : 0;
   size_t lds = 256 + (stage ? (size_t)3 * N * sizeof(float) : 0);
   dim3 g(B), b(threads);
-  if (dist) {
-    if (reg) hipLaunchKernelGGL((fps_kernel<true, true>), g, b, lds, st, data, temp, idx, N, M, block, logb, stage, (const int *)nullptr, 0);
-    else hipLaunchKernelGGL((fps_kernel<true, false>), g, b, lds, st, data, temp, idx, N, M, block, logb, stage, (const int *)nullptr, 0);
-  } else {
-    if (reg) hipLaunchKernelGGL((fps_kernel<false, true>), g, b, lds, st, data, temp, idx, N, M, block, logb, stage, (const int *)nullptr, 0);
-    else hipLaunchKernelGGL((fps_kernel<false, false>), g, b, lds, st, data, temp, idx, N, M, block, logb, stage, (const int *)nullptr, 0);
-  }
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  const int *none = nullptr;
+  if (dist)
+    return reg ? pcr_launch<fps_kernel<true, true>>(g, b, lds, st, data, temp, idx, N, M, block, logb, stage, none, 0)
+               : pcr_launch<fps_kernel<true, false>>(g, b, lds, st, data, temp, idx, N, M, block, logb, stage, none, 0);
+  return reg ? pcr_launch<fps_kernel<false, true>>(g, b, lds, st, data, temp, idx, N, M, block, logb, stage, none, 0)
+             : pcr_launch<fps_kernel<false, false>>(g, b, lds, st, data, temp, idx, N, M, block, logb, stage, none, 0);
 }
 
 // ------------------------------------------------------------------ pairwise distances ----
@@ -952,37 +940,42 @@ __global__ __launch_bounds__(256) void ball_query_reg_kernel(const float *__rest
   }
 }
 
-static void ball_query_launch(const float *centres, const float *xyz, int *idx, int *cnt, int B, int N, int M,
+static int ball_query_launch(const float *centres, const float *xyz, int *idx, int *cnt, int B, int N, int M,
                               float min_r2, float max_r2, int K, hipStream_t st, float *rows = nullptr) {
   if (rows) {   // (validated by the caller: N <= 1024, min radius 0, K even)
     const int cpw = 16, nchunk = (M + 4 * cpw - 1) / (4 * cpw);
     const dim3 grid((unsigned)((B + 7) / 8) * 8 * nchunk), blk(256);
     f32x4 *r4 = reinterpret_cast<f32x4 *>(rows);
-#define PCR_BQR(PPLv)                                                                                            \
-  hipLaunchKernelGGL((ball_query_reg_kernel<PPLv, true, true>), grid, blk, 0, st, centres, xyz, idx, N, M, min_r2, \
-                     max_r2, K, cnt, cpw, nchunk, B, r4)
-    if (N <= 256) PCR_BQR(4);
-    else if (N <= 512) PCR_BQR(8);
-    else PCR_BQR(16);
-#undef PCR_BQR
-    return;
+    if (N <= 256)
+      return pcr_launch<ball_query_reg_kernel<4, true, true>>(grid, blk, 0, st, centres, xyz, idx, N, M, min_r2, max_r2, K,
+                                                              cnt, cpw, nchunk, B, r4);
+    if (N <= 512)
+      return pcr_launch<ball_query_reg_kernel<8, true, true>>(grid, blk, 0, st, centres, xyz, idx, N, M, min_r2, max_r2, K,
+                                                              cnt, cpw, nchunk, B, r4);
+    return pcr_launch<ball_query_reg_kernel<16, true, true>>(grid, blk, 0, st, centres, xyz, idx, N, M, min_r2, max_r2, K,
+                                                             cnt, cpw, nchunk, B, r4);
   }
   if (N <= 1024) {
     const int cpw = 16;                                  // centres per wave
     const int nchunk = (M + 4 * cpw - 1) / (4 * cpw);
     const dim3 grid((unsigned)((B + 7) / 8) * 8 * nchunk), blk(256);
     const bool simple = min_r2 == 0.f && max_r2 > 0.f;
-#define PCR_BQ(PPLv, SIMPLEv)                                                                                    \
-  hipLaunchKernelGGL((ball_query_reg_kernel<PPLv, SIMPLEv>), grid, blk, 0, st, centres, xyz, idx, N, M, min_r2, \
-                     max_r2, K, cnt, cpw, nchunk, B)
-    if (N <= 256) { if (simple) PCR_BQ(4, true); else PCR_BQ(4, false); }
-    else if (N <= 512) { if (simple) PCR_BQ(8, true); else PCR_BQ(8, false); }
-    else { if (simple) PCR_BQ(16, true); else PCR_BQ(16, false); }
-#undef PCR_BQ
-  } else {
-    hipLaunchKernelGGL(ball_query_kernel<false>, dim3((M + 255) / 256, B), dim3(256), 0, st, centres, xyz, idx, N, M,
-                       min_r2, max_r2, K, cnt);
+    const int ppl = N <= 256 ? 4 : (N <= 512 ? 8 : 16);
+    if (ppl == 4 && simple) return pcr_launch<ball_query_reg_kernel<4, true>>(grid, blk, 0, st, centres, xyz, idx, N, M,
+      min_r2, max_r2, K, cnt, cpw, nchunk, B, (f32x4 *)nullptr);
+    if (ppl == 4) return pcr_launch<ball_query_reg_kernel<4, false>>(grid, blk, 0, st, centres, xyz, idx, N, M,
+      min_r2, max_r2, K, cnt, cpw, nchunk, B, (f32x4 *)nullptr);
+    if (ppl == 8 && simple) return pcr_launch<ball_query_reg_kernel<8, true>>(grid, blk, 0, st, centres, xyz, idx, N, M,
+      min_r2, max_r2, K, cnt, cpw, nchunk, B, (f32x4 *)nullptr);
+    if (ppl == 8) return pcr_launch<ball_query_reg_kernel<8, false>>(grid, blk, 0, st, centres, xyz, idx, N, M,
+      min_r2, max_r2, K, cnt, cpw, nchunk, B, (f32x4 *)nullptr);
+    if (simple) return pcr_launch<ball_query_reg_kernel<16, true>>(grid, blk, 0, st, centres, xyz, idx, N, M,
+      min_r2, max_r2, K, cnt, cpw, nchunk, B, (f32x4 *)nullptr);
+    return pcr_launch<ball_query_reg_kernel<16, false>>(grid, blk, 0, st, centres, xyz, idx, N, M,
+      min_r2, max_r2, K, cnt, cpw, nchunk, B, (f32x4 *)nullptr);
   }
+  return pcr_launch<ball_query_kernel<false>>(dim3((M + 255) / 256, B), dim3(256), 0, st, centres, xyz, idx, N, M, min_r2,
+                                              max_r2, K, cnt);
 }
 
 // --------------------------------------------------------------------------- heap kNN ----
@@ -1137,35 +1130,27 @@ __global__ __launch_bounds__(256) void scatter_owner_kernel(const float *__restr
   }
 }
 
-// -> false when the cloud is too large for the LDS accumulators (caller falls back to the atomic kernel)
-static bool scatter_owner_launch(const float *src, const int *idx, const float *w, float *grad_feat, int B, int C, int N,
-                                 int M, int DIV, hipStream_t st) {
+// -> -1 when the cloud is too large for the LDS accumulators (caller falls back to the atomic kernel), else the launch's status
+static int scatter_owner_launch(const float *src, const int *idx, const float *w, float *grad_feat, int B, int C, int N,
+                                int M, int DIV, hipStream_t st) {
   int cs = 32;
   while (cs > 1 && (size_t)cs * (N | 1) * 4 > 64 * 1024) cs >>= 1;
-  if ((size_t)cs * (N | 1) * 4 > 96 * 1024 || B > 65535) return false;
+  if ((size_t)cs * (N | 1) * 4 > 96 * 1024 || B > 65535) return -1;
   if (cs > C) {
     cs = 1;
     while (cs * 2 <= C) cs *= 2;
   }
   const size_t lds = ((size_t)cs * (N | 1) + (size_t)cs * 65 + 64 + 64) * sizeof(float);
   const dim3 grid((C + cs - 1) / cs, B);
-#define PCR_SC(CSv)                                                                                              \
-  do {                                                                                                           \
-    static bool ok = hipFuncSetAttribute(reinterpret_cast<const void *>(scatter_owner_kernel<CSv>),              \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess;  \
-    (void)ok;                                                                                                    \
-    hipLaunchKernelGGL(scatter_owner_kernel<CSv>, grid, dim3(256), lds, st, src, idx, w, grad_feat, C, N, M, DIV); \
-  } while (0)
+  const dim3 blk(256);
   switch (cs) {
-    case 32: PCR_SC(32); break;
-    case 16: PCR_SC(16); break;
-    case 8: PCR_SC(8); break;
-    case 4: PCR_SC(4); break;
-    case 2: PCR_SC(2); break;
-    default: PCR_SC(1); break;
+    case 32: return pcr_launch_lds<scatter_owner_kernel<32>>(grid, blk, lds, st, src, idx, w, grad_feat, C, N, M, DIV);
+    case 16: return pcr_launch_lds<scatter_owner_kernel<16>>(grid, blk, lds, st, src, idx, w, grad_feat, C, N, M, DIV);
+    case 8: return pcr_launch_lds<scatter_owner_kernel<8>>(grid, blk, lds, st, src, idx, w, grad_feat, C, N, M, DIV);
+    case 4: return pcr_launch_lds<scatter_owner_kernel<4>>(grid, blk, lds, st, src, idx, w, grad_feat, C, N, M, DIV);
+    case 2: return pcr_launch_lds<scatter_owner_kernel<2>>(grid, blk, lds, st, src, idx, w, grad_feat, C, N, M, DIV);
+    default: return pcr_launch_lds<scatter_owner_kernel<1>>(grid, blk, lds, st, src, idx, w, grad_feat, C, N, M, DIV);
   }
-#undef PCR_SC
-  return true;
 }
 
 int gather_launch(bool bwd, const float *a, const int *idx, float *o, int B, int C, int N, int M,
@@ -1175,12 +1160,10 @@ int gather_launch(bool bwd, const float *a, const int *idx, float *o, int B, int
   if (total == 0) return PCR_OK;
   size_t blocks = (total + 255) / 256;
   if (blocks > 8192) blocks = 8192;
-  if (bwd) {
-    if (!scatter_owner_launch(a, idx, nullptr, o, B, C, N, M, 1, st))
-      hipLaunchKernelGGL(gather_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a, idx, o, C, N, M, total);
-  } else hipLaunchKernelGGL(gather_fwd_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a, idx, o, C, N, M, total);
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  if (!bwd) return pcr_launch<gather_fwd_kernel>(dim3((unsigned)blocks), dim3(256), 0, st, a, idx, o, C, N, M, total);
+  const int rc = scatter_owner_launch(a, idx, nullptr, o, B, C, N, M, 1, st);
+  if (rc >= 0) return rc;
+  return pcr_launch<gather_bwd_kernel>(dim3((unsigned)blocks), dim3(256), 0, st, a, idx, o, C, N, M, total);
 }
 
 // ------------------------------------------------------------------------- three NN ----
@@ -1730,10 +1713,8 @@ PCR_EXPORT int pcr_pairwise_sqdist_f32(const float *a, const float *b, float *ou
   if (!a || !b || !out || B < 0 || N < 0 || M < 0 || C < 1) return PCR_ERR_INVALID;
   if (B == 0 || N == 0 || M == 0) return PCR_OK;
   if (B > 65535 || N > 65535) return PCR_ERR_INVALID;
-  hipLaunchKernelGGL(pairwise_sqdist_kernel, dim3((M + 255) / 256, N, B), dim3(256), 0, pcr_s(stream), a, b, out, N, M, C,
-                     norm);
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  return pcr_launch<pairwise_sqdist_kernel>(dim3((M + 255) / 256, N, B), dim3(256), 0, pcr_s(stream), a, b, out, N, M, C,
+                                            norm);
 }
 
 PCR_EXPORT int pcr_fps_py_f32(const float *xyz, float *temp, const int *start, int *idx, int B, int N, int M,
@@ -1747,12 +1728,11 @@ PCR_EXPORT int pcr_fps_py_f32(const float *xyz, float *temp, const int *start, i
   const bool reg = N <= kFpsPpt * block;
   const int stage = N <= kFpsLdsPts ? 1 : 0;
   const size_t lds = 256 + (stage ? (size_t)3 * N * sizeof(float) : 0);
-  if (reg) hipLaunchKernelGGL((fps_kernel<false, true>), dim3(B), dim3(threads), lds, pcr_s(stream), xyz, temp, idx, N, M,
-                              block, logb, stage, start, 1);
-  else hipLaunchKernelGGL((fps_kernel<false, false>), dim3(B), dim3(threads), lds, pcr_s(stream), xyz, temp, idx, N, M,
-                          block, logb, stage, start, 1);
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  if (reg)
+    return pcr_launch<fps_kernel<false, true>>(dim3(B), dim3(threads), lds, pcr_s(stream), xyz, temp, idx, N, M, block, logb,
+                                               stage, start, 1);
+  return pcr_launch<fps_kernel<false, false>>(dim3(B), dim3(threads), lds, pcr_s(stream), xyz, temp, idx, N, M, block, logb,
+                                              stage, start, 1);
 }
 
 PCR_EXPORT int pcr_query_ball_point_f32(const float *centres, const float *xyz, int *idx, int B, int N, int M,
@@ -1760,10 +1740,8 @@ PCR_EXPORT int pcr_query_ball_point_f32(const float *centres, const float *xyz, 
   if (!centres || !xyz || !idx || B < 0 || N < 1 || M < 0 || K < 1) return PCR_ERR_INVALID;
   if (B == 0 || M == 0) return PCR_OK;
   if (B > 65535) return PCR_ERR_INVALID;
-  hipLaunchKernelGGL(ball_query_kernel<true>, dim3((M + 255) / 256, B), dim3(256), 0, pcr_s(stream), centres, xyz, idx,
-                     N, M, 0.f, radius * radius, K, (int *)nullptr);
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  return pcr_launch<ball_query_kernel<true>>(dim3((M + 255) / 256, B), dim3(256), 0, pcr_s(stream), centres, xyz, idx,
+                                             N, M, 0.f, radius * radius, K, (int *)nullptr);
 }
 
 PCR_EXPORT int pcr_ball_query_f32(const float *centres, const float *xyz, int *idx, int B, int N,
@@ -1772,9 +1750,7 @@ PCR_EXPORT int pcr_ball_query_f32(const float *centres, const float *xyz, int *i
   if (B == 0 || M == 0) return PCR_OK;
   if (B > 65535) return PCR_ERR_INVALID;
   float max_r2 = max_r * max_r, min_r2 = min_r * min_r;
-  ball_query_launch(centres, xyz, idx, nullptr, B, N, M, min_r2, max_r2, K, pcr_s(stream));
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  return ball_query_launch(centres, xyz, idx, nullptr, B, N, M, min_r2, max_r2, K, pcr_s(stream));
 }
 
 PCR_EXPORT int pcr_ball_query_cnt_f32(const float *centres, const float *xyz, int *idx, int *cnt, int B, int N,
@@ -1783,9 +1759,7 @@ PCR_EXPORT int pcr_ball_query_cnt_f32(const float *centres, const float *xyz, in
   if (B == 0 || M == 0) return PCR_OK;
   if (B > 65535) return PCR_ERR_INVALID;
   float max_r2 = max_r * max_r, min_r2 = min_r * min_r;
-  ball_query_launch(centres, xyz, idx, cnt, B, N, M, min_r2, max_r2, K, pcr_s(stream));
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  return ball_query_launch(centres, xyz, idx, cnt, B, N, M, min_r2, max_r2, K, pcr_s(stream));
 }
 
 PCR_EXPORT long pcr_ball_query_rows_floats(int B, int M, int K) {
@@ -1802,9 +1776,7 @@ PCR_EXPORT int pcr_ball_query_rows_f32(const float *centres, const float *xyz, i
     return PCR_ERR_INVALID;
   if (B == 0 || M == 0) return PCR_OK;
   if (B > 65535) return PCR_ERR_INVALID;
-  ball_query_launch(centres, xyz, idx, cnt, B, N, M, 0.f, max_r * max_r, K, pcr_s(stream), rows);
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  return ball_query_launch(centres, xyz, idx, cnt, B, N, M, 0.f, max_r * max_r, K, pcr_s(stream), rows);
 }
 
 PCR_EXPORT int pcr_fps_ball_query_rows_ok(int N, int M, int K) {
@@ -1822,15 +1794,11 @@ PCR_EXPORT int pcr_fps_ball_query_rows_f32(const float *xyz, float *temp, int *i
   const float max_r2 = max_r * max_r;
   f32x4 *r4 = reinterpret_cast<f32x4 *>(rows);
   hipStream_t st = pcr_s(stream);
-#define PCR_FPS_BQ(PPv) \
-  hipLaunchKernelGGL((fps_bq_wave_kernel<PPv>), dim3(B), dim3(64), 0, st, xyz, temp, idx, new_xyz, cnt, r4, N, M, block, logb, max_r2, K)
-  if (N <= 128) PCR_FPS_BQ(1);
-  else if (N <= 256) PCR_FPS_BQ(2);
-  else if (N <= 512) PCR_FPS_BQ(4);
-  else PCR_FPS_BQ(8);
-#undef PCR_FPS_BQ
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  const dim3 g(B), b(64);
+  if (N <= 128) return pcr_launch<fps_bq_wave_kernel<1>>(g, b, 0, st, xyz, temp, idx, new_xyz, cnt, r4, N, M, block, logb, max_r2, K);
+  if (N <= 256) return pcr_launch<fps_bq_wave_kernel<2>>(g, b, 0, st, xyz, temp, idx, new_xyz, cnt, r4, N, M, block, logb, max_r2, K);
+  if (N <= 512) return pcr_launch<fps_bq_wave_kernel<4>>(g, b, 0, st, xyz, temp, idx, new_xyz, cnt, r4, N, M, block, logb, max_r2, K);
+  return pcr_launch<fps_bq_wave_kernel<8>>(g, b, 0, st, xyz, temp, idx, new_xyz, cnt, r4, N, M, block, logb, max_r2, K);
 }
 
 PCR_EXPORT int pcr_knn_f32(const float *xyz, const float *centres, int *idx, float *dist2, int B,
@@ -1840,10 +1808,8 @@ PCR_EXPORT int pcr_knn_f32(const float *xyz, const float *centres, int *idx, flo
   if (B == 0 || M == 0) return PCR_OK;
   if (B > 65535) return PCR_ERR_INVALID;
   size_t lds = (size_t)2 * K * 64 * 4 + 3 * kKnnTile * 4;
-  hipLaunchKernelGGL(knn_heap_kernel, dim3((M + 63) / 64, B), dim3(64), lds, pcr_s(stream), xyz,
-                     centres, idx, dist2, N, M, K);
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  return pcr_launch<knn_heap_kernel>(dim3((M + 63) / 64, B), dim3(64), lds, pcr_s(stream), xyz,
+                                     centres, idx, dist2, N, M, K);
 }
 
 PCR_EXPORT int pcr_gather_fwd_f32(const float *feat, const int *idx, float *out, int B, int C,
@@ -1873,10 +1839,8 @@ PCR_EXPORT int pcr_three_nn_f32(const float *unknown, const float *known, float 
   if (!unknown || !known || !dist2 || !idx || B < 0 || N < 0 || M < 1) return PCR_ERR_INVALID;
   if (B == 0 || N == 0) return PCR_OK;
   if (B > 65535) return PCR_ERR_INVALID;
-  hipLaunchKernelGGL(three_nn_kernel, dim3((N + 255) / 256, B), dim3(256), 0, pcr_s(stream),
-                     unknown, known, dist2, idx, N, M);
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  return pcr_launch<three_nn_kernel>(dim3((N + 255) / 256, B), dim3(256), 0, pcr_s(stream),
+                                     unknown, known, dist2, idx, N, M);
 }
 
 PCR_EXPORT int pcr_three_interp_fwd_f32(const float *feat, const int *idx, const float *weight,
@@ -1887,10 +1851,8 @@ PCR_EXPORT int pcr_three_interp_fwd_f32(const float *feat, const int *idx, const
   if (total == 0) return PCR_OK;
   size_t blocks = (total + 255) / 256;
   if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(three_interp_fwd_kernel, dim3((unsigned)blocks), dim3(256), 0, pcr_s(stream),
-                     feat, idx, weight, out, C, M, N, total);
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  return pcr_launch<three_interp_fwd_kernel>(dim3((unsigned)blocks), dim3(256), 0, pcr_s(stream),
+                                             feat, idx, weight, out, C, M, N, total);
 }
 
 PCR_EXPORT int pcr_three_interp_bwd_f32(const float *grad_out, const int *idx, const float *weight,
@@ -1904,11 +1866,10 @@ PCR_EXPORT int pcr_three_interp_bwd_f32(const float *grad_out, const int *idx, c
   if (blocks > 8192) blocks = 8192;
   // entries e = 3 n + j scatter grad_out[n] * weight[n][j] to idx[n][j]: owner-computes (deterministic) when the
   // accumulators fit LDS, the atomic kernel otherwise
-  if (!scatter_owner_launch(grad_out, idx, weight, grad_feat, B, C, M, 3 * N, 3, pcr_s(stream)))
-    hipLaunchKernelGGL(three_interp_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, pcr_s(stream),
-                       grad_out, idx, weight, grad_feat, C, N, M, total);
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  const int rc = scatter_owner_launch(grad_out, idx, weight, grad_feat, B, C, M, 3 * N, 3, pcr_s(stream));
+  if (rc >= 0) return rc;
+  return pcr_launch<three_interp_bwd_kernel>(dim3((unsigned)blocks), dim3(256), 0, pcr_s(stream), grad_out, idx, weight,
+                                             grad_feat, C, N, M, total);
 }
 
 static int knn_prefix_launch(const float *xyz, int *idx, int B, int N, int S, int K, int *idx2, int S2, int K2,
@@ -1923,13 +1884,11 @@ static int knn_prefix_launch(const float *xyz, int *idx, int B, int N, int S, in
   dim3 g((S + qpw - 1) / qpw, B), blk(kKnnPThreads);
   size_t lds = (size_t)(3 * N + (N & 1)) * sizeof(float);
   hipStream_t st = pcr_s(stream);
-#define PCR_KNN_REG(TP)                                                                                  \
-  hipLaunchKernelGGL((knn_prefix_reg_kernel<TP>), g, blk,                                                \
-                     lds + (size_t)4 * (kKnnCap + 64) * 8, st, xyz, idx, N, S, K, qpw, idx2, S2, K2)
-  if (N <= 128) PCR_KNN_REG(1);
-  else if (N <= 256) PCR_KNN_REG(2);
-  else if (N <= 512) PCR_KNN_REG(4);
-  else {
+  const size_t lds_reg = lds + (size_t)4 * (kKnnCap + 64) * 8;
+  if (N <= 128) return pcr_launch<knn_prefix_reg_kernel<1>>(g, blk, lds_reg, st, xyz, idx, N, S, K, qpw, idx2, S2, K2);
+  if (N <= 256) return pcr_launch<knn_prefix_reg_kernel<2>>(g, blk, lds_reg, st, xyz, idx, N, S, K, qpw, idx2, S2, K2);
+  if (N <= 512) return pcr_launch<knn_prefix_reg_kernel<4>>(g, blk, lds_reg, st, xyz, idx, N, S, K, qpw, idx2, S2, K2);
+  {
     // sixteen waves share one copy of the cloud in LDS (4 waves per SIMD already at one workgroup per CU)
     constexpr int NT = 1024;
     // queries per workgroup of the LDS form: 512 for clouds of more than 2048 points when that still leaves four workgroups
@@ -1938,25 +1897,15 @@ static int knn_prefix_launch(const float *xyz, int *idx, int B, int N, int S, in
     // (May look at B: the output is an index list, the same whatever the split.)
     const int qpw_l = (N > 2048 && (long)((S + 511) / 512) * B >= 1024) ? 512 : 128;
     const dim3 gl((S + qpw_l - 1) / qpw_l, B);
-    if (N <= 1024) {
-      PCR_KNN_REG(8);   // (the two-pass LDS form measures 1.79 ms against 1.60 here: registers win while they fit)
-    } else if (N <= 2048) {
+    // (the two-pass LDS form measures 1.79 ms against 1.60 at N <= 1024: registers win while they fit)
+    if (N <= 1024) return pcr_launch<knn_prefix_reg_kernel<8>>(g, blk, lds_reg, st, xyz, idx, N, S, K, qpw, idx2, S2, K2);
+    if (N <= 2048) {
       lds = (size_t)64 * 32 * 12 + (size_t)(NT / 64) * kKnnCap * 8;
-      static bool big = hipFuncSetAttribute(reinterpret_cast<const void *>(knn_prefix_lds_kernel<32, NT>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess;
-      (void)big;
-      hipLaunchKernelGGL((knn_prefix_lds_kernel<32, NT>), gl, dim3(NT), lds, st, xyz, idx, N, S, K, qpw_l, idx2, S2, K2);
-    } else {
-      lds = (size_t)64 * 64 * 12 + (size_t)(NT / 64) * kKnnCap * 8;
-      static bool big = hipFuncSetAttribute(reinterpret_cast<const void *>(knn_prefix_lds_kernel<64, NT>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess;
-      (void)big;
-      hipLaunchKernelGGL((knn_prefix_lds_kernel<64, NT>), gl, dim3(NT), lds, st, xyz, idx, N, S, K, qpw_l, idx2, S2, K2);
+      return pcr_launch_lds<knn_prefix_lds_kernel<32, NT>>(gl, dim3(NT), lds, st, xyz, idx, N, S, K, qpw_l, idx2, S2, K2);
     }
+    lds = (size_t)64 * 64 * 12 + (size_t)(NT / 64) * kKnnCap * 8;
+    return pcr_launch_lds<knn_prefix_lds_kernel<64, NT>>(gl, dim3(NT), lds, st, xyz, idx, N, S, K, qpw_l, idx2, S2, K2);
   }
-#undef PCR_KNN_REG
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
 }
 
 PCR_EXPORT int pcr_knn_prefix_f32(const float *xyz, int *idx, int B, int N, int S, int K, pcr_stream_t stream) {

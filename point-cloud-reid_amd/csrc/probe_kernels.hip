@@ -53,9 +53,5 @@ PCR_EXPORT int pcr_wall_clock_khz(void) {
 
 PCR_EXPORT int pcr_clock_probe(unsigned long long *ticks, int n_wg, int iters, pcr_stream_t stream) {
   if (!ticks || n_wg < 1 || iters < 1) return PCR_ERR_INVALID;
-  static bool ok = allow_big_lds(clock_probe_kernel);
-  (void)ok;
-  hipLaunchKernelGGL(clock_probe_kernel, dim3(n_wg), dim3(256), 128 * 1024, pcr_s(stream), ticks, iters);
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  return pcr_launch_lds<clock_probe_kernel>(dim3(n_wg), dim3(256), 128 * 1024, pcr_s(stream), ticks, iters);
 }

@@ -448,6 +448,45 @@ inline bool sas_claims(int c1, int c3, int N) {
 }
 constexpr int kTraceWgs = 1024, kTraceTiles = 24, kTraceMarks = 8;
 __device__ unsigned long long g_rag_trace[kTraceWgs * (2 + kTraceTiles * kTraceMarks)];
+constexpr int kSasWaves = 8;
+
+// ---- launch shapes: ONE definition of each rule, read by sa2_try in all three units and by the f32 unit's exported shape
+// queries (what engine.py asks before it builds row tables, tables with the coordinate term and workspaces)
+// the "ways" class of a layer of n 32-channel cout blocks
+static int sa_ways(int n) { return n >= 3 ? 1 : (n == 2 ? 2 : 4); }
+// rows of a tile of the ragged tile kernel: 64 when a layer has more than four cout blocks
+static int sa_tile_rows(int c2, int c3) { return (ceil32(c2) > 128 || ceil32(c3) > 128) ? 64 : 128; }
+// the ragged tile kernel's explicit-shape instantiations, the only ones the bf16 units hold
+static bool sa_tile_shape_ok(int c2, int c3) {
+  const int v2 = sa_ways(ceil32(c2) >> 5), v3 = sa_ways(ceil32(c3) >> 5);
+  if (sa_tile_rows(c2, c3) == 64) return v2 == 1 && v3 == 1;
+  return (v2 == 1 && v3 == 1) || (v2 == 2 && v3 == 1) || (v2 == 2 && v3 == 2) || (v2 == 4 && v3 == 4);
+}
+// the cout-split form (sa_wsplit_rag_kernel, bf16 units): 128 / 128 / 256 on 64-row tiles
+static bool sa_wsplit_shape(int c1, int c2, int c3, int K) { return c1 == 128 && c2 == 128 && c3 == 256 && K >= 1 && K <= 64; }
+// Wave-autonomous forms (sa_stream_kernel / sa_stream_rag_kernel): K in whole 16-row groups, at most three 32-row blocks
+// per item.  Their LDS: the staged weights and shifts, then one area per wave.
+static bool sas_k_ok(int K) {
+  if (K < 1) return false;
+  for (int nb = 1; nb <= 3; nb++)
+    if ((32 * nb) % K == 0) return (K & 15) == 0;
+  return false;
+}
+static size_t sas_fixed_lds(int c1, int c3) {
+  const int ncb = c1 >> 5, ncb3 = c3 >> 5;
+  return ((size_t)(2 * ncb) * ncb * 128 + (size_t)(2 * ncb) * ncb3 * 128) * 16 + (size_t)(2 * c1 + c3) * 4 + (size_t)ncb * 64 * 16;
+}
+static size_t sas_krow_lds(int c1, int c3) { return sas_fixed_lds(c1, c3) + (size_t)kSasWaves * 6 * c3 * 4 + 16; }   // (+ the four MFMA tokens)
+static size_t sas_rag_lds(int c1, int c3, int K, int waves, bool tab) {
+  return sas_fixed_lds(c1, c3) + (size_t)waves * sas_rag_wave_ints(c3, K, tab) * 4;
+}
+// Equal widths of 32 / 64 / 128 for layers 1 / 2, c3 = c2 or 2 c2, weights + per-wave areas within LDS.  Ball-query layers
+// (mode 1) can run either form depending on whether hit counts are given, and the tests hold the two to the same bits:
+// such a layer streams only when BOTH forms fit, so both always share one arithmetic.
+static bool sas_shape(int c1, int c2, int c3, int K, bool both_forms) {
+  if (c1 != c2 || !(c3 == c2 || c3 == 2 * c2) || !(c1 == 32 || c1 == 64 || c1 == 128) || !sas_k_ok(K)) return false;
+  return sas_krow_lds(c1, c3) <= (size_t)kMaxDynLds && (!both_forms || sas_rag_lds(c1, c3, K, kSasWaves, false) <= (size_t)kMaxDynLds);
+}
 
 #if PCR_SA_PREC != 0
 // ---- wave-autonomous K-row kernel: c1 = c2 = c3 = 32 NCB (the Point-Transformer's kNN-grouped SA layers), K % 16 == 0,
@@ -461,7 +500,6 @@ __device__ unsigned long long g_rag_trace[kTraceWgs * (2 + kTraceTiles * kTraceM
 // Work item = lcm(32, K) rows of one cloud (K = 48: three blocks = two centres): the group maxima of an item meet in a
 // wave-private LDS strip, the item's centres leave from there.  Items of a cloud stay on one XCD (its table rows are
 // gathered by every item of the cloud: one L2 should hold them).
-constexpr int kSasWaves = 8;
 constexpr int kSasCpi = 16;   // centres per item of the ragged form
 
 // the three layers of one 32-row block, shared by the K-row and the ragged form.  In: the row's neighbour i, its centre
@@ -2242,19 +2280,14 @@ void dense_pm_xyz_res_kernel(DensePmArgs a, int tpc, long ntile) {
 }  // namespace
 
 template <int TB, int NR, int W2, int W3, int NR2 = NR, int RKB = 0>
-static void sa2_launch_one(const Sa2Args &a, bool maxe, size_t lds, hipStream_t st, dim3 grid) {
+static int sa2_launch_one(const Sa2Args &a, bool maxe, size_t lds, hipStream_t st, dim3 grid) {
   // bf16 forms: layers whose first layer runs on the matrix core (NR2 == 1; the launcher has checked a.l1m) keep their
   // activations as bf images
   constexpr bool kImgK = kPrec != 0 && NR2 == 1;
-  if (maxe) {
-    static bool ok = allow_big_lds(sa_fused_kernel<TB, NR, W2, W3, true, NR2, RKB, kPrec, kImgK>);
-    (void)ok;
-    hipLaunchKernelGGL((sa_fused_kernel<TB, NR, W2, W3, true, NR2, RKB, kPrec, kImgK>), grid, dim3(kThreads), lds, st, a);
-  } else if constexpr (kPrec == 0) {
-    static bool ok = allow_big_lds(sa_fused_kernel<TB, NR, W2, W3, false, NR2, RKB, kPrec>);
-    (void)ok;
-    hipLaunchKernelGGL((sa_fused_kernel<TB, NR, W2, W3, false, NR2, RKB, kPrec>), grid, dim3(kThreads), lds, st, a);
-  }
+  if (maxe) return pcr_launch_lds<sa_fused_kernel<TB, NR, W2, W3, true, NR2, RKB, kPrec, kImgK>>(grid, dim3(kThreads), lds, st, a);
+  if constexpr (kPrec == 0)
+    return pcr_launch_lds<sa_fused_kernel<TB, NR, W2, W3, false, NR2, RKB, kPrec>>(grid, dim3(kThreads), lds, st, a);
+  return PCR_OK;
 }
 
 // wsel: 1 / 2 / 4 when both MFMA layers have the same cout class (specialised bodies), else 0
@@ -2272,27 +2305,27 @@ static int sa2_launch_tb(const Sa2Args &a, int nr, int nr2, int w2, int w3, bool
     (void)narrow4;
     if (!maxe || nr > 2) return -1;
     if (nr2 == 1 && !a.l1m) return -1;     // (the one-round instantiations are the bf-image ones: layer 1 on the matrix core)
-    if (wsel == 44) sa2_launch_one<TB, 1, 4, 4>(a, maxe, lds, st, grid);
-    else if (wsel == 22) sa2_launch_one<TB, 1, 2, 2>(a, maxe, lds, st, grid);
-    else if (wsel == 21) sa2_launch_one<TB, 1, 2, 1>(a, maxe, lds, st, grid);
-    else if (wsel == 11 && nr == 1) sa2_launch_one<TB, 1, 1, 1>(a, maxe, lds, st, grid);
-    else if (wsel == 11 && nr2 == 1) sa2_launch_one<TB, 2, 1, 1, 1>(a, maxe, lds, st, grid);
-    else if (wsel == 11) sa2_launch_one<TB, 2, 1, 1>(a, maxe, lds, st, grid);
+    if (wsel == 44) return sa2_launch_one<TB, 1, 4, 4>(a, maxe, lds, st, grid);
+    else if (wsel == 22) return sa2_launch_one<TB, 1, 2, 2>(a, maxe, lds, st, grid);
+    else if (wsel == 21) return sa2_launch_one<TB, 1, 2, 1>(a, maxe, lds, st, grid);
+    else if (wsel == 11 && nr == 1) return sa2_launch_one<TB, 1, 1, 1>(a, maxe, lds, st, grid);
+    else if (wsel == 11 && nr2 == 1) return sa2_launch_one<TB, 2, 1, 1, 1>(a, maxe, lds, st, grid);
+    else if (wsel == 11) return sa2_launch_one<TB, 2, 1, 1>(a, maxe, lds, st, grid);
     else return -1;
     return 0;
   } else {
   if (nr == 4) {
-    if constexpr (TB <= 2) sa2_launch_one<TB, 4, 1, 1, 4>(a, maxe, lds, st, grid);
+    if constexpr (TB <= 2) return sa2_launch_one<TB, 4, 1, 1, 4>(a, maxe, lds, st, grid);
     else return -1;
-  } else if (wsel == 4 && narrow4) sa2_launch_one<TB, 1, 4, 4, 1, 4>(a, maxe, lds, st, grid);
-  else if (wsel == 4) sa2_launch_one<TB, 1, 4, 4>(a, maxe, lds, st, grid);
-  else if (wsel == 2) sa2_launch_one<TB, 1, 2, 2>(a, maxe, lds, st, grid);
-  else if (wsel == 1 && nr == 1) sa2_launch_one<TB, 1, 1, 1>(a, maxe, lds, st, grid);
-  else if (wsel == 1 && nr2 == 1) sa2_launch_one<TB, 2, 1, 1, 1>(a, maxe, lds, st, grid);
-  else if (wsel == 1) sa2_launch_one<TB, 2, 1, 1>(a, maxe, lds, st, grid);
-  else if (nr == 1) sa2_launch_one<TB, 1, 0, 0>(a, maxe, lds, st, grid);
-  else if (nr2 == 1) sa2_launch_one<TB, 2, 0, 0, 1>(a, maxe, lds, st, grid);
-  else sa2_launch_one<TB, 2, 0, 0>(a, maxe, lds, st, grid);
+  } else if (wsel == 4 && narrow4) return sa2_launch_one<TB, 1, 4, 4, 1, 4>(a, maxe, lds, st, grid);
+  else if (wsel == 4) return sa2_launch_one<TB, 1, 4, 4>(a, maxe, lds, st, grid);
+  else if (wsel == 2) return sa2_launch_one<TB, 1, 2, 2>(a, maxe, lds, st, grid);
+  else if (wsel == 1 && nr == 1) return sa2_launch_one<TB, 1, 1, 1>(a, maxe, lds, st, grid);
+  else if (wsel == 1 && nr2 == 1) return sa2_launch_one<TB, 2, 1, 1, 1>(a, maxe, lds, st, grid);
+  else if (wsel == 1) return sa2_launch_one<TB, 2, 1, 1>(a, maxe, lds, st, grid);
+  else if (nr == 1) return sa2_launch_one<TB, 1, 0, 0>(a, maxe, lds, st, grid);
+  else if (nr2 == 1) return sa2_launch_one<TB, 2, 0, 0, 1>(a, maxe, lds, st, grid);
+  else return sa2_launch_one<TB, 2, 0, 0>(a, maxe, lds, st, grid);
   return 0;
   }
 }
@@ -2328,30 +2361,40 @@ int pcr_sa2_try_bf3(const pcr_sa_params *p, pcr_stream_t st);   // sa_kernels_bf
 int pcr_sa2_try_bf1(const pcr_sa_params *p, pcr_stream_t st);
 #endif
 
+// the ragged tile kernel, persistent: as many workgroups as are resident on the chip (registers and LDS), at most one per tile
+template <int TB, int NR, int A2, int A3, int NR2, int W1>
+static int rag_launch(const RagArgs &r, size_t lds, long long max_tiles, hipStream_t st, const char *rtrace) {
+  constexpr auto kern = sa_rag_kernel<TB, NR, A2, A3, NR2, W1, kPrec>;
+  allow_big_lds<kern>();   // (before the occupancy query)
+  static size_t occ_lds = 0;
+  static int occ = 0;   // resident workgroups per CU for this LDS size
+  if (occ_lds != lds) {
+    int n = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kern, kThreads, lds) != hipSuccess || n < 1) n = 1;
+    occ = n;
+    occ_lds = lds;
+  }
+  long long want = (long long)pcr_cu_count() * occ;
+  if (want > max_tiles) want = max_tiles;
+  const int rc = pcr_launch_lds<kern>(dim3((unsigned)want), dim3(kThreads), lds, st, r);
+  if (rtrace) rag_dump_trace(rtrace, TB == 2 ? "2,2" : "4,1", (int)want);
+  return rc;
+}
+
 #if PCR_SA_PREC != 0
-// shapes of the wave-autonomous forms (sa_stream_kernel / sa_stream_rag_kernel).  Ball-query layers (mode 1) can run
-// either form depending on whether hit counts are given, and the tests hold the two to the same bits: such a layer
-// streams only when BOTH forms fit, so both always share one arithmetic.
-static bool sas_k_ok(int K) {
-  for (int nb = 1; nb <= 3; nb++)
-    if ((32 * nb) % K == 0) return (K & 15) == 0;
-  return false;
+template <int NCB, int NCB3>
+static int sasr_launch(bool w12, dim3 gg, dim3 bb, size_t lds_r8, size_t lds_r12, hipStream_t st, const RagArgs &r) {
+  constexpr bool kLoS = kPrec == 1;
+  if (w12) return pcr_launch_lds<sa_stream_rag_kernel<NCB, NCB3, kLoS, true, 12>>(gg, bb, lds_r12, st, r);
+  if (r.rowtab) return pcr_launch_lds<sa_stream_rag_kernel<NCB, NCB3, kLoS, true>>(gg, bb, lds_r8, st, r);
+  return pcr_launch_lds<sa_stream_rag_kernel<NCB, NCB3, kLoS>>(gg, bb, lds_r8, st, r);
 }
-static size_t sas_fixed_lds(const pcr_sa_params &p) {
-  const int ncb = p.c1 >> 5, ncb3 = p.c3 >> 5;
-  return ((size_t)(2 * ncb) * ncb * 128 + (size_t)(2 * ncb) * ncb3 * 128) * 16 + (size_t)(2 * p.c1 + p.c3) * 4 + (size_t)ncb * 64 * 16;
-}
+
 static bool sas_shape_ok(const pcr_sa_params &p, bool ragged) {
   static const int no_stream = pcr_tune_int("PCR_SA_NO_STREAM");   // diagnostics
-  if (no_stream || p.B < 1 || !p.wa_packed || p.c1 != p.c2 || !(p.c3 == p.c2 || p.c3 == 2 * p.c2) ||
-      !(p.c1 == 32 || p.c1 == 64 || p.c1 == 128) || !sas_k_ok(p.K))
-    return false;
-  const size_t lds_k = sas_fixed_lds(p) + (size_t)kSasWaves * 6 * p.c3 * 4 + 16;
-  const size_t lds_r = sas_fixed_lds(p) + (size_t)kSasWaves * sas_rag_wave_ints(p.c3, p.K, false) * 4;
-  const size_t cap = (size_t)160 * 1024;
+  if (no_stream || p.B < 1 || !p.wa_packed) return false;
   if ((long)p.B * p.S >= 0x7FFFFFFFl) return false;    // (the kernels count items in 32 bits)
-  if (ragged || p.mode == 1) return lds_k <= cap && lds_r <= cap;
-  return lds_k <= cap;
+  return sas_shape(p.c1, p.c2, p.c3, p.K, ragged || p.mode == 1);
 }
 #endif
 
@@ -2382,29 +2425,17 @@ static int sa2_try(const pcr_sa_params &p, pcr_stream_t st_) {
   // weights is faster there: 2.2 vs 2.9 ms on the 32-channel kNN layer, its row tables are 0.5 GB of extra traffic.)
   // (the cout-split kernel's shape also takes count-less launches -- all K rows of every centre -- through the same tile
   // plan, so that ragged and K-row evaluation of that layer share one kernel and one arithmetic)
-  const bool wsplit_shape = kPrec != 0 && p.c1 == 128 && p.c2 == 128 && p.c3 == 256 && p.wa_shift_packed && p.K <= 64 &&
+  const bool wsplit_shape = kPrec != 0 && sa_wsplit_shape(p.c1, p.c2, p.c3, p.K) && p.wa_shift_packed &&
                             (size_t)p.B * ((p.S + (64 / rag_ceil(p.K)) - 1) / (64 / rag_ceil(p.K))) * 64 * 16 < 0x7FFFFFFFull;
   if (p.tile_ws && (p.cnt || wsplit_shape) && p.mode == 1 && p.c1 <= 256 && p.c2 <= 256 && p.c3 <= 256) {
     const int n2r = ceil32(p.c2) >> 5, n3r = ceil32(p.c3) >> 5;
-    const int nrr = (n2r > 4 || n3r > 4) ? 2 : 1;
-    const int tb = nrr == 2 ? 2 : 4;
-    const int ROWS = 32 * tb;
-    bool shape_ok = true;
-    if (kPrec != 0) {   // the bf16 units hold the explicit-shape instantiations only
-      const int v2 = n2r >= 3 ? 1 : (n2r == 2 ? 2 : 4), v3 = n3r >= 3 ? 1 : (n3r == 2 ? 2 : 4);
-      shape_ok = tb == 2 ? (v2 == 1 && v3 == 1)
-                         : ((v2 == 1 && v3 == 1) || (v2 == 2 && v3 == 1) || (v2 == 2 && v3 == 2) || (v2 == 4 && v3 == 4));
-    }
-    if (!shape_ok) return -1;
+    const int ROWS = sa_tile_rows(p.c2, p.c3), tb = ROWS / 32;
+    if (kPrec != 0 && !sa_tile_shape_ok(p.c2, p.c3)) return -1;
 #if PCR_SA_PREC != 0
     {
       // wave-autonomous ragged form (shape-only choice, the same shapes as the K-row form so that both paths share one
       // arithmetic): equal widths of layers 1 / 2, c3 = c2 or 2 c2, weights + per-wave areas within LDS
-      static const int no_stream = pcr_tune_int("PCR_SA_NO_STREAM");
       const int ncb = p.c1 >> 5, ncb3 = p.c3 >> 5;
-      const size_t fixed = ((size_t)(2 * ncb) * ncb * 128 + (size_t)(2 * ncb) * ncb3 * 128) * 16 + (size_t)(2 * p.c1 + p.c3) * 4 +
-                           (size_t)ncb * 64 * 16;
-      (void)no_stream;
       if (sas_shape_ok(p, true)) {
         if (p.D && !p.pq_ready) {
           const int rc = pcr_dense_pm_f32(p.feat, p.wpq, p.pq_ws, p.B, p.D, p.c1, p.N, p.feat_point_major, st_);
@@ -2420,43 +2451,23 @@ static int sa2_try(const pcr_sa_params &p, pcr_stream_t st_) {
         r.wp2 = wl2; r.wp3 = wl3; r.sh1 = p.shift[0]; r.sh2 = p.shift_pad[0]; r.sh3 = p.shift_pad[1];
         static const char *strace = pcr_tune_str("PCR_SA_TRACE");
         r.dbg = strace ? 256 : 0; r.out = p.out; r.out_pm = p.out_point_major;
-        static const int ncu = [] {
-          int dev = 0, n = 0;
-          if (hipGetDevice(&dev) != hipSuccess ||
-              hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 8)
-            n = 256;
-          return n;
-        }();
         const long items = (long)p.B * ((p.S + kSasCpi - 1) / kSasCpi);
-        const size_t cap = (size_t)160 * 1024;
-        const size_t lds_r8 = fixed + (size_t)8 * sas_rag_wave_ints(p.c3, p.K, r.rowtab != nullptr) * 4;
-        const size_t lds_r12 = fixed + (size_t)12 * sas_rag_wave_ints(p.c3, p.K, true) * 4;
+        const size_t lds_r8 = sas_rag_lds(p.c1, p.c3, p.K, 8, r.rowtab != nullptr);
+        const size_t lds_r12 = sas_rag_lds(p.c1, p.c3, p.K, 12, true);
         static const int no12 = pcr_tune_int("PCR_SA_NO_W12");   // diagnostics
-        const bool w12 = r.rowtab && lds_r12 <= cap && !no12;    // three waves per SIMD (see the kernel)
+        const bool w12 = r.rowtab && lds_r12 <= (size_t)kMaxDynLds && !no12;    // three waves per SIMD (see the kernel)
         const int nw = w12 ? 12 : 8;
         long wgs = (items + nw - 1) / nw;
-        if (wgs > ncu) wgs = ncu;
+        if (wgs > pcr_cu_count()) wgs = pcr_cu_count();
         wgs = (wgs + 7) / 8 * 8;
         const dim3 gg((unsigned)wgs), bb(64 * nw);
-        constexpr bool kLoS = kPrec == 1;
-#define PCR_SASR(NCBv, NCB3v)                                                                 \
-  do {                                                                                        \
-    static bool ok = allow_big_lds(sa_stream_rag_kernel<NCBv, NCB3v, kLoS>);                  \
-    static bool okt = allow_big_lds(sa_stream_rag_kernel<NCBv, NCB3v, kLoS, true>);           \
-    static bool okw = allow_big_lds(sa_stream_rag_kernel<NCBv, NCB3v, kLoS, true, 12>);       \
-    (void)ok; (void)okt; (void)okw;                                                           \
-    if (w12) hipLaunchKernelGGL((sa_stream_rag_kernel<NCBv, NCB3v, kLoS, true, 12>), gg, bb, lds_r12, st, r); \
-    else if (r.rowtab) hipLaunchKernelGGL((sa_stream_rag_kernel<NCBv, NCB3v, kLoS, true>), gg, bb, lds_r8, st, r); \
-    else hipLaunchKernelGGL((sa_stream_rag_kernel<NCBv, NCB3v, kLoS>), gg, bb, lds_r8, st, r); \
-  } while (0)
-        if (ncb == 1 && ncb3 == 1) PCR_SASR(1, 1);
-        else if (ncb == 1) PCR_SASR(1, 2);
-        else if (ncb3 == 2) PCR_SASR(2, 2);
-        else PCR_SASR(2, 4);
-#undef PCR_SASR
+        int rc;
+        if (ncb == 1 && ncb3 == 1) rc = sasr_launch<1, 1>(w12, gg, bb, lds_r8, lds_r12, st, r);
+        else if (ncb == 1) rc = sasr_launch<1, 2>(w12, gg, bb, lds_r8, lds_r12, st, r);
+        else if (ncb3 == 2) rc = sasr_launch<2, 2>(w12, gg, bb, lds_r8, lds_r12, st, r);
+        else rc = sasr_launch<2, 4>(w12, gg, bb, lds_r8, lds_r12, st, r);
         if (strace) rag_dump_trace(strace, "stream", (int)(2 * wgs));
-        if (hipGetLastError() != hipSuccess) return PCR_ERR_LAUNCH;
-        return PCR_OK;
+        return rc;
       }
     }
 #endif
@@ -2486,84 +2497,52 @@ static int sa2_try(const pcr_sa_params &p, pcr_stream_t st_) {
           const int rc = pcr_dense_pm_f32(p.feat, p.wpq, p.pq_ws, p.B, p.D, p.c1, p.N, p.feat_point_major, st_);
           if (rc != PCR_OK) return rc == PCR_ERR_INVALID ? -1 : rc;
         }
-        hipLaunchKernelGGL(sa_rag_plan_kernel, dim3((p.B + 3) / 4), dim3(256), 0, st, r, ROWS);
-        hipLaunchKernelGGL(sa_rag_scan_kernel, dim3(1), dim3(1024), 0, st, p.B, r.ws);
-        hipLaunchKernelGGL(sa_rag_flatten_kernel, dim3((p.B + 3) / 4), dim3(256), 0, st, p.B, r.maxT, r.ws);
-        {
-          long long wgs = ((long long)p.B * r.maxT + 3) / 4;
-          if (wgs > 4096) wgs = 4096;
-          if (tb == 2) hipLaunchKernelGGL(sa_rag_rows_kernel<64>, dim3((unsigned)wgs), dim3(256), 0, st, r);
-          else hipLaunchKernelGGL(sa_rag_rows_kernel<128>, dim3((unsigned)wgs), dim3(256), 0, st, r);
-        }
-        if (hipGetLastError() != hipSuccess) return PCR_ERR_LAUNCH;
-        static const int n_cu = [] {
-          int dev = 0, n = 0;
-          if (hipGetDevice(&dev) != hipSuccess ||
-              hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1)
-            n = 256;
-          return n;
-        }();
+        long long wgs_rows = ((long long)p.B * r.maxT + 3) / 4;
+        if (wgs_rows > 4096) wgs_rows = 4096;
+        int rc = pcr_launch<sa_rag_plan_kernel>(dim3((p.B + 3) / 4), dim3(256), 0, st, r, ROWS);
+        if (rc == PCR_OK) rc = pcr_launch<sa_rag_scan_kernel>(dim3(1), dim3(1024), 0, st, p.B, r.ws);
+        if (rc == PCR_OK) rc = pcr_launch<sa_rag_flatten_kernel>(dim3((p.B + 3) / 4), dim3(256), 0, st, p.B, r.maxT, r.ws);
+        if (rc == PCR_OK)
+          rc = tb == 2 ? pcr_launch<sa_rag_rows_kernel<64>>(dim3((unsigned)wgs_rows), dim3(256), 0, st, r)
+                       : pcr_launch<sa_rag_rows_kernel<128>>(dim3((unsigned)wgs_rows), dim3(256), 0, st, r);
+        if (rc != PCR_OK) return rc;
         const long long max_tiles = (long long)p.B * r.maxT;
-        const int w2 = n2r >= 3 ? 1 : (n2r == 2 ? 2 : 4), w3 = n3r >= 3 ? 1 : (n3r == 2 ? 2 : 4);
+        const int w2 = sa_ways(n2r), w3 = sa_ways(n3r);
 #if PCR_SA_PREC != 0
         {
           // cout-split form with register-resident weights (shape-only choice): 128 / 128 / 256 on 64-row tiles
           static const int no_wsplit = pcr_tune_int("PCR_SA_NO_WSPLIT");   // diagnostics
           if (!no_wsplit && tb == 2 && wsplit_shape) {
             constexpr bool kLoW = kPrec == 1;
-            static bool okw = allow_big_lds(sa_wsplit_rag_kernel<4, 8, kLoW>);
-            (void)okw;
             const size_t lds_w = ((size_t)3 * 128 * 64 + (size_t)32 * 256 + 2 * 128 + 64) * sizeof(float);   // X1 x 2, X2, obuf, seeds, coff
-            long long want = n_cu;                                           // persistent: one 8-wave workgroup per CU
+            long long want = pcr_cu_count();                                 // persistent: one 8-wave workgroup per CU
             if (want > max_tiles) want = max_tiles;
-            hipLaunchKernelGGL((sa_wsplit_rag_kernel<4, 8, kLoW>), dim3((unsigned)want), dim3(512), lds_w, st, r);
+            rc = pcr_launch_lds<sa_wsplit_rag_kernel<4, 8, kLoW>>(dim3((unsigned)want), dim3(512), lds_w, st, r);
             if (rtrace) rag_dump_trace(rtrace, "wsplit", (int)(2 * want));
-            if (hipGetLastError() != hipSuccess) return PCR_ERR_LAUNCH;
-            return PCR_OK;
+            return rc;
           }
         }
 #endif
-#define PCR_RAG(TBv, NRv, A2, A3, NR2v, W1v)                                                             \
-  do {                                                                                                   \
-    auto kern = sa_rag_kernel<TBv, NRv, A2, A3, NR2v, W1v, kPrec>;                                       \
-    static bool ok = allow_big_lds(kern);                                                                \
-    (void)ok;                                                                                            \
-    static size_t occ_lds = 0;                                                                           \
-    static int occ = 0;   /* resident workgroups per CU for this LDS size (registers and LDS) */          \
-    if (occ_lds != lds) {                                                                                \
-      int n = 0;                                                                                         \
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kern, kThreads, lds) != hipSuccess || n < 1)  \
-        n = 1;                                                                                           \
-      occ = n;                                                                                           \
-      occ_lds = lds;                                                                                     \
-    }                                                                                                    \
-    long long want = (long long)n_cu * occ;                                                              \
-    if (want > max_tiles) want = max_tiles;                                                              \
-    hipLaunchKernelGGL(kern, dim3((unsigned)want), dim3(kThreads), lds, st, r);                          \
-    if (rtrace) rag_dump_trace(rtrace, #TBv "," #NRv, (int)want);                                        \
-  } while (0)
         const int n1r = ceil32(p.c1) >> 5;
-        const int w1 = n1r >= 3 ? 1 : (n1r == 2 ? 2 : 4);
+        const int w1 = sa_ways(n1r);
         const bool l1m = p.wa_packed && n1r <= 4;   // layer 1 on the matrix core
         if (tb == 2) {
           const bool narrow2 = n2r <= 4;   // layer 2 needs one cout-block round only
-          if (w2 == 1 && w3 == 1 && narrow2 && l1m && w1 == 1) PCR_RAG(2, 2, 1, 1, 1, 1);
-          else if (w2 == 1 && w3 == 1 && narrow2) PCR_RAG(2, 2, 1, 1, 1, 0);
-          else if (w2 == 1 && w3 == 1) PCR_RAG(2, 2, 1, 1, 2, 0);
+          if (w2 == 1 && w3 == 1 && narrow2 && l1m && w1 == 1) return rag_launch<2, 2, 1, 1, 1, 1>(r, lds, max_tiles, st, rtrace);
+          else if (w2 == 1 && w3 == 1 && narrow2) return rag_launch<2, 2, 1, 1, 1, 0>(r, lds, max_tiles, st, rtrace);
+          else if (w2 == 1 && w3 == 1) return rag_launch<2, 2, 1, 1, 2, 0>(r, lds, max_tiles, st, rtrace);
           else if constexpr (kPrec == 0) {
-            if (narrow2) PCR_RAG(2, 2, 0, 0, 1, 0);
-            else PCR_RAG(2, 2, 0, 0, 2, 0);
+            if (narrow2) return rag_launch<2, 2, 0, 0, 1, 0>(r, lds, max_tiles, st, rtrace);
+            else return rag_launch<2, 2, 0, 0, 2, 0>(r, lds, max_tiles, st, rtrace);
           }
         } else {
-          if (w2 == 1 && w3 == 1) PCR_RAG(4, 1, 1, 1, 1, 0);
-          else if (w2 == 2 && w3 == 1 && l1m && w1 == 2 && !p.D) PCR_RAG(4, 1, 2, 1, 1, 2);
-          else if (w2 == 2 && w3 == 1) PCR_RAG(4, 1, 2, 1, 1, 0);
-          else if (w2 == 2 && w3 == 2) PCR_RAG(4, 1, 2, 2, 1, 0);
-          else if (w2 == 4 && w3 == 4) PCR_RAG(4, 1, 4, 4, 1, 0);
-          else if constexpr (kPrec == 0) PCR_RAG(4, 1, 0, 0, 1, 0);
+          if (w2 == 1 && w3 == 1) return rag_launch<4, 1, 1, 1, 1, 0>(r, lds, max_tiles, st, rtrace);
+          else if (w2 == 2 && w3 == 1 && l1m && w1 == 2 && !p.D) return rag_launch<4, 1, 2, 1, 1, 2>(r, lds, max_tiles, st, rtrace);
+          else if (w2 == 2 && w3 == 1) return rag_launch<4, 1, 2, 1, 1, 0>(r, lds, max_tiles, st, rtrace);
+          else if (w2 == 2 && w3 == 2) return rag_launch<4, 1, 2, 2, 1, 0>(r, lds, max_tiles, st, rtrace);
+          else if (w2 == 4 && w3 == 4) return rag_launch<4, 1, 4, 4, 1, 0>(r, lds, max_tiles, st, rtrace);
+          else if constexpr (kPrec == 0) return rag_launch<4, 1, 0, 0, 1, 0>(r, lds, max_tiles, st, rtrace);
         }
-#undef PCR_RAG
-        if (hipGetLastError() != hipSuccess) return PCR_ERR_LAUNCH;
         return PCR_OK;
       }
     }
@@ -2579,13 +2558,13 @@ static int sa2_try(const pcr_sa_params &p, pcr_stream_t st_) {
   };
   const int n2 = ceil32(p.c2) >> 5, n3 = ceil32(p.c3) >> 5;
   const int nmin = n2 < n3 ? n2 : n3;
-  const int ways = nmin >= 3 ? 1 : (nmin == 2 ? 2 : 4);
+  const int ways = sa_ways(nmin);
   // cout-block rounds per wave: 2 for 129-256 couts, 4 for 257-512 (the 1.5M / 7M Point-Transformer configs'
   // 256- / 512-channel layers, backbone_net.py:43-46); the four-round form is instantiated for both layers together
   const int nr = (n2 > 8 || n3 > 8) ? 4 : ((n2 > 4 || n3 > 4) ? 2 : 1);
   const int nr2 = nr == 4 ? 4 : (n2 > 4 ? 2 : 1);
   if (kPrec != 0) {   // the bf16 units: max-from-accumulators epilogue, explicit shapes, at most two cout-block rounds
-    const int v2 = n2 >= 3 ? 1 : (n2 == 2 ? 2 : 4), v3 = n3 >= 3 ? 1 : (n3 == 2 ? 2 : 4);
+    const int v2 = sa_ways(n2), v3 = sa_ways(n3);
     if (!maxe || nr > 2 || !((v2 == v3) || (v2 == 2 && v3 == 1))) return -1;
   }
   // Tile choice.  Measured on MI355X (re-fitted after the epilogue / k-loop work, which halved what
@@ -2640,8 +2619,8 @@ static int sa2_try(const pcr_sa_params &p, pcr_stream_t st_) {
   {
     static const int no_l1m = pcr_tune_int("PCR_SA_NO_L1M");   // diagnostics
     const int n1 = ceil32(p.c1) >> 5;
-    const int w1 = n1 >= 3 ? 1 : (n1 == 2 ? 2 : 4);
-    const int w2c = n2 >= 3 ? 1 : (n2 == 2 ? 2 : 4), w3c = n3 >= 3 ? 1 : (n3 == 2 ? 2 : 4);
+    const int w1 = sa_ways(n1);
+    const int w2c = sa_ways(n2), w3c = sa_ways(n3);
     // (the kernel deals layer 1's tiles with layer 2's compile-time shape: explicit shapes only, same class)
     // (f32 forms are instantiated for equal classes of layers 2 and 3 only; the bf16 units also hold (2, 1))
     a.l1m = (!no_l1m && p.wa_packed && n1 <= 4 && n2 <= 4 && w1 == w2c && (kPrec != 0 || w2c == w3c) && (p.c1 & 3) == 0) ? 1 : 0;
@@ -2650,7 +2629,6 @@ static int sa2_try(const pcr_sa_params &p, pcr_stream_t st_) {
   {
     // wave-autonomous form (shape-only choice): equal widths of 32 / 64 / 128, K in whole 16-row groups, at most three
     // 32-row blocks per item (K = 16, 32, 48, 64, 96)
-    static const int no_stream = pcr_tune_int("PCR_SA_NO_STREAM");   // diagnostics
     const int ncb = p.c1 >> 5, ncb3 = p.c3 >> 5;
     int nblk_item = 0, ncen_item = 0;
     // (the LARGEST item of whole centres within three blocks: K = 32 / 16 take three blocks = 3 / 6 centres per item, so the
@@ -2658,21 +2636,11 @@ static int sa2_try(const pcr_sa_params &p, pcr_stream_t st_) {
     static const int small_items = pcr_tune_int("PCR_SAS_SMALL_ITEMS");   // diagnostics: the smallest item instead
     for (int nb = 3; nb >= 1; nb--)
       if ((32 * nb) % p.K == 0 && (!nblk_item || small_items)) { nblk_item = nb; ncen_item = 32 * nb / p.K; }
-    const size_t fixed = ((size_t)(2 * ncb) * ncb * 128 + (size_t)(2 * ncb) * ncb3 * 128) * 16 + (size_t)(2 * p.c1 + p.c3) * 4 +
-                         (size_t)ncb * 64 * 16;
-    const size_t lds_s = fixed + (size_t)kSasWaves * 6 * p.c3 * 4 + 16;   // (+ the four MFMA tokens)
-    (void)no_stream;
+    const size_t lds_s = sas_krow_lds(p.c1, p.c3);
     if (maxe && nblk_item && sas_shape_ok(p, false)) {
-      static const int ncu = [] {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 8)
-          n = 256;
-        return n;
-      }();
       const long items = (long)p.B * ((p.S + ncen_item - 1) / ncen_item);
       long wgs = (items + kSasWaves - 1) / kSasWaves;
-      const long resident = (long)ncu * ((ncb + ncb3 >= 6 || lds_s > (size_t)80 * 1024) ? 1 : 2);
+      const long resident = (long)pcr_cu_count() * ((ncb + ncb3 >= 6 || lds_s > (size_t)80 * 1024) ? 1 : 2);
       if (wgs > resident) wgs = resident;
       wgs = (wgs + 7) / 8 * 8;                         // every XCD gets workgroups (the item order is per XCD)
       const dim3 gg((unsigned)wgs), bb(64 * kSasWaves);
@@ -2684,28 +2652,21 @@ static int sa2_try(const pcr_sa_params &p, pcr_stream_t st_) {
       if (p.pq_has_xyz && !a.xt) return PCR_ERR_INVALID;
       a.claim = (p.claim_ws && sas_claims(p.c1, p.c3, p.N) && !(a.dbg & 4096)) ? p.claim_ws : nullptr;
       if (a.claim && hipMemsetAsync(a.claim, 0, (size_t)kSasClaimInts * sizeof(int), st) != hipSuccess) return PCR_ERR_LAUNCH;
-#define PCR_SAS(NCBv, NCB3v)                                                                  \
-  do {                                                                                        \
-    static bool ok = allow_big_lds(sa_stream_kernel<NCBv, NCB3v, kLoS>);                      \
-    (void)ok;                                                                                 \
-    hipLaunchKernelGGL((sa_stream_kernel<NCBv, NCB3v, kLoS>), gg, bb, lds_s, st, a, nblk_item, ncen_item); \
-  } while (0)
-      if (ncb == 1 && ncb3 == 1) PCR_SAS(1, 1);
-      else if (ncb == 1) PCR_SAS(1, 2);
-      else if (ncb == 2 && ncb3 == 2) PCR_SAS(2, 2);
-      else if (ncb == 2) PCR_SAS(2, 4);
-      else PCR_SAS(4, 4);
-#undef PCR_SAS
+      int rc;
+      if (ncb == 1 && ncb3 == 1) rc = pcr_launch_lds<sa_stream_kernel<1, 1, kLoS>>(gg, bb, lds_s, st, a, nblk_item, ncen_item);
+      else if (ncb == 1) rc = pcr_launch_lds<sa_stream_kernel<1, 2, kLoS>>(gg, bb, lds_s, st, a, nblk_item, ncen_item);
+      else if (ncb == 2 && ncb3 == 2) rc = pcr_launch_lds<sa_stream_kernel<2, 2, kLoS>>(gg, bb, lds_s, st, a, nblk_item, ncen_item);
+      else if (ncb == 2) rc = pcr_launch_lds<sa_stream_kernel<2, 4, kLoS>>(gg, bb, lds_s, st, a, nblk_item, ncen_item);
+      else rc = pcr_launch_lds<sa_stream_kernel<4, 4, kLoS>>(gg, bb, lds_s, st, a, nblk_item, ncen_item);
       if (ktrace) rag_dump_trace(ktrace, "krow", (int)(2 * wgs));
-      if (hipGetLastError() != hipSuccess) return PCR_ERR_LAUNCH;
-      return PCR_OK;
+      return rc;
     }
   }
 #endif
   if (p.pq_has_xyz) return PCR_ERR_INVALID;   // (tables with the coordinate term: the K-row kernel above is their only reader)
   const size_t lds = lds_bytes(best_tb, best_cpw);
   dim3 grid((p.S + best_cpw - 1) / best_cpw, p.B);
-  const int w2 = n2 >= 3 ? 1 : (n2 == 2 ? 2 : 4), w3 = n3 >= 3 ? 1 : (n3 == 2 ? 2 : 4);
+  const int w2 = sa_ways(n2), w3 = sa_ways(n3);
   int lrc = 0;
   switch (best_tb) {
     case 1: lrc = sa2_launch_tb<1>(a, nr, nr2, w2, w3, maxe, lds, st, grid); break;
@@ -2715,9 +2676,7 @@ static int sa2_try(const pcr_sa_params &p, pcr_stream_t st_) {
     case 5: lrc = sa2_launch_tb<5>(a, nr, nr2, w2, w3, maxe, lds, st, grid); break;
     default: lrc = sa2_launch_tb<6>(a, nr, nr2, w2, w3, maxe, lds, st, grid); break;
   }
-  if (lrc < 0) return -1;
-  if (hipGetLastError() != hipSuccess) return PCR_ERR_LAUNCH;
-  return PCR_OK;
+  return lrc < 0 ? -1 : lrc;
 }
 
 #if PCR_SA_PREC == 1
@@ -2726,40 +2685,23 @@ int pcr_sa2_try_bf3(const pcr_sa_params *p, pcr_stream_t st) { return sa2_try(*p
 int pcr_sa2_try_bf1(const pcr_sa_params *p, pcr_stream_t st) { return sa2_try(*p, st); }
 #else
 
-// 1: launches of this shape WITHOUT hit counts (all K rows of every group) also run on the tile plan and want the
-// workspace of pcr_sa_tile_ws_ints -- the cout-split kernel's shape, sa2_try's `wsplit_shape` (bf16 modes)
 // does a ball-query layer with hit counts of this shape read the ball query's row table (pcr_ball_query_rows_f32)?
 // = the wave-autonomous ragged form runs it (sas_shape_ok, shape only)
 PCR_EXPORT int pcr_sa_uses_row_table(int c1, int c2, int c3, int K, int precision) {
-  if (precision == 0 || c1 != c2 || !(c3 == c2 || c3 == 2 * c2) || !(c1 == 32 || c1 == 64 || c1 == 128)) return 0;
-  bool kok = false;
-  for (int nb = 1; nb <= 3; nb++)
-    if ((32 * nb) % K == 0) { kok = (K & 15) == 0; break; }
-  if (!kok) return 0;
-  const int ncb = c1 >> 5, ncb3 = c3 >> 5;
-  {   // (sa2_try asks for a tile-kernel instantiation of the shape before it looks at the wave-autonomous form)
-    const int v2 = ncb >= 3 ? 1 : (ncb == 2 ? 2 : 4), v3 = ncb3 >= 3 ? 1 : (ncb3 == 2 ? 2 : 4);
-    if (!((v2 == 1 && v3 == 1) || (v2 == 2 && v3 == 1) || (v2 == 2 && v3 == 2) || (v2 == 4 && v3 == 4))) return 0;
-  }
-  const size_t fixed = ((size_t)(2 * ncb) * ncb * 128 + (size_t)(2 * ncb) * ncb3 * 128) * 16 + (size_t)(2 * c1 + c3) * 4 +
-                       (size_t)ncb * 64 * 16;
-  const size_t cap = (size_t)160 * 1024;
-  return fixed + (size_t)8 * 6 * c3 * 4 <= cap && fixed + (size_t)8 * sas_rag_wave_ints(c3, K, false) * 4 <= cap;
+  // (sa2_try asks for a tile-kernel instantiation of the shape before it looks at the wave-autonomous form)
+  return precision != 0 && sa_tile_shape_ok(c2, c3) && sas_shape(c1, c2, c3, K, true);
 }
 
+// 1: launches of this shape WITHOUT hit counts (all K rows of every group) also run on the tile plan and want the
+// workspace of pcr_sa_tile_ws_ints -- the cout-split kernel's shape, sa2_try's `wsplit_shape` (bf16 modes)
 PCR_EXPORT int pcr_sa_krow_uses_tiles(int c1, int c2, int c3, int K, int precision) {
-  return precision != 0 && c1 == 128 && c2 == 128 && c3 == 256 && K >= 1 && K <= 64;
+  return precision != 0 && sa_wsplit_shape(c1, c2, c3, K);
 }
 
 // sa2_try's K-row dispatch for the shapes whose tables may carry the coordinate term (pcr_sa_params.pq_has_xyz)
 PCR_EXPORT int pcr_sa_tables_take_xyz(int mode, int D, int c1, int c2, int c3, int K, int precision) {
   static const int no_stream = pcr_tune_int("PCR_SA_NO_STREAM"), no_xt = pcr_tune_int("PCR_SA_NO_XYZ_TABLES");   // diagnostics
-  if (no_stream || no_xt || precision == 0 || mode != 0 || D < 1 || c1 != c2 || c2 != c3 || !(c1 == 32 || c1 == 64 || c1 == 128))
-    return 0;
-  if (K < 16 || (K & 15) || !(32 % K == 0 || 64 % K == 0 || 96 % K == 0)) return 0;
-  const int ncb = c1 >> 5;
-  const size_t fixed = ((size_t)(2 * ncb) * ncb * 128 * 2) * 16 + (size_t)(3 * c1) * 4 + (size_t)ncb * 64 * 16;
-  return fixed + (size_t)8 * 6 * c3 * 4 + 16 <= (size_t)160 * 1024;
+  return !no_stream && !no_xt && precision != 0 && mode == 0 && D >= 1 && c2 == c3 && sas_shape(c1, c2, c3, K, false);
 }
 
 PCR_EXPORT long pcr_sa_claim_ws_ints(int c1, int c2, int c3, int K, int N, int precision) {
@@ -2770,11 +2712,26 @@ PCR_EXPORT long pcr_sa_claim_ws_ints(int c1, int c2, int c3, int K, int N, int p
 
 PCR_EXPORT long pcr_sa_tile_ws_ints(int B, int S, int K, int c2, int c3) {
   if (B < 1 || S < 1 || K < 1 || c2 < 1 || c3 < 1) return 0;
-  const int rows = (ceil32(c2) > 128 || ceil32(c3) > 128) ? 64 : 128;   // sa2_try's tile choice
+  const int rows = sa_tile_rows(c2, c3);
   if (K > rows) return 0;
   const int per_tile = rows / rag_ceil(K);
   const int maxT = (S + per_tile - 1) / per_tile;
   return (long)rag_ws_ints(B, maxT, rows);
+}
+
+// the persistent dense_pm forms' fan-out over their template shapes
+template <int NS, int NPI>
+static int dense_pm_res_launch(bool cout128, dim3 g, dim3 b, size_t lds, hipStream_t st, const DensePmArgs &d, long ntile) {
+  return cout128 ? pcr_launch<dense_pm_res_kernel<NS, NPI, 8>>(g, b, lds, st, d, ntile)
+                 : pcr_launch<dense_pm_res_kernel<NS, NPI, 4>>(g, b, lds, st, d, ntile);
+}
+template <int NS>
+static int dense_pm_xyz_res_launch(int cin, int cout, dim3 g, dim3 b, size_t lds, hipStream_t st, const DensePmArgs &d, int tpc,
+                                   long ntile) {
+  if (cin == 32 && cout == 128) return pcr_launch_lds<dense_pm_xyz_res_kernel<NS, 2, 8>>(g, b, lds, st, d, tpc, ntile);
+  if (cin == 32) return pcr_launch_lds<dense_pm_xyz_res_kernel<NS, 2, 16>>(g, b, lds, st, d, tpc, ntile);
+  if (cout == 128) return pcr_launch_lds<dense_pm_xyz_res_kernel<NS, 4, 8>>(g, b, lds, st, d, tpc, ntile);
+  return pcr_launch_lds<dense_pm_xyz_res_kernel<NS, 4, 16>>(g, b, lds, st, d, tpc, ntile);
 }
 
 static int dense_pm_launch(const float *x, const float *wp, float *y, int B, int cin, int cout, int L, int x_point_major,
@@ -2795,38 +2752,19 @@ static int dense_pm_launch(const float *x, const float *wp, float *y, int B, int
     const long ntok = (long)B * L;
     if (!no_res && !xyz && precision != 0 && x_point_major && (cin == 32 || cin == 64 || cin == 128) && (cout == 64 || cout == 128) &&
         ntok % 64 == 0 && (reinterpret_cast<size_t>(x) & 15) == 0 && (reinterpret_cast<size_t>(y) & 15) == 0) {
-      static const int ncu = [] {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1)
-          n = 256;
-        return n;
-      }();
       const long ntile = ntok / 64;
-      const long res = (long)ncu * (cin == 128 ? 2 : 4);   // (the kernel's registers: two or four workgroups per CU)
+      const long res = (long)pcr_cu_count() * (cin == 128 ? 2 : 4);   // (the kernel's registers: two or four workgroups per CU)
       const long wgs = ntile < res ? ntile : res;
       const size_t lds_r = (size_t)(cin > cout ? cin : cout) * 65 * sizeof(float);
-#define PCR_PMR(NSv, NPIv, NPOv)                                                                      \
-  hipLaunchKernelGGL((dense_pm_res_kernel<NSv, NPIv, NPOv>), dim3((unsigned)wgs), dim3(kThreads), lds_r, \
-                     pcr_s(stream), d, ntile)
-#define PCR_PMR_O(NSv, NPIv)                             \
-  do {                                                   \
-    if (cout == 128) PCR_PMR(NSv, NPIv, 8);              \
-    else PCR_PMR(NSv, NPIv, 4);                          \
-  } while (0)
-#define PCR_PMR_I(NSv)                                   \
-  do {                                                   \
-    if (cin == 128) PCR_PMR_O(NSv, 8);                   \
-    else if (cin == 64) PCR_PMR_O(NSv, 4);               \
-    else PCR_PMR_O(NSv, 2);                              \
-  } while (0)
-      if (precision == 1) PCR_PMR_I(3);
-      else PCR_PMR_I(1);
-#undef PCR_PMR_I
-#undef PCR_PMR_O
-#undef PCR_PMR
-      PCR_CHECK_LAUNCH();
-      return PCR_OK;
+      const dim3 g((unsigned)wgs), b(kThreads);
+      const hipStream_t st = pcr_s(stream);
+      if (precision == 1)
+        return cin == 128 ? dense_pm_res_launch<3, 8>(cout == 128, g, b, lds_r, st, d, ntile)
+             : cin == 64  ? dense_pm_res_launch<3, 4>(cout == 128, g, b, lds_r, st, d, ntile)
+                          : dense_pm_res_launch<3, 2>(cout == 128, g, b, lds_r, st, d, ntile);
+      return cin == 128 ? dense_pm_res_launch<1, 8>(cout == 128, g, b, lds_r, st, d, ntile)
+           : cin == 64  ? dense_pm_res_launch<1, 4>(cout == 128, g, b, lds_r, st, d, ntile)
+                        : dense_pm_res_launch<1, 2>(cout == 128, g, b, lds_r, st, d, ntile);
     }
   }
   if (xyz && !x_point_major && (cin == 32 || cin == 64) && (cout == 128 || cout == 256) && (L & 63) == 0 &&
@@ -2835,38 +2773,15 @@ static int dense_pm_launch(const float *x, const float *wp, float *y, int B, int
     // channel-major input, whole tiles per cloud: the persistent form with the coordinate term (shape-only choice)
     static const int no_res = pcr_tune_int("PCR_DENSE_PM_NO_RES");   // diagnostics
     if (!no_res) {
-      static const int ncu = [] {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1)
-          n = 256;
-        return n;
-      }();
       const int tpc = L / 64;
       const long ntile = (long)B * tpc;
-      const long res = (long)ncu * (cout == 256 ? 2 : 3);     // (the kernel's registers: two or three workgroups per CU)
+      const long res = (long)pcr_cu_count() * (cout == 256 ? 2 : 3);     // (the kernel's registers: two or three workgroups per CU)
       const long wgs = ntile < res ? ntile : res;
       const size_t lds_r = ((size_t)cout * 65 + 3 * 64) * sizeof(float);
-#define PCR_PMX(NSv, NPIv, NPOv)                                                                            \
-  do {                                                                                                      \
-    static bool ok = allow_big_lds(dense_pm_xyz_res_kernel<NSv, NPIv, NPOv>);                               \
-    (void)ok;                                                                                               \
-    hipLaunchKernelGGL((dense_pm_xyz_res_kernel<NSv, NPIv, NPOv>), dim3((unsigned)wgs), dim3(kThreads), lds_r, \
-                       pcr_s(stream), d, tpc, ntile);                                                       \
-  } while (0)
-#define PCR_PMX_S(NSv)                                      \
-  do {                                                      \
-    if (cin == 32 && cout == 128) PCR_PMX(NSv, 2, 8);       \
-    else if (cin == 32) PCR_PMX(NSv, 2, 16);                \
-    else if (cout == 128) PCR_PMX(NSv, 4, 8);               \
-    else PCR_PMX(NSv, 4, 16);                               \
-  } while (0)
-      if (precision == 1) PCR_PMX_S(3);
-      else PCR_PMX_S(1);
-#undef PCR_PMX_S
-#undef PCR_PMX
-      PCR_CHECK_LAUNCH();
-      return PCR_OK;
+      const dim3 g((unsigned)wgs), b(kThreads);
+      const hipStream_t st = pcr_s(stream);
+      return precision == 1 ? dense_pm_xyz_res_launch<3>(cin, cout, g, b, lds_r, st, d, tpc, ntile)
+                            : dense_pm_xyz_res_launch<1>(cin, cout, g, b, lds_r, st, d, tpc, ntile);
     }
   }
   const int wmax = cout < 256 ? cout : 256;
@@ -2874,24 +2789,16 @@ static int dense_pm_launch(const float *x, const float *wp, float *y, int B, int
   size_t lds = (size_t)rows * 65 * sizeof(float) + (xyz ? (size_t)(3 * 64 + 4 * wmax) * sizeof(float) : 0);
   if (lds > (size_t)kMaxDynLds) return PCR_ERR_INVALID;
   const dim3 grid((L + 63) / 64, B, (cout + 255) / 256);
-#define PCR_PM(NRv, PRv)                                                                          \
-  do {                                                                                            \
-    static bool ok = allow_big_lds(dense_pm_kernel<NRv, PRv>);                                    \
-    (void)ok;                                                                                     \
-    hipLaunchKernelGGL((dense_pm_kernel<NRv, PRv>), grid, dim3(kThreads), lds, pcr_s(stream), d); \
-  } while (0)
+  const dim3 b(kThreads);
+  const hipStream_t st = pcr_s(stream);
   if (cout > 128) {
-    if (precision == 0) PCR_PM(2, 0);
-    else if (precision == 1) PCR_PM(2, 1);
-    else PCR_PM(2, 2);
-  } else {
-    if (precision == 0) PCR_PM(1, 0);
-    else if (precision == 1) PCR_PM(1, 1);
-    else PCR_PM(1, 2);
+    if (precision == 0) return pcr_launch_lds<dense_pm_kernel<2, 0>>(grid, b, lds, st, d);
+    if (precision == 1) return pcr_launch_lds<dense_pm_kernel<2, 1>>(grid, b, lds, st, d);
+    return pcr_launch_lds<dense_pm_kernel<2, 2>>(grid, b, lds, st, d);
   }
-#undef PCR_PM
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  if (precision == 0) return pcr_launch_lds<dense_pm_kernel<1, 0>>(grid, b, lds, st, d);
+  if (precision == 1) return pcr_launch_lds<dense_pm_kernel<1, 1>>(grid, b, lds, st, d);
+  return pcr_launch_lds<dense_pm_kernel<1, 2>>(grid, b, lds, st, d);
 }
 
 PCR_EXPORT int pcr_dense_pm_f32(const float *x, const float *wp, float *y, int B, int cin, int cout, int L,
@@ -2949,11 +2856,6 @@ PCR_EXPORT int pcr_sa_mlp_f32(const pcr_sa_params *pp, pcr_stream_t stream) {
     if (lds <= 150 * 1024 || cpw == 1) break;
   }
   if (lds > (size_t)kMaxDynLds) return PCR_ERR_INVALID;
-  static bool ok = allow_big_lds(sa_mlp_kernel);
-  (void)ok;
-  hipLaunchKernelGGL(sa_mlp_kernel, dim3((p.S + a.CPW - 1) / a.CPW, p.B), dim3(kThreads), lds,
-                     pcr_s(stream), a);
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  return pcr_launch_lds<sa_mlp_kernel>(dim3((p.S + a.CPW - 1) / a.CPW, p.B), dim3(kThreads), lds, pcr_s(stream), a);
 }
 #endif   // PCR_SA_PREC == 0 (C-ABI entry points)

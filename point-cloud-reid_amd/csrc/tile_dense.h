@@ -29,7 +29,6 @@ constexpr int kThreads = 256;
 #ifndef PCR_PF
 #define PCR_PF 2
 #endif
-constexpr int kMaxDynLds = 160 * 1024;
 
 // out[o][t] = epi(sum_k W[o][k] * in[k][t], o, t) for o < OP (multiple of 32), t < 32*TB.
 //   in : LDS [CP][RP], CP multiple of 8, rows >= real cin must be ZERO
@@ -857,12 +856,6 @@ __device__ __forceinline__ void load_tile_pm(float *dst, int RP, const float *sr
       }
     }
   }
-}
-
-template <class Kern>
-bool allow_big_lds(Kern k) {
-  return hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                             kMaxDynLds) == hipSuccess;
 }
 
 }  // namespace

@@ -873,14 +873,12 @@ PCR_EXPORT int pcr_tnorm_fwd_f32(const float *x, const float *gamma, const float
   const unsigned nb = (unsigned)(((size_t)B * L + 63) / 64);
   const int gs = C / G;
   switch ((gs & 3) == 0 ? gs / 4 : 0) {
-    case 8: hipLaunchKernelGGL(tnorm_fwd4_kernel<8>, dim3(nb, G), dim3(256), 0, pcr_s(stream), a, B); break;
-    case 16: hipLaunchKernelGGL(tnorm_fwd4_kernel<16>, dim3(nb, G), dim3(256), 0, pcr_s(stream), a, B); break;
-    case 32: hipLaunchKernelGGL(tnorm_fwd4_kernel<32>, dim3(nb, G), dim3(256), 0, pcr_s(stream), a, B); break;
-    case 64: hipLaunchKernelGGL(tnorm_fwd4_kernel<64>, dim3(nb, G), dim3(256), 0, pcr_s(stream), a, B); break;
-    default: hipLaunchKernelGGL(tnorm_fwd_kernel, dim3(nb, G), dim3(64), 0, pcr_s(stream), a, B);
+    case 8: return pcr_launch<tnorm_fwd4_kernel<8>>(dim3(nb, G), dim3(256), 0, pcr_s(stream), a, B);
+    case 16: return pcr_launch<tnorm_fwd4_kernel<16>>(dim3(nb, G), dim3(256), 0, pcr_s(stream), a, B);
+    case 32: return pcr_launch<tnorm_fwd4_kernel<32>>(dim3(nb, G), dim3(256), 0, pcr_s(stream), a, B);
+    case 64: return pcr_launch<tnorm_fwd4_kernel<64>>(dim3(nb, G), dim3(256), 0, pcr_s(stream), a, B);
+    default: return pcr_launch<tnorm_fwd_kernel>(dim3(nb, G), dim3(64), 0, pcr_s(stream), a, B);
   }
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
 }
 
 PCR_EXPORT int pcr_tnorm_bwd_f32(const float *g, const float *x, const float *gamma, const float *mean, const float *rstd,
@@ -894,14 +892,12 @@ PCR_EXPORT int pcr_tnorm_bwd_f32(const float *g, const float *x, const float *ga
   const unsigned nb = (unsigned)(((size_t)B * L + 63) / 64);
   const int gs = C / G;
   switch ((gs & 3) == 0 ? gs / 4 : 0) {
-    case 8: hipLaunchKernelGGL(tnorm_bwd4_kernel<8>, dim3(nb, G), dim3(256), 0, pcr_s(stream), a, B); break;
-    case 16: hipLaunchKernelGGL(tnorm_bwd4_kernel<16>, dim3(nb, G), dim3(256), 0, pcr_s(stream), a, B); break;
-    case 32: hipLaunchKernelGGL(tnorm_bwd4_kernel<32>, dim3(nb, G), dim3(256), 0, pcr_s(stream), a, B); break;
-    case 64: hipLaunchKernelGGL(tnorm_bwd4_kernel<64>, dim3(nb, G), dim3(256), 0, pcr_s(stream), a, B); break;
-    default: hipLaunchKernelGGL(tnorm_bwd_kernel, dim3(nb, G), dim3(64), 0, pcr_s(stream), a, B);
+    case 8: return pcr_launch<tnorm_bwd4_kernel<8>>(dim3(nb, G), dim3(256), 0, pcr_s(stream), a, B);
+    case 16: return pcr_launch<tnorm_bwd4_kernel<16>>(dim3(nb, G), dim3(256), 0, pcr_s(stream), a, B);
+    case 32: return pcr_launch<tnorm_bwd4_kernel<32>>(dim3(nb, G), dim3(256), 0, pcr_s(stream), a, B);
+    case 64: return pcr_launch<tnorm_bwd4_kernel<64>>(dim3(nb, G), dim3(256), 0, pcr_s(stream), a, B);
+    default: return pcr_launch<tnorm_bwd_kernel>(dim3(nb, G), dim3(64), 0, pcr_s(stream), a, B);
   }
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
 }
 
 static int linattn_check(const pcr_linattn *p) {
@@ -926,21 +922,19 @@ PCR_EXPORT int pcr_linattn_fwd_f32(const pcr_linattn *p, pcr_stream_t stream) {
   if (p->B == 0) return PCR_OK;
   if (p->B > 65535) return PCR_ERR_INVALID;
   const LinAttn a = linattn_args(p);
+  int rc = PCR_OK;
   dh_dispatch(p->d / p->H, [&](auto tag) {
     constexpr int DH = decltype(tag)::value;
     if constexpr (DH == 32 || DH == 64) {
-      hipLaunchKernelGGL(linattn_fwd_mfma_kernel<DH>, dim3(p->H, p->B), dim3(256), 0, pcr_s(stream), a);
+      rc = pcr_launch<linattn_fwd_mfma_kernel<DH>>(dim3(p->H, p->B), dim3(256), 0, pcr_s(stream), a);
     } else {
       // scalar form: 16-wide heads, and the 128-wide ones (d_model 256: the mul = 2 configs) with 16-token chunks
       constexpr int KAT = DH == 128 ? 16 : kAT;
       const size_t lds = (2 * (size_t)DH * (KAT + 1) + (size_t)DH * (DH + 1) + DH + KAT) * sizeof(float);
-      static bool ok = allow_big_lds(linattn_fwd_kernel<DH, KAT>);
-      (void)ok;
-      hipLaunchKernelGGL((linattn_fwd_kernel<DH, KAT>), dim3(p->H, p->B), dim3(256), lds, pcr_s(stream), a);
+      rc = pcr_launch_lds<linattn_fwd_kernel<DH, KAT>>(dim3(p->H, p->B), dim3(256), lds, pcr_s(stream), a);
     }
   });
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  return rc;
 }
 
 PCR_EXPORT int pcr_linattn_bwd_f32(const pcr_linattn *p, pcr_stream_t stream) {
@@ -948,55 +942,43 @@ PCR_EXPORT int pcr_linattn_bwd_f32(const pcr_linattn *p, pcr_stream_t stream) {
   if (p->B == 0) return PCR_OK;
   if (p->B > 65535) return PCR_ERR_INVALID;
   const LinAttn a = linattn_args(p);
+  int rc = PCR_OK;
   dh_dispatch(p->d / p->H, [&](auto tag) {
     constexpr int DH = decltype(tag)::value;
     constexpr int KAT = DH == 128 ? 16 : kAT;
     const size_t lds = (3 * (size_t)DH * (KAT + 1) + 2 * (size_t)DH * (DH + 1) + 2 * DH + 2 * KAT) * sizeof(float);
     if constexpr (DH == 32 || DH == 64) {
-      static bool ok = allow_big_lds(linattn_bwd_mfma_kernel<DH>);
-      (void)ok;
-      hipLaunchKernelGGL(linattn_bwd_mfma_kernel<DH>, dim3(p->H, p->B), dim3(256), lds, pcr_s(stream), a);
+      rc = pcr_launch_lds<linattn_bwd_mfma_kernel<DH>>(dim3(p->H, p->B), dim3(256), lds, pcr_s(stream), a);
     } else {
-      static bool ok = allow_big_lds(linattn_bwd_kernel<DH, KAT>);
-      (void)ok;
-      hipLaunchKernelGGL((linattn_bwd_kernel<DH, KAT>), dim3(p->H, p->B), dim3(256), lds, pcr_s(stream), a);
+      rc = pcr_launch_lds<linattn_bwd_kernel<DH, KAT>>(dim3(p->H, p->B), dim3(256), lds, pcr_s(stream), a);
     }
   });
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  return rc;
 }
 
 PCR_EXPORT int pcr_pool_pair_fwd_f32(const float *o, float *pooled, int *arg, int P, int C, int L, pcr_stream_t stream) {
   if (!o || !pooled || !arg || P < 0 || C < 1 || L < 1) return PCR_ERR_INVALID;
   if (P == 0) return PCR_OK;
-  hipLaunchKernelGGL(pool_pair_fwd_kernel, dim3(P), dim3(256), 0, pcr_s(stream), o, pooled, arg, P, C, L);
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  return pcr_launch<pool_pair_fwd_kernel>(dim3(P), dim3(256), 0, pcr_s(stream), o, pooled, arg, P, C, L);
 }
 
 PCR_EXPORT int pcr_pool_pair_bwd_f32(const float *g, const int *arg, float *dout, int P, int C, int L,
                                      pcr_stream_t stream) {
   if (!g || !arg || !dout || P < 0 || C < 1 || L < 1) return PCR_ERR_INVALID;
   if (P == 0) return PCR_OK;
-  hipLaunchKernelGGL(pool_pair_bwd_kernel, dim3(2 * P * C), dim3(256), 0, pcr_s(stream), g, arg, dout, P, C, L);
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  return pcr_launch<pool_pair_bwd_kernel>(dim3(2 * P * C), dim3(256), 0, pcr_s(stream), g, arg, dout, P, C, L);
 }
 
 PCR_EXPORT int pcr_pool_both_fwd_f32(const float *o, float *pooled, int *arg, int P, int C, int L, pcr_stream_t stream) {
   if (!o || !pooled || !arg || P < 0 || C < 1 || L < 1) return PCR_ERR_INVALID;
   if (P == 0) return PCR_OK;
-  hipLaunchKernelGGL(pool_both_fwd_kernel, dim3(P), dim3(256), 0, pcr_s(stream), o, pooled, arg, C, L);
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  return pcr_launch<pool_both_fwd_kernel>(dim3(P), dim3(256), 0, pcr_s(stream), o, pooled, arg, C, L);
 }
 
 PCR_EXPORT int pcr_pool_both_bwd_f32(const float *g, const int *arg, float *dout, int P, int C, int L, pcr_stream_t stream) {
   if (!g || !arg || !dout || P < 0 || C < 1 || L < 1) return PCR_ERR_INVALID;
   if (P == 0) return PCR_OK;
-  hipLaunchKernelGGL(pool_both_bwd_kernel, dim3(P * C), dim3(256), 0, pcr_s(stream), g, arg, dout, C, L);
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  return pcr_launch<pool_both_bwd_kernel>(dim3(P * C), dim3(256), 0, pcr_s(stream), g, arg, dout, C, L);
 }
 
 PCR_EXPORT int pcr_channel_max_fwd_f32(const float *x, float *y, int *arg, int B, int C, int L, int W, pcr_stream_t stream) {
@@ -1005,9 +987,7 @@ PCR_EXPORT int pcr_channel_max_fwd_f32(const float *x, float *y, int *arg, int B
   const size_t total = (size_t)B * (C / W) * L;
   size_t blocks = (total + 255) / 256;
   if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(channel_max_idx_kernel, dim3((unsigned)blocks), dim3(256), 0, pcr_s(stream), x, y, arg, C, L, W, total);
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  return pcr_launch<channel_max_idx_kernel>(dim3((unsigned)blocks), dim3(256), 0, pcr_s(stream), x, y, arg, C, L, W, total);
 }
 
 PCR_EXPORT int pcr_channel_max_bwd_f32(const float *g, const int *arg, float *dx, int B, int C, int L, int W,
@@ -1017,7 +997,5 @@ PCR_EXPORT int pcr_channel_max_bwd_f32(const float *g, const int *arg, float *dx
   const size_t total = (size_t)B * C * L;
   size_t blocks = (total + 255) / 256;
   if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(channel_max_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, pcr_s(stream), g, arg, dx, C, L, W, total);
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  return pcr_launch<channel_max_bwd_kernel>(dim3((unsigned)blocks), dim3(256), 0, pcr_s(stream), g, arg, dx, C, L, W, total);
 }

@@ -166,10 +166,8 @@ PCR_EXPORT int pcr_edge_pool_fwd_f32(const float *y, const float *scale, const f
   const size_t total = (size_t)B * C * N;
   size_t blocks = (total + 255) / 256;
   if (blocks > 16384) blocks = 16384;
-  hipLaunchKernelGGL(edge_pool_fwd_kernel, dim3((unsigned)blocks), dim3(256), 0, pcr_s(stream), y, scale, shift, slope, pooled,
-                     arg, yraw, C, N, K, total);
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  return pcr_launch<edge_pool_fwd_kernel>(dim3((unsigned)blocks), dim3(256), 0, pcr_s(stream), y, scale, shift, slope, pooled,
+                                          arg, yraw, C, N, K, total);
 }
 
 PCR_EXPORT int pcr_edge_pool_route_f32(const float *gp, const float *pooled, const int *arg, float slope, float *g, int B,
@@ -178,10 +176,8 @@ PCR_EXPORT int pcr_edge_pool_route_f32(const float *gp, const float *pooled, con
   const size_t total = (size_t)B * C * N * K;
   size_t blocks = (total + 255) / 256;
   if (blocks > 16384) blocks = 16384;
-  hipLaunchKernelGGL(edge_pool_route_kernel, dim3((unsigned)blocks), dim3(256), 0, pcr_s(stream), gp, pooled, arg, slope, g, K,
-                     total);
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  return pcr_launch<edge_pool_route_kernel>(dim3((unsigned)blocks), dim3(256), 0, pcr_s(stream), gp, pooled, arg, slope, g, K,
+                                            total);
 }
 
 PCR_EXPORT int pcr_bn_sums_f32(const float *y, const float *g, const float *scale, const float *shift, int relu,
@@ -190,10 +186,8 @@ PCR_EXPORT int pcr_bn_sums_f32(const float *y, const float *g, const float *scal
   if (!y || !part || nparts < 1 || B < 1 || C < 1 || L < 1 || nparts > 65535 || (g && relu && (!scale || !shift)))
     return PCR_ERR_INVALID;
   const int CP = (C + 31) & ~31;
-  hipLaunchKernelGGL(bn_sums_kernel, dim3(C, nparts), dim3(256), 0, pcr_s(stream), y, g, scale, shift, relu, slope,
-                     centre, centre_first, part, B, C, CP, L);
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  return pcr_launch<bn_sums_kernel>(dim3(C, nparts), dim3(256), 0, pcr_s(stream), y, g, scale, shift, relu, slope,
+                                    centre, centre_first, part, B, C, CP, L);
 }
 
 PCR_EXPORT int pcr_bn_affine_f32(const float *y, const float *g, const float *a0, const float *a1, const float *a2,
@@ -204,10 +198,8 @@ PCR_EXPORT int pcr_bn_affine_f32(const float *y, const float *g, const float *a0
   const size_t total = (size_t)B * C * L;
   size_t blocks = (total + 255) / 256;
   if (blocks > 16384) blocks = 16384;
-  hipLaunchKernelGGL(bn_affine_kernel, dim3((unsigned)blocks), dim3(256), 0, pcr_s(stream), y, g, a0, a1, a2, scale, shift,
-                     centre, relu, slope, out, C, L, total);
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  return pcr_launch<bn_affine_kernel>(dim3((unsigned)blocks), dim3(256), 0, pcr_s(stream), y, g, a0, a1, a2, scale, shift,
+                                      centre, relu, slope, out, C, L, total);
 }
 
 PCR_EXPORT int pcr_bmm_apply_f32(const float *x, const float *T, float *y, int B, int k, int N, int transposed,
@@ -216,16 +208,12 @@ PCR_EXPORT int pcr_bmm_apply_f32(const float *x, const float *T, float *y, int B
   if (B == 0) return PCR_OK;
   if (B > 65535) return PCR_ERR_INVALID;
   const size_t lds = (size_t)k * (k + 1) * sizeof(float);
-  hipLaunchKernelGGL(bmm_apply_kernel, dim3((N + 63) / 64, B), dim3(256), lds, pcr_s(stream), x, T, y, k, N, transposed);
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  return pcr_launch<bmm_apply_kernel>(dim3((N + 63) / 64, B), dim3(256), lds, pcr_s(stream), x, T, y, k, N, transposed);
 }
 
 PCR_EXPORT int pcr_bmm_dt_f32(const float *x, const float *dy, float *dT, int B, int k, int N, pcr_stream_t stream) {
   if (!x || !dy || !dT || B < 0 || k < 1 || k > 128 || N < 1) return PCR_ERR_INVALID;
   if (B == 0) return PCR_OK;
   if (B > 65535) return PCR_ERR_INVALID;
-  hipLaunchKernelGGL(bmm_dt_kernel, dim3((k * k + 3) / 4, B), dim3(256), 0, pcr_s(stream), x, dy, dT, k, N);
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  return pcr_launch<bmm_dt_kernel>(dim3((k * k + 3) / 4, B), dim3(256), 0, pcr_s(stream), x, dy, dT, k, N);
 }

@@ -464,16 +464,6 @@ int chain_prec(int precision, int fwd_precision) {
   return precision == PCR_PREC_BF16X3 ? 1 : 0;
 }
 
-int ck_ncu() {
-  static const int n = [] {
-    hipDeviceProp_t pr;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&pr, dev) != hipSuccess) return 256;
-    return pr.multiProcessorCount > 0 ? pr.multiProcessorCount : 256;
-  }();
-  return n;
-}
-
 // the shapes of the reference's blocks: (d_model, c1 = width of the residual / first mlp input, hidden, out)
 //   self (32,32,64,32) (64,64,128,64); cross (64,64,128,64); FP (64,64,128,128) (64,32,128,64) (64,3,128,32)
 #define PCR_TAIL_SHAPES(X) \
@@ -502,8 +492,17 @@ int tail_grid(const pcr_attn_tail *p, bool bwd) {
   if (!in.ok) return 0;
   const long tiles = (long)p->B * ((p->L + kCT - 1) / kCT);
   const long occ = (long)(kMaxDynLds / in.lds) < 1 ? 1 : (long)(kMaxDynLds / in.lds);
-  const long cap = (long)ck_ncu() * (occ > 2 ? 2 : occ);
+  const long cap = (long)pcr_cu_count() * (occ > 2 ? 2 : occ);
   return (int)(tiles < cap ? tiles : cap);
+}
+
+// the arithmetic fan-out of one tail shape (prec: chain_prec)
+template <int D, int C1, int HID, int OUT, bool R, bool BW>
+int tail_go(int prec, int grid, size_t lds, hipStream_t st, const TailArgs &a) {
+  const dim3 g(grid), b(kThreads);
+  if (prec == 3) return pcr_launch_lds<attn_tail_kernel<D, C1, HID, OUT, R, BW, 3>>(g, b, lds, st, a);
+  if (prec == 1 && BW) return pcr_launch_lds<attn_tail_kernel<D, C1, HID, OUT, R, BW, (BW ? 1 : 0)>>(g, b, lds, st, a);
+  return pcr_launch_lds<attn_tail_kernel<D, C1, HID, OUT, R, BW, 0>>(g, b, lds, st, a);
 }
 
 template <int D, int C1, int HID, int OUT>
@@ -519,33 +518,12 @@ int tail_launch(const pcr_attn_tail *p, bool bwd, hipStream_t st) {
   const size_t lds = TailShape<D, C1, HID, OUT>::lds(bwd);
   const bool resid = p->residual != 0;
   const int prec = chain_prec(p->precision, p->fwd_precision);
-#define PCR_TL1(R, BW, PR)                                                                         \
-  do {                                                                                             \
-    static bool ok = allow_big_lds(attn_tail_kernel<D, C1, HID, OUT, R, BW, PR>);                  \
-    (void)ok;                                                                                      \
-    hipLaunchKernelGGL((attn_tail_kernel<D, C1, HID, OUT, R, BW, PR>), dim3(grid), dim3(kThreads), lds, st, a); \
-  } while (0)
-#define PCR_TL(R, BW)                                \
-  do {                                               \
-    if (prec == 3) PCR_TL1(R, BW, 3);                \
-    else if (prec == 1 && BW) PCR_TL1(R, BW, (BW ? 1 : 0)); \
-    else PCR_TL1(R, BW, 0);                          \
-  } while (0)
   if constexpr (OUT == C1) {
-    if (resid) {
-      if (bwd) PCR_TL(true, true);
-      else PCR_TL(true, false);
-      PCR_CHECK_LAUNCH();
-      return PCR_OK;
-    }
+    if (resid)
+      return bwd ? tail_go<D, C1, HID, OUT, true, true>(prec, grid, lds, st, a) : tail_go<D, C1, HID, OUT, true, false>(prec, grid, lds, st, a);
   }
   if (resid) return PCR_ERR_INVALID;
-  if (bwd) PCR_TL(false, true);
-  else PCR_TL(false, false);
-#undef PCR_TL
-#undef PCR_TL1
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  return bwd ? tail_go<D, C1, HID, OUT, false, true>(prec, grid, lds, st, a) : tail_go<D, C1, HID, OUT, false, false>(prec, grid, lds, st, a);
 }
 
 int tail_dispatch(const pcr_attn_tail *p, bool bwd, hipStream_t st) {
@@ -712,7 +690,7 @@ int head_grid(const pcr_attn_head *p) {
   if (!in.ok) return 0;
   const long tiles = (long)p->B * ((p->L + kCT - 1) / kCT);
   const long occ = (long)(kMaxDynLds / in.lds) < 1 ? 1 : (long)(kMaxDynLds / in.lds);
-  const long cap = (long)ck_ncu() * (occ > 2 ? 2 : occ);
+  const long cap = (long)pcr_cu_count() * (occ > 2 ? 2 : occ);
   return (int)(tiles < cap ? tiles : cap);
 }
 
@@ -728,24 +706,15 @@ int head_launch(const pcr_attn_head *p, bool bwd, hipStream_t st) {
   a.B = p->B; a.L = p->L; a.tpc = (p->L + kCT - 1) / kCT; a.total = p->B * a.tpc;
   const int grid = head_grid(p);
   const size_t lds = head_lds(C, HD, D, NP);
-#define PCR_HL(BW, PR)                                                                              \
-  do {                                                                                             \
-    static bool ok = allow_big_lds(attn_head_kernel<C, HD, D, NP, SRC, BW, PR>);                   \
-    (void)ok;                                                                                      \
-    hipLaunchKernelGGL((attn_head_kernel<C, HD, D, NP, SRC, BW, PR>), dim3(grid), dim3(kThreads), lds, st, a); \
-  } while (0)
   const int prec = chain_prec(p->precision, p->fwd_precision);
+  const dim3 g(grid), b(kThreads);
   if (bwd) {
-    if (prec == 3) PCR_HL(true, 3);
-    else if (prec == 1) PCR_HL(true, 1);
-    else PCR_HL(true, 0);
-  } else {
-    if (prec == 3) PCR_HL(false, 3);
-    else PCR_HL(false, 0);
+    if (prec == 3) return pcr_launch_lds<attn_head_kernel<C, HD, D, NP, SRC, true, 3>>(g, b, lds, st, a);
+    if (prec == 1) return pcr_launch_lds<attn_head_kernel<C, HD, D, NP, SRC, true, 1>>(g, b, lds, st, a);
+    return pcr_launch_lds<attn_head_kernel<C, HD, D, NP, SRC, true, 0>>(g, b, lds, st, a);
   }
-#undef PCR_HL
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  if (prec == 3) return pcr_launch_lds<attn_head_kernel<C, HD, D, NP, SRC, false, 3>>(g, b, lds, st, a);
+  return pcr_launch_lds<attn_head_kernel<C, HD, D, NP, SRC, false, 0>>(g, b, lds, st, a);
 }
 
 int head_dispatch(const pcr_attn_head *p, bool bwd, hipStream_t st) {

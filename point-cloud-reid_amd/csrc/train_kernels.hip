@@ -1110,11 +1110,6 @@ __global__ __launch_bounds__(256) void pack_weights_multi_kernel(const PackDesc 
   }
 }
 
-template <class K>
-static bool big_lds(K k) {
-  return allow_big_lds(k);
-}
-
 }  // namespace
 
 // grid.y: clouds are strided over at most this many workgroup rows, so that a launch has ~768 workgroups whatever the
@@ -1175,10 +1170,8 @@ PCR_EXPORT int pcr_pack_weight_dev_f32(const float *w, int rows, int cols, int l
   if (!w || !packed || rows < 1 || cols < 1 || ld < cols || transpose < 0 || transpose > 2) return PCR_ERR_INVALID;
   const int n0 = ceil8(cols) * ceil32(rows), n1 = ceil8(rows) * ceil32(cols);
   const int total = transpose == 2 ? n0 + n1 : (transpose ? n1 : n0);
-  hipLaunchKernelGGL(pack_weight_kernel, dim3((total + 255) / 256 > 1024 ? 1024 : (total + 255) / 256), dim3(256), 0,
-                     pcr_s(stream), w, rows, cols, ld, transpose, packed);
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  return pcr_launch<pack_weight_kernel>(dim3((total + 255) / 256 > 1024 ? 1024 : (total + 255) / 256), dim3(256), 0,
+                                        pcr_s(stream), w, rows, cols, ld, transpose, packed);
 }
 
 PCR_EXPORT int pcr_pack_weight_bf16_dev_f32(const float *w, int rows, int cols, int ld, int transpose, float *packed,
@@ -1186,19 +1179,24 @@ PCR_EXPORT int pcr_pack_weight_bf16_dev_f32(const float *w, int rows, int cols, 
   if (!w || !packed || rows < 1 || cols < 1 || ld < cols || transpose < 0 || transpose > 1) return PCR_ERR_INVALID;
   const int cout = transpose ? cols : rows, cin = transpose ? rows : cols;
   const int total = ((cin + 15) >> 4) * (ceil32(cout) >> 5) * 512;
-  hipLaunchKernelGGL(pack_weight_bf_kernel, dim3((total + 255) / 256 > 1024 ? 1024 : (total + 255) / 256), dim3(256), 0,
-                     pcr_s(stream), w, rows, cols, ld, transpose, reinterpret_cast<unsigned short *>(packed));
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  return pcr_launch<pack_weight_bf_kernel>(dim3((total + 255) / 256 > 1024 ? 1024 : (total + 255) / 256), dim3(256), 0,
+                                           pcr_s(stream), w, rows, cols, ld, transpose, reinterpret_cast<unsigned short *>(packed));
 }
 
 PCR_EXPORT int pcr_pack_weights_multi_f32(const pcr_pack_desc *descs_dev, int n, pcr_stream_t stream) {
   if (!descs_dev || n < 0 || n > 65535) return PCR_ERR_INVALID;
   if (n == 0) return PCR_OK;
-  hipLaunchKernelGGL(pack_weights_multi_kernel, dim3(8, n), dim3(256), 0, pcr_s(stream),
-                     reinterpret_cast<const PackDesc *>(descs_dev));
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  return pcr_launch<pack_weights_multi_kernel>(dim3(8, n), dim3(256), 0, pcr_s(stream),
+                                               reinterpret_cast<const PackDesc *>(descs_dev));
+}
+
+// the forward's fan-out over the prefetch depth (pfq pieces of 16 bytes per thread, 0: none)
+template <int WS, int NR>
+static int tdense_fwd_go(int pfq, dim3 grid, dim3 blk, size_t lds, hipStream_t st, const TFwd &a) {
+  if (pfq == 2) return pcr_launch_lds<tdense_fwd_kernel<WS, NR, 2>>(grid, blk, lds, st, a);
+  if (pfq == 4) return pcr_launch_lds<tdense_fwd_kernel<WS, NR, 4>>(grid, blk, lds, st, a);
+  if (pfq == 8) return pcr_launch_lds<tdense_fwd_kernel<WS, NR, 8>>(grid, blk, lds, st, a);
+  return pcr_launch_lds<tdense_fwd_kernel<WS, NR, 0>>(grid, blk, lds, st, a);
 }
 
 PCR_EXPORT int pcr_tdense_fwd_f32(const pcr_tdense_fwd *p, pcr_stream_t stream) {
@@ -1226,29 +1224,12 @@ PCR_EXPORT int pcr_tdense_fwd_f32(const pcr_tdense_fwd *p, pcr_stream_t stream) 
   const int pfq = need <= 2 ? 2 : (need <= 4 ? 4 : (need <= 8 ? 8 : 0));
   const dim3 grid(gx, wg_cloud_rows(p->B, gx)), blk(kThreads);
   hipStream_t st = pcr_s(stream);
-#define PCR_TF(WSv, NRv, Qv)                                                        \
-  do {                                                                              \
-    static bool ok = big_lds(tdense_fwd_kernel<WSv, NRv, Qv>);                      \
-    (void)ok;                                                                       \
-    hipLaunchKernelGGL((tdense_fwd_kernel<WSv, NRv, Qv>), grid, blk, lds, st, a);   \
-  } while (0)
-#define PCR_TFQ(WSv, NRv)                                                           \
-  do {                                                                              \
-    if (pfq == 2) PCR_TF(WSv, NRv, 2);                                              \
-    else if (pfq == 4) PCR_TF(WSv, NRv, 4);                                         \
-    else if (pfq == 8) PCR_TF(WSv, NRv, 8);                                         \
-    else PCR_TF(WSv, NRv, 0);                                                       \
-  } while (0)
   const int nb = coutP >> 5;
-  if (nb == 1) PCR_TFQ(4, 1);
-  else if (nb == 2) PCR_TFQ(2, 1);
-  else if (nb <= 4) PCR_TFQ(1, 1);
-  else if (nb <= 8) PCR_TFQ(1, 2);
-  else PCR_TFQ(1, 3);
-#undef PCR_TFQ
-#undef PCR_TF
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  if (nb == 1) return tdense_fwd_go<4, 1>(pfq, grid, blk, lds, st, a);
+  if (nb == 2) return tdense_fwd_go<2, 1>(pfq, grid, blk, lds, st, a);
+  if (nb <= 4) return tdense_fwd_go<1, 1>(pfq, grid, blk, lds, st, a);
+  if (nb <= 8) return tdense_fwd_go<1, 2>(pfq, grid, blk, lds, st, a);
+  return tdense_fwd_go<1, 3>(pfq, grid, blk, lds, st, a);
 }
 
 PCR_EXPORT int pcr_tdense_bwd_f32(const pcr_tdense_bwd *p, pcr_stream_t stream) {
@@ -1289,56 +1270,31 @@ PCR_EXPORT int pcr_tdense_bwd_f32(const pcr_tdense_bwd *p, pcr_stream_t stream) 
   hipStream_t st = pcr_s(stream);
   const int nx = cinP >> 5;
   const int rowsY = coutP > cinP ? coutP : cinP;
-#define PCR_TB(WSv, NRXv, QYv, QXv)                                                              \
-  do {                                                                                           \
-    static bool ok = big_lds(tdense_bwd_kernel<WSv, NRXv, NTW, QYv, QXv>);                       \
-    (void)ok;                                                                                    \
-    hipLaunchKernelGGL((tdense_bwd_kernel<WSv, NRXv, NTW, QYv, QXv>), grid, blk, lds, st, a);    \
-  } while (0)
-#define PCR_TB4(WSv, NRXv)                                                              \
-  do {                                                                                  \
-    static bool ok = big_lds(tdense_bwd_kernel_o4<WSv, NRXv>);                          \
-    (void)ok;                                                                           \
-    hipLaunchKernelGGL((tdense_bwd_kernel_o4<WSv, NRXv>), grid, blk, lds, st, a);       \
-  } while (0)
   static const int variant = pcr_tune_int("PCR_TD_VARIANT");   // tuning aid
   // narrow layers (<= 4 dW tiles, LDS <= 40 KB): four workgroups per CU; wider ones: two per CU (with operand prefetch
   // for the 64-channel square layers whose pieces fit the registers)
   // (measured at B = 512: 64 x 64, L = 3072: 0.94 -> 0.72 ms with four workgroups per CU, 0.63 with the batched fill;
   // 32 x 32, L = 4096: 0.59 with the prefetch variant against 0.62)
   // (64-wide inputs: three workgroups per CU without scratch beat four with 136 B of spills per lane, 0.61 vs 0.63 ms)
-  if (variant != 2 && items <= 4 && lds <= 40 * 1024 && nx == 2) {
-    static bool ok3 = big_lds(tdense_bwd_kernel_o3<2, 1>);
-    (void)ok3;
-    hipLaunchKernelGGL((tdense_bwd_kernel_o3<2, 1>), grid, blk, lds, st, a);
-  } else
-  if (items <= 4 && lds <= 40 * 1024 && variant != 2 && !(rowsY == 32 && cinP == 32)) {
-    if (nx == 1) PCR_TB4(4, 1);
-    else PCR_TB4(2, 1);
-  } else if (rowsY == 32 && cinP == 32) {
-    // one accumulator tile per wave (NTW = 4 carried three dead tiles and 160 B of spills): 0.58 -> 0.49 ms
-    static bool okp = big_lds(tdense_bwd_kernel_p1<4, 1, 2, 2>);
-    (void)okp;
-    hipLaunchKernelGGL((tdense_bwd_kernel_p1<4, 1, 2, 2>), grid, blk, lds, st, a);
-  }
-  else if (rowsY == 64 && cinP == 64) PCR_TB(2, 1, 4, 4);
-  else if (p->precision == PCR_PREC_BF16X3 && p->wpT_bf && p->wpT && coutP == 128 && cinP == 128 && p->cout == 128 &&
-           p->cin1 == 128 && !p->cin2 && gz == 1) {
+  if (variant != 2 && items <= 4 && lds <= 40 * 1024 && nx == 2)
+    return pcr_launch_lds<tdense_bwd_kernel_o3<2, 1>>(grid, blk, lds, st, a);
+  if (items <= 4 && lds <= 40 * 1024 && variant != 2 && !(rowsY == 32 && cinP == 32))
+    return nx == 1 ? pcr_launch_lds<tdense_bwd_kernel_o4<4, 1>>(grid, blk, lds, st, a)
+                   : pcr_launch_lds<tdense_bwd_kernel_o4<2, 1>>(grid, blk, lds, st, a);
+  // one accumulator tile per wave (NTW = 4 carried three dead tiles and 160 B of spills): 0.58 -> 0.49 ms
+  if (rowsY == 32 && cinP == 32) return pcr_launch_lds<tdense_bwd_kernel_p1<4, 1, 2, 2>>(grid, blk, lds, st, a);
+  if (rowsY == 64 && cinP == 64) return pcr_launch_lds<tdense_bwd_kernel<2, 1, NTW, 4, 4>>(grid, blk, lds, st, a);
+  if (p->precision == PCR_PREC_BF16X3 && p->wpT_bf && p->wpT && coutP == 128 && cinP == 128 && p->cout == 128 &&
+      p->cin1 == 128 && !p->cin2 && gz == 1) {
     // the 128 x 128 grouped-MLP layers on the bf16 matrix core (split bf16: dx and dW)
-    static bool okb = big_lds(tdense_bwd_bf_kernel);
-    (void)okb;
     pcr_note_arith(PCR_PREC_BF16X3);
-    hipLaunchKernelGGL(tdense_bwd_bf_kernel, grid, blk, lds, st, a);
+    return pcr_launch_lds<tdense_bwd_bf_kernel>(grid, blk, lds, st, a);
   }
-  else if (nx == 1) PCR_TB(4, 1, 0, 0);
-  else if (nx == 2) PCR_TB(2, 1, 0, 0);
-  else if (nx <= 4) PCR_TB(1, 1, 0, 0);
-  else if (nx <= 8) PCR_TB(1, 2, 0, 0);
-  else PCR_TB(1, 3, 0, 0);
-#undef PCR_TB4
-#undef PCR_TB
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  if (nx == 1) return pcr_launch_lds<tdense_bwd_kernel<4, 1, NTW, 0, 0>>(grid, blk, lds, st, a);
+  if (nx == 2) return pcr_launch_lds<tdense_bwd_kernel<2, 1, NTW, 0, 0>>(grid, blk, lds, st, a);
+  if (nx <= 4) return pcr_launch_lds<tdense_bwd_kernel<1, 1, NTW, 0, 0>>(grid, blk, lds, st, a);
+  if (nx <= 8) return pcr_launch_lds<tdense_bwd_kernel<1, 2, NTW, 0, 0>>(grid, blk, lds, st, a);
+  return pcr_launch_lds<tdense_bwd_kernel<1, 3, NTW, 0, 0>>(grid, blk, lds, st, a);
 }
 
 // Many reductions in ONE launch (round 5): a training step's backward leaves ~40 partial-sum buffers (weight / bias /
@@ -1429,8 +1385,8 @@ PCR_EXPORT int pcr_reduce_multi_f32(const pcr_reduce_job *jobs, int n, pcr_strea
       most = total > most ? total : most;
     }
     for (int i = m; i < kReduceJobs; i++) a.j[i] = a.j[0];
-    hipLaunchKernelGGL(reduce_multi_kernel, dim3((most + 31) / 32, m), dim3(256), 0, pcr_s(stream), a);
-    PCR_CHECK_LAUNCH();
+    const int rc = pcr_launch<reduce_multi_kernel>(dim3((most + 31) / 32, m), dim3(256), 0, pcr_s(stream), a);
+    if (rc != PCR_OK) return rc;
   }
   return PCR_OK;
 }
@@ -1442,13 +1398,10 @@ PCR_EXPORT int pcr_reduce_parts_f32(const float *part, int nparts, long stride, 
   const bool dense = (rows == 1 || ld == cols) && (stride & 3) == 0 && (total & 3) == 0 &&
                      (reinterpret_cast<uintptr_t>(part) & 15) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0;
   if (dense && nparts >= 64)
-    hipLaunchKernelGGL(reduce_parts4_kernel, dim3((total + 31) / 32), dim3(256), 0, pcr_s(stream), part, nparts,
-                       (size_t)stride, total, out);
-  else
-  hipLaunchKernelGGL(reduce_parts_kernel, dim3((total + 31) / 32), dim3(256), 0, pcr_s(stream), part, nparts,
-                     (size_t)stride, rows, cols, ld, out);
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+    return pcr_launch<reduce_parts4_kernel>(dim3((total + 31) / 32), dim3(256), 0, pcr_s(stream), part, nparts,
+                                            (size_t)stride, total, out);
+  return pcr_launch<reduce_parts_kernel>(dim3((total + 31) / 32), dim3(256), 0, pcr_s(stream), part, nparts,
+                                         (size_t)stride, rows, cols, ld, out);
 }
 
 PCR_EXPORT int pcr_bn_fwd_finalize_f32(const pcr_bn_fwd_fin *p, pcr_stream_t stream) {
@@ -1461,9 +1414,7 @@ PCR_EXPORT int pcr_bn_fwd_finalize_f32(const pcr_bn_fwd_fin *p, pcr_stream_t str
   a.running_mean = p->running_mean; a.running_var = p->running_var;
   a.scale = p->scale; a.shift = p->shift; a.inv_scale = p->inv_scale; a.mean = p->mean; a.invstd = p->invstd;
   a.shift0 = p->shift0; a.shift0_stride = p->shift0_stride;
-  hipLaunchKernelGGL(bn_fwd_finalize_kernel, dim3(a.CP / 32), dim3(1024), 0, pcr_s(stream), a);
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  return pcr_launch<bn_fwd_finalize_kernel>(dim3(a.CP / 32), dim3(1024), 0, pcr_s(stream), a);
 }
 
 PCR_EXPORT int pcr_bn_bwd_finalize_f32(const pcr_bn_bwd_fin *p, pcr_stream_t stream) {
@@ -1475,7 +1426,5 @@ PCR_EXPORT int pcr_bn_bwd_finalize_f32(const pcr_bn_bwd_fin *p, pcr_stream_t str
   a.gamma = p->gamma; a.mean = p->mean; a.invstd = p->invstd;
   a.ka = p->ka; a.kb = p->kb; a.kc = p->kc; a.dgamma = p->dgamma; a.dbeta = p->dbeta;
   a.centre = p->centre;
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(a.CP / 32), dim3(1024), 0, pcr_s(stream), a);
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  return pcr_launch<bn_bwd_finalize_kernel>(dim3(a.CP / 32), dim3(1024), 0, pcr_s(stream), a);
 }

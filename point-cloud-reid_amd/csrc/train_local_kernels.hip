@@ -102,9 +102,7 @@ PCR_EXPORT int pcr_local_attn_train_fwd_f32(const float *qkv, const int *idx, fl
   if (la_check(qkv, idx, B, N, C, K, nhead) || !msg) return PCR_ERR_INVALID;
   if (B == 0) return PCR_OK;
   LAArgs a{qkv, idx, nullptr, msg, nullptr, nullptr, 0, N, C, K, C / nhead, eps};
-  hipLaunchKernelGGL(local_attn_cm_kernel<false>, dim3((N + kLT / 64 - 1) / (kLT / 64), B), dim3(kLT), 0, pcr_s(stream), a);
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  return pcr_launch<local_attn_cm_kernel<false>>(dim3((N + kLT / 64 - 1) / (kLT / 64), B), dim3(kLT), 0, pcr_s(stream), a);
 }
 
 PCR_EXPORT int pcr_local_attn_train_bwd_f32(const float *qkv, const int *idx, const float *g, float *dq, long dq_bstride,
@@ -113,7 +111,5 @@ PCR_EXPORT int pcr_local_attn_train_bwd_f32(const float *qkv, const int *idx, co
   if (la_check(qkv, idx, B, N, C, K, nhead) || !g || !dq || !edge || dq_bstride < (long)C * N) return PCR_ERR_INVALID;
   if (B == 0) return PCR_OK;
   LAArgs a{qkv, idx, g, nullptr, dq, edge, dq_bstride, N, C, K, C / nhead, eps};
-  hipLaunchKernelGGL(local_attn_cm_kernel<true>, dim3((N + kLT / 64 - 1) / (kLT / 64), B), dim3(kLT), 0, pcr_s(stream), a);
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  return pcr_launch<local_attn_cm_kernel<true>>(dim3((N + kLT / 64 - 1) / (kLT / 64), B), dim3(kLT), 0, pcr_s(stream), a);
 }

@@ -453,14 +453,12 @@ PCR_EXPORT int pcr_sa_l1_fwd_f32(const float *xyz, const int *idx, const float *
   const size_t lds = ((tab ? (size_t)cs * (N + S) : 0) + 3 * (size_t)N + 4 * cs + 8 * cs) * sizeof(float);
   if (lds > (size_t)kMaxDynLds) return PCR_ERR_INVALID;
   const dim3 grid((c1 + cs - 1) / cs, B);
+  int rc = PCR_OK;
   l1_dispatch(cs, [&](auto tag) {
     constexpr int CS = decltype(tag)::value;
-    static bool ok = allow_big_lds(sa_l1_fwd_kernel<CS>);
-    (void)ok;
-    hipLaunchKernelGGL(sa_l1_fwd_kernel<CS>, grid, dim3(kThreads), lds, pcr_s(stream), a);
+    rc = pcr_launch_lds<sa_l1_fwd_kernel<CS>>(grid, dim3(kThreads), lds, pcr_s(stream), a);
   });
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  return rc;
 }
 
 PCR_EXPORT int pcr_sa_l1_bwd_f32(const float *xyz, const int *idx, const float *g, const float *y, const float *ka,
@@ -478,14 +476,12 @@ PCR_EXPORT int pcr_sa_l1_bwd_f32(const float *xyz, const int *idx, const float *
                       (size_t)parts * cs * 4 + 4 * (size_t)parts + 2) * sizeof(float);
   if (lds > (size_t)kMaxDynLds) return PCR_ERR_INVALID;
   const dim3 grid((c1 + cs - 1) / cs, B);
+  int rc = PCR_OK;
   l1_dispatch(cs, [&](auto tag) {
     constexpr int CS = decltype(tag)::value;
-    static bool ok = allow_big_lds(sa_l1_bwd_kernel<CS>);
-    (void)ok;
-    hipLaunchKernelGGL(sa_l1_bwd_kernel<CS>, grid, dim3(kThreads), lds, pcr_s(stream), a);
+    rc = pcr_launch_lds<sa_l1_bwd_kernel<CS>>(grid, dim3(kThreads), lds, pcr_s(stream), a);
   });
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  return rc;
 }
 
 PCR_EXPORT int pcr_sa_pool_fwd_f32(const float *y, const float *scale, const float *shift, float *pooled, int *argmax,
@@ -499,9 +495,7 @@ PCR_EXPORT int pcr_sa_pool_fwd_f32(const float *y, const float *scale, const flo
   const int cb = (C + 31) / 32, tiles = (S + G - 1) / G;
   int gz = (2048 + cb * B - 1) / (cb * B);      // ~2048 workgroups
   gz = gz < 1 ? 1 : (gz > tiles ? tiles : gz);
-  hipLaunchKernelGGL(sa_pool_fwd_kernel, dim3(cb, B, gz), dim3(kThreads), lds, pcr_s(stream), a);
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  return pcr_launch<sa_pool_fwd_kernel>(dim3(cb, B, gz), dim3(kThreads), lds, pcr_s(stream), a);
 }
 
 PCR_EXPORT int pcr_sa_pool_bwd_stats_f32(const float *gp, const float *pooled, const float *ymax, float *part, float *gz,
@@ -510,8 +504,6 @@ PCR_EXPORT int pcr_sa_pool_bwd_stats_f32(const float *gp, const float *pooled, c
   if (B == 0) return PCR_OK;
   if (B > 65535) return PCR_ERR_INVALID;
   const int CP = ceil32(C);
-  hipLaunchKernelGGL(sa_pool_bwd_stats_kernel, dim3(CP / (kThreads / 64), B), dim3(kThreads), 0, pcr_s(stream), gp, pooled,
-                     ymax, part, gz, C, S);
-  PCR_CHECK_LAUNCH();
-  return PCR_OK;
+  return pcr_launch<sa_pool_bwd_stats_kernel>(dim3(CP / (kThreads / 64), B), dim3(kThreads), 0, pcr_s(stream), gp, pooled,
+                                              ymax, part, gz, C, S);
 }

@@ -846,16 +846,6 @@ __global__ __launch_bounds__(64 * kTsWaves, NB == 1 ? 3 : 1) void tstream_bwd_ke
   for (int e = tid; e < 2 * C; e += 64 * kTsWaves) a.dstats[(size_t)blockIdx.x * 2 * C + e] = img_ds[e];
 }
 
-int ts_cus() {
-  static int cus = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 256;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1) return 256;
-    return n;
-  }();
-  return cus;
-}
-
 }  // namespace
 
 // ---- eligibility + grid (shared by the launch paths in train_kernels.hip and the *_groups exports) ----
@@ -908,7 +898,7 @@ int pcr_ts_fwd_grid(const pcr_tdense_fwd *p, int *per) {
   if (p->cout == 64 || p->cin1 == 64) wgs_per_cu = wgs_per_cu > 3 ? 3 : wgs_per_cu;
   const int waves = p->cin1 == 128 ? kTpWaves : kTsWaves;
   if (p->cin1 == 128) wgs_per_cu = 1;
-  int g = ts_cus() * wgs_per_cu;
+  int g = pcr_cu_count() * wgs_per_cu;
   int pw = (nblk + g * waves - 1) / (g * waves);
   // rounds come in pairs (two register sets); with the fused pooling a wave's range is whole centre groups
   // (lcm(32, K) / 32 blocks), so that a centre never straddles two waves
@@ -924,13 +914,6 @@ int pcr_ts_fwd_grid(const pcr_tdense_fwd *p, int *per) {
   return g;
 }
 
-template <int NBI, int NBO, bool WLDS>
-static void ts_fwd_go(const TSFwd &a, int g, size_t lds, hipStream_t st) {
-  static bool ok = allow_big_lds(tstream_fwd_kernel<NBI, NBO, WLDS>);
-  (void)ok;
-  hipLaunchKernelGGL((tstream_fwd_kernel<NBI, NBO, WLDS>), dim3(g), dim3(64 * kTsWaves), lds, st, a);
-}
-
 int pcr_ts_fwd_launch(const pcr_tdense_fwd *p, hipStream_t st) {
   TSFwd a;
   a.x = p->x; a.isc = p->isc; a.ish = p->ish; a.in_relu = p->in_relu; a.wp = p->wp; a.bias = p->bias;
@@ -941,16 +924,12 @@ int pcr_ts_fwd_launch(const pcr_tdense_fwd *p, hipStream_t st) {
   const int g = pcr_ts_fwd_grid(p, &a.per);
   const size_t lds = ts_fwd_lds(p->cin1, p->cout);
   const int ci = p->cin1, co = p->cout;
-  if (ci == 32 && co == 32) ts_fwd_go<1, 1, false>(a, g, lds, st);
-  else if (ci == 64 && co == 64) ts_fwd_go<2, 2, true>(a, g, lds, st);
-  else if (ci == 32 && co == 64) ts_fwd_go<1, 2, true>(a, g, lds, st);
-  else if (ci == 64 && co == 32) ts_fwd_go<2, 1, true>(a, g, lds, st);
-  else {
-    static bool ok = allow_big_lds(tstream_fwd_pipe_kernel<4, false>);
-    (void)ok;
-    hipLaunchKernelGGL((tstream_fwd_pipe_kernel<4, false>), dim3(g), dim3(64 * kTpWaves), lds, st, a);
-  }
-  return hipGetLastError() == hipSuccess ? PCR_OK : PCR_ERR_LAUNCH;
+  const dim3 grid(g), blk(64 * kTsWaves);
+  if (ci == 32 && co == 32) return pcr_launch_lds<tstream_fwd_kernel<1, 1, false>>(grid, blk, lds, st, a);
+  if (ci == 64 && co == 64) return pcr_launch_lds<tstream_fwd_kernel<2, 2, true>>(grid, blk, lds, st, a);
+  if (ci == 32 && co == 64) return pcr_launch_lds<tstream_fwd_kernel<1, 2, true>>(grid, blk, lds, st, a);
+  if (ci == 64 && co == 32) return pcr_launch_lds<tstream_fwd_kernel<2, 1, true>>(grid, blk, lds, st, a);
+  return pcr_launch_lds<tstream_fwd_pipe_kernel<4, false>>(grid, dim3(64 * kTpWaves), lds, st, a);
 }
 
 // backward: square 32 / 64-channel layers behind a BatchNorm (dy_mode 1 / 3) with every output wanted
@@ -967,7 +946,7 @@ bool pcr_ts_bwd_ok(const pcr_tdense_bwd *p) {
 int pcr_ts_bwd_grid(const pcr_tdense_bwd *p, int *per) {
   const int nblk = p->B * (p->L >> 5);
   const int wgs_per_cu = p->cout == 64 ? 1 : 3;      // what registers / LDS admit (one / three waves per SIMD)
-  int g = ts_cus() * wgs_per_cu;
+  int g = pcr_cu_count() * wgs_per_cu;
   int pw = (nblk + g * kTsWaves - 1) / (g * kTsWaves);
   pw = (pw + 1) & ~1;                    // rounds come in pairs (two register sets)
   if (pw < 2) pw = 2;
@@ -986,12 +965,7 @@ int pcr_ts_bwd_launch(const pcr_tdense_bwd *p, hipStream_t st) {
   a.B = p->B; a.L = p->L; a.nblk = p->B * (p->L >> 5);
   const int g = pcr_ts_bwd_grid(p, &a.per);
   const dim3 grid(g), blk(64 * kTsWaves);
-  if (p->cout == 32) {
-    if (p->dy_mode == 3) hipLaunchKernelGGL((tstream_bwd_kernel<1, 3>), grid, blk, 0, st, a);
-    else hipLaunchKernelGGL((tstream_bwd_kernel<1, 1>), grid, blk, 0, st, a);
-  } else {
-    if (p->dy_mode == 3) hipLaunchKernelGGL((tstream_bwd_kernel<2, 3>), grid, blk, 0, st, a);
-    else hipLaunchKernelGGL((tstream_bwd_kernel<2, 1>), grid, blk, 0, st, a);
-  }
-  return hipGetLastError() == hipSuccess ? PCR_OK : PCR_ERR_LAUNCH;
+  if (p->cout == 32)
+    return p->dy_mode == 3 ? pcr_launch<tstream_bwd_kernel<1, 3>>(grid, blk, 0, st, a) : pcr_launch<tstream_bwd_kernel<1, 1>>(grid, blk, 0, st, a);
+  return p->dy_mode == 3 ? pcr_launch<tstream_bwd_kernel<2, 3>>(grid, blk, 0, st, a) : pcr_launch<tstream_bwd_kernel<2, 1>>(grid, blk, 0, st, a);
 }

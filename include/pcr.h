@@ -144,6 +144,68 @@ int pcr_three_interp_fwd_f32(const float *feat, const int *idx, const float *wei
 int pcr_three_interp_bwd_f32(const float *grad_out, const int *idx, const float *weight,
                              float *grad_feat, int B, int C, int N, int M, pcr_stream_t stream);
 
+/* ------------------------------------------- A2. points in boxes, per-box crops ------- */
+
+/* A box is [x, y, z, w, l, h, rz] in LiDAR coordinates, z the BOTTOM face.  Membership restates check_pt_in_box3d /
+ * lidar_to_local_coords (ops/roiaware_pool3d/src/points_in_boxes_cuda.cu:24-49) with that file's widths:
+ *   cz = z + h / 2.0 (double sum, rounded to float); outside if fabsf(pz - cz) > h / 2.0 (both z faces are inside);
+ *   rot = rz + pi/2 (double sum, rounded to float), sx = px - x, sy = py - y,
+ *   local_x = sx*cos(rot) - sy*sin(rot), local_y = sx*sin(rot) + sy*cos(rot) (float, products and sums not contracted);
+ *   inside iff -l/2.0 < local_x < l/2.0 and -w/2.0 < local_y < w/2.0 (double compares; the x / y faces are outside).
+ *
+ * pcr_box_frames_f32: boxes (T,7) -> frames (T,2) = (cosf(rot), sinf(rot)), the pair every kernel of this section derives
+ * from a box through one device function.  With this table a host restatement needs no trigonometry of its own and
+ * equals the entry points below bit for bit. */
+int pcr_box_frames_f32(const float *boxes, float *frames, int T, pcr_stream_t stream);
+
+/* points_in_boxes_batch (roiaware_pool3d/points_in_boxes.py:83-122, kernel points_in_boxes_cuda.cu:79-105).
+ * points (B,P,3), boxes (B,T,7) -> out (B,P,T) int32, 1 where box t holds point p and 0 elsewhere; EVERY element is
+ * written (the reference zero-fills first and writes the ones).  B <= 65535, T <= 65535 * 256. */
+int pcr_points_in_boxes_batch_f32(const float *points, const float *boxes, int *out, int B, int P, int T,
+                                  pcr_stream_t stream);
+
+/* points_in_boxes_gpu (points_in_boxes.py:6-49, kernel points_in_boxes_cuda.cu:51-77).  -> out (B,P) int32: the LOWEST
+ * index of a box that holds the point, -1 for none; every element is written (the reference pre-fills -1).  B <= 65535. */
+int pcr_points_in_boxes_f32(const float *points, const float *boxes, int *out, int B, int P, int T, pcr_stream_t stream);
+
+/* The fused crop: what the reference's tracker does with points_in_boxes_batch, a Python loop over the boxes, a padded
+ * batch, a batched affine and one host-side torch.randint per box (models/trackers/deprecated/pc_utils.py:31-96), and
+ * what its loader does per object with subsamplePC (datasets/utils.py:606-621), as ONE launch without a host read.
+ *
+ * points: P rows of `stride` floats, xyz first (a nuScenes sweep is (P,5)); boxes (M,7) -> clouds (M,n,3) f32 and
+ * lengths (M) int32, the number of sweep points box m holds (under both rules).  The in-box points of a box are numbered
+ * 0 .. len-1 in ascending sweep index; slot s of box m takes in-box point j = ((uint64)u * len) >> 32, u a 32-bit word
+ * (torch.randint(high=len) with replacement for every slot, pc_utils.py:84).
+ *   u = rand[m*n + s] read as bits when rand != NULL; otherwise the counter-based word of (seed[0], m, s):
+ *       mix(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16      (uint32)
+ *       h = mix((uint32)seed ^ 0x9e3779b9); h = mix(h ^ (uint32)(seed >> 32)); h = mix(h ^ m); u = mix(h ^ s)
+ *     seed is a DEVICE pointer to one int64 (NULL = 0): a captured launch draws fresh samples once that word changes.
+ *   rule PCR_CROP_RULE_TRACKER: len == 0 -> zeros, otherwise every slot is drawn (pc_utils.py:84-95);
+ *        PCR_CROP_RULE_DATASET: len <= 2 -> zeros, len == n -> the in-box points in order, otherwise drawn (subsamplePC).
+ *   frame PCR_CROP_FRAME_SENSOR: coordinates as read; _CENTRED: minus (x, y, cz); _BOX: (local_x, local_y, pz - cz), the
+ *        values of the membership test (= interpolate_per_frame's affine, INTEGRATION.md "from a sweep and boxes").
+ *   z_is_centre != 0: boxes[.][2] is cz itself (gravity-centre boxes, what the tracker holds).
+ * One workgroup per box: the sweep is tested in 64-point chunks, the chunks' counts are scanned in LDS, and each slot
+ * finds its chunk by binary search and picks by rank inside the chunk's ballot -- no list, no atomics, the same bits on
+ * every run.  pcr_crop_boxes_ok(P, M, n, stride): 0 <= P <= PCR_CROP_MAX_POINTS (the count table, one LDS word per 64
+ * points plus 64 words of scan scratch, fills the 160 KiB a gfx950 workgroup may take: 64 * (40960 - 64)),
+ * 0 <= M <= PCR_CROP_MAX_BOXES, 1 <= n <= PCR_CROP_MAX_SAMPLES, 3 <= stride <= PCR_CROP_MAX_STRIDE; anything else, an
+ * unknown frame / rule or a NULL tensor that would be read returns PCR_ERR_INVALID.  M == 0 launches nothing; P == 0
+ * gives zero clouds and zero lengths. */
+#define PCR_CROP_FRAME_SENSOR 0
+#define PCR_CROP_FRAME_CENTRED 1
+#define PCR_CROP_FRAME_BOX 2
+#define PCR_CROP_RULE_TRACKER 0
+#define PCR_CROP_RULE_DATASET 1
+#define PCR_CROP_MAX_POINTS 2617344
+#define PCR_CROP_MAX_BOXES 65536
+#define PCR_CROP_MAX_SAMPLES 65536
+#define PCR_CROP_MAX_STRIDE 16
+int pcr_crop_boxes_ok(int P, int M, int n, int stride);
+int pcr_crop_boxes_f32(const float *points, int stride, const float *boxes, const int *rand, const long long *seed,
+                       float *clouds, int *lengths, int P, int M, int n, int frame, int rule, int z_is_centre,
+                       pcr_stream_t stream);
+
 /* ------------------------------------------------- B. fused model kernels ------------ */
 
 /* Neighbour search of the "Point-Transformer" set-abstraction layers: centres are the first S

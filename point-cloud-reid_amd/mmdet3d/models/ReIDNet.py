@@ -316,6 +316,25 @@ class ReIDNet(nn.Module):
                     return self.backbone(pts_batched, self.backbone_list)
             return self.backbone(pts_batched, self.backbone_list)
 
+    def forward_inference_boxes(self, points, boxes, n=None, **crop_args):
+        """a sweep (P, C >= 3) and boxes (M, 7) on the device -> (xyz, feats, lengths): pcr_amd.crops.crops_from_boxes (the
+        reference tracker's interpolate_per_frame + get_input_batch, trackers/deprecated/pc_utils.py:31-96) followed by
+        forward_inference.  n defaults to the encoder's input size, backbone_list[0], for the Point-Transformer backbone
+        and must be given for the others.  A box without points is encoded as a cloud of zeros, as in the reference;
+        masking it is the caller's decision (lengths == 0; tracking_point_reid.py:93-100)."""
+        from pcr_amd import crops
+        if n is None:
+            if not isinstance(self.backbone, Pointnet_Backbone):
+                raise ValueError("forward_inference_boxes: n (points per crop) must be given for this backbone")
+            n = int(self.backbone_list[0])
+        if crop_args.get("return_frames"):
+            raise ValueError("forward_inference_boxes returns (xyz, feats, lengths); ask crops_from_boxes for frames")
+        clouds, lengths = crops.crops_from_boxes(points, boxes, n, **crop_args)
+        if self.use_dgcnn or isinstance(self.backbone, PointNet):
+            clouds = clouds.permute(0, 2, 1).contiguous()
+        xyz, feats = self.forward_inference(clouds)
+        return xyz, feats, lengths
+
     def siamese_forward(self, sparse_1, sparse_2):
         self._guard_tick(sparse_1, sparse_2)
         lvl = self.precision_level()

@@ -18,6 +18,7 @@ SO = os.path.join(LIBDIR, "libpcr_hip%s.so" % ("_" + _TAG if _TAG else ""))
 FLAGS = {
     "point_ops.hip": ["-ffp-contract=off"] + os.environ.get("PCR_POINT_FLAGS", "").split(),
     "edge_kernels.hip": ["-ffp-contract=off"],
+    "crop_kernels.hip": ["-ffp-contract=off"],       # membership and box-frame coordinates are compared bit for bit
 }
 
 

@@ -855,7 +855,8 @@ int pcr_edge_pool_route_f32(const float *gp, const float *pooled, const int *arg
                             int N, int K, pcr_stream_t stream);
 /* Per-cloud transforms (torch.bmm(x^T, T)^T, models/pointnet.py:109-111, 117-119): x (B,k,N), T (B,k,k) ->
  * y[b][j][n] = sum_i T[b][i][j] x[b][i][n]; transposed = 1 applies T^T instead (the backward's dx from dy);
- * pcr_bmm_dt_f32: dT[b][i][j] = sum_n x[b][i][n] dy[b][j][n].  k <= 128. */
+ * pcr_bmm_dt_f32: dT[b][i][j] = sum_n x[b][i][n] dy[b][j][n].  1 <= k <= 128 for both (the apply keeps T[b] in
+ * k (k + 1) floats of LDS: 66 048 bytes at k = 128, launched with the large-LDS opt-in); B = 0 is a no-op. */
 int pcr_bmm_apply_f32(const float *x, const float *T, float *y, int B, int k, int N, int transposed, pcr_stream_t stream);
 int pcr_bmm_dt_f32(const float *x, const float *dy, float *dT, int B, int k, int N, pcr_stream_t stream);
 

@@ -207,8 +207,8 @@ PCR_EXPORT int pcr_bmm_apply_f32(const float *x, const float *T, float *y, int B
   if (!x || !T || !y || B < 0 || k < 1 || k > 128 || N < 1) return PCR_ERR_INVALID;
   if (B == 0) return PCR_OK;
   if (B > 65535) return PCR_ERR_INVALID;
-  const size_t lds = (size_t)k * (k + 1) * sizeof(float);
-  return pcr_launch<bmm_apply_kernel>(dim3((N + 63) / 64, B), dim3(256), lds, pcr_s(stream), x, T, y, k, N, transposed);
+  const size_t lds = (size_t)k * (k + 1) * sizeof(float);      // k = 128: 66 048 bytes, past the 64 KiB default
+  return pcr_launch_lds<bmm_apply_kernel>(dim3((N + 63) / 64, B), dim3(256), lds, pcr_s(stream), x, T, y, k, N, transposed);
 }
 
 PCR_EXPORT int pcr_bmm_dt_f32(const float *x, const float *dy, float *dT, int B, int k, int N, pcr_stream_t stream) {

@@ -1083,8 +1083,9 @@ class PoolBoth(Function):
         P, C, Ln = o.shape
         pooled = _f32(P, 2 * C, device=o.device)
         arg = torch.empty((P, C), dtype=torch.int32, device=o.device)
-        L.check(L.load().pcr_pool_both_fwd_f32(L.ptr(o), L.ptr(pooled), L.ptr(arg), P, C, Ln, L.stream_ptr()),
-                "pcr_pool_both_fwd_f32")
+        if P:                                                # (no clouds: empty tensors, nothing to launch)
+            L.check(L.load().pcr_pool_both_fwd_f32(L.ptr(o), L.ptr(pooled), L.ptr(arg), P, C, Ln, L.stream_ptr()),
+                    "pcr_pool_both_fwd_f32")
         ctx.save_for_backward(arg)
         ctx.dims = (P, C, Ln)
         return pooled
@@ -1095,8 +1096,9 @@ class PoolBoth(Function):
         P, C, Ln = ctx.dims
         g = g.contiguous()
         dout = _f32(P, C, Ln, device=g.device)
-        L.check(L.load().pcr_pool_both_bwd_f32(L.ptr(g), L.ptr(arg), L.ptr(dout), P, C, Ln, L.stream_ptr()),
-                "pcr_pool_both_bwd_f32")
+        if P:
+            L.check(L.load().pcr_pool_both_bwd_f32(L.ptr(g), L.ptr(arg), L.ptr(dout), P, C, Ln, L.stream_ptr()),
+                    "pcr_pool_both_bwd_f32")
         return dout
 
 
@@ -1110,8 +1112,9 @@ class ChannelMax(Function):
         B, C, Ln = x.shape
         y = _f32(B, C // W, Ln, device=x.device)
         arg = torch.empty((B, C // W, Ln), dtype=torch.int32, device=x.device)
-        L.check(L.load().pcr_channel_max_fwd_f32(L.ptr(x), L.ptr(y), L.ptr(arg), B, C, Ln, W, L.stream_ptr()),
-                "pcr_channel_max_fwd_f32")
+        if B:                                              # (no clouds: empty tensors, nothing to launch)
+            L.check(L.load().pcr_channel_max_fwd_f32(L.ptr(x), L.ptr(y), L.ptr(arg), B, C, Ln, W, L.stream_ptr()),
+                    "pcr_channel_max_fwd_f32")
         ctx.save_for_backward(arg)
         ctx.dims = (B, C, Ln, W)
         return y
@@ -1122,12 +1125,20 @@ class ChannelMax(Function):
         B, C, Ln, W = ctx.dims
         g = g.contiguous()
         dx = _f32(B, C, Ln, device=g.device)
-        L.check(L.load().pcr_channel_max_bwd_f32(L.ptr(g), L.ptr(arg), L.ptr(dx), B, C, Ln, W, L.stream_ptr()),
-                "pcr_channel_max_bwd_f32")
+        if B:
+            L.check(L.load().pcr_channel_max_bwd_f32(L.ptr(g), L.ptr(arg), L.ptr(dx), B, C, Ln, W, L.stream_ptr()),
+                    "pcr_channel_max_bwd_f32")
         return dx, None
 
 
 # --------------------------------------------------------------- PointNet pieces (csrc/train_bn_kernels.hip) --
+def _require_batch(R, shape):
+    """torch's training-mode BatchNorm refuses a single value per channel (there is no variance to normalise by); so
+    does this path, before any launch, rather than return beta and update the running statistics"""
+    if R <= 1:
+        raise L.PcrError("Expected more than 1 value per channel when training, got input size %s" % (tuple(shape),))
+
+
 class BnAct(Function):
     """act(BatchNorm(y)) with BATCH statistics over (B, L) per channel on a (B,C,L) tensor; act: None, "relu" or
     ("leaky", slope).  Running statistics are updated in place as nn.BatchNorm1d does in training mode.  (The
@@ -1141,6 +1152,7 @@ class BnAct(Function):
         lib = L.load()
         if bn.momentum is None:
             raise L.PcrError("BatchNorm with momentum=None (cumulative average) is not supported by the HIP training path")
+        _require_batch(B * Ln, y.shape)
         nparts = max(1, min(B, 2048 // max(C, 1)))
         part = _f32(nparts, 2, _c32(C), device=y.device)
         # sums of y - y[0][c][0] (first element of the channel as the offset): see pcr_bn_fwd_fin.shift0
@@ -1204,6 +1216,7 @@ class EdgeConvTrain(Function):
         dev = tab.device
         if bn.momentum is None:
             raise L.PcrError("BatchNorm with momentum=None (cumulative average) is not supported by the HIP training path")
+        _require_batch(B * N * K, (B, Co, N, K))
         xyz0 = torch.zeros((B, N, 3), dtype=torch.float32, device=dev)       # (no coordinate term: zero weights below)
         wa0 = torch.zeros((Co, 3), dtype=torch.float32, device=dev)
         b0 = torch.zeros((Co,), dtype=torch.float32, device=dev)

@@ -206,6 +206,68 @@ int pcr_crop_boxes_f32(const float *points, int stride, const float *boxes, cons
                        float *clouds, int *lengths, int P, int M, int n, int frame, int rule, int z_is_centre,
                        pcr_stream_t stream);
 
+/* ------------------------------------------------------------ A3. association --------- */
+
+/* What the reference's tracker does on the host between the matching logits and the track update, as fixed-shape launches
+ * without a host read: the class-gated pair list (get_labels_to_compare, trackers/deprecated/tracking_point_reid.py:15-33),
+ * the augmented cost matrix (get_cost_mat_margin, tracking_association.py:22-53, :126-128) and the rectangular linear sum
+ * assignment it hands to scipy (:141).  Every output is the same bits on every run.  An entry with nothing to do (see each)
+ * returns PCR_OK, launches nothing and writes nothing.
+ *
+ * pcr_assoc_pairs_i32: track_labels (T), det_labels (D), optional track_lengths (T) / det_lengths (D) -> pairs (cap,2)
+ * int32 and count (1) int32.  (t, d) is listed iff track_labels[t] == det_labels[d], that label lies in [0, num_classes)
+ * and -- when the length pointers are not NULL (use_lengths) -- both lengths are >= min_points.  Order: class ascending,
+ * then track index ascending, then detection index ascending (torch.cat of the per-class cartesian_prod).  count is the
+ * TRUE number of pairs, also when it exceeds cap (then the first cap pairs are written); slots from count on hold (0, 0).
+ * Ranks come from ballots and LDS scans, no atomics.  pcr_assoc_pairs_ok: 0 <= T, D <= PCR_ASSOC_MAX_OBJECTS,
+ * 1 <= num_classes <= PCR_ASSOC_MAX_CLASSES, 0 <= cap <= PCR_ASSOC_MAX_OBJECTS^2.  Nothing to do: T == 0 or D == 0 (the
+ * list is empty; count and pairs are left as they are). */
+#define PCR_ASSOC_MAX_OBJECTS 4096
+#define PCR_ASSOC_MAX_CLASSES 32
+int pcr_assoc_pairs_ok(int T, int D, int num_classes, int cap);
+int pcr_assoc_pairs_i32(const int *track_labels, const int *det_labels, const int *track_lengths, const int *det_lengths,
+                        int *pairs, int *count, int T, int D, int num_classes, int min_points, int cap,
+                        pcr_stream_t stream);
+
+/* pcr_assoc_cost_f32: cost (T+D, D+T) row-major, EVERY element written (one tracking and one detection decision):
+ *   top-left (T,D):     -logits[k] at (t, d) = pairs[k] for k < min(count[0], cap), plus dist_penalty where dist != NULL and
+ *                       dist[t*D + d] > dist_max (the distance prior, :26-31); fill elsewhere;
+ *   top-right (T,T):    track_miss[t] on the diagonal, fill elsewhere;      bottom-left (D,D): det_new[d] likewise;
+ *   bottom-right (D,T): the transpose of the top-left block (:33-38).
+ * NULL track_miss / det_new are zeros.  The listed pairs must be distinct (pcr_assoc_pairs_i32's are); a pair outside
+ * [0,T) x [0,D) is skipped.  Range as pcr_assoc_pairs_ok(T, D, 1, cap).  Nothing to do: T + D == 0. */
+int pcr_assoc_cost_f32(const float *logits, const int *pairs, const int *count, const float *track_miss,
+                       const float *det_new, const float *dist, float dist_max, float dist_penalty, float fill,
+                       float *cost, int T, int D, int cap, pcr_stream_t stream);
+
+/* pcr_lsa_f32: rectangular linear sum assignment (minimum total) of B problems.  cost (B,R,C) -> col4row (B,R), row4col
+ * (B,C) (-1 = unassigned), info (B), and the duals u (B,R), v (B,C) unless NULL.  info 0: solved.  info 1: the problem
+ * holds a NaN or an infinity (found by a pre-scan): both index outputs are -1, the duals 0, the solver does not run.
+ * info 2: a search found no column (an intermediate value overflowed); outputs as for 1.
+ * pcr_lsa_ok: 0 <= R, C <= PCR_LSA_MAX, 0 <= B <= 65535.  Nothing to do: B, R or C == 0.
+ *
+ * The result is DEFINED by these rules, each operation rounded to binary32, nothing contracted (tests/assoc_ref.py::lsa
+ * restates them; the kernel equals it bit for bit, duals included):
+ *   transpose   shortest augmenting paths (Jonker-Volgenant) over the rows 0 .. R-1 in order; if R > C the transposed
+ *               problem is solved and the outputs are swapped back (col4row <-> row4col, u <-> v);
+ *   search      for row cur: minv = 0, short[] = +inf, no column done, i = cur; then repeat:
+ *     candidates  every column j not done gets r = ((c[i][j] - u[i]) - v[j]) + minv;
+ *     update      if r < short[j] (strict): short[j] = r, pred[j] = i;
+ *     selection   the next column is the not-done column with the lowest short, ties (by float comparison, -0 == +0) to
+ *                 the LOWEST column index; minv = its short; it is done; if it is unassigned it ends the search (the
+ *                 sink), otherwise i = its row;
+ *   duals       u[cur] += minv; for every done column j but the sink, with ri its row: u[ri] += (minv - short[j]);
+ *               for every done column j: v[j] -= (minv - short[j]);
+ *   augment     along pred from the sink back to cur.
+ * A search marks one more column done per step, so a problem takes at most min(R,C) * max(R,C) steps; every loop of the
+ * kernel is bounded by such an integer count.  One wave per problem: column j lives in lane j % 64 (short / pred / v /
+ * row4col and the done bits in registers), u and col4row in LDS, the matrix too when it fits beside them (R*C + 2*min(R,C)
+ * words in 160 KiB: 200 x 200 does), otherwise rows are read from global memory. */
+#define PCR_LSA_MAX 1024
+int pcr_lsa_ok(int B, int R, int C);
+int pcr_lsa_f32(const float *cost, int *col4row, int *row4col, float *u, float *v, int *info, int B, int R, int C,
+                pcr_stream_t stream);
+
 /* ------------------------------------------------- B. fused model kernels ------------ */
 
 /* Neighbour search of the "Point-Transformer" set-abstraction layers: centres are the first S

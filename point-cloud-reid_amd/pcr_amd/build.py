@@ -19,6 +19,7 @@ FLAGS = {
     "point_ops.hip": ["-ffp-contract=off"] + os.environ.get("PCR_POINT_FLAGS", "").split(),
     "edge_kernels.hip": ["-ffp-contract=off"],
     "crop_kernels.hip": ["-ffp-contract=off"],       # membership and box-frame coordinates are compared bit for bit
+    "assoc_kernels.hip": ["-ffp-contract=off"],      # the assignment's candidate values and duals are compared bit for bit
 }
 
 

@@ -39,23 +39,20 @@ def farthest_point_sample(xyz, npoint, start=None):
     start = start.to(device=xyz.device, dtype=torch.int32).contiguous()
     idx = torch.empty((B, npoint), dtype=torch.int32, device=xyz.device)
     temp = torch.full((B, N), 1e10, dtype=torch.float32, device=xyz.device)
-    L.check(L.load().pcr_fps_py_f32(L.ptr(xyz), L.ptr(temp), L.ptr(start), L.ptr(idx), B, N, npoint, L.stream_ptr()),
-            "pcr_fps_py_f32")
+    L.run.pcr_fps_py_f32(xyz, temp, start, idx, B, N, npoint, L.stream_ptr())
     return idx.long()
 
 
 def query_ball_point(radius, nsample, xyz, new_xyz):
     """(:218-240) first `nsample` points with d <= radius^2 (expanded-form distance) in index order, padded with the
     first -> (B,S,nsample) int64"""
-    import ctypes
     L.require_cuda(xyz, new_xyz)
     L.require_f32(xyz, new_xyz)
     xyz, new_xyz = xyz.contiguous(), new_xyz.contiguous()
     B, N, _ = xyz.shape
     S = new_xyz.shape[1]
     idx = torch.empty((B, S, nsample), dtype=torch.int32, device=xyz.device)
-    L.check(L.load().pcr_query_ball_point_f32(L.ptr(new_xyz), L.ptr(xyz), L.ptr(idx), B, N, S, ctypes.c_float(radius),
-                                              nsample, L.stream_ptr()), "pcr_query_ball_point_f32")
+    L.run.pcr_query_ball_point_f32(new_xyz, xyz, idx, B, N, S, radius, nsample, L.stream_ptr())
     return idx.long()
 
 

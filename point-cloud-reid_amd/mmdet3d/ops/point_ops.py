@@ -7,12 +7,12 @@ Reference wrappers mirrored (bentherien/point-cloud-reid, mmdet3d/ops/...):
   interpolate/three_nn.py:8-45, interpolate/three_interpolate.py:8-59.
 Index outputs are int32 and non-differentiable; index ops return None gradients.
 """
-import ctypes
 
 import torch
 from torch.autograd import Function
 
 from pcr_amd import _lib as L
+from pcr_amd._lib import _f32, _i32
 from pcr_amd.engine import _prof
 
 
@@ -30,14 +30,6 @@ def _on_device(fn):
     return staticmethod(wrapped)
 
 
-def _i32(*shape, device):
-    return torch.empty(shape, dtype=torch.int32, device=device)
-
-
-def _f32(*shape, device):
-    return torch.empty(shape, dtype=torch.float32, device=device)
-
-
 class FurthestPointSampling(Function):
     @_on_device
     def forward(ctx, points_xyz, num_points):
@@ -48,8 +40,7 @@ class FurthestPointSampling(Function):
         out = _i32(B, num_points, device=points_xyz.device)
         temp = torch.full((B, N), 1e10, dtype=torch.float32, device=points_xyz.device)
         with _prof("fps[N=%d,M=%d]" % (N, num_points), 8.0 * B * N * num_points, 4.0 * B * (3 * N + num_points)):
-            L.check(L.load().pcr_fps_f32(L.ptr(points_xyz), L.ptr(temp), L.ptr(out), B, N, num_points,
-                                         L.stream_ptr()), "pcr_fps_f32")
+            L.run.pcr_fps_f32(points_xyz, temp, out, B, N, num_points, L.stream_ptr())
         ctx.mark_non_differentiable(out)
         return out
 
@@ -67,8 +58,7 @@ class FurthestPointSamplingWithDist(Function):
         B, N, _ = points_dist.size()
         out = _i32(B, num_points, device=points_dist.device)
         temp = torch.full((B, N), 1e10, dtype=torch.float32, device=points_dist.device)
-        L.check(L.load().pcr_fps_dist_f32(L.ptr(points_dist), L.ptr(temp), L.ptr(out), B, N, num_points,
-                                          L.stream_ptr()), "pcr_fps_dist_f32")
+        L.run.pcr_fps_dist_f32(points_dist, temp, out, B, N, num_points, L.stream_ptr())
         ctx.mark_non_differentiable(out)
         return out
 
@@ -90,9 +80,8 @@ class BallQuery(Function):
         idx = _i32(B, npoint, sample_num, device=xyz.device)
         with _prof("ball_query[N=%d,M=%d,K=%d]" % (N, npoint, sample_num), 8.0 * B * N * npoint,
                    4.0 * B * (3 * N + 3 * npoint + npoint * sample_num)):
-            L.check(L.load().pcr_ball_query_f32(L.ptr(center_xyz), L.ptr(xyz), L.ptr(idx), B, N, npoint,
-                                                ctypes.c_float(min_radius), ctypes.c_float(max_radius),
-                                                sample_num, L.stream_ptr()), "pcr_ball_query_f32")
+            L.run.pcr_ball_query_f32(center_xyz, xyz, idx, B, N, npoint, min_radius, max_radius, sample_num,
+                                     L.stream_ptr())
         ctx.mark_non_differentiable(idx)
         return idx
 
@@ -118,9 +107,8 @@ class BallQueryCnt(Function):
         cnt = _i32(B, npoint, device=xyz.device)
         with _prof("ball_query[N=%d,M=%d,K=%d]" % (N, npoint, sample_num), 8.0 * B * N * npoint,
                    4.0 * B * (3 * N + 3 * npoint + npoint * sample_num)):
-            L.check(L.load().pcr_ball_query_cnt_f32(L.ptr(center_xyz), L.ptr(xyz), L.ptr(idx), L.ptr(cnt), B, N,
-                                                    npoint, ctypes.c_float(min_radius), ctypes.c_float(max_radius),
-                                                    sample_num, L.stream_ptr()), "pcr_ball_query_cnt_f32")
+            L.run.pcr_ball_query_cnt_f32(center_xyz, xyz, idx, cnt, B, N, npoint, min_radius, max_radius, sample_num,
+                                         L.stream_ptr())
         ctx.mark_non_differentiable(idx, cnt)
         return idx, cnt
 
@@ -144,9 +132,8 @@ def ball_query_rows(max_radius, sample_num, xyz, center_xyz, want_idx=False):
                            device=xyz.device)
         with _prof("ball_query[N=%d,M=%d,K=%d]" % (N, npoint, sample_num), 8.0 * B * N * npoint,
                    4.0 * B * (3 * N + 3 * npoint + npoint * sample_num)):
-            L.check(L.load().pcr_ball_query_rows_f32(L.ptr(center_xyz), L.ptr(xyz), L.ptr(idx), L.ptr(cnt), L.ptr(rows),
-                                                     B, N, npoint, ctypes.c_float(0.0), ctypes.c_float(max_radius),
-                                                     sample_num, L.stream_ptr()), "pcr_ball_query_rows_f32")
+            L.run.pcr_ball_query_rows_f32(center_xyz, xyz, idx, cnt, rows, B, N, npoint, 0.0, max_radius, sample_num,
+                                          L.stream_ptr())
     return idx, cnt, rows
 
 
@@ -170,9 +157,8 @@ def fps_ball_query_rows(xyz, num_points, max_radius, sample_num):
         rows = torch.empty((L.load().pcr_ball_query_rows_floats(B, num_points, sample_num),), dtype=torch.float32, device=dev)
         with _prof("fps_ball_query[N=%d,M=%d,K=%d]" % (N, num_points, sample_num), 8.0 * B * N * num_points,
                    4.0 * B * (3 * N + 4 * num_points + num_points * sample_num)):
-            L.check(L.load().pcr_fps_ball_query_rows_f32(L.ptr(xyz), L.ptr(temp), L.ptr(idx), L.ptr(new_xyz), L.ptr(cnt),
-                                                         L.ptr(rows), B, N, num_points, ctypes.c_float(max_radius),
-                                                         sample_num, L.stream_ptr()), "pcr_fps_ball_query_rows_f32")
+            L.run.pcr_fps_ball_query_rows_f32(xyz, temp, idx, new_xyz, cnt, rows, B, N, num_points, max_radius,
+                                              sample_num, L.stream_ptr())
     return idx, new_xyz, cnt, rows
 
 
@@ -194,8 +180,7 @@ class KNN(Function):
         N = xyz.shape[1]
         idx = _i32(B, npoint, k, device=xyz.device)
         dist2 = _f32(B, npoint, k, device=xyz.device)
-        L.check(L.load().pcr_knn_f32(L.ptr(xyz), L.ptr(center_xyz), L.ptr(idx), L.ptr(dist2), B, N,
-                                     npoint, k, L.stream_ptr()), "pcr_knn_f32")
+        L.run.pcr_knn_f32(xyz, center_xyz, idx, dist2, B, N, npoint, k, L.stream_ptr())
         idx = idx.transpose(2, 1).contiguous()      # (B, k, npoint) as in knn.py:62
         ctx.mark_non_differentiable(idx)
         return idx
@@ -216,8 +201,7 @@ class GatherPoints(Function):
         B, npoint = indices.size()
         _, C, N = features.size()
         out = _f32(B, C, npoint, device=features.device)
-        L.check(L.load().pcr_gather_fwd_f32(L.ptr(features), L.ptr(indices), L.ptr(out), B, C, N, npoint,
-                                            L.stream_ptr()), "pcr_gather_fwd_f32")
+        L.run.pcr_gather_fwd_f32(features, indices, out, B, C, N, npoint, L.stream_ptr())
         ctx.for_backwards = (indices, C, N)
         ctx.mark_non_differentiable(indices)
         return out
@@ -228,8 +212,7 @@ class GatherPoints(Function):
         B, npoint = idx.size()
         grad_features = torch.zeros(B, C, N, dtype=torch.float32, device=grad_out.device)
         g = grad_out.data.float().contiguous()
-        L.check(L.load().pcr_gather_bwd_f32(L.ptr(g), L.ptr(idx), L.ptr(grad_features), B, C, N, npoint,
-                                            L.stream_ptr()), "pcr_gather_bwd_f32")
+        L.run.pcr_gather_bwd_f32(g, idx, grad_features, B, C, N, npoint, L.stream_ptr())
         return grad_features, None
 
 
@@ -244,8 +227,7 @@ class GroupingOperation(Function):
         B, nfeatures, nsample = indices.size()
         _, C, N = features.size()
         out = _f32(B, C, nfeatures, nsample, device=features.device)
-        L.check(L.load().pcr_group_fwd_f32(L.ptr(features), L.ptr(indices), L.ptr(out), B, C, N, nfeatures,
-                                           nsample, L.stream_ptr()), "pcr_group_fwd_f32")
+        L.run.pcr_group_fwd_f32(features, indices, out, B, C, N, nfeatures, nsample, L.stream_ptr())
         ctx.for_backwards = (indices, N)
         return out
 
@@ -255,8 +237,7 @@ class GroupingOperation(Function):
         B, C, npoint, nsample = grad_out.size()
         grad_features = torch.zeros(B, C, N, dtype=torch.float32, device=grad_out.device)
         g = grad_out.data.float().contiguous()
-        L.check(L.load().pcr_group_bwd_f32(L.ptr(g), L.ptr(idx), L.ptr(grad_features), B, C, N, npoint,
-                                           nsample, L.stream_ptr()), "pcr_group_bwd_f32")
+        L.run.pcr_group_bwd_f32(g, idx, grad_features, B, C, N, npoint, nsample, L.stream_ptr())
         return grad_features, None
 
 
@@ -271,8 +252,7 @@ class ThreeNN(Function):
         m = source.size(1)
         dist2 = _f32(B, N, 3, device=target.device)
         idx = _i32(B, N, 3, device=target.device)
-        L.check(L.load().pcr_three_nn_f32(L.ptr(target), L.ptr(source), L.ptr(dist2), L.ptr(idx), B, N, m,
-                                          L.stream_ptr()), "pcr_three_nn_f32")
+        L.run.pcr_three_nn_f32(target, source, dist2, idx, B, N, m, L.stream_ptr())
         ctx.mark_non_differentiable(idx)
         return torch.sqrt(dist2), idx
 
@@ -294,8 +274,7 @@ class ThreeInterpolate(Function):
         n = indices.size(1)
         ctx.three_interpolate_for_backward = (indices, weight, m)
         out = _f32(B, c, n, device=features.device)
-        L.check(L.load().pcr_three_interp_fwd_f32(L.ptr(features), L.ptr(indices), L.ptr(weight), L.ptr(out),
-                                                  B, c, m, n, L.stream_ptr()), "pcr_three_interp_fwd_f32")
+        L.run.pcr_three_interp_fwd_f32(features, indices, weight, out, B, c, m, n, L.stream_ptr())
         return out
 
     @_on_device
@@ -304,8 +283,7 @@ class ThreeInterpolate(Function):
         B, c, n = grad_out.size()
         grad_features = torch.zeros(B, c, m, dtype=torch.float32, device=grad_out.device)
         g = grad_out.data.float().contiguous()
-        L.check(L.load().pcr_three_interp_bwd_f32(L.ptr(g), L.ptr(idx), L.ptr(weight), L.ptr(grad_features),
-                                                  B, c, n, m, L.stream_ptr()), "pcr_three_interp_bwd_f32")
+        L.run.pcr_three_interp_bwd_f32(g, idx, weight, grad_features, B, c, n, m, L.stream_ptr())
         return grad_features, None, None
 
 

@@ -54,8 +54,7 @@ def calc_square_dist(point_feat_a, point_feat_b, norm=True):
     B, N, C = a.shape
     M = b.shape[1]
     dist = torch.empty((B, N, M), dtype=torch.float32, device=a.device)
-    L.check(L.load().pcr_pairwise_sqdist_f32(L.ptr(a), L.ptr(b), L.ptr(dist), B, N, M, C, int(bool(norm)), L.stream_ptr()),
-            "pcr_pairwise_sqdist_f32")
+    L.run.pcr_pairwise_sqdist_f32(a, b, dist, B, N, M, C, int(bool(norm)), L.stream_ptr())
     return dist
 
 

@@ -26,8 +26,8 @@ def points_in_boxes_gpu(points, boxes):
         L.require_cuda(points, boxes)
         L.require_f32(points, boxes)
         box_idxs_of_pts = torch.empty((batch_size, num_points), dtype=torch.int, device=points.device)
-        L.check(L.load().pcr_points_in_boxes_f32(L.ptr(points), L.ptr(boxes), L.ptr(box_idxs_of_pts), batch_size,
-                                                 num_points, boxes.shape[1], L.stream_ptr()), "pcr_points_in_boxes_f32")
+        L.run.pcr_points_in_boxes_f32(points, boxes, box_idxs_of_pts, batch_size, num_points, boxes.shape[1],
+                                      L.stream_ptr())
     return box_idxs_of_pts
 
 
@@ -41,7 +41,6 @@ def points_in_boxes_batch(points, boxes):
         L.require_cuda(points, boxes)
         L.require_f32(points, boxes)
         box_idxs_of_pts = torch.empty((batch_size, num_points, num_boxes), dtype=torch.int, device=points.device)
-        L.check(L.load().pcr_points_in_boxes_batch_f32(L.ptr(points), L.ptr(boxes), L.ptr(box_idxs_of_pts), batch_size,
-                                                       num_points, num_boxes, L.stream_ptr()),
-                "pcr_points_in_boxes_batch_f32")
+        L.run.pcr_points_in_boxes_batch_f32(points, boxes, box_idxs_of_pts, batch_size, num_points, num_boxes,
+                                            L.stream_ptr())
     return box_idxs_of_pts

@@ -5,6 +5,8 @@ import os
 
 import torch  # must be imported before the library so that libamdhip64.so.7 resolves to torch's copy
 
+from . import abi
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # (PCR_LIB_TAG: a diagnostic build made by pcr_amd/build.py under the same variable, e.g. libpcr_hip_tune.so)
 _TAG = os.environ.get("PCR_LIB_TAG", "")
@@ -26,19 +28,39 @@ def load():
                 "libpcr_hip.so is not built (%s). Run `python -c 'import __graft_entry__ as g; g.build()'` "
                 "or `python point-cloud-reid_amd/pcr_amd/build.py`; there is no CPU fallback." % SO_PATH)
         lib = ctypes.CDLL(SO_PATH)
-        lib.pcr_status_string.restype = ctypes.c_char_p
-        lib.pcr_packed_weight_floats.restype = ctypes.c_long
-        lib.pcr_packed_weight_bf16_floats.restype = ctypes.c_long
-        lib.pcr_attn_kv_floats.restype = ctypes.c_long
-        lib.pcr_sa_tile_ws_ints.restype = ctypes.c_long
-        lib.pcr_sa_claim_ws_ints.restype = ctypes.c_long
-        lib.pcr_ball_query_rows_floats.restype = ctypes.c_long
         if lib.pcr_abi_version() != ABI_VERSION:
             raise PcrError("libpcr_hip.so ABI %d != binding %d: rebuild" % (lib.pcr_abi_version(), ABI_VERSION))
+        for name, sig in abi.SIGNATURES.items():         # every prototype of include/pcr.h, once
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = abi.prototype(sig)
+            if sig[0] == "s":
+                setattr(run, name, _checked(name))
         if os.environ.get("PCR_STREAM_MIN_BLOCKS"):      # launch policy of the train-dense kernels (include/pcr.h)
             lib.pcr_set_stream_min_blocks(int(os.environ["PCR_STREAM_MIN_BLOCKS"]))
         _lib = lib
     return _lib
+
+
+def _checked(name):
+    def call(*args):
+        status = getattr(load(), name)(*args)            # through load(), so that whoever substitutes it sees the call
+        if status != 0:
+            raise PcrError("%s failed: %s" % (name, _lib.pcr_status_string(status).decode()))
+    return call
+
+
+class _Run:
+    """`run.pcr_x(args...)`: `load().pcr_x(args...)`, raising PcrError on a nonzero status.  load() puts one callable per
+    status-returning entry point on the instance; this hook only serves the first use before the library is loaded."""
+
+    def __getattr__(self, name):
+        if _lib is not None or name not in abi.SIGNATURES:
+            raise AttributeError(name)
+        load()
+        return getattr(self, name)
+
+
+run = _Run()
 
 
 def stream_ptr():
@@ -49,6 +71,27 @@ def ptr(t):
     if t is None:
         return ctypes.c_void_p(0)
     return ctypes.c_void_p(t.data_ptr())
+
+
+def _p(t):
+    """address for a pointer FIELD of a parameter block (the blocks hold plain addresses; None = NULL)"""
+    return None if t is None else t.data_ptr()
+
+
+def _c8(n):
+    return (n + 7) // 8 * 8
+
+
+def _c32(n):
+    return (n + 31) // 32 * 32
+
+
+def _f32(*shape, device):
+    return torch.empty(shape, dtype=torch.float32, device=device)
+
+
+def _i32(*shape, device):
+    return torch.empty(shape, dtype=torch.int32, device=device)
 
 
 def check(status, what):

@@ -1,0 +1,266 @@
+"""The C ABI of libpcr_hip.so (include/pcr.h) as Python sees it, in ONE place: the parameter blocks, the two device-table
+record layouts, and the signature of every entry point.  `_lib.load()` applies SIGNATURES to the loaded library;
+tests/test_abi.py holds every line of this file against the header (prototypes by a parse, layouts by a compiled
+sizeof / offsetof probe)."""
+import ctypes
+
+import numpy as np
+import torch
+
+_CTYPES = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "long": ctypes.c_long,
+           "ptr": ctypes.c_void_p}
+
+
+def _block(name, decl):
+    """ctypes mirror of a pcr.h parameter block.  `decl` follows the header's struct body, one `type field field ...`
+    group per `;` (ptr = any data pointer: the launches fill them with addresses, `_lib._p`; ptr[n] = an array of n)."""
+    fields = []
+    for group in decl.split(";"):
+        ty, *names = group.split()
+        base, _, n = ty.partition("[")
+        ct = _CTYPES[base] * int(n[:-1]) if n else _CTYPES[base]
+        fields += [(f, ct) for f in names]
+    return type(name, (ctypes.Structure,), {"_fields_": fields})
+
+
+# ---- section B (pcr_sa_params, pcr_attn_params, pcr_head_params) ----
+SaParams = _block("SaParams", """
+    int mode B N S K D c1 c2 c3; ptr xyz feat idx centre_idx; ptr[3] wp scale shift; ptr wa wpq; ptr[2] wps shift_pad;
+    ptr cnt tile_ws pq_ws; int pq_ready feat_point_major out_point_major; ptr out wa_packed; int precision;
+    ptr[2] wps_bf; ptr wa_shift_packed row_tab claim_ws; int pq_has_xyz""")
+AttnParams = _block("AttnParams", """
+    int B Lq Sk c1 c2 d cout nhead q_pos residual; ptr feat_q xyz_q feat_k xyz_k kv_index q_index pos0_w pos0_b;
+    ptr wq bq wkv bkv wmerge wmlp0 wmlp2 ln1_g ln1_b ln2_g ln2_b wfinal bfinal; int cfinal;
+    ptr wkv_wide bkv_wide wmerge_packed kv out; int precision; ptr wq_bf wmlp0_bf wmlp2_bf wfinal_bf; int kv_splits;
+    ptr kv_part wkv_bf wmlp0_bf_xpad pool_out""")
+HeadParams = _block("HeadParams", """
+    int P C L groups; ptr o w1 w2 gn1_g gn1_b gn2_g gn2_b w_out b_out pooled logits w1t w2t""")
+
+# ---- section C (pcr_tdense_fwd / _bwd, pcr_bn_fwd_fin / _bwd_fin, pcr_reduce_job, pcr_linattn, pcr_attn_tail / _head) ----
+_TFwd = _block("_TFwd", """
+    int B cin1 cin2 cout L; ptr x x2 isc ish; int in_relu; ptr wp bias res; int out_relu; ptr y stats; int pool_K;
+    ptr pool_gamma pool_ymax pool_arg""")
+_TBwd = _block("_TBwd", """
+    int B cin1 cin2 cout L; ptr g y; int dy_mode; ptr ka kb kc argmax pooled; int K S; ptr x x2 isc ish iinv; int in_relu;
+    ptr wpT dx dx2 dstats dwp dbp; long part_stride; int precision; ptr wpT_bf""")
+_BnFwd = _block("_BnFwd", """
+    ptr part; int nparts C; double R; ptr gamma beta; float eps momentum;
+    ptr running_mean running_var scale shift inv_scale mean invstd shift0; int shift0_stride""")
+_BnBwd = _block("_BnBwd", """
+    ptr part; int nparts C; double R; ptr gamma mean invstd ka kb kc dgamma dbeta centre""")
+_ReduceJob = _block("_ReduceJob", "ptr part out; long stride; int nparts rows cols ld")
+_LinAttnP = _block("_LinAttnP", """
+    int B Lq Sk d H; float eps; ptr q k v; long q_bs k_bs v_bs; ptr out A ks dout dq dk dv; long dq_bs dk_bs dv_bs;
+    int kv_roll""")
+_AttnTailP = _block("_AttnTailP", """
+    int B L d c1 hid out residual; float eps; ptr msg res wm w0 w2 wmT w0T w2T g1 b1 g2 b2 outp dout dmsg dres parts;
+    long part_stride; int precision fwd_precision""")
+_AttnHeadP = _block("_AttnHeadP", """
+    int B L c hd d np src; ptr x xyz p1 p2 c1 c2 p2T; ptr[3] w wT; ptr outp dout dx parts; long part_stride;
+    int precision fwd_precision""")
+
+# the header's name of every block (what the layout test compiles against)
+BLOCKS = {"pcr_sa_params": SaParams, "pcr_attn_params": AttnParams, "pcr_head_params": HeadParams,
+          "pcr_tdense_fwd": _TFwd, "pcr_tdense_bwd": _TBwd, "pcr_bn_fwd_fin": _BnFwd, "pcr_bn_bwd_fin": _BnBwd,
+          "pcr_reduce_job": _ReduceJob, "pcr_linattn": _LinAttnP, "pcr_attn_tail": _AttnTailP,
+          "pcr_attn_head": _AttnHeadP}
+
+# ---- records of the DEVICE tables (built with numpy on the host, uploaded as bytes) ----
+pcr_pack_desc = np.dtype([("w", "<u8"), ("out", "<u8"), ("rows", "<i4"), ("cols", "<i4"), ("kind", "<i4"),
+                          ("reserved", "<i4")])
+pcr_opt_tensor = np.dtype([("p", "<u8"), ("g", "<u8"), ("m", "<u8"), ("v", "<u8"), ("n", "<i8"), ("step_size", "<f4"),
+                           ("bc2_sqrt", "<f4"), ("decay", "<f4"), ("one_m_beta1", "<f4"), ("beta2", "<f4"),
+                           ("one_m_beta2", "<f4"), ("eps", "<f4"), ("pad_", "<f4")])
+TABLES = {"pcr_pack_desc": pcr_pack_desc, "pcr_opt_tensor": pcr_opt_tensor}
+
+
+# ---- pointer parameters that take a tensor ----
+class _TensorPtr:
+    """argtype of a `float *` / `int *` parameter.  Accepts None (NULL), a device tensor of `dtype` on the current device
+    (strided views included: the callers pass an explicit ld), a Python int address (`data_ptr() + 4 * off`), and
+    anything ctypes itself takes for a void pointer (c_void_p, byref, arrays: host images).  Any other tensor raises,
+    which ctypes reports as ArgumentError with the argument's index before the call is made.  A tensor of another dtype
+    that is meant to go in (index bits in a float table) takes the explicit unchecked route, `_lib.ptr(t)`."""
+    dtype = None
+
+    @classmethod
+    def from_param(cls, v):
+        if isinstance(v, torch.Tensor):
+            if v.dtype is not cls.dtype:
+                raise TypeError("expected a %s tensor, got %s" % (cls.dtype, v.dtype))
+            if not v.is_cuda or v.device.index != torch.cuda.current_device():
+                raise TypeError("expected a tensor on the current GPU, got one on %s" % v.device)
+            return ctypes.c_void_p(v.data_ptr())
+        if v is None:
+            return None
+        if isinstance(v, int):
+            return ctypes.c_void_p(v)
+        return ctypes.c_void_p.from_param(v)
+
+
+class FloatPtr(_TensorPtr):
+    dtype = torch.float32
+
+
+class IntPtr(_TensorPtr):
+    dtype = torch.int32
+
+
+# ---- every prototype of pcr.h: "<return> <one letter per parameter>" ----
+#   return     s status int (0 = ok; `_lib.run.<name>` raises on anything else)   i int   l long   c char *
+#   parameter  i int   f float   l long   S stream   F float *   I int *   P any other pointer (double *, long long *,
+#              a device table)   <Block> pointer to that parameter block
+SIGNATURES = {
+    "pcr_abi_version": "i ",
+    "pcr_status_string": "c i",
+    # A. point ops
+    "pcr_fps_f32": "s FFIiiiS",
+    "pcr_fps_dist_f32": "s FFIiiiS",
+    "pcr_pairwise_sqdist_f32": "s FFFiiiiiS",
+    "pcr_ball_query_f32": "s FFIiiiffiS",
+    "pcr_ball_query_cnt_f32": "s FFIIiiiffiS",
+    "pcr_ball_query_rows_floats": "l iii",
+    "pcr_ball_query_rows_ok": "i iif",
+    "pcr_ball_query_rows_f32": "s FFIIFiiiffiS",
+    "pcr_fps_ball_query_rows_ok": "i iii",
+    "pcr_fps_ball_query_rows_f32": "s FFIFIFiiifiS",
+    "pcr_fps_py_f32": "s FFIIiiiS",
+    "pcr_query_ball_point_f32": "s FFIiiifiS",
+    "pcr_knn_f32": "s FFIFiiiiS",
+    "pcr_gather_fwd_f32": "s FIFiiiiS",
+    "pcr_gather_bwd_f32": "s FIFiiiiS",
+    "pcr_group_fwd_f32": "s FIFiiiiiS",
+    "pcr_group_bwd_f32": "s FIFiiiiiS",
+    "pcr_three_nn_f32": "s FFFIiiiS",
+    "pcr_three_interp_fwd_f32": "s FIFFiiiiS",
+    "pcr_three_interp_bwd_f32": "s FIFFiiiiS",
+    # A2. points in boxes, crops
+    "pcr_box_frames_f32": "s FFiS",
+    "pcr_points_in_boxes_batch_f32": "s FFIiiiS",
+    "pcr_points_in_boxes_f32": "s FFIiiiS",
+    "pcr_crop_boxes_ok": "i iiii",
+    "pcr_crop_boxes_f32": "s FiFIPFIiiiiiiS",
+    # A3. association
+    "pcr_assoc_pairs_ok": "i iiii",
+    "pcr_assoc_pairs_i32": "s IIIIIIiiiiiS",
+    "pcr_assoc_cost_f32": "s FIIFFFfffFiiiS",
+    "pcr_lsa_ok": "i iii",
+    "pcr_lsa_f32": "s FIIFFIiiiS",
+    # B. fused model kernels
+    "pcr_knn_prefix_f32": "s FIiiiiS",
+    "pcr_knn_prefix2_f32": "s FIIiiiiiiS",
+    "pcr_packed_weight_floats": "l ii",
+    "pcr_pack_weight_f32": "s FiiF",
+    "pcr_packed_weight_bf16_floats": "l ii",
+    "pcr_pack_weight_bf16x2_f32": "s FiiF",
+    "pcr_sa_mlp_f32": "s <SaParams>S",
+    "pcr_sa_claim_ws_ints": "l iiiiii",
+    "pcr_sa_tile_ws_ints": "l iiiii",
+    "pcr_sa_krow_uses_tiles": "i iiiii",
+    "pcr_sa_uses_row_table": "i iiiii",
+    "pcr_dense_pm_f32": "s FFFiiiiiS",
+    "pcr_dense_pm_prec_f32": "s FFFiiiiiiS",
+    "pcr_dense_pm_xyz_f32": "s FFFFFiiiiiiiiS",
+    "pcr_sa_tables_take_xyz": "i iiiiiii",
+    "pcr_attn_kv_floats": "l i",
+    "pcr_attn_kv_splits": "i iii",
+    "pcr_attn_kv_f32": "s <AttnParams>S",
+    "pcr_attn_apply_f32": "s <AttnParams>S",
+    "pcr_attn_apply_pool_ok": "i <AttnParams>",
+    "pcr_pool_head_f32": "s <HeadParams>S",
+    "pcr_pool_both_f32": "s FFiiiS",
+    "pcr_channel_max_f32": "s FFiiiiS",
+    "pcr_dense_f32": "s FFFFFiiiiiS",
+    "pcr_dense_xpm_f32": "s FFFFFiiiiiS",
+    "pcr_dense_gn_f32": "s FFFFFFiiiiiiS",
+    "pcr_dense_prec_ok": "i iii",
+    "pcr_dense_prec_f32": "s FFFFFiiiiiiS",
+    "pcr_dense_gn_prec_f32": "s FFFFFFiiiiiiiS",
+    "pcr_dense_xpm_prec_ok": "i iii",
+    "pcr_dense_xpm_prec_f32": "s FFFFFiiiiiiS",
+    "pcr_max_over_l_f32": "s FFiiiS",
+    "pcr_dense_max_ok": "i iii",
+    "pcr_dense_max_f32": "s FFFFFiiiiiS",
+    "pcr_pack_bmm_f32": "s FFiiS",
+    "pcr_dense_bmm_f32": "s FFFiiiiS",
+    "pcr_groupnorm_f32": "s FFFFFiiiiiS",
+    "pcr_knn_feat_f32": "s FFIiiiilS",
+    "pcr_edge_max_f32": "s FFIFfFlFliiiiS",
+    "pcr_local_attn_f32": "s FIFiiiiifS",
+    # C. training-mode kernels
+    "pcr_pack_weight_dev_f32": "s FiiiiFS",
+    "pcr_train_groups": "i ii",
+    "pcr_train_groups_bwd": "i iiii",
+    "pcr_tdense_fwd_groups": "i <_TFwd>",
+    "pcr_tdense_bwd_groups": "i <_TBwd>",
+    "pcr_set_stream_min_blocks": "i i",
+    "pcr_tdense_fwd_f32": "s <_TFwd>S",
+    "pcr_tdense_fwd_pooled": "i <_TFwd>",
+    "pcr_tdense_bwd_f32": "s <_TBwd>S",
+    "pcr_pack_weight_bf16_dev_f32": "s FiiiiFS",
+    "pcr_local_attn_train_fwd_f32": "s FIFiiiiifS",
+    "pcr_local_attn_train_bwd_f32": "s FIFFlFiiiiifS",
+    "pcr_reduce_parts_f32": "s FiliiiFS",
+    "pcr_reduce_multi_f32": "s <_ReduceJob>iS",
+    "pcr_bn_fwd_finalize_f32": "s <_BnFwd>S",
+    "pcr_bn_bwd_finalize_f32": "s <_BnBwd>S",
+    "pcr_sa_l1_fwd_f32": "s FIFFFFFiiiiiS",
+    "pcr_sa_l1_bwd_f32": "s FIFFFFFFFiiiiiS",
+    "pcr_sa_pool_fwd_f32": "s FFFFIFiiiiS",
+    "pcr_sa_pool_bwd_stats_f32": "s FFFFFiiiS",
+    "pcr_tnorm_fwd_f32": "s FFFFFFFiiiifiS",
+    "pcr_tnorm_bwd_f32": "s FFFFFFFFFiiiiS",
+    "pcr_linattn_fwd_f32": "s <_LinAttnP>S",
+    "pcr_linattn_bwd_f32": "s <_LinAttnP>S",
+    "pcr_attn_tail_ok": "i iiiii",
+    "pcr_attn_tail_part_floats": "i iiii",
+    "pcr_attn_tail_groups": "i <_AttnTailP>",
+    "pcr_attn_tail_fwd_f32": "s <_AttnTailP>S",
+    "pcr_attn_tail_bwd_f32": "s <_AttnTailP>S",
+    "pcr_attn_head_ok": "i iiiii",
+    "pcr_attn_head_part_floats": "i iiiii",
+    "pcr_attn_head_groups": "i <_AttnHeadP>",
+    "pcr_attn_head_fwd_f32": "s <_AttnHeadP>S",
+    "pcr_attn_head_bwd_f32": "s <_AttnHeadP>S",
+    "pcr_pool_pair_fwd_f32": "s FFIiiiS",
+    "pcr_pool_pair_bwd_f32": "s FIFiiiS",
+    "pcr_pool_both_fwd_f32": "s FFIiiiS",
+    "pcr_pool_both_bwd_f32": "s FIFiiiS",
+    "pcr_channel_max_fwd_f32": "s FFIiiiiS",
+    "pcr_channel_max_bwd_f32": "s FIFiiiiS",
+    "pcr_bn_sums_f32": "s FFFFifFiFiiiiS",
+    "pcr_bn_affine_f32": "s FFFFFFFFifFiiiS",
+    "pcr_edge_pool_fwd_f32": "s FFFfFIFiiiiS",
+    "pcr_edge_pool_route_f32": "s FFIfFiiiiS",
+    "pcr_bmm_apply_f32": "s FFFiiiiS",
+    "pcr_bmm_dt_f32": "s FFFiiiS",
+    "pcr_pack_weights_multi_f32": "s PiS",
+    "pcr_opt_chunk": "i ",
+    "pcr_grad_sumsq_f32": "s PIIiPS",
+    "pcr_adamw_step_f32": "s PIIiPfFS",
+    # measurement aid
+    "pcr_wall_clock_khz": "i ",
+    "pcr_last_launch_arith": "i ",
+    "pcr_clock_probe": "s PiiS",
+}
+
+_RETURN = {"s": ctypes.c_int, "i": ctypes.c_int, "l": ctypes.c_long, "c": ctypes.c_char_p}
+_KIND = {"i": ctypes.c_int, "f": ctypes.c_float, "l": ctypes.c_long, "S": ctypes.c_void_p, "P": ctypes.c_void_p,
+         "F": FloatPtr, "I": IntPtr}
+
+
+def kinds(sig):
+    """"s FI<SaParams>S" -> ("s", ["F", "I", "<SaParams>", "S"])"""
+    ret, _, params = sig.partition(" ")
+    out, i = [], 0
+    while i < len(params):
+        j = params.index(">", i) + 1 if params[i] == "<" else i + 1
+        out.append(params[i:j])
+        i = j
+    return ret, out
+
+
+def prototype(sig):
+    """-> (restype, argtypes) of a SIGNATURES entry"""
+    ret, params = kinds(sig)
+    return _RETURN[ret], [_KIND[k] if k in _KIND else ctypes.POINTER(globals()[k[1:-1]]) for k in params]

@@ -55,8 +55,8 @@ def compare_pairs(track_labels, det_labels, track_lengths=None, det_lengths=None
         pairs.zero_()
         count.zero_()
         return pairs, count
-    L.check(lib.pcr_assoc_pairs_i32(L.ptr(tl), L.ptr(dl), L.ptr(tn), L.ptr(dn), L.ptr(pairs), L.ptr(count), T, D,
-                                    int(num_classes), int(min_points), cap, L.stream_ptr()), "pcr_assoc_pairs_i32")
+    L.run.pcr_assoc_pairs_i32(tl, dl, tn, dn, pairs, count, T, D, int(num_classes), int(min_points), cap,
+                              L.stream_ptr())
     return pairs, count
 
 
@@ -84,11 +84,8 @@ def association_cost(logits, pairs, count, T, D, track_miss=None, det_new=None, 
     if out is None:
         out = torch.empty((T + D, D + T), dtype=torch.float32, device=logits.device)
     assert out.shape == (T + D, D + T) and out.is_contiguous()
-    import ctypes
-    f = ctypes.c_float
-    L.check(lib.pcr_assoc_cost_f32(L.ptr(logits), L.ptr(pairs), L.ptr(count), L.ptr(track_miss), L.ptr(det_new),
-                                   L.ptr(dist), f(dist_max), f(dist_penalty), f(fill), L.ptr(out), T, D, cap,
-                                   L.stream_ptr()), "pcr_assoc_cost_f32")
+    L.run.pcr_assoc_cost_f32(logits, pairs, count, track_miss, det_new, dist, dist_max, dist_penalty, fill, out, T, D, cap,
+                             L.stream_ptr())
     return out
 
 
@@ -133,6 +130,5 @@ def linear_assignment(cost, return_duals=False, out=None):
             u.zero_()
             v.zero_()
     else:
-        L.check(lib.pcr_lsa_f32(L.ptr(cost), L.ptr(col4row), L.ptr(row4col), L.ptr(u), L.ptr(v), L.ptr(info), B, R, C,
-                                L.stream_ptr()), "pcr_lsa_f32")
+        L.run.pcr_lsa_f32(cost, col4row, row4col, u, v, info, B, R, C, L.stream_ptr())
     return (col4row, row4col, info, u, v) if return_duals else (col4row, row4col, info)

@@ -28,7 +28,7 @@ def box_frames(boxes, out=None):
     if out is None:
         out = torch.empty((T, 2), dtype=torch.float32, device=boxes.device)
     assert out.shape == (T, 2) and out.is_contiguous()
-    L.check(L.load().pcr_box_frames_f32(L.ptr(boxes), L.ptr(out), T, L.stream_ptr()), "pcr_box_frames_f32")
+    L.run.pcr_box_frames_f32(boxes, out, T, L.stream_ptr())
     return out
 
 
@@ -82,9 +82,8 @@ def crops_from_boxes(points, boxes, n, frame="box", rule="tracker", rand=None, s
     else:
         clouds = torch.empty((M, n, 3), dtype=torch.float32, device=dev)
         lengths = torch.empty((M,), dtype=torch.int32, device=dev)
-    L.check(L.load().pcr_crop_boxes_f32(L.ptr(points), stride, L.ptr(boxes), L.ptr(rand), L.ptr(seed_t), L.ptr(clouds),
-                                        L.ptr(lengths), P, M, n, FRAMES[frame], RULES[rule], int(bool(z_is_centre)),
-                                        L.stream_ptr()), "pcr_crop_boxes_f32")
+    L.run.pcr_crop_boxes_f32(points, stride, boxes, rand, L.ptr(seed_t), clouds, lengths, P, M, n, FRAMES[frame],
+                             RULES[rule], int(bool(z_is_centre)), L.stream_ptr())
     if return_frames:
         fr = box_frames(boxes, out[2] if out is not None and len(out) > 2 else None)
         return clouds, lengths, fr

@@ -3,7 +3,6 @@ pcr_knn_feat_f32 (feature-space kNN on the matrix core + wave selection) -> 2 x 
 of the decomposed conv: s.W [f_j - f_i; f_i] = (s.W1) f_j + (s.(W2 - W1)) f_i) -> pcr_edge_max_f32 (gather, max over
 the k neighbours, BatchNorm shift, LeakyReLU).  The (B,2C,N,k) edge tensor of the reference is never built; the four
 layer outputs are written straight into their slices of the (B,512,N) conv5 input."""
-import ctypes
 
 import torch
 
@@ -39,8 +38,7 @@ def knn_feat(x, k, bstride=0):
     xx = torch.empty((B, N), dtype=torch.float32, device=x.device)
     idx = torch.empty((B, N, k), dtype=torch.int32, device=x.device)
     with E._prof("knn_feat[C=%d,N=%d]" % (C, N), 2.0 * B * N * N * C, 4.0 * B * N * (C + k)):
-        L.check(L.load().pcr_knn_feat_f32(L.ptr(x), L.ptr(xx), L.ptr(idx), B, C, N, k, ctypes.c_long(bstride),
-                                          L.stream_ptr()), "pcr_knn_feat_f32")
+        L.run.pcr_knn_feat_f32(x, xx, idx, B, C, N, k, bstride, L.stream_ptr())
     return idx
 
 
@@ -48,8 +46,7 @@ def _table(x, wp, co):
     B, cin, N = x.shape
     y = torch.empty((B, N, co), dtype=torch.float32, device=x.device)
     with E._prof("edge_tables", 2.0 * B * N * cin * co, 4.0 * B * N * (cin + co)):
-        L.check(L.load().pcr_dense_pm_f32(L.ptr(x), L.ptr(wp), L.ptr(y), B, cin, co, N, 0, L.stream_ptr()),
-                "pcr_dense_pm_f32")
+        L.run.pcr_dense_pm_f32(x, wp, y, B, cin, co, N, 0, L.stream_ptr())
     return y
 
 
@@ -73,7 +70,6 @@ def forward(net, xyz, stages=None):
     if p.k > N:
         raise L.PcrError("DGCNN: k=%d neighbours need at least that many points (N=%d)" % (p.k, N))
     cat = torch.empty((B, p.cat, N), dtype=torch.float32, device=x.device)
-    lib = L.load()
     off = 0
     f = x
     for c, co, wa, wb, sh in p.layers:
@@ -81,9 +77,8 @@ def forward(net, xyz, stages=None):
         ta, tb = _table(f, wa, co), _table(f, wb, co)
         out = torch.empty((B, co, N), dtype=torch.float32, device=x.device)
         with E._prof("edge_max", 0.0, 4.0 * B * N * (co * (p.k + 3) + p.k)):
-            L.check(lib.pcr_edge_max_f32(L.ptr(ta), L.ptr(tb), L.ptr(idx), L.ptr(sh), ctypes.c_float(0.2),
-                                         L.ptr(out), ctypes.c_long(0), L.ptr(cat[:, off:off + co]),
-                                         ctypes.c_long(p.cat * N), B, N, co, p.k, L.stream_ptr()), "pcr_edge_max_f32")
+            L.run.pcr_edge_max_f32(ta, tb, idx, sh, 0.2, out, 0, cat[:, off:off + co], p.cat * N, B, N, co, p.k,
+                                   L.stream_ptr())
         off += co
         f = out
         if stages is not None:

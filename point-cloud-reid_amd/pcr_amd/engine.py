@@ -10,9 +10,8 @@ import numpy as np
 import torch
 
 from . import _lib as L
-
-c_float_p = ctypes.c_void_p
-c_int_p = ctypes.c_void_p
+from ._lib import _p
+from .abi import AttnParams, HeadParams, SaParams
 
 # Arithmetic of the MFMA-bound layers (include/pcr.h PCR_PREC_*):
 #   "f32"    f32-input MFMA, exact fmaf chains (the reference's arithmetic, 157 TFLOP/s peak);
@@ -163,52 +162,6 @@ class _prof:
         return False
 
 
-class SaParams(ctypes.Structure):
-    _fields_ = [("mode", ctypes.c_int), ("B", ctypes.c_int), ("N", ctypes.c_int), ("S", ctypes.c_int),
-                ("K", ctypes.c_int), ("D", ctypes.c_int),
-                ("c1", ctypes.c_int), ("c2", ctypes.c_int), ("c3", ctypes.c_int),
-                ("xyz", c_float_p), ("feat", c_float_p), ("idx", c_int_p), ("centre_idx", c_int_p),
-                ("wp", c_float_p * 3), ("scale", c_float_p * 3), ("shift", c_float_p * 3),
-                ("wa", c_float_p), ("wpq", c_float_p), ("wps", c_float_p * 2), ("shift_pad", c_float_p * 2),
-                ("cnt", c_int_p), ("tile_ws", c_int_p),
-                ("pq_ws", c_float_p), ("pq_ready", ctypes.c_int),
-                ("feat_point_major", ctypes.c_int), ("out_point_major", ctypes.c_int),
-                ("out", c_float_p), ("wa_packed", c_float_p),
-                ("precision", ctypes.c_int), ("wps_bf", c_float_p * 2), ("wa_shift_packed", c_float_p),
-                ("row_tab", c_float_p), ("claim_ws", c_int_p), ("pq_has_xyz", ctypes.c_int)]
-
-
-class AttnParams(ctypes.Structure):
-    _fields_ = [("B", ctypes.c_int), ("Lq", ctypes.c_int), ("Sk", ctypes.c_int),
-                ("c1", ctypes.c_int), ("c2", ctypes.c_int), ("d", ctypes.c_int), ("cout", ctypes.c_int),
-                ("nhead", ctypes.c_int), ("q_pos", ctypes.c_int), ("residual", ctypes.c_int),
-                ("feat_q", c_float_p), ("xyz_q", c_float_p), ("feat_k", c_float_p), ("xyz_k", c_float_p),
-                ("kv_index", c_int_p), ("q_index", c_int_p),
-                ("pos0_w", c_float_p), ("pos0_b", c_float_p),
-                ("wq", c_float_p), ("bq", c_float_p), ("wkv", c_float_p), ("bkv", c_float_p),
-                ("wmerge", c_float_p), ("wmlp0", c_float_p), ("wmlp2", c_float_p),
-                ("ln1_g", c_float_p), ("ln1_b", c_float_p), ("ln2_g", c_float_p), ("ln2_b", c_float_p),
-                ("wfinal", c_float_p), ("bfinal", c_float_p), ("cfinal", ctypes.c_int),
-                ("wkv_wide", c_float_p), ("bkv_wide", c_float_p), ("wmerge_packed", c_float_p),
-                ("kv", c_float_p), ("out", c_float_p),
-                ("precision", ctypes.c_int),
-                ("wq_bf", c_float_p), ("wmlp0_bf", c_float_p), ("wmlp2_bf", c_float_p), ("wfinal_bf", c_float_p),
-                ("kv_splits", ctypes.c_int), ("kv_part", c_float_p), ("wkv_bf", c_float_p),
-                ("wmlp0_bf_xpad", c_float_p), ("pool_out", c_float_p)]
-
-
-class HeadParams(ctypes.Structure):
-    _fields_ = [("P", ctypes.c_int), ("C", ctypes.c_int), ("L", ctypes.c_int), ("groups", ctypes.c_int),
-                ("o", c_float_p), ("w1", c_float_p), ("w2", c_float_p),
-                ("gn1_g", c_float_p), ("gn1_b", c_float_p), ("gn2_g", c_float_p), ("gn2_b", c_float_p),
-                ("w_out", c_float_p), ("b_out", c_float_p),
-                ("pooled", c_float_p), ("logits", c_float_p), ("w1t", c_float_p), ("w2t", c_float_p)]
-
-
-def _p(t):
-    return t.data_ptr() if t is not None else None
-
-
 def _dev32(t, device):
     return t.detach().to(device=device, dtype=torch.float32).contiguous()
 
@@ -220,8 +173,7 @@ def pack_weight(w, device):
     lib = L.load()
     n = lib.pcr_packed_weight_floats(cout, cin)
     out = np.empty(n, np.float32)
-    L.check(lib.pcr_pack_weight_f32(w2.ctypes.data_as(ctypes.c_void_p), cout, cin,
-                                    out.ctypes.data_as(ctypes.c_void_p)), "pcr_pack_weight_f32")
+    L.run.pcr_pack_weight_f32(w2.ctypes.data_as(ctypes.c_void_p), cout, cin, out.ctypes.data_as(ctypes.c_void_p))
     return torch.from_numpy(out).to(device)
 
 
@@ -232,8 +184,8 @@ def pack_weight_bf(w, device):
     lib = L.load()
     n = lib.pcr_packed_weight_bf16_floats(cout, cin)
     out = np.empty(n, np.float32)
-    L.check(lib.pcr_pack_weight_bf16x2_f32(w2.ctypes.data_as(ctypes.c_void_p), cout, cin,
-                                           out.ctypes.data_as(ctypes.c_void_p)), "pcr_pack_weight_bf16x2_f32")
+    L.run.pcr_pack_weight_bf16x2_f32(w2.ctypes.data_as(ctypes.c_void_p), cout, cin,
+                                     out.ctypes.data_as(ctypes.c_void_p))
     return torch.from_numpy(out).to(device)
 
 
@@ -269,8 +221,7 @@ def knn_prefix(xyz, S, K):
     B, N, _ = xyz.shape
     idx = torch.empty((B, S, K), dtype=torch.int32, device=xyz.device)
     with _prof("knn_prefix[N=%d,S=%d,K=%d]" % (N, S, K), 8.0 * B * S * N, 12.0 * B * N + 4.0 * B * S * K):
-        L.check(L.load().pcr_knn_prefix_f32(L.ptr(xyz), L.ptr(idx), B, N, S, K, L.stream_ptr()),
-                "pcr_knn_prefix_f32")
+        L.run.pcr_knn_prefix_f32(xyz, idx, B, N, S, K, L.stream_ptr())
     return idx
 
 
@@ -286,8 +237,7 @@ def knn_prefix2(xyz, S, K, S2, K2):
     idx2 = torch.empty((B, S2, K2), dtype=torch.int32, device=xyz.device)
     with _prof("knn_prefix2[N=%d,S=%d,K=%d,S2=%d,K2=%d]" % (N, S, K, S2, K2), 8.0 * B * S * N,
                12.0 * B * N + 4.0 * B * (S * K + S2 * K2)):
-        L.check(L.load().pcr_knn_prefix2_f32(L.ptr(xyz), L.ptr(idx), L.ptr(idx2), B, N, S, K, S2, K2, L.stream_ptr()),
-                "pcr_knn_prefix2_f32")
+        L.run.pcr_knn_prefix2_f32(xyz, idx, idx2, B, N, S, K, S2, K2, L.stream_ptr())
     return idx, idx2
 
 
@@ -349,7 +299,7 @@ class SaPlan:
         lib = L.load()
         if os.environ.get("PCR_SA_NO_STREAM") or int(B) * int(S) >= 2 ** 31:
             return False
-        return bool(self.fast and self.mode == 1 and lib.pcr_ball_query_rows_ok(N, K, ctypes.c_float(min_radius or 0.0)) and
+        return bool(self.fast and self.mode == 1 and lib.pcr_ball_query_rows_ok(N, K, min_radius or 0.0) and
                     lib.pcr_sa_uses_row_table(self.couts[0], self.couts[1], self.couts[2], K, PRECISIONS[PRECISION]))
 
     def run(self, xyz, feat, idx, centre_idx=None, cnt=None, out_point_major=False, rows=None, K=None):
@@ -421,8 +371,7 @@ class SaPlan:
                 with _prof("sa_tables[D=%d,out=%d,N=%d]" % (D, pqw, N), 2.0 * B * N * D * pqw,
                            4.0 * B * N * (D + pqw), arith="lib"):
                     if PRECISION == "f32":
-                        L.check(L.load().pcr_dense_pm_f32(L.ptr(feat), L.ptr(self.wpq), L.ptr(ws), B, D, pqw, N,
-                                                          int(feat_pm), L.stream_ptr()), "pcr_dense_pm_f32")
+                        L.run.pcr_dense_pm_f32(feat, self.wpq, ws, B, D, pqw, N, int(feat_pm), L.stream_ptr())
                     elif (SA_XYZ_TABLES and not ragged and not tiled and idx is not None and
                           L.load().pcr_sa_tables_take_xyz(self.mode, D, c1_, c2_, c3_, K, PRECISIONS[PRECISION])):
                         # the K-row kernel's shapes: tables WITH the coordinate term and the shift (exact f32 fmas on top of
@@ -430,15 +379,13 @@ class SaPlan:
                         # (prefix sampling: the centres are the first S points, and only centres' Q rows are ever read)
                         q_rows = min(N, (S + 63) // 64 * 64) if centre_idx is None else N
                         q_rows = q_rows if q_rows % 64 == 0 else N
-                        L.check(L.load().pcr_dense_pm_xyz_f32(L.ptr(feat), L.ptr(self.wpq_bf), L.ptr(xyz), L.ptr(self.wxyz),
-                                                              L.ptr(ws), B, D, pqw, N, int(feat_pm), PRECISIONS[PRECISION],
-                                                              q_rows, c1_ if q_rows < N else pqw,
-                                                              L.stream_ptr()), "pcr_dense_pm_xyz_f32")
+                        L.run.pcr_dense_pm_xyz_f32(feat, self.wpq_bf, xyz, self.wxyz, ws, B, D, pqw, N, int(feat_pm),
+                                                   PRECISIONS[PRECISION], q_rows, c1_ if q_rows < N else pqw,
+                                                   L.stream_ptr())
                         p.pq_has_xyz = 1
                     else:   # the tables on the bf16 matrix core too (the layer-1 MFMAs on the coordinates stay f32)
-                        L.check(L.load().pcr_dense_pm_prec_f32(L.ptr(feat), L.ptr(self.wpq_bf), L.ptr(ws), B, D, pqw, N,
-                                                               int(feat_pm), PRECISIONS[PRECISION], L.stream_ptr()),
-                                "pcr_dense_pm_prec_f32")
+                        L.run.pcr_dense_pm_prec_f32(feat, self.wpq_bf, ws, B, D, pqw, N, int(feat_pm),
+                                                    PRECISIONS[PRECISION], L.stream_ptr())
                 p.pq_ready = 1
         c1, c2, c3 = self.couts
         flops = 2.0 * B * S * K * (self.cin * c1 + c1 * c2 + c2 * c3)
@@ -450,7 +397,7 @@ class SaPlan:
         name = "sa_ragged" if ragged else "sa_fused"
         with _prof("%s[D=%d,c=%d/%d/%d,N=%d,S=%d,K=%d]" % (name, D, c1, c2, c3, N, S, K), flops, nbytes, exec_flops,
                    arith="lib"):
-            L.check(L.load().pcr_sa_mlp_f32(ctypes.byref(p), L.stream_ptr()), "pcr_sa_mlp_f32")
+            L.run.pcr_sa_mlp_f32(ctypes.byref(p), L.stream_ptr())
         return out.transpose(1, 2) if out_point_major else out
 
 
@@ -558,7 +505,7 @@ class AttnPlan:
         kv_flops = 2.0 * B * Sk * (3 * d + d * c2 + 2 * c2 * d + d * d / self.nhead)   # reference's op count
         with _prof("attn_kv[d=%d,c2=%d,Sk=%d]" % (d, c2, Sk), kv_flops, 4.0 * B * (c2 * Sk + 3 * Sk + d * d + d),
                    arith="lib"):
-            L.check(lib.pcr_attn_kv_f32(ctypes.byref(p), L.stream_ptr()), "pcr_attn_kv_f32")
+            L.run.pcr_attn_kv_f32(ctypes.byref(p), L.stream_ptr())
         kv._pcr_precision = PRECISION      # the per-cloud matrix is an image of this kind: apply() must match
         return kv
 
@@ -598,7 +545,7 @@ class AttnPlan:
                                    + self.cout * self.cfinal + (self.q_pos * (3 * d + d * c1)))
         with _prof("attn_apply[d=%d,c1=%d,out=%d,Lq=%d%s]" % (d, c1, self.cfinal or self.cout, Lq, ",pooled" if pooled else ""),
                    ap_flops, 4.0 * B * (c1 * Lq + d * d + d + (2 if pooled else Lq) * (self.cfinal or self.cout)), arith="lib"):
-            L.check(L.load().pcr_attn_apply_f32(ctypes.byref(p), L.stream_ptr()), "pcr_attn_apply_f32")
+            L.run.pcr_attn_apply_f32(ctypes.byref(p), L.stream_ptr())
         return out
 
     def run(self, feat_q, xyz_q, feat_k, xyz_k, kv_index=None):
@@ -640,7 +587,7 @@ class HeadPlan:
             setattr(p, k, _p(v))
         p.pooled, p.logits = _p(pooled), _p(logits)
         with _prof("pool_head", 4.0 * P * (2 * C) ** 2, 4.0 * twoP * C * Lp):
-            L.check(L.load().pcr_pool_head_f32(ctypes.byref(p), L.stream_ptr()), "pcr_pool_head_f32")
+            L.run.pcr_pool_head_f32(ctypes.byref(p), L.stream_ptr())
         return (logits, pooled) if want_pooled else logits
 
 
@@ -669,19 +616,18 @@ def dense(x, wp, cout, scale=None, shift=None, act=0):
         # the wide per-point layers (PointNet convs, DGCNN conv5, LinearRes rows) on the bf16 matrix core
         with _prof("dense[cin=%d,cout=%d,L=%d]" % (cin, cout, Ln), 2.0 * B * Ln * cin * cout, 4.0 * B * Ln * (cin + cout),
                    arith=PRECISION):
-            L.check(lib.pcr_dense_prec_f32(L.ptr(x), L.ptr(bf), L.ptr(scale), L.ptr(shift), L.ptr(y), B, cin, cout, Ln, act,
-                                           PRECISIONS[PRECISION], L.stream_ptr()), "pcr_dense_prec_f32")
+            L.run.pcr_dense_prec_f32(x, bf, scale, shift, y, B, cin, cout, Ln, act, PRECISIONS[PRECISION],
+                                     L.stream_ptr())
         return y
     if PRECISION != "f32" and bf is not None and x_pm and lib.pcr_dense_xpm_prec_ok(cin, cout, Ln):
         # a point-major tensor (the last SA layer's output) straight into the bf16 matrix core: a token's row is the operand
         with _prof("dense[cin=%d,cout=%d,L=%d]" % (cin, cout, Ln), 2.0 * B * Ln * cin * cout, 4.0 * B * Ln * (cin + cout),
                    arith="lib"):
-            L.check(lib.pcr_dense_xpm_prec_f32(L.ptr(x), L.ptr(bf), L.ptr(scale), L.ptr(shift), L.ptr(y), B, cin, cout, Ln,
-                                               act, PRECISIONS[PRECISION], L.stream_ptr()), "pcr_dense_xpm_prec_f32")
+            L.run.pcr_dense_xpm_prec_f32(x, bf, scale, shift, y, B, cin, cout, Ln, act, PRECISIONS[PRECISION],
+                                         L.stream_ptr())
         return y
-    fn = lib.pcr_dense_xpm_f32 if x_pm else lib.pcr_dense_f32
+    fn = L.run.pcr_dense_xpm_f32 if x_pm else L.run.pcr_dense_f32
     with _prof("dense[cin=%d,cout=%d,L=%d]" % (cin, cout, Ln), 2.0 * B * Ln * cin * cout, 4.0 * B * Ln * (cin + cout),
                arith="f32"):
-        L.check(fn(L.ptr(x), L.ptr(wp), L.ptr(scale), L.ptr(shift), L.ptr(y), B, cin, cout, Ln, act, L.stream_ptr()),
-                "pcr_dense_f32")
+        fn(x, wp, scale, shift, y, B, cin, cout, Ln, act, L.stream_ptr())
     return y

@@ -4,7 +4,6 @@ pcr_dense_pm_f32 (q | k | v of feat + pos(xyz) for every POINT, point-major: the
 (B*N, K, C) neighbour tensor, i.e. every point's key / value K times) -> pcr_local_attn_f32 (one query token per
 point over its K neighbours) -> merge + LayerNorm, feed-forward on cat[feat, msg], LayerNorm + residual through the
 dense / group-norm kernels (LayerNorm over C channels per token = GroupNorm with one group)."""
-import ctypes
 import types
 
 import torch
@@ -60,14 +59,11 @@ def forward(m, feat, xyz):
     h = E.dense(xyz.contiguous().float().transpose(1, 2), p.w1, p.hid, None, p.b1, act=1)        # (B,hid,N)
     x = torch.cat([feat, h, torch.ones((B, 1, N), dtype=torch.float32, device=feat.device)], dim=1)
     qkv = torch.empty((B, N, 3 * C), dtype=torch.float32, device=feat.device)
-    lib = L.load()
     with E._prof("local_qkv", 2.0 * B * N * x.shape[1] * 3 * C, 4.0 * B * N * (x.shape[1] + 3 * C)):
-        L.check(lib.pcr_dense_pm_f32(L.ptr(x), L.ptr(p.wqkv), L.ptr(qkv), B, x.shape[1], 3 * C, N, 0, L.stream_ptr()),
-                "pcr_dense_pm_f32")
+        L.run.pcr_dense_pm_f32(x, p.wqkv, qkv, B, x.shape[1], 3 * C, N, 0, L.stream_ptr())
     msg = torch.empty((B, C, N), dtype=torch.float32, device=feat.device)
     with E._prof("local_attn", 4.0 * B * N * m.knum * C, 4.0 * B * N * (m.knum * (2 * C + 1) + 2 * C)):
-        L.check(lib.pcr_local_attn_f32(L.ptr(qkv), L.ptr(idx), L.ptr(msg), B, N, C, m.knum, m.nhead,
-                                       ctypes.c_float(1e-6), L.stream_ptr()), "pcr_local_attn_f32")
+        L.run.pcr_local_attn_f32(qkv, idx, msg, B, N, C, m.knum, m.nhead, 1e-6, L.stream_ptr())
     m1 = rows.dense_gn(msg, p.wm, C, p.ln1)
     f = E.dense(torch.cat([feat, m1], dim=1), p.wf0, 2 * C, act=1)
     return rows.dense_gn(f, p.wf2, C, p.ln2, res=feat)

@@ -7,17 +7,12 @@ torch.optim.AdamW.step() (reference configs_reid/_base_/schedules/cyclic_200e_lr
 pt128_train shape); here the norm never leaves the device.  `state_dict()` has torch.optim.AdamW's layout (per
 parameter: step, exp_avg, exp_avg_sq), so checkpoints move between the two.
 """
-import ctypes
-
 import numpy as np
 import torch
 
 from . import _lib as L
+from .abi import pcr_opt_tensor
 
-_TAB = np.dtype([("p", "<u8"), ("g", "<u8"), ("m", "<u8"), ("v", "<u8"), ("n", "<i8"), ("step_size", "<f4"),
-                 ("bc2_sqrt", "<f4"), ("decay", "<f4"), ("one_m_beta1", "<f4"), ("beta2", "<f4"),
-                 ("one_m_beta2", "<f4"), ("eps", "<f4"), ("pad_", "<f4")])
-assert _TAB.itemsize == 72
 _RING = 8
 
 
@@ -54,15 +49,15 @@ class FusedAdamW(torch.optim.Optimizer):
             for first in range(0, p.numel(), chunk):
                 ct.append(i)
                 cf.append(first)
-        tab = np.zeros(len(ts), dtype=_TAB)
+        tab = np.zeros(len(ts), dtype=pcr_opt_tensor)
         tab["p"] = [p.data_ptr() for _, p in ts]
         tab["n"] = [p.numel() for _, p in ts]
         plan = dict(ts=ts, dev=dev, tab=tab, n_chunks=len(ct),
                     chunk_tensor=torch.tensor(ct, dtype=torch.int32, device=dev),
                     chunk_first=torch.tensor(cf, dtype=torch.int32, device=dev),
                     part=torch.empty(max(len(ct), 1), dtype=torch.float64, device=dev),
-                    tab_dev=torch.empty(len(ts) * _TAB.itemsize, dtype=torch.uint8, device=dev),
-                    ring=[torch.empty(len(ts) * _TAB.itemsize, dtype=torch.uint8).pin_memory() for _ in range(_RING)],
+                    tab_dev=torch.empty(len(ts) * pcr_opt_tensor.itemsize, dtype=torch.uint8, device=dev),
+                    ring=[torch.empty(len(ts) * pcr_opt_tensor.itemsize, dtype=torch.uint8).pin_memory() for _ in range(_RING)],
                     events=[None] * _RING,
                     steps=np.zeros(len(ts), dtype=np.int64), have_state=[False] * len(ts))
         for i, (_, p) in enumerate(ts):       # state that a checkpoint brought in
@@ -133,18 +128,16 @@ class FusedAdamW(torch.optim.Optimizer):
         ev = torch.cuda.Event()
         ev.record()
         plan["events"][k] = ev
-        lib, stream = L.load(), L.stream_ptr()
-        tab_p = ctypes.c_void_p(plan["tab_dev"].data_ptr())
+        stream = L.stream_ptr()
+        tab_p = L.ptr(plan["tab_dev"])        # (a byte image of pcr_opt_tensor records, doubles: no typed slot)
         norm = None
         part = None
         if max_norm is not None:
             norm = torch.empty(1, dtype=torch.float32, device=plan["dev"])
-            part = ctypes.c_void_p(plan["part"].data_ptr())
-            L.check(lib.pcr_grad_sumsq_f32(tab_p, L.ptr(plan["chunk_tensor"]), L.ptr(plan["chunk_first"]),
-                                           plan["n_chunks"], part, stream), "pcr_grad_sumsq_f32")
-        L.check(lib.pcr_adamw_step_f32(tab_p, L.ptr(plan["chunk_tensor"]), L.ptr(plan["chunk_first"]),
-                                       plan["n_chunks"], part, ctypes.c_float(max_norm if max_norm is not None else 0.0),
-                                       L.ptr(norm) if norm is not None else None, stream), "pcr_adamw_step_f32")
+            part = L.ptr(plan["part"])
+            L.run.pcr_grad_sumsq_f32(tab_p, plan["chunk_tensor"], plan["chunk_first"], plan["n_chunks"], part, stream)
+        L.run.pcr_adamw_step_f32(tab_p, plan["chunk_tensor"], plan["chunk_first"], plan["n_chunks"], part,
+                                 max_norm if max_norm is not None else 0.0, norm, stream)
         # the kernels write through raw pointers: tell autograd / every cache keyed by Tensor._version (inference launch
         # plans, padded biases) that these tensors changed, as an in-place torch op would
         torch.autograd.graph.increment_version([p for i, (_, p) in enumerate(ts) if live[i]])

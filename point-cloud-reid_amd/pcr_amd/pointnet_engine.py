@@ -45,23 +45,22 @@ class _StnPlan:
             # conv3 + BN + ReLU + max over the points in one launch: the (B,1024,N) tensor is never written
             with E._prof("dense_max[cin=%d,cout=%d,L=%d]" % (cin, C, Ln), 2.0 * B * Ln * cin * C, 4.0 * B * (Ln * cin + C),
                          arith="f32"):
-                L.check(lib.pcr_dense_max_f32(L.ptr(x), L.ptr(wp), L.ptr(sc), L.ptr(sh), L.ptr(g), B, cin, C, Ln, 1,
-                                              L.stream_ptr()), "pcr_dense_max_f32")
+                L.run.pcr_dense_max_f32(x, wp, sc, sh, g, B, cin, C, Ln, 1, L.stream_ptr())
         else:
             x = E.dense(x, wp, C, sc, sh, act=1)
-            L.check(lib.pcr_max_over_l_f32(L.ptr(x), L.ptr(g), B, C, x.shape[2], L.stream_ptr()), "pcr_max_over_l_f32")
+            L.run.pcr_max_over_l_f32(x, g, B, C, x.shape[2], L.stream_ptr())
         for wp, cout, sc, sh, act in self.fcs:
             g = E.dense(g, wp, cout, sc, sh, act=act)
         lib = L.load()
         img = torch.empty((B, lib.pcr_packed_weight_floats(self.k, self.k)), dtype=torch.float32, device=x.device)
-        L.check(lib.pcr_pack_bmm_f32(L.ptr(g), L.ptr(img), B, self.k, L.stream_ptr()), "pcr_pack_bmm_f32")
+        L.run.pcr_pack_bmm_f32(g, img, B, self.k, L.stream_ptr())
         return img
 
 
 def _bmm(x, img, k):
     B, _, N = x.shape
     y = torch.empty((B, k, N), dtype=torch.float32, device=x.device)
-    L.check(L.load().pcr_dense_bmm_f32(L.ptr(x), L.ptr(img), L.ptr(y), B, k, k, N, L.stream_ptr()), "pcr_dense_bmm_f32")
+    L.run.pcr_dense_bmm_f32(x, img, y, B, k, k, N, L.stream_ptr())
     return y
 
 

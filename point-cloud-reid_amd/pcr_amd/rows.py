@@ -10,7 +10,7 @@ def pool_both(x):
     x = x.contiguous()
     B, C, Ln = x.shape
     out = torch.empty((B, 2 * C), dtype=torch.float32, device=x.device)
-    L.check(L.load().pcr_pool_both_f32(L.ptr(x), L.ptr(out), B, C, Ln, L.stream_ptr()), "pcr_pool_both_f32")
+    L.run.pcr_pool_both_f32(x, out, B, C, Ln, L.stream_ptr())
     return out
 
 
@@ -24,7 +24,7 @@ def pool_channel_max(x, window):
         raise L.PcrError("MaxPool1d(%d) over %d channels has no output" % (window, C))
     G = C // window
     out = torch.empty((B, Ln, G), dtype=torch.float32, device=x.device)
-    L.check(L.load().pcr_channel_max_f32(L.ptr(x), L.ptr(out), B, C, Ln, window, L.stream_ptr()), "pcr_channel_max_f32")
+    L.run.pcr_channel_max_f32(x, out, B, C, Ln, window, L.stream_ptr())
     return out.squeeze(-1)
 
 
@@ -41,8 +41,7 @@ def groupnorm(x, gn, res=None, relu=False):
     y = torch.empty_like(x)
     g = gn.weight.detach().to(x.device).float().contiguous()
     b = gn.bias.detach().to(x.device).float().contiguous()
-    L.check(L.load().pcr_groupnorm_f32(L.ptr(x), L.ptr(g), L.ptr(b), L.ptr(res), L.ptr(y), B, C, Ln, gn.num_groups,
-                                       1 if relu else 0, L.stream_ptr()), "pcr_groupnorm_f32")
+    L.run.pcr_groupnorm_f32(x, g, b, res, y, B, C, Ln, gn.num_groups, 1 if relu else 0, L.stream_ptr())
     return y
 
 
@@ -80,14 +79,12 @@ def dense_gn(x, wp, cout, gn, res=None, relu=False):
     if _E.PRECISION != "f32" and bf is not None and L.load().pcr_dense_prec_ok(cin, cout, Ln):
         with _E._prof("dense_gn[cin=%d,cout=%d,L=%d]" % (cin, cout, Ln), 2.0 * B * Ln * cin * cout,
                       4.0 * B * Ln * (cin + cout * (2 if res is not None else 1)), arith=_E.PRECISION):
-            L.check(L.load().pcr_dense_gn_prec_f32(L.ptr(x), L.ptr(bf), L.ptr(g), L.ptr(b), L.ptr(res), L.ptr(y), B, cin,
-                                                   cout, Ln, gn.num_groups, 1 if relu else 0,
-                                                   _E.PRECISIONS[_E.PRECISION], L.stream_ptr()), "pcr_dense_gn_prec_f32")
+            L.run.pcr_dense_gn_prec_f32(x, bf, g, b, res, y, B, cin, cout, Ln, gn.num_groups, 1 if relu else 0,
+                                        _E.PRECISIONS[_E.PRECISION], L.stream_ptr())
         return y
     with _E._prof("dense_gn[cin=%d,cout=%d,L=%d]" % (cin, cout, Ln), 2.0 * B * Ln * cin * cout,
                   4.0 * B * Ln * (cin + cout * (2 if res is not None else 1)), arith="f32"):
-        L.check(L.load().pcr_dense_gn_f32(L.ptr(x), L.ptr(wp), L.ptr(g), L.ptr(b), L.ptr(res), L.ptr(y), B, cin, cout,
-                                          Ln, gn.num_groups, 1 if relu else 0, L.stream_ptr()), "pcr_dense_gn_f32")
+        L.run.pcr_dense_gn_f32(x, wp, g, b, res, y, B, cin, cout, Ln, gn.num_groups, 1 if relu else 0, L.stream_ptr())
     return y
 
 

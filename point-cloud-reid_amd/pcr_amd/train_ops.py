@@ -14,57 +14,11 @@ import torch
 from torch.autograd import Function
 
 from . import _lib as L
+from ._lib import _c8, _c32, _f32, _p
+from .abi import _AttnHeadP, _AttnTailP, _BnBwd, _BnFwd, _LinAttnP, _ReduceJob, _TBwd, _TFwd, pcr_pack_desc
 from .engine import _prof
 
-c_fp = ctypes.c_void_p
 FUSE_POOL = True       # SaEdgeTrain: take the max over K inside the last layer's launch where the library offers it
-
-
-def _c32(n):
-    return (n + 31) // 32 * 32
-
-
-def _c8(n):
-    return (n + 7) // 8 * 8
-
-
-class _TFwd(ctypes.Structure):
-    _fields_ = [("B", ctypes.c_int), ("cin1", ctypes.c_int), ("cin2", ctypes.c_int), ("cout", ctypes.c_int),
-                ("L", ctypes.c_int), ("x", c_fp), ("x2", c_fp), ("isc", c_fp), ("ish", c_fp), ("in_relu", ctypes.c_int),
-                ("wp", c_fp), ("bias", c_fp), ("res", c_fp), ("out_relu", ctypes.c_int), ("y", c_fp), ("stats", c_fp),
-                ("pool_K", ctypes.c_int), ("pool_gamma", c_fp), ("pool_ymax", c_fp), ("pool_arg", c_fp)]
-
-
-class _TBwd(ctypes.Structure):
-    _fields_ = [("B", ctypes.c_int), ("cin1", ctypes.c_int), ("cin2", ctypes.c_int), ("cout", ctypes.c_int),
-                ("L", ctypes.c_int), ("g", c_fp), ("y", c_fp), ("dy_mode", ctypes.c_int),
-                ("ka", c_fp), ("kb", c_fp), ("kc", c_fp), ("argmax", c_fp), ("pooled", c_fp),
-                ("K", ctypes.c_int), ("S", ctypes.c_int), ("x", c_fp), ("x2", c_fp),
-                ("isc", c_fp), ("ish", c_fp), ("iinv", c_fp), ("in_relu", ctypes.c_int), ("wpT", c_fp),
-                ("dx", c_fp), ("dx2", c_fp), ("dstats", c_fp), ("dwp", c_fp), ("dbp", c_fp), ("part_stride", ctypes.c_long),
-                ("precision", ctypes.c_int), ("wpT_bf", c_fp)]
-
-
-class _BnFwd(ctypes.Structure):
-    _fields_ = [("part", c_fp), ("nparts", ctypes.c_int), ("C", ctypes.c_int), ("R", ctypes.c_double),
-                ("gamma", c_fp), ("beta", c_fp), ("eps", ctypes.c_float), ("momentum", ctypes.c_float),
-                ("running_mean", c_fp), ("running_var", c_fp),
-                ("scale", c_fp), ("shift", c_fp), ("inv_scale", c_fp), ("mean", c_fp), ("invstd", c_fp),
-                ("shift0", c_fp), ("shift0_stride", ctypes.c_int)]
-
-
-class _BnBwd(ctypes.Structure):
-    _fields_ = [("part", c_fp), ("nparts", ctypes.c_int), ("C", ctypes.c_int), ("R", ctypes.c_double),
-                ("gamma", c_fp), ("mean", c_fp), ("invstd", c_fp),
-                ("ka", c_fp), ("kb", c_fp), ("kc", c_fp), ("dgamma", c_fp), ("dbeta", c_fp), ("centre", c_fp)]
-
-
-def _p(t):
-    return None if t is None else t.data_ptr()
-
-
-def _f32(*shape, device):
-    return torch.empty(shape, dtype=torch.float32, device=device)
 
 
 def _dev(t):
@@ -98,8 +52,7 @@ class _Prepack:
         self.biases = {}           # id(bias) -> [param, version, zero-padded image]
         self.want_bf &= {p.data_ptr() for p in params}
         desc = np.zeros(len(params) + len(biases) + len(self.want_bf),
-                        dtype=np.dtype([("w", "<u8"), ("out", "<u8"), ("rows", "<i4"), ("cols", "<i4"), ("kind", "<i4"),
-                                        ("reserved", "<i4")]))
+                        dtype=pcr_pack_desc)
         nbf = 0
         for i, p in enumerate(params):
             rows, cols = p.shape[0], p.numel() // p.shape[0]
@@ -148,8 +101,7 @@ class _Prepack:
         elif build_only or all(e[3] == e[0]._version for e in self.entries.values()) and \
                 all(e[1] == e[0]._version for e in self.biases.values()):
             return        # nothing changed since the last refresh (micro-steps of a gradient accumulation)
-        L.check(L.load().pcr_pack_weights_multi_f32(ctypes.c_void_p(self.descs.data_ptr()), self.ndesc,
-                                                    L.stream_ptr()), "pcr_pack_weights_multi_f32")
+        L.run.pcr_pack_weights_multi_f32(L.ptr(self.descs), self.ndesc, L.stream_ptr())
         for e in self.entries.values():
             e[3] = e[0]._version
         for e in self.biases.values():
@@ -216,8 +168,7 @@ def pack_dev(w, transpose=False):
     rows, cols = w.shape
     cout, cin = (cols, rows) if transpose else (rows, cols)
     out = _f32(_c8(cin) * _c32(cout), device=w.device)
-    L.check(L.load().pcr_pack_weight_dev_f32(L.ptr(w), rows, cols, cols, int(transpose), L.ptr(out), L.stream_ptr()),
-            "pcr_pack_weight_dev_f32")
+    L.run.pcr_pack_weight_dev_f32(w, rows, cols, cols, int(transpose), out, L.stream_ptr())
     return out
 
 
@@ -230,8 +181,7 @@ def pack_both(w):
     rows, cols = w.shape
     n0, n1 = _c8(cols) * _c32(rows), _c8(rows) * _c32(cols)
     out = _f32(n0 + n1, device=w.device)
-    L.check(L.load().pcr_pack_weight_dev_f32(L.ptr(w), rows, cols, cols, 2, L.ptr(out), L.stream_ptr()),
-            "pcr_pack_weight_dev_f32")
+    L.run.pcr_pack_weight_dev_f32(w, rows, cols, cols, 2, out, L.stream_ptr())
     return out[:n0], out[n0:]
 
 
@@ -300,7 +250,7 @@ def tdense_fwd(x, wp, cout, x2=None, isc=None, ish=None, in_relu=False, bias=Non
     cin = cin1 + cin2
     with _prof("tdense_fwd[cin=%d,cout=%d,L=%d]" % (cin, cout, Ln), 2.0 * B * Ln * cin * cout,
                4.0 * B * Ln * (cin + cout * (2 if res is not None else 1)), arith="lib"):
-        L.check(L.load().pcr_tdense_fwd_f32(ctypes.byref(p), L.stream_ptr()), "pcr_tdense_fwd_f32")
+        L.run.pcr_tdense_fwd_f32(ctypes.byref(p), L.stream_ptr())
     if pool is not None:
         return y, stats, pooled
     return y, stats
@@ -308,8 +258,7 @@ def tdense_fwd(x, wp, cout, x2=None, isc=None, ish=None, in_relu=False, bias=Non
 
 def reduce_parts(part, nparts, stride, rows, cols, ld):
     out = _f32(rows, cols, device=part.device)
-    L.check(L.load().pcr_reduce_parts_f32(L.ptr(part), nparts, ctypes.c_long(stride), rows, cols, ld, L.ptr(out),
-                                          L.stream_ptr()), "pcr_reduce_parts_f32")
+    L.run.pcr_reduce_parts_f32(part, nparts, stride, rows, cols, ld, out, L.stream_ptr())
     return out
 
 
@@ -320,11 +269,6 @@ def reduce_parts(part, nparts, stride, rows, cols, ld):
 # reductions of a backward pass to one launch at its end through an autograd-engine callback.  It measured no faster --
 # the cost is the bytes of the partial records, not the ~35 launches -- and it is only safe for a parameter used ONCE in
 # the graph: a second use makes the engine add the still-unreduced buffer.)
-class _ReduceJob(ctypes.Structure):
-    _fields_ = [("part", c_fp), ("out", c_fp), ("stride", ctypes.c_long), ("nparts", ctypes.c_int), ("rows", ctypes.c_int),
-                ("cols", ctypes.c_int), ("ld", ctypes.c_int)]
-
-
 def reduce_regions(part, nparts, stride, regions):
     """regions [(offset in floats, rows, cols, ld)] of every partial record -> compact (rows, cols) tensors, summed over the
     nparts records (increasing record order, fixed: bit-reproducible)"""
@@ -333,7 +277,7 @@ def reduce_regions(part, nparts, stride, regions):
     jobs = [_ReduceJob(part.data_ptr() + 4 * off, o.data_ptr(), stride, nparts, rows, cols, ld)
             for (off, rows, cols, ld), o in zip(regions, outs)]
     arr = (_ReduceJob * len(jobs))(*jobs)
-    L.check(L.load().pcr_reduce_multi_f32(arr, len(jobs), L.stream_ptr()), "pcr_reduce_multi_f32")
+    L.run.pcr_reduce_multi_f32(arr, len(jobs), L.stream_ptr())
     return outs
 
 
@@ -381,10 +325,8 @@ def pack_both_bf(w):
     lib = L.load()
     a = _f32(lib.pcr_packed_weight_bf16_floats(rows, cols), device=wd.device)
     b = _f32(lib.pcr_packed_weight_bf16_floats(cols, rows), device=wd.device)
-    L.check(lib.pcr_pack_weight_bf16_dev_f32(L.ptr(wd), rows, cols, cols, 0, L.ptr(a), L.stream_ptr()),
-            "pcr_pack_weight_bf16_dev_f32")
-    L.check(lib.pcr_pack_weight_bf16_dev_f32(L.ptr(wd), rows, cols, cols, 1, L.ptr(b), L.stream_ptr()),
-            "pcr_pack_weight_bf16_dev_f32")
+    L.run.pcr_pack_weight_bf16_dev_f32(wd, rows, cols, cols, 0, a, L.stream_ptr())
+    L.run.pcr_pack_weight_bf16_dev_f32(wd, rows, cols, cols, 1, b, L.stream_ptr())
     return a, b
 
 
@@ -394,8 +336,7 @@ def pack_bf_T(w):
     wd = _dev(w.detach())
     rows, cols = wd.shape
     out = _f32(L.load().pcr_packed_weight_bf16_floats(cols, rows), device=wd.device)
-    L.check(L.load().pcr_pack_weight_bf16_dev_f32(L.ptr(wd), rows, cols, cols, 1, L.ptr(out), L.stream_ptr()),
-            "pcr_pack_weight_bf16_dev_f32")
+    L.run.pcr_pack_weight_bf16_dev_f32(wd, rows, cols, cols, 1, out, L.stream_ptr())
     return out
 
 
@@ -450,7 +391,7 @@ def tdense_bwd(g, x, cout, dy_mode=0, y=None, k=None, argmax=None, pooled=None, 
     nbytes = 4.0 * B * Ln * ((cout if dy_mode != 3 else 0) + (cout if dy_mode != 0 else 0) + cin +
                              (cin if wpT is not None else 0))
     with _prof("tdense_bwd[mode=%d,cin=%d,cout=%d,L=%d]" % (dy_mode, cin, cout, Ln), flops, nbytes, arith="lib"):
-        L.check(L.load().pcr_tdense_bwd_f32(ctypes.byref(p), L.stream_ptr()), "pcr_tdense_bwd_f32")
+        L.run.pcr_tdense_bwd_f32(ctypes.byref(p), L.stream_ptr())
     if want_dw:
         dW, db = reduce_regions(parts, nwg, per, [(0, cout, cin, cinP), (coutP * cinP, 1, cout, cout)])
         out["dW"], out["db"] = dW, db.view(cout)
@@ -468,7 +409,7 @@ def bn_fwd_finalize(part, nparts, C, R, gamma, beta, eps, momentum, running_mean
     p.shift0, p.shift0_stride = _p(shift0), shift0_stride
     for k, v in o.items():
         setattr(p, k, _p(v))
-    L.check(L.load().pcr_bn_fwd_finalize_f32(ctypes.byref(p), L.stream_ptr()), "pcr_bn_fwd_finalize_f32")
+    L.run.pcr_bn_fwd_finalize_f32(ctypes.byref(p), L.stream_ptr())
     return o
 
 
@@ -481,7 +422,7 @@ def bn_bwd_finalize(part, nparts, C, R, gamma, mean, invstd, centre=None):
     p.centre = _p(centre)
     for k, v in o.items():
         setattr(p, k, _p(v))
-    L.check(L.load().pcr_bn_bwd_finalize_f32(ctypes.byref(p), L.stream_ptr()), "pcr_bn_bwd_finalize_f32")
+    L.run.pcr_bn_bwd_finalize_f32(ctypes.byref(p), L.stream_ptr())
     return o
 
 
@@ -557,7 +498,6 @@ class SaEdgeTrain(Function):
 
     @staticmethod
     def forward(ctx, xyz, idx, tab, wa, b1, g1, be1, w2, b2, g2, be2, w3, b3, g3, be3, bns):
-        lib = L.load()
         xyz, idx = _dev(xyz), idx.contiguous()
         L.require_i32(idx)
         B, N, _ = xyz.shape
@@ -570,8 +510,8 @@ class SaEdgeTrain(Function):
         y1 = _f32(B, c1, Ln, device=dev)
         st1 = _f32(B, 2, _c32(c1), device=dev)
         with _prof("sa_l1_fwd[c1=%d,N=%d,S=%d,K=%d]" % (c1, N, S, K), 8.0 * B * Ln * c1, 4.0 * B * (Ln * (c1 + 1) + 2 * c1 * N)):
-            L.check(lib.pcr_sa_l1_fwd_f32(L.ptr(xyz), L.ptr(idx), L.ptr(tab), L.ptr(_dev(wa.detach())), L.ptr(b1.detach()),
-                                          L.ptr(y1), L.ptr(st1), B, N, S, K, c1, L.stream_ptr()), "pcr_sa_l1_fwd_f32")
+            L.run.pcr_sa_l1_fwd_f32(xyz, idx, tab, _dev(wa.detach()), b1.detach(), y1, st1, B, N, S, K, c1,
+                                    L.stream_ptr())
 
         def fin(st, nparts, C, gamma, beta, bn):
             if bn.momentum is None:
@@ -600,15 +540,14 @@ class SaEdgeTrain(Function):
         pooled = _f32(B, c3, S, device=dev)
         if won is not None:
             ymax, argmax = won
-            L.check(lib.pcr_bn_affine_f32(L.ptr(ymax), None, L.ptr(n3["scale"]), L.ptr(n3["shift"]), None, None, None, None,
-                                          1, ctypes.c_float(0.0), L.ptr(pooled), B, c3, S, L.stream_ptr()),
-                    "pcr_bn_affine_f32")
+            L.run.pcr_bn_affine_f32(ymax, None, n3["scale"], n3["shift"], None, None, None, None, 1, 0.0, pooled, B,
+                                    c3, S, L.stream_ptr())
         else:
             argmax = torch.empty((B, c3, S), dtype=torch.int32, device=dev)
             ymax = _f32(B, c3, S, device=dev)
             with _prof("sa_pool_fwd[c=%d,S=%d,K=%d]" % (c3, S, K), 2.0 * B * Ln * c3, 4.0 * B * c3 * (Ln + 2 * S)):
-                L.check(lib.pcr_sa_pool_fwd_f32(L.ptr(y3), L.ptr(n3["scale"]), L.ptr(n3["shift"]), L.ptr(pooled),
-                                                L.ptr(argmax), L.ptr(ymax), B, c3, S, K, L.stream_ptr()), "pcr_sa_pool_fwd_f32")
+                L.run.pcr_sa_pool_fwd_f32(y3, n3["scale"], n3["shift"], pooled, argmax, ymax, B, c3, S, K,
+                                          L.stream_ptr())
         ctx.save_for_backward(xyz, idx, y1, y2, y3, pooled, argmax, w2, w3, g1, g2, g3, ymax)
         ctx.norms = (n1, n2, n3)
         ctx.has_tab = tab is not None
@@ -618,7 +557,6 @@ class SaEdgeTrain(Function):
 
     @staticmethod
     def backward(ctx, gp):
-        lib = L.load()
         xyz, idx, y1, y2, y3, pooled, argmax, w2, w3, g1, g2, g3, ymax = ctx.saved_tensors
         n1, n2, n3 = ctx.norms
         B, N, S, K, c1, c2, c3 = ctx.dims
@@ -626,8 +564,7 @@ class SaEdgeTrain(Function):
         gp = gp.contiguous()
         part3 = _f32(B, 2, _c32(c3), device=dev)
         gz = _f32(B, c3, S, device=dev)          # the pooled gradient where the ReLU is open, zero elsewhere
-        L.check(lib.pcr_sa_pool_bwd_stats_f32(L.ptr(gp), L.ptr(pooled), L.ptr(ymax), L.ptr(part3), L.ptr(gz), B, c3, S,
-                                              L.stream_ptr()), "pcr_sa_pool_bwd_stats_f32")
+        L.run.pcr_sa_pool_bwd_stats_f32(gp, pooled, ymax, part3, gz, B, c3, S, L.stream_ptr())
         k3 = bn_bwd_finalize(part3, B, c3, R, g3, n3["mean"], n3["invstd"])
         # (128 x 128 layers: dx and dW on the bf16 matrix core when TRAIN_PRECISION says so)
         bf3 = pack_bf_T(w3) if (_bwd_bf() and c3 == 128 and c2 == 128) else None
@@ -642,9 +579,8 @@ class SaEdgeTrain(Function):
         dtab = _f32(B, 2 * c1, N, device=dev) if ctx.has_tab else None
         dwa_p = _f32(B, c1, 4, device=dev)
         with _prof("sa_l1_bwd[c1=%d,N=%d,S=%d,K=%d]" % (c1, N, S, K), 10.0 * B * Ln * c1, 4.0 * B * (Ln * (2 * c1 + 1) + 2 * c1 * N)):
-            L.check(lib.pcr_sa_l1_bwd_f32(L.ptr(xyz), L.ptr(idx), L.ptr(r2["dx"]), L.ptr(y1), L.ptr(k1["ka"]), L.ptr(k1["kb"]),
-                                          L.ptr(k1["kc"]), L.ptr(dtab), L.ptr(dwa_p), B, N, S, K, c1, L.stream_ptr()),
-                    "pcr_sa_l1_bwd_f32")
+            L.run.pcr_sa_l1_bwd_f32(xyz, idx, r2["dx"], y1, k1["ka"], k1["kb"], k1["kc"], dtab, dwa_p, B, N, S, K, c1,
+                                    L.stream_ptr())
         dwa4 = reduce_parts(dwa_p, B, c1 * 4, c1, 4, 4)
         return (None, None, dtab, dwa4[:, :3].contiguous(), dwa4[:, 3].contiguous(), k1["dgamma"], k1["dbeta"],
                 r2["dW"], r2["db"], k2["dgamma"], k2["dbeta"], r3["dW"], r3["db"], k3["dgamma"], k3["dbeta"], None)
@@ -670,14 +606,6 @@ def sa_edge_train(sa, xyz, feats, idx):
 
 
 # ---------------------------------------------------------------- attention / norm / pooling Functions --
-class _LinAttnP(ctypes.Structure):
-    _fields_ = [("B", ctypes.c_int), ("Lq", ctypes.c_int), ("Sk", ctypes.c_int), ("d", ctypes.c_int), ("H", ctypes.c_int),
-                ("eps", ctypes.c_float), ("q", c_fp), ("k", c_fp), ("v", c_fp),
-                ("q_bs", ctypes.c_long), ("k_bs", ctypes.c_long), ("v_bs", ctypes.c_long),
-                ("out", c_fp), ("A", c_fp), ("ks", c_fp), ("dout", c_fp), ("dq", c_fp), ("dk", c_fp), ("dv", c_fp),
-                ("dq_bs", ctypes.c_long), ("dk_bs", ctypes.c_long), ("dv_bs", ctypes.c_long), ("kv_roll", ctypes.c_int)]
-
-
 def _block(t, d):
     """(pointer, batch stride) of a (B,d,L) channel-major block that may be a channel slice of a wider tensor"""
     assert t.dim() == 3 and t.shape[1] == d and t.stride(2) == 1 and t.stride(1) == t.shape[2], \
@@ -697,7 +625,7 @@ def _linattn_fwd(q, k, v, H, eps, kv_roll=0):
     p.B, p.Lq, p.Sk, p.d, p.H, p.eps, p.kv_roll = B, Lq, Sk, d, H, eps, kv_roll
     (p.q, p.q_bs), (p.k, p.k_bs), (p.v, p.v_bs) = _block(q, d), _block(k, d), _block(v, d)
     p.out, p.A, p.ks = _p(out), _p(A), _p(ks)
-    L.check(L.load().pcr_linattn_fwd_f32(ctypes.byref(p), L.stream_ptr()), "pcr_linattn_fwd_f32")
+    L.run.pcr_linattn_fwd_f32(ctypes.byref(p), L.stream_ptr())
     return out, A, ks
 
 
@@ -708,7 +636,7 @@ def _linattn_bwd(q, k, v, A, ks, g, dq, dk, dv, H, eps, kv_roll=0):
     (p.q, p.q_bs), (p.k, p.k_bs), (p.v, p.v_bs) = _block(q, d), _block(k, d), _block(v, d)
     p.A, p.ks, p.dout = _p(A), _p(ks), _p(g)
     (p.dq, p.dq_bs), (p.dk, p.dk_bs), (p.dv, p.dv_bs) = _block(dq, d), _block(dk, d), _block(dv, d)
-    L.check(L.load().pcr_linattn_bwd_f32(ctypes.byref(p), L.stream_ptr()), "pcr_linattn_bwd_f32")
+    L.run.pcr_linattn_bwd_f32(ctypes.byref(p), L.stream_ptr())
 
 
 class LinAttn(Function):
@@ -770,8 +698,7 @@ class LocalAttn(Function):
         B, C3, N = qkv.shape
         C, K = C3 // 3, idx.shape[2]
         msg = _f32(B, C, N, device=qkv.device)
-        L.check(L.load().pcr_local_attn_train_fwd_f32(L.ptr(qkv), L.ptr(idx), L.ptr(msg), B, N, C, K, H,
-                                                      ctypes.c_float(eps), L.stream_ptr()), "pcr_local_attn_train_fwd_f32")
+        L.run.pcr_local_attn_train_fwd_f32(qkv, idx, msg, B, N, C, K, H, eps, L.stream_ptr())
         ctx.save_for_backward(qkv, idx)
         ctx.meta = (H, eps)
         return msg
@@ -782,16 +709,12 @@ class LocalAttn(Function):
         H, eps = ctx.meta
         B, C3, N = qkv.shape
         C, K = C3 // 3, idx.shape[2]
-        lib = L.load()
         g = g.contiguous()
         dqkv = torch.zeros((B, 3 * C, N), dtype=torch.float32, device=qkv.device)      # (k | v rows: accumulated into)
         edge = _f32(B, 2 * C, N, K, device=qkv.device)
-        L.check(lib.pcr_local_attn_train_bwd_f32(L.ptr(qkv), L.ptr(idx), L.ptr(g), L.ptr(dqkv), ctypes.c_long(3 * C * N),
-                                                 L.ptr(edge), B, N, C, K, H, ctypes.c_float(eps), L.stream_ptr()),
-                "pcr_local_attn_train_bwd_f32")
+        L.run.pcr_local_attn_train_bwd_f32(qkv, idx, g, dqkv, 3 * C * N, edge, B, N, C, K, H, eps, L.stream_ptr())
         dkv = torch.zeros((B, 2 * C, N), dtype=torch.float32, device=qkv.device)
-        L.check(lib.pcr_group_bwd_f32(L.ptr(edge), L.ptr(idx), L.ptr(dkv), B, 2 * C, N, N, K, L.stream_ptr()),
-                "pcr_group_bwd_f32")
+        L.run.pcr_group_bwd_f32(edge, idx, dkv, B, 2 * C, N, N, K, L.stream_ptr())
         dqkv[:, C:] = dkv
         return dqkv, None, None, None
 
@@ -805,9 +728,8 @@ class TNorm(Function):
         B, C, Ln = x.shape
         y = torch.empty_like(x)
         mean, rstd = _f32(B, G, Ln, device=x.device), _f32(B, G, Ln, device=x.device)
-        L.check(L.load().pcr_tnorm_fwd_f32(L.ptr(x), L.ptr(gamma.detach()), L.ptr(beta.detach()),
-                                           L.ptr(None if res is None else _dev(res)), L.ptr(y), L.ptr(mean), L.ptr(rstd),
-                                           B, C, Ln, G, ctypes.c_float(eps), int(relu), L.stream_ptr()), "pcr_tnorm_fwd_f32")
+        L.run.pcr_tnorm_fwd_f32(x, gamma.detach(), beta.detach(), None if res is None else _dev(res), y, mean, rstd, B,
+                                C, Ln, G, eps, int(relu), L.stream_ptr())
         ctx.save_for_backward(x, gamma, mean, rstd, y if relu else None)
         ctx.meta = (G, res is not None)
         return y
@@ -822,9 +744,7 @@ class TNorm(Function):
         dres = torch.empty_like(x) if (has_res and y is not None) else None
         nparts = (B * Ln + 63) // 64              # one partial row per 64-token wave
         part = _f32(nparts, 2, C, device=x.device)
-        L.check(L.load().pcr_tnorm_bwd_f32(L.ptr(g), L.ptr(x), L.ptr(gamma.detach()), L.ptr(mean), L.ptr(rstd), L.ptr(y),
-                                           L.ptr(dx), L.ptr(dres), L.ptr(part), B, C, Ln, G, L.stream_ptr()),
-                "pcr_tnorm_bwd_f32")
+        L.run.pcr_tnorm_bwd_f32(g, x, gamma.detach(), mean, rstd, y, dx, dres, part, B, C, Ln, G, L.stream_ptr())
         dgam, dbet = reduce_regions(part, nparts, 2 * C, [(0, 1, C, C), (C, 1, C, C)])
         return dx, dgam.view(C), dbet.view(C), (dres if dres is not None else g) if has_res else None, None, None, None
 
@@ -839,15 +759,6 @@ def tnorm(x, norm, res=None, relu=False):
 # PCR_TRAIN_FUSED=0 keeps the unfused graph (one launch per layer: the form of rounds 2-4, and the yardstick of
 # tests/test_gpu_train_chain.py)
 FUSED_CHAINS = os.environ.get("PCR_TRAIN_FUSED", "1") != "0"
-
-
-class _AttnTailP(ctypes.Structure):
-    _fields_ = [("B", ctypes.c_int), ("L", ctypes.c_int), ("d", ctypes.c_int), ("c1", ctypes.c_int), ("hid", ctypes.c_int),
-                ("out", ctypes.c_int), ("residual", ctypes.c_int), ("eps", ctypes.c_float),
-                ("msg", c_fp), ("res", c_fp), ("wm", c_fp), ("w0", c_fp), ("w2", c_fp), ("wmT", c_fp), ("w0T", c_fp),
-                ("w2T", c_fp), ("g1", c_fp), ("b1", c_fp), ("g2", c_fp), ("b2", c_fp), ("outp", c_fp), ("dout", c_fp),
-                ("dmsg", c_fp), ("dres", c_fp), ("parts", c_fp), ("part_stride", ctypes.c_long),
-                ("precision", ctypes.c_int), ("fwd_precision", ctypes.c_int)]
 
 
 def _chain_bf():
@@ -890,7 +801,7 @@ class AttnTail(Function):
         flops = 2.0 * B * Ln * (d * d + (c1 + d) * hid + hid * out)
         with _prof("attn_tail_fwd[d=%d,c1=%d,hid=%d,out=%d,L=%d]" % (d, c1, hid, out, Ln), flops,
                    4.0 * B * Ln * (d + c1 + out), arith="lib"):
-            L.check(L.load().pcr_attn_tail_fwd_f32(ctypes.byref(p), L.stream_ptr()), "pcr_attn_tail_fwd_f32")
+            L.run.pcr_attn_tail_fwd_f32(ctypes.byref(p), L.stream_ptr())
         ctx.save_for_backward(msg, res, Wm, g1, b1, W0, W2, g2, b2, *[t for im in images for t in im])
         ctx.meta = (residual, eps, bf)
         return y
@@ -912,7 +823,7 @@ class AttnTail(Function):
         flops = 2.0 * B * Ln * (d * d + (c1 + d) * hid + hid * out)
         with _prof("attn_tail_bwd[d=%d,c1=%d,hid=%d,out=%d,L=%d]" % (d, c1, hid, out, Ln), 3.0 * flops,
                    4.0 * B * Ln * (2 * d + 2 * c1 + out), arith="lib"):
-            L.check(lib.pcr_attn_tail_bwd_f32(ctypes.byref(p), L.stream_ptr()), "pcr_attn_tail_bwd_f32")
+            L.run.pcr_attn_tail_bwd_f32(ctypes.byref(p), L.stream_ptr())
         cup = _c32(c1 + d)
         o0, o2 = d * d, d * d + hid * cup
         og = o2 + out * hid
@@ -938,14 +849,6 @@ def attn_tail(m, msg, res, residual, names=("merge", "norm1", "mlp", "norm2")):
     L.require_default_eps(n1)
     return AttnTail.apply(msg, res, merge.weight, n1.weight, n1.bias, mlp[0].weight, mlp[2].weight, n2.weight, n2.bias,
                           bool(residual), float(n1.eps))
-
-
-class _AttnHeadP(ctypes.Structure):
-    _fields_ = [("B", ctypes.c_int), ("L", ctypes.c_int), ("c", ctypes.c_int), ("hd", ctypes.c_int), ("d", ctypes.c_int),
-                ("np", ctypes.c_int), ("src", ctypes.c_int), ("x", c_fp), ("xyz", c_fp), ("p1", c_fp), ("p2", c_fp),
-                ("c1", c_fp), ("c2", c_fp), ("p2T", c_fp), ("w", c_fp * 3), ("wT", c_fp * 3), ("outp", c_fp),
-                ("dout", c_fp), ("dx", c_fp), ("parts", c_fp), ("part_stride", ctypes.c_long),
-                ("precision", ctypes.c_int), ("fwd_precision", ctypes.c_int)]
 
 
 def _head_params(x, xyz, P1, c1, P2, c2, src, Ws, images, bf):
@@ -977,7 +880,7 @@ class AttnHead(Function):
         flops = 2.0 * B * Ln * (3 * hd + hd * C + n * d * C)
         with _prof("attn_head_fwd[c=%d,hd=%d,d=%d,n=%d,L=%d]" % (C, hd, d, n, Ln), flops, 4.0 * B * Ln * (C + 3 + n * d),
                    arith="lib"):
-            L.check(L.load().pcr_attn_head_fwd_f32(ctypes.byref(p), L.stream_ptr()), "pcr_attn_head_fwd_f32")
+            L.run.pcr_attn_head_fwd_f32(ctypes.byref(p), L.stream_ptr())
         ctx.save_for_backward(x, xyz, P1, c1, P2, c2, *Ws, *[t for im in images for t in im])
         ctx.meta = (src, len(Ws), bf)
         return out
@@ -999,7 +902,7 @@ class AttnHead(Function):
         flops = 2.0 * B * Ln * (3 * hd + hd * C + n * d * C)
         with _prof("attn_head_bwd[c=%d,hd=%d,d=%d,n=%d,L=%d]" % (C, hd, d, n, Ln), 3.0 * flops,
                    4.0 * B * Ln * (2 * C + 3 + n * d), arith="lib"):
-            L.check(lib.pcr_attn_head_bwd_f32(ctypes.byref(p), L.stream_ptr()), "pcr_attn_head_bwd_f32")
+            L.run.pcr_attn_head_bwd_f32(ctypes.byref(p), L.stream_ptr())
         o_p2 = hd * 32
         o_w = o_p2 + C * hd
         o_c1 = o_w + n * d * C
@@ -1057,8 +960,7 @@ class PoolPair(Function):
         P = twoP // 2
         pooled = _f32(P, 2 * C, device=o.device)
         arg = torch.empty((P, C), dtype=torch.int32, device=o.device)
-        L.check(L.load().pcr_pool_pair_fwd_f32(L.ptr(o), L.ptr(pooled), L.ptr(arg), P, C, Ln, L.stream_ptr()),
-                "pcr_pool_pair_fwd_f32")
+        L.run.pcr_pool_pair_fwd_f32(o, pooled, arg, P, C, Ln, L.stream_ptr())
         ctx.save_for_backward(arg)
         ctx.dims = (P, C, Ln)
         return pooled
@@ -1069,8 +971,7 @@ class PoolPair(Function):
         P, C, Ln = ctx.dims
         g = g.contiguous()
         dout = _f32(2 * P, C, Ln, device=g.device)
-        L.check(L.load().pcr_pool_pair_bwd_f32(L.ptr(g), L.ptr(arg), L.ptr(dout), P, C, Ln, L.stream_ptr()),
-                "pcr_pool_pair_bwd_f32")
+        L.run.pcr_pool_pair_bwd_f32(g, arg, dout, P, C, Ln, L.stream_ptr())
         return dout
 
 
@@ -1084,8 +985,7 @@ class PoolBoth(Function):
         pooled = _f32(P, 2 * C, device=o.device)
         arg = torch.empty((P, C), dtype=torch.int32, device=o.device)
         if P:                                                # (no clouds: empty tensors, nothing to launch)
-            L.check(L.load().pcr_pool_both_fwd_f32(L.ptr(o), L.ptr(pooled), L.ptr(arg), P, C, Ln, L.stream_ptr()),
-                    "pcr_pool_both_fwd_f32")
+            L.run.pcr_pool_both_fwd_f32(o, pooled, arg, P, C, Ln, L.stream_ptr())
         ctx.save_for_backward(arg)
         ctx.dims = (P, C, Ln)
         return pooled
@@ -1097,8 +997,7 @@ class PoolBoth(Function):
         g = g.contiguous()
         dout = _f32(P, C, Ln, device=g.device)
         if P:
-            L.check(L.load().pcr_pool_both_bwd_f32(L.ptr(g), L.ptr(arg), L.ptr(dout), P, C, Ln, L.stream_ptr()),
-                    "pcr_pool_both_bwd_f32")
+            L.run.pcr_pool_both_bwd_f32(g, arg, dout, P, C, Ln, L.stream_ptr())
         return dout
 
 
@@ -1113,8 +1012,7 @@ class ChannelMax(Function):
         y = _f32(B, C // W, Ln, device=x.device)
         arg = torch.empty((B, C // W, Ln), dtype=torch.int32, device=x.device)
         if B:                                              # (no clouds: empty tensors, nothing to launch)
-            L.check(L.load().pcr_channel_max_fwd_f32(L.ptr(x), L.ptr(y), L.ptr(arg), B, C, Ln, W, L.stream_ptr()),
-                    "pcr_channel_max_fwd_f32")
+            L.run.pcr_channel_max_fwd_f32(x, y, arg, B, C, Ln, W, L.stream_ptr())
         ctx.save_for_backward(arg)
         ctx.dims = (B, C, Ln, W)
         return y
@@ -1126,8 +1024,7 @@ class ChannelMax(Function):
         g = g.contiguous()
         dx = _f32(B, C, Ln, device=g.device)
         if B:
-            L.check(L.load().pcr_channel_max_bwd_f32(L.ptr(g), L.ptr(arg), L.ptr(dx), B, C, Ln, W, L.stream_ptr()),
-                    "pcr_channel_max_bwd_f32")
+            L.run.pcr_channel_max_bwd_f32(g, arg, dx, B, C, Ln, W, L.stream_ptr())
         return dx, None
 
 
@@ -1149,15 +1046,13 @@ class BnAct(Function):
     def forward(ctx, y, gamma, beta, bn, act, slope):
         y = _dev(y)
         B, C, Ln = y.shape
-        lib = L.load()
         if bn.momentum is None:
             raise L.PcrError("BatchNorm with momentum=None (cumulative average) is not supported by the HIP training path")
         _require_batch(B * Ln, y.shape)
         nparts = max(1, min(B, 2048 // max(C, 1)))
         part = _f32(nparts, 2, _c32(C), device=y.device)
         # sums of y - y[0][c][0] (first element of the channel as the offset): see pcr_bn_fwd_fin.shift0
-        L.check(lib.pcr_bn_sums_f32(L.ptr(y), None, None, None, 0, ctypes.c_float(0.0), None, 1, L.ptr(part), nparts, B, C, Ln,
-                                    L.stream_ptr()), "pcr_bn_sums_f32")
+        L.run.pcr_bn_sums_f32(y, None, None, None, 0, 0.0, None, 1, part, nparts, B, C, Ln, L.stream_ptr())
         n = bn_fwd_finalize(part, nparts, C, B * Ln, gamma, beta, bn.eps, bn.momentum,
                             bn.running_mean if bn.track_running_stats else None,
                             bn.running_var if bn.track_running_stats else None, shift0=y, shift0_stride=Ln)
@@ -1166,9 +1061,8 @@ class BnAct(Function):
             if bn.num_batches_tracked is not None:
                 bn.num_batches_tracked += 1
         z = _f32(B, C, Ln, device=y.device)
-        L.check(lib.pcr_bn_affine_f32(L.ptr(y), None, L.ptr(n["scale"]), L.ptr(n["shift"]), None, None, None, None,
-                                      int(act), ctypes.c_float(slope), L.ptr(z), B, C, Ln, L.stream_ptr()),
-                "pcr_bn_affine_f32")
+        L.run.pcr_bn_affine_f32(y, None, n["scale"], n["shift"], None, None, None, None, int(act), slope, z, B, C, Ln,
+                                L.stream_ptr())
         ctx.save_for_backward(y, gamma)
         ctx.norm, ctx.act, ctx.slope, ctx.nparts = n, int(act), float(slope), nparts
         return z
@@ -1179,16 +1073,14 @@ class BnAct(Function):
         n, act, slope, nparts = ctx.norm, ctx.act, ctx.slope, ctx.nparts
         B, C, Ln = y.shape
         g = g.contiguous()
-        lib = L.load()
         part = _f32(nparts, 2, _c32(C), device=y.device)
-        L.check(lib.pcr_bn_sums_f32(L.ptr(y), L.ptr(g), L.ptr(n["scale"]), L.ptr(n["shift"]), act, ctypes.c_float(slope),
-                                    L.ptr(n["mean"]), 0, L.ptr(part), nparts, B, C, Ln, L.stream_ptr()), "pcr_bn_sums_f32")
+        L.run.pcr_bn_sums_f32(y, g, n["scale"], n["shift"], act, slope, n["mean"], 0, part, nparts, B, C, Ln,
+                              L.stream_ptr())
         k = bn_bwd_finalize(part, nparts, C, B * Ln, gamma, n["mean"], n["invstd"], centre=n["mean"])
         dy = _f32(B, C, Ln, device=y.device)
         kc = k["ka"] * k["dbeta"] * (-1.0 / (B * Ln))        # centred form: dy = ka g' + kb (y - mean) - ka dbeta / R
-        L.check(lib.pcr_bn_affine_f32(L.ptr(y), L.ptr(g), L.ptr(k["ka"]), L.ptr(k["kb"]), L.ptr(kc), L.ptr(n["scale"]),
-                                      L.ptr(n["shift"]), L.ptr(n["mean"]), act, ctypes.c_float(slope), L.ptr(dy), B, C, Ln,
-                                      L.stream_ptr()), "pcr_bn_affine_f32")
+        L.run.pcr_bn_affine_f32(y, g, k["ka"], k["kb"], kc, n["scale"], n["shift"], n["mean"], act, slope, dy, B, C,
+                                Ln, L.stream_ptr())
         return dy, k["dgamma"], k["dbeta"], None, None, None
 
 
@@ -1207,7 +1099,6 @@ class EdgeConvTrain(Function):
 
     @staticmethod
     def forward(ctx, tab, idx, gamma, beta, bn, slope):
-        lib = L.load()
         tab, idx = _dev(tab), idx.contiguous()
         L.require_i32(idx)
         B, two_co, N = tab.shape
@@ -1222,8 +1113,7 @@ class EdgeConvTrain(Function):
         b0 = torch.zeros((Co,), dtype=torch.float32, device=dev)
         y = _f32(B, Co, N * K, device=dev)
         st = _f32(B, 2, _c32(Co), device=dev)
-        L.check(lib.pcr_sa_l1_fwd_f32(L.ptr(xyz0), L.ptr(idx), L.ptr(tab), L.ptr(wa0), L.ptr(b0), L.ptr(y), L.ptr(st),
-                                      B, N, N, K, Co, L.stream_ptr()), "pcr_sa_l1_fwd_f32")
+        L.run.pcr_sa_l1_fwd_f32(xyz0, idx, tab, wa0, b0, y, st, B, N, N, K, Co, L.stream_ptr())
         R = B * N * K
         n = bn_fwd_finalize(st, B, Co, R, gamma, beta, bn.eps, bn.momentum,
                             bn.running_mean if bn.track_running_stats else None,
@@ -1235,15 +1125,13 @@ class EdgeConvTrain(Function):
         pooled = _f32(B, Co, N, device=dev)
         arg = torch.empty((B, Co, N), dtype=torch.int32, device=dev)
         yraw = _f32(B, Co, N, device=dev)
-        L.check(lib.pcr_edge_pool_fwd_f32(L.ptr(y), L.ptr(n["scale"]), L.ptr(n["shift"]), ctypes.c_float(slope), L.ptr(pooled),
-                                          L.ptr(arg), L.ptr(yraw), B, Co, N, K, L.stream_ptr()), "pcr_edge_pool_fwd_f32")
+        L.run.pcr_edge_pool_fwd_f32(y, n["scale"], n["shift"], slope, pooled, arg, yraw, B, Co, N, K, L.stream_ptr())
         ctx.save_for_backward(idx, y, pooled, arg, yraw, gamma, xyz0)
         ctx.norm, ctx.slope, ctx.dims = n, float(slope), (B, Co, N, K)
         return pooled
 
     @staticmethod
     def backward(ctx, gp):
-        lib = L.load()
         idx, y, pooled, arg, yraw, gamma, xyz0 = ctx.saved_tensors
         n, slope = ctx.norm, ctx.slope
         B, Co, N, K = ctx.dims
@@ -1253,16 +1141,15 @@ class EdgeConvTrain(Function):
         # the two sums of the BatchNorm backward: the routed gradient is non-zero on ONE edge per (channel, point)
         nparts = max(1, min(B, 2048 // max(Co, 1)))
         part = _f32(nparts, 2, _c32(Co), device=dev)
-        L.check(lib.pcr_bn_sums_f32(L.ptr(yraw), L.ptr(gp), L.ptr(n["scale"]), L.ptr(n["shift"]), 1, ctypes.c_float(slope),
-                                    L.ptr(n["mean"]), 0, L.ptr(part), nparts, B, Co, N, L.stream_ptr()), "pcr_bn_sums_f32")
+        L.run.pcr_bn_sums_f32(yraw, gp, n["scale"], n["shift"], 1, slope, n["mean"], 0, part, nparts, B, Co, N,
+                              L.stream_ptr())
         k = bn_bwd_finalize(part, nparts, Co, R, gamma, n["mean"], n["invstd"], centre=n["mean"])
         g = _f32(B, Co, N * K, device=dev)
-        L.check(lib.pcr_edge_pool_route_f32(L.ptr(gp), L.ptr(pooled), L.ptr(arg), ctypes.c_float(slope), L.ptr(g), B, Co, N, K,
-                                            L.stream_ptr()), "pcr_edge_pool_route_f32")
+        L.run.pcr_edge_pool_route_f32(gp, pooled, arg, slope, g, B, Co, N, K, L.stream_ptr())
         dtab = _f32(B, 2 * Co, N, device=dev)
         dwa_p = _f32(B, Co, 4, device=dev)
-        L.check(lib.pcr_sa_l1_bwd_f32(L.ptr(xyz0), L.ptr(idx), L.ptr(g), L.ptr(y), L.ptr(k["ka"]), L.ptr(k["kb"]), L.ptr(k["kc"]),
-                                      L.ptr(dtab), L.ptr(dwa_p), B, N, N, K, Co, L.stream_ptr()), "pcr_sa_l1_bwd_f32")
+        L.run.pcr_sa_l1_bwd_f32(xyz0, idx, g, y, k["ka"], k["kb"], k["kc"], dtab, dwa_p, B, N, N, K, Co,
+                                L.stream_ptr())
         return dtab, None, k["dgamma"], k["dbeta"], None, None
 
 
@@ -1275,7 +1162,7 @@ class Bmm(Function):
         x, T = _dev(x), _dev(T)
         B, k, N = x.shape
         y = _f32(B, k, N, device=x.device)
-        L.check(L.load().pcr_bmm_apply_f32(L.ptr(x), L.ptr(T), L.ptr(y), B, k, N, 0, L.stream_ptr()), "pcr_bmm_apply_f32")
+        L.run.pcr_bmm_apply_f32(x, T, y, B, k, N, 0, L.stream_ptr())
         ctx.save_for_backward(x, T)
         return y
 
@@ -1284,12 +1171,11 @@ class Bmm(Function):
         x, T = ctx.saved_tensors
         B, k, N = x.shape
         g = g.contiguous()
-        lib = L.load()
         dx = dT = None
         if ctx.needs_input_grad[0]:
             dx = _f32(B, k, N, device=x.device)
-            L.check(lib.pcr_bmm_apply_f32(L.ptr(g), L.ptr(T), L.ptr(dx), B, k, N, 1, L.stream_ptr()), "pcr_bmm_apply_f32")
+            L.run.pcr_bmm_apply_f32(g, T, dx, B, k, N, 1, L.stream_ptr())
         if ctx.needs_input_grad[1]:
             dT = _f32(B, k, k, device=x.device)
-            L.check(lib.pcr_bmm_dt_f32(L.ptr(x), L.ptr(g), L.ptr(dT), B, k, N, L.stream_ptr()), "pcr_bmm_dt_f32")
+            L.run.pcr_bmm_dt_f32(x, g, dT, B, k, N, L.stream_ptr())
         return dx, dT

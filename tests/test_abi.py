@@ -1,5 +1,6 @@
 """CPU: the C-ABI library builds for gfx950, loads, and exports every symbol include/pcr.h
-declares (no compute calls without a GPU); host-side weight packing round-trips."""
+declares (no compute calls without a GPU); host-side weight packing round-trips; the Python description of the ABI
+(pcr_amd/abi.py) agrees with the header, prototype by prototype and field by field."""
 import ctypes
 import os
 import re
@@ -30,6 +31,156 @@ def test_every_declared_symbol_is_exported(lib):
         assert hasattr(lib, s), "libpcr_hip.so does not export %s" % s
     assert lib.pcr_abi_version() == 17
     assert lib.pcr_status_string(0) == b"ok"
+
+
+def header_text():
+    """include/pcr.h without comments"""
+    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "pcr.h")).read(), flags=re.S)
+
+
+def header_structs():
+    """{struct name: [field names in order]} of every `typedef struct NAME { ... } NAME;` of the header"""
+    out = {}
+    for name, body in re.findall(r"typedef struct (\w+) \{(.*?)\} \w+;", header_text(), flags=re.S):
+        names = []
+        for decl in body.split(";"):
+            for d in decl.split(","):
+                m = re.search(r"(\w+)\s*(?:\[\d+\])?\s*$", d)
+                if m:
+                    names.append(m.group(1))
+        out[name] = names
+    return out
+
+
+def header_prototypes():
+    """{function: (return kind, [parameter kinds])} in abi.SIGNATURES' letters, except that a status return reads "i"
+    (the header says `int` for both) and a pointer to a struct reads <struct name of the header>"""
+    text = re.sub(r"typedef struct \w+ \{.*?\} \w+;", "", header_text(), flags=re.S)
+    scalar = {"int": "i", "float": "f", "long": "l", "pcr_stream_t": "S"}
+    out = {}
+    for ret, name, params in re.findall(r"^\s*((?:const\s+)?(?:int|long|char)\s*\*?)\s*(pcr_\w+)\s*\(([^)]*)\)\s*;", text, flags=re.M):
+        kinds = []
+        for p in [q.strip() for q in params.split(",")]:
+            if p == "void":
+                continue
+            ty, star, _ = re.match(r"(.*?)(\*?)\s*(\w+)$", re.sub(r"\b(const|struct)\b", "", p).strip()).groups()
+            ty = " ".join(ty.split())
+            if not star:
+                kinds.append(scalar[ty])
+            else:
+                kinds.append({"float": "F", "int": "I"}.get(ty, "<%s>" % ty if ty.startswith("pcr_") else "P"))
+        out[name] = ({"int": "i", "long": "l", "char*": "c"}[ret.replace("const", "").replace(" ", "")], kinds)
+    return out
+
+
+def test_signature_table_matches_the_header():
+    from pcr_amd import abi
+    protos = header_prototypes()
+    assert len(protos) >= 120, len(protos)
+    assert sorted(protos) == declared_symbols()          # (the prototype regex missed none of the declared names)
+    assert sorted(abi.SIGNATURES) == sorted(protos)
+    n_float = n_long = 0
+    for name, (ret, want) in protos.items():
+        got_ret, got = abi.kinds(abi.SIGNATURES[name])
+        # a pointer to one of the eleven parameter blocks names its ctypes mirror; any other struct (the records of a
+        # device table) is an untyped pointer
+        want = [("<%s>" % abi.BLOCKS[k[1:-1]].__name__ if k[1:-1] in abi.BLOCKS else "P") if k[0] == "<" else k for k in want]
+        assert got == want, (name, got, want)
+        assert {"s": "i"}.get(got_ret, got_ret) == ret, (name, got_ret, ret)
+        n_float += want.count("f")
+        n_long += want.count("l")
+        restype, argtypes = abi.prototype(abi.SIGNATURES[name])
+        assert len(argtypes) == len(want)
+    assert (n_float, n_long) == (22, 5)                  # (what the header holds today: the kinds are really told apart)
+
+
+def _host_clang():
+    from pcr_amd import build
+    rocm = os.path.dirname(os.path.dirname(os.path.realpath(build.hipcc())))
+    for cand in (os.path.join(rocm, "lib", "llvm", "bin", "clang"), os.path.join(rocm, "llvm", "bin", "clang")):
+        if os.path.exists(cand):
+            return cand
+    raise AssertionError("no host clang beside %s (the library build needs it too)" % build.hipcc())
+
+
+def test_parameter_block_layouts_match_the_header(tmp_path):
+    """sizeof / offsetof of every field of every parameter block and device-table record, as the host compiler lays the
+    header out, against the ctypes mirrors and numpy dtypes of pcr_amd/abi.py"""
+    import subprocess
+    from pcr_amd import abi
+    fields = header_structs()
+    assert sorted(fields) == sorted(list(abi.BLOCKS) + list(abi.TABLES))
+    lines = ['#include <stddef.h>', '#include <stdio.h>', '#include "pcr.h"', 'int main(void) {']
+    for s, names in fields.items():
+        lines.append('  printf("%s . %%zu 0\\n", sizeof(%s));' % (s, s))
+        for f in names:
+            lines.append('  printf("%s %s %%zu %%zu\\n", offsetof(%s, %s), sizeof(((%s *)0)->%s));' % (s, f, s, f, s, f))
+    lines += ['  return 0;', '}']
+    src = tmp_path / "probe.c"
+    src.write_text("\n".join(lines) + "\n")
+    exe = str(tmp_path / "probe")
+    subprocess.run([_host_clang(), "-I" + os.path.join(ROOT, "include"), str(src), "-o", exe], check=True)
+    compared = 0
+    seen = {s: [] for s in fields}
+    for line in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.splitlines():
+        s, f, off, size = line.split()
+        off, size = int(off), int(size)
+        if s in abi.BLOCKS:
+            ct = abi.BLOCKS[s]
+            if f == ".":
+                assert ctypes.sizeof(ct) == off, (s, ctypes.sizeof(ct), off)
+                continue
+            d = getattr(ct, f)
+            assert (d.offset, d.size) == (off, size), (s, f, d.offset, d.size, off, size)
+        else:
+            dt = abi.TABLES[s]
+            if f == ".":
+                assert dt.itemsize == off, (s, dt.itemsize, off)
+                continue
+            assert (dt.fields[f][1], dt.fields[f][0].itemsize) == (off, size), (s, f, dt.fields[f], off, size)
+        seen[s].append(f)
+        compared += 1
+    for s, names in fields.items():                      # the header's names, all of them, in the header's order
+        assert seen[s] == names
+        have = [n for n, _ in abi.BLOCKS[s]._fields_] if s in abi.BLOCKS else list(abi.TABLES[s].names)
+        assert have == names, (s, have, names)
+    assert compared >= 250, compared
+
+
+def test_boundary_refuses_wrong_tensors_before_the_call(lib):
+    import torch
+    for bad in ((torch.zeros(1, 8, 3), None, None),                                  # a CPU tensor
+                (torch.zeros(1, 8, 3, dtype=torch.float64), None, None),             # float64 in a float * slot
+                (None, None, torch.zeros(1, 4, dtype=torch.int64))):                 # int64 in an int * slot
+        with pytest.raises(ctypes.ArgumentError):
+            lib.pcr_fps_f32(*bad, 1, 8, 4, None)
+    assert lib.pcr_fps_f32(None, None, None, 1, 8, 4, None) == 1
+    with pytest.raises(ctypes.ArgumentError):                                        # a byref of the wrong block
+        from pcr_amd import abi
+        lib.pcr_sa_mlp_f32(ctypes.byref(abi.HeadParams()), None)
+    # plain Python numbers go in as the header types them: a float in a float slot, a stride past 2^31 in a long slot
+    assert lib.pcr_ball_query_f32(None, None, None, 1, 8, 4, 0.0, 0.5, 4, None) == 1
+    assert lib.pcr_reduce_parts_f32(None, 2, (1 << 31) + 5, 1, 1, 1, None, None) == 1
+    assert lib.pcr_ball_query_rows_ok(1024, 32, 0.0) == 1 and lib.pcr_ball_query_rows_ok(1024, 32, 0.25) == 0
+    from pcr_amd import _lib
+    with pytest.raises(_lib.PcrError, match="pcr_fps_f32 failed: "):
+        _lib.run.pcr_fps_f32(None, None, None, 1, 8, 4, None)
+
+
+def test_checked_route_calls_through_load(lib, monkeypatch):
+    """`run.pcr_x` reaches the library through `_lib.load()` on every call, as `check(load().pcr_x(...))` did: the GPU tests
+    that put a spy in load()'s place (tests/test_gpu_sa_xyz_tables.py) must see the package's launches"""
+    from pcr_amd import _lib
+    seen = []
+
+    class Spy:
+        def __getattr__(self, name):
+            seen.append(name)
+            return getattr(lib, name)
+    monkeypatch.setattr(_lib, "load", lambda: Spy())
+    with pytest.raises(_lib.PcrError, match="pcr_fps_f32 failed: "):
+        _lib.run.pcr_fps_f32(None, None, None, 1, 8, 4, None)
+    assert seen == ["pcr_fps_f32"]
 
 
 def test_weight_packing_layout(lib):

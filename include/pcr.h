@@ -268,6 +268,95 @@ int pcr_lsa_ok(int B, int R, int C);
 int pcr_lsa_f32(const float *cost, int *col4row, int *row4col, float *u, float *v, int *info, int B, int R, int C,
                 pcr_stream_t stream);
 
+/* ------------------------------------------- A4. box overlap and suppression --------- */
+
+/* Overlap between bird's-eye-view boxes and the suppression of duplicates, the two steps of the tracker's frame that the
+ * reference leaves the device for: the track NMS (VirtualTracker.non_max_suppression, models/trackers/deprecated/
+ * virtual_tracker.py:232-259: torch.where on a data-dependent shape) and the detection NMS of ops/iou3d (iou3d_utils.py:
+ * 23-68, src/iou3d.cpp:100-148: the whole mask copied to the host, the sweep in a C++ loop, cudaMalloc / cudaFree in the
+ * middle).  Here every step is a fixed-shape launch without a host read, an allocation or an atomic, and writes the same
+ * bits on every run.  An entry with nothing to do (N == 0, A == 0 or B == 0) returns PCR_OK, launches nothing and writes
+ * nothing.  Thresholds are DEVICE pointers to one float: a replayed graph re-reads them (as seed in pcr_crop_boxes_f32).
+ *
+ * A BEV box is [x1, y1, x2, y2, angle] (iou3d's xyxyr), float.  Nothing is contracted into fma; divisions are IEEE.
+ *
+ * pcr_nearest_bev_f32: boxes7 (N,7) [x, y, z, w, l, h, rz] -> out5 (N,5), LiDARInstance3DBoxes.nearest_bev
+ * (core/bbox/structures/lidar_box3d.py:96-114 with limit_period, core/bbox/structures/utils.py:6-19):
+ *   r = |rz - floorf(rz / pi + 0.5) * pi|, pi rounded to float, every operation in binary32;
+ *   (w, l) are swapped where r > pi/4 (rounded to float); out5 = [x - w/2, y - l/2, x + w/2, y + l/2, 0].
+ *
+ * pcr_bev_frames_f32: boxes5 (N,5) -> frames (N,2) = (cosf(angle), sinf(angle)), through the ONE device function every
+ * rotated kernel of this section takes its trigonometry from (the reference's cos(-angle), sin(-angle) in check_in_box2d
+ * are c and -s exactly).  With this table a host restatement needs no trigonometry of its own (as pcr_box_frames_f32, A2). */
+int pcr_nearest_bev_f32(const float *boxes7, float *out5, int N, pcr_stream_t stream);
+int pcr_bev_frames_f32(const float *boxes5, float *frames, int N, pcr_stream_t stream);
+
+/* pcr_iou_bev_f32: a (A,5), b (B,5) -> out (A,B), EVERY element written; 0 <= A, B <= PCR_IOU_MAX_BOXES.
+ *   PCR_IOU_AXIS     iou_normal (ops/iou3d/src/iou3d_kernel.cu:335-343): the angle is ignored;
+ *                    inter = max(min(ax2,bx2) - max(ax1,bx1), 0) * max(min(ay2,by2) - max(ay1,by1), 0),
+ *                    iou = inter / fmaxf((Sa + Sb) - inter, 1e-8f), S = (x2 - x1) * (y2 - y1);
+ *   PCR_IOU_OVERLAP  box_overlap (:127-242), the area of the intersection polygon only;
+ *   PCR_IOU_ROTATED  iou_bev (:244-251) = overlap / fmaxf((Sa + Sb) - overlap, 1e-8f).
+ * The rotated kinds follow the reference's algorithm step by step, in float and in its order of operations:
+ *   corners     (x1,y1) (x2,y1) (x2,y2) (x1,y2) rotated about the centre ((x1+x2)/2, (y1+y2)/2):
+ *               x' = ((x-cx)*c + (y-cy)*s) + cx, y' = (-(x-cx)*s + (y-cy)*c) + cy (rotate_around_center, :111-119);
+ *   crossings   the 16 edge pairs (edge i of a outer, edge j of b inner) through intersection (:79-109): the bounding-
+ *               rectangle exclusion check_rect_cross (:45-52), the strict test s1*s2 > 0 && s3*s4 > 0, the point by
+ *               (s5*q0 - s1*q1) / (s5 - s1) where fabsf(s5 - s1) > EPS = 1e-8f and by the line equations otherwise;
+ *   corners in  for k = 0..3: corner k of b inside a, then corner k of a inside b, check_in_box2d with MARGIN = 1e-5f
+ *               (:54-77);
+ *   centroid    the running float sum of the points in that order, divided by their number;
+ *   order       the reference's bubble sort (:215-224) by atan2f(y - cy, x - cx) about the centroid (swap where the left
+ *               angle is greater);
+ *   area        the fan sum of cross(p[k] - p[0], p[k+1] - p[0]), k = 0 .. cnt-2, then fabsf(area) / 2.
+ * The reference's cross_points[16] can in principle be asked for up to 24 points (16 crossings + 8 corners); here the
+ * array has 24 slots.  No point at all (cnt == 0) gives area 0: the reference's NaN centroid is never used.  The points
+ * live in LDS (one column per lane), not in a scratch-backed private array. */
+#define PCR_IOU_AXIS 0
+#define PCR_IOU_ROTATED 1
+#define PCR_IOU_OVERLAP 2
+#define PCR_IOU_MAX_BOXES 65535
+int pcr_iou_bev_f32(const float *a, const float *b, float *out, int A, int B, int kind, pcr_stream_t stream);
+
+/* pcr_nms_f32: greedy NMS entirely on the device (nms_gpu / nms_normal_gpu, iou3d_utils.py:23-68 with iou3d.cpp:96-202).
+ * boxes (N,5), scores (N), thresh (device, 1 float) -> order (N), keep (N), count (1), info (1), all int32.
+ *   ranking  order holds the indices by descending score; equal scores (float compare, -0 == +0) go lowest index first
+ *            (the reference's torch.sort leaves ties unspecified: this rule is ours).  Ranks are counted, never sorted
+ *            with atomics: rank_i = #{j : s_j > s_i, or s_j == s_i and j < i}; a NaN score ranks behind every number,
+ *            NaNs among themselves by index, so order is always a permutation.  Only the ranks < pre_max take part in
+ *            what follows (pre_maxsize; pre_max <= 0 or >= N: all of them); call their number n.
+ *   mask     the reference's upper-triangular 64-bit mask over the ranked boxes (nms_kernel, iou3d_kernel.cu:284-333):
+ *            bit c of word (r, cb) is set iff column 64*cb + c > r and iou(box of rank r, box of that column) > thresh,
+ *            iou = iou_normal for kind PCR_IOU_AXIS (nms_normal_gpu) and iou_bev for PCR_IOU_ROTATED (nms_gpu), row
+ *            first.  A wave owns a 64 x 64 tile, lane = column, and one ballot is one word; only column blocks >= the
+ *            row block are computed.
+ *   sweep    iou3d.cpp:128-143 by one wave: for r = 0 .. n-1, rank r is kept iff its bit of remv is clear, and a kept
+ *            row ORs its words into remv.  Row blocks of 64 mask rows pass through two LDS buffers: the global loads of
+ *            block b+1 are issued before the 64 decisions of block b, which read LDS and registers only, and are waited
+ *            for after them; the kept indices of a block are stored after its decisions.
+ *   outputs  keep = the original indices of the kept boxes in rank order, padded with -1 to N; count = their true
+ *            number; info = 0.  info = 1 when a score is NaN or a box that takes part holds a NaN or an infinity
+ *            (x1..y2; the angle too for PCR_IOU_ROTATED): then keep is all -1 and count 0 (pcr_lsa_f32's convention);
+ *            order is written either way.  A NaN score counts at ANY rank, also behind pre_max: where a NaN stands in a
+ *            ranking is a convention, so which boxes take part would rest on it; a box is looked at only if it takes part.
+ * pcr_nms_ok(N): 0 <= N <= PCR_NMS_MAX (the remv words are one per lane).  ws: pcr_nms_ws_bytes(N) bytes of device
+ * memory (0 when N is out of range), 16-byte aligned, the launch's own until it has run: the ranked box table, the
+ * flags and the mask.  Every loop is bounded by an integer count. */
+#define PCR_NMS_MAX 4096
+int pcr_nms_ok(int N);
+int pcr_nms_ws_bytes(int N);
+int pcr_nms_f32(const float *boxes, const float *scores, const float *thresh, int *order, int *keep, int *count,
+                int *info, void *ws, int N, int kind, int pre_max, pcr_stream_t stream);
+
+/* pcr_track_nms_f32: the tracker's rule (virtual_tracker.py:249-255), pairwise and NOT greedy.  boxes5 (N,5) (angle
+ * ignored: the tracker compares nearest_bev boxes), classes (N) int32, scores (N), thresh (device, 1 float) ->
+ * suppressed (N) int32, every element written, 0 or 1.  For every i < j with classes[i] == classes[j] and
+ * iou_normal(box i, box j) > thresh: i is suppressed if scores[i] - scores[j] <= 0, j if that difference is > 0.
+ * The reference adds -10000 to the IoU of unlike classes before the compare; an IoU is at most 1, so for every
+ * thresh > -9999 that is exactly the class gate used here.  Range: pcr_nms_ok(N). */
+int pcr_track_nms_f32(const float *boxes5, const int *classes, const float *scores, const float *thresh,
+                      int *suppressed, int N, pcr_stream_t stream);
+
 /* ------------------------------------------------- B. fused model kernels ------------ */
 
 /* Neighbour search of the "Point-Transformer" set-abstraction layers: centres are the first S

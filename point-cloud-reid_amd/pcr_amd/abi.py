@@ -146,6 +146,14 @@ SIGNATURES = {
     "pcr_assoc_cost_f32": "s FIIFFFfffFiiiS",
     "pcr_lsa_ok": "i iii",
     "pcr_lsa_f32": "s FIIFFIiiiS",
+    # A4. box overlap and suppression
+    "pcr_nearest_bev_f32": "s FFiS",
+    "pcr_bev_frames_f32": "s FFiS",
+    "pcr_iou_bev_f32": "s FFFiiiS",
+    "pcr_nms_ok": "i i",
+    "pcr_nms_ws_bytes": "i i",
+    "pcr_nms_f32": "s FFFIIIIPiiiS",
+    "pcr_track_nms_f32": "s FIFFIiS",
     # B. fused model kernels
     "pcr_knn_prefix_f32": "s FIiiiiS",
     "pcr_knn_prefix2_f32": "s FIIiiiiiiS",

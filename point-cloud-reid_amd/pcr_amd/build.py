@@ -20,6 +20,7 @@ FLAGS = {
     "edge_kernels.hip": ["-ffp-contract=off"],
     "crop_kernels.hip": ["-ffp-contract=off"],       # membership and box-frame coordinates are compared bit for bit
     "assoc_kernels.hip": ["-ffp-contract=off"],      # the assignment's candidate values and duals are compared bit for bit
+    "nms_kernels.hip": ["-ffp-contract=off"],        # IoUs are compared with a threshold; the axis-aligned ones bit for bit
 }
 
 

@@ -1276,7 +1276,8 @@ __device__ __forceinline__ void knn_emit_from_candidates(unsigned long long *can
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
   if (total > 64 && total <= 128) {
-    // 2b. a few candidates too many for one per lane (K = 48: 62-72 of them): the same bound once more, on the
+    // 2b. a few candidates too many for one per lane (K = 48: one query in ten under the two-group bound; K = 64 always):
+    // the plain bound once more, on the
     // candidates -- the minimum of a lane's two candidates, rank K-1 of those 64 (K distinct candidates are
     // <= it) -- and the survivors compacted in place (every lane holds its two before the first write).
     const uint32_t i0 = cand32[2 * lane], d0 = cand32[2 * lane + 1];
@@ -1287,7 +1288,10 @@ __device__ __forceinline__ void knn_emit_from_candidates(unsigned long long *can
     const uint32_t dm = dmr < 0x7F7FFFFFu ? dmr : 0x7F7FFFFFu;   // (+inf / NaN bits: the tagged key must stay a finite float)
     const uint32_t ts2 =
         (uint32_t)__builtin_amdgcn_readlane((int)pcr_wave_sort_posf32((dm & ~63u) | (uint32_t)lane, lane), K - 1);
-    const uint32_t tau2 = ts2 | 63u;
+    // (rank K-1 at the clamp = fewer than K lanes hold a finite candidate, the rest overflowed to +inf: every candidate
+    // passes, as under the first bound, and 3b ranks them by their raw bits.  `ts2 | 63` alone dropped the +inf candidates
+    // and left fewer than K of them)
+    const uint32_t tau2 = ts2 >= 0x7F7FFFC0u ? 0x7F800000u : (ts2 | 63u);
     __builtin_amdgcn_wave_barrier();
     const bool p0 = d0 <= tau2, p1 = has1 && d1 <= tau2;
     const unsigned long long m0 = __ballot(p0), m1 = __ballot(p1);
@@ -1352,6 +1356,56 @@ __device__ __forceinline__ void knn_emit_from_candidates(unsigned long long *can
   }
 }
 
+// ---- the candidate bound from TWO minima per lane (both kNN kernels, K > kKnnTwoMinK).  A lane's points are split into
+// two fixed groups with minima a and c; lo = min(a, c), hi = max(a, c): the 128 values {lo, hi} are distances of 128
+// DISTINCT points (padding points sit at +inf and never pass a compare below).  `sorted` = the lane-tagged keys
+// (lo & ~63) | lane after pcr_wave_sort_posf32: s[0 .. 63] over the lanes.  Why tau = s[r] | 63 is a valid bound:
+//   1. theta_r = s[r] | 63 is >= the lo of the lanes of ranks 0 .. r, so #{lo <= theta_r} >= r + 1;
+//   2. a lane's hi belongs to another point than every lo, so #{points with d <= theta_r} >= f(r) = r + 1 + #{hi <= theta_r};
+//   3. f(r) >= K therefore makes theta_r an upper bound of the K-th smallest distance: every point among the K nearest,
+//      ties by index included, has d <= theta_r, and the exact ranking of the candidates gives the same list for every
+//      such theta.
+// f is non-decreasing and f(K-1) >= K, so a wave-uniform binary search finds the smallest such r <= K-1: per step one
+// v_readlane with a scalar lane, one compare, one s_bcnt1 (five steps at K = 48).  It starts at r = (K-1) / 2: without
+// truncation ties f(r) <= 2 (r + 1), and with them an r above the smallest is still valid by 3.  The r returned is either
+// K-1 (the plain bound) or one whose f was evaluated.  Returns s[r]; the caller applies the clamp rule (keys at 0x7F7FFFC0
+// and above: every point passes) -- below the clamp the lo of ranks 0 .. r and every hi <= theta_r are genuine finite
+// distances (+inf and NaN bits compare above every theta).
+// Rank K-1 of the 64 lane minima alone admits ~85 candidates at K = 48 (a second threshold pass for practically every
+// query, path 2b of knn_emit_from_candidates); this bound ~59, 2b for one query in ten (CPU simulation).
+#ifndef PCR_KNN_TWO_MIN_K
+#define PCR_KNN_TWO_MIN_K 32
+#endif
+// queries of K <= kKnnTwoMinK keep the plain bound: it admits ~43 candidates at K = 32, never more than 64, and the search
+// would cost its ~12 instructions for nothing the ranking notices (from the simulation, not yet from an A/B: -D overrides it
+// for one; docs/DESIGN_HISTORY.md 4.3)
+constexpr int kKnnTwoMinK = PCR_KNN_TWO_MIN_K;
+
+__device__ __forceinline__ uint32_t knn_two_group_rank(uint32_t sorted, uint32_t hi, int K) {
+  int a = (K - 1) >> 1, b = K - 1;   // (K: a scalar register)
+  while (a < b) {
+    const int mid = (a + b) >> 1;
+    const uint32_t theta = (uint32_t)__builtin_amdgcn_readlane((int)sorted, mid) | 63u;
+    const int f = mid + 1 + __popcll(__ballot(hi <= theta));
+    if (f >= K) b = mid;
+    else a = mid + 1;
+  }
+  return (uint32_t)__builtin_amdgcn_readlane((int)sorted, a);
+}
+
+// the sorted key that gives tau: rank K-1 of the lane minima (K <= kKnnTwoMinK), else the two-group bound.  ma / mc: the
+// minima of the lane's two groups as distance bits; K wave-uniform
+__device__ __forceinline__ uint32_t knn_bound_key(uint32_t ma, uint32_t mc, int K, int lane) {
+  const int Ks = __builtin_amdgcn_readfirstlane(K);
+  const uint32_t lo = ma < mc ? ma : mc, hi = ma < mc ? mc : ma;
+  // (a lane without a valid point holds +inf: clamped to the largest finite float so that the tagged key is not a NaN
+  // pattern for the float-bits network)
+  const uint32_t lc = lo < 0x7F7FFFFFu ? lo : 0x7F7FFFFFu;
+  const uint32_t sorted = pcr_wave_sort_posf32((lc & ~63u) | (uint32_t)lane, lane);
+  if (Ks > kKnnTwoMinK) return knn_two_group_rank(sorted, hi, Ks);
+  return (uint32_t)__builtin_amdgcn_readlane((int)sorted, Ks - 1);
+}
+
 // -------------------------------------------------------------- PT neighbour search ----
 // knn_point(K, xyz, xyz[:, :S]) of the Point-Transformer (pointnet2_utils.py:205-216): for each of the first S
 // points its K nearest points in (distance, index) order, distance = pcr_sqdist3.  One wave per query; selection
@@ -1365,7 +1419,8 @@ __device__ __forceinline__ void knn_emit_from_candidates(unsigned long long *can
 // comparand -- on keys whose order is the required one:
 //   tau : lane minima as 32-bit keys (distance bits with the low 6 bits replaced by the lane: unique, and
 //         monotone up to 64 ulps); the lane of rank K-1 gives tau = its distance with those 6 bits SET, still an
-//         upper bound of the K-th smallest distance (K lanes have a minimum <= tau);
+//         upper bound of the K-th smallest distance (K lanes have a minimum <= tau); for K > kKnnTwoMinK a lower rank
+//         that a second minimum per lane proves sufficient (knn_two_group_rank above);
 //   rank: the candidates d <= tau (a few more than K) are compacted one per lane and ranked by their exact
 //         64-bit (distance, index) keys; ranks < K are the answer in (distance, index) order.
 // More than 64 candidates (duplicate-heavy clouds) are ranked four per lane over broadcast LDS reads, more than
@@ -1409,7 +1464,7 @@ __global__ __launch_bounds__(kKnnPThreads) void knn_prefix_reg_kernel(const floa
     const float qx = sx[q], qy = sy[q], qz = sz[q];
     const f32x2 x1 = {qx, qx}, y1 = {qy, qy}, z1 = {qz, qz};
     uint32_t d[T];   // distances as BITS (>= +0: unsigned order = float order; +inf = 0x7f800000 sorts last)
-    uint32_t m = 0xFFFFFFFFu;
+    uint32_t mg[2] = {0xFFFFFFFFu, 0xFFFFFFFFu};   // the minima of the lane's registers t < T/2 and t >= T/2
 #pragma unroll
     for (int t = 0; t < TP; t++) {
       const f32x2 dx = px[t] - x1, dy = py[t] - y1, dz = pz[t] - z1;   // pcr_sqdist3(q, p): p - q
@@ -1420,15 +1475,12 @@ __global__ __launch_bounds__(kKnnPThreads) void knn_prefix_reg_kernel(const floa
       const f32x2 dd = sab + c;
       d[2 * t] = __float_as_uint(dd[0]);
       d[2 * t + 1] = __float_as_uint(dd[1]);
-      const uint32_t m01 = d[2 * t] < d[2 * t + 1] ? d[2 * t] : d[2 * t + 1];
-      m = m01 < m ? m01 : m;
+#pragma unroll
+      for (int e = 2 * t; e < 2 * t + 2; e++) mg[e >= T / 2] = d[e] < mg[e >= T / 2] ? d[e] : mg[e >= T / 2];
     }
-    // 1. the (truncated, lane-tagged) lane minimum of rank K-1: sort the 64 keys across the lanes (21-step network
-    // on float bits, pcr_common.h; a lane without a valid point holds +inf: clamped to the largest finite float so
-    // that the tagged key is not a NaN pattern)
-    const uint32_t mc = m < 0x7F7FFFFFu ? m : 0x7F7FFFFFu;
-    const uint32_t mkey = (mc & ~63u) | (uint32_t)lane;
-    const uint32_t ts = (uint32_t)__builtin_amdgcn_readlane((int)pcr_wave_sort_posf32(mkey, lane), K - 1);
+    // 1. the (truncated, lane-tagged) key that bounds the K-th smallest distance: the 64 lane minima sorted across the
+    // lanes (21-step network on float bits, pcr_common.h), then rank K-1 of them or the two-group bound (knn_bound_key)
+    const uint32_t ts = knn_bound_key(mg[0], mg[1], K, lane);
     // (rank K-1 at the clamp = distances overflowed: let every point pass, the rounds below rank them)
     const uint32_t tau = ts >= 0x7F7FFFC0u ? 0x7F800000u : (ts | 63u);
     // 2. candidates d <= tau, compacted in (t, lane) order: the slot of a candidate is the number of candidates
@@ -1583,7 +1635,7 @@ __global__ __launch_bounds__(NT) void knn_prefix_lds_kernel(const float *__restr
     // instead of being recomputed from a second 64 KB sweep of the LDS copy: the kernel was bound by LDS bandwidth, 128 KB
     // per query; the rare overflow path below still recomputes)
     uint32_t dk[T];
-    uint32_t m = 0xFFFFFFFFu;
+    uint32_t mg[2] = {0xFFFFFFFFu, 0xFFFFFFFFu};   // the minima of the two halves of the lane's points (tp < TP/2, >= TP/2)
 #pragma unroll
     for (int tp = 0; tp < TP; tp++) {
       if ((tp & 3) == 0) __builtin_amdgcn_sched_barrier(0);   // (eight points in flight: all T reads at once would spill)
@@ -1591,14 +1643,12 @@ __global__ __launch_bounds__(NT) void knn_prefix_lds_kernel(const float *__restr
       dk[2 * tp] = __float_as_uint(dd[0]);
       dk[2 * tp + 1] = __float_as_uint(dd[1]);
       const uint32_t m01 = dk[2 * tp] < dk[2 * tp + 1] ? dk[2 * tp] : dk[2 * tp + 1];
-      m = m01 < m ? m01 : m;
+      mg[tp >= TP / 2] = m01 < mg[tp >= TP / 2] ? m01 : mg[tp >= TP / 2];
     }
     __builtin_amdgcn_sched_barrier(0);
     // (the float-bits network of the register kernel: two VALU instructions per step instead of the integer network's four;
-    // a lane whose points are all padding holds +inf: clamped so that the tagged key is not a NaN pattern)
-    const uint32_t mc = m < 0x7F7FFFFFu ? m : 0x7F7FFFFFu;
-    const uint32_t mkey = (mc & ~63u) | (uint32_t)lane;
-    const uint32_t ts = (uint32_t)__builtin_amdgcn_readlane((int)pcr_wave_sort_posf32(mkey, lane), K - 1);
+    // rank K-1 of the lane minima or the two-group bound, knn_bound_key)
+    const uint32_t ts = knn_bound_key(mg[0], mg[1], K, lane);
     const uint32_t tau = ts >= 0x7F7FFFC0u ? 0x7F800000u : (ts | 63u);
     // ---- pass 2 (round 5): the candidates d <= tau WITHOUT a ballot per register.  Every lane shifts one compare per
     // register into private words (v_cmp + v_addc_co: w = 2 w + carry; bit t % 32 of word t / 32 = "my point t passed"),

@@ -92,7 +92,7 @@ __global__ __launch_bounds__(kPairThreads) void assoc_pairs_kernel(const int *__
       int rank = 0;
       for (int cls = 0; cls < ncls; ++cls) {
         const unsigned long long bal = __ballot(x == cls);
-        const int r = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+        const int r = (int)pcr_lanes_below(bal);
         if (x == cls) rank = r;
       }
       if (x >= 0) list[s][cbase[s][x] + cnt[s][c][x] + rank] = i;

@@ -252,7 +252,7 @@ __global__ __launch_bounds__(kCropThreads) void crop_boxes_kernel(const float *_
       float ox, oy, oz;
       const bool in = crop_test(bx, pts, stride, P, ci * kWave + lane, frame, ox, oy, oz);
       const unsigned long long bal = __ballot(in);
-      const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+      const uint32_t rank = pcr_lanes_below(bal);
       const unsigned long long hit = __ballot(in && rank == ri);
       const int src = hit ? __ffsll((long long)hit) - 1 : 0;
       const float vx = __shfl(ox, src, kWave), vy = __shfl(oy, src, kWave), vz = __shfl(oz, src, kWave);

@@ -81,6 +81,11 @@ __device__ __forceinline__ uint32_t pcr_orderable(float v) {
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
+// the number of lanes below the calling one whose bit is set in a ballot: a passing lane's slot in an ordered compaction
+__device__ __forceinline__ uint32_t pcr_lanes_below(unsigned long long mask) {
+  return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+}
+
 __device__ __forceinline__ unsigned long long pcr_wave_max_u64(unsigned long long k) {
 #pragma unroll
   for (int m = 32; m >= 1; m >>= 1) {

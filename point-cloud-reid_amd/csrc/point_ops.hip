@@ -127,6 +127,14 @@ __global__ void fps_kernel(const float *__restrict__ data, float *__restrict__ t
   }
 }
 
+// The low word of point k's packed key: the merge tree's preference of k mod block (the bit-reversed thread id, larger =
+// preferred) in the high bits, 0x3FFFFF - k (smaller k wins) in the low 22; 0 for a point beyond n, which never wins.
+__device__ __forceinline__ uint32_t fps_tie_key(int k, int n, int block, int logb) {
+  const uint32_t tr = (uint32_t)k & (uint32_t)(block - 1);
+  const uint32_t rev = logb ? (__brev(tr) >> (32 - logb)) : 0u;
+  return k < n ? ((((uint32_t)(block - 1) - rev) << 22) | (0x3FFFFFu - (uint32_t)k)) : 0u;
+}
+
 // Fast D-FPS for N <= 4096: 256 threads per cloud, PPT points per thread in registers, the cloud SoA
 // in LDS for the broadcast read of the last pick, one barrier per step.  Same result as fps_kernel:
 // the reference's outcome is the maximum of the total order (distance, merge-tree preference of
@@ -163,9 +171,7 @@ __global__ __launch_bounds__(NT) void fps_fast_kernel(const float *__restrict__ 
     py[p] = ok ? sx[3 * k + 1] : 0.f;
     pz[p] = ok ? sx[3 * k + 2] : 0.f;
     t[p] = ok ? temp[k] : 0.f;
-    const uint32_t tr = (uint32_t)k & (uint32_t)(block - 1);
-    const uint32_t rev = logb ? (__brev(tr) >> (32 - logb)) : 0u;
-    low[p] = ok ? ((((uint32_t)(block - 1) - rev) << 22) | (0x3FFFFFu - (uint32_t)k)) : 0u;
+    low[p] = fps_tie_key(k, n, block, logb);
   }
   int old = 0;
   if (tid == 0) idxs[0] = 0;
@@ -246,6 +252,18 @@ __device__ __forceinline__ f32x2 operator*(const f32x2 &x, const f32x2 &y) { ret
 #endif
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
+// (dx dx + dy dy) + dz dz of a difference, one point (float) or two (f32x2): the order of pcr_sqdist3, every product and
+// sum a statement of its own so that nothing contracts (-ffp-contract=off besides) -- the bits are pcr_sqdist3's.  The
+// direction of the difference is the caller's: p - q in FPS and kNN, centre - p in the ball query.
+template <class V>
+__device__ __forceinline__ V sqdist_terms(V dx, V dy, V dz) {
+  const V a = dx * dx;
+  const V b = dy * dy;
+  const V c = dz * dz;
+  const V s = a + b;
+  return s + c;
+}
+
 __device__ __forceinline__ uint32_t dpp_max_u32(uint32_t v) {
   uint32_t o;
   o = dpp_u32<0xB1>(v); v = o > v ? o : v;
@@ -300,15 +318,111 @@ __device__ __forceinline__ uint32_t fps_slot_bits(const uint32_t (&t)[NS], uint3
   return (uint32_t)__builtin_amdgcn_readlane((int)w, L);
 }
 
+// A lane's coordinates as ONE vector per axis: slot p = element p (pairs (2 p, 2 p + 1) feed the packed arithmetic; the
+// pick reads element `slot` with a wave-uniform DYNAMIC index, i.e. relative register addressing, see fps_pick_coord)
+template <int PP>
+using fps_vec = float __attribute__((ext_vector_type(2 * PP)));
+// the vector forms of the slot search and of the coordinate fetch move ~100 scalar instructions per pick of a
+// 1024-point cloud to ~40 vector ones; clouds of <= 512 points have half the slots, run at higher occupancy (scalar
+// and vector instructions of different waves issue side by side) and are faster with the scalar forms (measured)
+template <int PP>
+constexpr bool kFpsVecPick = PP >= 8;
+
 // The picked point's coordinates come straight out of the register file: the pick `old` is wave-uniform, so its slot
 // (old / 64) selects a REGISTER -- a wave-uniform dynamic index into the per-axis vector of a lane's coordinates, which
 // the compiler turns into relative register addressing (s_set_gpr_idx_on + v_mov_b32) -- and v_readlane fetches lane
-// old % 64 of it: ~12 instructions, no branch.  (Rounds 2-4, and still for clouds of <= 512 points: a scalar `switch` over
-// the slot, which the structuriser compiles into a chain of fall-through flags -- ~35 scalar instructions and eight
-// branches per pick of a 1024-point cloud.)  (Round 2 kept a
-// {x,y,z,-} copy of the cloud in LDS for one broadcast read per pick: 16 KB per wave, which held a CU to ten waves --
-// 2.5 per SIMD, 4096 clouds = 1.6 rounds -- and put an LDS round trip on every pick's critical path; without it four
-// waves share a SIMD and the chip takes 4096 clouds in one round.)
+// old % 64 of it: ~12 instructions, no branch.  Clouds of <= 512 points: a scalar `switch` over the slot, which the
+// structuriser compiles into a chain of fall-through flags -- ~35 scalar instructions and eight branches per pick of a
+// 1024-point cloud.  (No LDS copy of the cloud: 16 KB per wave would hold a CU to ten waves and put an LDS round trip
+// on every pick's critical path; without it four waves share a SIMD and the chip takes 4096 clouds in one round.)
+// -> {x, y, z, 0}.  (Vectors in and a vector out BY VALUE: with reference parameters the kernels' register allocation
+// changes.)
+template <int PP>
+__device__ __forceinline__ f32x4 fps_pick_coord(fps_vec<PP> vx, fps_vec<PP> vy, fps_vec<PP> vz, int old) {
+  const int slot = __builtin_amdgcn_readfirstlane(old >> 6), ln = __builtin_amdgcn_readfirstlane(old & 63);
+  float ox = 0.f, oy = 0.f, oz = 0.f;
+  if constexpr (kFpsVecPick<PP>) {
+    ox = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(vx[slot]), ln));
+    oy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(vy[slot]), ln));
+    oz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(vz[slot]), ln));
+  } else {
+#define PCR_FPS_PICK(P)                                                               \
+  case P:                                                                             \
+    if constexpr (P < 2 * PP) {                                                       \
+      ox = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(vx[P]), ln));      \
+      oy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(vy[P]), ln));      \
+      oz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(vz[P]), ln));      \
+    }                                                                                 \
+    break;
+    switch (slot) {
+      PCR_FPS_PICK(0) PCR_FPS_PICK(1) PCR_FPS_PICK(2) PCR_FPS_PICK(3) PCR_FPS_PICK(4) PCR_FPS_PICK(5) PCR_FPS_PICK(6)
+      PCR_FPS_PICK(7)
+      default: break;
+    }
+#undef PCR_FPS_PICK
+  }
+  return f32x4{ox, oy, oz, 0.f};
+}
+
+// The running minima back to `temp` (they are kept as BITS: for floats >= +0 the unsigned order of the bit patterns is the
+// float order, and integer min / max need no NaN canonicalisation instructions)
+template <int PP>
+__device__ __forceinline__ void fps_store_minima(float *temp, int n, int lane, const uint32_t (&t)[2 * PP]) {
+#pragma unroll
+  for (int p = 0; p < 2 * PP; p++) {
+    const int k = lane + 64 * p;
+    if (k < n) temp[k] = __uint_as_float(t[p]);
+  }
+}
+
+// The next pick when ONE point holds the wave maximum `best` of the running minima (mx: the lane's maximum) -- almost
+// always: one lane and, in it, one slot; the pick is then 64 slot + lane, found by the slots' equality words
+// (fps_slot_bits) or, for the small clouds, a scalar walk over the slots' equality masks, instead of the 40-instruction
+// tie-break pass and its second wave reduction.  Returns false, `old` untouched, for anything else -- two lanes, or two
+// slots of the lane: the caller then takes the reference's tie rule, fps_tie_pick.
+template <int PP>
+__device__ __forceinline__ bool fps_unique_pick(const uint32_t (&t)[2 * PP], uint32_t mx, uint32_t best, int &old) {
+  const unsigned long long lm = __ballot(mx == best);
+  bool unique = __popcll(lm) == 1;
+  if (unique) {
+    const int L = (int)__builtin_ctzll(lm);
+    if constexpr (kFpsVecPick<PP>) {
+      const uint32_t sb = fps_slot_bits<2 * PP>(t, best, L);
+      if (__popc(sb) == 1) old = 64 * (2 * PP - 1 - (int)__builtin_ctz(sb)) + L;
+      else unique = false;
+    } else {
+      int hits = 0, slot_found = 0;
+#pragma unroll
+      for (int p = 0; p < 2 * PP; p++) {
+        const unsigned long long mp = __ballot(t[p] == best);
+        const int bit = (int)((mp >> L) & 1ull);
+        hits += bit;
+        slot_found = bit ? p : slot_found;
+      }
+      if (hits == 1) old = 64 * slot_found + L;
+      else unique = false;
+    }
+  }
+  return unique;
+}
+
+// The reference's tie rule among the points that attain `best`: the largest tie key (fps_tie_key; key_of_slot(p) = that of
+// the lane's slot p) wins.  -> the pick
+template <int PP, class KeyOfSlot>
+__device__ __forceinline__ int fps_tie_pick(const uint32_t (&t)[2 * PP], uint32_t best, KeyOfSlot key_of_slot) {
+  uint32_t lo = 0u;
+#pragma unroll
+  for (int p = 0; p < PP; p++) {   // (pairs: the two selects feed one three-way max)
+    const uint32_t k0 = key_of_slot(2 * p), k1 = key_of_slot(2 * p + 1);   // (unconditionally: selects, not branches)
+    const uint32_t l0 = t[2 * p] == best ? k0 : 0u;
+    const uint32_t l1 = t[2 * p + 1] == best ? k1 : 0u;
+    const uint32_t l01 = l0 > l1 ? l0 : l1;
+    lo = l01 > lo ? l01 : lo;
+  }
+  lo = dpp_max_u32(lo);
+  return (int)(0x3FFFFFu - (lo & 0x3FFFFFu));
+}
+
 template <int PP>   // point PAIRS per lane: n <= 128 * PP
 __global__ __launch_bounds__(64) void fps_wave_kernel(const float *__restrict__ xyz, float *__restrict__ temp,
                                                       int *__restrict__ idxs, int n, int m, int block, int logb) {
@@ -317,16 +431,7 @@ __global__ __launch_bounds__(64) void fps_wave_kernel(const float *__restrict__ 
   xyz += cloud * n * 3;
   temp += cloud * n;
   idxs += cloud * m;
-  // the running minimum distances are kept as BITS: for floats >= +0 the unsigned order of the bit
-  // patterns is the float order, and integer min / max need no NaN canonicalisation instructions
-  // a lane's coordinates as ONE vector per axis: slot p = element p (pairs (2 p, 2 p + 1) feed the packed arithmetic; the
-  // pick reads element `slot` with a wave-uniform DYNAMIC index, i.e. relative register addressing, see fps_pick_coord)
-  typedef float fvec __attribute__((ext_vector_type(2 * PP)));
-  fvec vx, vy, vz;
-  // the vector forms of the slot search and of the coordinate fetch move ~100 scalar instructions per pick of a
-  // 1024-point cloud to ~40 vector ones; clouds of <= 512 points have half the slots, run at higher occupancy (scalar
-  // and vector instructions of different waves issue side by side) and are faster with the scalar forms (measured)
-  constexpr bool kVecPick = PP >= 8;
+  fps_vec<PP> vx, vy, vz;
   uint32_t t[2 * PP], low[2 * PP];
 #pragma unroll
   for (int p = 0; p < 2 * PP; p++) {
@@ -338,47 +443,20 @@ __global__ __launch_bounds__(64) void fps_wave_kernel(const float *__restrict__ 
     vy[p] = ok ? y : 0.f;
     vz[p] = ok ? z : 0.f;
     t[p] = ok ? __float_as_uint(tk) : 0u;   // min(d, 0) = 0: a point beyond n never beats a real one (low = 0)
-    const uint32_t tr = (uint32_t)k & (uint32_t)(block - 1);
-    const uint32_t rev = logb ? (__brev(tr) >> (32 - logb)) : 0u;
-    low[p] = ok ? ((((uint32_t)(block - 1) - rev) << 22) | (0x3FFFFFu - (uint32_t)k)) : 0u;
+    low[p] = fps_tie_key(k, n, block, logb);
     asm volatile("" : "+v"(low[p]));   // keep the value in a register (else it is re-derived from masks every step)
   }
   int old = 0;
   if (lane == 0) idxs[0] = 0;
   for (int j = 1; j < m; j++) {
-    const int slot = __builtin_amdgcn_readfirstlane(old >> 6), ln = __builtin_amdgcn_readfirstlane(old & 63);
-    float ox = 0.f, oy = 0.f, oz = 0.f;
-    if constexpr (kVecPick) {
-      ox = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(vx[slot]), ln));
-      oy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(vy[slot]), ln));
-      oz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(vz[slot]), ln));
-    } else {
-#define PCR_FPS_PICK(P)                                                               \
-  case P:                                                                             \
-    if constexpr (P < 2 * PP) {                                                       \
-      ox = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(vx[P]), ln));      \
-      oy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(vy[P]), ln));      \
-      oz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(vz[P]), ln));      \
-    }                                                                                 \
-    break;
-      switch (slot) {
-        PCR_FPS_PICK(0) PCR_FPS_PICK(1) PCR_FPS_PICK(2) PCR_FPS_PICK(3) PCR_FPS_PICK(4) PCR_FPS_PICK(5) PCR_FPS_PICK(6)
-        PCR_FPS_PICK(7)
-        default: break;
-      }
-#undef PCR_FPS_PICK
-    }
+    const f32x4 o = fps_pick_coord<PP>(vx, vy, vz, old);
+    const float ox = o[0], oy = o[1], oz = o[2];
     const f32x2 x1 = {ox, ox}, y1 = {oy, oy}, z1 = {oz, oz};
     uint32_t mx = 0u;
 #pragma unroll
     for (int p = 0; p < PP; p++) {
-      const f32x2 dx = f32x2{vx[2 * p], vx[2 * p + 1]} - x1, dy = f32x2{vy[2 * p], vy[2 * p + 1]} - y1,
-                  dz = f32x2{vz[2 * p], vz[2 * p + 1]} - z1;
-      const f32x2 a = dx * dx;
-      const f32x2 b = dy * dy;
-      const f32x2 c = dz * dz;
-      const f32x2 s = a + b;
-      const f32x2 d = s + c;
+      const f32x2 d = sqdist_terms(f32x2{vx[2 * p], vx[2 * p + 1]} - x1, f32x2{vy[2 * p], vy[2 * p + 1]} - y1,
+                                   f32x2{vz[2 * p], vz[2 * p + 1]} - z1);
       const uint32_t d0 = __float_as_uint(d[0]), d1 = __float_as_uint(d[1]);
       t[2 * p] = d0 < t[2 * p] ? d0 : t[2 * p];
       t[2 * p + 1] = d1 < t[2 * p + 1] ? d1 : t[2 * p + 1];
@@ -386,50 +464,10 @@ __global__ __launch_bounds__(64) void fps_wave_kernel(const float *__restrict__ 
       mx = m01 > mx ? m01 : mx;
     }
     const uint32_t best = dpp_max_u32(mx);
-    // which point holds it?  Almost always ONE lane and, in it, ONE slot: then the pick is 64 slot + lane, found by a scalar
-    // walk over the slots' equality masks (16 compares + scalar bit tests instead of the 40-instruction tie-break pass and
-    // its second wave reduction).  Anything else -- two lanes, or two slots of the lane -- takes the reference's tie rule
-    // below, unchanged.
-    const unsigned long long lm = __ballot(mx == best);
-    bool unique = __popcll(lm) == 1;
-    if (unique) {
-      const int L = (int)__builtin_ctzll(lm);
-      if constexpr (kVecPick) {
-        const uint32_t sb = fps_slot_bits<2 * PP>(t, best, L);
-        if (__popc(sb) == 1) old = 64 * (2 * PP - 1 - (int)__builtin_ctz(sb)) + L;
-        else unique = false;
-      } else {
-        int hits = 0, slot_found = 0;
-#pragma unroll
-        for (int p = 0; p < 2 * PP; p++) {
-          const unsigned long long mp = __ballot(t[p] == best);
-          const int bit = (int)((mp >> L) & 1ull);
-          hits += bit;
-          slot_found = bit ? p : slot_found;
-        }
-        if (hits == 1) old = 64 * slot_found + L;
-        else unique = false;
-      }
-    }
-    if (!unique) {
-      uint32_t lo = 0u;
-#pragma unroll
-      for (int p = 0; p < PP; p++) {   // (pairs: the two selects feed one three-way max)
-        const uint32_t l0 = t[2 * p] == best ? low[2 * p] : 0u;
-        const uint32_t l1 = t[2 * p + 1] == best ? low[2 * p + 1] : 0u;
-        const uint32_t l01 = l0 > l1 ? l0 : l1;
-        lo = l01 > lo ? l01 : lo;
-      }
-      lo = dpp_max_u32(lo);
-      old = (int)(0x3FFFFFu - (lo & 0x3FFFFFu));
-    }
+    if (!fps_unique_pick<PP>(t, mx, best, old)) old = fps_tie_pick<PP>(t, best, [&](int p) { return low[p]; });
     if (lane == 0) idxs[j] = old;
   }
-#pragma unroll
-  for (int p = 0; p < 2 * PP; p++) {
-    const int k = lane + 64 * p;
-    if (k < n) temp[k] = __uint_as_float(t[p]);
-  }
+  fps_store_minima<PP>(temp, n, lane, t);
 }
 
 // D-FPS and the ball query of the picked centres in ONE pass (round 5).  A pick's distances to every point of the cloud
@@ -454,14 +492,7 @@ __global__ __launch_bounds__(64) void fps_bq_wave_kernel(const float *__restrict
   constexpr int cpw = 16;
   const int nitems = (m + cpw - 1) / cpw;
   f32x4 *rcloud = rows_out + cloud * (size_t)nitems * (size_t)(cpw * K);
-  // a lane's coordinates as ONE vector per axis: slot p = element p (pairs (2 p, 2 p + 1) feed the packed arithmetic; the
-  // pick reads element `slot` with a wave-uniform DYNAMIC index, i.e. relative register addressing, see fps_pick_coord)
-  typedef float fvec __attribute__((ext_vector_type(2 * PP)));
-  fvec vx, vy, vz;
-  // the vector forms of the slot search and of the coordinate fetch move ~100 scalar instructions per pick of a
-  // 1024-point cloud to ~40 vector ones; clouds of <= 512 points have half the slots, run at higher occupancy (scalar
-  // and vector instructions of different waves issue side by side) and are faster with the scalar forms (measured)
-  constexpr bool kVecPick = PP >= 8;
+  fps_vec<PP> vx, vy, vz;
   uint32_t t[2 * PP];
 #pragma unroll
   for (int p = 0; p < 2 * PP; p++) {
@@ -472,7 +503,7 @@ __global__ __launch_bounds__(64) void fps_bq_wave_kernel(const float *__restrict
     vx[p] = ok ? x : INFINITY;    // a point at infinity is never inside a ball (and min(inf, 0) = 0 below)
     vy[p] = ok ? y : INFINITY;
     vz[p] = ok ? z : INFINITY;
-    t[p] = ok ? __float_as_uint(tk) : 0u;     // min(d, 0) = 0: a point beyond n never beats a real one
+    t[p] = ok ? __float_as_uint(tk) : 0u;   // min(d, 0) = 0: a point beyond n never beats a real one
   }
   typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
   // one buffer descriptor for the cloud's whole row region (items of cpw K rows follow each other; a descriptor per item
@@ -482,36 +513,11 @@ __global__ __launch_bounds__(64) void fps_bq_wave_kernel(const float *__restrict
   int old = 0, roff = 0;
   int acc_i = 0, acc_x = 0, acc_y = 0, acc_z = 0, acc_c = 0;
   for (int j = 0; j < m; j++) {
-    if (j == m - 1) {   // the running minima as pcr_fps_f32 leaves them: the last centre does not enter them
-#pragma unroll
-      for (int p = 0; p < 2 * PP; p++) {
-        const int k = lane + 64 * p;
-        if (k < n) temp[k] = __uint_as_float(t[p]);
-      }
-    }
+    // the running minima as pcr_fps_f32 leaves them: the last centre does not enter them
+    if (j == m - 1) fps_store_minima<PP>(temp, n, lane, t);
     // ---- centre j = point `old`: its coordinates out of the register file
-    const int slot = __builtin_amdgcn_readfirstlane(old >> 6), ln = __builtin_amdgcn_readfirstlane(old & 63);
-    float ox = 0.f, oy = 0.f, oz = 0.f;
-    if constexpr (kVecPick) {
-      ox = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(vx[slot]), ln));
-      oy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(vy[slot]), ln));
-      oz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(vz[slot]), ln));
-    } else {
-#define PCR_FPS_PICK(P)                                                               \
-  case P:                                                                             \
-    if constexpr (P < 2 * PP) {                                                       \
-      ox = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(vx[P]), ln));      \
-      oy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(vy[P]), ln));      \
-      oz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(vz[P]), ln));      \
-    }                                                                                 \
-    break;
-      switch (slot) {
-        PCR_FPS_PICK(0) PCR_FPS_PICK(1) PCR_FPS_PICK(2) PCR_FPS_PICK(3) PCR_FPS_PICK(4) PCR_FPS_PICK(5) PCR_FPS_PICK(6)
-        PCR_FPS_PICK(7)
-        default: break;
-      }
-#undef PCR_FPS_PICK
-    }
+    const f32x4 o = fps_pick_coord<PP>(vx, vy, vz, old);
+    const float ox = o[0], oy = o[1], oz = o[2];
     // (what a pick leaves behind -- index, centre, hit count -- is parked in lane j % 64 of five registers by v_writelane
     // and leaves as whole stores every 64 picks: a lane-0 store per pick and value was ~20 instructions behind an exec
     // mask)
@@ -525,13 +531,8 @@ __global__ __launch_bounds__(64) void fps_bq_wave_kernel(const float *__restrict
     uint32_t mx = 0u;
 #pragma unroll
     for (int p = 0; p < PP; p++) {
-      const f32x2 dx = f32x2{vx[2 * p], vx[2 * p + 1]} - x1, dy = f32x2{vy[2 * p], vy[2 * p + 1]} - y1,
-                  dz = f32x2{vz[2 * p], vz[2 * p + 1]} - z1;
-      const f32x2 a = dx * dx;
-      const f32x2 b = dy * dy;
-      const f32x2 c = dz * dz;
-      const f32x2 s = a + b;
-      const f32x2 d = s + c;
+      const f32x2 d = sqdist_terms(f32x2{vx[2 * p], vx[2 * p + 1]} - x1, f32x2{vy[2 * p], vy[2 * p + 1]} - y1,
+                                   f32x2{vz[2 * p], vz[2 * p + 1]} - z1);
       hit[2 * p] = d[0] < max_r2;         // (kept as lane masks: the hit blocks below take "my point" from them)
       hit[2 * p + 1] = d[1] < max_r2;
       mk[2 * p] = __ballot(hit[2 * p]);
@@ -563,8 +564,7 @@ __global__ __launch_bounds__(64) void fps_bq_wave_kernel(const float *__restrict
 #pragma unroll
       for (int q = 0; q < 2 * PP; q++) {
         if (__builtin_expect(mk[q] != 0ull, 0)) {   // wave-uniform: hits are rare (a few per 1024 points; out of line)
-          const int pos = cnt + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mk[q] >> 32),
-                                                                __builtin_amdgcn_mbcnt_lo((uint32_t)mk[q], 0u));
+          const int pos = cnt + (int)pcr_lanes_below(mk[q]);
           const bool mine = hit[q];
           // (rounds 5a-5f routed the point's coordinates through an opaque copy inside the branch, because the compiler
           // speculated the row data of all 2 PP slots above the wave-uniform branches; with the hit blocks out of line
@@ -609,45 +609,25 @@ __global__ __launch_bounds__(64) void fps_bq_wave_kernel(const float *__restrict
     if (j + 1 >= m) break;
     // ---- the next pick (fps_wave_kernel): the maximum of the running minima, the reference's tie rule
     const uint32_t best = dpp_max_u32(mx);
-    const unsigned long long lm = __ballot(mx == best);
-    bool unique = __popcll(lm) == 1;
-    if (unique) {
-      const int L = (int)__builtin_ctzll(lm);
-      if constexpr (kVecPick) {
-        const uint32_t sb = fps_slot_bits<2 * PP>(t, best, L);
-        if (__popc(sb) == 1) old = 64 * (2 * PP - 1 - (int)__builtin_ctz(sb)) + L;
-        else unique = false;
-      } else {
-        int hits = 0, slot_found = 0;
-#pragma unroll
-        for (int p = 0; p < 2 * PP; p++) {
-          const unsigned long long mp = __ballot(t[p] == best);
-          const int bit = (int)((mp >> L) & 1ull);
-          hits += bit;
-          slot_found = bit ? p : slot_found;
-        }
-        if (hits == 1) old = 64 * slot_found + L;
-        else unique = false;
-      }
-    }
-    if (!unique) {   // rare: the tie keys are derived here, not kept in registers (the opaque lane keeps them from
-      // being hoisted out of the pick loop again)
-      uint32_t lo = 0u;
+    if (!fps_unique_pick<PP>(t, mx, best, old)) {   // rare: the tie keys are derived here, not kept in registers (the
+      // opaque lane keeps them from being hoisted out of the pick loop again)
       int lane_o = lane;
       asm volatile("" : "+v"(lane_o));
-#pragma unroll
-      for (int p = 0; p < 2 * PP; p++) {
-        const int k = lane_o + 64 * p;
-        const uint32_t tr = (uint32_t)k & (uint32_t)(block - 1);
-        const uint32_t rev = logb ? (__brev(tr) >> (32 - logb)) : 0u;
-        const uint32_t lowp = k < n ? ((((uint32_t)(block - 1) - rev) << 22) | (0x3FFFFFu - (uint32_t)k)) : 0u;
-        const uint32_t l0 = t[p] == best ? lowp : 0u;
-        lo = l0 > lo ? l0 : lo;
-      }
-      lo = dpp_max_u32(lo);
-      old = (int)(0x3FFFFFu - (lo & 0x3FFFFFu));
+      old = fps_tie_pick<PP>(t, best, [&](int p) { return fps_tie_key(lane_o + 64 * p, n, block, logb); });
     }
   }
+}
+
+// The wave kernels' size classes: clouds of up to 128 / 256 / 512 / 1024 points keep PP = 1 / 2 / 4 / 8 point pairs per lane.
+// -> f(std::integral_constant<int, PP>) for the class of N <= 1024, the kernel's template argument
+static inline int pcr_size_class(int N) { return N <= 128 ? 0 : N <= 256 ? 1 : N <= 512 ? 2 : 3; }
+template <class F>
+static int pcr_by_size_class(int N, F f) {
+  const int c = pcr_size_class(N);
+  if (c == 0) return f(std::integral_constant<int, 1>{});
+  if (c == 1) return f(std::integral_constant<int, 2>{});
+  if (c == 2) return f(std::integral_constant<int, 4>{});
+  return f(std::integral_constant<int, 8>{});
 }
 
 int fps_launch(bool dist, const float *data, float *temp, int *idx, int B, int N, int M,
@@ -658,11 +638,9 @@ int fps_launch(bool dist, const float *data, float *temp, int *idx, int B, int N
   while ((2 << logb) <= N && logb < 10) logb++;  // block = min(1024, 2^floor(log2 N))
   int block = 1 << logb;
   if (!dist && N <= 1024 && M > 1) {
-    const dim3 gw(B), bw(64);
-    if (N <= 128) return pcr_launch<fps_wave_kernel<1>>(gw, bw, 0, st, data, temp, idx, N, M, block, logb);
-    if (N <= 256) return pcr_launch<fps_wave_kernel<2>>(gw, bw, 0, st, data, temp, idx, N, M, block, logb);
-    if (N <= 512) return pcr_launch<fps_wave_kernel<4>>(gw, bw, 0, st, data, temp, idx, N, M, block, logb);
-    return pcr_launch<fps_wave_kernel<8>>(gw, bw, 0, st, data, temp, idx, N, M, block, logb);
+    return pcr_by_size_class(N, [&](auto pp) {
+      return pcr_launch<fps_wave_kernel<decltype(pp)::value>>(dim3(B), dim3(64), 0, st, data, temp, idx, N, M, block, logb);
+    });
   }
   if (!dist && N <= 4096 && M > 1) {
     const size_t lds_fast = 64 + (size_t)3 * N * sizeof(float);
@@ -873,6 +851,8 @@ __global__ __launch_bounds__(256) void ball_query_reg_kernel(const float *__rest
       unsigned long long mk[PPL];
 #pragma unroll
       for (int t = 0; t < PPL / 2; t++) {
+        // (sqdist_terms's statements in place: through the helper the kRows variants allocate four more VGPRs -- 132 at
+        // PPL = 16, a wave of occupancy)
         const f32x2 dx = x1 - px[t], dy = y1 - py[t], dz = z1 - pz[t];   // pcr_sqdist3(p, centre): centre - p
         const f32x2 a2 = dx * dx;
         const f32x2 b2 = dy * dy;
@@ -887,8 +867,7 @@ __global__ __launch_bounds__(256) void ball_query_reg_kernel(const float *__rest
 #pragma unroll
       for (int j = 0; j < PPL; j++) {
         if (mk[j] != 0ull) {   // wave-uniform, ONE scalar test per j (the scalar unit is shared by the CU's four SIMDs)
-          const int pos = cnt + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mk[j] >> 32),
-                                                                __builtin_amdgcn_mbcnt_lo((uint32_t)mk[j], 0u));
+          const int pos = cnt + (int)pcr_lanes_below(mk[j]);
           if (hit[j] && pos < K) {
             if (gout) {
               if (staged) row[pos] = j * 64 + lane;   // (kept apart: one pointer for both would be a flat store)
@@ -942,37 +921,21 @@ __global__ __launch_bounds__(256) void ball_query_reg_kernel(const float *__rest
 
 static int ball_query_launch(const float *centres, const float *xyz, int *idx, int *cnt, int B, int N, int M,
                               float min_r2, float max_r2, int K, hipStream_t st, float *rows = nullptr) {
-  if (rows) {   // (validated by the caller: N <= 1024, min radius 0, K even)
-    const int cpw = 16, nchunk = (M + 4 * cpw - 1) / (4 * cpw);
-    const dim3 grid((unsigned)((B + 7) / 8) * 8 * nchunk), blk(256);
-    f32x4 *r4 = reinterpret_cast<f32x4 *>(rows);
-    if (N <= 256)
-      return pcr_launch<ball_query_reg_kernel<4, true, true>>(grid, blk, 0, st, centres, xyz, idx, N, M, min_r2, max_r2, K,
-                                                              cnt, cpw, nchunk, B, r4);
-    if (N <= 512)
-      return pcr_launch<ball_query_reg_kernel<8, true, true>>(grid, blk, 0, st, centres, xyz, idx, N, M, min_r2, max_r2, K,
-                                                              cnt, cpw, nchunk, B, r4);
-    return pcr_launch<ball_query_reg_kernel<16, true, true>>(grid, blk, 0, st, centres, xyz, idx, N, M, min_r2, max_r2, K,
-                                                             cnt, cpw, nchunk, B, r4);
-  }
-  if (N <= 1024) {
+  if (N <= 1024) {   // (rows: validated by the caller -- N <= 1024, min radius 0, K even)
     const int cpw = 16;                                  // centres per wave
     const int nchunk = (M + 4 * cpw - 1) / (4 * cpw);
     const dim3 grid((unsigned)((B + 7) / 8) * 8 * nchunk), blk(256);
     const bool simple = min_r2 == 0.f && max_r2 > 0.f;
-    const int ppl = N <= 256 ? 4 : (N <= 512 ? 8 : 16);
-    if (ppl == 4 && simple) return pcr_launch<ball_query_reg_kernel<4, true>>(grid, blk, 0, st, centres, xyz, idx, N, M,
-      min_r2, max_r2, K, cnt, cpw, nchunk, B, (f32x4 *)nullptr);
-    if (ppl == 4) return pcr_launch<ball_query_reg_kernel<4, false>>(grid, blk, 0, st, centres, xyz, idx, N, M,
-      min_r2, max_r2, K, cnt, cpw, nchunk, B, (f32x4 *)nullptr);
-    if (ppl == 8 && simple) return pcr_launch<ball_query_reg_kernel<8, true>>(grid, blk, 0, st, centres, xyz, idx, N, M,
-      min_r2, max_r2, K, cnt, cpw, nchunk, B, (f32x4 *)nullptr);
-    if (ppl == 8) return pcr_launch<ball_query_reg_kernel<8, false>>(grid, blk, 0, st, centres, xyz, idx, N, M,
-      min_r2, max_r2, K, cnt, cpw, nchunk, B, (f32x4 *)nullptr);
-    if (simple) return pcr_launch<ball_query_reg_kernel<16, true>>(grid, blk, 0, st, centres, xyz, idx, N, M,
-      min_r2, max_r2, K, cnt, cpw, nchunk, B, (f32x4 *)nullptr);
-    return pcr_launch<ball_query_reg_kernel<16, false>>(grid, blk, 0, st, centres, xyz, idx, N, M,
-      min_r2, max_r2, K, cnt, cpw, nchunk, B, (f32x4 *)nullptr);
+    f32x4 *r4 = reinterpret_cast<f32x4 *>(rows);
+    return pcr_by_size_class(N, [&](auto pp) {
+      constexpr int PPL = decltype(pp)::value < 2 ? 4 : 2 * decltype(pp)::value;   // 4 / 8 / 16 points per lane
+      auto go = [&](auto simple_c, auto rows_c) {
+        return pcr_launch<ball_query_reg_kernel<PPL, decltype(simple_c)::value, decltype(rows_c)::value>>(
+            grid, blk, 0, st, centres, xyz, idx, N, M, min_r2, max_r2, K, cnt, cpw, nchunk, B, r4);
+      };
+      return rows ? go(std::true_type{}, std::true_type{}) : simple ? go(std::true_type{}, std::false_type{})
+                                                                    : go(std::false_type{}, std::false_type{});
+    });
   }
   return pcr_launch<ball_query_kernel<false>>(dim3((M + 255) / 256, B), dim3(256), 0, st, centres, xyz, idx, N, M, min_r2,
                                               max_r2, K, cnt);
@@ -1266,6 +1229,25 @@ __device__ __forceinline__ int pcr_wave_incl_scan_i32(int x) {
 constexpr int kKnnPThreads = 256;
 constexpr int kKnnCap = 256;  // candidates per query the fast path can rank (4 per lane)
 
+// ---- 32-bit keys of the float-bits sorting network (pcr_wave_sort_posf32): distance bits with the low 6 bits replaced by
+// the lane -- unique, and monotone up to 64 ulps.  A tagged key must stay a finite float: a distance that overflowed to
+// +inf, or a NaN, would make it a NaN pattern, which the float-min network mis-orders, so the distance is clamped to the
+// largest finite float first.  Keys at kKnnPadKey and above are therefore "no finite distance here": clamped distances,
+// and the padding keys kKnnPadKey | lane of lanes without a candidate.
+constexpr uint32_t kKnnMaxFinite = 0x7F7FFFFFu;
+constexpr uint32_t kKnnPadKey = kKnnMaxFinite & ~63u;
+__device__ __forceinline__ uint32_t knn_tagged_key(uint32_t dist_bits, int lane) {
+  const uint32_t c = dist_bits < kKnnMaxFinite ? dist_bits : kKnnMaxFinite;
+  return (c & ~63u) | (uint32_t)lane;
+}
+// The threshold that a sorted key of rank r gives: its distance with the 6 tag bits SET, an upper bound of the distances
+// of ranks 0 .. r.  The clamp rule: a rank at kKnnPadKey or above means that fewer than r + 1 lanes hold a finite
+// distance, the rest overflowed to +inf -- then EVERY candidate passes (+inf bits included; `key | 63` alone would drop
+// them and leave fewer than K), and the exact ranking that follows orders them by their raw bits.
+__device__ __forceinline__ uint32_t knn_tau(uint32_t sorted_key) {
+  return sorted_key >= kKnnPadKey ? 0x7F800000u : (sorted_key | 63u);
+}
+
 // Ranks 0 .. K-1 of `total` <= kKnnCap candidates {index, distance bits} (= 64-bit (distance, index) keys) in the wave's
 // LDS strip `cand` -> out[0 .. K), in (distance, index) order.  Shared by the register and the LDS kNN kernels.
 // out_b / Kb (optional): the first Kb <= K ranks are ALSO written there (pcr_knn_prefix2_f32: the K-nearest list of a
@@ -1283,22 +1265,17 @@ __device__ __forceinline__ void knn_emit_from_candidates(unsigned long long *can
     const uint32_t i0 = cand32[2 * lane], d0 = cand32[2 * lane + 1];
     const bool has1 = lane + 64 < total;
     const uint32_t i1 = cand32[2 * lane + 128], d1r = cand32[2 * lane + 129];
-    const uint32_t d1 = has1 ? d1r : 0x7F7FFFFFu;
-    const uint32_t dmr = d0 < d1 ? d0 : d1;
-    const uint32_t dm = dmr < 0x7F7FFFFFu ? dmr : 0x7F7FFFFFu;   // (+inf / NaN bits: the tagged key must stay a finite float)
-    const uint32_t ts2 =
-        (uint32_t)__builtin_amdgcn_readlane((int)pcr_wave_sort_posf32((dm & ~63u) | (uint32_t)lane, lane), K - 1);
-    // (rank K-1 at the clamp = fewer than K lanes hold a finite candidate, the rest overflowed to +inf: every candidate
-    // passes, as under the first bound, and 3b ranks them by their raw bits.  `ts2 | 63` alone dropped the +inf candidates
-    // and left fewer than K of them)
-    const uint32_t tau2 = ts2 >= 0x7F7FFFC0u ? 0x7F800000u : (ts2 | 63u);
+    const uint32_t d1 = has1 ? d1r : kKnnMaxFinite;
+    const uint32_t dm = d0 < d1 ? d0 : d1;
+    // (at the clamp every candidate passes, as under the first bound, and 3b ranks them: knn_tau)
+    const uint32_t tau2 = knn_tau(
+        (uint32_t)__builtin_amdgcn_readlane((int)pcr_wave_sort_posf32(knn_tagged_key(dm, lane), lane), K - 1));
     __builtin_amdgcn_wave_barrier();
     const bool p0 = d0 <= tau2, p1 = has1 && d1 <= tau2;
     const unsigned long long m0 = __ballot(p0), m1 = __ballot(p1);
-    const int s0 = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m0 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m0, 0u));
+    const int s0 = (int)pcr_lanes_below(m0);
     const int n0 = __popcll(m0);
-    const int s1 = n0 + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m1 >> 32),
-                                                        __builtin_amdgcn_mbcnt_lo((uint32_t)m1, 0u));
+    const int s1 = n0 + (int)pcr_lanes_below(m1);
     if (p0) {
       cand32[2 * s0] = i0;
       cand32[2 * s0 + 1] = d0;
@@ -1315,12 +1292,9 @@ __device__ __forceinline__ void knn_emit_from_candidates(unsigned long long *can
     // 3a. one candidate per lane.  Fast form: sort 32-bit keys (distance bits with the low 6 bits replaced by
     // the SLOT) with the float network; exact unless two of the first K + 1 ranks share their truncated
     // distance (~1 % of the queries), which is detected on the sorted keys and sent through the 64-bit sort.
-    // (a distance that overflowed to +inf, or a NaN, would make the tagged key a NaN pattern, which the float-min
-    // network mis-orders: clamped to the largest finite float -- such candidates then share their truncated key and
-    // the tie detector below sends the query through the exact 64-bit path, which sorts the RAW bits)
-    const uint32_t djr = cand32[2 * lane + 1];
-    const uint32_t dj = djr < 0x7F7FFFFFu ? djr : 0x7F7FFFFFu;
-    const uint32_t key = lane < total ? ((dj & ~63u) | (uint32_t)lane) : (0x7F7FFFC0u | (uint32_t)lane);
+    // (candidates at +inf share their clamped key, knn_tagged_key: the tie detector below then sends the query through
+    // the exact 64-bit path, which sorts the RAW bits)
+    const uint32_t key = lane < total ? knn_tagged_key(cand32[2 * lane + 1], lane) : (kKnnPadKey | (uint32_t)lane);
     const uint32_t sk = pcr_wave_sort_posf32(key, lane);
     const uint32_t nx = (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)sk, 0x130, 0xF, 0xF, false);   // lane + 1
     const bool tie = lane < K && ((sk ^ nx) < 64u);
@@ -1368,8 +1342,8 @@ __device__ __forceinline__ void knn_emit_from_candidates(unsigned long long *can
 // f is non-decreasing and f(K-1) >= K, so a wave-uniform binary search finds the smallest such r <= K-1: per step one
 // v_readlane with a scalar lane, one compare, one s_bcnt1 (five steps at K = 48).  It starts at r = (K-1) / 2: without
 // truncation ties f(r) <= 2 (r + 1), and with them an r above the smallest is still valid by 3.  The r returned is either
-// K-1 (the plain bound) or one whose f was evaluated.  Returns s[r]; the caller applies the clamp rule (keys at 0x7F7FFFC0
-// and above: every point passes) -- below the clamp the lo of ranks 0 .. r and every hi <= theta_r are genuine finite
+// K-1 (the plain bound) or one whose f was evaluated.  Returns s[r]; the caller applies the clamp rule (knn_tau: keys at
+// kKnnPadKey and above, every point passes) -- below the clamp the lo of ranks 0 .. r and every hi <= theta_r are genuine finite
 // distances (+inf and NaN bits compare above every theta).
 // Rank K-1 of the 64 lane minima alone admits ~85 candidates at K = 48 (a second threshold pass for practically every
 // query, path 2b of knn_emit_from_candidates); this bound ~59, 2b for one query in ten (CPU simulation).
@@ -1398,10 +1372,7 @@ __device__ __forceinline__ uint32_t knn_two_group_rank(uint32_t sorted, uint32_t
 __device__ __forceinline__ uint32_t knn_bound_key(uint32_t ma, uint32_t mc, int K, int lane) {
   const int Ks = __builtin_amdgcn_readfirstlane(K);
   const uint32_t lo = ma < mc ? ma : mc, hi = ma < mc ? mc : ma;
-  // (a lane without a valid point holds +inf: clamped to the largest finite float so that the tagged key is not a NaN
-  // pattern for the float-bits network)
-  const uint32_t lc = lo < 0x7F7FFFFFu ? lo : 0x7F7FFFFFu;
-  const uint32_t sorted = pcr_wave_sort_posf32((lc & ~63u) | (uint32_t)lane, lane);
+  const uint32_t sorted = pcr_wave_sort_posf32(knn_tagged_key(lo, lane), lane);   // (a lane without a valid point holds +inf)
   if (Ks > kKnnTwoMinK) return knn_two_group_rank(sorted, hi, Ks);
   return (uint32_t)__builtin_amdgcn_readlane((int)sorted, Ks - 1);
 }
@@ -1467,12 +1438,7 @@ __global__ __launch_bounds__(kKnnPThreads) void knn_prefix_reg_kernel(const floa
     uint32_t mg[2] = {0xFFFFFFFFu, 0xFFFFFFFFu};   // the minima of the lane's registers t < T/2 and t >= T/2
 #pragma unroll
     for (int t = 0; t < TP; t++) {
-      const f32x2 dx = px[t] - x1, dy = py[t] - y1, dz = pz[t] - z1;   // pcr_sqdist3(q, p): p - q
-      const f32x2 a = dx * dx;
-      const f32x2 bb = dy * dy;
-      const f32x2 c = dz * dz;
-      const f32x2 sab = a + bb;
-      const f32x2 dd = sab + c;
+      const f32x2 dd = sqdist_terms(px[t] - x1, py[t] - y1, pz[t] - z1);   // pcr_sqdist3(q, p): p - q
       d[2 * t] = __float_as_uint(dd[0]);
       d[2 * t + 1] = __float_as_uint(dd[1]);
 #pragma unroll
@@ -1480,9 +1446,7 @@ __global__ __launch_bounds__(kKnnPThreads) void knn_prefix_reg_kernel(const floa
     }
     // 1. the (truncated, lane-tagged) key that bounds the K-th smallest distance: the 64 lane minima sorted across the
     // lanes (21-step network on float bits, pcr_common.h), then rank K-1 of them or the two-group bound (knn_bound_key)
-    const uint32_t ts = knn_bound_key(mg[0], mg[1], K, lane);
-    // (rank K-1 at the clamp = distances overflowed: let every point pass, the rounds below rank them)
-    const uint32_t tau = ts >= 0x7F7FFFC0u ? 0x7F800000u : (ts | 63u);
+    const uint32_t tau = knn_tau(knn_bound_key(mg[0], mg[1], K, lane));
     // 2. candidates d <= tau, compacted in (t, lane) order: the slot of a candidate is the number of candidates
     // before it -- the running total of the earlier t (scalar) + the passing lanes below it (mbcnt of the ballot)
     int total = 0;
@@ -1520,6 +1484,8 @@ __global__ __launch_bounds__(kKnnPThreads) void knn_prefix_reg_kernel(const floa
           const int i = (int)cand32[2 * c];
           const bool ok = i < n;                       // (a lane's padding points sit at infinity: distance +inf)
           const int ii = ok ? i : 0;
+          // (sqdist_terms's statements in place: through the helper this loop is unrolled four times and the kernel takes
+          // 122 VGPRs and 250 more instructions)
           const float dx = sx[ii] - qx, dy = sy[ii] - qy, dz = sz[ii] - qz;
           const float a = dx * dx;
           const float bb = dy * dy;
@@ -1533,8 +1499,7 @@ __global__ __launch_bounds__(kKnnPThreads) void knn_prefix_reg_kernel(const floa
     for (int t = 0; t < T; t++) {
       const bool pass = d[t] <= tau;
       const unsigned long long mask = __ballot(pass);
-      const int pos = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32),
-                                                     __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+      const int pos = (int)pcr_lanes_below(mask);
       uint32_t *wp = cand32 + 2 * total;   // (scalar)
       if (total <= kKnnCap && pass) {   // (scalar test: past kKnnCap the candidates are not used, only counted)
         wp[2 * pos] = (uint32_t)(lane + 64 * t);
@@ -1620,12 +1585,7 @@ __global__ __launch_bounds__(NT) void knn_prefix_lds_kernel(const float *__restr
     auto dist_pair = [&](int tp) {   // pcr_sqdist3(query, point) of the pair's two points (bits >= +0; +inf sorts last)
       const f32x4 pp = sP[tp * 64 + lane];
       const f32x2 pz = sZ[tp * 64 + lane];
-      const f32x2 dx = f32x2{pp[0], pp[1]} - x1, dy = f32x2{pp[2], pp[3]} - y1, dz = pz - z1;   // (p - q, as pcr_sqdist3)
-      const f32x2 a = dx * dx;
-      const f32x2 bb = dy * dy;
-      const f32x2 c = dz * dz;
-      const f32x2 sab = a + bb;
-      return sab + c;
+      return sqdist_terms(f32x2{pp[0], pp[1]} - x1, f32x2{pp[2], pp[3]} - y1, pz - z1);   // (p - q, as pcr_sqdist3)
     };
     auto dist_bits = [&](int t) {
       const f32x2 dd = dist_pair(t >> 1);
@@ -1648,8 +1608,7 @@ __global__ __launch_bounds__(NT) void knn_prefix_lds_kernel(const float *__restr
     __builtin_amdgcn_sched_barrier(0);
     // (the float-bits network of the register kernel: two VALU instructions per step instead of the integer network's four;
     // rank K-1 of the lane minima or the two-group bound, knn_bound_key)
-    const uint32_t ts = knn_bound_key(mg[0], mg[1], K, lane);
-    const uint32_t tau = ts >= 0x7F7FFFC0u ? 0x7F800000u : (ts | 63u);
+    const uint32_t tau = knn_tau(knn_bound_key(mg[0], mg[1], K, lane));
     // ---- pass 2 (round 5): the candidates d <= tau WITHOUT a ballot per register.  Every lane shifts one compare per
     // register into private words (v_cmp + v_addc_co: w = 2 w + carry; bit t % 32 of word t / 32 = "my point t passed"),
     // a wave scan of the lanes' counts gives every lane the first slot of its own candidates, and a short divergent
@@ -1699,12 +1658,8 @@ __global__ __launch_bounds__(NT) void knn_prefix_lds_kernel(const float *__restr
       for (int c = lane; c < total; c += 64) {
         const int i = (int)cand32[2 * c];
         const int t = i >> 6, unit = (t >> 1) * 64 + (i & 63), sl = t & 1;
-        const float dx = sPf[4 * unit + sl] - qx, dy = sPf[4 * unit + 2 + sl] - qy, dz = sZf[2 * unit + sl] - qz;
-        const float a = dx * dx;
-        const float bb = dy * dy;
-        const float cc = dz * dz;
-        const float sab = a + bb;
-        cand32[2 * c + 1] = __float_as_uint(sab + cc);
+        const float dd = sqdist_terms(sPf[4 * unit + sl] - qx, sPf[4 * unit + 2 + sl] - qy, sZf[2 * unit + sl] - qz);
+        cand32[2 * c + 1] = __float_as_uint(dd);
       }
     }
     __builtin_amdgcn_wave_barrier();
@@ -1844,11 +1799,10 @@ PCR_EXPORT int pcr_fps_ball_query_rows_f32(const float *xyz, float *temp, int *i
   const float max_r2 = max_r * max_r;
   f32x4 *r4 = reinterpret_cast<f32x4 *>(rows);
   hipStream_t st = pcr_s(stream);
-  const dim3 g(B), b(64);
-  if (N <= 128) return pcr_launch<fps_bq_wave_kernel<1>>(g, b, 0, st, xyz, temp, idx, new_xyz, cnt, r4, N, M, block, logb, max_r2, K);
-  if (N <= 256) return pcr_launch<fps_bq_wave_kernel<2>>(g, b, 0, st, xyz, temp, idx, new_xyz, cnt, r4, N, M, block, logb, max_r2, K);
-  if (N <= 512) return pcr_launch<fps_bq_wave_kernel<4>>(g, b, 0, st, xyz, temp, idx, new_xyz, cnt, r4, N, M, block, logb, max_r2, K);
-  return pcr_launch<fps_bq_wave_kernel<8>>(g, b, 0, st, xyz, temp, idx, new_xyz, cnt, r4, N, M, block, logb, max_r2, K);
+  return pcr_by_size_class(N, [&](auto pp) {
+    return pcr_launch<fps_bq_wave_kernel<decltype(pp)::value>>(dim3(B), dim3(64), 0, st, xyz, temp, idx, new_xyz, cnt, r4, N, M,
+                                                               block, logb, max_r2, K);
+  });
 }
 
 PCR_EXPORT int pcr_knn_f32(const float *xyz, const float *centres, int *idx, float *dist2, int B,
@@ -1935,9 +1889,11 @@ static int knn_prefix_launch(const float *xyz, int *idx, int B, int N, int S, in
   size_t lds = (size_t)(3 * N + (N & 1)) * sizeof(float);
   hipStream_t st = pcr_s(stream);
   const size_t lds_reg = lds + (size_t)4 * (kKnnCap + 64) * 8;
-  if (N <= 128) return pcr_launch<knn_prefix_reg_kernel<1>>(g, blk, lds_reg, st, xyz, idx, N, S, K, qpw, idx2, S2, K2);
-  if (N <= 256) return pcr_launch<knn_prefix_reg_kernel<2>>(g, blk, lds_reg, st, xyz, idx, N, S, K, qpw, idx2, S2, K2);
-  if (N <= 512) return pcr_launch<knn_prefix_reg_kernel<4>>(g, blk, lds_reg, st, xyz, idx, N, S, K, qpw, idx2, S2, K2);
+  // (the two-pass LDS form measures 1.79 ms against 1.60 at N <= 1024: registers win while they fit)
+  if (N <= 1024)
+    return pcr_by_size_class(N, [&](auto tp) {
+      return pcr_launch<knn_prefix_reg_kernel<decltype(tp)::value>>(g, blk, lds_reg, st, xyz, idx, N, S, K, qpw, idx2, S2, K2);
+    });
   {
     // sixteen waves share one copy of the cloud in LDS (4 waves per SIMD already at one workgroup per CU)
     constexpr int NT = 1024;
@@ -1947,8 +1903,6 @@ static int knn_prefix_launch(const float *xyz, int *idx, int B, int N, int S, in
     // (May look at B: the output is an index list, the same whatever the split.)
     const int qpw_l = (N > 2048 && (long)((S + 511) / 512) * B >= 1024) ? 512 : 128;
     const dim3 gl((S + qpw_l - 1) / qpw_l, B);
-    // (the two-pass LDS form measures 1.79 ms against 1.60 at N <= 1024: registers win while they fit)
-    if (N <= 1024) return pcr_launch<knn_prefix_reg_kernel<8>>(g, blk, lds_reg, st, xyz, idx, N, S, K, qpw, idx2, S2, K2);
     if (N <= 2048) {
       lds = (size_t)64 * 32 * 12 + (size_t)(NT / 64) * kKnnCap * 8;
       return pcr_launch_lds<knn_prefix_lds_kernel<32, NT>>(gl, dim3(NT), lds, st, xyz, idx, N, S, K, qpw_l, idx2, S2, K2);

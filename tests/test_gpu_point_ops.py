@@ -30,6 +30,53 @@ def test_fps_bit_exact(ops, n, m, kind):
     assert got.dtype == np.int32 and (got == want).all()
 
 
+def _tie_clouds(n, kind):
+    if kind == "lattice3":     # 27 sites: from pick 28 on every running minimum is 0 and the tie rule alone decides
+        return np.random.default_rng(n).integers(0, 3, (3, n, 3)).astype(np.float32)
+    return T.synthetic_clouds(3, n, seed=n, kind=kind).numpy()
+
+
+@pytest.mark.parametrize("n,m,kind,r,k", [(1024, 1024, "lattice3", 0.5, 64), (600, 600, "lattice3", 1.1, 32),
+                                          (1024, 512, "dup", 0.2, 32)])
+def test_fps_tie_rule_of_the_wave_kernels_against_the_oracle(ops, n, m, kind, r, k):
+    """The >= 8-pair wave kernels (513-1024 points; n = 600 with padding lanes) where the reference's tie rule decides
+    practically every pick -- pcr_fps_f32 and the fused pcr_fps_ball_query_rows_f32 each against the C ORACLE (the fused
+    kernel is otherwise only compared with the separate launches, which share its pick helpers): the pick order, and the
+    hit counts against the oracle's ball query of the oracle's centres."""
+    from mmdet3d.ops import point_ops as PO
+    xyz = _tie_clouds(n, kind)
+    want = P.fps(xyz, m)
+    got = ops.furthest_point_sample(dev(xyz), m).cpu().numpy()
+    assert (got == want).all()
+    assert PO.fps_ball_query_rows_ok(n, m, k)
+    idx, new_xyz, cnt, _ = PO.fps_ball_query_rows(dev(xyz), m, r, k)
+    assert (idx.cpu().numpy() == want).all()
+    centres = np.take_along_axis(xyz, want[:, :, None].astype(np.int64), 1)
+    assert (new_xyz.cpu().numpy() == centres).all()
+    rows = P.ball_query(0.0, r, k, xyz, centres)
+    # a row of the oracle: its hits in increasing index order, then copies of the first -> the count is where it stops rising
+    rising = np.concatenate([np.ones((3, m, 1), bool), rows[:, :, 1:] > rows[:, :, :-1]], 2)
+    want_cnt = np.where(rising.all(2), k, rising.argmin(2))
+    assert (cnt.cpu().numpy() == want_cnt).all()
+
+
+@pytest.mark.parametrize("n,s,k", [(1024, 64, 48), (2048, 64, 48), (4096, 64, 64)])
+def test_knn_prefix_overflow_fallbacks_bit_exact(n, s, k):
+    """More than kKnnCap = 256 candidates per query: the K-round fallbacks of the register kernel (n = 1024) and of the LDS
+    kernel, the one part of both that the shared ranking does not serve.  Every point sits on one of two sites, so each
+    query has hundreds of points AT its K-th distance (checked below) and the index decides."""
+    from pcr_amd import engine
+    from test_oracle_ops import two_site_clouds
+    xyz = two_site_clouds(n, k)
+    d = xyz[:, :s, None, :] - xyz[:, None, :, :]
+    d2 = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+    kth = np.partition(d2, k - 1, axis=2)[:, :, k - 1]
+    assert ((d2 <= kth[:, :, None]).sum(2) > 256).all()
+    want = P.knn_prefix(xyz, s, k)
+    got = engine.knn_prefix(dev(xyz), s, k).cpu().numpy()
+    assert (got == want).all()
+
+
 def test_fps_with_dist_bit_exact(ops):
     g = np.random.default_rng(3)
     for n, m in ((96, 32), (300, 77), (1500, 20)):

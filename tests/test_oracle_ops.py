@@ -77,6 +77,30 @@ def test_knn_prefix_is_sorted_by_distance_then_index():
             assert (idx[b, s] == want).all()
 
 
+def two_site_clouds(n, seed):
+    """3 clouds of n points that sit on only TWO sites each (more than 256 points per site for n >= 1024): every query has
+    hundreds of points at distance exactly 0, so its K nearest are decided by the index alone.  Cloud 1 has
+    non-representable coordinates, cloud 2 an uneven split (300 points on the first site)."""
+    g = np.random.default_rng([n, seed])
+    sites = np.array([[[0, 0, 0], [1, 2, 3]], [[0.37, -1.11, 0.74], [-0.37, 0.74, 1.85]], [[5, 5, 5], [5, 5, 6]]], np.float32)
+    xyz = np.empty((3, n, 3), np.float32)
+    for c in range(3):
+        on_second = g.permutation(n) >= (300 if c == 2 else n // 2)
+        xyz[c] = sites[c, on_second.astype(np.int64)]
+    return xyz
+
+
+def test_knn_prefix_ranks_equal_distances_by_index():
+    """what tests/test_gpu_point_ops.py's overflow cases rely on: among points at the same distance the oracle takes the
+    lowest indices, in increasing order"""
+    xyz = two_site_clouds(1024, 7)
+    idx = P.knn_prefix(xyz, 64, 48)
+    for c in range(3):
+        for q in range(64):
+            same = np.flatnonzero((xyz[c] == xyz[c, q]).all(1))
+            assert len(same) > 256 and (idx[c, q] == same[:48]).all()
+
+
 def test_gather_group_interp_roundtrip():
     g = np.random.default_rng(0)
     feat = g.standard_normal((2, 5, 33)).astype(np.float32)

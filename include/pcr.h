@@ -357,6 +357,93 @@ int pcr_nms_f32(const float *boxes, const float *scores, const float *thresh, in
 int pcr_track_nms_f32(const float *boxes5, const int *classes, const float *scores, const float *thresh,
                       int *suppressed, int N, pcr_stream_t stream);
 
+/* ------------------------------------------------------------ A5. track state --------- */
+
+/* The state the assignments of A3 and the masks of A4 refer to, kept on the device: a bank of C track slots that a frame
+ * updates in place by fixed-shape launches.  It stands for what the reference's tracker keeps on the host between frames
+ * (models/trackers/deprecated/): PointFeatureSet (tracking_feature_set.py:11-63: a store grown by torch.cat, replaced
+ * through a torch.where of data-dependent shape), TrackingUpdater.__call__ (tracking_updater.py:22-98: a walk over
+ * decisions[...].cpu().numpy() and lists of Track objects), Track.transform_over_time / EgoVehicle.transform_over_time
+ * (track.py:116-183, tracking_manager.py:111-149: numpy on the host) and VirtualTracker.get_track_det_distances
+ * (virtual_tracker.py:287-295: the detections go to the host and back).  No host read, no allocation, no atomic; the same
+ * bits on every run.  Pointers are checked against NULL only (as everywhere in this header, they are not probed for
+ * being device memory).
+ *
+ * The bank.  Slot s of C holds feats (feat_floats), xyz (xyz_floats), lengths, boxes (W floats: [x, y, z, w, l, h, rz] and,
+ * for W == 9, [vx, vy]), scores, labels, ids (the global track id), steps (the reference's len(det_bboxes)) and misses
+ * (its unmatchedFrameCount).  A slot is ACTIVE iff ids[s] >= 0; a free slot has ids = labels = -1 and lengths = 0, so the
+ * class gate of pcr_assoc_pairs_i32 leaves it out without further code; its other entries are stale.  next_id (1) is the
+ * id the next born track gets, info (1) the number of newborns the last plan dropped.
+ * pcr_bank_ok: 1 <= C <= PCR_ASSOC_MAX_OBJECTS, 0 <= D <= PCR_ASSOC_MAX_OBJECTS, W == 7 or 9,
+ * 0 <= feat_floats, xyz_floats <= PCR_BANK_MAX_ROW.
+ *
+ * pcr_bank_plan_i32 makes one frame's decisions and updates the small state IN PLACE (everything but feats / xyz).
+ * Inputs: track_to_det (C), det_to_track (D) as the assignment gives them (anything outside the range means none),
+ * det_labels / det_lengths (D) int32, det_boxes (D,W), det_scores (D); optional masks born (D), kill (C) int32; optional
+ * carry (12): a row-major 3 x 4 affine that takes the previous sweep's frame to the current one; frame_limit >= 1 and the
+ * flags replace_all, reset_on_match, propagate.  The det_* pointers, det_slot and det_id may be NULL when D == 0.
+ * Outputs: src (C): the detection whose features go into the slot, or -1 (pcr_bank_move_f32 reads it); det_slot / det_id
+ * (D): the slot and the global id of the track a detection joined (the reference's dets_to_trk_idx), -1 for none.
+ * The result is DEFINED by these rules over the state as it was BEFORE the launch (tests/track_ref.py::plan restates
+ * them; the kernel equals it bit for bit):
+ *   killed   slot s is active and kill != NULL and kill[s] != 0: ids = labels = -1, lengths = 0, whatever else holds;
+ *   matched  s is active, not killed, d = track_to_det[s] lies in [0, D), det_labels[d] >= 0 and det_to_track[d] == s
+ *            (the two maps must agree: nothing is trusted).  boxes[s], scores[s], labels[s] are the detection's,
+ *            steps += 1, misses = 0 if reset_on_match and unchanged otherwise (the reference's reset is commented out,
+ *            track.py:78-79).  If replace_all or lengths[s] <= det_lengths[d] (replace_old's rule): lengths[s] =
+ *            det_lengths[d] and src[s] = d; otherwise lengths stays and src[s] = -1.  det_slot[d] = s, det_id[d] = ids[s];
+ *   missed   s is active, neither killed nor matched: misses += 1; if misses >= frame_limit the slot is freed like a
+ *            killed one (tracking_updater.py:133-139).  Otherwise, if propagate (update_track_false_negative; without
+ *            it the track only waits, update_track_unmatched): the centre becomes
+ *              x' = x + vx / 2, y' = y + vy / 2 for W == 9 (x' = x, y' = y for W == 7), z' = z, and then, unless carry is
+ *              NULL, row i of the box centre = ((carry[4i] * x' + carry[4i+1] * y') + carry[4i+2] * z') + carry[4i+3],
+ *            each operation rounded to binary32, nothing contracted; size, yaw and velocity stay (track.py:168-181);
+ *            scores *= 0.01f and steps += 1 (add_false_negative_timestep, :97-113).  src[s] = -1;
+ *   born     detection d has det_labels[d] >= 0, is the detection of no matched slot, and born == NULL or born[d] != 0.
+ *            The k-th such detection in index order takes the k-th slot that was free BEFORE the launch, in slot order
+ *            (a slot freed by this launch is reused from the next one on): ids = next_id + k, steps = 1, misses = 0,
+ *            labels, boxes, scores, lengths from the detection, src = d; det_slot[d] / det_id[d] name them.  Newborns
+ *            beyond the free slots are dropped (det_slot = det_id = -1); info[0] = how many, and next_id advances by the
+ *            number really born.  A free slot that takes no newborn is left as it is, src = -1.
+ * One workgroup: every cross-thread read of the old state (ids, the maps) happens before the first barrier; the two
+ * ranks are ballots and popcounts per 64-entry word plus a prefix over the words in LDS, and a slot_of_rank / det_of_rank
+ * pair of LDS tables joins the k-th birth to the k-th free slot.  A slot is written by its owner thread only.
+ *
+ * pcr_bank_move_f32: for every slot s with src[s] in [0, D): feats[s] = det_feats[src[s]], xyz[s] = det_xyz[src[s]]; any
+ * other slot keeps its bits.  16-byte accesses where the row size is a multiple of 4 floats and both bases are 16-byte
+ * aligned (decided per array), 4-byte accesses otherwise.  Grid (row chunk, slot): the workgroups of an idle slot leave at
+ * once.  Nothing to do: D == 0 or feat_floats + xyz_floats == 0.
+ *
+ * pcr_bank_dist_f32: out (C,D), EVERY element written: 0 for a free slot, otherwise the BEV distance between the stored
+ * centre and the detection's centre taken back into the previous frame (get_track_det_distances, in the direct form;
+ * the reference's torch.cdist may take the matmul form, which is less exact):
+ *   px = ((m[0] * x + m[1] * y) + m[2] * z) + m[3], py with m[4..7], m = carry_inv (12), (px, py) = (x, y) for NULL;
+ *   dx = boxes[s][0] - px, dy = boxes[s][1] - py, out = sqrtf(dx * dx + dy * dy), IEEE (correctly rounded) square root.
+ * Nothing to do: D == 0.
+ *
+ * pcr_bank_retire_i32: every active slot with mask[s] != 0 is freed (ids = labels = -1, lengths = 0): the pruning of
+ * activeTracks by pcr_track_nms_f32's mask, run after the update as the reference does (tracking_updater.py:96). */
+#define PCR_BANK_MAX_ROW 1048576
+typedef struct pcr_bank {
+  int C, D, W;
+  int frame_limit, replace_all, reset_on_match, propagate;
+  int *lengths;   /* state (C ...), updated in place */
+  float *boxes, *scores;
+  int *labels, *ids, *steps, *misses, *next_id, *info;
+  const int *track_to_det, *det_to_track, *det_labels, *det_lengths;   /* the frame */
+  const float *det_boxes, *det_scores;
+  const int *born, *kill;
+  const float *carry;
+  int *src, *det_slot, *det_id;   /* the decisions */
+} pcr_bank;
+int pcr_bank_ok(int C, int D, int W, int feat_floats, int xyz_floats);
+int pcr_bank_plan_i32(const pcr_bank *p, pcr_stream_t stream);
+int pcr_bank_move_f32(const int *src, const float *det_feats, const float *det_xyz, float *feats, float *xyz, int C, int D,
+                      int feat_floats, int xyz_floats, pcr_stream_t stream);
+int pcr_bank_dist_f32(const float *boxes, const int *ids, const float *det_boxes, const float *carry_inv, float *out,
+                      int C, int D, int W, pcr_stream_t stream);
+int pcr_bank_retire_i32(const int *mask, int *labels, int *ids, int *lengths, int C, pcr_stream_t stream);
+
 /* ------------------------------------------------- B. fused model kernels ------------ */
 
 /* Neighbour search of the "Point-Transformer" set-abstraction layers: centres are the first S

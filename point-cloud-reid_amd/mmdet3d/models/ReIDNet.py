@@ -574,6 +574,67 @@ class ReIDNet(nn.Module):
                     det_to_track=torch.where(r < T, r, torch.full_like(r, -1)), pairs=pairs, count=count, logits=logits,
                     cost=cost, info=info)
 
+    def track_step(self, bank, sweep, boxes, labels, scores, carry=None, carry_inv=None, min_points=2, num_classes=8,
+                   cap=None, n=None, crop_args=None, born=None, kill=None, frame_limit=10, replace_all=False,
+                   reset_on_match=False, propagate=True, suppress_threshold=0.15, **cost_args):
+        """One whole tracker frame on the device without a host read (pcr_amd/tracks.py; INTEGRATION.md "2e. Track
+        state"; the split-bf16 guard calibrates on the first batch of a weight version, as in every inference entry
+        point: run a frame eagerly before capturing): the sweep (P, C >= 3) and this frame's boxes (M <= bank.max_dets, bank.box_width) with labels and
+        scores (M,) -> crops and features (forward_inference_boxes, written behind the bank's rows of the gallery), the
+        distance prior (bank.distances with carry_inv, current frame -> previous), compare_pairs, match_gallery over
+        the bank's gallery, association_cost(dist=...), linear_assignment, bank.update (births, deaths, feature
+        replacement, propagation by carry, previous frame -> current; born / kill are the learned decisions' masks) and
+        bank.suppress (suppress_threshold None = no track NMS).  The detections are padded to bank.max_dets with label
+        -1, which joins nothing.  crop_args go to crops_from_boxes, cost_args to association_cost (track_miss, det_new,
+        dist_max, dist_penalty, fill).  -> associate's dict (track_to_det (capacity,), det_to_track (max_dets,), pairs,
+        count, logits, cost, info) plus det_slot, det_id (max_dets,), bank_info (1,) = the newborns dropped for want of
+        a free slot, dist, lengths."""
+        from pcr_amd import associate as A
+        from pcr_amd import tracks as TR
+        if not isinstance(bank, TR.TrackBank):
+            raise L.PcrError("track_step: bank must be a pcr_amd.tracks.TrackBank")
+        L.require_cuda(sweep, boxes, labels, scores)
+        L.require_f32(boxes, scores)
+        C, D, W = bank.capacity, bank.max_dets, bank.box_width
+        if boxes.dim() != 2 or boxes.shape[1] != W or boxes.shape[0] > D:
+            raise L.PcrError("track_step: boxes must be (M <= %d, %d), got %s" % (D, W, tuple(boxes.shape)))
+        M = boxes.shape[0]
+        if labels.shape != (M,) or scores.shape != (M,):
+            raise L.PcrError("track_step: labels and scores must be (M,)")
+        if not L.load().pcr_lsa_ok(1, C + D, C + D):
+            raise L.PcrError("track_step: capacity + max_dets = %d is beyond linear_assignment (PCR_LSA_MAX)" % (C + D))
+        labels = labels.to(torch.int32)
+        if M < D:                                   # padding: a box of size zero holds no point, label -1 joins nothing
+            boxes = torch.cat([boxes, boxes.new_zeros((D - M, W))], dim=0)
+            labels = torch.cat([labels, labels.new_full((D - M,), -1)], dim=0)
+            scores = torch.cat([scores, scores.new_zeros((D - M,))], dim=0)
+            if born is not None and born.shape == (M,):
+                born = torch.cat([born, born.new_zeros((D - M,))], dim=0)
+        boxes, labels, scores = boxes.contiguous(), labels.contiguous(), scores.contiguous()
+        xyz, feats, lengths = self.forward_inference_boxes(sweep, boxes[:, :7].contiguous(), n=n, **(crop_args or {}))
+        if tuple(feats.shape[1:]) != bank.feat_shape or tuple(xyz.shape[1:]) != (bank.feat_shape[1], 3):
+            raise L.PcrError("track_step: the encoder returns features %s, the bank was made for %s"
+                             % (tuple(feats.shape[1:]), bank.feat_shape))
+        bank.det_feats.copy_(feats)
+        bank.det_xyz.copy_(xyz)
+        dist = bank.distances(boxes, carry_inv)
+        pairs, count = A.compare_pairs(bank.labels, labels, bank.lengths, lengths, min_points=min_points,
+                                       num_classes=num_classes, cap=cap)
+        gallery_pairs = torch.stack([pairs[:, 0], pairs[:, 1] + C], dim=1)       # detections follow the bank's rows
+        logits = self.match_gallery(bank.gallery, bank.gallery_xyz, gallery_pairs).contiguous()
+        cost = A.association_cost(logits, pairs, count, C, D, dist=dist, **cost_args)
+        col4row, row4col, info = A.linear_assignment(cost)
+        c, r = col4row[0, :C], row4col[0, :D]
+        t2d = torch.where(c < D, c, torch.full_like(c, -1))
+        d2t = torch.where(r < C, r, torch.full_like(r, -1))
+        det_slot, det_id, bank_info = bank.update(
+            (t2d, d2t), dict(labels=labels, lengths=lengths, boxes=boxes, scores=scores), born=born, kill=kill, carry=carry,
+            frame_limit=frame_limit, replace_all=replace_all, reset_on_match=reset_on_match, propagate=propagate)
+        if suppress_threshold is not None:
+            bank.suppress(suppress_threshold)
+        return dict(track_to_det=t2d, det_to_track=d2t, pairs=pairs, count=count, logits=logits, cost=cost, info=info,
+                    det_slot=det_slot, det_id=det_id, bank_info=bank_info, dist=dist, lengths=lengths)
+
     def get_match_supervision(self, h1, h2, xyz1, xyz2, id_1, id_2):
         return h1, h2, xyz1, xyz2, (id_1 == id_2).float()
 

@@ -23,6 +23,12 @@ def _block(name, decl):
     return type(name, (ctypes.Structure,), {"_fields_": fields})
 
 
+# ---- section A5 (pcr_bank) ----
+BankParams = _block("BankParams", """
+    int C D W frame_limit replace_all reset_on_match propagate;
+    ptr lengths boxes scores labels ids steps misses next_id info;
+    ptr track_to_det det_to_track det_labels det_lengths det_boxes det_scores born kill carry; ptr src det_slot det_id""")
+
 # ---- section B (pcr_sa_params, pcr_attn_params, pcr_head_params) ----
 SaParams = _block("SaParams", """
     int mode B N S K D c1 c2 c3; ptr xyz feat idx centre_idx; ptr[3] wp scale shift; ptr wa wpq; ptr[2] wps shift_pad;
@@ -60,7 +66,7 @@ _AttnHeadP = _block("_AttnHeadP", """
     int precision fwd_precision""")
 
 # the header's name of every block (what the layout test compiles against)
-BLOCKS = {"pcr_sa_params": SaParams, "pcr_attn_params": AttnParams, "pcr_head_params": HeadParams,
+BLOCKS = {"pcr_bank": BankParams, "pcr_sa_params": SaParams, "pcr_attn_params": AttnParams, "pcr_head_params": HeadParams,
           "pcr_tdense_fwd": _TFwd, "pcr_tdense_bwd": _TBwd, "pcr_bn_fwd_fin": _BnFwd, "pcr_bn_bwd_fin": _BnBwd,
           "pcr_reduce_job": _ReduceJob, "pcr_linattn": _LinAttnP, "pcr_attn_tail": _AttnTailP,
           "pcr_attn_head": _AttnHeadP}
@@ -154,6 +160,12 @@ SIGNATURES = {
     "pcr_nms_ws_bytes": "i i",
     "pcr_nms_f32": "s FFFIIIIPiiiS",
     "pcr_track_nms_f32": "s FIFFIiS",
+    # A5. track state
+    "pcr_bank_ok": "i iiiii",
+    "pcr_bank_plan_i32": "s <BankParams>S",
+    "pcr_bank_move_f32": "s IFFFFiiiiS",
+    "pcr_bank_dist_f32": "s FIFFFiiiS",
+    "pcr_bank_retire_i32": "s IIIIiS",
     # B. fused model kernels
     "pcr_knn_prefix_f32": "s FIiiiiS",
     "pcr_knn_prefix2_f32": "s FIIiiiiiiS",

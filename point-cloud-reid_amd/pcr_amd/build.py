@@ -21,6 +21,7 @@ FLAGS = {
     "crop_kernels.hip": ["-ffp-contract=off"],       # membership and box-frame coordinates are compared bit for bit
     "assoc_kernels.hip": ["-ffp-contract=off"],      # the assignment's candidate values and duals are compared bit for bit
     "nms_kernels.hip": ["-ffp-contract=off"],        # IoUs are compared with a threshold; the axis-aligned ones bit for bit
+    "track_kernels.hip": ["-ffp-contract=off"],      # the propagated boxes and the distances are compared bit for bit
 }
 
 

@@ -1,0 +1,266 @@
+"""Track state on the device (include/pcr.h section A5, csrc/track_kernels.hip).
+
+`ReIDNet.associate` ends with `track_to_det` / `det_to_track`; the reference's tracker then goes to the host to decide
+what is stored where: `PointFeatureSet` grows by `torch.cat` and replaces through a `torch.where` of data-dependent shape
+(trackers/deprecated/tracking_feature_set.py:11-63), `TrackingUpdater.__call__` walks `decisions[...].cpu().numpy()`
+and lists of `Track` objects (tracking_updater.py:22-98), missed tracks are propagated in numpy (track.py:116-183) and
+the distance prior copies the detections to the host and back (virtual_tracker.py:287-295).  `TrackBank` is that state
+with a fixed capacity: every step is a fixed-shape launch without a host read and with the same bits on every run, so a
+whole tracker frame can be captured in a HIP graph.  INTEGRATION.md ("2e. Track state") has the mapping;
+`ReIDNet.track_step` chains a frame.
+"""
+import ctypes
+
+import torch
+
+from . import _lib as L
+from . import abi
+from . import nms as NMS
+
+
+def _require(ok, what):
+    if not ok:
+        raise L.PcrError("pcr_amd.tracks: " + what)
+
+
+def bank_ok(C, D, W=9, feat_floats=0, xyz_floats=0):
+    """whether the section-A5 entry points take a bank of C slots, D detections, box width W and these row sizes"""
+    return bool(L.load().pcr_bank_ok(int(C), int(D), int(W), int(feat_floats), int(xyz_floats)))
+
+
+def _vec(t, dtype, n, name):
+    """a contiguous (n,) device tensor of dtype (int64 labels / lengths are converted on the device), or None"""
+    if t is None:
+        return None
+    _require(isinstance(t, torch.Tensor), "%s must be a tensor" % name)
+    L.require_cuda(t)
+    if dtype is torch.int32:
+        if t.dtype == torch.int64:
+            t = t.to(torch.int32)
+        L.require_i32(t)
+    else:
+        L.require_f32(t)
+    _require(t.shape == (n,), "%s must be (%d,), got %s" % (name, n, tuple(t.shape)))
+    return t.contiguous()
+
+
+def _affine(t, name):
+    """a row-major 3 x 4 affine as the kernels read it: (12,) or (3, 4) float32 on the device, or None (identity)"""
+    if t is None:
+        return None
+    _require(isinstance(t, torch.Tensor), "%s must be a tensor" % name)
+    L.require_cuda(t)
+    L.require_f32(t)
+    _require(t.numel() == 12 and t.is_contiguous(), "%s must be a contiguous (12,) or (3, 4) tensor" % name)
+    return t
+
+
+def plan(state, track_to_det, det_to_track, det_labels, det_lengths, det_boxes, det_scores, src, det_slot, det_id,
+         born=None, kill=None, carry=None, frame_limit=10, replace_all=False, reset_on_match=False, propagate=True):
+    """pcr_bank_plan_i32 on explicit tensors.  state = dict(lengths, boxes, scores, labels, ids, steps, misses, next_id,
+    info), updated in place; src (C,), det_slot (D,), det_id (D,) are written."""
+    names_i = ("lengths", "labels", "ids", "steps", "misses", "next_id", "info")
+    tensors = [state[k] for k in names_i] + [state["boxes"], state["scores"], track_to_det, det_to_track, det_labels,
+                                             det_lengths, det_boxes, det_scores, src, det_slot, det_id, born, kill, carry]
+    for t in tensors:
+        _require(t is None or isinstance(t, torch.Tensor), "every argument must be a tensor")
+    L.require_cuda(*tensors)
+    L.require_i32(*[state[k] for k in names_i], track_to_det, det_to_track, det_labels, det_lengths, src, det_slot, det_id,
+                  born, kill)
+    L.require_f32(state["boxes"], state["scores"], det_boxes, det_scores, carry)
+    boxes = state["boxes"]
+    _require(boxes.dim() == 2, "boxes must be (C, W)")
+    C, W = boxes.shape
+    D = det_boxes.shape[0]
+    _require(bank_ok(C, D, W), "C=%d D=%d W=%d is out of range (pcr_bank_ok)" % (C, D, W))
+    _require(int(frame_limit) >= 1, "frame_limit must be at least 1")
+    for k in ("lengths", "labels", "ids", "steps", "misses", "scores"):
+        _require(state[k].shape == (C,) and state[k].is_contiguous(), "state[%r] must be a contiguous (C,) tensor" % k)
+    _require(state["next_id"].numel() == 1 and state["info"].numel() == 1, "next_id and info hold one int each")
+    _require(boxes.is_contiguous() and det_boxes.shape == (D, W) and det_boxes.is_contiguous(),
+             "boxes (C, W) and det_boxes (D, W) must be contiguous and of one width")
+    for t, n, name in ((track_to_det, C, "track_to_det"), (kill, C, "kill"), (src, C, "src"), (det_to_track, D, "det_to_track"),
+                       (det_labels, D, "det_labels"), (det_lengths, D, "det_lengths"), (det_scores, D, "det_scores"),
+                       (born, D, "born"), (det_slot, D, "det_slot"), (det_id, D, "det_id")):
+        _require(t is None or (t.shape == (n,) and t.is_contiguous()), "%s must be a contiguous (%d,) tensor" % (name, n))
+    carry = _affine(carry, "carry")
+    p = abi.BankParams()
+    p.C, p.D, p.W = C, D, W
+    p.frame_limit, p.replace_all, p.reset_on_match, p.propagate = int(frame_limit), int(bool(replace_all)), \
+        int(bool(reset_on_match)), int(bool(propagate))
+    for k in names_i + ("boxes", "scores"):
+        setattr(p, k, L._p(state[k]))
+    for k, t in (("track_to_det", track_to_det), ("det_to_track", det_to_track), ("det_labels", det_labels),
+                 ("det_lengths", det_lengths), ("det_boxes", det_boxes), ("det_scores", det_scores), ("born", born),
+                 ("kill", kill), ("carry", carry), ("src", src), ("det_slot", det_slot), ("det_id", det_id)):
+        setattr(p, k, L._p(t))
+    L.run.pcr_bank_plan_i32(ctypes.byref(p), L.stream_ptr())
+    return src, det_slot, det_id
+
+
+def move(src, det_feats, det_xyz, feats, xyz):
+    """pcr_bank_move_f32: feats[s] = det_feats[src[s]] and xyz[s] = det_xyz[src[s]] for every slot with src[s] in [0, D);
+    feats (C, ...), det_feats (D, ...) of one row shape, likewise xyz; rows must be dense (a view may start anywhere)"""
+    for t in (src, det_feats, det_xyz, feats, xyz):
+        _require(isinstance(t, torch.Tensor), "every argument must be a tensor")
+    L.require_cuda(src, det_feats, det_xyz, feats, xyz)
+    L.require_i32(src)
+    L.require_f32(det_feats, det_xyz, feats, xyz)
+    C, D = feats.shape[0], det_feats.shape[0]
+    _require(src.shape == (C,) and src.is_contiguous(), "src must be a contiguous (C,) tensor")
+    _require(xyz.shape[0] == C and det_xyz.shape[0] == D, "feats / xyz must agree on C, det_feats / det_xyz on D")
+    _require(feats.shape[1:] == det_feats.shape[1:] and xyz.shape[1:] == det_xyz.shape[1:],
+             "the bank's rows and the detections' rows must have one shape")
+    for t in (det_feats, det_xyz, feats, xyz):
+        _require(t.is_contiguous(), "a tensor is not contiguous")
+    ff = feats[0].numel() if C else 0
+    xf = xyz[0].numel() if C else 0
+    _require(bank_ok(C, D, 7, ff, xf), "C=%d D=%d rows of %d and %d floats are out of range (pcr_bank_ok)" % (C, D, ff, xf))
+    L.run.pcr_bank_move_f32(src, det_feats, det_xyz, feats, xyz, C, D, ff, xf, L.stream_ptr())
+
+
+def distances(boxes, ids, det_boxes, carry_inv=None, out=None):
+    """pcr_bank_dist_f32: boxes (C, W), ids (C,), det_boxes (D, W) -> (C, D) float32, every element written: the BEV
+    distance between a stored centre and a detection's centre taken back into the previous frame by carry_inv (3 x 4,
+    None = identity); 0 in a free slot's row.  It is the `dist=` operand of associate.association_cost."""
+    for t in (boxes, ids, det_boxes):
+        _require(isinstance(t, torch.Tensor), "every argument must be a tensor")
+    L.require_cuda(boxes, ids, det_boxes, carry_inv, out)
+    L.require_f32(boxes, det_boxes, carry_inv, out)
+    L.require_i32(ids)
+    _require(boxes.dim() == 2 and det_boxes.dim() == 2 and boxes.shape[1] == det_boxes.shape[1],
+             "boxes (C, W) and det_boxes (D, W) must be of one width")
+    C, W = boxes.shape
+    D = det_boxes.shape[0]
+    _require(bank_ok(C, D, W), "C=%d D=%d W=%d is out of range (pcr_bank_ok)" % (C, D, W))
+    _require(boxes.is_contiguous() and det_boxes.is_contiguous() and ids.shape == (C,) and ids.is_contiguous(),
+             "a tensor has the wrong shape or is not contiguous")
+    carry_inv = _affine(carry_inv, "carry_inv")
+    if out is None:
+        out = torch.empty((C, D), dtype=torch.float32, device=boxes.device)
+    _require(out.shape == (C, D) and out.is_contiguous(), "out must be a contiguous (C, D) tensor")
+    L.run.pcr_bank_dist_f32(boxes, ids, det_boxes, carry_inv, out, C, D, W, L.stream_ptr())
+    return out
+
+
+def retire(mask, labels, ids, lengths):
+    """pcr_bank_retire_i32: the active slots with mask != 0 are freed"""
+    for t in (mask, labels, ids, lengths):
+        _require(isinstance(t, torch.Tensor), "every argument must be a tensor")
+    L.require_cuda(mask, labels, ids, lengths)
+    L.require_i32(mask, labels, ids, lengths)
+    C = ids.shape[0]
+    _require(bank_ok(C, 0), "C=%d is out of range (pcr_bank_ok)" % C)
+    for t in (mask, labels, ids, lengths):
+        _require(t.shape == (C,) and t.is_contiguous(), "mask, labels, ids and lengths must be contiguous (C,) tensors")
+    L.run.pcr_bank_retire_i32(mask, labels, ids, lengths, C, L.stream_ptr())
+
+
+class TrackBank:
+    """`capacity` track slots and the room for `max_dets` detections of a frame, all on `device`.
+
+    The features live in ONE gallery buffer (capacity + max_dets, *feat_shape): `feats` is `gallery[:capacity]` and a
+    frame's detections are written to `det_feats` = `gallery[capacity:]` (likewise `gallery_xyz`, rows (feat_shape[1],
+    3)), so that ReIDNet.match_gallery needs no per-frame torch.cat of the bank.  A slot is active iff ids >= 0; a free
+    slot has label -1, which compare_pairs' class gate leaves out.  Differences from the reference's store (deliberate):
+    the capacity is fixed and freed slots are reused, while PointFeatureSet grows for the whole scene; ids are numbered
+    over the born tracks in detection order.
+
+    Every method launches on the current stream, returns fixed-shape tensors and never reads the device.  The tensors
+    `update` returns are the bank's own and are overwritten by the next update."""
+
+    STATE = ("lengths", "boxes", "scores", "labels", "ids", "steps", "misses", "next_id", "info")
+
+    def __init__(self, capacity, max_dets, feat_shape=(64, 128), box_width=9, device=None):
+        C, D = int(capacity), int(max_dets)
+        _require(len(feat_shape) == 2 and min(feat_shape) >= 1, "feat_shape must be (channels, points)")
+        ch, n = int(feat_shape[0]), int(feat_shape[1])
+        device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if device.type != "cuda":
+            raise L.PcrError("pcr_amd.tracks: the bank lives on an MI355X device (got %s); there is no CPU fallback" % device)
+        _require(bank_ok(C, D, box_width, ch * n, n * 3),
+                 "capacity=%d max_dets=%d box_width=%d feat_shape=%s is out of range (pcr_bank_ok)"
+                 % (C, D, box_width, tuple(feat_shape)))
+        self.capacity, self.max_dets, self.box_width, self.feat_shape, self.device = C, D, int(box_width), (ch, n), device
+        f32 = dict(dtype=torch.float32, device=device)
+        i32 = dict(dtype=torch.int32, device=device)
+        self.gallery = torch.zeros((C + D, ch, n), **f32)
+        self.gallery_xyz = torch.zeros((C + D, n, 3), **f32)
+        self.feats, self.det_feats = self.gallery[:C], self.gallery[C:]
+        self.xyz, self.det_xyz = self.gallery_xyz[:C], self.gallery_xyz[C:]
+        self.lengths, self.labels, self.ids = torch.zeros(C, **i32), torch.zeros(C, **i32), torch.zeros(C, **i32)
+        self.steps, self.misses = torch.zeros(C, **i32), torch.zeros(C, **i32)
+        self.boxes, self.scores = torch.zeros((C, self.box_width), **f32), torch.zeros(C, **f32)
+        self.next_id, self.info = torch.zeros(1, **i32), torch.zeros(1, **i32)
+        self.src, self.det_slot, self.det_id = torch.zeros(C, **i32), torch.zeros(D, **i32), torch.zeros(D, **i32)
+        self._dist = torch.zeros((C, D), **f32)
+        self._track_scores, self._suppressed = torch.zeros(C, **f32), torch.zeros(C, **i32)
+        self.reset()
+
+    def state(self):
+        return {k: getattr(self, k) for k in self.STATE}
+
+    def reset(self):
+        """every slot free, ids from 0 again"""
+        for t in (self.gallery, self.gallery_xyz, self.lengths, self.steps, self.misses, self.boxes, self.scores,
+                  self.next_id, self.info):
+            t.zero_()
+        for t in (self.labels, self.ids, self.src, self.det_slot, self.det_id):
+            t.fill_(-1)
+
+    def distances(self, det_boxes, carry_inv=None):
+        """det_boxes (D <= max_dets, box_width) -> (capacity, D): see `distances`; the bank's own buffer when D == max_dets"""
+        _require(isinstance(det_boxes, torch.Tensor) and det_boxes.dim() == 2, "det_boxes must be a (D, W) tensor")
+        D = det_boxes.shape[0]
+        _require(D <= self.max_dets, "%d detections, the bank was made for %d" % (D, self.max_dets))
+        return distances(self.boxes, self.ids, det_boxes, carry_inv, out=self._dist if D == self.max_dets else None)
+
+    def update(self, assignment, dets, born=None, kill=None, carry=None, frame_limit=10, replace_all=False,
+               reset_on_match=False, propagate=True):
+        """One frame: pcr_bank_plan_i32, then pcr_bank_move_f32.
+
+        assignment  a dict with track_to_det (capacity,) and det_to_track (D,) as ReIDNet.associate returns them, or
+                    that pair
+        dets        a dict: labels, lengths (D,) int, boxes (D, box_width), scores (D,), and feats (D, *feat_shape) /
+                    xyz (D, points, 3); without feats / xyz the first D rows of det_feats / det_xyz are the frame's
+        born, kill  (D,) / (capacity,) int32 masks: the learned newborn and false-positive decisions; None = every
+                    unmatched valid detection is born, no track is killed
+        carry       (12,) or (3, 4) float32: previous sweep's frame -> the current one (None = identity)
+        -> det_slot (D,), det_id (D,), info (1,)"""
+        if isinstance(assignment, dict):
+            t2d, d2t = assignment["track_to_det"], assignment["det_to_track"]
+        else:
+            t2d, d2t = assignment
+        C = self.capacity
+        boxes = dets["boxes"]
+        _require(isinstance(boxes, torch.Tensor) and boxes.dim() == 2, "dets['boxes'] must be a (D, W) tensor")
+        L.require_cuda(boxes)
+        D = boxes.shape[0]
+        _require(D <= self.max_dets, "%d detections, the bank was made for %d" % (D, self.max_dets))
+        _require(boxes.shape[1] == self.box_width, "dets['boxes'] must be (D, %d)" % self.box_width)
+        labels, lengths = _vec(dets["labels"], torch.int32, D, "dets['labels']"), _vec(dets["lengths"], torch.int32, D, "dets['lengths']")
+        scores = _vec(dets["scores"], torch.float32, D, "dets['scores']")
+        t2d, d2t = _vec(t2d, torch.int32, C, "track_to_det"), _vec(d2t, torch.int32, D, "det_to_track")
+        born, kill = _vec(born, torch.int32, D, "born"), _vec(kill, torch.int32, C, "kill")
+        feats, xyz = dets.get("feats"), dets.get("xyz")
+        _require((feats is None) == (xyz is None), "dets['feats'] and dets['xyz'] come together")
+        if feats is None:
+            feats, xyz = self.det_feats[:D], self.det_xyz[:D]
+        det_slot, det_id = self.det_slot[:D], self.det_id[:D]
+        plan(self.state(), t2d, d2t, labels, lengths, boxes.contiguous(), scores, self.src, det_slot, det_id, born=born,
+             kill=kill, carry=carry, frame_limit=frame_limit, replace_all=replace_all, reset_on_match=reset_on_match,
+             propagate=propagate)
+        move(self.src, feats, xyz, self.feats, self.xyz)
+        return det_slot, det_id, self.info
+
+    def track_scores(self):
+        """(capacity,) float32: steps + scores, the reference's `len(det_bboxes) + scores[-1]` (stale in a free slot)"""
+        return torch.add(self.steps, self.scores, out=self._track_scores)
+
+    def suppress(self, thresh):
+        """The reference's track NMS after the update (tracking_updater.py:96): nms.suppress_tracks over the bank, then
+        the suppressed active slots are freed.  A free slot has class -1 and so cannot suppress an active one.
+        thresh: a Python float or a (1,) float32 device tensor.  -> suppressed (capacity,) int32"""
+        NMS.suppress_tracks(self.boxes[:, :7], self.labels, self.track_scores(), thresh, out=self._suppressed)
+        retire(self._suppressed, self.labels, self.ids, self.lengths)
+        return self._suppressed

@@ -444,6 +444,82 @@ int pcr_bank_dist_f32(const float *boxes, const int *ids, const float *det_boxes
                       int C, int D, int W, pcr_stream_t stream);
 int pcr_bank_retire_i32(const int *mask, int *labels, int *ids, int *lengths, int C, pcr_stream_t stream);
 
+/* ------------------------------------------------------------ A6. crop store ---------- */
+
+/* The loader side of training and evaluation with the crop set resident on the device: what the reference does per item
+ * on the host -- one file read per cloud, subsamplePC (datasets/utils.py:606-621) and the training pair rule
+ * (ReIDDatasetNuscenesFP.__getitem__, datasets/reidentification_nuscenes.py:37-72, with get_random_other_even_train,
+ * get_class_list_density and get_random_frame_even, reidentification_base.py:316-357, object_loader_base.py:201-238) on
+ * numpy's global generator -- as two launches over tables that are uploaded once (pcr_amd/store.py builds them).  No host
+ * read, no allocation, no synchronisation; the same bits on every run.  tests/store_ref.py restates both.
+ *
+ * The word.  Every sample is a 32-bit word of a counter-based generator keyed by (seed, stream, key, k), with the mix of
+ * section A2:
+ *       mix(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16      (uint32)
+ *       h = mix((uint32)seed ^ 0x9e3779b9); h = mix(h ^ (uint32)(seed >> 32)); h = mix(h ^ stream); h = mix(h ^ key);
+ *       W(seed, stream, key, k) = mix(h ^ k)
+ *       pick(u, len) = ((uint64)u * len) >> 32
+ *   stream 1 is the pair rule, stream 2 the gather.  seed is a DEVICE pointer to one int64 (NULL = 0), read at run time:
+ *   a captured launch draws fresh samples once that word changes.  The stream of samples is not numpy's; the
+ *   distribution is.
+ *
+ * info (1) is a word of sticky flags that both launches OR into and never clear (the caller zeroes it when it wants to):
+ *   PCR_STORE_INFO_RETRY  an item's PCR_STORE_PAIR_ATTEMPTS candidate picks all hit its own object (see below);
+ *   PCR_STORE_INFO_ITEM   an item the tables cannot serve (index out of range, fewer than two observations, a class or
+ *                         pool without a bucket of two objects): its rows, labels and ids are -1;
+ *   PCR_STORE_INFO_ROW    a row >= R, or a row whose offsets do not lie in order inside [offsets[0], offsets[R]].
+ *
+ * pcr_store_gather_f32: subsamplePC of B stored crops.  points (total,3) f32; offsets (R+1) int64 ascending: crop r is
+ * points[offsets[r] .. offsets[r+1]); rows (B) int32; keys (B) int32 or NULL (key = b); rand (B*n) int32 read as bits, or
+ * NULL -> clouds (B,n,3), sizes (B) = the stored length of the row.  With len = sizes[b]:
+ *   len <= 2 -> zeros; len == n -> the stored points in order; otherwise slot s takes point pick(u, len) of the crop,
+ *   u = rand[b*n + s], or W(seed, 2, keys[b], s).
+ *   rows[b] < 0 is padding: zeros, size 0.  A row >= R gives zeros and size 0 too and sets PCR_STORE_INFO_ROW: no address
+ *   outside points[offsets[0] .. offsets[R]) is ever read.
+ * One wave per cloud, lanes over the cloud's 3n floats: every store of a wave is 64 consecutive words.  The two clouds of
+ * a batch of pairs go through ONE launch: rows (2B) = (pair, side), key 2 * key + side.  1 <= n <= PCR_STORE_MAX_SAMPLES.
+ *
+ * pcr_store_train_pairs_i32: TrainPairs.__getitem__ for B items, one thread each.  items (B): object indices; keys (B);
+ * rand (B * PCR_STORE_PAIR_WORDS) int32 or NULL: word k of item b, in the place of W(seed, 1, keys[b], k) (for tests)
+ * -> rows (B,2), labels (B,2), ids (B,2).  The tables (int32, on the device), every order the one the host rule indexes:
+ *   obj_cls, obj_fp, obj_id (num_objects);
+ *   nums_off (num_objects + 1), nums_rows: the rows of an object's usable observations, ascending observation number;
+ *   bucket_off (num_objects * PCR_STORE_BUCKETS + 1), bucket_rows: CSR over (object, point-count bucket [2^b, 2^(b+1)))
+ *     of the same rows, bucket by bucket;
+ *   pool_off (2 * num_classes * PCR_STORE_BUCKETS + 1), pool_objs: CSR over (pool: 0 true objects, 1 false positives;
+ *     class; bucket) of the indices of the objects with an observation in the bucket, in table order.
+ * With c the item's class, n its number of usable observations, and the item's draws W0, W1, ... counted from 0:
+ *   W0 >> 31 == 1: a POSITIVE.  ia = pick(W1, n), j = pick(W2, n - 1), ib = j + (j >= ia); rows = nums[ia], nums[ib];
+ *     labels (c, c); both ids the object's.
+ *   otherwise a NEGATIVE.  rows[0] = nums[pick(W1, n)].  Density: r = pick(W2, n), d = the bucket that holds the r-th
+ *     entry of the object's bucket_rows (a draw from the object's own bucket distribution).  use_tp = W3 >> 31 == 1.
+ *     Candidates: from d down to 0, then from 0 up, the first bucket d' of (pool, c) with at least two objects.
+ *     Partner: pool_objs entry pick(W(4 + t), len) for attempts t = 0 .. PCR_STORE_PAIR_ATTEMPTS - 1 until it is not the
+ *     item's own object; after that many failures the first entry that is not, and PCR_STORE_INFO_RETRY.  Observation:
+ *     from d' down to 0, then from 0 up, the partner's first non-empty bucket; rows[1] = its entry pick(W, len), W the
+ *     item's next draw.  labels (c, c) from the true pool, (c, c + num_classes) from the false positives;
+ *     ids[1] = -1 for a false positive. */
+#define PCR_STORE_BUCKETS 20
+#define PCR_STORE_PAIR_ATTEMPTS 32
+#define PCR_STORE_PAIR_WORDS 40
+#define PCR_STORE_MAX_SAMPLES 65536
+#define PCR_STORE_INFO_RETRY 1
+#define PCR_STORE_INFO_ITEM 2
+#define PCR_STORE_INFO_ROW 4
+typedef struct pcr_store_tables {
+  int num_objects, num_classes;
+  const int *obj_cls, *obj_fp, *obj_id;
+  const int *nums_off, *nums_rows;
+  const int *bucket_off, *bucket_rows;
+  const int *pool_off, *pool_objs;
+} pcr_store_tables;
+int pcr_store_gather_f32(const float *points, const long long *offsets, int R, const int *rows, const int *keys,
+                         const int *rand, const long long *seed, float *clouds, int *sizes, int *info, int B, int n,
+                         pcr_stream_t stream);
+int pcr_store_train_pairs_i32(const pcr_store_tables *tables, const int *items, const int *keys, const int *rand,
+                              const long long *seed, int *rows, int *labels, int *ids, int *info, int B,
+                              pcr_stream_t stream);
+
 /* ------------------------------------------------- B. fused model kernels ------------ */
 
 /* Neighbour search of the "Point-Transformer" set-abstraction layers: centres are the first S

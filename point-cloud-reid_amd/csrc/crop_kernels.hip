@@ -59,21 +59,12 @@ __device__ __forceinline__ bool in_box(const CropBox &b, float x, float y, float
   return ((double)lx > b.nhl) & ((double)lx < b.hl) & ((double)ly > b.nhw) & ((double)ly < b.hw);
 }
 
-__device__ __forceinline__ uint32_t crop_mix(uint32_t x) {
-  x ^= x >> 16;
-  x *= 0x7feb352du;
-  x ^= x >> 15;
-  x *= 0x846ca68bu;
-  x ^= x >> 16;
-  return x;
-}
-
 // the counter-based generator of pcr.h: the word of slot s of box m under seed
 __device__ __forceinline__ uint32_t crop_word(unsigned long long seed, uint32_t m, uint32_t s) {
-  uint32_t h = crop_mix((uint32_t)seed ^ 0x9e3779b9u);
-  h = crop_mix(h ^ (uint32_t)(seed >> 32));
-  h = crop_mix(h ^ m);
-  return crop_mix(h ^ s);
+  uint32_t h = pcr_mix32((uint32_t)seed ^ 0x9e3779b9u);
+  h = pcr_mix32(h ^ (uint32_t)(seed >> 32));
+  h = pcr_mix32(h ^ m);
+  return pcr_mix32(h ^ s);
 }
 
 __global__ void box_frames_kernel(const float *__restrict__ boxes, float *__restrict__ frames, int T) {

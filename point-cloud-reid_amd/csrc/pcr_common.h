@@ -81,6 +81,17 @@ __device__ __forceinline__ uint32_t pcr_orderable(float v) {
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
+// The 32-bit finaliser of the counter-based generators of pcr.h (sections A2 and A6): one definition, so that the crop
+// kernel's words and the crop store's are the same function by construction.
+__device__ __forceinline__ uint32_t pcr_mix32(uint32_t x) {
+  x ^= x >> 16;
+  x *= 0x7feb352du;
+  x ^= x >> 15;
+  x *= 0x846ca68bu;
+  x ^= x >> 16;
+  return x;
+}
+
 // the number of lanes below the calling one whose bit is set in a ballot: a passing lane's slot in an ordered compaction
 __device__ __forceinline__ uint32_t pcr_lanes_below(unsigned long long mask) {
   return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));

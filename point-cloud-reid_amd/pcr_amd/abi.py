@@ -29,6 +29,10 @@ BankParams = _block("BankParams", """
     ptr lengths boxes scores labels ids steps misses next_id info;
     ptr track_to_det det_to_track det_labels det_lengths det_boxes det_scores born kill carry; ptr src det_slot det_id""")
 
+# ---- section A6 (pcr_store_tables) ----
+StoreTables = _block("StoreTables", """
+    int num_objects num_classes; ptr obj_cls obj_fp obj_id nums_off nums_rows bucket_off bucket_rows pool_off pool_objs""")
+
 # ---- section B (pcr_sa_params, pcr_attn_params, pcr_head_params) ----
 SaParams = _block("SaParams", """
     int mode B N S K D c1 c2 c3; ptr xyz feat idx centre_idx; ptr[3] wp scale shift; ptr wa wpq; ptr[2] wps shift_pad;
@@ -66,7 +70,7 @@ _AttnHeadP = _block("_AttnHeadP", """
     int precision fwd_precision""")
 
 # the header's name of every block (what the layout test compiles against)
-BLOCKS = {"pcr_bank": BankParams, "pcr_sa_params": SaParams, "pcr_attn_params": AttnParams, "pcr_head_params": HeadParams,
+BLOCKS = {"pcr_bank": BankParams, "pcr_store_tables": StoreTables, "pcr_sa_params": SaParams, "pcr_attn_params": AttnParams, "pcr_head_params": HeadParams,
           "pcr_tdense_fwd": _TFwd, "pcr_tdense_bwd": _TBwd, "pcr_bn_fwd_fin": _BnFwd, "pcr_bn_bwd_fin": _BnBwd,
           "pcr_reduce_job": _ReduceJob, "pcr_linattn": _LinAttnP, "pcr_attn_tail": _AttnTailP,
           "pcr_attn_head": _AttnHeadP}
@@ -166,6 +170,9 @@ SIGNATURES = {
     "pcr_bank_move_f32": "s IFFFFiiiiS",
     "pcr_bank_dist_f32": "s FIFFFiiiS",
     "pcr_bank_retire_i32": "s IIIIiS",
+    # A6. crop store
+    "pcr_store_gather_f32": "s FPiIIIPFIIiiS",
+    "pcr_store_train_pairs_i32": "s <StoreTables>IIIPIIIIiS",
     # B. fused model kernels
     "pcr_knn_prefix_f32": "s FIiiiiS",
     "pcr_knn_prefix2_f32": "s FIIiiiiiiS",

@@ -128,11 +128,15 @@ def build_val_set(val_cfg, crop_root, meta=None, max_combinations=None, seed=Non
 
 
 def evaluate_model(model, dataset, batch_size, seed=0, device="cuda", rank=None, world=None, cls_to_idx=None,
-                   num_classes=None, on_batch=None):
+                   num_classes=None, on_batch=None, store=None):
     """multi_gpu_test + dataset.evaluate for one model over one ValPairs: this rank's contiguous shard of the pairs in
     batches of `batch_size` through forward_test, logits gathered in pair order on every rank, metrics from the gathered
     set.  -> dict(val_match_acc, f1 / precision / recall, per-class and per-bucket accuracies, `tables`, `logits`,
-    `targets`, `num_pairs`, `world`)"""
+    `targets`, `num_pairs`, `world`)
+    store: a pcr_amd.store.CropStore over the dataset's crops -- the batches then come from `store.val_batch` (two
+    launches, no host read; the dataset's pair list is uploaded once if the store holds none), keyed by the GLOBAL pair
+    index, so a pair's clouds are the same bits on any number of ranks and at any batch size.  Its samples are another
+    stream than numpy's; None keeps the host path and its results."""
     if rank is None:
         rank, _, world = shard.env_world()
         if not shard.is_dist():
@@ -144,13 +148,21 @@ def evaluate_model(model, dataset, batch_size, seed=0, device="cuda", rank=None,
     shard.broadcast_buffers(model)
     keep = ("val_match_gt", "match_classes", "num_points", "val_vis_gt_all", "is_fp")
     local = []
+    if store is not None:
+        if store.val is None:
+            store.set_val_pairs(dataset.pairs, (), dataset.visibility)
+        if store.val["num_pairs"] != n:
+            raise ValueError("the store holds %d validation pairs, the dataset %d" % (store.val["num_pairs"], n))
     with torch.no_grad():
         for b0 in range(lo, hi, batch_size):
-            items = []
-            for i in range(b0, min(hi, b0 + batch_size)):
-                np.random.seed(seed_of(seed, i))
-                items.append(dataset[i])
-            batch = D.collate_pairs(items, device=device)
+            if store is not None:
+                batch = store.val_batch(b0, min(hi, b0 + batch_size), seed, n=dataset.tp.ns)
+            else:
+                items = []
+                for i in range(b0, min(hi, b0 + batch_size)):
+                    np.random.seed(seed_of(seed, i))
+                    items.append(dataset[i])
+                batch = D.collate_pairs(items, device=device)
             (res,) = model(return_loss=False, **batch)
             if on_batch is not None:
                 on_batch(b0, batch, res)
@@ -182,10 +194,12 @@ def evaluate_model(model, dataset, batch_size, seed=0, device="cuda", rank=None,
 
 
 def evaluate_checkpoint(cfg_path, ckpt_path, crop_root, max_combinations=None, seed=None, meta=None, batch_size=None,
-                        device="cuda", cfg_options=None, literal_exclusion=False, num_classes=None):
+                        device="cuda", cfg_options=None, literal_exclusion=False, num_classes=None, device_store=False):
     """(config file, mmcv-layout checkpoint, crop directory) -> `val_match_acc` and everything else
     `ReIDDatasetBase.evaluate` logs, on however many ranks torch.distributed is running (one process per GPU; no
-    data-path collective -- BatchNorm statistics are broadcast once before, the per-pair results gathered once after)."""
+    data-path collective -- BatchNorm statistics are broadcast once before, the per-pair results gathered once after).
+    device_store: read the crop directory once into a pcr_amd.store.CropStore on this rank's device and assemble the
+    batches there (see evaluate_model)."""
     cfg = Config.fromfile(cfg_path)
     if cfg_options:
         cfg.merge_from_dict(cfg_options)
@@ -200,8 +214,14 @@ def evaluate_checkpoint(cfg_path, ckpt_path, crop_root, max_combinations=None, s
                               literal_exclusion=literal_exclusion, num_classes=num_classes)
     bs = int(batch_size or data_cfg.get("val_samples_per_gpu") or data_cfg.get("samples_per_gpu") or 512)
     seed = int(val_cfg.get("validation_seed", 0) if seed is None else seed)
+    store = None
+    if device_store:
+        from .store import CropStore
+        sl = dict(val_cfg.get("sparse_loader") or {})
+        store = CropStore.from_directory(crop_root, table, device=device,
+                                         load_fraction=float(sl.get("load_fraction", 1.0) or 1.0), pair_rule=False)
     out = evaluate_model(model, ds, bs, seed=seed, device=device, cls_to_idx=val_cfg.get("cls_to_idx"),
-                         num_classes=table.num_classes)
+                         num_classes=table.num_classes, store=store)
     out["checkpoint_meta"] = ck_meta
     out["config"] = os.path.abspath(cfg_path)
     guard = getattr(model, "guard_state", lambda: None)()
@@ -222,12 +242,13 @@ def main(argv=None):
     ap.add_argument("--max-combinations", type=int, default=None)
     ap.add_argument("--seed", type=int, default=None)
     ap.add_argument("--batch-size", type=int, default=None)
+    ap.add_argument("--device-store", action="store_true", help="keep the crops on the device (pcr_amd.store)")
     args = ap.parse_args(argv)
     rank, local, world = shard.env_world()
     torch.cuda.set_device(local)
     shard.init(device=torch.device("cuda", local))
     out = evaluate_checkpoint(args.config, args.checkpoint, args.crop_root, max_combinations=args.max_combinations,
-                              seed=args.seed, meta=args.meta, batch_size=args.batch_size)
+                              seed=args.seed, meta=args.meta, batch_size=args.batch_size, device_store=args.device_store)
     if rank == 0:
         flat = {k: v for k, v in out.items() if isinstance(v, (int, float, str))}
         flat["tables"] = {name: {str(k): v for k, v in metrics.flatten_tables(t).items()}

@@ -746,6 +746,34 @@ int pcr_attn_apply_f32(const pcr_attn_params *p, pcr_stream_t stream);
  * mode, never of B: a pair's result does not depend on the batch it travels in), else 0 */
 int pcr_attn_apply_pool_ok(const pcr_attn_params *p);
 
+/* Gated launches (additive to ABI 17): score only the live pairs of a device-counted list.  A fixed-shape pair list
+ * (pcr_assoc_pairs_i32: capacity rows of which *count are real, the rest (0, 0) padding) makes fixed-shape launches, and a
+ * captured graph fixes their grids -- so the launches themselves read the count and do no work for the padding.
+ * pcr_live says which virtual clouds of a launch are live: with n = clamp(*count - offset, 0, period), cloud b is live
+ * iff b % period < n.  For the matching stages (B = 2 period: cloud p < period is pair p's first direction, cloud
+ * period + p its second) the live clouds are the two runs [0, n) and [period, period + n).
+ *   Dead clouds.  The launch reads NOTHING of a dead cloud -- neither its q_index / kv_index entries nor its features --
+ *     and writes nothing for it: its rows of kv / out / pool_out keep what they held.
+ *   Live clouds.  A live cloud's output is bit for bit what the un-gated entry point writes for that cloud.  The kernel
+ *     choice stays a function of the launch shape and the arithmetic mode; a pair's bits never depend on the batch it
+ *     travels in, and *count does not change that.
+ *   Capture.  *count is read by the launch (one load per workgroup), not by the host: a captured graph re-reads it on
+ *     every replay.  count may exceed period (a list scored in chunks: offset = the pairs of the earlier chunks).
+ *   live == NULL is the un-gated call.
+ *   Unsupported shapes.  pcr_attn_live_ok (shape and arithmetic only, never B) says yes for d = c1 = c2 = cout = 64
+ *     without kv_splits -- the matching stages' corss_attention blocks -- whichever kernel pcr_attn_kv_f32 /
+ *     pcr_attn_apply_f32 choose for them (wave-autonomous or tile form, pooled output, q_pos, trailing conv; all three
+ *     arithmetic modes).  Where it says no, the _live entry points return PCR_ERR_INVALID; they never score everything
+ *     silently. */
+typedef struct pcr_live {
+  const int *count;          /* device, (1): the caller's pair count (may exceed period) */
+  int period;                /* > 0: cloud b is live iff (b % period) < clamp(*count - offset, 0, period) */
+  int offset;                /* >= 0: pairs scored by earlier chunks */
+} pcr_live;
+int pcr_attn_live_ok(const pcr_attn_params *p);
+int pcr_attn_kv_live_f32(const pcr_attn_params *p, const pcr_live *live, pcr_stream_t stream);
+int pcr_attn_apply_live_f32(const pcr_attn_params *p, const pcr_live *live, pcr_stream_t stream);
+
 /* Matching head tail: pool 'both' over the point-concatenated pair (get_pooled_feats,
  * models/ReIDNet.py:526-534: [max over 2L points, mean over 2L points]) followed by
  * LinearRes(2C,2C,GroupNorm) + Linear(2C,1) (models/lanegcn_nets.py:228-241, ReIDNet.py:455-457).
@@ -763,6 +791,10 @@ typedef struct pcr_head_params {
   const float *w1t, *w2t;
 } pcr_head_params;
 int pcr_pool_head_f32(const pcr_head_params *p, pcr_stream_t stream);
+/* gated (pcr_live above, pairs in place of clouds: pair p is live iff p % period < n): a dead pair's clouds are not read;
+ * logits[p] = *dead_value (a HOST float, read when the call is made; NULL: 0.0f) and, if asked for, pooled[p] = zeros.
+ * Live pairs: bit for bit pcr_pool_head_f32.  live == NULL is the un-gated call. */
+int pcr_pool_head_live_f32(const pcr_head_params *p, const pcr_live *live, const float *dead_value, pcr_stream_t stream);
 
 /* get_pooled_feats with pool_type='both' on its own (models/ReIDNet.py:529-532):
  * x (B,C,L) -> out (B,2C) = [max over L, mean over L]. */

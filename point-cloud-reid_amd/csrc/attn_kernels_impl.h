@@ -20,7 +20,44 @@ struct AttnArgs {
   pcr_attn_params p;
   int dbg;   // diagnostics (trace builds): 256 = stamp the shader clock
   int wpc;   // attn_kv_stream128_kernel: waves per cloud (1, 2, 4), a function of Sk only
+  // gated launches only (pcr_live, the GATE instantiations below); the un-gated kernels never read these
+  const int *live_count;
+  int live_period, live_offset;
 };
+
+// ---- gated launches (pcr_live): which virtual clouds of a launch are live ------------------------------------------------
+// n = clamp(*count - offset, 0, period) pairs of every period are live: cloud b iff b % period < n.  The count is ONE load
+// per workgroup from a kernel-argument address, broadcast through readfirstlane, so every branch on it is wave-uniform.
+// The persistent kernels walk the compact index v in [0, total) of the live clouds only and map it back:
+// b = (v / n) period + v % n -- for the matching stages' two runs [0, n) and [period, period + n) that is
+// v < n ? v : v - n + period.  Dead clouds are never indexed: neither their q_index / kv_index entries nor their features are
+// read, nothing of theirs is written.
+struct LiveWalk {
+  unsigned n, period;
+  long total;   // live clouds of the launch
+  __device__ __forceinline__ long map(long v) const {
+    const unsigned q = (unsigned)v / n;
+    return (long)q * period + ((unsigned)v - q * n);
+  }
+};
+__device__ __forceinline__ unsigned live_pairs(const AttnArgs &a) {
+  int c = __builtin_amdgcn_readfirstlane(*a.live_count);
+  c = c < 0 ? 0 : c;
+  c -= a.live_offset;
+  return (unsigned)(c < 0 ? 0 : (c > a.live_period ? a.live_period : c));
+}
+__device__ __forceinline__ LiveWalk live_walk(const AttnArgs &a) {
+  LiveWalk w;
+  w.n = live_pairs(a);
+  w.period = (unsigned)a.live_period;
+  const unsigned B = (unsigned)a.p.B, full = B / w.period, rem = B - full * w.period;
+  w.total = (long)full * w.n + (rem < w.n ? rem : w.n);
+  return w;
+}
+// the tile kernels (one workgroup per cloud): is cloud b live?  Workgroup-uniform, asked before any barrier.
+__device__ __forceinline__ bool live_cloud(const AttnArgs &a, unsigned b) {
+  return b % (unsigned)a.live_period < live_pairs(a);
+}
 
 // shader-clock stamps of the wave-autonomous kv kernel (trace builds only: -DPCR_SA_TRACE_BUILD, PCR_ATTN_TRACE=<file>);
 // one record of kATraceMarks stamps per cloud round of waves 0 and 5 of the first workgroups
@@ -332,6 +369,12 @@ template <int TB, int NR, int WSEL, int NTW>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(3, 3))) void attn_kv_kernel_o3(AttnArgs a) {
   attn_kv_body<TB, NR, WSEL, NTW>(a);
 }
+// ... gated (pcr_live): the workgroup of a dead cloud leaves at entry
+template <int TB, int NR, int WSEL, int NTW>
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(3, 3))) void attn_kv_kernel_o3_live(AttnArgs a) {
+  if (!live_cloud(a, blockIdx.x)) return;
+  attn_kv_body<TB, NR, WSEL, NTW>(a);
+}
 // ... and to half of it: the d = 128 shape, whose LDS allows two workgroups per CU and no more
 template <int TB, int NR, int WSEL, int NTW, bool BFP = false>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2))) void attn_kv_kernel_o2(AttnArgs a) {
@@ -373,7 +416,9 @@ constexpr int kKvsWaves = 8;
 // v 8 g + 4 h + q), which makes register r of the tile the A operand of fold step r as it stands (contraction over the v
 // pairs (v_r, v_r + 4) instead of (2 s, 2 s + 1): other rounding in the last bits, still one fixed order per cloud), the
 // key sums never leave the wave, and eight clouds are in flight per workgroup with no barrier after the staging.
-template <bool DIAG, bool BF, int XS = 4, bool ONEW = false>
+// GATE (pcr_live): the rounds walk the compact index of the live clouds; a slot past their end is a dead slot of the
+// un-gated walk (it stays inside the barriers); a workgroup with no round at all leaves before it stages anything.
+template <bool DIAG, bool BF, int XS = 4, bool ONEW = false, bool GATE = false>
 __global__ __launch_bounds__(64 * kKvsWaves) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void attn_kv_stream64_kernel(AttnArgs a) {
   static_assert(BF || XS == 4, "the f32 form is c2 = 64 only");
@@ -389,6 +434,11 @@ void attn_kv_stream64_kernel(AttnArgs a) {
   float *s_red = s_wm + D * LD;                                   // [CPG][KVS]
   const int tid = threadIdx.x, lane = tid & 63, j = lane & 31, h = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  LiveWalk lw{};
+  if constexpr (GATE) {
+    lw = live_walk(a);
+    if ((long)blockIdx.x * (kKvsWaves / (ONEW ? 1 : 4)) >= lw.total) return;   // (cpg >= this: no round for this workgroup)
+  }
   {
     const f32x4 *src = reinterpret_cast<const f32x4 *>(BF ? p.wkv_bf : p.wkv);   // (both images are 4096 16-byte units)
     for (int e = tid; e < WU; e += 64 * kKvsWaves) s_w[e] = src[e];
@@ -431,9 +481,10 @@ void attn_kv_stream64_kernel(AttnArgs a) {
 #define PCR_AMARK(m) do { } while (0)
 #define PCR_ANEXT() do { } while (0)
 #endif
-  for (long c0 = (long)blockIdx.x * cpg; c0 < p.B; c0 += (long)gridDim.x * cpg) {
-    const long b = c0 + cslot;
-    const bool live = b < p.B;
+  const long nB = GATE ? lw.total : (long)p.B;
+  for (long c0 = (long)blockIdx.x * cpg; c0 < nB; c0 += (long)gridDim.x * cpg) {
+    const bool live = c0 + cslot < nB;
+    const long b = GATE ? (live ? lw.map(c0 + cslot) : 0) : c0 + cslot;
     PCR_AMARK(4);
     f32x16 kv[NKV];
 #pragma unroll
@@ -998,8 +1049,12 @@ __global__ __launch_bounds__(kThreads) void attn_kv_wide_kernel(AttnArgs a) {
 //   rows [0,c1) query features x, rows [c1,c1+d) position hidden h  --Q-->  rows [c1,c1+d) = elu(.)+1
 //   --scale by Sk/(Q.ksum)--> --M (kv image)--> message --LayerNorm--> [x ; msg] --FFN0--> 2d rows --FFN1-->
 //   cout rows --LayerNorm--> (+ x, re-read from global: it was overwritten by FFN0) --cov_final--> store.
-template <int TB, int NR>
+// GATE (pcr_live): the workgroups of a dead cloud leave at entry.
+template <int TB, int NR, bool GATE = false>
 __global__ __launch_bounds__(kThreads) void attn_apply_kernel(AttnArgs a) {
+  if constexpr (GATE) {
+    if (!live_cloud(a, blockIdx.y)) return;
+  }
   constexpr int T = 32 * TB, RP = T + 1;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const pcr_attn_params &p = a.p;
@@ -1128,7 +1183,9 @@ constexpr int kApsWaves = 8;
 // cloud, reduces every block's 32 tokens per channel with a TRANSPOSING butterfly (five exchange steps; a lane keeps half
 // of its registers per step, so the steps cost 16 + 8 + 4 + 2 + 1 registers, not 5 x 32) and writes the cloud's
 // per-channel maximum and sum: p.pool_out (B, 2, 64) -- 512 bytes per cloud instead of 32 KB that pool_head would read back.
-template <bool QPOS, int C1S, int CF, int NOB = 2, int ND = 2, bool POOL = false>
+// GATE (pcr_live): the items are the blocks (POOL: the clouds) of the live clouds only, by their compact index; a workgroup
+// with no item leaves before it stages anything.
+template <bool QPOS, int C1S, int CF, int NOB = 2, int ND = 2, bool POOL = false, bool GATE = false>
 __global__ __launch_bounds__(64 * kApsWaves) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void attn_apply_stream64_kernel(AttnArgs a) {
   static_assert(!QPOS || C1S == 2 * ND, "q_pos needs c1 == d");
@@ -1146,6 +1203,11 @@ void attn_apply_stream64_kernel(AttnArgs a) {
   float *s_ks = reinterpret_cast<float *>(s_p0 + 64);    // [waves][64] key sums of the wave's current cloud
   const int tid = threadIdx.x, lane = tid & 63, j = lane & 31, h = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  LiveWalk lw{};
+  if constexpr (GATE) {
+    lw = live_walk(a);
+    if ((long)blockIdx.x * kApsWaves >= lw.total * (POOL ? 1 : (p.Lq >> 5))) return;
+  }
   {
     // (c1 not a multiple of 16: the padded image of mlp[0]; the packer pads wq's single step with zero columns itself)
     const f32x4 *wq = reinterpret_cast<const f32x4 *>(p.wq),
@@ -1170,7 +1232,8 @@ void attn_apply_stream64_kernel(AttnArgs a) {
   }
   __syncthreads();
   const int nblk = p.Lq >> 5;
-  const long nitem = (long)p.B * nblk;
+  const long nB = GATE ? lw.total : (long)p.B;
+  const long nitem = nB * nblk;
   const int dh = D / p.nhead;
   const float skf = (float)p.Sk;
   float *ksw = s_ks + wave * 64;
@@ -1203,11 +1266,12 @@ void attn_apply_stream64_kernel(AttnArgs a) {
   long pc = gw;
   int pblk = 0;
   float pmax = -INFINITY, psum = 0.f;
-  for (long it = gw; POOL ? pc < p.B : it < nitem; it += POOL ? 0 : nwav) {
+  for (long it = gw; POOL ? pc < nB : it < nitem; it += POOL ? 0 : nwav) {
     asm volatile("" ::: "memory");   // (weight reads stay inside the item loop)
     PCR_AMARK(0);
-    const long b = POOL ? pc : it / nblk;
-    const int blk = POOL ? pblk : (int)(it - b * nblk);
+    const long vb = POOL ? pc : it / nblk;   // (GATE: the cloud's compact index)
+    const int blk = POOL ? pblk : (int)(it - vb * nblk);
+    const long b = GATE ? lw.map(vb) : vb;
     const size_t bq_ = p.q_index ? (size_t)p.q_index[b] : (size_t)b;
     const size_t kb_ = p.kv_index ? (size_t)p.kv_index[b] : (size_t)b;
     const float *kvp = p.kv + kb_ * ((size_t)D * D + D);
@@ -2187,12 +2251,35 @@ static void attn_dump_trace(const char *path, const char *tag, int wgs, int B, i
   fclose(f);
 }
 
+// gated launches (pcr_live): the caller's count, period and offset travel in AttnArgs; false = not a valid gate
+static bool attn_set_live(AttnArgs &a, const pcr_live *live) {
+  a.live_count = nullptr;
+  a.live_period = a.live_offset = 0;
+  if (!live) return true;
+  if (!live->count || live->period < 1 || live->offset < 0) return false;
+  a.live_count = live->count;
+  a.live_period = live->period;
+  a.live_offset = live->offset;
+  return true;
+}
+// the blocks a gated launch covers: the matching stages' (d = c1 = c2 = cout = 64, whole launches) -- every kernel the
+// dispatchers below choose for them has a GATE form.  Shape only.
+static bool attn_live_shape(const pcr_attn_params &p) {
+  return p.d == 64 && p.c1 == 64 && p.c2 == 64 && p.cout == 64 && p.kv_splits <= 1;
+}
+// KERN, or its gated form when the launch carries a pcr_live
+template <auto KERN, auto KERN_LIVE>
+static inline int attn_launch_g(dim3 grid, dim3 block, size_t lds, hipStream_t st, const AttnArgs &a) {
+  return a.live_count ? pcr_launch_lds<KERN_LIVE>(grid, block, lds, st, a) : pcr_launch_lds<KERN>(grid, block, lds, st, a);
+}
+
 // d_model <= 128: one workgroup per key-side cloud (both precisions; wq / wkv / ... are images of THIS unit's kind)
-static int attn_kv_narrow(const pcr_attn_params *pp, pcr_stream_t stream) {
+static int attn_kv_narrow(const pcr_attn_params *pp, const pcr_live *live, pcr_stream_t stream) {
   AttnArgs a;
   a.p = *pp;
   a.dbg = 0;
   a.wpc = 0;
+  if (!attn_set_live(a, live) || (live && !attn_live_shape(*pp))) return PCR_ERR_INVALID;
   const int d = pp->d;
   if (pp->c2 < pp->d) return PCR_ERR_INVALID;   // the in-place K/V projection needs 2d <= c2 + d rows
   const int tb = d <= 64 ? 2 : 1, RP = 32 * tb + 1;
@@ -2233,22 +2320,23 @@ static int attn_kv_narrow(const pcr_attn_params *pp, pcr_stream_t stream) {
     const dim3 gg(gs), bb(64 * kKvsWaves);
     const bool mh = pp->nhead >= 2;
     if (bf && wide) {
+      if (live) return PCR_ERR_INVALID;   // (c2 = 128: not a matching-stage block)
       constexpr int W = kBfUnit ? 8 : 4;
       return mh ? pcr_launch_lds<attn_kv_stream64_kernel<true, kBfUnit, W>>(gg, bb, lds_s, st, a)
                 : pcr_launch_lds<attn_kv_stream64_kernel<false, kBfUnit, W>>(gg, bb, lds_s, st, a);
     }
     if (!bf)
-      return mh ? pcr_launch_lds<attn_kv_stream64_kernel<true, false>>(gg, bb, lds_s, st, a)
-                : pcr_launch_lds<attn_kv_stream64_kernel<false, false>>(gg, bb, lds_s, st, a);
+      return mh ? attn_launch_g<attn_kv_stream64_kernel<true, false>, attn_kv_stream64_kernel<true, false, 4, false, true>>(gg, bb, lds_s, st, a)
+                : attn_launch_g<attn_kv_stream64_kernel<false, false>, attn_kv_stream64_kernel<false, false, 4, false, true>>(gg, bb, lds_s, st, a);
     static const char *atrace = pcr_tune_str("PCR_ATTN_TRACE");
     if (atrace) a.dbg |= 256;
     int rc;
     if (onew)
-      rc = mh ? pcr_launch_lds<attn_kv_stream64_kernel<true, kBfUnit, 4, kBfUnit>>(gg, bb, lds_s, st, a)
-              : pcr_launch_lds<attn_kv_stream64_kernel<false, kBfUnit, 4, kBfUnit>>(gg, bb, lds_s, st, a);
+      rc = mh ? attn_launch_g<attn_kv_stream64_kernel<true, kBfUnit, 4, kBfUnit>, attn_kv_stream64_kernel<true, kBfUnit, 4, kBfUnit, true>>(gg, bb, lds_s, st, a)
+              : attn_launch_g<attn_kv_stream64_kernel<false, kBfUnit, 4, kBfUnit>, attn_kv_stream64_kernel<false, kBfUnit, 4, kBfUnit, true>>(gg, bb, lds_s, st, a);
     else
-      rc = mh ? pcr_launch_lds<attn_kv_stream64_kernel<true, kBfUnit>>(gg, bb, lds_s, st, a)
-              : pcr_launch_lds<attn_kv_stream64_kernel<false, kBfUnit>>(gg, bb, lds_s, st, a);
+      rc = mh ? attn_launch_g<attn_kv_stream64_kernel<true, kBfUnit>, attn_kv_stream64_kernel<true, kBfUnit, 4, false, true>>(gg, bb, lds_s, st, a)
+              : attn_launch_g<attn_kv_stream64_kernel<false, kBfUnit>, attn_kv_stream64_kernel<false, kBfUnit, 4, false, true>>(gg, bb, lds_s, st, a);
     if (atrace) attn_dump_trace(atrace, "kv64", gs, (int)pp->B, pp->Sk);
     return rc;
   }
@@ -2283,10 +2371,11 @@ static int attn_kv_narrow(const pcr_attn_params *pp, pcr_stream_t stream) {
                           : pcr_launch_lds<attn_kv_stream128_kernel<4>>(gg, bb, lds_s, st, a);
   }
 #endif
+  if (live && (d != 64 || ns != 1)) return PCR_ERR_INVALID;
   pcr_note_arith(PCR_PREC_F32);   // the tile kernel projects in f32 in both units (only the form of M differs)
   int rc;
   if (d == 32) rc = pcr_launch_lds<attn_kv_kernel<2, 1, 2, 1>>(g, blk, lds, st, a);        // 2d = 64: two cout blocks
-  else if (d == 64) rc = pcr_launch_lds<attn_kv_kernel_o3<2, 1, 1, 1>>(g, blk, lds, st, a);   // four, one per wave
+  else if (d == 64) rc = attn_launch_g<attn_kv_kernel_o3<2, 1, 1, 1>, attn_kv_kernel_o3_live<2, 1, 1, 1>>(g, blk, lds, st, a);   // four, one per wave
   else if (d == 128) {
     // eight cout blocks, two rounds.  NOT the three-workgroups-per-CU form: this shape's fold buffer (d (d + 1) floats =
     // 66 KB) allows two workgroups per CU whatever the registers say, and held to a third of the register file the body
@@ -2312,12 +2401,13 @@ static bool aps64_shape(const pcr_attn_params &p) {
   return p.d == 64 && aps_in && aps_out && (p.Lq & 31) == 0 && (p.nhead == 1 || p.nhead == 2 || p.nhead == 4);
 }
 
-static int attn_apply_launch(const pcr_attn_params *pp, pcr_stream_t stream) {
+static int attn_apply_launch(const pcr_attn_params *pp, const pcr_live *live, pcr_stream_t stream) {
   const pcr_attn_params &p = *pp;
   AttnArgs a;
   a.p = p;
   a.dbg = 0;
   a.wpc = 0;
+  if (!attn_set_live(a, live) || (live && !attn_live_shape(p))) return PCR_ERR_INVALID;
   // (round 6, measured and dropped: 64-token tiles for d = 128 -- half the weight traffic from L2, half the waves per CU:
   // pt1024's attn_apply[d=128] 0.455 -> 0.518 ms, profiles/r06_inproc_ab.txt)
   const int tb = p.d <= 32 ? 4 : (p.d <= 64 ? 2 : 1), T = 32 * tb, RP = T + 1;
@@ -2371,7 +2461,7 @@ static int attn_apply_launch(const pcr_attn_params *pp, pcr_stream_t stream) {
       // pooled output (pcr_attn_apply_pool_ok said yes): whole clouds per wave
       const long nwgp = ((long)p.B + kApsWaves - 1) / kApsWaves;
       const dim3 ggp((unsigned)(nwgp < pcr_cu_count() ? nwgp : pcr_cu_count()));
-      return pcr_launch_lds<attn_apply_stream64_kernel<false, 4, 0, 2, 2, true>>(ggp, bb, aps_lds, st, a);
+      return attn_launch_g<attn_apply_stream64_kernel<false, 4, 0, 2, 2, true>, attn_apply_stream64_kernel<false, 4, 0, 2, 2, true, true>>(ggp, bb, aps_lds, st, a);
     }
     int rc;
     if (nob == 4)
@@ -2382,20 +2472,22 @@ static int attn_apply_launch(const pcr_attn_params *pp, pcr_stream_t stream) {
       rc = cf ? pcr_launch_lds<attn_apply_stream64_kernel<false, 2, 4>>(gg, bb, aps_lds, st, a)
               : pcr_launch_lds<attn_apply_stream64_kernel<false, 2, 0>>(gg, bb, aps_lds, st, a);
     else if (p.q_pos)
-      rc = cf ? pcr_launch_lds<attn_apply_stream64_kernel<true, 4, 4>>(gg, bb, aps_lds, st, a)
-              : pcr_launch_lds<attn_apply_stream64_kernel<true, 4, 0>>(gg, bb, aps_lds, st, a);
+      rc = cf ? attn_launch_g<attn_apply_stream64_kernel<true, 4, 4>, attn_apply_stream64_kernel<true, 4, 4, 2, 2, false, true>>(gg, bb, aps_lds, st, a)
+              : attn_launch_g<attn_apply_stream64_kernel<true, 4, 0>, attn_apply_stream64_kernel<true, 4, 0, 2, 2, false, true>>(gg, bb, aps_lds, st, a);
     else
-      rc = cf ? pcr_launch_lds<attn_apply_stream64_kernel<false, 4, 4>>(gg, bb, aps_lds, st, a)
-              : pcr_launch_lds<attn_apply_stream64_kernel<false, 4, 0>>(gg, bb, aps_lds, st, a);
+      rc = cf ? attn_launch_g<attn_apply_stream64_kernel<false, 4, 4>, attn_apply_stream64_kernel<false, 4, 4, 2, 2, false, true>>(gg, bb, aps_lds, st, a)
+              : attn_launch_g<attn_apply_stream64_kernel<false, 4, 0>, attn_apply_stream64_kernel<false, 4, 0, 2, 2, false, true>>(gg, bb, aps_lds, st, a);
     if (aptrace) attn_dump_trace(aptrace, "apply64", (int)gg.x, (int)p.B, p.Lq);
     return rc;
   }
 #endif
   const bool wide = 2 * p.d > 128 || p.cout > 128 || p.cfinal > 128;   // some layer has > 4 cout blocks
-  if (tb == 4)
+  if (tb == 4 && !live)
     return wide ? pcr_launch_lds<attn_apply_kernel<4, 2>>(g, blk, lds, st, a) : pcr_launch_lds<attn_apply_kernel<4, 1>>(g, blk, lds, st, a);
   if (tb == 2)
-    return wide ? pcr_launch_lds<attn_apply_kernel<2, 2>>(g, blk, lds, st, a) : pcr_launch_lds<attn_apply_kernel<2, 1>>(g, blk, lds, st, a);
+    return wide ? attn_launch_g<attn_apply_kernel<2, 2>, attn_apply_kernel<2, 2, true>>(g, blk, lds, st, a)
+                : attn_launch_g<attn_apply_kernel<2, 1>, attn_apply_kernel<2, 1, true>>(g, blk, lds, st, a);
+  if (live) return PCR_ERR_INVALID;
   // cout blocks of the widest layer: up to 8 -> two rounds per wave, up to 16 -> four, up to 32 (d_model 512) -> eight
   int widest = 2 * p.d > p.cout ? 2 * p.d : p.cout;
   if (p.cfinal > widest) widest = p.cfinal;
@@ -2410,11 +2502,11 @@ static int attn_apply_launch(const pcr_attn_params *pp, pcr_stream_t stream) {
 
 #if PCR_ATTN_PREC == 1
 // (the caller -- attn_kernels.hip -- has validated the parameters and swapped the bf16 images into wq / wkv / ...)
-int pcr_attn_kv_bf3(const pcr_attn_params *pp, pcr_stream_t stream) { return attn_kv_narrow(pp, stream); }
-int pcr_attn_apply_bf3(const pcr_attn_params *pp, pcr_stream_t stream) { return attn_apply_launch(pp, stream); }
+int pcr_attn_kv_bf3(const pcr_attn_params *pp, const pcr_live *live, pcr_stream_t stream) { return attn_kv_narrow(pp, live, stream); }
+int pcr_attn_apply_bf3(const pcr_attn_params *pp, const pcr_live *live, pcr_stream_t stream) { return attn_apply_launch(pp, live, stream); }
 #else
-int pcr_attn_kv_bf3(const pcr_attn_params *pp, pcr_stream_t stream);      // attn_kernels_bf3.hip
-int pcr_attn_apply_bf3(const pcr_attn_params *pp, pcr_stream_t stream);
+int pcr_attn_kv_bf3(const pcr_attn_params *pp, const pcr_live *live, pcr_stream_t stream);      // attn_kernels_bf3.hip
+int pcr_attn_apply_bf3(const pcr_attn_params *pp, const pcr_live *live, pcr_stream_t stream);
 
 // precision != f32, d_model <= 128 and bf16 images given: the same parameters with the images swapped in
 static bool attn_bf(const pcr_attn_params &p, pcr_attn_params &q) {
@@ -2441,8 +2533,9 @@ PCR_EXPORT int pcr_attn_kv_splits(int B, int Sk, int d) {
   return ntile >= 16 ? 4 : (ntile >= 8 ? 2 : 1);
 }
 
-PCR_EXPORT int pcr_attn_kv_f32(const pcr_attn_params *pp, pcr_stream_t stream) {
+static int attn_kv_entry(const pcr_attn_params *pp, const pcr_live *live, pcr_stream_t stream) {
   if (!pp || attn_check(*pp)) return PCR_ERR_INVALID;
+  if (live && !attn_live_shape(*pp)) return PCR_ERR_INVALID;   // (never a silent un-gated launch)
   if (pp->B == 0) return PCR_OK;
   const int d = pp->d;
   if (d > 128) {   // wide: d / 64 workgroups per cloud (attn_kv_wide_kernel)
@@ -2462,8 +2555,16 @@ PCR_EXPORT int pcr_attn_kv_f32(const pcr_attn_params *pp, pcr_stream_t stream) {
     return pcr_launch_lds<attn_kv_wide_kernel<3>>(g, blk, lds, pcr_s(stream), a);
   }
   pcr_attn_params q;
-  if (attn_bf(*pp, q)) return pcr_attn_kv_bf3(&q, stream);
-  return attn_kv_narrow(pp, stream);
+  if (attn_bf(*pp, q)) return pcr_attn_kv_bf3(&q, live, stream);
+  return attn_kv_narrow(pp, live, stream);
+}
+
+PCR_EXPORT int pcr_attn_kv_f32(const pcr_attn_params *pp, pcr_stream_t stream) { return attn_kv_entry(pp, nullptr, stream); }
+PCR_EXPORT int pcr_attn_kv_live_f32(const pcr_attn_params *pp, const pcr_live *live, pcr_stream_t stream) {
+  return attn_kv_entry(pp, live, stream);
+}
+PCR_EXPORT int pcr_attn_live_ok(const pcr_attn_params *pp) {
+  return (pp && !attn_check(*pp) && attn_live_shape(*pp)) ? 1 : 0;
 }
 
 static bool attn_pool_ok(const pcr_attn_params &p) {
@@ -2475,13 +2576,19 @@ PCR_EXPORT int pcr_attn_apply_pool_ok(const pcr_attn_params *pp) {
   return (pp && !attn_check(*pp) && attn_pool_ok(*pp)) ? 1 : 0;
 }
 
-PCR_EXPORT int pcr_attn_apply_f32(const pcr_attn_params *pp, pcr_stream_t stream) {
+static int attn_apply_entry(const pcr_attn_params *pp, const pcr_live *live, pcr_stream_t stream) {
   if (!pp || attn_check(*pp) || (!pp->out && !pp->pool_out)) return PCR_ERR_INVALID;
   if (pp->pool_out && !attn_pool_ok(*pp)) return PCR_ERR_INVALID;
+  if (live && !attn_live_shape(*pp)) return PCR_ERR_INVALID;   // (never a silent un-gated launch)
   if (pp->B == 0) return PCR_OK;
   if (pp->B > 65535) return PCR_ERR_INVALID;
   pcr_attn_params q;
-  if (attn_bf(*pp, q)) return pcr_attn_apply_bf3(&q, stream);
-  return attn_apply_launch(pp, stream);
+  if (attn_bf(*pp, q)) return pcr_attn_apply_bf3(&q, live, stream);
+  return attn_apply_launch(pp, live, stream);
+}
+
+PCR_EXPORT int pcr_attn_apply_f32(const pcr_attn_params *pp, pcr_stream_t stream) { return attn_apply_entry(pp, nullptr, stream); }
+PCR_EXPORT int pcr_attn_apply_live_f32(const pcr_attn_params *pp, const pcr_live *live, pcr_stream_t stream) {
+  return attn_apply_entry(pp, live, stream);
 }
 #endif

@@ -20,7 +20,7 @@ __device__ __forceinline__ float wave_max(float v) {
 
 // the same reductions without LDS round trips: four DPP steps inside a row of 16 lanes (xor 1, xor 2, half-row mirror, row
 // mirror: afterwards every lane holds its row's result), then the four rows' results by v_readlane.  (__shfl_xor is
-// ds_bpermute: six dependent LDS round trips per reduction, and pool_head_kernel does 128 of them per pair.)
+// ds_bpermute: six dependent LDS round trips per reduction, and pool_head_kernel_t does 128 of them per pair.)
 template <int CTRL>
 __device__ __forceinline__ float dpp_f32(float v) {
   return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
@@ -68,7 +68,32 @@ __device__ __forceinline__ void vec_groupnorm(float *v, int n, int g, const floa
   __syncthreads();
 }
 
-__global__ __launch_bounds__(kThreads) void pool_head_kernel(pcr_head_params p) {
+// gated form (pcr_live): pair pr is live iff pr % period < clamp(*count - offset, 0, period).  The workgroup of a dead pair
+// reads nothing of it and leaves `dead_value` (and a zero pooled row) behind -- workgroup-uniform, before any barrier.
+struct HeadLiveArgs {
+  pcr_head_params p;
+  const int *count;
+  int period, offset;
+  float dead_value;
+};
+__device__ __forceinline__ pcr_head_params head_params_of(const pcr_head_params &a) { return a; }
+__device__ __forceinline__ pcr_head_params head_params_of(const HeadLiveArgs &a) { return a.p; }
+// (one body, two kernels: GATE = false takes pcr_head_params itself and compiles to what it always was)
+template <bool GATE>
+__global__ __launch_bounds__(kThreads) void pool_head_kernel_t(std::conditional_t<GATE, HeadLiveArgs, pcr_head_params> arg) {
+  const pcr_head_params p = head_params_of(arg);
+  if constexpr (GATE) {
+    int c = __builtin_amdgcn_readfirstlane(*arg.count);
+    c = (c < 0 ? 0 : c) - arg.offset;
+    c = c < 0 ? 0 : (c > arg.period ? arg.period : c);
+    if ((int)(blockIdx.x % (unsigned)arg.period) >= c) {
+      const size_t pr = blockIdx.x;
+      const int n = 2 * p.C;
+      if (threadIdx.x == 0) p.logits[pr] = arg.dead_value;
+      if (p.pooled && (int)threadIdx.x < n) p.pooled[pr * n + threadIdx.x] = 0.f;
+      return;
+    }
+  }
   __shared__ float x[256], y[256], z[256];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const size_t pr = blockIdx.x;
@@ -1222,14 +1247,28 @@ PCR_EXPORT int pcr_pack_weight_bf16x2_f32(const float *w, int cout, int cin, flo
 
 PCR_EXPORT long pcr_attn_kv_floats(int d) { return (long)d * d + d; }
 
-PCR_EXPORT int pcr_pool_head_f32(const pcr_head_params *pp, pcr_stream_t stream) {
-  if (!pp) return PCR_ERR_INVALID;
+static int pool_head_check(const pcr_head_params *pp) {
+  if (!pp) return 1;
   const pcr_head_params &p = *pp;
-  if (p.P < 0 || p.C < 1 || 2 * p.C > 256 || p.L < 1 || p.groups < 1 || (2 * p.C) % p.groups || !p.o ||
-      !p.w1 || !p.w2 || !p.gn1_g || !p.gn1_b || !p.gn2_g || !p.gn2_b || !p.w_out || !p.b_out || !p.logits)
-    return PCR_ERR_INVALID;
+  return p.P < 0 || p.C < 1 || 2 * p.C > 256 || p.L < 1 || p.groups < 1 || (2 * p.C) % p.groups || !p.o ||
+         !p.w1 || !p.w2 || !p.gn1_g || !p.gn1_b || !p.gn2_g || !p.gn2_b || !p.w_out || !p.b_out || !p.logits;
+}
+
+PCR_EXPORT int pcr_pool_head_f32(const pcr_head_params *pp, pcr_stream_t stream) {
+  if (pool_head_check(pp)) return PCR_ERR_INVALID;
+  const pcr_head_params &p = *pp;
   if (p.P == 0) return PCR_OK;
-  return pcr_launch<pool_head_kernel>(dim3(p.P), dim3(kThreads), 0, pcr_s(stream), p);
+  return pcr_launch<pool_head_kernel_t<false>>(dim3(p.P), dim3(kThreads), 0, pcr_s(stream), p);
+}
+
+PCR_EXPORT int pcr_pool_head_live_f32(const pcr_head_params *pp, const pcr_live *live, const float *dead_value,
+                                      pcr_stream_t stream) {
+  if (!live) return pcr_pool_head_f32(pp, stream);
+  if (pool_head_check(pp) || !live->count || live->period < 1 || live->offset < 0) return PCR_ERR_INVALID;
+  const pcr_head_params &p = *pp;
+  if (p.P == 0) return PCR_OK;
+  const HeadLiveArgs a{p, live->count, live->period, live->offset, dead_value ? *dead_value : 0.f};
+  return pcr_launch<pool_head_kernel_t<true>>(dim3(p.P), dim3(kThreads), 0, pcr_s(stream), a);
 }
 
 PCR_EXPORT int pcr_pool_both_f32(const float *x, float *out, int B, int C, int L, pcr_stream_t stream) {

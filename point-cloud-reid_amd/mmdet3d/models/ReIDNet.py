@@ -494,19 +494,27 @@ class ReIDNet(nn.Module):
                 return self._match_logits(h1, h2, xyz1, xyz2, inference=True)[0]
         return self._match_logits(h1, h2, xyz1, xyz2, inference=True)[0]
 
-    def match_gallery(self, h, xyz, pairs):
+    # the launches index clouds by a 16-bit grid dimension: at most 32 k pairs (64 k virtual clouds) per pass of match_gallery
+    GALLERY_CHUNK = 32000
+
+    def match_gallery(self, h, xyz, pairs, count=None, dead_value=0.0):
         lvl = self._match_level(*self._halves(xyz))
         if lvl:
             with engine.guard_level(lvl):
-                return self._match_gallery(h, xyz, pairs)
-        return self._match_gallery(h, xyz, pairs)
+                return self._match_gallery(h, xyz, pairs, count, dead_value)
+        return self._match_gallery(h, xyz, pairs, count, dead_value)
 
-    def _match_gallery(self, h, xyz, pairs):
+    def _match_gallery(self, h, xyz, pairs, count=None, dead_value=0.0):
         """Amortised matching (the reference's tracker use-case of forward_inference +
         match_forward_inference, ReIDNet.py:189-191, 444-462): every object is encoded ONCE, then any list
         of (i, j) combinations is scored.  h (M,C,N), xyz (M,N,3) from forward_inference / siamese_forward;
         pairs (P,2) integer tensor -> logits (P), identical to match_forward_inference(h[i], h[j], ...).
-        Stage-1 key/value state is computed once per object and shared by all its pairs."""
+        Stage-1 key/value state is computed once per object and shared by all its pairs.
+        count ((1,) int32 device tensor; None: every pair): only pairs[:count] are real, as in the fixed-shape list of
+        compare_pairs.  The pair launches read the count themselves and do no work for the rest (engine.AttnPlan live=:
+        nothing of a pair beyond count is read, its indices included); logits[:count] are bit for bit those of the un-gated
+        call, logits[count:] are dead_value exactly.  No host read: a captured graph follows the count from replay to
+        replay."""
         if self.match_type != "xcorr_eff" or self.combine != "point-cat" or self.pool_type != "both":
             raise NotImplementedError("match_gallery covers the xcorr_eff / point-cat / both matching head")
         h, xyz = h.contiguous(), xyz.contiguous()
@@ -519,8 +527,15 @@ class ReIDNet(nn.Module):
         # (pcr_attn_apply_pool_ok: the launch shape and the arithmetic decide, never the number of pairs)
         pooled_ok = p2.pool_ok(n_pts, n_pts)
         out = []
-        # the launches index clouds by a 16-bit grid dimension: at most 32 k pairs (64 k virtual clouds) per pass
-        chunk = 32000
+        chunk = self.GALLERY_CHUNK
+        if count is not None:
+            L.require_cuda(count)
+            if count.dtype != torch.int32 or count.numel() != 1:
+                raise L.PcrError("match_gallery: count must be a (1,) int32 device tensor")
+            if not (p1.live_ok() and p2.live_ok()):
+                raise L.PcrError("match_gallery: count= needs matching stages the gated launches cover "
+                                 "(pcr_attn_live_ok: d_model = 64 with 64-channel features)")
+            count = count.reshape(1).contiguous()
         for lo in range(0, pairs.shape[0], chunk):
             pc = pairs[lo:lo + chunk]
             n_pairs = pc.shape[0]
@@ -528,6 +543,10 @@ class ReIDNet(nn.Module):
             j = pc[:, 1].to(device=h.device, dtype=torch.int32)
             q_idx = torch.cat([i, j]).contiguous()        # virtual cloud b < P: object i queries object j ...
             k_idx = torch.cat([j, i]).contiguous()        # ... and b >= P: object j queries object i
+            if count is not None:
+                out.append(self._match_chunk_live(p1, p2, h, xyz, kv1, q_idx, k_idx, n_pairs, pooled_ok,
+                                                  (count, n_pairs, lo), dead_value))
+                continue
             s1 = p1.apply(h, None, kv1, n_pts, kv_index=k_idx, q_index=q_idx, n_out=2 * n_pairs)
             xyz_v = xyz.index_select(0, q_idx.long()).contiguous()
             partner = torch.cat([torch.arange(n_pairs, 2 * n_pairs, device=h.device, dtype=torch.int32),
@@ -544,15 +563,38 @@ class ReIDNet(nn.Module):
             return torch.empty(0, dtype=torch.float32, device=h.device)
         return out[0] if len(out) == 1 else torch.cat(out, dim=0)
 
+    def _match_chunk_live(self, p1, p2, h, xyz, kv1, q_idx, k_idx, n_pairs, pooled_ok, live, dead_value):
+        """one pass of _match_gallery over a chunk whose pairs from live = (count, period = n_pairs, offset = lo) on are
+        padding: the stage-1 apply, the stage-2 kv and apply and, on the un-pooled route, the head are gated"""
+        n_pts = h.shape[2]
+        count, _, lo = live
+        s1 = p1.apply(h, None, kv1, n_pts, kv_index=k_idx, q_index=q_idx, n_out=2 * n_pairs, live=live)
+        xyz_v = xyz.index_select(0, q_idx.long()).contiguous()
+        partner = torch.cat([torch.arange(n_pairs, 2 * n_pairs, device=h.device, dtype=torch.int32),
+                             torch.arange(0, n_pairs, device=h.device, dtype=torch.int32)])
+        kv2 = p2.kv(s1, xyz_v, live=live)
+        if not pooled_ok:
+            o = p2.apply(s1, None, kv2, n_pts, kv_index=partner, live=live)
+            return self._head(o.device).run(o, live=live, dead_value=dead_value)
+        # (the pooled rows of dead pairs are zeros: the row kernels read every row, and a row's logit depends on that row alone)
+        pl = p2.apply(s1, None, kv2, n_pts, kv_index=partner, pooled=True, live=live)
+        a, b2 = pl[:n_pairs], pl[n_pairs:]
+        feat = torch.cat([torch.maximum(a[:, 0], b2[:, 0]), (a[:, 1] + b2[:, 1]) / float(2 * n_pts)], dim=1)
+        logits = self._head_rows(feat)
+        alive = torch.arange(lo, lo + n_pairs, device=h.device, dtype=torch.int32) < count
+        return torch.where(alive, logits, logits.new_full((), float(dead_value)))
+
     def associate(self, track_feats, track_xyz, track_labels, track_lengths, det_feats, det_xyz, det_labels, det_lengths,
-                  min_points=2, num_classes=8, cap=None, **cost_args):
+                  min_points=2, num_classes=8, cap=None, live_only=False, **cost_args):
         """One frame of the reference tracker's association on the device (pcr_amd/associate.py): the class-gated pair
         list (get_labels_to_compare, tracking_point_reid.py:15-33), match_gallery over [tracks | detections], the
         augmented cost matrix (get_cost_mat_margin, tracking_association.py:22-53) and the linear assignment the
         reference hands to scipy (:141) -- no host read anywhere.  track_feats (T,C,N) / track_xyz (T,N,3) are the
         caller's stored track features, det_* what forward_inference returned for this frame's crops; lengths may be
         None (no length filter); cost_args go to association_cost (track_miss, det_new, dist, dist_max, dist_penalty,
-        fill).  -> dict(track_to_det (T,), det_to_track (D,) [-1 = none], pairs, count, logits, cost, info)."""
+        fill).  live_only: match_gallery scores the count real pairs of the list only (count=; logits[count:] are then 0.0
+        instead of the padding pairs' scores -- association_cost reads logits[:count], so everything else is bit-identical).
+        -> dict(track_to_det (T,), det_to_track (D,) [-1 = none], pairs, count, logits, cost, info)."""
         from pcr_amd import associate as A
         L.require_cuda(track_feats, track_xyz, det_feats, det_xyz)
         T, D = track_feats.shape[0], det_feats.shape[0]
@@ -566,7 +608,7 @@ class ReIDNet(nn.Module):
                         info=torch.zeros((1,), dtype=torch.int32, device=dev))
         gallery_pairs = torch.stack([pairs[:, 0], pairs[:, 1] + T], dim=1)       # detections follow the tracks
         logits = self.match_gallery(torch.cat([track_feats, det_feats], dim=0), torch.cat([track_xyz, det_xyz], dim=0),
-                                    gallery_pairs).contiguous()
+                                    gallery_pairs, count=count if live_only else None).contiguous()
         cost = A.association_cost(logits, pairs, count, T, D, **cost_args)
         col4row, row4col, info = A.linear_assignment(cost)
         c, r = col4row[0, :T], row4col[0, :D]
@@ -576,7 +618,7 @@ class ReIDNet(nn.Module):
 
     def track_step(self, bank, sweep, boxes, labels, scores, carry=None, carry_inv=None, min_points=2, num_classes=8,
                    cap=None, n=None, crop_args=None, born=None, kill=None, frame_limit=10, replace_all=False,
-                   reset_on_match=False, propagate=True, suppress_threshold=0.15, **cost_args):
+                   reset_on_match=False, propagate=True, suppress_threshold=0.15, live_only=False, **cost_args):
         """One whole tracker frame on the device without a host read (pcr_amd/tracks.py; INTEGRATION.md "2e. Track
         state"; the split-bf16 guard calibrates on the first batch of a weight version, as in every inference entry
         point: run a frame eagerly before capturing): the sweep (P, C >= 3) and this frame's boxes (M <= bank.max_dets, bank.box_width) with labels and
@@ -586,7 +628,8 @@ class ReIDNet(nn.Module):
         replacement, propagation by carry, previous frame -> current; born / kill are the learned decisions' masks) and
         bank.suppress (suppress_threshold None = no track NMS).  The detections are padded to bank.max_dets with label
         -1, which joins nothing.  crop_args go to crops_from_boxes, cost_args to association_cost (track_miss, det_new,
-        dist_max, dist_penalty, fill).  -> associate's dict (track_to_det (capacity,), det_to_track (max_dets,), pairs,
+        dist_max, dist_penalty, fill).  live_only: as in associate -- the match runs over the frame's real pairs instead of
+        capacity x max_dets of them.  -> associate's dict (track_to_det (capacity,), det_to_track (max_dets,), pairs,
         count, logits, cost, info) plus det_slot, det_id (max_dets,), bank_info (1,) = the newborns dropped for want of
         a free slot, dist, lengths."""
         from pcr_amd import associate as A
@@ -621,7 +664,8 @@ class ReIDNet(nn.Module):
         pairs, count = A.compare_pairs(bank.labels, labels, bank.lengths, lengths, min_points=min_points,
                                        num_classes=num_classes, cap=cap)
         gallery_pairs = torch.stack([pairs[:, 0], pairs[:, 1] + C], dim=1)       # detections follow the bank's rows
-        logits = self.match_gallery(bank.gallery, bank.gallery_xyz, gallery_pairs).contiguous()
+        logits = self.match_gallery(bank.gallery, bank.gallery_xyz, gallery_pairs,
+                                    count=count if live_only else None).contiguous()
         cost = A.association_cost(logits, pairs, count, C, D, dist=dist, **cost_args)
         col4row, row4col, info = A.linear_assignment(cost)
         c, r = col4row[0, :C], row4col[0, :D]

@@ -45,6 +45,7 @@ AttnParams = _block("AttnParams", """
     ptr kv_part wkv_bf wmlp0_bf_xpad pool_out""")
 HeadParams = _block("HeadParams", """
     int P C L groups; ptr o w1 w2 gn1_g gn1_b gn2_g gn2_b w_out b_out pooled logits w1t w2t""")
+LiveParams = _block("LiveParams", "ptr count; int period offset")      # pcr_live: the gate of the _live launches
 
 # ---- section C (pcr_tdense_fwd / _bwd, pcr_bn_fwd_fin / _bwd_fin, pcr_reduce_job, pcr_linattn, pcr_attn_tail / _head) ----
 _TFwd = _block("_TFwd", """
@@ -71,6 +72,7 @@ _AttnHeadP = _block("_AttnHeadP", """
 
 # the header's name of every block (what the layout test compiles against)
 BLOCKS = {"pcr_bank": BankParams, "pcr_store_tables": StoreTables, "pcr_sa_params": SaParams, "pcr_attn_params": AttnParams, "pcr_head_params": HeadParams,
+          "pcr_live": LiveParams,
           "pcr_tdense_fwd": _TFwd, "pcr_tdense_bwd": _TBwd, "pcr_bn_fwd_fin": _BnFwd, "pcr_bn_bwd_fin": _BnBwd,
           "pcr_reduce_job": _ReduceJob, "pcr_linattn": _LinAttnP, "pcr_attn_tail": _AttnTailP,
           "pcr_attn_head": _AttnHeadP}
@@ -194,7 +196,11 @@ SIGNATURES = {
     "pcr_attn_kv_f32": "s <AttnParams>S",
     "pcr_attn_apply_f32": "s <AttnParams>S",
     "pcr_attn_apply_pool_ok": "i <AttnParams>",
+    "pcr_attn_live_ok": "i <AttnParams>",
+    "pcr_attn_kv_live_f32": "s <AttnParams><LiveParams>S",
+    "pcr_attn_apply_live_f32": "s <AttnParams><LiveParams>S",
     "pcr_pool_head_f32": "s <HeadParams>S",
+    "pcr_pool_head_live_f32": "s <HeadParams><LiveParams>FS",
     "pcr_pool_both_f32": "s FFiiiS",
     "pcr_channel_max_f32": "s FFiiiiS",
     "pcr_dense_f32": "s FFFFFiiiiiS",

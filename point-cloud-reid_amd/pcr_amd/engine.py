@@ -11,7 +11,7 @@ import torch
 
 from . import _lib as L
 from ._lib import _p
-from .abi import AttnParams, HeadParams, SaParams
+from .abi import AttnParams, HeadParams, LiveParams, SaParams
 
 # Arithmetic of the MFMA-bound layers (include/pcr.h PCR_PREC_*):
 #   "f32"    f32-input MFMA, exact fmaf chains (the reference's arithmetic, 157 TFLOP/s peak);
@@ -401,6 +401,20 @@ class SaPlan:
         return out.transpose(1, 2) if out_point_major else out
 
 
+def _live_block(live):
+    """live = (count, period, offset) -> pcr_live: count a (1,) int32 device tensor (the pair count of a fixed-shape list,
+    read by the launch itself), cloud b is live iff b % period < clamp(count - offset, 0, period)"""
+    count, period, offset = live
+    L.require_cuda(count)
+    if count.dtype != torch.int32 or count.numel() < 1 or not count.is_contiguous():
+        raise L.PcrError("live: count must be a contiguous int32 device tensor of at least one element")
+    if int(period) < 1 or int(offset) < 0:
+        raise L.PcrError("live: period must be positive and offset non-negative, got %r, %r" % (period, offset))
+    lv = LiveParams()
+    lv.count, lv.period, lv.offset = _p(count), int(period), int(offset)
+    return lv
+
+
 class AttnPlan:
     """packed linear-attention block.  `m` exposes pos-MLP (name given), q/k/v/merge projections,
     mlp.{0,2}, norm1/norm2 as in the reference's Self_Attention / FP_SA / corss_attention."""
@@ -487,25 +501,44 @@ class AttnPlan:
         p.precision = PRECISIONS[PRECISION]
         return p
 
-    def kv(self, feat_k, xyz_k):
-        """key-side state of every cloud: (B, d*d + d) per-cloud images (reusable across many queries)"""
+    def live_ok(self):
+        """can kv(.., live=) / apply(.., live=) be honoured for this block (pcr_attn_live_ok: the shape decides, never the
+        batch)?"""
+        dummy = torch.empty(0)
+        p = self._params(1, 32, 32, dummy, None, dummy, None, dummy, dummy)
+        p.feat_q = p.feat_k = p.xyz_q = p.xyz_k = p.kv = p.out = 1        # (only tested against NULL)
+        return bool(L.load().pcr_attn_live_ok(ctypes.byref(p)))
+
+    def kv(self, feat_k, xyz_k, live=None, out=None):
+        """key-side state of every cloud: (B, d*d + d) per-cloud images (reusable across many queries).
+        live = (count, period, offset) (pcr_live; only where live_ok says so): dead clouds are neither read nor written --
+        their rows of the result hold whatever the buffer held.  out: the (B, d*d + d) buffer to write into."""
         L.require_cuda(feat_k, xyz_k)
         assert feat_k.is_contiguous() and xyz_k.is_contiguous() and feat_k.dtype == torch.float32
         B, c2, Sk = feat_k.shape
         assert c2 == self.c2
         lib = L.load()
-        kv = torch.empty((B, lib.pcr_attn_kv_floats(self.d)), dtype=torch.float32, device=feat_k.device)
+        if out is not None:
+            L.require_cuda(out)
+            assert out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == (B, lib.pcr_attn_kv_floats(self.d))
+        kv = out if out is not None else torch.empty((B, lib.pcr_attn_kv_floats(self.d)), dtype=torch.float32,
+                                                     device=feat_k.device)
         p = self._params(B, 1, Sk, feat_k, xyz_k, feat_k, xyz_k, kv, kv)
         d = self.d
         # token split (the library's suggestion for this launch shape): partial matrices + a fold launch
         ns = lib.pcr_attn_kv_splits(B, Sk, d) if KV_SPLITS is None else KV_SPLITS
+        if live is not None and ns > 1:
+            raise L.PcrError("a gated kv launch takes whole clouds (kv_splits = %d)" % ns)
         if ns > 1:
             part = torch.empty((B, ns, lib.pcr_attn_kv_floats(d)), dtype=torch.float32, device=feat_k.device)
             p.kv_splits, p.kv_part = ns, _p(part)
         kv_flops = 2.0 * B * Sk * (3 * d + d * c2 + 2 * c2 * d + d * d / self.nhead)   # reference's op count
         with _prof("attn_kv[d=%d,c2=%d,Sk=%d]" % (d, c2, Sk), kv_flops, 4.0 * B * (c2 * Sk + 3 * Sk + d * d + d),
                    arith="lib"):
-            L.run.pcr_attn_kv_f32(ctypes.byref(p), L.stream_ptr())
+            if live is not None:
+                L.run.pcr_attn_kv_live_f32(ctypes.byref(p), ctypes.byref(_live_block(live)), L.stream_ptr())
+            else:
+                L.run.pcr_attn_kv_f32(ctypes.byref(p), L.stream_ptr())
         kv._pcr_precision = PRECISION      # the per-cloud matrix is an image of this kind: apply() must match
         return kv
 
@@ -517,11 +550,14 @@ class AttnPlan:
         p.feat_q = p.feat_k = p.xyz_k = p.kv = p.out = 1        # (only tested against NULL)
         return bool(L.load().pcr_attn_apply_pool_ok(ctypes.byref(p)))
 
-    def apply(self, feat_q, xyz_q, kv, Sk, kv_index=None, q_index=None, n_out=None, pooled=False):
+    def apply(self, feat_q, xyz_q, kv, Sk, kv_index=None, q_index=None, n_out=None, pooled=False, live=None, out=None):
         """query side: n_out virtual clouds (default: one per query cloud); virtual cloud b takes its tokens
         from cloud q_index[b] (default b) and the key-side state kv[kv_index[b]] (default b).
         pooled (ABI 16; only where pool_ok says so): the block output is not written -- returns (B, 2, cout) = every
-        virtual cloud's per-channel [maximum | sum] over its Lq tokens"""
+        virtual cloud's per-channel [maximum | sum] over its Lq tokens.
+        live = (count, period, offset) (pcr_live; only where live_ok says so): dead virtual clouds are neither read (their
+        q_index / kv_index entries included) nor written; a pooled result then starts as zeros, because what follows reads
+        it in full, an un-pooled one holds whatever its buffer held.  out: the buffer to write into."""
         L.require_cuda(feat_q, kv)
         assert feat_q.is_contiguous() and feat_q.dtype == torch.float32 and (xyz_q is None or xyz_q.is_contiguous())
         Bq, c1, Lq = feat_q.shape
@@ -531,13 +567,19 @@ class AttnPlan:
             raise L.PcrError("attention state was built in %r mode and is applied in %r mode: the per-cloud matrix is "
                              "stored in the arithmetic's own layout" % (made, PRECISION))
         B = n_out if n_out is not None else Bq
+        shape = (B, 2, self.cout) if pooled else (B, self.cfinal or self.cout, Lq)
+        if out is not None:
+            L.require_cuda(out)
+            assert out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == shape
         if pooled:
-            out = torch.empty((B, 2, self.cout), dtype=torch.float32, device=feat_q.device)
+            if out is None:
+                out = (torch.zeros if live is not None else torch.empty)(shape, dtype=torch.float32, device=feat_q.device)
             p = self._params(B, Lq, Sk, feat_q, xyz_q, feat_q, xyz_q if xyz_q is not None else feat_q, kv, None,
                              kv_index, q_index)
             p.pool_out = _p(out)
         else:
-            out = torch.empty((B, self.cfinal or self.cout, Lq), dtype=torch.float32, device=feat_q.device)
+            if out is None:
+                out = torch.empty(shape, dtype=torch.float32, device=feat_q.device)
             p = self._params(B, Lq, Sk, feat_q, xyz_q, feat_q, xyz_q if xyz_q is not None else feat_q, kv, out,
                              kv_index, q_index)
         d = self.d
@@ -545,7 +587,10 @@ class AttnPlan:
                                    + self.cout * self.cfinal + (self.q_pos * (3 * d + d * c1)))
         with _prof("attn_apply[d=%d,c1=%d,out=%d,Lq=%d%s]" % (d, c1, self.cfinal or self.cout, Lq, ",pooled" if pooled else ""),
                    ap_flops, 4.0 * B * (c1 * Lq + d * d + d + (2 if pooled else Lq) * (self.cfinal or self.cout)), arith="lib"):
-            L.run.pcr_attn_apply_f32(ctypes.byref(p), L.stream_ptr())
+            if live is not None:
+                L.run.pcr_attn_apply_live_f32(ctypes.byref(p), ctypes.byref(_live_block(live)), L.stream_ptr())
+            else:
+                L.run.pcr_attn_apply_f32(ctypes.byref(p), L.stream_ptr())
         return out
 
     def run(self, feat_q, xyz_q, feat_k, xyz_k, kv_index=None):
@@ -571,8 +616,10 @@ class HeadPlan:
                       w1t=_dev32(linres.linear1.weight.detach().t().contiguous(), device),
                       w2t=_dev32(linres.linear2.weight.detach().t().contiguous(), device))
 
-    def run(self, o, want_pooled=False):
-        """o (2P, C, L): clouds p and p+P are pair p -> logits (P) [, pooled (P,2C)]"""
+    def run(self, o, want_pooled=False, live=None, dead_value=0.0):
+        """o (2P, C, L): clouds p and p+P are pair p -> logits (P) [, pooled (P,2C)]
+        live = (count, period, offset) (pcr_live, pairs in place of clouds): the clouds of a dead pair are not read, its logit
+        is dead_value and its pooled row zeros"""
         L.require_cuda(o)
         assert o.is_contiguous() and o.dtype == torch.float32
         twoP, C, Lp = o.shape
@@ -587,7 +634,11 @@ class HeadPlan:
             setattr(p, k, _p(v))
         p.pooled, p.logits = _p(pooled), _p(logits)
         with _prof("pool_head", 4.0 * P * (2 * C) ** 2, 4.0 * twoP * C * Lp):
-            L.run.pcr_pool_head_f32(ctypes.byref(p), L.stream_ptr())
+            if live is not None:
+                L.run.pcr_pool_head_live_f32(ctypes.byref(p), ctypes.byref(_live_block(live)),
+                                             ctypes.byref(ctypes.c_float(dead_value)), L.stream_ptr())
+            else:
+                L.run.pcr_pool_head_f32(ctypes.byref(p), L.stream_ptr())
         return (logits, pooled) if want_pooled else logits
 
 

@@ -520,6 +520,125 @@ int pcr_store_train_pairs_i32(const pcr_store_tables *tables, const int *items, 
                               const long long *seed, int *rows, int *labels, int *ids, int *info, int B,
                               pcr_stream_t stream);
 
+/* ------------------------------------------------------------ A7. ground truth -------- */
+
+/* Scoring the tracker of A3 - A5 against ground-truth tracks, the last host-side half of the reference's
+ * VirtualTracker.step (models/trackers/deprecated/): get_iou_idx (virtual_tracker.py:186-229: detections matched to
+ * ground-truth boxes by centre distance or IoU plus a +10000 class mask, scipy on a host copy, a threshold through
+ * torch.where), TrackingDecisionModifier.__call__ (tracking_decision_modifier.py:62-129 with the four rules at :35-59: the
+ * frame's TRUE decisions, np.intersect1d on host copies), get_stats (:132-172) with get_scene_metrics
+ * (virtual_tracker.py:1008-1017), update_gt_track_mapping (:297-347) and teacher forcing in mode 'gt' (:620-622,
+ * tracking_decision_modifier.py:200-208).  Here: a cost launch, pcr_lsa_f32 of A3 over it as a (1, D, G) problem, one
+ * launch before pcr_bank_plan_i32 and one after the update and the track NMS.  Fixed shapes, no host read, no allocation,
+ * no float atomic (integer sums and minima in LDS only: their result does not depend on the order); the same bits on
+ * every run; every loop is bounded by an integer count.  Pointers are checked against NULL only.
+ * pcr_truth_ok: 1 <= C <= PCR_ASSOC_MAX_OBJECTS, 0 <= D, G <= PCR_LSA_MAX, W == 7 or 9, 1 <= gt_cap <= PCR_TRUTH_MAX_IDS.
+ *
+ * Validity.  A detection d is VALID iff det_labels[d] >= 0; a ground-truth box j iff gt_labels[j] >= 0 and gt_ids[j] lies
+ * in [0, gt_cap).  Anything else is PADDING.  (This rule is ours: the reference has no padding, and its class mask gives
+ * two entries of equal label -1 a zero.)  Padding takes part in the assignment the way an entry of another class does in
+ * the reference: a padding row that has to take a real column pays 10000 plus its distance to it, and which columns are
+ * left to such rows is part of the optimum, so it can move real pairs.  Where a frame holds as many valid detections as
+ * valid ground-truth boxes and D == G, the padding rows take the padding columns (zero boxes: 10000 flat) and the real
+ * boxes are assigned as in the unpadded problem; so are they with an IoU base, which lies in [-1, 0].  With D == G and
+ * fewer valid detections than valid ground-truth boxes -- any frame with a missed object -- it does happen: a detection at
+ * (10, 0), its object at (9.7, 0) and a missed object at (20, 0) cost 10019.7 with the detection on the missed object
+ * and the padding row on its own, against 10020.3 for the true pair.  It is avoidable by the shape: with
+ * G >= D + (the most valid ground-truth boxes of a frame) every row has a padding column of its own at 10000 flat and no
+ * padding row takes a real column (with the roles swapped where D > G).  What then remains is the reference's own: a valid
+ * detection without a partner of its class still pays 10000 plus a distance somewhere.
+ *
+ * pcr_truth_cost_f32: det_boxes (D,W), det_labels (D), gt_boxes (G,W), gt_labels / gt_ids (G), iou (D,G) or NULL ->
+ * cost (D,G), EVERY element written:
+ *   base = sqrtf(dx * dx + dy * dy), dx = det_boxes[d][0] - gt_boxes[g][0], dy likewise with [1], for iou == NULL
+ *          (Center2DRange, :31-42, in the direct form as pcr_bank_dist_f32: the reference's cdist may take the matmul
+ *          form), and base = -iou[d*G + g] otherwise;
+ *   cost = base + m, m = 10000.0f where the labels differ or either side is padding, 0.0f otherwise; each operation
+ *          rounded to binary32, nothing contracted, IEEE square root.
+ * Nothing to do: D == 0 or G == 0.
+ *
+ * pcr_truth_decide_i32: one launch (one workgroup) over the bank's state as it is BEFORE pcr_bank_plan_i32.  Inputs: ids
+ * (C), the book slot_gt / slot_tte (C): the ground-truth track id a slot's track was last seen as (-1: a false positive
+ * or none) and its time to end; col4row (D), row4col (G), info (1) of the assignment over cost (D,G); thresh (device, 1
+ * float: a replayed graph re-reads it); gt_labels / gt_ids / gt_tte (G); det_labels (D); the tracker's own track_to_det
+ * (C), det_to_track (D) and the optional born (D) / kill (C) with pcr_bank_plan_i32's meaning.  The D-sized pointers may
+ * be NULL when D == 0, the G-sized ones when G == 0.  The result is DEFINED by these rules (tests/truth_ref.py::decide
+ * restates them; the kernel equals it bit for bit):
+ *   det_gt (D)       det_gt[d] = j iff info[0] == 0, j = col4row[d] lies in [0, G), row4col[j] == d (nothing is
+ *                    trusted), d and j are valid and of one label, and cost[d*G + j] < thresh[0], strictly (get_iou_idx's
+ *                    `<`); -1 otherwise.  Such a d is a TRUE POSITIVE and g(d) = gt_ids[det_gt[d]] its track.
+ *   true_t2d (C), true_d2t (D)   slot s HOLDS id g iff s is active, slot_gt[s] == g >= 0 and no lower slot does (np.
+ *                    intersect1d's first occurrence; the reference cannot hold one id twice, a bank driven by a learned
+ *                    head can).  The holder of g(d) and the LOWEST true positive d of that id belong together
+ *                    (true_t2d[s] = d, true_d2t[d] = s); everything else is -1.
+ *   det_truth (D)    -1 padding; 0 match (true_d2t >= 0); 1 newborn: any other true positive; 2 false positive: a valid
+ *                    detection that is no true positive.
+ *   track_truth (C)  -1 a free slot; 0 match (true_t2d >= 0); 2 false positive: slot_gt[s] < 0 or slot_tte[s] < 0;
+ *                    1 false negative: the rest.  The classes are exclusive, in the order match, false positive, false
+ *                    negative (the reference's sets can overlap only for a track whose stored tte contradicts its ground
+ *                    truth: matched by id while its tte says the track has ended).
+ *   the tracker's own decisions, by pcr_bank_plan_i32's rules: a slot is killed, matched (the two maps agree) or missed;
+ *                    a valid detection is matched, else born (born == NULL or born[d] != 0; a birth that the plan later
+ *                    drops for want of a slot still counts), else rejected.
+ *   stats            for kind k of PCR_TRUTH_DET_MATCH .. PCR_TRUTH_TRACK_FP, with the true set / the tracker's set:
+ *                    match (true_d2t >= 0 / matched), newborn (det_truth 1 / born), det false positive (det_truth 2 /
+ *                    rejected), track false negative (track_truth 1 / missed), track false positive (track_truth 2 /
+ *                    killed): stats[3k] += |true| (gt), stats[3k+1] += |both| (correct; for the match kind the (slot,
+ *                    detection) PAIRS in both), stats[3k+2] += |tracker's| (num_pred); PCR_TRUTH_TOTAL_GT / _CORRECT add
+ *                    up gt and correct over the kinds (get_stats).  skip_empty != 0 keeps the reference's quirk: a kind
+ *                    whose true set is empty in a frame adds nothing that frame, num_pred included (:139-140).
+ * Teacher forcing in mode 'gt' needs no entry of its own: true_t2d / true_d2t, det_truth == 1 and track_truth == 2 are
+ * pcr_bank_plan_i32's track_to_det / det_to_track, born and kill.  forced != 0 says that these are the decisions the
+ * frame applies: the tracker's sets ARE the true sets then (track_to_det, det_to_track, born and kill are not read and
+ * may be NULL), so every kind counts gt == correct == num_pred.  (The reference scores the head's own decisions in
+ * both modes; forced == 0 does.)
+ *
+ * pcr_truth_record_i32: one launch (one workgroup) AFTER the update and the track NMS.  ids (C) are read as they are NOW;
+ * track_truth tells which slots were active before the frame; det_slot / det_id (D) are the plan's, det_gt decide's (an
+ * entry outside [0, G), or whose ground-truth box is padding, counts as -1).
+ *   the book   (update_gt_track_mapping) per slot s, in this order: if track_truth[s] >= 0: slot_tte[s] -= 1; if a
+ *              detection d has det_slot[d] == s (the lowest such d): (slot_gt, slot_tte)[s] = (g(d), gt_tte[det_gt[d]])
+ *              for a true positive and (-1, -1) otherwise; if ids[s] < 0: (-1, -1), so that stale truth cannot reach the
+ *              slot's next occupant.
+ *   MOT        (an addition: the reference keeps none) stats[PCR_TRUTH_FRAMES] += 1; GT_TOTAL += the valid ground-truth
+ *              boxes; TP += the true positives; FP += the valid detections that are none; FN += the valid ground-truth
+ *              boxes that are no true positive's; for a true positive d with g = g(d) and i = det_id[d]: if i < 0:
+ *              UNTRACKED += 1; and, for the lowest true positive of g only (ids are distinct in a sane frame): if
+ *              gt_last[g] >= 0 and gt_last[g] != i: SWITCHES += 1; then gt_last[g] = i.  gt_last (gt_cap) starts at -1. */
+#define PCR_TRUTH_MAX_IDS 65536
+#define PCR_TRUTH_DET_MATCH 0
+#define PCR_TRUTH_DET_NEWBORN 1
+#define PCR_TRUTH_DET_FP 2
+#define PCR_TRUTH_TRACK_FN 3
+#define PCR_TRUTH_TRACK_FP 4
+#define PCR_TRUTH_TOTAL_GT 15
+#define PCR_TRUTH_TOTAL_CORRECT 16
+#define PCR_TRUTH_FRAMES 17
+#define PCR_TRUTH_GT_TOTAL 18
+#define PCR_TRUTH_TP 19
+#define PCR_TRUTH_FP 20
+#define PCR_TRUTH_FN 21
+#define PCR_TRUTH_SWITCHES 22
+#define PCR_TRUTH_UNTRACKED 23
+#define PCR_TRUTH_STATS 24
+typedef struct pcr_truth {
+  int C, D, G, gt_cap, skip_empty, forced;
+  const int *ids;                                            /* the bank's (C) */
+  int *slot_gt, *slot_tte, *gt_last, *stats;                 /* the book: (C), (C), (gt_cap), (PCR_TRUTH_STATS) */
+  const int *col4row, *row4col, *info;                       /* the assignment over cost */
+  const float *cost, *thresh;
+  const int *gt_labels, *gt_ids, *gt_tte, *det_labels;       /* the frame */
+  const int *track_to_det, *det_to_track, *born, *kill;      /* the tracker's own decisions */
+  int *det_gt, *true_t2d, *true_d2t, *det_truth, *track_truth;   /* decide writes them, record reads det_gt, track_truth */
+  const int *det_slot, *det_id;                              /* record: the plan's */
+} pcr_truth;
+int pcr_truth_ok(int C, int D, int G, int W, int gt_cap);
+int pcr_truth_cost_f32(const float *det_boxes, const int *det_labels, const float *gt_boxes, const int *gt_labels,
+                       const int *gt_ids, const float *iou, float *cost, int D, int G, int W, int gt_cap,
+                       pcr_stream_t stream);
+int pcr_truth_decide_i32(const pcr_truth *p, pcr_stream_t stream);
+int pcr_truth_record_i32(const pcr_truth *p, pcr_stream_t stream);
+
 /* ------------------------------------------------- B. fused model kernels ------------ */
 
 /* Neighbour search of the "Point-Transformer" set-abstraction layers: centres are the first S

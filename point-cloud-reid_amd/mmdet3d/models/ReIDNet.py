@@ -618,7 +618,8 @@ class ReIDNet(nn.Module):
 
     def track_step(self, bank, sweep, boxes, labels, scores, carry=None, carry_inv=None, min_points=2, num_classes=8,
                    cap=None, n=None, crop_args=None, born=None, kill=None, frame_limit=10, replace_all=False,
-                   reset_on_match=False, propagate=True, suppress_threshold=0.15, live_only=False, **cost_args):
+                   reset_on_match=False, propagate=True, suppress_threshold=0.15, live_only=False, truth=None,
+                   force_truth=False, **cost_args):
         """One whole tracker frame on the device without a host read (pcr_amd/tracks.py; INTEGRATION.md "2e. Track
         state"; the split-bf16 guard calibrates on the first batch of a weight version, as in every inference entry
         point: run a frame eagerly before capturing): the sweep (P, C >= 3) and this frame's boxes (M <= bank.max_dets, bank.box_width) with labels and
@@ -631,9 +632,25 @@ class ReIDNet(nn.Module):
         dist_max, dist_penalty, fill).  live_only: as in associate -- the match runs over the frame's real pairs instead of
         capacity x max_dets of them.  -> associate's dict (track_to_det (capacity,), det_to_track (max_dets,), pairs,
         count, logits, cost, info) plus det_slot, det_id (max_dets,), bank_info (1,) = the newborns dropped for want of
-        a free slot, dist, lengths."""
+        a free slot, dist, lengths.
+
+        truth = dict(book= a pcr_amd.truth.TruthBook over this bank, boxes= (G <= book.max_gt, bank.box_width), labels=, ids=,
+        tte= (G,)) scores the frame against ground-truth tracks (INTEGRATION.md "2g. Ground truth"): book.match and
+        book.decide run between the assignment and bank.update, book.record after bank.suppress, and the dict gains det_gt,
+        true_det_to_track, det_truth (max_dets,), true_track_to_det, track_truth (capacity,).  force_truth: the true
+        association drives bank.update in place of the tracker's own, det_truth == 1 as born and track_truth == 2 as
+        kill (the reference's teacher forcing in mode 'gt': the upper bound a matching head is compared against), and
+        the book's decision counters score those applied decisions; the returned track_to_det / det_to_track stay the
+        tracker's own.  Without truth= nothing new is launched."""
         from pcr_amd import associate as A
         from pcr_amd import tracks as TR
+        if truth is None and force_truth:
+            raise L.PcrError("track_step: force_truth needs truth=")
+        if truth is not None:
+            from pcr_amd import truth as TU
+            book = truth.get("book") if isinstance(truth, dict) else None
+            if not isinstance(book, TU.TruthBook) or book.bank is not bank:
+                raise L.PcrError("track_step: truth['book'] must be a pcr_amd.truth.TruthBook made over this bank")
         if not isinstance(bank, TR.TrackBank):
             raise L.PcrError("track_step: bank must be a pcr_amd.tracks.TrackBank")
         L.require_cuda(sweep, boxes, labels, scores)
@@ -671,13 +688,21 @@ class ReIDNet(nn.Module):
         c, r = col4row[0, :C], row4col[0, :D]
         t2d = torch.where(c < D, c, torch.full_like(c, -1))
         d2t = torch.where(r < C, r, torch.full_like(r, -1))
+        decisions, truth_out = (t2d, d2t), {}
+        if truth is not None:
+            book.match(boxes, labels, truth)
+            truth_out = book.decide(decisions, labels, born=born, kill=kill, forced=force_truth)
+            if force_truth:
+                decisions, born, kill = book.forced()
         det_slot, det_id, bank_info = bank.update(
-            (t2d, d2t), dict(labels=labels, lengths=lengths, boxes=boxes, scores=scores), born=born, kill=kill, carry=carry,
+            decisions, dict(labels=labels, lengths=lengths, boxes=boxes, scores=scores), born=born, kill=kill, carry=carry,
             frame_limit=frame_limit, replace_all=replace_all, reset_on_match=reset_on_match, propagate=propagate)
         if suppress_threshold is not None:
             bank.suppress(suppress_threshold)
+        if truth is not None:
+            book.record(det_slot, det_id)
         return dict(track_to_det=t2d, det_to_track=d2t, pairs=pairs, count=count, logits=logits, cost=cost, info=info,
-                    det_slot=det_slot, det_id=det_id, bank_info=bank_info, dist=dist, lengths=lengths)
+                    det_slot=det_slot, det_id=det_id, bank_info=bank_info, dist=dist, lengths=lengths, **truth_out)
 
     def get_match_supervision(self, h1, h2, xyz1, xyz2, id_1, id_2):
         return h1, h2, xyz1, xyz2, (id_1 == id_2).float()

@@ -126,6 +126,25 @@ def require_i32(*tensors):
             raise PcrError("expected an int32 index tensor, got %s" % t.dtype)
 
 
+def as_vec(t, dtype, n, name, who="pcr_amd"):
+    """a contiguous (n,) device tensor of dtype torch.int32 / torch.float32 (int64 labels, lengths and masks are converted
+    on the device), or None; `who` prefixes the error"""
+    if t is None:
+        return None
+    if not isinstance(t, torch.Tensor):
+        raise PcrError("%s: %s must be a tensor" % (who, name))
+    require_cuda(t)
+    if dtype is torch.int32:
+        if t.dtype == torch.int64:
+            t = t.to(torch.int32)
+        require_i32(t)
+    else:
+        require_f32(t)
+    if t.shape != (n,):
+        raise PcrError("%s: %s must be (%d,), got %s" % (who, name, n, tuple(t.shape)))
+    return t.contiguous()
+
+
 def require_default_eps(*norms):
     """GroupNorm / LayerNorm kernels use eps = 1e-5 (every norm layer of the ReID configs): anything else is refused
     rather than silently computed with the wrong constant"""

@@ -29,6 +29,12 @@ BankParams = _block("BankParams", """
     ptr lengths boxes scores labels ids steps misses next_id info;
     ptr track_to_det det_to_track det_labels det_lengths det_boxes det_scores born kill carry; ptr src det_slot det_id""")
 
+# ---- section A7 (pcr_truth) ----
+TruthParams = _block("TruthParams", """
+    int C D G gt_cap skip_empty forced; ptr ids slot_gt slot_tte gt_last stats col4row row4col info cost thresh;
+    ptr gt_labels gt_ids gt_tte det_labels track_to_det det_to_track born kill;
+    ptr det_gt true_t2d true_d2t det_truth track_truth det_slot det_id""")
+
 # ---- section A6 (pcr_store_tables) ----
 StoreTables = _block("StoreTables", """
     int num_objects num_classes; ptr obj_cls obj_fp obj_id nums_off nums_rows bucket_off bucket_rows pool_off pool_objs""")
@@ -71,7 +77,7 @@ _AttnHeadP = _block("_AttnHeadP", """
     int precision fwd_precision""")
 
 # the header's name of every block (what the layout test compiles against)
-BLOCKS = {"pcr_bank": BankParams, "pcr_store_tables": StoreTables, "pcr_sa_params": SaParams, "pcr_attn_params": AttnParams, "pcr_head_params": HeadParams,
+BLOCKS = {"pcr_bank": BankParams, "pcr_truth": TruthParams, "pcr_store_tables": StoreTables, "pcr_sa_params": SaParams, "pcr_attn_params": AttnParams, "pcr_head_params": HeadParams,
           "pcr_live": LiveParams,
           "pcr_tdense_fwd": _TFwd, "pcr_tdense_bwd": _TBwd, "pcr_bn_fwd_fin": _BnFwd, "pcr_bn_bwd_fin": _BnBwd,
           "pcr_reduce_job": _ReduceJob, "pcr_linattn": _LinAttnP, "pcr_attn_tail": _AttnTailP,
@@ -175,6 +181,11 @@ SIGNATURES = {
     # A6. crop store
     "pcr_store_gather_f32": "s FPiIIIPFIIiiS",
     "pcr_store_train_pairs_i32": "s <StoreTables>IIIPIIIIiS",
+    # A7. ground truth
+    "pcr_truth_ok": "i iiiii",
+    "pcr_truth_cost_f32": "s FIFIIFFiiiiS",
+    "pcr_truth_decide_i32": "s <TruthParams>S",
+    "pcr_truth_record_i32": "s <TruthParams>S",
     # B. fused model kernels
     "pcr_knn_prefix_f32": "s FIiiiiS",
     "pcr_knn_prefix2_f32": "s FIIiiiiiiS",

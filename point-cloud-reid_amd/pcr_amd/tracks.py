@@ -30,18 +30,7 @@ def bank_ok(C, D, W=9, feat_floats=0, xyz_floats=0):
 
 def _vec(t, dtype, n, name):
     """a contiguous (n,) device tensor of dtype (int64 labels / lengths are converted on the device), or None"""
-    if t is None:
-        return None
-    _require(isinstance(t, torch.Tensor), "%s must be a tensor" % name)
-    L.require_cuda(t)
-    if dtype is torch.int32:
-        if t.dtype == torch.int64:
-            t = t.to(torch.int32)
-        L.require_i32(t)
-    else:
-        L.require_f32(t)
-    _require(t.shape == (n,), "%s must be (%d,), got %s" % (name, n, tuple(t.shape)))
-    return t.contiguous()
+    return L.as_vec(t, dtype, n, name, who="pcr_amd.tracks")
 
 
 def _affine(t, name):

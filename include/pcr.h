@@ -1079,7 +1079,10 @@ int pcr_tdense_fwd_pooled(const pcr_tdense_fwd *p);
  * Outputs (each optional): dx / dx2 = W^T dy masked by f(x) > 0 when in_relu (wpT = packed W^T); dstats = partials
  * [groups][2][ceil32(cin1)] of sum dx and sum dx * (raw x) for the next BatchNorm backward (iinv = 1 / isc);
  * dwp = partials [groups][ceil32(cout)][ceil32(cin)] of dy f(x)^T, dbp = partials [groups][ceil32(cout)] of sum dy
- * (reduce with pcr_reduce_parts_f32).  cout <= 384, cin1 + cin2 <= 288. */
+ * (reduce with pcr_reduce_parts_f32).  cout <= 384, cin1 + cin2 <= 288, and dy and the forward input of a 64-token tile
+ * must fit the LDS together: ((max(ceil32(cout), ceil32(cin)) + ceil32(cin)) * 65 + 3 cout + 3 cin1) * 4 <= 160 KiB with
+ * cin = cin1 + cin2 -- (256, 288), (288, 256) and (384, 192) are taken, (320, 288), (352, 256) and (384, 224) are not.  A
+ * shape outside returns PCR_ERR_INVALID before anything is launched (pcr_amd.train_ops.dense tiles such layers). */
 typedef struct pcr_tdense_bwd {
   int B, cin1, cin2, cout, L;
   const float *g, *y;

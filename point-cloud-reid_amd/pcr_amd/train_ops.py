@@ -459,16 +459,34 @@ class TDense(Function):
         return (r.get("dx"), r.get("dx2"), r.get("dW"), r.get("db") if has_bias else None, g_res, None)
 
 
-# pcr_tdense_{fwd,bwd}_f32 take up to 384 output rows and 288 input rows per launch (the backward keeps dy and the forward
-# input of a 64-token tile in LDS together).  Wider layers -- the 256-channel attention blocks and 512-row feed-forward /
-# table layers of the mul = 2 Point-Transformer -- run as a grid of launches: output rows in chunks, input rows in chunks
-# chained through the launch's residual input; autograd sees ordinary Functions, so the backward tiles the same way.
+# pcr_tdense_{fwd,bwd}_f32 take up to 384 output rows and 288 input rows per launch, and the backward less than that
+# rectangle: it keeps dy and the forward input of a 64-token tile in LDS together (`bwd_fits`, the rule of include/pcr.h),
+# which excludes the corner from (384, 224) / (320, 288) on.  Wider layers -- the 256-channel attention blocks and 512-row
+# feed-forward / table layers of the mul = 2 Point-Transformer -- and the layers of that corner run as a grid of launches:
+# output rows in chunks, input rows in chunks chained through the launch's residual input; autograd sees ordinary
+# Functions, so the backward tiles the same way.
 _MAX_COUT, _MAX_CIN, _CHUNK = 384, 288, 256
+_BWD_LDS, _TILE_PITCH = 160 * 1024, 65
+
+
+def bwd_fits(cout, cin, cin1):
+    """whether pcr_tdense_bwd_f32 takes a (cout, cin = cin1 + cin2) layer in ONE launch: its LDS rule
+    ((max(ceil32(cout), ceil32(cin)) + ceil32(cin)) 65 + 3 cout + 3 cin1) 4 <= 160 KiB inside cout <= 384, cin <= 288"""
+    coutP, cinP = _c32(cout), _c32(cin)
+    return cout <= _MAX_COUT and cin <= _MAX_CIN and \
+        ((max(coutP, cinP) + cinP) * _TILE_PITCH + 3 * cout + 3 * cin1) * 4 <= _BWD_LDS
+
+
+def _trains(*tensors):
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
 
 
 def dense(x, W, bias=None, x2=None, res=None, relu=False):
     cout, cin = W.shape
-    if cout <= _MAX_COUT and cin <= _MAX_CIN and not (relu and res is not None):
+    # (the shapes the backward takes too -- every layer of the models -- pay a few integer operations here; a forward
+    # that no backward will follow needs the forward's limits only)
+    if cout <= _MAX_COUT and cin <= _MAX_CIN and not (relu and res is not None) and \
+            (bwd_fits(cout, cin, x.shape[1]) or not _trains(x, x2, W, bias, res)):
         return TDense.apply(x, x2, W, bias, res, relu)
     segs = [x] if x2 is None else [x, x2]             # input = the channel concatenation of the segments
     pieces, c0 = [], 0                                # (tensor, first column of W)

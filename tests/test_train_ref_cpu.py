@@ -1,12 +1,14 @@
 """CPU: the float64 references of tests/train_ref.py against torch.nn / torch.autograd in float64 (1e-12 on tie-free
 inputs), their first-index rule on constructed exact ties, and -- for every parametrised input of
 test_gpu_train_pointwise_ops.py, imported from there so both files share one table -- that conditioning terminates
-with ZERO marginal decisions.  The device tests' inputs are thereby known to be usable before a GPU is involved."""
+with ZERO marginal decisions.  The device tests' inputs are thereby known to be usable before a GPU is involved.  The
+same for the grouped-MLP launches and the tables of test_gpu_train_sa_ops.py, with the cap on what conditioning may move."""
 import pytest
 import torch
 import torch.nn.functional as F
 
 import test_gpu_train_pointwise_ops as G
+import test_gpu_train_sa_ops as S
 import train_ref as R
 
 F64 = torch.float64
@@ -191,3 +193,135 @@ def test_planted_pooling_inputs_hold_the_edges_they_claim():
     for B, C, Ln, W in G.CMAX_CASES:
         x = G.make_cmax_input(B, C, Ln, W)["x"]
         assert tuple(x.shape) == (B, C, Ln) and x.is_contiguous()
+
+
+# ============================================================================ grouped-MLP launches (SaEdgeTrain) --
+@pytest.mark.parametrize("B,N,S_,K,D,c1", [(2, 12, 5, 4, 3, 6), (1, 9, 9, 9, 2, 5), (2, 7, 3, 1, 0, 4)])
+def test_sa_l1_ref_is_the_first_conv_on_the_materialised_rows(B, N, S_, K, D, c1):
+    """tables P = Wf f, Q = (Wc - Wf) f gathered by sa_l1_ref against the 1x1 conv [Wa | Wc | Wf] on the rows
+    [dxyz, f_c, f_i - f_c] (the reference graph of test_gpu_train_ops._torch_sa): value and every gradient"""
+    xyz, go = _randn(B, N, 3, seed=20, grad=False), _randn(B, c1, S_ * K, seed=21, grad=False)
+    idx = torch.randint(0, N, (B, S_, K), generator=torch.Generator().manual_seed(22), dtype=torch.int32)
+    w1, b1 = _randn(c1, 3 + 2 * D, seed=23), _randn(c1, seed=24)
+    feats = _randn(B, D, N, seed=25) if D else None
+    leaves = [w1, b1] + ([feats] if D else [])
+    tab = None
+    if D:
+        wc, wf = w1[:, 3:3 + D], w1[:, 3 + D:]
+        tab = torch.einsum("oc,bcn->bon", torch.cat([wf, wc - wf], dim=0), feats)
+    ours = R.sa_l1_ref(xyz, idx, tab, w1[:, :3], b1)
+    want = torch.einsum("oc,bcl->bol", w1, R.sa_l1_rows(xyz, feats, idx)) + b1.view(1, c1, 1)
+    assert _err(ours, want) < TIGHT
+    for a, b in zip(torch.autograd.grad(ours, leaves, go), torch.autograd.grad(want, leaves, go)):
+        assert _err(a, b) < TIGHT
+    if D:        # the centre half of the table takes no gradient beyond the S centres
+        t = tab.detach().requires_grad_(True)
+        dt, = torch.autograd.grad(R.sa_l1_ref(xyz, idx, t, w1[:, :3].detach(), b1.detach()), t, go)
+        assert bool((dt[:, c1:, S_:] == 0).all()) and (S_ == N or bool((dt[:, :c1] != 0).any()))
+
+
+@pytest.mark.parametrize("B,cin1,cin2,cout,Ln", [(3, 5, 0, 7, 11), (2, 4, 3, 6, 9), (1, 8, 0, 8, 33)])
+def test_tdense_ref_mode_1_is_autograd_through_batchnorm(B, cin1, cin2, cout, Ln):
+    """stats_ref -> bn_fwd_consts_ref -> (sums of the output gradient) -> bn_bwd_consts_ref -> tdense_dy(1) ->
+    tdense_bwd_ref, against autograd through W f(x) + b -> nn.BatchNorm1d in float64; and the running update"""
+    x, x2 = _randn(B, cin1, Ln, seed=30, grad=False), (_randn(B, cin2, Ln, seed=31) if cin2 else None)
+    W, b = _randn(cout, cin1 + cin2, seed=32), _randn(cout, seed=33)
+    isc, ish = _randn(cin1, seed=34, grad=False).abs() + 0.5, _randn(cin1, seed=35, grad=False)
+    gamma, beta, go = _randn(cout, seed=36), _randn(cout, seed=37), _randn(B, cout, Ln, seed=38, grad=False)
+    z0 = (isc.view(1, -1, 1) * x + ish.view(1, -1, 1)).requires_grad_(True)
+    f = torch.relu(z0)
+    y = torch.einsum("oc,bcl->bol", W, f if x2 is None else torch.cat([f, x2], dim=1)) + b.view(1, -1, 1)
+    bn = _layer(torch.nn.BatchNorm1d, cout, gamma, beta, 0.5)
+    rm0, rv0 = bn.running_mean.clone(), bn.running_var.clone()
+    leaves = [z0, W, b, bn.weight, bn.bias] + ([x2] if cin2 else [])
+    want = torch.autograd.grad(bn(y), leaves, go)
+    # the launches' route
+    y_ = R.tdense_ref(x, x2, W, b, isc, ish, True, None, False).detach()
+    assert _err(y_, y) < TIGHT
+    Rn = B * Ln
+    n = R.bn_fwd_consts_ref(R.stats_ref(y_).unsqueeze(0), cout, Rn, gamma.detach(), beta.detach(), G.EPS)
+    assert _err(R.running_update(rm0, n["mean"], 0.5), bn.running_mean) < TIGHT
+    assert _err(R.running_update(rv0, n["unbiased"], 0.5), bn.running_var) < TIGHT
+    sums = torch.stack([go.sum(dim=(0, 2)), (go * y_).sum(dim=(0, 2))]).unsqueeze(0)
+    k = R.bn_bwd_consts_ref(sums, cout, Rn, gamma.detach(), n["mean"], n["invstd"])
+    r = R.tdense_bwd_ref(R.tdense_dy(1, go, y_, k), x, None if x2 is None else x2.detach(), W.detach(), isc, ish, True)
+    ours = [r["dx"], r["dW"], r["db"], k["dgamma"], k["dbeta"]] + ([r["dx2"]] if cin2 else [])
+    for a, w in zip(ours, want):
+        assert _err(a, w) < 1e-11                 # (E[y^2] - mean^2 in float64: a few 1e-13 on these sizes)
+    # the shifted / centred records describe the same constants
+    off = n["mean"] + 0.3
+    ys = y_ - off.view(1, -1, 1)
+    n2 = R.bn_fwd_consts_ref(R.stats_ref(ys).unsqueeze(0), cout, Rn, gamma.detach(), beta.detach(), G.EPS, shift0=off)
+    sums2 = torch.stack([go.sum(dim=(0, 2)), (go * ys).sum(dim=(0, 2))]).unsqueeze(0)
+    k2 = R.bn_bwd_consts_ref(sums2, cout, Rn, gamma.detach(), n["mean"], n["invstd"], centre=off)
+    assert max(_err(n2[q], n[q]) for q in n) < TIGHT and max(_err(k2[q], k[q]) for q in k) < 1e-11
+
+
+def test_pool_and_route_refs_follow_the_first_index_rule():
+    y = torch.tensor([[[1.0, 3.0, 3.0, -1.0, -2.0, -1.0, 0.5, 0.5, 0.5]]], dtype=F64)             # C = 1, S = 3, K = 3
+    pooled, arg, ymax = R.sa_pool_ref(y, torch.tensor([1.0], dtype=F64), torch.tensor([0.0], dtype=F64), 3)
+    assert pooled.tolist() == [[[3.0, 0.0, 0.5]]] and arg.tolist() == [[[1, 0, 0]]] and ymax.tolist() == [[[3.0, -1.0, 0.5]]]
+    pooled, arg, ymax = R.sa_pool_ref(y, torch.tensor([-1.0], dtype=F64), torch.tensor([0.0], dtype=F64), 3)
+    assert pooled.tolist() == [[[0.0, 2.0, 0.0]]] and arg.tolist() == [[[0, 1, 0]]] and ymax[0, 0, 1] == -2.0
+    gp = torch.tensor([[[5.0, 6.0, 7.0]]], dtype=F64)
+    gz, s = R.pool_bwd_stats_ref(gp, pooled, ymax)
+    assert gz.tolist() == [[[0.0, 6.0, 0.0]]] and s.tolist() == [[6.0], [-12.0]]
+    assert R.route_ref(gp, arg, pooled, 3).tolist() == [[[0, 0, 0, 0, 6.0, 0, 0, 0, 0]]]
+    assert R.route_ref(gz, arg, None, 3).tolist() == [[[0, 0, 0, 0, 6.0, 0, 0, 0, 0]]]
+
+
+def _within_cap(inp):
+    assert inp["moved"] <= S.MOVE_CAP * inp["total"], (inp["moved"], inp["total"])
+
+
+@pytest.mark.parametrize("shape,flags", S.FWD_CASES + [((B, ci, 0, co, Ln), "bn") for B, ci, co, Ln in S.STREAM_FWD])
+def test_every_tdense_fwd_input_conditions_to_zero_marginal_decisions(shape, flags):
+    inp = S.make_fwd_input(shape, flags)
+    assert S.fwd_marginals(inp) == 0
+    _within_cap(inp)
+    assert all(t is None or (t.dtype == torch.float32 and bool(torch.isfinite(t).all())) for t in (inp["x"], inp["res"]))
+
+
+BWD_INPUTS = sorted({(s, m, K) for s, m, _ in S.BWD_CASES for K in (S.bwd_ks(s) if m == 3 else [0])} |
+                    {((B, c, 0, c, S_ * K), m, K if m == 3 else 0) for B, c, S_, K, m in S.STREAM_BWD})
+
+
+@pytest.mark.parametrize("shape,mode,K", BWD_INPUTS)
+def test_every_tdense_bwd_input_conditions_to_zero_marginal_decisions(shape, mode, K):
+    inp = S.make_bwd_input(shape, mode, K)
+    assert R.relu_arg_marginals(inp["x"], inp["isc"], inp["ish"]) == 0
+    _within_cap(inp)
+    if mode == 2:
+        assert int((inp["y"] == 0).sum()) > 0
+    if mode == 3:
+        assert inp["S"] * K == shape[4] and int(inp["argmax"].max()) < K
+
+
+@pytest.mark.parametrize("shape", S.POOL_CASES)
+def test_every_pooling_input_conditions_to_zero_marginal_decisions(shape):
+    B, C, S_, K = shape
+    inp = S.make_pool_input(shape)
+    assert R.pool_marginals(inp["y"], inp["scale"], inp["shift"], K) == (0, 0)
+    _within_cap(inp)
+    assert float(inp["scale"][0]) < 0 and float(inp["scale"][1]) == 0
+    # the planted edges are there: closed rows, open rows, and (K > 1) exact ties at the top of open rows
+    pooled, arg, _ = R.sa_pool_ref(inp["y"].to(F64), inp["scale"].to(F64), inp["shift"].to(F64), K)
+    assert bool((pooled > 0).any()) and bool((pooled == 0).any())
+    if K > 1:
+        z = inp["scale"].to(F64).view(1, C, 1, 1) * inp["y"].to(F64).view(B, C, S_, K) + inp["shift"].to(F64).view(1, C, 1, 1)
+        top = z.topk(2, dim=3).values
+        assert int(((top[..., 0] == top[..., 1]) & (top[..., 0] > 0)).sum()) > 0
+        assert int((arg == K - 1).sum()) > 0 and int((arg == 0).sum()) > 0
+
+
+@pytest.mark.parametrize("low,stress", S.COMP_CASES)
+def test_every_composition_input_conditions_to_zero_marginal_decisions(low, stress):
+    inp = S.make_comp_input(low, stress)
+    assert S.comp_marginals(inp) == 0
+    _within_cap(inp)
+    assert inp["changed"] <= (1 if low == "l1" else S.COMP_DENSE[1]) * inp["moved"]
+    ratio = S._ratio(S.comp_lower_ref(inp))
+    if stress != "none":
+        assert 9.0 < float(ratio.min()) and float(ratio.max()) < 11.5
+    else:
+        assert float(ratio.max()) < 5.0

@@ -268,6 +268,96 @@ int pcr_lsa_ok(int B, int R, int C);
 int pcr_lsa_f32(const float *cost, int *col4row, int *row4col, float *u, float *v, int *info, int B, int R, int C,
                 pcr_stream_t stream);
 
+/* Any set of decisions per side (additive to ABI 17).  The reference's tracker runs with dd detection decisions and td
+ * tracking decisions (VirtualTracker, trackers/deprecated/virtual_tracker.py:80-81, :114-117: by default dd = 2, td = 0);
+ * its matrix is (R, C) = (T + dd*D, D + td*T) (tracking_association.py:126).  The two entries below build that matrix by
+ * either of its cost rules and turn the solved assignment into per-object decisions and the born / kill masks
+ * pcr_bank_plan_i32 takes, as fixed-shape launches without a host read.  Both take a parameter block.
+ *
+ * pcr_assoc_multi_ok: 0 <= T, D; 0 <= dd, td <= PCR_ASSOC_MAX_DECISIONS; T + dd*D <= PCR_LSA_MAX and D + td*T <=
+ * PCR_LSA_MAX; 0 <= cap <= T*D.
+ *
+ * pcr_assoc_cost_multi_f32: logits (cap), pairs (cap,2), count (1), det_dec (dd,D), trk_dec (td,T) -> cost (R,C) row-major,
+ * EVERY element written.  NULL det_dec / trk_dec are zeros.  Layout (:22-53):
+ *   top-left (T,D)                               the listed pairs k < min(count[0], cap), fill elsewhere (a pair outside
+ *                                                [0,T) x [0,D) is skipped; the listed pairs must be distinct);
+ *   rows T + i*D .. T + (i+1)*D, columns < D     detection decision i on the diagonal, fill elsewhere;
+ *   columns D + j*T .. D + (j+1)*T, rows < T     tracking decision j on the diagonal, fill elsewhere;
+ *   every (i, j) block of the bottom right       the transpose of the top-left block, fill entries included (only when
+ *                                                dd > 0 and td > 0).
+ * kind PCR_COST_MARGIN: a listed pair holds -logits[k], plus dist_penalty where dist != NULL and dist[t*D + d] > dist_max;
+ *   the decision entries are det_dec / trk_dec as given (costs).  With dd == td == 1 the matrix is pcr_assoc_cost_f32's
+ *   bit for bit.
+ * kind PCR_COST_SOFTMAX (get_cost_mat_softmax, :56-98): logits and decision values are scores.  For track t, p_row is the
+ *   softmax over {the logits of its listed pairs} and {trk_dec[j][t]}; for detection d, p_col the softmax over {the logits
+ *   of its listed pairs} and {det_dec[i][d]}.  A listed pair holds -max(p_row, p_col), detection decision i of d holds
+ *   -p_col of that decision, tracking decision j of t holds -p_row of that decision.  dist must be NULL (the reference
+ *   applies no distance prior here) and reduce 0: anything else is PCR_ERR_INVALID.  DIFFERENCE from the reference: a pair
+ *   the class gate leaves out takes part in neither softmax and stays at fill (the reference's 10000-filled matrix would put
+ *   exp(10000) into the sums).
+ *   The arithmetic, written down: the listed logits are scattered into a dense (T,D) score image in ws (unlisted = -inf; a
+ *   listed logit of -inf therefore counts as unlisted).  One wave per track and one per detection reduces its set: lane l
+ *   takes the set's elements l, l + 64, ... in order (the pairs by ascending partner index, then the decisions by ascending
+ *   index); m = the maximum (NaN ignored); s = the sum of exp(x - m) over the lane's elements in that order, then over the
+ *   lanes by six butterfly exchanges (s += s of lane ^ 32, then 16, 8, 4, 2, 1), each term and each partial sum in binary64.  An
+ *   entry is p = exp(x - m) / s in binary64, rounded to binary32 once, after max(p_row, p_col).  No atomics; the same bits
+ *   on every run.  A NaN logit makes its track's and its detection's entries NaN (pcr_lsa_f32 then reports info 1).
+ * reduce = 1 (margin only; TrackingAssociatorMax.get_cost_mat_margin, :319-363): each side with at least one decision gets
+ *   ONE diagonal block holding the object's cheapest decision, min over the decisions, ties to the lowest decision index
+ *   (x < best, strict, starting from decision 0); the chosen index goes to det_choice (D) / trk_choice (T) (a side without
+ *   decisions leaves its choice array as it is).  The matrix is (T + [dd>0]*D, D + [td>0]*T); the bottom-right transpose
+ *   exists iff both sides have a decision.  Without reduce det_choice / trk_choice may be NULL and are not written.
+ * ws: device scratch of pcr_assoc_multi_ws_bytes(T, D, dd, td) bytes (the score image and the 2*(T + D) row / column
+ *   maxima and sums in binary64), used by the softmax kind only; may be NULL for margin.
+ * count is read on the device.  Nothing to do: R*C == 0.
+ *
+ * pcr_assoc_decode_i32: cost (R,C) as built above, col4row (R), row4col (C), solver_info (1, NULL = 0) of pcr_lsa_f32 ->
+ * track_to_det (T), det_to_track (D) (-1 = none), det_decision (D), track_decision (T), born (D), kill (T), info (4).  One
+ * workgroup; every loop is bounded by an integer count.  It restates tracking_association.py:146-245 in fixed shape:
+ *   void      an assigned entry (r, c) with cost[r][c] == fill is void: both sides become unassigned; info[1] counts them
+ *             (the reference prints and exits);
+ *   drop      only when td > 0: pairs with r >= T and c >= D are dropped;
+ *   repair    only when td > 0: for every track t ascending without a pair, the column of least cost[t][c] among the
+ *             columns no kept pair uses, ties to the lowest index; if there is none or that value == fill the track is
+ *             skipped, otherwise (t, c) is a pair and c is used; info[2] counts them.  Then for every detection d ascending
+ *             without a pair the same over the unused rows; info[3] counts them.  DIFFERENCE from the reference, which
+ *             picks for all forgotten tracks at once (:171-181) and can hand one detection to two tracks: here the picks
+ *             are sequential, and equal the reference's whenever its picks are distinct;
+ *   classify  det_decision[d]: 0 = matched to a track (det_to_track[d] = it), 1 + i = detection decision i (the row block
+ *             of d's pair; under reduce i = det_choice[d]), 1 + dd = unmatched.  track_decision[t] likewise with td, the
+ *             column block and trk_choice;
+ *   masks     born[d] = det_decision[d] == 1 + born_dec, all 0 when born_dec < 0; kill[t] = track_decision[t] ==
+ *             1 + kill_dec, all 0 when kill_dec < 0 (int32 0 / 1, the form pcr_bank_plan_i32 takes);
+ *   info[0]   the solver's info; when it is not 0 nothing is assigned: the maps are -1, every decision is "unmatched",
+ *             the masks 0, info[1..3] 0.
+ * Range as pcr_assoc_multi_ok(T, D, dd, td, 0).  Nothing to do: T + D == 0. */
+#define PCR_ASSOC_MAX_DECISIONS 4
+#define PCR_COST_MARGIN 0
+#define PCR_COST_SOFTMAX 1
+typedef struct pcr_assoc_multi {
+  int T, D, dd, td, cap;
+  int kind, reduce;
+  float dist_max, dist_penalty, fill;
+  const float *logits;
+  const int *pairs, *count;
+  const float *det_dec, *trk_dec, *dist;
+  void *ws;
+  float *cost;
+  int *det_choice, *trk_choice;
+} pcr_assoc_multi;
+typedef struct pcr_assoc_decode {
+  int T, D, dd, td;
+  int reduce, born_dec, kill_dec;
+  float fill;
+  const float *cost;
+  const int *col4row, *row4col, *solver_info, *det_choice, *trk_choice;
+  int *track_to_det, *det_to_track, *det_decision, *track_decision, *born, *kill, *info;
+} pcr_assoc_decode;
+int pcr_assoc_multi_ok(int T, int D, int dd, int td, int cap);
+int pcr_assoc_multi_ws_bytes(int T, int D, int dd, int td);
+int pcr_assoc_cost_multi_f32(const pcr_assoc_multi *p, pcr_stream_t stream);
+int pcr_assoc_decode_i32(const pcr_assoc_decode *p, pcr_stream_t stream);
+
 /* ------------------------------------------- A4. box overlap and suppression --------- */
 
 /* Overlap between bird's-eye-view boxes and the suppression of duplicates, the two steps of the tracker's frame that the

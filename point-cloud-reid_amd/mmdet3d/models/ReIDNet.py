@@ -584,8 +584,59 @@ class ReIDNet(nn.Module):
         alive = torch.arange(lo, lo + n_pairs, device=h.device, dtype=torch.int32) < count
         return torch.where(alive, logits, logits.new_full((), float(dead_value)))
 
+    @staticmethod
+    def _decision_set(decisions, T, D, cost_args, who, M=None):
+        """decisions=dict(detection=(names...), tracking=(names...), det_values=(dd, D) or None, track_values=(td, T) or
+        None, kind="margin", reduce=False) -> what _associate_decisions takes.  The names are sorted, as the reference sorts
+        them (trackers/deprecated/virtual_tracker.py:114-115), and the rows of det_values / track_values follow the sorted
+        order; None values are zeros.  det_values of width M < D (track_step's padding) are zero-padded."""
+        if not isinstance(decisions, dict) or set(decisions) - {"detection", "tracking", "det_values", "track_values", "kind",
+                                                                "reduce"}:
+            raise L.PcrError("%s: decisions must be dict(detection=, tracking=, det_values=, track_values=, kind=, reduce=)"
+                             % who)
+        if "track_miss" in cost_args or "det_new" in cost_args:
+            raise L.PcrError("%s: track_miss / det_new belong to the one-decision matrix; with decisions= the values are "
+                             "det_values / track_values" % who)
+        det_names, trk_names = sorted(decisions.get("detection", ())), sorted(decisions.get("tracking", ()))
+        dev = torch.device("cuda", torch.cuda.current_device())
+        values = []
+        for names, v, n, key in ((det_names, decisions.get("det_values"), D, "det_values"),
+                                 (trk_names, decisions.get("track_values"), T, "track_values")):
+            if v is None:
+                v = torch.zeros((len(names), n), dtype=torch.float32, device=dev)
+            L.require_cuda(v)
+            L.require_f32(v)
+            if key == "det_values" and M is not None and v.dim() == 2 and v.shape[1] == M and M < n:
+                v = torch.cat([v, v.new_zeros((v.shape[0], n - M))], dim=1)
+            if v.shape != (len(names), n):
+                raise L.PcrError("%s: decisions[%r] must be (%d, %d), got %s" % (who, key, len(names), n, tuple(v.shape)))
+            values.append(v.contiguous())
+        return dict(det_names=det_names, trk_names=trk_names, det_values=values[0], trk_values=values[1],
+                    kind=decisions.get("kind", "margin"), reduce=bool(decisions.get("reduce", False)),
+                    born=det_names.index("det_newborn") if "det_newborn" in det_names else -1,
+                    kill=trk_names.index("track_false_positive") if "track_false_positive" in trk_names else -1)
+
+    @staticmethod
+    def _associate_decisions(logits, pairs, count, T, D, ds, dist, cost_args):
+        """the matrix for the decision set ds, its assignment and the decode (pcr_amd/associate.py) -> the entries that
+        associate / track_step return"""
+        from pcr_amd import associate as A
+        dd, td = len(ds["det_names"]), len(ds["trk_names"])
+        R, C = A.multi_shape(T, D, dd, td, ds["reduce"])
+        if not L.load().pcr_lsa_ok(1, R, C):
+            raise L.PcrError("decisions: the (%d, %d) matrix is beyond linear_assignment (PCR_LSA_MAX)" % (R, C))
+        out = A.association_cost_multi(logits, pairs, count, T, D, ds["det_values"], ds["trk_values"], kind=ds["kind"],
+                                       reduce=ds["reduce"], dist=dist, **cost_args)
+        cost, choices = (out[0], (out[1], out[2])) if ds["reduce"] else (out, None)
+        assignment = A.linear_assignment(cost)
+        dec = A.decode_assignment(cost, assignment, T, D, dd, td, fill=cost_args.get("fill", 10000.0), choices=choices,
+                                  born_decision=ds["born"], kill_decision=ds["kill"])
+        return dict(track_to_det=dec["track_to_det"], det_to_track=dec["det_to_track"], cost=cost, info=assignment[2],
+                    det_decision=dec["det_decision"], track_decision=dec["track_decision"], born=dec["born"],
+                    kill=dec["kill"], decode_info=dec["info"])
+
     def associate(self, track_feats, track_xyz, track_labels, track_lengths, det_feats, det_xyz, det_labels, det_lengths,
-                  min_points=2, num_classes=8, cap=None, live_only=False, **cost_args):
+                  min_points=2, num_classes=8, cap=None, live_only=False, decisions=None, **cost_args):
         """One frame of the reference tracker's association on the device (pcr_amd/associate.py): the class-gated pair
         list (get_labels_to_compare, tracking_point_reid.py:15-33), match_gallery over [tracks | detections], the
         augmented cost matrix (get_cost_mat_margin, tracking_association.py:22-53) and the linear assignment the
@@ -594,13 +645,33 @@ class ReIDNet(nn.Module):
         None (no length filter); cost_args go to association_cost (track_miss, det_new, dist, dist_max, dist_penalty,
         fill).  live_only: match_gallery scores the count real pairs of the list only (count=; logits[count:] are then 0.0
         instead of the padding pairs' scores -- association_cost reads logits[:count], so everything else is bit-identical).
-        -> dict(track_to_det (T,), det_to_track (D,) [-1 = none], pairs, count, logits, cost, info)."""
+        -> dict(track_to_det (T,), det_to_track (D,) [-1 = none], pairs, count, logits, cost, info).
+
+        decisions=dict(detection=(names...), tracking=(names...), det_values=(dd, D) or None, track_values=(td, T) or None,
+        kind="margin" | "softmax", reduce=False) runs the reference's tracker with any set of decisions:
+        association_cost_multi builds the (T + dd*D, D + td*T) matrix (cost_args: dist, dist_max, dist_penalty, fill; no
+        dist with the softmax kind), decode_assignment turns the assignment into decisions, and the dict gains det_decision
+        (D,), track_decision (T,) [0 = matched, 1 + k = decision k of the SORTED names, 1 + dd / 1 + td = unmatched], born
+        (D,) = the detections that took 'det_newborn', kill (T,) = the tracks that took 'track_false_positive' (all zero when
+        the name is absent) and decode_info (4,).  An empty side is no special case then: the detections of a first frame
+        still take their decisions."""
         from pcr_amd import associate as A
         L.require_cuda(track_feats, track_xyz, det_feats, det_xyz)
         T, D = track_feats.shape[0], det_feats.shape[0]
+        ds = None if decisions is None else self._decision_set(decisions, T, D, cost_args, "associate")
         pairs, count = A.compare_pairs(track_labels, det_labels, track_lengths, det_lengths, min_points=min_points,
                                        num_classes=num_classes, cap=cap)
         dev = track_feats.device
+        if ds is not None:
+            if T == 0 or D == 0:
+                pairs, logits = pairs[:0], torch.empty((0,), dtype=torch.float32, device=dev)
+            else:
+                gallery_pairs = torch.stack([pairs[:, 0], pairs[:, 1] + T], dim=1)
+                logits = self.match_gallery(torch.cat([track_feats, det_feats], dim=0), torch.cat([track_xyz, det_xyz], dim=0),
+                                            gallery_pairs, count=count if live_only else None).contiguous()
+            dist = cost_args.pop("dist", None)
+            return dict(pairs=pairs, count=count, logits=logits,
+                        **self._associate_decisions(logits, pairs, count, T, D, ds, dist, cost_args))
         if T == 0 or D == 0:
             return dict(track_to_det=torch.full((T,), -1, dtype=torch.int32, device=dev),
                         det_to_track=torch.full((D,), -1, dtype=torch.int32, device=dev), pairs=pairs, count=count,
@@ -619,7 +690,7 @@ class ReIDNet(nn.Module):
     def track_step(self, bank, sweep, boxes, labels, scores, carry=None, carry_inv=None, min_points=2, num_classes=8,
                    cap=None, n=None, crop_args=None, born=None, kill=None, frame_limit=10, replace_all=False,
                    reset_on_match=False, propagate=True, suppress_threshold=0.15, live_only=False, truth=None,
-                   force_truth=False, **cost_args):
+                   force_truth=False, decisions=None, **cost_args):
         """One whole tracker frame on the device without a host read (pcr_amd/tracks.py; INTEGRATION.md "2e. Track
         state"; the split-bf16 guard calibrates on the first batch of a weight version, as in every inference entry
         point: run a frame eagerly before capturing): the sweep (P, C >= 3) and this frame's boxes (M <= bank.max_dets, bank.box_width) with labels and
@@ -641,7 +712,14 @@ class ReIDNet(nn.Module):
         association drives bank.update in place of the tracker's own, det_truth == 1 as born and track_truth == 2 as
         kill (the reference's teacher forcing in mode 'gt': the upper bound a matching head is compared against), and
         the book's decision counters score those applied decisions; the returned track_to_det / det_to_track stay the
-        tracker's own.  Without truth= nothing new is launched."""
+        tracker's own.  Without truth= nothing new is launched.
+
+        decisions= (as in associate; det_values may be (dd, M) and is zero-padded to max_dets) runs the frame with any set of
+        decisions: the matrix is association_cost_multi's (the margin kind takes dist, the softmax kind does not), the
+        decoded born / kill masks -- 'det_newborn' and 'track_false_positive', nothing is born or killed when the name is
+        absent, as in the reference, whose updater makes tracks from decision lists only -- drive bank.update, and the dict
+        gains det_decision, track_decision, born, kill and decode_info.  born= / kill= cannot be passed with it.  truth= /
+        force_truth= work on top unchanged.  propagate stays the bank's one flag for every missed track."""
         from pcr_amd import associate as A
         from pcr_amd import tracks as TR
         if truth is None and force_truth:
@@ -653,6 +731,9 @@ class ReIDNet(nn.Module):
                 raise L.PcrError("track_step: truth['book'] must be a pcr_amd.truth.TruthBook made over this bank")
         if not isinstance(bank, TR.TrackBank):
             raise L.PcrError("track_step: bank must be a pcr_amd.tracks.TrackBank")
+        if decisions is not None and (born is not None or kill is not None):
+            raise L.PcrError("track_step: with decisions= the born / kill masks come from the decoded decisions; pass one or "
+                             "the other")
         L.require_cuda(sweep, boxes, labels, scores)
         L.require_f32(boxes, scores)
         C, D, W = bank.capacity, bank.max_dets, bank.box_width
@@ -661,8 +742,14 @@ class ReIDNet(nn.Module):
         M = boxes.shape[0]
         if labels.shape != (M,) or scores.shape != (M,):
             raise L.PcrError("track_step: labels and scores must be (M,)")
-        if not L.load().pcr_lsa_ok(1, C + D, C + D):
+        ds = None if decisions is None else self._decision_set(decisions, C, D, cost_args, "track_step", M=M)
+        if ds is None and not L.load().pcr_lsa_ok(1, C + D, C + D):
             raise L.PcrError("track_step: capacity + max_dets = %d is beyond linear_assignment (PCR_LSA_MAX)" % (C + D))
+        if ds is not None:
+            from pcr_amd.associate import multi_shape
+            if not L.load().pcr_lsa_ok(1, *multi_shape(C, D, len(ds["det_names"]), len(ds["trk_names"]), ds["reduce"])):
+                raise L.PcrError("track_step: the decisions' matrix for capacity %d and max_dets %d is beyond "
+                                 "linear_assignment (PCR_LSA_MAX)" % (C, D))
         labels = labels.to(torch.int32)
         if M < D:                                   # padding: a box of size zero holds no point, label -1 joins nothing
             boxes = torch.cat([boxes, boxes.new_zeros((D - M, W))], dim=0)
@@ -683,11 +770,18 @@ class ReIDNet(nn.Module):
         gallery_pairs = torch.stack([pairs[:, 0], pairs[:, 1] + C], dim=1)       # detections follow the bank's rows
         logits = self.match_gallery(bank.gallery, bank.gallery_xyz, gallery_pairs,
                                     count=count if live_only else None).contiguous()
-        cost = A.association_cost(logits, pairs, count, C, D, dist=dist, **cost_args)
-        col4row, row4col, info = A.linear_assignment(cost)
-        c, r = col4row[0, :C], row4col[0, :D]
-        t2d = torch.where(c < D, c, torch.full_like(c, -1))
-        d2t = torch.where(r < C, r, torch.full_like(r, -1))
+        decoded = {}
+        if ds is not None:
+            decoded = self._associate_decisions(logits, pairs, count, C, D, ds, dist if ds["kind"] == "margin" else None,
+                                                cost_args)
+            t2d, d2t, cost, info = (decoded.pop(k) for k in ("track_to_det", "det_to_track", "cost", "info"))
+            born, kill = decoded["born"], decoded["kill"]
+        else:
+            cost = A.association_cost(logits, pairs, count, C, D, dist=dist, **cost_args)
+            col4row, row4col, info = A.linear_assignment(cost)
+            c, r = col4row[0, :C], row4col[0, :D]
+            t2d = torch.where(c < D, c, torch.full_like(c, -1))
+            d2t = torch.where(r < C, r, torch.full_like(r, -1))
         decisions, truth_out = (t2d, d2t), {}
         if truth is not None:
             book.match(boxes, labels, truth)
@@ -702,7 +796,7 @@ class ReIDNet(nn.Module):
         if truth is not None:
             book.record(det_slot, det_id)
         return dict(track_to_det=t2d, det_to_track=d2t, pairs=pairs, count=count, logits=logits, cost=cost, info=info,
-                    det_slot=det_slot, det_id=det_id, bank_info=bank_info, dist=dist, lengths=lengths, **truth_out)
+                    det_slot=det_slot, det_id=det_id, bank_info=bank_info, dist=dist, lengths=lengths, **decoded, **truth_out)
 
     def get_match_supervision(self, h1, h2, xyz1, xyz2, id_1, id_2):
         return h1, h2, xyz1, xyz2, (id_1 == id_2).float()

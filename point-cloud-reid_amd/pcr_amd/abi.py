@@ -29,6 +29,14 @@ BankParams = _block("BankParams", """
     ptr lengths boxes scores labels ids steps misses next_id info;
     ptr track_to_det det_to_track det_labels det_lengths det_boxes det_scores born kill carry; ptr src det_slot det_id""")
 
+# ---- section A3 (pcr_assoc_multi, pcr_assoc_decode) ----
+AssocMultiParams = _block("AssocMultiParams", """
+    int T D dd td cap kind reduce; float dist_max dist_penalty fill; ptr logits pairs count det_dec trk_dec dist ws cost;
+    ptr det_choice trk_choice""")
+AssocDecodeParams = _block("AssocDecodeParams", """
+    int T D dd td reduce born_dec kill_dec; float fill; ptr cost col4row row4col solver_info det_choice trk_choice;
+    ptr track_to_det det_to_track det_decision track_decision born kill info""")
+
 # ---- section A7 (pcr_truth) ----
 TruthParams = _block("TruthParams", """
     int C D G gt_cap skip_empty forced; ptr ids slot_gt slot_tte gt_last stats col4row row4col info cost thresh;
@@ -77,7 +85,7 @@ _AttnHeadP = _block("_AttnHeadP", """
     int precision fwd_precision""")
 
 # the header's name of every block (what the layout test compiles against)
-BLOCKS = {"pcr_bank": BankParams, "pcr_truth": TruthParams, "pcr_store_tables": StoreTables, "pcr_sa_params": SaParams, "pcr_attn_params": AttnParams, "pcr_head_params": HeadParams,
+BLOCKS = {"pcr_assoc_multi": AssocMultiParams, "pcr_assoc_decode": AssocDecodeParams, "pcr_bank": BankParams,"pcr_truth": TruthParams, "pcr_store_tables": StoreTables, "pcr_sa_params": SaParams, "pcr_attn_params": AttnParams, "pcr_head_params": HeadParams,
           "pcr_live": LiveParams,
           "pcr_tdense_fwd": _TFwd, "pcr_tdense_bwd": _TBwd, "pcr_bn_fwd_fin": _BnFwd, "pcr_bn_bwd_fin": _BnBwd,
           "pcr_reduce_job": _ReduceJob, "pcr_linattn": _LinAttnP, "pcr_attn_tail": _AttnTailP,
@@ -164,6 +172,10 @@ SIGNATURES = {
     "pcr_assoc_cost_f32": "s FIIFFFfffFiiiS",
     "pcr_lsa_ok": "i iii",
     "pcr_lsa_f32": "s FIIFFIiiiS",
+    "pcr_assoc_multi_ok": "i iiiii",
+    "pcr_assoc_multi_ws_bytes": "i iiii",
+    "pcr_assoc_cost_multi_f32": "s <AssocMultiParams>S",
+    "pcr_assoc_decode_i32": "s <AssocDecodeParams>S",
     # A4. box overlap and suppression
     "pcr_nearest_bev_f32": "s FFiS",
     "pcr_bev_frames_f32": "s FFiS",

@@ -7,9 +7,12 @@ trackers/deprecated/tracking_point_reid.py:15-33), the cost matrix is filled by 
 launch without a host read and with the same bits on every run, so the whole per-frame path can be captured in a HIP
 graph.  INTEGRATION.md ("from logits to assignments") has the mapping; `ReIDNet.associate` chains the steps.
 """
+import ctypes
+
 import torch
 
 from . import _lib as L
+from . import abi
 
 
 def _i32(t):
@@ -132,3 +135,152 @@ def linear_assignment(cost, return_duals=False, out=None):
     else:
         L.run.pcr_lsa_f32(cost, col4row, row4col, u, v, info, B, R, C, L.stream_ptr())
     return (col4row, row4col, info, u, v) if return_duals else (col4row, row4col, info)
+
+
+# ---- any set of decisions per side (pcr.h A3, "Any set of decisions") ----------------------------------------------------
+KINDS = {"margin": 0, "softmax": 1}
+
+_WS = {}          # (device index, T, D, dd, td) -> uint8 workspace of pcr_assoc_multi_ws_bytes
+
+
+def _decision_rows(values, n, what):
+    """decision values (k, n) -> (k, tensor or None); None = no decision on this side"""
+    if values is None:
+        return 0, None
+    L.require_cuda(values)
+    L.require_f32(values)
+    if values.dim() != 2 or values.shape[1] != n or not values.is_contiguous():
+        raise L.PcrError("association_cost_multi: %s must be a contiguous (decisions, %d) tensor, got %s"
+                         % (what, n, tuple(values.shape)))
+    return values.shape[0], (values if values.shape[0] else None)
+
+
+def multi_shape(T, D, dd, td, reduce=False):
+    """(R, C) of the matrix with dd detection and td tracking decisions; reduce keeps one diagonal block per side"""
+    de, te = (int(dd > 0), int(td > 0)) if reduce else (dd, td)
+    return T + de * D, D + te * T
+
+
+def association_cost_multi(logits, pairs, count, T, D, det_decisions=None, track_decisions=None, kind="margin", reduce=False,
+                           dist=None, dist_max=22.0, dist_penalty=3.0, fill=10000.0, out=None):
+    """logits (cap,), pairs (cap, 2), count (1,), det_decisions (dd, D), track_decisions (td, T) -> cost (T + dd*D, D + td*T)
+    float32, every element written: the reference's matrix for any set of decisions (tracking_association.py:22-53, :126).
+
+    kind "margin": -logits[k] at the listed pairs (+ dist_penalty where dist > dist_max), the decision values as costs on
+    the diagonals of their blocks, the transpose of the top-left block in every bottom-right block; with dd = td = 1 it is
+    association_cost's matrix bit for bit.  kind "softmax" (get_cost_mat_softmax, :56-98): logits and decision values
+    are scores; a listed pair holds -max(p_row, p_col), a decision -p of that decision, the softmaxes running over a
+    track's (a detection's) listed pairs and its decisions only; dist must be None.  reduce (margin only,
+    TrackingAssociatorMax): one diagonal block per side holding each object's cheapest decision, and the return value is
+    (cost, det_choice (D,), track_choice (T,)) with the chosen decision indices (zeros for a side without decisions).
+    None for det_decisions / track_decisions means no decision on that side.  out = cost, or (cost, det_choice,
+    track_choice) under reduce, to write into."""
+    if kind not in KINDS:
+        raise L.PcrError("association_cost_multi: kind must be 'margin' or 'softmax', got %r" % (kind,))
+    reduce = bool(reduce)
+    if kind == "softmax" and dist is not None:
+        raise L.PcrError("association_cost_multi: the softmax kind takes no distance prior (dist must be None)")
+    if kind == "softmax" and reduce:
+        raise L.PcrError("association_cost_multi: reduce goes with the margin kind only")
+    L.require_cuda(logits, pairs, count, dist)
+    L.require_f32(logits, dist)
+    L.require_i32(pairs, count)
+    T, D = int(T), int(D)
+    if pairs.dim() != 2 or pairs.shape[1] != 2 or not pairs.is_contiguous():
+        raise L.PcrError("association_cost_multi: pairs must be a contiguous (cap, 2) tensor")
+    cap = pairs.shape[0]
+    if logits.shape != (cap,) or not logits.is_contiguous() or count.numel() != 1:
+        raise L.PcrError("association_cost_multi: logits must be a contiguous (cap,) tensor and count hold one int")
+    if dist is not None and (dist.shape != (T, D) or not dist.is_contiguous()):
+        raise L.PcrError("association_cost_multi: dist must be a contiguous (T, D) tensor")
+    dd, det_dec = _decision_rows(det_decisions, D, "det_decisions")
+    td, trk_dec = _decision_rows(track_decisions, T, "track_decisions")
+    lib = L.load()
+    if not lib.pcr_assoc_multi_ok(T, D, dd, td, cap):
+        raise L.PcrError("association_cost_multi: T=%d D=%d dd=%d td=%d cap=%d is out of range (pcr_assoc_multi_ok)"
+                         % (T, D, dd, td, cap))
+    R, C = multi_shape(T, D, dd, td, reduce)
+    dev = logits.device
+    cost, det_choice, trk_choice = (out if reduce else (out, None, None)) if out is not None else (None, None, None)
+    if cost is None:
+        cost = torch.empty((R, C), dtype=torch.float32, device=dev)
+    if reduce and det_choice is None:
+        det_choice = torch.zeros((D,), dtype=torch.int32, device=dev)
+    if reduce and trk_choice is None:
+        trk_choice = torch.zeros((T,), dtype=torch.int32, device=dev)
+    L.require_cuda(cost, det_choice, trk_choice)
+    L.require_f32(cost)
+    L.require_i32(det_choice, trk_choice)
+    if cost.shape != (R, C) or not cost.is_contiguous():
+        raise L.PcrError("association_cost_multi: out must be a contiguous (%d, %d) tensor" % (R, C))
+    if reduce and (det_choice.shape != (D,) or trk_choice.shape != (T,)):
+        raise L.PcrError("association_cost_multi: det_choice must be (D,) and track_choice (T,)")
+    if R * C:                            # the entry launches nothing for an empty matrix
+        p = abi.AssocMultiParams()
+        p.T, p.D, p.dd, p.td, p.cap, p.kind, p.reduce = T, D, dd, td, cap, KINDS[kind], int(reduce)
+        p.dist_max, p.dist_penalty, p.fill = float(dist_max), float(dist_penalty), float(fill)
+        ws = None
+        if kind == "softmax":
+            key = (dev.index, T, D, dd, td)
+            ws = _WS.get(key)
+            if ws is None:
+                if torch.cuda.is_current_stream_capturing():
+                    raise L.PcrError("association_cost_multi: nothing is cached for %r yet; run the call once outside the "
+                                     "capture" % (key,))
+                ws = _WS[key] = torch.empty((max(lib.pcr_assoc_multi_ws_bytes(T, D, dd, td), 8),), dtype=torch.uint8,
+                                            device=dev)
+        for k, t in (("logits", logits), ("pairs", pairs), ("count", count), ("det_dec", det_dec), ("trk_dec", trk_dec),
+                     ("dist", dist), ("ws", ws), ("cost", cost), ("det_choice", det_choice), ("trk_choice", trk_choice)):
+            setattr(p, k, L._p(t))
+        L.run.pcr_assoc_cost_multi_f32(ctypes.byref(p), L.stream_ptr())
+    return (cost, det_choice, trk_choice) if reduce else cost
+
+
+DECODE_OUTPUTS = ("track_to_det", "det_to_track", "det_decision", "track_decision", "born", "kill", "info")
+
+
+def decode_assignment(cost, assignment, T, D, dd, td, fill=10000.0, choices=None, born_decision=-1, kill_decision=-1):
+    """cost (R, C) of association_cost_multi and assignment = linear_assignment's (col4row, row4col, info) over it -> dict of
+    track_to_det (T,), det_to_track (D,) [-1 = none], det_decision (D,) [0 = matched, 1 + i = detection decision i, 1 + dd =
+    unmatched], track_decision (T,) [likewise with td], born (D,) = det_decision == 1 + born_decision, kill (T,) =
+    track_decision == 1 + kill_decision (int32 0 / 1, what TrackBank.update takes; all zero for a decision of -1) and info
+    (4,) = the solver's info, void assignments (an assigned entry that holds fill: both sides become unassigned), repaired
+    tracks, repaired detections.  It is tracking_association.py:146-245 in fixed shape (pcr.h has the rules and the two
+    deliberate differences).  choices = (det_choice, track_choice) of a reduce matrix."""
+    T, D, dd, td = int(T), int(D), int(dd), int(td)
+    reduce = choices is not None
+    det_choice, trk_choice = choices if reduce else (None, None)
+    col4row, row4col, sinfo = assignment[0], assignment[1], assignment[2]
+    L.require_cuda(cost, col4row, row4col, sinfo, det_choice, trk_choice)
+    L.require_f32(cost)
+    L.require_i32(col4row, row4col, sinfo, det_choice, trk_choice)
+    lib = L.load()
+    if not lib.pcr_assoc_multi_ok(T, D, dd, td, 0):
+        raise L.PcrError("decode_assignment: T=%d D=%d dd=%d td=%d is out of range (pcr_assoc_multi_ok)" % (T, D, dd, td))
+    if not (-1 <= int(born_decision) < dd and -1 <= int(kill_decision) < td):
+        raise L.PcrError("decode_assignment: born_decision must be -1 or below dd = %d, kill_decision -1 or below td = %d"
+                         % (dd, td))
+    R, C = multi_shape(T, D, dd, td, reduce)
+    if tuple(cost.shape[-2:]) != (R, C) or cost.numel() != R * C or not cost.is_contiguous():
+        raise L.PcrError("decode_assignment: cost must be a contiguous (%d, %d) tensor, got %s" % (R, C, tuple(cost.shape)))
+    if col4row.numel() != R or row4col.numel() != C or sinfo.numel() != 1 or not col4row.is_contiguous() \
+            or not row4col.is_contiguous():
+        raise L.PcrError("decode_assignment: the assignment must hold col4row (%d,), row4col (%d,) and info (1,)" % (R, C))
+    if reduce and (det_choice.shape != (D,) or trk_choice.shape != (T,)):
+        raise L.PcrError("decode_assignment: choices must be (det_choice (D,), track_choice (T,))")
+    dev = cost.device
+    sizes = dict(track_to_det=T, det_to_track=D, det_decision=D, track_decision=T, born=D, kill=T, info=4)
+    out = {k: torch.empty((sizes[k],), dtype=torch.int32, device=dev) for k in DECODE_OUTPUTS}
+    if T + D == 0:                       # the entry launches nothing
+        out["info"].zero_()
+        return out
+    p = abi.AssocDecodeParams()
+    p.T, p.D, p.dd, p.td, p.reduce = T, D, dd, td, int(reduce)
+    p.born_dec, p.kill_dec, p.fill = int(born_decision), int(kill_decision), float(fill)
+    for k, t in (("cost", cost), ("col4row", col4row), ("row4col", row4col), ("solver_info", sinfo),
+                 ("det_choice", det_choice), ("trk_choice", trk_choice)):
+        setattr(p, k, L._p(t))
+    for k in DECODE_OUTPUTS:
+        setattr(p, k, L._p(out[k]))
+    L.run.pcr_assoc_decode_i32(ctypes.byref(p), L.stream_ptr())
+    return out

@@ -20,6 +20,7 @@ FLAGS = {
     "edge_kernels.hip": ["-ffp-contract=off"],
     "crop_kernels.hip": ["-ffp-contract=off"],       # membership and box-frame coordinates are compared bit for bit
     "assoc_kernels.hip": ["-ffp-contract=off"],      # the assignment's candidate values and duals are compared bit for bit
+    "assoc_multi_kernels.hip": ["-ffp-contract=off"],  # the margin matrix is compared bit for bit with pcr_assoc_cost_f32's
     "nms_kernels.hip": ["-ffp-contract=off"],        # IoUs are compared with a threshold; the axis-aligned ones bit for bit
     "track_kernels.hip": ["-ffp-contract=off"],      # the propagated boxes and the distances are compared bit for bit
     "truth_kernels.hip": ["-ffp-contract=off"],      # the ground-truth matching cost is compared bit for bit

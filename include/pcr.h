@@ -268,6 +268,43 @@ int pcr_lsa_ok(int B, int R, int C);
 int pcr_lsa_f32(const float *cost, int *col4row, int *row4col, float *u, float *v, int *info, int B, int R, int C,
                 pcr_stream_t stream);
 
+/* The block rule (additive to ABI 17): pcr_lsa_blocks_f32 solves ONE (R,C) problem block by block.  row_block (R) and
+ * col_block (C) are int32 and give every row and column a block id in [0, G); any other value means the row or column
+ * takes no part.  For each block g:
+ *   sub-problem  cost[rows of g][columns of g], both lists in ascending original index;
+ *   solution     exactly pcr_lsa_f32's rules above over the sub-problem: the transpose when the block has more rows than
+ *                columns, ties to the LOWEST column index of the sub-problem, the duals;
+ *   outputs      col4row (R), row4col (C) hold ORIGINAL indices; a block with no rows or no columns assigns nothing (its
+ *                rows and columns get -1, duals 0); rows and columns outside every block get -1, their duals 0;
+ *   reads        only entries of the sub-problems are read: a NaN elsewhere is never seen;
+ *   info (G)     0 / 1 / 2 per block with pcr_lsa_f32's meanings; the NaN / infinity pre-scan covers the block's own entries
+ *                only; a failed block's rows and columns are -1 (duals 0), the other blocks are solved.
+ * EVERY element of col4row, row4col, info (and u, v unless NULL) is written.  One launch, one wave per block: the wave
+ * compacts the block's rows and columns into two LDS index lists (ballots over 64 ids, ranks from mbcnt, no atomics),
+ * gathers the sub-matrix through them into LDS when lists + u + col4row + sub-matrix fit (R + C + 2*min(nr,nc) + nr*nc
+ * words in 160 KiB), otherwise reads the gathered rows from global memory, runs the one solver body pcr_lsa_f32 runs,
+ * and scatters the results through the lists.  Block sizes are device data: the launch asks for the LDS one block of all
+ * R x C could use, capped at 160 KiB.  The blocks run on different CUs at the same time.
+ * pcr_lsa_blocks_ok: 0 <= R, C <= PCR_LSA_MAX, 1 <= G <= PCR_ASSOC_MAX_CLASSES + 1.  Nothing to do: never (info is written).
+ *
+ * pcr_assoc_blocks_i32: track_labels (T), det_labels (D) -> row_block (T + de*D), col_block (D + te*T), the block ids of
+ * the matrix pcr_assoc_cost_f32 (de = te = 1) or pcr_assoc_cost_multi_f32 (de / te = dd / td, or [dd > 0] / [td > 0] under
+ * reduce) builds.  An object's block is its label when the label lies in [0, num_classes), otherwise the REST block
+ * num_classes (free bank slots, padded detections, foreign labels); lengths play no part (an object below min_points
+ * stays in its class block: its row is all fill, its decisions are not).  Row t and columns D + j*T + t take track t's
+ * block; column d and rows T + i*D + d take detection d's block; G = num_classes + 1.  The top-left block of such a matrix
+ * joins only objects of one class (pcr_assoc_pairs_i32 lists no other pair), so the matrix is block-diagonal up to fill
+ * and the decoded frame of the block solve equals the full solve's, except that decode info[1] may be smaller (the full
+ * solve can be forced to pair leftovers across classes through fill; the blocks are not).  A hand-made matrix with a
+ * non-fill entry between two classes does not meet this precondition.
+ * Range as pcr_assoc_multi_ok(T, D, de, te, 0) and 1 <= num_classes <= PCR_ASSOC_MAX_CLASSES.  Nothing to do: both
+ * outputs empty. */
+int pcr_lsa_blocks_ok(int R, int C, int G);
+int pcr_lsa_blocks_f32(const float *cost, const int *row_block, const int *col_block, int *col4row, int *row4col, float *u,
+                       float *v, int *info, int R, int C, int G, pcr_stream_t stream);
+int pcr_assoc_blocks_i32(const int *track_labels, const int *det_labels, int *row_block, int *col_block, int T, int D,
+                         int de, int te, int num_classes, pcr_stream_t stream);
+
 /* Any set of decisions per side (additive to ABI 17).  The reference's tracker runs with dd detection decisions and td
  * tracking decisions (VirtualTracker, trackers/deprecated/virtual_tracker.py:80-81, :114-117: by default dd = 2, td = 0);
  * its matrix is (R, C) = (T + dd*D, D + td*T) (tracking_association.py:126).  The two entries below build that matrix by

@@ -174,39 +174,41 @@ __device__ __forceinline__ float lsa_wave_min(float v) {
   return fminf(fminf(lsa_bcast(v, 0), lsa_bcast(v, 16)), fminf(lsa_bcast(v, 32), lsa_bcast(v, 48)));
 }
 
-// One wave per problem; NK = columns per lane (column j = k * 64 + lane); STAGED: the matrix is copied to LDS (as the
-// solved problem's rows) and read from there.  The rules are pcr.h's, in its words.
-template <int NK, bool STAGED>
-__global__ __launch_bounds__(kWave) void lsa_kernel(const float *__restrict__ cost, int *__restrict__ col4row_o,
-                                                    int *__restrict__ row4col_o, float *__restrict__ u_o,
-                                                    float *__restrict__ v_o, int *__restrict__ info, int R, int C) {
-  extern __shared__ float lsa_lds[];
-  const int b = blockIdx.x, lane = threadIdx.x;
-  const bool tr = R > C;
-  const int nr = tr ? C : R, nc = tr ? R : C;             // the solved problem: nr <= nc
-  float *u = lsa_lds;
-  int *c4r = reinterpret_cast<int *>(lsa_lds + nr);
-  float *cl = lsa_lds + 2 * nr;                           // (nr, nc) when STAGED
-  const float *cb = cost + (size_t)b * R * C;
-  const float inf = __builtin_inff();
-
-  bool bad = false;
-  for (int e = lane; e < R * C; e += kWave) {
-    const float x = cb[e];
-    bad |= (__float_as_uint(x) & 0x7F800000u) == 0x7F800000u;
-    if constexpr (STAGED) {
-      if (tr) {
-        const int r0 = e / C;
-        cl[(e - r0 * C) * nc + r0] = x;
-      } else {
-        cl[e] = x;
-      }
-    }
+// How a search step reads entry (i, jj) of the SOLVED problem (nr <= nc rows i, columns jj).  Each reader keeps one
+// address space: LDS for the staged matrix, global for the other two.
+struct LsaLdsRows {                                       // the staged (nr, nc) copy
+  const float *cl;
+  int nc;
+  __device__ __forceinline__ float operator()(int i, int jj) const { return cl[i * nc + jj]; }
+};
+struct LsaGlobalRows {                                    // the caller's (R, C) matrix, transposed on the way if tr
+  const float *cb;
+  int C;
+  bool tr;
+  __device__ __forceinline__ float operator()(int i, int jj) const {
+    return tr ? cb[(size_t)jj * C + i] : cb[(size_t)i * C + jj];
   }
-  int status = __ballot(bad) ? 1 : 0;
+};
+struct LsaGatherRows {                                    // a block of the caller's matrix through its two LDS index lists
+  const float *cb;
+  const int *ri, *ci;                                     // original indices of the solved problem's rows / columns
+  int C;
+  bool tr;
+  __device__ __forceinline__ float operator()(int i, int jj) const {
+    const int a = ri[i], b = ci[jj];
+    return tr ? cb[(size_t)b * C + a] : cb[(size_t)a * C + b];
+  }
+};
 
-  float sh[NK], v[NK];
-  int pr[NK], r4c[NK];
+// The ONE copy of the solver: search, dual update and augmentation over the solved problem (nr <= nc), by one wave.
+// NK = columns per lane (column j = k * 64 + lane): v and r4c come back in registers, u and c4r (nr each) in LDS.
+// status is what the pre-scan found; the return value is the problem's info.  The rules are pcr.h's, in its words.
+template <int NK, class Rows>
+__device__ __forceinline__ int lsa_solve(const Rows &entry, float *u, int *c4r, int nr, int nc, int lane, int status,
+                                         float (&v)[NK], int (&r4c)[NK]) {
+  const float inf = __builtin_inff();
+  float sh[NK];
+  int pr[NK];
 #pragma unroll
   for (int k = 0; k < NK; ++k) v[k] = 0.f, r4c[k] = -1, sh[k] = inf, pr[k] = -1;
   for (int i = lane; i < nr; i += kWave) u[i] = 0.f, c4r[i] = -1;
@@ -224,11 +226,7 @@ __global__ __launch_bounds__(kWave) void lsa_kernel(const float *__restrict__ co
 #pragma unroll
       for (int k = 0; k < NK; ++k) {
         cv[k] = 0.f;
-        if (k * kWave < nc) {
-          const int jj = min(k * kWave + lane, nc - 1);
-          if constexpr (STAGED) cv[k] = cl[i * nc + jj];
-          else cv[k] = tr ? cb[(size_t)jj * C + i] : cb[(size_t)i * C + jj];
-        }
+        if (k * kWave < nc) cv[k] = entry(i, min(k * kWave + lane, nc - 1));
       }
       float lmin = inf;
 #pragma unroll
@@ -309,6 +307,42 @@ __global__ __launch_bounds__(kWave) void lsa_kernel(const float *__restrict__ co
     }
   }
   wave_sync();
+  return status;
+}
+
+// One wave per problem; STAGED: the matrix is copied to LDS (as the solved problem's rows) and read from there.
+template <int NK, bool STAGED>
+__global__ __launch_bounds__(kWave) void lsa_kernel(const float *__restrict__ cost, int *__restrict__ col4row_o,
+                                                    int *__restrict__ row4col_o, float *__restrict__ u_o,
+                                                    float *__restrict__ v_o, int *__restrict__ info, int R, int C) {
+  extern __shared__ float lsa_lds[];
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const bool tr = R > C;
+  const int nr = tr ? C : R, nc = tr ? R : C;             // the solved problem: nr <= nc
+  float *u = lsa_lds;
+  int *c4r = reinterpret_cast<int *>(lsa_lds + nr);
+  float *cl = lsa_lds + 2 * nr;                           // (nr, nc) when STAGED
+  const float *cb = cost + (size_t)b * R * C;
+
+  bool bad = false;
+  for (int e = lane; e < R * C; e += kWave) {
+    const float x = cb[e];
+    bad |= (__float_as_uint(x) & 0x7F800000u) == 0x7F800000u;
+    if constexpr (STAGED) {
+      if (tr) {
+        const int r0 = e / C;
+        cl[(e - r0 * C) * nc + r0] = x;
+      } else {
+        cl[e] = x;
+      }
+    }
+  }
+  int status = __ballot(bad) ? 1 : 0;
+
+  float v[NK];
+  int r4c[NK];
+  if constexpr (STAGED) status = lsa_solve<NK>(LsaLdsRows{cl, nc}, u, c4r, nr, nc, lane, status, v, r4c);
+  else status = lsa_solve<NK>(LsaGlobalRows{cb, C, tr}, u, c4r, nr, nc, lane, status, v, r4c);
 
   // the transposed problem's rows are the caller's columns
   int *rows_o = tr ? row4col_o + (size_t)b * C : col4row_o + (size_t)b * R;
@@ -331,6 +365,96 @@ __global__ __launch_bounds__(kWave) void lsa_kernel(const float *__restrict__ co
   if (lane == 0) info[b] = status;
 }
 
+// One wave per BLOCK of one (R, C) problem (pcr.h, "the block rule"): compact the block's rows and columns into two LDS
+// index lists (ascending: a ballot over 64 ids, the rank from mbcnt), gather the sub-matrix through them -- into LDS when
+// it fits beside the lists (lds_words is what the launch asked for), with the pre-scan folded in -- solve it with
+// lsa_solve and scatter the results through the lists.  Wave 0 also writes the rows and columns outside every block.
+template <int NK>
+__global__ __launch_bounds__(kWave) void lsa_blocks_kernel(const float *__restrict__ cost, const int *__restrict__ row_block,
+                                                           const int *__restrict__ col_block, int *__restrict__ col4row_o,
+                                                           int *__restrict__ row4col_o, float *__restrict__ u_o,
+                                                           float *__restrict__ v_o, int *__restrict__ info, int R, int C,
+                                                           int G, int lds_words) {
+  extern __shared__ float lsa_lds[];
+  const int g = blockIdx.x, lane = threadIdx.x;
+  int *lists = reinterpret_cast<int *>(lsa_lds);          // [0, R): the block's rows, [R, R + C): its columns
+  int n[2] = {0, 0};
+#pragma unroll
+  for (int s = 0; s < 2; ++s) {
+    const int len = s ? C : R;
+    const int *ids = s ? col_block : row_block;
+    int *list = lists + (s ? R : 0), *idx_o = s ? row4col_o : col4row_o;
+    float *dual_o = s ? v_o : u_o;
+    for (int c0 = 0; c0 < len; c0 += kWave) {
+      const int i = c0 + lane;
+      const int id = i < len ? ids[i] : g - 1;            // past the end: neither this block nor outside every block
+      const unsigned long long bal = __ballot(i < len && id == g);
+      if (i < len && id == g) list[n[s] + (int)pcr_lanes_below(bal)] = i;
+      n[s] += __popcll(bal);
+      if (g == 0 && i < len && (id < 0 || id >= G)) {
+        idx_o[i] = -1;
+        if (dual_o) dual_o[i] = 0.f;
+      }
+    }
+  }
+  wave_sync();
+
+  const bool tr = n[0] > n[1];
+  const int nr = tr ? n[1] : n[0], nc = tr ? n[0] : n[1];  // the solved problem: nr <= nc
+  const int *ri = lists + (tr ? R : 0), *ci = lists + (tr ? 0 : R);
+  float *u = lsa_lds + R + C;
+  int *c4r = reinterpret_cast<int *>(u + nr);
+  float *cl = u + 2 * nr;                                 // (nr, nc) when it fits
+  const bool staged = R + C + 2 * nr + nr * nc <= lds_words;
+
+  bool bad = false;
+  for (int e = lane; e < nr * nc; e += kWave) {
+    const int i = e / nc, a = ri[i], b = ci[e - i * nc];
+    const float x = tr ? cost[(size_t)b * C + a] : cost[(size_t)a * C + b];
+    bad |= (__float_as_uint(x) & 0x7F800000u) == 0x7F800000u;
+    if (staged) cl[e] = x;
+  }
+  int status = __ballot(bad) ? 1 : 0;
+
+  float v[NK];
+  int r4c[NK];
+  if (staged) status = lsa_solve<NK>(LsaLdsRows{cl, nc}, u, c4r, nr, nc, lane, status, v, r4c);
+  else status = lsa_solve<NK>(LsaGatherRows{cost, ri, ci, C, tr}, u, c4r, nr, nc, lane, status, v, r4c);
+
+  int *rows_o = tr ? row4col_o : col4row_o, *cols_o = tr ? col4row_o : row4col_o;
+  float *ur_o = tr ? v_o : u_o, *vc_o = tr ? u_o : v_o;
+  const bool ok = status == 0;
+  for (int i = lane; i < nr; i += kWave) {
+    const int j = c4r[i];
+    rows_o[ri[i]] = ok && j >= 0 ? ci[j] : -1;
+    if (ur_o) ur_o[ri[i]] = ok ? u[i] : 0.f;
+  }
+#pragma unroll
+  for (int k = 0; k < NK; ++k) {
+    const int j = k * kWave + lane;
+    if (j < nc) {
+      cols_o[ci[j]] = ok && r4c[k] >= 0 ? ri[r4c[k]] : -1;
+      if (vc_o) vc_o[ci[j]] = ok ? v[k] : 0.f;
+    }
+  }
+  if (lane == 0) info[g] = status;
+}
+
+// row / column -> block id of the (T + de*D, D + te*T) layout: an object's label in [0, ncls), the rest block ncls otherwise
+__global__ __launch_bounds__(256) void assoc_blocks_kernel(const int *__restrict__ tl, const int *__restrict__ dl,
+                                                           int *__restrict__ row_block, int *__restrict__ col_block, int T,
+                                                           int D, int R, int C, int ncls) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < R) {
+    const int x = i < T ? tl[i] : dl[(i - T) % D];
+    row_block[i] = x >= 0 && x < ncls ? x : ncls;
+  }
+  if (i < C) {
+    const int x = i < D ? dl[i] : tl[(i - D) % T];
+    col_block[i] = x >= 0 && x < ncls ? x : ncls;
+  }
+}
+
 template <int NK>
 int lsa_launch(const float *cost, int *col4row, int *row4col, float *u, float *v, int *info, int B, int R, int C,
                hipStream_t st) {
@@ -340,6 +464,16 @@ int lsa_launch(const float *cost, int *col4row, int *row4col, float *u, float *v
                                                 v, info, R, C);
   return pcr_launch_lds<lsa_kernel<NK, false>>(dim3(B), dim3(kWave), 2 * nr * sizeof(float), st, cost, col4row, row4col, u,
                                                v, info, R, C);
+}
+
+template <int NK>
+int lsa_blocks_launch(const float *cost, const int *row_block, const int *col_block, int *col4row, int *row4col, float *u,
+                      float *v, int *info, int R, int C, int G, hipStream_t st) {
+  // block sizes are device data: the LDS a largest block (all of R x C) could use, capped
+  const size_t nr = (size_t)(R < C ? R : C), want = (size_t)R + C + 2 * nr + (size_t)R * C;
+  const size_t words = want * sizeof(float) <= (size_t)kMaxDynLds ? want : (size_t)kMaxDynLds / sizeof(float);
+  return pcr_launch_lds<lsa_blocks_kernel<NK>>(dim3(G), dim3(kWave), words * sizeof(float), st, cost, row_block, col_block,
+                                               col4row, row4col, u, v, info, R, C, G, (int)words);
 }
 
 }  // namespace
@@ -393,4 +527,34 @@ PCR_EXPORT int pcr_lsa_f32(const float *cost, int *col4row, int *row4col, float 
   if (nc <= 256) return lsa_launch<4>(cost, col4row, row4col, u, v, info, B, R, C, st);
   if (nc <= 512) return lsa_launch<8>(cost, col4row, row4col, u, v, info, B, R, C, st);
   return lsa_launch<16>(cost, col4row, row4col, u, v, info, B, R, C, st);
+}
+
+PCR_EXPORT int pcr_lsa_blocks_ok(int R, int C, int G) {
+  return R >= 0 && R <= PCR_LSA_MAX && C >= 0 && C <= PCR_LSA_MAX && G >= 1 && G <= PCR_ASSOC_MAX_CLASSES + 1;
+}
+
+PCR_EXPORT int pcr_lsa_blocks_f32(const float *cost, const int *row_block, const int *col_block, int *col4row, int *row4col,
+                                  float *u, float *v, int *info, int R, int C, int G, pcr_stream_t stream) {
+  if (!pcr_lsa_blocks_ok(R, C, G)) return PCR_ERR_INVALID;
+  if (!info || (R > 0 && (!row_block || !col4row)) || (C > 0 && (!col_block || !row4col)) || (R > 0 && C > 0 && !cost))
+    return PCR_ERR_INVALID;
+  const int nc = R > C ? R : C;
+  hipStream_t st = pcr_s(stream);
+  if (nc <= 64) return lsa_blocks_launch<1>(cost, row_block, col_block, col4row, row4col, u, v, info, R, C, G, st);
+  if (nc <= 128) return lsa_blocks_launch<2>(cost, row_block, col_block, col4row, row4col, u, v, info, R, C, G, st);
+  if (nc <= 256) return lsa_blocks_launch<4>(cost, row_block, col_block, col4row, row4col, u, v, info, R, C, G, st);
+  if (nc <= 512) return lsa_blocks_launch<8>(cost, row_block, col_block, col4row, row4col, u, v, info, R, C, G, st);
+  return lsa_blocks_launch<16>(cost, row_block, col_block, col4row, row4col, u, v, info, R, C, G, st);
+}
+
+PCR_EXPORT int pcr_assoc_blocks_i32(const int *track_labels, const int *det_labels, int *row_block, int *col_block, int T,
+                                    int D, int de, int te, int num_classes, pcr_stream_t stream) {
+  if (!pcr_assoc_multi_ok(T, D, de, te, 0)) return PCR_ERR_INVALID;
+  if (num_classes < 1 || num_classes > PCR_ASSOC_MAX_CLASSES) return PCR_ERR_INVALID;
+  const int R = T + de * D, C = D + te * T, N = R > C ? R : C;
+  if (N == 0) return PCR_OK;
+  if ((T > 0 && !track_labels) || (D > 0 && !det_labels) || (R > 0 && !row_block) || (C > 0 && !col_block))
+    return PCR_ERR_INVALID;
+  return pcr_launch<assoc_blocks_kernel>(dim3((N + 255) / 256), dim3(256), 0, pcr_s(stream), track_labels, det_labels,
+                                         row_block, col_block, T, D, R, C, num_classes);
 }

@@ -617,7 +617,21 @@ class ReIDNet(nn.Module):
                     kill=trk_names.index("track_false_positive") if "track_false_positive" in trk_names else -1)
 
     @staticmethod
-    def _associate_decisions(logits, pairs, count, T, D, ds, dist, cost_args):
+    def _assign(cost, T, D, dd, td, reduce, by_class):
+        """linear_assignment over cost, or -- by_class = (track_labels, det_labels, num_classes) -- the block rule: the ids
+        from the labels on the device, one wave per class (linear_assignment_blocks) and the solver's one word as the
+        maximum over the blocks -> (col4row (R,), row4col (C,), info (1,)), block_info (G,) or None"""
+        from pcr_amd import associate as A
+        if by_class is None:
+            col4row, row4col, info = A.linear_assignment(cost)
+            return (col4row[0], row4col[0], info), None
+        row_block, col_block, G = A.association_blocks(by_class[0], by_class[1], T, D, dd, td, num_classes=by_class[2],
+                                                       reduce=reduce)
+        col4row, row4col, block_info = A.linear_assignment_blocks(cost, row_block, col_block, G)
+        return (col4row, row4col, block_info.amax(dim=0, keepdim=True)), block_info
+
+    @staticmethod
+    def _associate_decisions(logits, pairs, count, T, D, ds, dist, cost_args, by_class=None):
         """the matrix for the decision set ds, its assignment and the decode (pcr_amd/associate.py) -> the entries that
         associate / track_step return"""
         from pcr_amd import associate as A
@@ -628,15 +642,15 @@ class ReIDNet(nn.Module):
         out = A.association_cost_multi(logits, pairs, count, T, D, ds["det_values"], ds["trk_values"], kind=ds["kind"],
                                        reduce=ds["reduce"], dist=dist, **cost_args)
         cost, choices = (out[0], (out[1], out[2])) if ds["reduce"] else (out, None)
-        assignment = A.linear_assignment(cost)
+        assignment, block_info = ReIDNet._assign(cost, T, D, dd, td, ds["reduce"], by_class)
         dec = A.decode_assignment(cost, assignment, T, D, dd, td, fill=cost_args.get("fill", 10000.0), choices=choices,
                                   born_decision=ds["born"], kill_decision=ds["kill"])
         return dict(track_to_det=dec["track_to_det"], det_to_track=dec["det_to_track"], cost=cost, info=assignment[2],
                     det_decision=dec["det_decision"], track_decision=dec["track_decision"], born=dec["born"],
-                    kill=dec["kill"], decode_info=dec["info"])
+                    kill=dec["kill"], decode_info=dec["info"], **({} if block_info is None else {"block_info": block_info}))
 
     def associate(self, track_feats, track_xyz, track_labels, track_lengths, det_feats, det_xyz, det_labels, det_lengths,
-                  min_points=2, num_classes=8, cap=None, live_only=False, decisions=None, **cost_args):
+                  min_points=2, num_classes=8, cap=None, live_only=False, decisions=None, by_class=False, **cost_args):
         """One frame of the reference tracker's association on the device (pcr_amd/associate.py): the class-gated pair
         list (get_labels_to_compare, tracking_point_reid.py:15-33), match_gallery over [tracks | detections], the
         augmented cost matrix (get_cost_mat_margin, tracking_association.py:22-53) and the linear assignment the
@@ -646,6 +660,10 @@ class ReIDNet(nn.Module):
         fill).  live_only: match_gallery scores the count real pairs of the list only (count=; logits[count:] are then 0.0
         instead of the padding pairs' scores -- association_cost reads logits[:count], so everything else is bit-identical).
         -> dict(track_to_det (T,), det_to_track (D,) [-1 = none], pairs, count, logits, cost, info).
+        by_class: the assignment is solved class by class, one wave per class, instead of as one problem (pcr.h, "the
+        block rule"; INTEGRATION.md 2c: the matrix is block-diagonal because compare_pairs lists pairs of one class only).
+        Everything returned is the same bits -- decode_info[1] alone may be smaller, no leftovers being paired across
+        classes -- info stays one word (the maximum over the blocks) and the dict gains block_info (num_classes + 1,).
 
         decisions=dict(detection=(names...), tracking=(names...), det_values=(dd, D) or None, track_values=(td, T) or None,
         kind="margin" | "softmax", reduce=False) runs the reference's tracker with any set of decisions:
@@ -662,6 +680,7 @@ class ReIDNet(nn.Module):
         pairs, count = A.compare_pairs(track_labels, det_labels, track_lengths, det_lengths, min_points=min_points,
                                        num_classes=num_classes, cap=cap)
         dev = track_feats.device
+        blocks = (track_labels, det_labels, num_classes) if by_class else None
         if ds is not None:
             if T == 0 or D == 0:
                 pairs, logits = pairs[:0], torch.empty((0,), dtype=torch.float32, device=dev)
@@ -671,26 +690,27 @@ class ReIDNet(nn.Module):
                                             gallery_pairs, count=count if live_only else None).contiguous()
             dist = cost_args.pop("dist", None)
             return dict(pairs=pairs, count=count, logits=logits,
-                        **self._associate_decisions(logits, pairs, count, T, D, ds, dist, cost_args))
+                        **self._associate_decisions(logits, pairs, count, T, D, ds, dist, cost_args, by_class=blocks))
         if T == 0 or D == 0:
+            empty = {"block_info": torch.zeros((num_classes + 1,), dtype=torch.int32, device=dev)} if by_class else {}
             return dict(track_to_det=torch.full((T,), -1, dtype=torch.int32, device=dev),
                         det_to_track=torch.full((D,), -1, dtype=torch.int32, device=dev), pairs=pairs, count=count,
                         logits=torch.empty((pairs.shape[0],), dtype=torch.float32, device=dev), cost=None,
-                        info=torch.zeros((1,), dtype=torch.int32, device=dev))
+                        info=torch.zeros((1,), dtype=torch.int32, device=dev), **empty)
         gallery_pairs = torch.stack([pairs[:, 0], pairs[:, 1] + T], dim=1)       # detections follow the tracks
         logits = self.match_gallery(torch.cat([track_feats, det_feats], dim=0), torch.cat([track_xyz, det_xyz], dim=0),
                                     gallery_pairs, count=count if live_only else None).contiguous()
         cost = A.association_cost(logits, pairs, count, T, D, **cost_args)
-        col4row, row4col, info = A.linear_assignment(cost)
-        c, r = col4row[0, :T], row4col[0, :D]
+        (col4row, row4col, info), block_info = self._assign(cost, T, D, 1, 1, False, blocks)
+        c, r = col4row[:T], row4col[:D]
         return dict(track_to_det=torch.where(c < D, c, torch.full_like(c, -1)),
                     det_to_track=torch.where(r < T, r, torch.full_like(r, -1)), pairs=pairs, count=count, logits=logits,
-                    cost=cost, info=info)
+                    cost=cost, info=info, **({} if block_info is None else {"block_info": block_info}))
 
     def track_step(self, bank, sweep, boxes, labels, scores, carry=None, carry_inv=None, min_points=2, num_classes=8,
                    cap=None, n=None, crop_args=None, born=None, kill=None, frame_limit=10, replace_all=False,
                    reset_on_match=False, propagate=True, suppress_threshold=0.15, live_only=False, truth=None,
-                   force_truth=False, decisions=None, **cost_args):
+                   force_truth=False, decisions=None, by_class=False, **cost_args):
         """One whole tracker frame on the device without a host read (pcr_amd/tracks.py; INTEGRATION.md "2e. Track
         state"; the split-bf16 guard calibrates on the first batch of a weight version, as in every inference entry
         point: run a frame eagerly before capturing): the sweep (P, C >= 3) and this frame's boxes (M <= bank.max_dets, bank.box_width) with labels and
@@ -719,7 +739,12 @@ class ReIDNet(nn.Module):
         decoded born / kill masks -- 'det_newborn' and 'track_false_positive', nothing is born or killed when the name is
         absent, as in the reference, whose updater makes tracks from decision lists only -- drive bank.update, and the dict
         gains det_decision, track_decision, born, kill and decode_info.  born= / kill= cannot be passed with it.  truth= /
-        force_truth= work on top unchanged.  propagate stays the bank's one flag for every missed track."""
+        force_truth= work on top unchanged.  propagate stays the bank's one flag for every missed track.
+
+        by_class: as in associate -- the assignment runs class by class over block ids made from the bank's and the frame's
+        labels on the device each frame (free slots and padded detections share the rest block), so one captured graph
+        follows changing classes; the dict gains block_info (num_classes + 1,).  It composes with live_only, decisions=
+        and truth=."""
         from pcr_amd import associate as A
         from pcr_amd import tracks as TR
         if truth is None and force_truth:
@@ -770,16 +795,19 @@ class ReIDNet(nn.Module):
         gallery_pairs = torch.stack([pairs[:, 0], pairs[:, 1] + C], dim=1)       # detections follow the bank's rows
         logits = self.match_gallery(bank.gallery, bank.gallery_xyz, gallery_pairs,
                                     count=count if live_only else None).contiguous()
+        blocks = (bank.labels, labels, num_classes) if by_class else None
         decoded = {}
         if ds is not None:
             decoded = self._associate_decisions(logits, pairs, count, C, D, ds, dist if ds["kind"] == "margin" else None,
-                                                cost_args)
+                                                cost_args, by_class=blocks)
             t2d, d2t, cost, info = (decoded.pop(k) for k in ("track_to_det", "det_to_track", "cost", "info"))
             born, kill = decoded["born"], decoded["kill"]
         else:
             cost = A.association_cost(logits, pairs, count, C, D, dist=dist, **cost_args)
-            col4row, row4col, info = A.linear_assignment(cost)
-            c, r = col4row[0, :C], row4col[0, :D]
+            (col4row, row4col, info), block_info = self._assign(cost, C, D, 1, 1, False, blocks)
+            if block_info is not None:
+                decoded["block_info"] = block_info
+            c, r = col4row[:C], row4col[:D]
             t2d = torch.where(c < D, c, torch.full_like(c, -1))
             d2t = torch.where(r < C, r, torch.full_like(r, -1))
         decisions, truth_out = (t2d, d2t), {}

@@ -172,6 +172,9 @@ SIGNATURES = {
     "pcr_assoc_cost_f32": "s FIIFFFfffFiiiS",
     "pcr_lsa_ok": "i iii",
     "pcr_lsa_f32": "s FIIFFIiiiS",
+    "pcr_lsa_blocks_ok": "i iii",
+    "pcr_lsa_blocks_f32": "s FIIIIFFIiiiS",
+    "pcr_assoc_blocks_i32": "s IIIIiiiiiS",
     "pcr_assoc_multi_ok": "i iiiii",
     "pcr_assoc_multi_ws_bytes": "i iiii",
     "pcr_assoc_cost_multi_f32": "s <AssocMultiParams>S",

@@ -137,6 +137,73 @@ def linear_assignment(cost, return_duals=False, out=None):
     return (col4row, row4col, info, u, v) if return_duals else (col4row, row4col, info)
 
 
+def linear_assignment_blocks(cost, row_block, col_block, num_blocks, return_duals=False, out=None):
+    """cost (R, C) float32, row_block (R,), col_block (C,) int32 -> col4row (R,), row4col (C,) int32 (-1 = unassigned),
+    info (num_blocks,) int32 [, u (R,), v (C,)].
+
+    The block rule of include/pcr.h: every block id g in [0, num_blocks) names the sub-problem cost[rows of g][columns of
+    g] (ascending original index), solved by linear_assignment's rules by a wave of its own and written back as original
+    indices; a row or column with any other id takes no part (-1, dual 0) and only the sub-problems' entries are read.
+    info[g] 0 = solved, 1 = block g holds a NaN or an infinity (its rows and columns are -1; the other blocks are solved).
+    One launch for all blocks.  out = (col4row, row4col, info[, u, v]) to write into."""
+    L.require_cuda(cost, row_block, col_block)
+    L.require_f32(cost)
+    L.require_i32(row_block, col_block)
+    if cost.dim() != 2 or not cost.is_contiguous():
+        raise L.PcrError("linear_assignment_blocks: cost must be a contiguous (R, C) tensor, got %s" % (tuple(cost.shape),))
+    R, C = cost.shape
+    G = int(num_blocks)
+    if row_block.shape != (R,) or col_block.shape != (C,) or not row_block.is_contiguous() or not col_block.is_contiguous():
+        raise L.PcrError("linear_assignment_blocks: row_block must be a contiguous (%d,) and col_block a (%d,) tensor"
+                         % (R, C))
+    lib = L.load()
+    if not lib.pcr_lsa_blocks_ok(R, C, G):
+        raise L.PcrError("linear_assignment_blocks: R=%d C=%d num_blocks=%d is out of range (pcr_lsa_blocks_ok)" % (R, C, G))
+    dev = cost.device
+    if out is not None:
+        col4row, row4col, info = out[0], out[1], out[2]
+        u, v = (out[3], out[4]) if return_duals else (None, None)
+        L.require_cuda(col4row, row4col, info, u, v)
+        L.require_i32(col4row, row4col, info)
+        L.require_f32(u, v)
+    else:
+        col4row = torch.empty((R,), dtype=torch.int32, device=dev)
+        row4col = torch.empty((C,), dtype=torch.int32, device=dev)
+        info = torch.empty((G,), dtype=torch.int32, device=dev)
+        u = torch.empty((R,), dtype=torch.float32, device=dev) if return_duals else None
+        v = torch.empty((C,), dtype=torch.float32, device=dev) if return_duals else None
+    if col4row.shape != (R,) or row4col.shape != (C,) or info.shape != (G,) or not col4row.is_contiguous() \
+            or not row4col.is_contiguous() or not info.is_contiguous():
+        raise L.PcrError("linear_assignment_blocks: out must hold col4row (%d,), row4col (%d,) and info (%d,)" % (R, C, G))
+    if u is not None and (u.shape != (R,) or v.shape != (C,) or not u.is_contiguous() or not v.is_contiguous()):
+        raise L.PcrError("linear_assignment_blocks: the duals must be u (%d,) and v (%d,)" % (R, C))
+    L.run.pcr_lsa_blocks_f32(cost, row_block, col_block, col4row, row4col, u, v, info, R, C, G, L.stream_ptr())
+    return (col4row, row4col, info, u, v) if return_duals else (col4row, row4col, info)
+
+
+def association_blocks(track_labels, det_labels, T, D, dd, td, num_classes=8, reduce=False):
+    """track_labels (T,), det_labels (D,) -> row_block (T + de*D,), col_block (D + te*T,) int32 and the number of blocks
+    num_classes + 1: the block ids of association_cost's (dd = td = 1) or association_cost_multi's matrix for
+    linear_assignment_blocks.  An object's block is its label when that lies in [0, num_classes), the rest block num_classes
+    otherwise (free bank slots, padded detections, foreign labels); a decision row or column takes its object's block."""
+    L.require_cuda(track_labels, det_labels)
+    T, D, dd, td = int(T), int(D), int(dd), int(td)
+    if track_labels.shape != (T,) or det_labels.shape != (D,):
+        raise L.PcrError("association_blocks: labels must be (T,) = (%d,) and (D,) = (%d,)" % (T, D))
+    tl, dl = _i32(track_labels), _i32(det_labels)
+    lib = L.load()
+    if not lib.pcr_assoc_multi_ok(T, D, dd, td, 0) or not lib.pcr_assoc_pairs_ok(0, 0, int(num_classes), 0):
+        raise L.PcrError("association_blocks: T=%d D=%d dd=%d td=%d num_classes=%d is out of range (pcr_assoc_multi_ok, "
+                         "pcr_assoc_pairs_ok)" % (T, D, dd, td, num_classes))
+    R, C = multi_shape(T, D, dd, td, reduce)
+    de, te = (int(dd > 0), int(td > 0)) if reduce else (dd, td)
+    row_block = torch.empty((R,), dtype=torch.int32, device=tl.device)
+    col_block = torch.empty((C,), dtype=torch.int32, device=tl.device)
+    if R + C:                            # the entry launches nothing for two empty outputs
+        L.run.pcr_assoc_blocks_i32(tl, dl, row_block, col_block, T, D, de, te, int(num_classes), L.stream_ptr())
+    return row_block, col_block, int(num_classes) + 1
+
+
 # ---- any set of decisions per side (pcr.h A3, "Any set of decisions") ----------------------------------------------------
 KINDS = {"margin": 0, "softmax": 1}
 

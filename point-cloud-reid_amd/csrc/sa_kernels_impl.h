@@ -476,7 +476,14 @@ static size_t sas_fixed_lds(int c1, int c3) {
   const int ncb = c1 >> 5, ncb3 = c3 >> 5;
   return ((size_t)(2 * ncb) * ncb * 128 + (size_t)(2 * ncb) * ncb3 * 128) * 16 + (size_t)(2 * c1 + c3) * 4 + (size_t)ncb * 64 * 16;
 }
-static size_t sas_krow_lds(int c1, int c3) { return sas_fixed_lds(c1, c3) + (size_t)kSasWaves * 6 * c3 * 4 + 16; }   // (+ the four MFMA tokens)
+static size_t sas_krow_lds(int c1, int c3) { return sas_fixed_lds(c1, c3) + 16; }   // (+ the four MFMA tokens)
+// the K-row form addresses a cloud's coordinates, table, indices and output with 32-bit byte offsets (SasBufTab), and
+// multiplies a point index by the table's row bytes in 24 bits
+__attribute__((unused)) static bool sas_krow_spans(int B, int N, int S, int K, int pqw, int c3) {
+  const size_t lim = 0x7FFFFFFFull;
+  return N <= (1 << 24) && (size_t)N * pqw * 4 <= lim && (size_t)B * N * 12 <= lim && (size_t)B * S * K * 4 <= lim &&
+         (size_t)B * S * c3 * 4 <= lim;
+}
 static size_t sas_rag_lds(int c1, int c3, int K, int waves, bool tab) {
   return sas_fixed_lds(c1, c3) + (size_t)waves * sas_rag_wave_ints(c3, K, tab) * 4;
 }
@@ -497,9 +504,9 @@ static bool sas_shape(int c1, int c2, int c3, int K, bool both_forms) {
 // accumulators into layer 3's, and the max over K starts from layer 3's accumulators (16-lane DPP groups) -- no LDS
 // activation tile, no workgroup barrier after the weights are staged.  The arithmetic (seeds, the order of the three
 // MFMAs of a product, signed-integer maxima, ReLU last) is sa_fused_kernel's, so the bits are the same.
-// Work item = lcm(32, K) rows of one cloud (K = 48: three blocks = two centres): the group maxima of an item meet in a
-// wave-private LDS strip, the item's centres leave from there.  Items of a cloud stay on one XCD (its table rows are
-// gathered by every item of the cloud: one L2 should hold them).
+// Work item = lcm(32, K) rows of one cloud (K = 48: three blocks = two centres): the group maxima fold into a running
+// maximum per centre that stays in registers across the item's blocks, and a centre leaves when its last group is in.
+// Items of a cloud stay on one XCD (its table rows are gathered by every item of the cloud: one L2 should hold them).
 constexpr int kSasCpi = 16;   // centres per item of the ragged form
 
 // the three layers of one 32-row block, shared by the K-row and the ragged form.  In: the row's neighbour i, its centre
@@ -521,6 +528,56 @@ __device__ __forceinline__ float add_row_bcast_f32(float s, float q, int p) {
   return r;
 }
 
+// Where a block's rows come from.  The ragged form hands SasBlock plain pointers: a 64-bit lane address per gather.
+struct SasPtrTab {
+  const float *xyz, *pq;
+  int pqw;
+  using row_t = const float *;
+  __device__ __forceinline__ bool any() const { return pq != nullptr; }
+  __device__ __forceinline__ row_t row(int i, int h) const { return pq + (size_t)i * pqw + 4 * h; }
+  __device__ __forceinline__ f32x4 piece(row_t r, int off) const { return *reinterpret_cast<const f32x4 *>(r + off); }
+  __device__ __forceinline__ f32x4 qpiece(int ci, int qoff, int p16, int h) const {
+    return *reinterpret_cast<const f32x4 *>(pq + (size_t)ci * pqw + qoff + (p16 >> 2) * 32 + 8 * (p16 & 3) + 4 * h);
+  }
+  __device__ __forceinline__ void delta(int i, int ci, float &dx, float &dy, float &dz) const {
+    dx = xyz[i * 3] - xyz[ci * 3];
+    dy = xyz[i * 3 + 1] - xyz[ci * 3 + 1];
+    dz = xyz[i * 3 + 2] - xyz[ci * 3 + 2];
+  }
+};
+// The K-row form addresses a cloud's table and coordinates through buffer resources (scalar base, 32-bit lane offset):
+// ONE multiply-add per row gives the lane offset of all of a block's 4 NCB table pieces, whose offsets inside the row are
+// immediates of the loads; a point's three coordinates are one 12-byte load.  (With pointers each gather built a 64-bit
+// address: v_lshl_add_u64 / v_add_co / v_addc_co chains.)  The host keeps a cloud's table and the launch's coordinates,
+// indices and output below 2^31 bytes and N within 24 bits (sas_krow_spans).
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t sas_rsrc(const void *p, int bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, bytes, 0x00020000);
+}
+struct SasBufTab {
+  __amdgpu_buffer_rsrc_t rxyz, rpq;   // all coordinates (the cloud's at byte xyz_b); the cloud's table
+  int xyz_b;
+  int pqw4;                 // bytes of a table row
+  bool on;                  // the launch has tables
+  int hoff, qlane;          // lane constants, bytes: 16 h; the lane's piece of a centre's Q row (SasBlock: lane p of a DPP row)
+  using row_t = int;
+  __device__ __forceinline__ bool any() const { return on; }
+  __device__ __forceinline__ row_t row(int i, int) const { return (int)__umul24(i, pqw4) + hoff; }
+  __device__ __forceinline__ f32x4 piece(row_t r, int off) const {
+    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rpq, r + off * 4, 0, 0));
+  }
+  __device__ __forceinline__ f32x4 qpiece(int ci, int, int, int) const {
+    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rpq, (int)__umul24(ci, pqw4) + qlane, 0, 0));
+  }
+  __device__ __forceinline__ void delta(int i, int ci, float &dx, float &dy, float &dz) const {
+    typedef float f32x3 __attribute__((ext_vector_type(3)));
+    const f32x3 p = __builtin_bit_cast(f32x3, __builtin_amdgcn_raw_buffer_load_b96(rxyz, (int)__umul24(i, 12), xyz_b, 0));
+    const f32x3 c = __builtin_bit_cast(f32x3, __builtin_amdgcn_raw_buffer_load_b96(rxyz, (int)__umul24(ci, 12), xyz_b, 0));
+    dx = p[0] - c[0];
+    dy = p[1] - c[1];
+    dz = p[2] - c[2];
+  }
+};
+
 template <int NCB, int NCB3, bool LO>
 struct SasBlock {
   static constexpr int C = 32 * NCB, NS = 2 * NCB;
@@ -528,14 +585,17 @@ struct SasBlock {
                                              const float *s_sh1, const float *s_sh2, const float *s_sh3, const f32x4 *s_wa,
                                              const bf16x8 *s_w2, const bf16x8 *s_w3, int lane, f32x16 (&y3)[NCB3],
                                              unsigned long long *tr = nullptr, int *tok = nullptr, bool xt = false) {
+    run_t(SasPtrTab{xyz, pq, pqw}, qoff, has_q, i, ci, s_sh1, s_sh2, s_sh3, s_wa, s_w2, s_w3, lane, y3, tr, tok, xt);
+  }
+  template <class TAB>
+  __device__ static __forceinline__ void run_t(const TAB &t, int qoff, bool has_q, int i, int ci, const float *s_sh1,
+                                               const float *s_sh2, const float *s_sh3, const f32x4 *s_wa, const bf16x8 *s_w2,
+                                               const bf16x8 *s_w3, int lane, f32x16 (&y3)[NCB3],
+                                               unsigned long long *tr = nullptr, int *tok = nullptr, bool xt = false) {
     // xt (pcr_sa_params.pq_has_xyz): the tables carry the coordinate term and layer 1's shift -- no coordinates are read
     float dxv = 0.f, dyv = 0.f, dzv = 0.f;
-    if (!xt) {
-      dxv = xyz[i * 3] - xyz[ci * 3];
-      dyv = xyz[i * 3 + 1] - xyz[ci * 3 + 1];
-      dzv = xyz[i * 3 + 2] - xyz[ci * 3 + 2];
-    }
-    run_d(dxv, dyv, dzv, pq, pqw, qoff, has_q, i, ci, s_sh1, s_sh2, s_sh3, s_wa, s_w2, s_w3, lane, y3, tr, tok, xt);
+    if (!xt) t.delta(i, ci, dxv, dyv, dzv);
+    run_dt(t, dxv, dyv, dzv, qoff, has_q, i, ci, s_sh1, s_sh2, s_sh3, s_wa, s_w2, s_w3, lane, y3, tr, tok, xt);
   }
   // the same with the row's point - centre given (the ball query's row table holds it)
   __device__ static __forceinline__ void run_d(float dxv, float dyv, float dzv, const float *pq, int pqw, int qoff, bool has_q,
@@ -543,6 +603,15 @@ struct SasBlock {
                                                const f32x4 *s_wa, const bf16x8 *s_w2, const bf16x8 *s_w3, int lane,
                                                f32x16 (&y3)[NCB3], unsigned long long *tr = nullptr, int *tok = nullptr,
                                                bool xt = false) {
+    run_dt(SasPtrTab{nullptr, pq, pqw}, dxv, dyv, dzv, qoff, has_q, i, ci, s_sh1, s_sh2, s_sh3, s_wa, s_w2, s_w3, lane, y3, tr,
+           tok, xt);
+  }
+  template <class TAB>
+  __device__ static __forceinline__ void run_dt(const TAB &t, float dxv, float dyv, float dzv, int qoff, bool has_q, int i,
+                                                int ci, const float *s_sh1, const float *s_sh2, const float *s_sh3,
+                                                const f32x4 *s_wa, const bf16x8 *s_w2, const bf16x8 *s_w3, int lane,
+                                                f32x16 (&y3)[NCB3], unsigned long long *tr = nullptr, int *tok = nullptr,
+                                                bool xt = false) {
 #ifdef PCR_SA_TRACE_BUILD   // (diagnostic builds: tr = the caller's record of this block, marks 6 / 7 = layer 1 / layer 2 done)
 #define PCR_BMARK(m) do { if (tr) tr[m] = __builtin_readcyclecounter(); } while (0)
 #else
@@ -561,9 +630,9 @@ struct SasBlock {
     f32x4 qv = {0.f, 0.f, 0.f, 0.f};
     if (has_q) {
       const int p16 = lane & 15;
-      if (p16 < 4 * NCB)
-        qv = *reinterpret_cast<const f32x4 *>(pq + (size_t)ci * pqw + qoff + (p16 >> 2) * 32 + 8 * (p16 & 3) + 4 * h);
+      if (p16 < 4 * NCB) qv = t.qpiece(ci, qoff, p16, h);
     }
+    const typename TAB::row_t prow = t.row(i, h);        // the neighbour's table row, this lane's half of a piece
     // ---- layer 1, one cout block at a time (the gathers of a block: 4 sixteen-byte pieces of the neighbour's row).
     // The 128-channel form has the registers (200 of its 256) to request ALL 16 pieces before the first block's MFMAs
     // instead of block by block -- four L2 round trips in a row were 30 % of its block (tools/trace_stream.py)
@@ -576,9 +645,8 @@ struct SasBlock {
       if constexpr (kAllP && PQ) {
 #pragma unroll
         for (int cb = 0; cb < NCB; cb++) {
-          const float *pr = pq + (size_t)i * pqw + cb * 32 + 4 * h;
 #pragma unroll
-          for (int g = 0; g < 4; g++) ppa[cb][g] = *reinterpret_cast<const f32x4 *>(pr + 8 * g);
+          for (int g = 0; g < 4; g++) ppa[cb][g] = t.piece(prow, cb * 32 + 8 * g);
         }
 #pragma unroll
         for (int cb = 0; cb < NCB; cb++)
@@ -590,11 +658,10 @@ struct SasBlock {
       for (int cb = 0; cb < NCB; cb++) {
         f32x4 pp[4];
         if constexpr (PQ) {
-          const float *pr = pq + (size_t)i * pqw + cb * 32 + 4 * h;
 #pragma unroll
           for (int g = 0; g < 4; g++) {
             if constexpr (kAllP) pp[g] = ppa[cb][g];
-            else pp[g] = *reinterpret_cast<const f32x4 *>(pr + 8 * g);
+            else pp[g] = t.piece(prow, cb * 32 + 8 * g);
           }
         }
         f32x16 acc;
@@ -633,9 +700,8 @@ struct SasBlock {
       if constexpr (kAllP) {
 #pragma unroll
         for (int cb = 0; cb < NCB; cb++) {
-          const float *pr = pq + (size_t)i * pqw + cb * 32 + 4 * h;
 #pragma unroll
-          for (int g = 0; g < 4; g++) ppa[cb][g] = *reinterpret_cast<const f32x4 *>(pr + 8 * g);
+          for (int g = 0; g < 4; g++) ppa[cb][g] = t.piece(prow, cb * 32 + 8 * g);
         }
 #pragma unroll
         for (int cb = 0; cb < NCB; cb++)
@@ -646,11 +712,10 @@ struct SasBlock {
 #pragma unroll
       for (int cb = 0; cb < NCB; cb++) {
         f32x4 pp[4];
-        const float *pr = pq + (size_t)i * pqw + cb * 32 + 4 * h;
 #pragma unroll
         for (int g = 0; g < 4; g++) {
           if constexpr (kAllP) pp[g] = ppa[cb][g];
-          else pp[g] = *reinterpret_cast<const f32x4 *>(pr + 8 * g);
+          else pp[g] = t.piece(prow, cb * 32 + 8 * g);
         }
 #pragma unroll
         for (int G = 0; G < 2; G++) {
@@ -666,7 +731,7 @@ struct SasBlock {
     };
     if (xt) {
       layer1_xt();
-    } else if (pq) {
+    } else if (t.any()) {
       if (has_q) layer1(std::true_type{}, std::true_type{});
       else layer1(std::false_type{}, std::true_type{});
     } else {
@@ -792,10 +857,9 @@ void sa_stream_kernel(Sa2Args a, int nblk_item, int ncen_item) {
   const bf16x8 *s_w3 = s_w2 + L::W2U;
   const float *s_sh = reinterpret_cast<const float *>(s_w3 + L::W3U);
   const f32x4 *s_wa = reinterpret_cast<const f32x4 *>(s_sh + 2 * C + C3);
-  float *s_gm = reinterpret_cast<float *>(smem) + L::kFixed / 4;   // [waves][6 groups][C3] group maxima of the wave's item
   const int tid = threadIdx.x, lane = tid & 63, j = lane & 31, h = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  int *s_tok = reinterpret_cast<int *>(s_gm + kSasWaves * 6 * C3);   // [4 SIMDs] MFMA tokens
+  int *s_tok = reinterpret_cast<int *>(smem) + L::kFixed / 4;        // [4 SIMDs] MFMA tokens
   if (tid < 4) s_tok[tid] = 0;
   sas_stage<NCB, NCB3>(smem, a.wp2, a.wp3, a.sh1, a.sh2, a.sh3, a.wap, 64 * kSasWaves);
   // on for the shapes that run two waves per SIMD (128-wide layers; measured -6..-9 % on pt1024's SA3 launch, same bits);
@@ -804,9 +868,37 @@ void sa_stream_kernel(Sa2Args a, int nblk_item, int ncen_item) {
   int *tok = ((NCB + NCB3 >= 6) != ((a.dbg & 1024) != 0)) ? s_tok + pcr_simd_id() : nullptr;
   const int K = a.K, gpc = K >> 4;                      // 16-row groups per centre
   const int nitem = (a.S + ncen_item - 1) / ncen_item;  // items per cloud
-  float *gm = s_gm + wave * 6 * C3;
   const bool has_q = a.pq && a.qoff >= 0;
   const bool xt = a.xt != 0 && has_q;
+  // The bookkeeping of a row is wave-uniform: K is a multiple of 16, so a 16-row group lies inside one centre and the
+  // centre of group g of an item is g / gpc -- for the groups 0..5 and gpc <= 6 that is (g ginv) >> 8, two scalar
+  // instructions; a lane takes the centre of its block's first or second group by j >> 4.  (Until round 15 every lane
+  // divided its row by K: a hoisted reciprocal, v_mul_hi_u32 and corrections per block.)
+  const int ginv = 256 / gpc + 1;
+  const int hi16 = j >> 4;
+  const int partner = (lane ^ 32) << 2;                 // ds_bpermute address of the lane that holds the other half's rows
+  // q / nitem of a claimed item on the scalar unit: one s_mul_hi_u32 and a correction (floor(n m / 2^32) with
+  // m = floor((2^32 - 1) / d) is n / d or one less for every n < 2^32)
+  const unsigned nitem_m = 0xFFFFFFFFu / (unsigned)nitem;
+  auto div_nitem = [&](int q, int &quo, int &rem) __attribute__((always_inline)) {
+    int d = (int)__umulhi((unsigned)q, nitem_m), r = q - d * nitem;
+    if (r >= nitem) {
+      d++;
+      r -= nitem;
+    }
+    quo = d;
+    rem = r;
+  };
+  SasBufTab tab;
+  tab.rxyz = sas_rsrc(a.xyz, a.B * a.N * 12);
+  const __amdgpu_buffer_rsrc_t rout = sas_rsrc(a.out, a.B * a.S * (C3 * 4));
+  tab.pqw4 = a.pqw * 4;
+  tab.on = a.pq != nullptr;
+  tab.hoff = 16 * h;
+  tab.qlane = (a.qoff + ((lane & 15) >> 2) * 32 + 8 * (lane & 3) + 4 * h) * 4;
+  // the output of a centre: cout block cb's 32 channels leave from the lanes h == 0 -- a 128-byte run of a (B,S,c3) row,
+  // or 32 strided words of (B,c3,S): lane offset + (centre, cout block) as the store's scalar offset
+  const int out_lane = a.out_pm ? j * 4 : j * a.S * 4, out_cen = a.out_pm ? C3 * 4 : 4, out_cb = a.out_pm ? 128 : 128 * a.S;
   // XCD-aware item order: workgroup w sits on XCD w % 8; the clouds b % 8 == x belong to XCD x
   const int xcd = blockIdx.x & 7, wrank = (blockIdx.x >> 3) * kSasWaves + wave, wstride = ((gridDim.x + 7 - xcd) >> 3) * kSasWaves;
   const int nq = ((a.B + 7 - xcd) >> 3) * nitem;                 // items of this XCD's clouds (the host keeps B x items < 2^31)
@@ -832,23 +924,39 @@ void sa_stream_kernel(Sa2Args a, int nblk_item, int ncen_item) {
     q_first = __builtin_amdgcn_readfirstlane(claim2());
     q_end = q_first + 2;
     pend = claim2();
-    bq = q_first / nitem;
-    item = q_first - bq * nitem;
+    div_nitem(q_first, bq, item);
   }
   // a block's row indices {neighbour, centre point} are requested one block ahead (the next item's first block during
-  // the current item's last): nothing else stands between a wave and its table gathers
+  // the current item's last): nothing else stands between a wave and its table gathers.  fetch_item points the index
+  // loads at an item (scalar byte offsets of its rows of idx and of its cloud's centre_idx); the fetches of its blocks
+  // follow.  (Round 15, measured and dropped: the request BEHIND the current block's gathers, so that the wait for the
+  // gathers does not include it -- SA1 -2 %, SA2 +-0, SA3 +1 % in one process, docs/DESIGN_HISTORY.md 4.1e.)
   int i_pre = 0, ci_pre = 0;
-  auto fetch_rows = [&](int bq2, int it2, int blk2) __attribute__((always_inline)) {
-    const size_t b2 = (size_t)bq2 * 8 + xcd;
-    const int c02 = it2 * ncen_item;
-    const int nc2 = a.S - c02 < ncen_item ? a.S - c02 : ncen_item;
-    int r2 = blk2 * 32 + j;
-    r2 = r2 < nc2 * K ? r2 : nc2 * K - 1;               // padding rows repeat the last one (a max does not care)
-    const int s2 = c02 + r2 / K;
-    ci_pre = a.centre_idx ? a.centre_idx[b2 * a.S + s2] : s2;
-    i_pre = a.idx[(b2 * a.S + c02) * (size_t)K + r2];
+  int f_c0 = 0, f_nc = 1, f_rows = 16, f_idx = 0, f_cen = 0;
+  const __amdgpu_buffer_rsrc_t ridx = sas_rsrc(a.idx, a.B * a.S * K * 4);
+  const __amdgpu_buffer_rsrc_t rcen = sas_rsrc(a.centre_idx ? a.centre_idx : a.idx, a.centre_idx ? a.B * a.S * 4 : 0);
+  auto fetch_item = [&](int bq2, int it2) __attribute__((always_inline)) {
+    const int bs2 = (bq2 * 8 + xcd) * a.S;
+    f_c0 = it2 * ncen_item;
+    f_nc = a.S - f_c0 < ncen_item ? a.S - f_c0 : ncen_item;
+    f_rows = f_nc * K;
+    f_idx = (bs2 + f_c0) * K * 4;
+    f_cen = bs2 * 4;
   };
-  if (q_first < nq) fetch_rows(bq, item, 0);
+  auto fetch_rows = [&](int blk2) __attribute__((always_inline)) {
+    int r2 = blk2 * 32 + j;
+    r2 = r2 < f_rows ? r2 : f_rows - 1;                 // padding rows repeat the last one (a max does not care)
+    const int cen0 = (2 * blk2 * ginv) >> 8;            // the centres of the block's two groups; a padding group has the
+    int cen1 = ((2 * blk2 + 1) * ginv) >> 8;            // last real row's centre, and that is the item's last
+    cen1 = cen1 < f_nc ? cen1 : f_nc - 1;
+    const int s2 = f_c0 + cen0 + (int)__umul24(hi16, cen1 - cen0);
+    ci_pre = a.centre_idx ? (int)__builtin_amdgcn_raw_buffer_load_b32(rcen, s2 * 4, f_cen, 0) : s2;
+    i_pre = (int)__builtin_amdgcn_raw_buffer_load_b32(ridx, r2 * 4, f_idx, 0);
+  };
+  if (q_first < nq) {
+    fetch_item(bq, item);
+    fetch_rows(0);
+  }
 #ifdef PCR_SA_TRACE_BUILD   // diagnostic builds only: waves 0 and 5 of a workgroup stamp the shader clock (one record per block)
   const bool tracing = (a.dbg & 256) && lane == 0 && (wave == 0 || wave == 5) && blockIdx.x < kTraceWgs / 2;
   unsigned long long *trace = g_rag_trace + (size_t)(2 * blockIdx.x + (wave ? 1 : 0)) * (2 + kTraceTiles * kTraceMarks);
@@ -871,9 +979,9 @@ void sa_stream_kernel(Sa2Args a, int nblk_item, int ncen_item) {
     const int c0 = item * ncen_item;
     const int nc = a.S - c0 < ncen_item ? a.S - c0 : ncen_item;
     const int rows = nc * K;
-    const float *xyz = a.xyz + b * a.N * 3;
-    const float *pq = a.pq ? a.pq + b * a.N * (size_t)a.pqw : nullptr;
-    const int bq_cur = bq, item_cur = item;
+    tab.xyz_b = (int)b * a.N * 12;
+    tab.rpq = sas_rsrc(a.pq ? a.pq + b * a.N * (size_t)a.pqw : a.xyz, a.pq ? a.N * tab.pqw4 : 0);
+    const int out_b = (int)b * a.S * (C3 * 4);
     if (!claimed) {
       qn = qi + wstride;
       item += step_i;                                   // the next item of this wave
@@ -890,9 +998,34 @@ void sa_stream_kernel(Sa2Args a, int nblk_item, int ncen_item) {
         q_end = qn + 2;
         pend = claim2();
       }
-      bq = qn / nitem;                                  // (qn >= nq: never used)
-      item = qn - bq * nitem;
+      div_nitem(qn, bq, item);                          // (qn >= nq: never used)
     }
+    // The maxima of a centre stay in registers: after the exchange with its partner every lane holds the maxima of its
+    // channel over the block's two 16-row groups; they fold into a running maximum per cout block that is carried
+    // across the item's blocks (K = 48: groups {0,1,2} and {3,4,5} of three blocks), and when a centre's last group is
+    // in, the lanes h == 0 store it -- max(relu(a), relu(b)) = relu(max(a, b)) on the bit patterns, so the ReLU is
+    // taken once, at the store.  (Until round 15 the group maxima met in a wave-private LDS strip: two ds_write per
+    // cout block and block, fences and a wave barrier per item, and a read-back loop with a division per element.)
+    int cen = 0, gin = 0;                               // the centre being folded, its groups so far
+    int run[NCB3];
+#pragma unroll
+    for (int cb = 0; cb < NCB3; cb++) run[cb] = (int)0x80000000;
+    auto fold = [&](const int (&m)[NCB3]) __attribute__((always_inline)) {
+#pragma unroll
+      for (int cb = 0; cb < NCB3; cb++) run[cb] = imax(run[cb], m[cb]);
+      if (++gin == gpc) {
+        const int so = out_b + (c0 + cen) * out_cen;
+        if (h == 0) {
+#pragma unroll
+          for (int cb = 0; cb < NCB3; cb++)
+            __builtin_amdgcn_raw_buffer_store_b32((unsigned)imax(run[cb], 0), rout, out_lane, so + cb * out_cb, 0);
+        }
+#pragma unroll
+        for (int cb = 0; cb < NCB3; cb++) run[cb] = (int)0x80000000;
+        gin = 0;
+        cen++;
+      }
+    };
     for (int blk = 0; blk < nblk_item; blk++) {
       if (blk * 32 >= rows) break;                      // (a partial last item: whole blocks of padding are skipped)
       PCR_SMARK(0);
@@ -900,46 +1033,36 @@ void sa_stream_kernel(Sa2Args a, int nblk_item, int ncen_item) {
       if (tracing && trace_it >= 0 && trace_it < kTraceTiles) trace[2 + trace_it * kTraceMarks + 5] = __builtin_amdgcn_s_memrealtime();
 #endif
       const int i = i_pre, ci = ci_pre;
-      if (blk + 1 < nblk_item && (blk + 1) * 32 < rows) fetch_rows(bq_cur, item_cur, blk + 1);
-      else if (qn < nq) fetch_rows(bq, item, 0);
+      if (blk + 1 < nblk_item && (blk + 1) * 32 < rows) {
+        fetch_rows(blk + 1);
+      } else if (qn < nq) {
+        fetch_item(bq, item);
+        fetch_rows(0);
+      }
       f32x16 y[NCB3];
-      SasBlock<NCB, NCB3, LO>::run(xyz, pq, a.pqw, a.qoff, has_q, i, ci, s_sh, s_sh + C, s_sh + 2 * C, s_wa, s_w2, s_w3, lane, y,
-                                   PCR_STR(), tok, xt);
+      SasBlock<NCB, NCB3, LO>::run_t(tab, a.qoff, has_q, i, ci, s_sh, s_sh + C, s_sh + 2 * C, s_wa, s_w2, s_w3, lane, y,
+                                     PCR_STR(), tok, xt);
       PCR_SMARK(1);
       // the maximum over a 16-row group = a maximum over eight of the lane's OWN registers plus one exchange with its
       // partner lane (20 instructions per cout block; the token-per-lane form needs a 4-step DPP reduction of every
       // register: 128)
+      int m0[NCB3], m1[NCB3];
 #pragma unroll
       for (int cb = 0; cb < NCB3; cb++) {
-        int m0 = __float_as_int(y[cb][0]), m1 = __float_as_int(y[cb][8]);   // (signed maxima of the bit patterns, ReLU last)
+        m0[cb] = __float_as_int(y[cb][0]), m1[cb] = __float_as_int(y[cb][8]);   // (signed maxima of the bit patterns, ReLU last)
 #pragma unroll
         for (int rr = 1; rr < 8; rr++) {
-          m0 = imax(m0, __float_as_int(y[cb][rr]));
-          m1 = imax(m1, __float_as_int(y[cb][8 + rr]));
+          m0[cb] = imax(m0[cb], __float_as_int(y[cb][rr]));
+          m1[cb] = imax(m1[cb], __float_as_int(y[cb][8 + rr]));
         }
-        m0 = imax(m0, __shfl_xor(m0, 32, 64));
-        m1 = imax(m1, __shfl_xor(m1, 32, 64));
-        if (h == 0) {
-          gm[(blk * 2) * C3 + cb * 32 + j] = __int_as_float(imax(m0, 0));
-          gm[(blk * 2 + 1) * C3 + cb * 32 + j] = __int_as_float(imax(m1, 0));
-        }
+        m0[cb] = imax(m0[cb], __builtin_amdgcn_ds_bpermute(partner, m0[cb]));   // (__shfl_xor(., 32) with its address hoisted)
+        m1[cb] = imax(m1[cb], __builtin_amdgcn_ds_bpermute(partner, m1[cb]));
       }
+      fold(m0);
+      if (blk * 32 + 16 < rows) fold(m1);               // (the second group of an item's last block can be padding)
       PCR_SMARK(2);
       PCR_SNEXT();
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    // the item's centres: max over their groups, centre-major so that (B,S,c3) rows leave as whole lines
-    for (int e = lane; e < nc * C3; e += 64) {
-      const int c = e / C3, o = e - c * C3;
-      const float *g = gm + (c * gpc) * C3 + o;
-      float m = g[0];
-      for (int k = 1; k < gpc; k++) m = fmaxf(m, g[k * C3]);
-      if (a.out_pm) a.out[(b * a.S + c0 + c) * (size_t)C3 + o] = m;
-      else a.out[(b * C3 + o) * (size_t)a.S + c0 + c] = m;
-    }
-    __builtin_amdgcn_wave_barrier();
   }
 #undef PCR_SMARK
 #undef PCR_STR
@@ -2637,7 +2760,7 @@ static int sa2_try(const pcr_sa_params &p, pcr_stream_t st_) {
     for (int nb = 3; nb >= 1; nb--)
       if ((32 * nb) % p.K == 0 && (!nblk_item || small_items)) { nblk_item = nb; ncen_item = 32 * nb / p.K; }
     const size_t lds_s = sas_krow_lds(p.c1, p.c3);
-    if (maxe && nblk_item && sas_shape_ok(p, false)) {
+    if (maxe && nblk_item && sas_shape_ok(p, false) && sas_krow_spans(p.B, p.N, p.S, p.K, p.D ? pqw : 0, p.c3)) {
       const long items = (long)p.B * ((p.S + ncen_item - 1) / ncen_item);
       long wgs = (items + kSasWaves - 1) / kSasWaves;
       const long resident = (long)pcr_cu_count() * ((ncb + ncb3 >= 6 || lds_s > (size_t)80 * 1024) ? 1 : 2);

@@ -852,7 +852,12 @@ typedef struct pcr_sa_params {
   /* arithmetic of layers 2 and 3 (layer 1 and the tables stay f32): PCR_PREC_F32 = f32-input MFMA, exact fmaf chains
    * (wps); PCR_PREC_BF16X3 = split bf16, three bf16 MFMAs per product with f32 accumulation; PCR_PREC_BF16 = plain bf16
    * activations and weights, f32 accumulation (BASELINE config 2 as stated).  wps_bf[l]: pcr_pack_weight_bf16x2_f32
-   * images of the matrices wps[l] holds.  Shapes the bf16 kernels do not cover run in f32. */
+   * images of the matrices wps[l] holds.  Shapes the bf16 kernels do not cover run in f32 (pcr_last_launch_arith says
+   * so).  Among them, not exhaustively (sa2_try is the rule, tests/sa_ref.py restates it): c1 or c2 no multiple of 32; a
+   * layer wider than 256; in the K-row kernel K no multiple of 16, and a layer 2 of up to 128 channels (one cout-block
+   * round) whose layer 1 cannot share its class on the matrix core (32 / 64 / 64, 64 / 32 / 32, 64 / 128 / 256); layer classes
+   * other than equal ones and (64 -> up to 128 channels) -- in particular 64 / 64 / c3 with 129 <= c3 <= 256, whose last
+   * layer would need two cout-block rounds behind a two-way layer 2, an instantiation the bf16 units do not hold. */
   int precision;
   const float *wps_bf[2];
   /* optional (ABI 11): pcr_pack_weight_f32 image of the (c1, 4) matrix [wa | shift[0]] -- the cout-split kernel feeds

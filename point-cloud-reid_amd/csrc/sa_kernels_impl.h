@@ -2415,6 +2415,10 @@ static int sa2_launch_one(const Sa2Args &a, bool maxe, size_t lds, hipStream_t s
 
 // wsel: 1 / 2 / 4 when both MFMA layers have the same cout class (specialised bodies), else 0
 // nr2 / nr: cout-block rounds of layer 2 / of the wider of the two layers
+// bf16 units: the mixed class (2 ways in layer 2, 1 way in layer 3) exists with ONE cout-block round only, <TB,1,2,1> --
+// with W3 = 1, NR = 1 wave w computes cout block w and nothing else, four blocks = 128 channels.  A last layer of 129 ..
+// 256 channels behind two 64-channel layers (nr == 2) is therefore refused here and in sa2_try, and runs in the f32
+// unit's <TB,2,0,0,1>.
 template <int TB>
 static int sa2_launch_tb(const Sa2Args &a, int nr, int nr2, int w2, int w3, bool maxe, size_t lds, hipStream_t st,
                          dim3 grid) {
@@ -2430,7 +2434,7 @@ static int sa2_launch_tb(const Sa2Args &a, int nr, int nr2, int w2, int w3, bool
     if (nr2 == 1 && !a.l1m) return -1;     // (the one-round instantiations are the bf-image ones: layer 1 on the matrix core)
     if (wsel == 44) return sa2_launch_one<TB, 1, 4, 4>(a, maxe, lds, st, grid);
     else if (wsel == 22) return sa2_launch_one<TB, 1, 2, 2>(a, maxe, lds, st, grid);
-    else if (wsel == 21) return sa2_launch_one<TB, 1, 2, 1>(a, maxe, lds, st, grid);
+    else if (wsel == 21 && nr == 1) return sa2_launch_one<TB, 1, 2, 1>(a, maxe, lds, st, grid);
     else if (wsel == 11 && nr == 1) return sa2_launch_one<TB, 1, 1, 1>(a, maxe, lds, st, grid);
     else if (wsel == 11 && nr2 == 1) return sa2_launch_one<TB, 2, 1, 1, 1>(a, maxe, lds, st, grid);
     else if (wsel == 11) return sa2_launch_one<TB, 2, 1, 1>(a, maxe, lds, st, grid);
@@ -2688,7 +2692,8 @@ static int sa2_try(const pcr_sa_params &p, pcr_stream_t st_) {
   const int nr2 = nr == 4 ? 4 : (n2 > 4 ? 2 : 1);
   if (kPrec != 0) {   // the bf16 units: max-from-accumulators epilogue, explicit shapes, at most two cout-block rounds
     const int v2 = sa_ways(n2), v3 = sa_ways(n3);
-    if (!maxe || nr > 2 || !((v2 == v3) || (v2 == 2 && v3 == 1))) return -1;
+    // (the mixed class has a single-round instantiation only: see sa2_launch_tb)
+    if (!maxe || nr > 2 || !((v2 == v3) || (v2 == 2 && v3 == 1 && nr == 1))) return -1;
   }
   // Tile choice.  Measured on MI355X (re-fitted after the epilogue / k-loop work, which halved what
   // a low residency costs): time per row ~ padding x wave imbalance x (1 + 1.0 / resident workgroups per CU); residency is bounded by LDS (160 KiB, 2 KiB granules),

@@ -27,11 +27,15 @@ def main(budget=None, seed=None, max_cases=None):
         g = torch.Generator().manual_seed(int(rng.integers(0, 1 << 30)))
         mode = int(rng.integers(0, 2))
         D = int(rng.choice([0, 3, 8, 16, 32, 64, 128]))
-        K = int(rng.choice([4, 16, 20, 32, 48, 64]))
-        N = int(rng.integers(max(K, 8), 600))
-        S = int(rng.integers(1, N + 1)) if mode == 1 else int(rng.integers(1, N + 1))
         widths = [(32, 32, 32), (64, 64, 64), (128, 128, 128), (64, 64, 128), (128, 128, 256), (24, 40, 72),
-                  (32, 64, 128), (256, 256, 256), (512, 512, 512), (128, 320, 384)][rng.integers(0, 10)]
+                  (32, 64, 128), (256, 256, 256), (512, 512, 512), (128, 320, 384), (64, 64, 256), (64, 256, 64),
+                  (64, 32, 32)][rng.integers(0, 13)]
+        # K above 96: the K-row tile kernel's TB = 4, 5, 6.  Layers 1 / 2 wider than 128 or a last layer wider than 256 have no
+        # tile of that many rows, and the generic kernel no LDS for them (pcr_sa_mlp_f32 answers PCR_ERR_INVALID)
+        tall = max(widths[:2]) <= 128 and widths[2] <= 256
+        K = int(rng.choice([4, 16, 20, 32, 48, 64, 80, 112, 144, 176] if tall else [4, 16, 20, 32, 48, 64]))
+        N = int(rng.integers(max(K, 8), 600))
+        S = int(rng.integers(1, min(N, 600 * 64 // K) + 1))                  # (no more rows per cloud than K = 64 draws)
         if max(widths) > 256 or (widths[0] > 128 and mode == 0):     # the wide (mul = 2 / 4) layers: 64 rows at most per tile
             D = int(rng.choice([0, 64, 128, 256]))
         B = int(rng.integers(1, 4))
@@ -49,7 +53,9 @@ def main(budget=None, seed=None, max_cases=None):
             last = w
         xyz = T.synthetic_clouds(B, N, int(rng.integers(0, 1 << 30)), "box")
         feat = torch.randn(B, D, N, generator=g) if D else None
-        idx = torch.randint(0, N, (B, S, K), generator=g, dtype=torch.int32)
+        # a group's entries are DISTINCT points (a prefix of a per-group permutation, N >= K): with repeated points a row
+        # that a kernel leaves out of the maximum goes unseen, its twin is still in (tests/sa_ref.py: groups)
+        idx = torch.rand(B, S, N, generator=g).argsort(dim=-1)[:, :, :K].to(torch.int32).contiguous()
         cnt = None
         if mode == 1 and rng.random() < 0.6:          # ball-query rows: entries [cnt, K) repeat entry 0
             cnt = torch.randint(1, K + 1, (B, S), generator=g, dtype=torch.int32)

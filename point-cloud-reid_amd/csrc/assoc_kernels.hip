@@ -12,12 +12,6 @@ constexpr int kPairChunks = PCR_ASSOC_MAX_OBJECTS / kWave;          // 64-object
 constexpr int kPairClasses = PCR_ASSOC_MAX_CLASSES;
 constexpr int kPairSlotsPerBlock = kPairThreads * 8;
 
-// LDS traffic of ONE wave needs no barrier, only program order
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
 // the class of object i if it takes part, -1 otherwise
 __device__ __forceinline__ int pair_class(const int *__restrict__ labels, const int *__restrict__ lengths, int i, int n,
                                           int ncls, int min_points) {
@@ -156,24 +150,6 @@ __global__ __launch_bounds__(256) void assoc_cost_pairs_kernel(const float *__re
 }
 
 // ---- linear sum assignment ----------------------------------------------------------------------------------------
-template <int CTRL>
-__device__ __forceinline__ float lsa_dpp(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), CTRL, 0xF, 0xF, false));
-}
-
-__device__ __forceinline__ float lsa_bcast(float v, int src) {
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src));
-}
-
-// minimum over the wave (no NaN among the operands): four exchanges inside each row of 16 lanes, then the four rows
-__device__ __forceinline__ float lsa_wave_min(float v) {
-  v = fminf(v, lsa_dpp<0xB1>(v));      // quad_perm [1,0,3,2]
-  v = fminf(v, lsa_dpp<0x4E>(v));      // quad_perm [2,3,0,1]
-  v = fminf(v, lsa_dpp<0x141>(v));     // row_half_mirror
-  v = fminf(v, lsa_dpp<0x140>(v));     // row_mirror
-  return fminf(fminf(lsa_bcast(v, 0), lsa_bcast(v, 16)), fminf(lsa_bcast(v, 32), lsa_bcast(v, 48)));
-}
-
 // How a search step reads entry (i, jj) of the SOLVED problem (nr <= nc rows i, columns jj).  Each reader keeps one
 // address space: LDS for the staged matrix, global for the other two.
 struct LsaLdsRows {                                       // the staged (nr, nc) copy
@@ -239,7 +215,7 @@ __device__ __forceinline__ int lsa_solve(const Rows &entry, float *u, int *c4r, 
           lmin = sh[k] < lmin ? sh[k] : lmin;
         }
       }
-      const float gmin = lsa_wave_min(lmin);
+      const float gmin = wave_reduce<true>(lmin, WaveMin());   // (no NaN among the operands)
       int j = -1, ri = -1;
       float mv = 0.f;
 #pragma unroll
@@ -249,7 +225,7 @@ __device__ __forceinline__ int lsa_solve(const Rows &entry, float *u, int *c4r, 
           if (bal) {
             const int owner = __builtin_amdgcn_readfirstlane(__ffsll((long long)bal) - 1);
             j = k * kWave + owner;
-            mv = lsa_bcast(sh[k], owner);
+            mv = wave_readlane(sh[k], owner);
             ri = __builtin_amdgcn_readlane(r4c[k], owner);
             if (lane == owner) done |= 1u << k;
           }

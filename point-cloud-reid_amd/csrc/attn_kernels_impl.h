@@ -8,6 +8,7 @@
 #define PCR_ATTN_PREC 0
 #endif
 #include "tile_dense.h"
+#include "wave_trace.h"
 
 #include <stdio.h>
 
@@ -62,7 +63,8 @@ __device__ __forceinline__ bool live_cloud(const AttnArgs &a, unsigned b) {
 // shader-clock stamps of the wave-autonomous kv kernel (trace builds only: -DPCR_SA_TRACE_BUILD, PCR_ATTN_TRACE=<file>);
 // one record of kATraceMarks stamps per cloud round of waves 0 and 5 of the first workgroups
 constexpr int kATraceWgs = 512, kATraceRecs = 24, kATraceMarks = 8;
-__device__ unsigned long long g_attn_trace[2 * kATraceWgs * kATraceRecs * kATraceMarks];
+using AttnTrace = WaveTrace<0, kATraceRecs, kATraceMarks, 2 * kATraceWgs>;
+__device__ unsigned long long g_attn_trace[AttnTrace::kCap * AttnTrace::kWords];
 
 // Algebra used by both kernels (the host folds it into the weights, see AttnPlan in
 // pcr_amd/engine.py): with h = relu(W0 xyz + b0) the position encoding is W2 h + b2, so
@@ -468,24 +470,16 @@ void attn_kv_stream64_kernel(AttnArgs a) {
 #pragma unroll
   for (int cb = 0; cb < 4; cb++) bias[cb] = s_bkv[cb * 32 + j];
   const int dh = D / p.nhead;
-#ifdef PCR_SA_TRACE_BUILD
-  const bool tracing = (a.dbg & 256) && lane == 0 && (wave == 0 || wave == 5) && blockIdx.x < kATraceWgs;
-  unsigned long long *trace = g_attn_trace + (size_t)(2 * blockIdx.x + (wave ? 1 : 0)) * (kATraceRecs * kATraceMarks);
-  int trace_it = 0;
-#define PCR_AMARK(m)                                                                                       \
-  do {                                                                                                     \
-    if (tracing && trace_it < kATraceRecs) trace[trace_it * kATraceMarks + (m)] = __builtin_readcyclecounter(); \
-  } while (0)
-#define PCR_ANEXT() trace_it++
-#else
-#define PCR_AMARK(m) do { } while (0)
-#define PCR_ANEXT() do { } while (0)
-#endif
+  // trace builds: waves 0 and 5 of the first workgroups stamp the shader clock
+  AttnTrace trace;
+  if constexpr (kTraceBuild)
+    trace.begin((a.dbg & 256) && lane == 0 && (wave == 0 || wave == 5) && blockIdx.x < kATraceWgs,
+                g_attn_trace, 2 * blockIdx.x + (wave ? 1 : 0));
   const long nB = GATE ? lw.total : (long)p.B;
   for (long c0 = (long)blockIdx.x * cpg; c0 < nB; c0 += (long)gridDim.x * cpg) {
     const bool live = c0 + cslot < nB;
     const long b = GATE ? (live ? lw.map(c0 + cslot) : 0) : c0 + cslot;
-    PCR_AMARK(4);
+    trace.mark(4);
     f32x16 kv[NKV];
 #pragma unroll
     for (int i = 0; i < NKV; i++)
@@ -499,7 +493,7 @@ void attn_kv_stream64_kernel(AttnArgs a) {
           __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(feat), 0, C2 * p.Sk * 4, 0x00020000);
       for (int blk = wsub; blk < nblk; blk += wpc2) {
         asm volatile("" ::: "memory");   // (the weight reads below stay inside the block loop: hoisted, they are 256 registers)
-        PCR_AMARK(0);
+        trace.mark(0);
         const int t = blk * 32 + j;
         const float px = xyz[3 * t], py = xyz[3 * t + 1], pz = xyz[3 * t + 2];
         f32x16 acc[4];
@@ -572,7 +566,7 @@ void attn_kv_stream64_kernel(AttnArgs a) {
           for (int cb = 0; cb < 4; cb++)
 #pragma unroll
             for (int r = 0; r < 16; r++) acc[cb][r] = 0.f;
-          PCR_AMARK(1);
+          trace.mark(1);
           const bf16x8 *wb = reinterpret_cast<const bf16x8 *>(s_w) + lane;
 #pragma unroll
           for (int s2 = 0; s2 < XS + 4; s2++) {
@@ -590,7 +584,7 @@ void attn_kv_stream64_kernel(AttnArgs a) {
             for (int cb = 0; cb < 4; cb++) acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[s2], wl[cb], acc[cb], 0, 0, 0);
           }
         }
-        PCR_AMARK(2);
+        trace.mark(2);
 #pragma unroll
         for (int r = 0; r < 16; r++) {
           acc[0][r] = elu1(acc[0][r] + bias[0]);
@@ -614,10 +608,10 @@ void attn_kv_stream64_kernel(AttnArgs a) {
             else kv[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(acc[ib][r], acc[2 + jb][r], kv[i], 0, 0, 0);
           }
         }
-        PCR_AMARK(3);
+        trace.mark(3);
       }
     }
-    PCR_AMARK(5);
+    trace.mark(5);
     ks0 += __shfl_xor(ks0, 32, 64);
     ks1 += __shfl_xor(ks1, 32, 64);
     if constexpr (ONEW) {
@@ -663,9 +657,9 @@ void attn_kv_stream64_kernel(AttnArgs a) {
           kvo[(size_t)D * D + 32 + j] = ks1;
         }
       }
-      PCR_AMARK(6);
-      PCR_AMARK(7);
-      PCR_ANEXT();
+      trace.mark(6);
+      trace.mark(7);
+      trace.next();
       continue;
     }
     // the waves of a cloud add their KV / key sums into the cloud's LDS area in wave order
@@ -689,7 +683,7 @@ void attn_kv_stream64_kernel(AttnArgs a) {
       }
       __syncthreads();
     }
-    PCR_AMARK(6);
+    trace.mark(6);
     // merge fold M[o][dd] = sum_{v in head(dd)} Wm[o][v] KV[dd][v] on the matrix core: four 32 x 32 tiles (o block, dd
     // block) over the cloud's waves, operands straight from LDS (A = Wm rows, B = KV rows with the head mask applied on
     // the read; DIAG: only the dd block's own 32 columns exist), then the packed image of M and the key sums
@@ -744,12 +738,10 @@ void attn_kv_stream64_kernel(AttnArgs a) {
       }
       for (int e = wsub * 64 + lane; e < D; e += 64 * wpc2) kvo[(size_t)D * D + e] = s_kt[e];
     }
-    PCR_AMARK(7);
-    PCR_ANEXT();
+    trace.mark(7);
+    trace.next();
     __syncthreads();   // the next round overwrites the reduction areas
   }
-#undef PCR_AMARK
-#undef PCR_ANEXT
 }
 
 #if PCR_ATTN_PREC != 0
@@ -1247,19 +1239,11 @@ void attn_apply_stream64_kernel(AttnArgs a) {
     for (int e = 0; e < 8; e++) v[e] = acc[8 * G + e];
     bf_split8(v, oh, ol, true);
   };
-#ifdef PCR_SA_TRACE_BUILD
-  const bool tracing = (a.dbg & 256) && lane == 0 && (wave == 0 || wave == 5) && blockIdx.x < kATraceWgs;
-  unsigned long long *trace = g_attn_trace + (size_t)(2 * blockIdx.x + (wave ? 1 : 0)) * (kATraceRecs * kATraceMarks);
-  int trace_it = 0;
-#define PCR_AMARK(m)                                                                                       \
-  do {                                                                                                     \
-    if (tracing && trace_it < kATraceRecs) trace[trace_it * kATraceMarks + (m)] = __builtin_readcyclecounter(); \
-  } while (0)
-#define PCR_ANEXT() trace_it++
-#else
-#define PCR_AMARK(m) do { } while (0)
-#define PCR_ANEXT() do { } while (0)
-#endif
+  // trace builds: waves 0 and 5 of the first workgroups stamp the shader clock
+  AttnTrace trace;
+  if constexpr (kTraceBuild)
+    trace.begin((a.dbg & 256) && lane == 0 && (wave == 0 || wave == 5) && blockIdx.x < kATraceWgs,
+                g_attn_trace, 2 * blockIdx.x + (wave ? 1 : 0));
   // item walk: (cloud, block) dealt block by block over the waves -- or, POOL, cloud by cloud (all blocks of a cloud on one
   // wave, in order: the running maximum / sum of the cloud live in two registers)
   const long nwav = (long)gridDim.x * kApsWaves, gw = (long)blockIdx.x * kApsWaves + wave;
@@ -1268,7 +1252,7 @@ void attn_apply_stream64_kernel(AttnArgs a) {
   float pmax = -INFINITY, psum = 0.f;
   for (long it = gw; POOL ? pc < nB : it < nitem; it += POOL ? 0 : nwav) {
     asm volatile("" ::: "memory");   // (weight reads stay inside the item loop)
-    PCR_AMARK(0);
+    trace.mark(0);
     const long vb = POOL ? pc : it / nblk;   // (GATE: the cloud's compact index)
     const int blk = POOL ? pblk : (int)(it - vb * nblk);
     const long b = GATE ? lw.map(vb) : vb;
@@ -1311,7 +1295,7 @@ void attn_apply_stream64_kernel(AttnArgs a) {
       for (int e = 0; e < 8; e++) xv[e] = xf[8 * s2 + e];
       bf_split8(xv, bh[s2], bl[s2], true);
     }
-    PCR_AMARK(1);
+    trace.mark(1);
     // ---- Q = elu(Wq [x ; h] + bq) + 1
     f32x16 q[ND];
 #pragma unroll
@@ -1336,7 +1320,7 @@ void attn_apply_stream64_kernel(AttnArgs a) {
         for (int cb = 0; cb < ND; cb++) q[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl[cb], bh[s2], q[cb], 0, 0, 0);
       }
     }
-    PCR_AMARK(2);
+    trace.mark(2);
     // the message-phase A operands (the cloud's matrix M): requested now, used after the normaliser
     bf16x8 mh[SD][ND], ml[SD][ND];
     {
@@ -1441,9 +1425,9 @@ void attn_apply_stream64_kernel(AttnArgs a) {
           for (int qq = 0; qq < 4; qq++) v[cb][4 * g + qq] = (v[cb][4 * g + qq] - mean) * inv * gv[qq] + bv[qq];
         }
     };
-    PCR_AMARK(3);
+    trace.mark(3);
     layernorm(m, std::integral_constant<int, ND>{}, s_c + 64, s_c + 128);
-    PCR_AMARK(4);
+    trace.mark(4);
     // ---- FFN0: relu(W0 [x ; msg]) (128 couts), operands: x re-converted from its f32 registers, msg from m
 #pragma unroll
     for (int s2 = 0; s2 < C1S; s2++) {
@@ -1486,7 +1470,7 @@ void attn_apply_stream64_kernel(AttnArgs a) {
 #pragma unroll
       for (int G = 0; G < 2; G++) to_ops(f[cb], G, bh[2 * cb + G], bl[2 * cb + G]);
     }
-    PCR_AMARK(5);
+    trace.mark(5);
     // ---- FFN1 (64 couts), LayerNorm, residual, store
     f32x16 o[NOB];
 #pragma unroll
@@ -1511,7 +1495,7 @@ void attn_apply_stream64_kernel(AttnArgs a) {
         for (int cb = 0; cb < NOB; cb++) o[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl[cb], bh[s2], o[cb], 0, 0, 0);
       }
     }
-    PCR_AMARK(6);
+    trace.mark(6);
     layernorm(o, std::integral_constant<int, NOB>{}, s_c + 192, s_c + 192 + 32 * NOB);
     if constexpr (C1S == 2 * NOB) {   // cout == c1
       if (p.residual) {
@@ -1619,11 +1603,9 @@ void attn_apply_stream64_kernel(AttnArgs a) {
         }
     }
     __builtin_amdgcn_wave_barrier();   // (the key-sum strip is rewritten by the next item)
-    PCR_AMARK(7);
-    PCR_ANEXT();
+    trace.mark(7);
+    trace.next();
   }
-#undef PCR_AMARK
-#undef PCR_ANEXT
 }
 
 // ---- the same wave-autonomous form at d = c1 = cout = 128 (SA3's self-attention: q_pos, residual, no trailing conv) --------
@@ -2231,24 +2213,8 @@ static int attn_check(const pcr_attn_params &p) {
 }
 
 static void attn_dump_trace(const char *path, const char *tag, int wgs, int B, int Sk) {
-  static int launches = 0;
-  static const int skip = pcr_tune_int("PCR_SA_TRACE_SKIP");
-  launches++;
-  if (launches <= skip || launches > skip + 8) return;
-  static std::vector<unsigned long long> host(2 * kATraceWgs * kATraceRecs * kATraceMarks);
-  if (hipDeviceSynchronize() != hipSuccess) return;
-  if (hipMemcpyFromSymbol(host.data(), HIP_SYMBOL(g_attn_trace), host.size() * sizeof(unsigned long long)) != hipSuccess) return;
-  FILE *f = fopen(path, "a");
-  if (!f) return;
-  const int n = 2 * (wgs < kATraceWgs ? wgs : kATraceWgs);
-  fprintf(f, "launch %d kernel %s wgs %d B %d Sk %d\n", launches, tag, wgs, B, Sk);
-  for (int w = 0; w < n; w++) {
-    const unsigned long long *t = host.data() + (size_t)w * (kATraceRecs * kATraceMarks);
-    fprintf(f, "wg %d", w);
-    for (int i = 0; i < kATraceRecs * kATraceMarks; i++) fprintf(f, " %llu", t[i]);
-    fprintf(f, "\n");
-  }
-  fclose(f);
+  wave_trace_dump<AttnTrace>(path, HIP_SYMBOL(g_attn_trace), 2 * wgs, "kernel %s wgs %d B %d Sk %d\n", tag, wgs, B,
+                             Sk);
 }
 
 // gated launches (pcr_live): the caller's count, period and offset travel in AttnArgs; false = not a valid gate

@@ -345,26 +345,16 @@ __global__ __launch_bounds__(kEdgeThreads) void edge_max_lds_kernel(const EdgeMa
 // lanes, dh a power of two); the output tile is transposed through LDS into channel-major msg (B,C,N).
 __device__ __forceinline__ float edge_elu1(float x) { return x > 0.f ? x + 1.0f : __expf(x); }
 
-template <int CTRL>
-__device__ __forceinline__ float dpp_f32(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
-}
-// sum over the DH lanes of a head, every lane gets the total.  DH = 16 / 32: DPP adds inside the 16-lane row
-// (lane ^ 1, lane ^ 2, other quad of the half, other half of the row -- the same pairings as the xor butterfly, so
-// the result is bit-identical) + one ds_swizzle across the two rows; the generic form is five ds_bpermute round
-// trips per value, which is what this kernel spent its time on.
+// sum over the DH lanes of a head, every lane gets the total.  DH = 16 / 32: the row reduction (+ one ds_swizzle across the
+// two rows); the generic form is five ds_bpermute round trips per value, which is what this kernel spent its time on.
 template <int DH>
 __device__ __forceinline__ float head_sum(float a, int dh) {
-  if constexpr (DH == 16 || DH == 32) {
-    a += dpp_f32<0xB1>(a);
-    a += dpp_f32<0x4E>(a);
-    a += dpp_f32<0x141>(a);
-    a += dpp_f32<0x140>(a);
-    if constexpr (DH == 32) a += __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(a), 0x401F));   // lane ^ 16
-  } else {
+  if constexpr (DH == 16) return row_sum(a);
+  else if constexpr (DH == 32) return half_sum(a);
+  else {
     for (int m = 1; m < dh; m <<= 1) a += __shfl_xor(a, m, 64);
+    return a;
   }
-  return a;
 }
 
 template <int DH>

@@ -7,47 +7,6 @@
 
 namespace {
 // ------------------------------------------------------------------ pool + head ----
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m, 64));
-  return v;
-}
-
-// the same reductions without LDS round trips: four DPP steps inside a row of 16 lanes (xor 1, xor 2, half-row mirror, row
-// mirror: afterwards every lane holds its row's result), then the four rows' results by v_readlane.  (__shfl_xor is
-// ds_bpermute: six dependent LDS round trips per reduction, and pool_head_kernel_t does 128 of them per pair.)
-template <int CTRL>
-__device__ __forceinline__ float dpp_f32(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float wave_sum_dpp(float v) {
-  v += dpp_f32<0xB1>(v);
-  v += dpp_f32<0x4E>(v);
-  v += dpp_f32<0x141>(v);
-  v += dpp_f32<0x140>(v);
-  const float a = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 0));
-  const float b = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 16));
-  const float c = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 32));
-  const float d = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 48));
-  return (a + b) + (c + d);
-}
-__device__ __forceinline__ float wave_max_dpp(float v) {
-  v = fmaxf(v, dpp_f32<0xB1>(v));
-  v = fmaxf(v, dpp_f32<0x4E>(v));
-  v = fmaxf(v, dpp_f32<0x141>(v));
-  v = fmaxf(v, dpp_f32<0x140>(v));
-  const float a = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 0));
-  const float b = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 16));
-  const float c = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 32));
-  const float d = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 48));
-  return fmaxf(fmaxf(a, b), fmaxf(c, d));
-}
-
 // GroupNorm of a length-n vector in LDS (one sample), groups of n/g channels; in place.
 __device__ __forceinline__ void vec_groupnorm(float *v, int n, int g, const float *gamma, const float *beta) {
   const int gs = n / g;
@@ -165,7 +124,7 @@ __global__ __launch_bounds__(kThreads) void pool_head_kernel_t(std::conditional_
 #pragma unroll
     for (int u = 0; u < 4; u++) {
       const int c = c0 + u * NW;
-      const float m1 = wave_max(mx[u]), s1 = wave_sum(sm[u]);
+      const float m1 = wave_max_shfl(mx[u]), s1 = wave_sum_shfl(sm[u]);
       if (lane == 0 && c < C) { x[c] = m1; x[C + c] = s1 / (float)(2 * L); }
     }
   }
@@ -214,7 +173,7 @@ __global__ __launch_bounds__(kThreads) void pool_head_kernel_t(std::conditional_
   vec_groupnorm(z, n, p.groups, p.gn2_g, p.gn2_b);
   float part = 0.f;
   if (tid < n) part = fmaxf(z[tid] + x[tid], 0.f) * p.w_out[tid];
-  part = wave_sum(part);
+  part = wave_sum_shfl(part);
   if (lane == 0) y[wave] = part;  // y is free after the second matvec
   __syncthreads();
   if (tid == 0) {
@@ -237,8 +196,8 @@ __global__ __launch_bounds__(kThreads) void pool_both_kernel(const float *__rest
       mx = fmaxf(mx, a);
       sm += a;
     }
-    mx = wave_max(mx);
-    sm = wave_sum(sm);
+    mx = wave_max_shfl(mx);
+    sm = wave_sum_shfl(sm);
     if (lane == 0) { out[b * 2 * C + c] = mx; out[b * 2 * C + C + c] = sm / (float)L; }
   }
 }
@@ -1024,7 +983,7 @@ __global__ __launch_bounds__(kThreads) void max_over_l_kernel(const float *__res
   const float *p = x + row * L;
   float m = -INFINITY;
   for (int i = lane; i < L; i += 64) m = fmaxf(m, p[i]);
-  m = wave_max(m);
+  m = wave_max_shfl(m);
   if (lane == 0) out[(row % C) * B + row / C] = m;
 }
 

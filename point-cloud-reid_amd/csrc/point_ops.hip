@@ -142,11 +142,6 @@ __device__ __forceinline__ uint32_t fps_tie_key(int k, int n, int block, int log
 // in-register DPP moves inside 16-lane rows, v_readlane across rows and a 4-entry LDS slot across
 // waves.  (Only for coordinates: there d2 >= 0 > -1, so the reference's "best = -1" start never
 // matters; the distance-matrix variant keeps the literal per-thread scan of fps_kernel.)
-template <int CTRL>
-__device__ __forceinline__ uint32_t dpp_u32(uint32_t v) {
-  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, true);
-}
-
 template <int PPT, int NT>
 __global__ __launch_bounds__(NT) void fps_fast_kernel(const float *__restrict__ xyz, float *__restrict__ temp,
                                                        int *__restrict__ idxs, int n, int m, int block,
@@ -190,15 +185,15 @@ __global__ __launch_bounds__(NT) void fps_fast_kernel(const float *__restrict__ 
     }
 #define PCR_FPS_STEP(CTRL)                                         \
     {                                                              \
-      const uint32_t oh = dpp_u32<CTRL>(hi), ol = dpp_u32<CTRL>(lo); \
+      const uint32_t oh = wave_dpp<CTRL>(hi), ol = wave_dpp<CTRL>(lo); \
       const bool take = oh > hi || (oh == hi && ol > lo);          \
       hi = take ? oh : hi;                                         \
       lo = take ? ol : lo;                                         \
     }
-    PCR_FPS_STEP(0xB1)   // lane ^ 1
-    PCR_FPS_STEP(0x4E)   // lane ^ 2
-    PCR_FPS_STEP(0x141)  // row_half_mirror
-    PCR_FPS_STEP(0x140)  // row_mirror: every lane of a 16-lane row now holds the row maximum
+    PCR_FPS_STEP(kDppXor1)         // (row_reduce's four steps on a 64-bit key held as two words)
+    PCR_FPS_STEP(kDppXor2)
+    PCR_FPS_STEP(kDppHalfMirror)
+    PCR_FPS_STEP(kDppRowMirror)
 #undef PCR_FPS_STEP
     unsigned long long key = 0ull;
 #pragma unroll
@@ -262,18 +257,6 @@ __device__ __forceinline__ V sqdist_terms(V dx, V dy, V dz) {
   const V c = dz * dz;
   const V s = a + b;
   return s + c;
-}
-
-__device__ __forceinline__ uint32_t dpp_max_u32(uint32_t v) {
-  uint32_t o;
-  o = dpp_u32<0xB1>(v); v = o > v ? o : v;
-  o = dpp_u32<0x4E>(v); v = o > v ? o : v;
-  o = dpp_u32<0x141>(v); v = o > v ? o : v;
-  o = dpp_u32<0x140>(v); v = o > v ? o : v;
-  const uint32_t a = (uint32_t)__builtin_amdgcn_readlane((int)v, 0), b = (uint32_t)__builtin_amdgcn_readlane((int)v, 16);
-  const uint32_t c = (uint32_t)__builtin_amdgcn_readlane((int)v, 32), d = (uint32_t)__builtin_amdgcn_readlane((int)v, 48);
-  const uint32_t ab = a > b ? a : b, cd = c > d ? c : d;
-  return ab > cd ? ab : cd;
 }
 
 // lane `l` (wave-uniform) of a register := a wave-uniform value (v_writelane_b32; this clang has no builtin for it, and on
@@ -419,7 +402,7 @@ __device__ __forceinline__ int fps_tie_pick(const uint32_t (&t)[2 * PP], uint32_
     const uint32_t l01 = l0 > l1 ? l0 : l1;
     lo = l01 > lo ? l01 : lo;
   }
-  lo = dpp_max_u32(lo);
+  lo = wave_reduce(lo, WaveMax());
   return (int)(0x3FFFFFu - (lo & 0x3FFFFFu));
 }
 
@@ -463,7 +446,7 @@ __global__ __launch_bounds__(64) void fps_wave_kernel(const float *__restrict__ 
       const uint32_t m01 = t[2 * p] > t[2 * p + 1] ? t[2 * p] : t[2 * p + 1];
       mx = m01 > mx ? m01 : mx;
     }
-    const uint32_t best = dpp_max_u32(mx);
+    const uint32_t best = wave_reduce(mx, WaveMax());
     if (!fps_unique_pick<PP>(t, mx, best, old)) old = fps_tie_pick<PP>(t, best, [&](int p) { return low[p]; });
     if (lane == 0) idxs[j] = old;
   }
@@ -608,7 +591,7 @@ __global__ __launch_bounds__(64) void fps_bq_wave_kernel(const float *__restrict
     }
     if (j + 1 >= m) break;
     // ---- the next pick (fps_wave_kernel): the maximum of the running minima, the reference's tie rule
-    const uint32_t best = dpp_max_u32(mx);
+    const uint32_t best = wave_reduce(mx, WaveMax());
     if (!fps_unique_pick<PP>(t, mx, best, old)) {   // rare: the tie keys are derived here, not kept in registers (the
       // opaque lane keeps them from being hoisted out of the pick loop again)
       int lane_o = lane;
@@ -1215,17 +1198,6 @@ __global__ void three_interp_bwd_kernel(const float *__restrict__ grad_out,
   }
 }
 
-// inclusive prefix sum over the 64 lanes (row shifts inside the 16-lane rows, then the two row broadcasts)
-__device__ __forceinline__ int pcr_wave_incl_scan_i32(int x) {
-  x += __builtin_amdgcn_update_dpp(0, x, 0x111, 0xF, 0xF, false);   // row_shr:1
-  x += __builtin_amdgcn_update_dpp(0, x, 0x112, 0xF, 0xF, false);   // row_shr:2
-  x += __builtin_amdgcn_update_dpp(0, x, 0x114, 0xF, 0xF, false);   // row_shr:4
-  x += __builtin_amdgcn_update_dpp(0, x, 0x118, 0xF, 0xF, false);   // row_shr:8
-  x += __builtin_amdgcn_update_dpp(0, x, 0x142, 0xA, 0xF, false);   // row_bcast:15 -> rows 1, 3
-  x += __builtin_amdgcn_update_dpp(0, x, 0x143, 0xC, 0xF, false);   // row_bcast:31 -> rows 2, 3
-  return x;
-}
-
 constexpr int kKnnPThreads = 256;
 constexpr int kKnnCap = 256;  // candidates per query the fast path can rank (4 per lane)
 
@@ -1296,7 +1268,7 @@ __device__ __forceinline__ void knn_emit_from_candidates(unsigned long long *can
     // the exact 64-bit path, which sorts the RAW bits)
     const uint32_t key = lane < total ? knn_tagged_key(cand32[2 * lane + 1], lane) : (kKnnPadKey | (uint32_t)lane);
     const uint32_t sk = pcr_wave_sort_posf32(key, lane);
-    const uint32_t nx = (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)sk, 0x130, 0xF, 0xF, false);   // lane + 1
+    const uint32_t nx = wave_dpp_or<kDppWaveShl1>(~0u, sk);   // lane + 1 (lane 63: all ones)
     const bool tie = lane < K && ((sk ^ nx) < 64u);
     if (__ballot(tie) == 0ull) {
       const int v = (int)cand32[2 * (sk & 63u)];
@@ -1468,7 +1440,7 @@ __global__ __launch_bounds__(kKnnPThreads) void knn_prefix_reg_kernel(const floa
       }
 #undef PCR_KW1
       const int mycnt = __popc(w);
-      const int incl = pcr_wave_incl_scan_i32(mycnt);
+      const int incl = wave_incl_scan(mycnt);
       total = __builtin_amdgcn_readlane(incl, 63);
       if (total <= kKnnCap) {
         int pos = incl - mycnt;
@@ -1637,7 +1609,7 @@ __global__ __launch_bounds__(NT) void knn_prefix_lds_kernel(const float *__restr
     int mycnt = 0;
 #pragma unroll
     for (int u = 0; u < NW; u++) mycnt += __popc(w[u]);
-    const int incl = pcr_wave_incl_scan_i32(mycnt);
+    const int incl = wave_incl_scan(mycnt);
     const int total = __builtin_amdgcn_readlane(incl, 63);
     if (total <= kKnnCap) {
       uint32_t *cand32 = reinterpret_cast<uint32_t *>(cand);

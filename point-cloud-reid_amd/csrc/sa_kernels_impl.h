@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "tile_dense.h"
+#include "wave_trace.h"
 
 // 1: the first weight fragments of layers 2 AND 3 are requested one phase early; 2: layer 3 only (layer 2's
 // would stay live across the gather / max-pool phases and push the kernel over 192 VGPRs = one workgroup per CU)
@@ -134,10 +135,6 @@ __global__ __launch_bounds__(kThreads) void sa_mlp_kernel(SaArgs a) {
 __device__ __forceinline__ float relu_bits(float v) {
   const int b = __float_as_int(v);
   return __int_as_float(b > 0 ? b : 0);
-}
-template <int CTRL>
-__device__ __forceinline__ int dpp_i32(int v) {
-  return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, true);
 }
 __device__ __forceinline__ int imax(int a, int b) { return a > b ? a : b; }
 
@@ -381,10 +378,7 @@ __global__ __launch_bounds__(kThreads) void sa_fused_kernel(Sa2Args a) {
         for (int r = 0; r < 16; r++) {
           const int o = cb * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
           int v = __float_as_int(acc[r]);
-          v = imax(v, dpp_i32<0xB1>(v));    // quad_perm [1,0,3,2]  : lane ^ 1
-          v = imax(v, dpp_i32<0x4E>(v));    // quad_perm [2,3,0,1]  : lane ^ 2
-          v = imax(v, dpp_i32<0x141>(v));   // row_half_mirror      : other quad of the 8-lane half
-          v = imax(v, dpp_i32<0x140>(v));   // row_mirror           : other half of the 16-lane row
+          v = row_reduce(v, WaveMax());
           if ((l31 & 15) == 0) gmax[o * NG + tb * 2 + (l31 >> 4)] = __int_as_float(imax(v, 0));   // ceil32(c3) rows
         }
       };
@@ -447,7 +441,9 @@ inline bool sas_claims(int c1, int c3, int N) {
   return N >= (min_n_t > 0 ? min_n_t : 1024) && c1 <= max_c && c3 <= max_c;
 }
 constexpr int kTraceWgs = 1024, kTraceTiles = 24, kTraceMarks = 8;
-__device__ unsigned long long g_rag_trace[kTraceWgs * (2 + kTraceTiles * kTraceMarks)];
+using SaTrace = WaveTrace<2, kTraceTiles, kTraceMarks, kTraceWgs>;   // (the two header words: sa_rag_kernel's hardware ids)
+using SaSkipTrace = WaveTrace<2, kTraceTiles, kTraceMarks, kTraceWgs, true>;
+__device__ unsigned long long g_rag_trace[SaTrace::kCap * SaTrace::kWords];
 constexpr int kSasWaves = 8;
 
 // ---- launch shapes: ONE definition of each rule, read by sa2_try in all three units and by the f32 unit's exported shape
@@ -612,11 +608,7 @@ struct SasBlock {
                                                 const f32x4 *s_wa, const bf16x8 *s_w2, const bf16x8 *s_w3, int lane,
                                                 f32x16 (&y3)[NCB3], unsigned long long *tr = nullptr, int *tok = nullptr,
                                                 bool xt = false) {
-#ifdef PCR_SA_TRACE_BUILD   // (diagnostic builds: tr = the caller's record of this block, marks 6 / 7 = layer 1 / layer 2 done)
-#define PCR_BMARK(m) do { if (tr) tr[m] = __builtin_readcyclecounter(); } while (0)
-#else
-#define PCR_BMARK(m) do { (void)tr; } while (0)
-#endif
+    // (tr = the caller's trace row of this block, marks 6 / 7 = layer 1 / layer 2 done)
     const int j = lane & 31, h = lane >> 5;
     auto cvec = [&](const float *base, int cb, int g) __attribute__((always_inline)) {
       return *reinterpret_cast<const f32x4 *>(base + 32 * cb + 8 * g + 4 * h);
@@ -737,11 +729,11 @@ struct SasBlock {
     } else {
       layer1(std::false_type{}, std::false_type{});
     }
-    PCR_BMARK(6);
+    wave_trace_stamp(tr, 6);
     // (round 6, measured and dropped: taking the token BEFORE layer 1 -- after its gathers have landed -- so that all of a
     // block's f32 VALU work runs inside the holder: pt1024 SA3 2.117 -> 2.200 ms, profiles/r06_inproc_ab.txt)
     mfma_token_acquire(tok, lane);
-    PCR_BMARK(3);      // (K-row form: token taken; the ragged form's caller overwrites mark 3 with its own)
+    wave_trace_stamp(tr, 3);      // (K-row form: token taken; the ragged form's caller overwrites mark 3 with its own)
     // ---- layer 2 (normal orientation: its accumulators convert into layer 3's operand)
     {
       f32x16 y[NCB];
@@ -784,8 +776,7 @@ struct SasBlock {
           bf_split8(v, bh[2 * cb + G], bl[2 * cb + G], LO);
         }
     }
-    PCR_BMARK(7);
-#undef PCR_BMARK
+    wave_trace_stamp(tr, 7);
     // ---- layer 3 TRANSPOSED (activations as the A operand, the same weight image as B)
     // (round 6, measured and dropped: these seeds from an LDS table that holds every shift four times over -- four
     // ds_read_b128 that land in the accumulator registers instead of sixteen v_mov per cout block: the three K-row launches of
@@ -957,24 +948,15 @@ void sa_stream_kernel(Sa2Args a, int nblk_item, int ncen_item) {
     fetch_item(bq, item);
     fetch_rows(0);
   }
-#ifdef PCR_SA_TRACE_BUILD   // diagnostic builds only: waves 0 and 5 of a workgroup stamp the shader clock (one record per block)
-  const bool tracing = (a.dbg & 256) && lane == 0 && (wave == 0 || wave == 5) && blockIdx.x < kTraceWgs / 2;
-  unsigned long long *trace = g_rag_trace + (size_t)(2 * blockIdx.x + (wave ? 1 : 0)) * (2 + kTraceTiles * kTraceMarks);
-  int trace_it = -(a.dbg >> 16);       // (PCR_SA_DBG bits 16..: blocks to skip before the kTraceTiles recorded ones)
-#define PCR_SMARK(m)                                                                                   \
-  do {                                                                                                 \
-    if (tracing && trace_it >= 0 && trace_it < kTraceTiles) trace[2 + trace_it * kTraceMarks + (m)] = __builtin_readcyclecounter(); \
-  } while (0)
-#define PCR_STR() ((tracing && trace_it >= 0 && trace_it < kTraceTiles) ? trace + 2 + trace_it * kTraceMarks : nullptr)
-#define PCR_SNEXT() trace_it++
-#else
-#define PCR_SMARK(m) do { } while (0)
-#define PCR_STR() nullptr
-#define PCR_SNEXT() do { } while (0)
-#endif
+  // trace builds: waves 0 and 5 of a workgroup stamp the shader clock, one row per block (PCR_SA_DBG bits 16..: blocks to
+  // skip before the kTraceTiles recorded ones)
+  SaSkipTrace trace;
+  if constexpr (kTraceBuild)
+    trace.begin((a.dbg & 256) && lane == 0 && (wave == 0 || wave == 5) && blockIdx.x < kTraceWgs / 2,
+                g_rag_trace, 2 * blockIdx.x + (wave ? 1 : 0), a.dbg >> 16);
   for (int qi = q_first, qn = 0; qi < nq; qi = qn) {
     asm volatile("" ::: "memory");
-    PCR_SMARK(4);
+    trace.mark(4);
     const size_t b = (size_t)bq * 8 + xcd;
     const int c0 = item * ncen_item;
     const int nc = a.S - c0 < ncen_item ? a.S - c0 : ncen_item;
@@ -1028,10 +1010,8 @@ void sa_stream_kernel(Sa2Args a, int nblk_item, int ncen_item) {
     };
     for (int blk = 0; blk < nblk_item; blk++) {
       if (blk * 32 >= rows) break;                      // (a partial last item: whole blocks of padding are skipped)
-      PCR_SMARK(0);
-#ifdef PCR_SA_TRACE_BUILD   // (mark 5 of the K-row form: the constant 100 MHz counter at the block top -> the clock the launch runs at)
-      if (tracing && trace_it >= 0 && trace_it < kTraceTiles) trace[2 + trace_it * kTraceMarks + 5] = __builtin_amdgcn_s_memrealtime();
-#endif
+      trace.mark(0);
+      trace.mark_realtime(5);   // (mark 5 of the K-row form: the block top on the constant counter -> the clock the launch runs at)
       const int i = i_pre, ci = ci_pre;
       if (blk + 1 < nblk_item && (blk + 1) * 32 < rows) {
         fetch_rows(blk + 1);
@@ -1041,8 +1021,8 @@ void sa_stream_kernel(Sa2Args a, int nblk_item, int ncen_item) {
       }
       f32x16 y[NCB3];
       SasBlock<NCB, NCB3, LO>::run_t(tab, a.qoff, has_q, i, ci, s_sh, s_sh + C, s_sh + 2 * C, s_wa, s_w2, s_w3, lane, y,
-                                     PCR_STR(), tok, xt);
-      PCR_SMARK(1);
+                                     trace.row(), tok, xt);
+      trace.mark(1);
       // the maximum over a 16-row group = a maximum over eight of the lane's OWN registers plus one exchange with its
       // partner lane (20 instructions per cout block; the token-per-lane form needs a 4-step DPP reduction of every
       // register: 128)
@@ -1060,13 +1040,10 @@ void sa_stream_kernel(Sa2Args a, int nblk_item, int ncen_item) {
       }
       fold(m0);
       if (blk * 32 + 16 < rows) fold(m1);               // (the second group of an item's last block can be padding)
-      PCR_SMARK(2);
-      PCR_SNEXT();
+      trace.mark(2);
+      trace.next();
     }
   }
-#undef PCR_SMARK
-#undef PCR_STR
-#undef PCR_SNEXT
 }
 
 #endif
@@ -1358,24 +1335,14 @@ void sa_stream_rag_kernel(RagArgs a) {
     }
   };
   if constexpr (TAB) prefetch_item(wrank < nq, bq, item);
-#ifdef PCR_SA_TRACE_BUILD   // diagnostic builds only: waves 0 and 5 of a workgroup stamp the shader clock (one record per block)
-  const bool tracing = (a.dbg & 256) && lane == 0 && (wave == 0 || wave == 5) && blockIdx.x < kTraceWgs / 2;
-  unsigned long long *trace = g_rag_trace + (size_t)(2 * blockIdx.x + (wave ? 1 : 0)) * (2 + kTraceTiles * kTraceMarks);
-  int trace_it = 0;
-#define PCR_SMARK(m)                                                                                   \
-  do {                                                                                                 \
-    if (tracing && trace_it < kTraceTiles) trace[2 + trace_it * kTraceMarks + (m)] = __builtin_readcyclecounter(); \
-  } while (0)
-#define PCR_STR() ((tracing && trace_it < kTraceTiles) ? trace + 2 + trace_it * kTraceMarks : nullptr)
-#define PCR_SNEXT() trace_it++
-#else
-#define PCR_SMARK(m) do { } while (0)
-#define PCR_STR() nullptr
-#define PCR_SNEXT() do { } while (0)
-#endif
+  // trace builds: waves 0 and 5 of a workgroup stamp the shader clock, one row per block
+  SaTrace trace;
+  if constexpr (kTraceBuild)
+    trace.begin((a.dbg & 256) && lane == 0 && (wave == 0 || wave == 5) && blockIdx.x < kTraceWgs / 2,
+                g_rag_trace, 2 * blockIdx.x + (wave ? 1 : 0));
   for (int qi = wrank; qi < nq; qi += wstride) {
     asm volatile("" ::: "memory");
-    PCR_SMARK(4);
+    trace.mark(4);
     const size_t b = (size_t)bq * 8 + xcd;
     const int c0 = item * CPI;
     const int nc = a.S - c0 < CPI ? a.S - c0 : CPI;
@@ -1399,11 +1366,7 @@ void sa_stream_rag_kernel(RagArgs a) {
       bq++;
     }
     if constexpr (TAB) prefetch_item(qi + wstride < nq, bq, item);
-    int incl = n;   // inclusive prefix over the 16-lane row (DPP row shifts: lanes >= 16 hold zeros and are not read)
-    incl += __builtin_amdgcn_update_dpp(0, incl, 0x111, 0xF, 0xF, true);   // row_shr:1
-    incl += __builtin_amdgcn_update_dpp(0, incl, 0x112, 0xF, 0xF, true);   // row_shr:2
-    incl += __builtin_amdgcn_update_dpp(0, incl, 0x114, 0xF, 0xF, true);   // row_shr:4
-    incl += __builtin_amdgcn_update_dpp(0, incl, 0x118, 0xF, 0xF, true);   // row_shr:8
+    const int incl = row_incl_scan(n);   // (lanes >= 16 hold zeros and are not read)
     const int R = __builtin_amdgcn_readlane(incl, CPI - 1);
     if (lane < nc) eflag[(incl >> 1) - 1] = 1;          // the centre's last pair
     if constexpr (!TAB) {
@@ -1417,10 +1380,10 @@ void sa_stream_rag_kernel(RagArgs a) {
     int cur[CPL], cc = 0;            // the open centre's running maxima, the number of centres closed so far
 #pragma unroll
     for (int e = 0; e < CPL; e++) cur[e] = 0;
-    PCR_SMARK(5);
+    trace.mark(5);
     for (int blk = 0; blk < nb; blk++) {
       f32x16 y[NCB3];
-      PCR_SMARK(0);
+      trace.mark(0);
       // which of the block's pairs close a centre (lane p < 16 looks at pair p and takes the flag down again)
       const int np = (R >> 1) - blk * 16 < 16 ? (R >> 1) - blk * 16 : 16;
       bool is_end = false;
@@ -1432,7 +1395,7 @@ void sa_stream_rag_kernel(RagArgs a) {
         const f32x4 e = e_nb;
         if (blk + 1 < nb) e_nb = rt[(blk + 1) * 32 + j];   // (whole blocks are written: rows past R are zero entries)
         SasBlock<NCB, NCB3, LO>::run_d(e[1], e[2], e[3], pq, a.pqw, -1, false, __float_as_int(e[0]), 0, s_sh, s_sh + C,
-                                       s_sh + 2 * C, s_wa, s_w2, s_w3, lane, y, PCR_STR());
+                                       s_sh + 2 * C, s_wa, s_w2, s_w3, lane, y, trace.row());
       } else {
         int r = blk * 32 + j;
         r = r < R ? r : R - 1;
@@ -1443,7 +1406,7 @@ void sa_stream_rag_kernel(RagArgs a) {
         const int i = a.idx[(b * a.S + s) * (size_t)K + k];
         SasBlock<NCB, NCB3, LO>::run(xyz, pq, a.pqw, -1, false, i, ci, s_sh, s_sh + C, s_sh + 2 * C, s_wa, s_w2, s_w3, lane, y);
       }
-      PCR_SMARK(1);
+      trace.mark(1);
       // pairs of rows (tokens 8 g + 4 h + 2 p, + 1) belong to one centre: pair 4 g + 2 h + p of the block puts its maximum
       // into row `pair` of pbuf with plain stores (the first version sent it to the centre's row with LDS integer atomics:
       // 32 per lane and block, each far slower than a store on an LDS unit that eight waves share)
@@ -1460,7 +1423,7 @@ void sa_stream_rag_kernel(RagArgs a) {
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      PCR_SMARK(2);
+      trace.mark(2);
       // the lane's channels over the block's pairs in row order: a running maximum (from +0: the ReLU, signed maxima of
       // the bit patterns) that leaves for the output whenever a centre closes and carries over to the next block otherwise
       int v[16][CPL];
@@ -1499,13 +1462,10 @@ void sa_stream_rag_kernel(RagArgs a) {
       }
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();   // (the next block's pair maxima overwrite pbuf)
-      PCR_SMARK(3);
-      PCR_SNEXT();
+      trace.mark(3);
+      trace.next();
     }
   }
-#undef PCR_SMARK
-#undef PCR_STR
-#undef PCR_SNEXT
 }
 #endif
 
@@ -1695,17 +1655,11 @@ void sa_wsplit_rag_kernel(RagArgs a) {
     }
   };
 #define PCR_SB() __builtin_amdgcn_sched_barrier(0)
-#ifdef PCR_SA_TRACE_BUILD   // diagnostic builds only: wave 0 and wave 7 stamp the shader clock at the step boundaries
-  const bool tracing = (a.dbg & 256) && lane == 0 && (w == 0 || w == 7) && blockIdx.x < kTraceWgs / 2;
-  unsigned long long *trace = g_rag_trace + (size_t)(2 * blockIdx.x + (w ? 1 : 0)) * (2 + kTraceTiles * kTraceMarks);
-  int trace_it = 0;
-#define PCR_WMARK(m)                                                                                   \
-  do {                                                                                                 \
-    if (tracing && trace_it < kTraceTiles) trace[2 + trace_it * kTraceMarks + (m)] = __builtin_readcyclecounter(); \
-  } while (0)
-#else
-#define PCR_WMARK(m) do { } while (0)
-#endif
+  // trace builds: wave 0 and wave 7 stamp the shader clock at the step boundaries
+  SaTrace trace;
+  if constexpr (kTraceBuild)
+    trace.begin((a.dbg & 256) && lane == 0 && (w == 0 || w == 7) && blockIdx.x < kTraceWgs / 2,
+                g_rag_trace, 2 * blockIdx.x + (w ? 1 : 0));
   // ---- prologue: tile 0's layer 1, tile 1's row entry
   int4 td_prev = make_int4(0, 0, 0, 0), td_cur = make_int4(0, 0, 0, 0), td_next = make_int4(0, 0, 0, 0);
   unsigned pe_lo = 0u, pe_hi = 0u;                     // previous tile's segment mask / group count (its pair maxima)
@@ -1742,7 +1696,7 @@ void sa_wsplit_rag_kernel(RagArgs a) {
     const bf16x8 *x1u = reinterpret_cast<const bf16x8 *>(x1 + par * C * ROWS);
     float *x1n = x1 + (par ^ 1) * C * ROWS;
     // ---- step 1: layer 2 of (cb2, rb2); between its MFMA triples the pair maxima of the previous tile
-    PCR_WMARK(0);
+    trace.mark(0);
     int *obase = obuf + (16 * rb3 + 2 * h) * C3 + cb3 * 32 + j;
     gather(tile + t_step, td_next.x);                  // (its row entry was requested most of a tile ago; the pieces land
                                                        //  in layer 1's accumulator during this step)
@@ -1786,12 +1740,12 @@ void sa_wsplit_rag_kernel(RagArgs a) {
           if constexpr (LO) xl = nl;
         }
       }
-      PCR_WMARK(1);
+      trace.mark(1);
       bf_store_tile<LO>(x2, ROWS, y, cb2, rb2, j, h);
     }
-    PCR_WMARK(2);
+    trace.mark(2);
     __syncthreads();
-    PCR_WMARK(3);
+    trace.mark(3);
     // ---- step 2: layer 3 (transposed) of cout block cb3, row blocks rb3 + k G3; between its MFMA triples layer 1 of the
     // next tile and the previous tile's output
     {
@@ -1850,12 +1804,10 @@ void sa_wsplit_rag_kernel(RagArgs a) {
             pm[k][2 * g + pr] = imax(__float_as_int(y3[4 * g + 2 * pr]), __float_as_int(y3[4 * g + 2 * pr + 1]));
       }
     }
-    PCR_WMARK(4);
+    trace.mark(4);
     __syncthreads();
-    PCR_WMARK(5);
-#ifdef PCR_SA_TRACE_BUILD
-    trace_it++;
-#endif
+    trace.mark(5);
+    trace.next();
     td_prev = td_cur;
     td_cur = td_next;
     asm volatile("" : "+v"(nn_x), "+v"(nn_y), "+v"(nn_z));
@@ -1896,20 +1848,13 @@ __global__ __launch_bounds__(kThreads) void sa_rag_kernel(RagArgs a) {
   constexpr int QS = kThreads / ROWS;     // channel quads advance by QS per item: a thread keeps ONE row
   constexpr int NI = 8;                   // 16-byte table pieces a thread holds in registers
   const bool tracing = (a.dbg & 256) && threadIdx.x == 0 && blockIdx.x < kTraceWgs;
-  unsigned long long *trace = g_rag_trace + (size_t)blockIdx.x * (2 + kTraceTiles * kTraceMarks);
-  int trace_it = 0;
-  if (tracing) {
-    trace[0] = __builtin_amdgcn_s_getreg((4) | (0 << 6) | (31 << 11));    // HW_REG_HW_ID, 32 bits
-    trace[1] = __builtin_amdgcn_s_getreg((20) | (0 << 6) | (31 << 11));   // HW_REG_XCC_ID
+  unsigned long long *const trace_rec = g_rag_trace + (size_t)blockIdx.x * SaTrace::kWords;
+  if (tracing) {   // (every build: the record's two header words)
+    trace_rec[0] = __builtin_amdgcn_s_getreg((4) | (0 << 6) | (31 << 11));    // HW_REG_HW_ID, 32 bits
+    trace_rec[1] = __builtin_amdgcn_s_getreg((20) | (0 << 6) | (31 << 11));   // HW_REG_XCC_ID
   }
-#ifdef PCR_SA_TRACE_BUILD   // diagnostic builds only (the stamps cost registers in the hot kernel)
-#define PCR_MARK(m)                                                                                    \
-  do {                                                                                                 \
-    if (tracing && trace_it < kTraceTiles) trace[2 + trace_it * kTraceMarks + (m)] = __builtin_readcyclecounter(); \
-  } while (0)
-#else
-#define PCR_MARK(m) do { (void)tracing; (void)trace; } while (0)
-#endif
+  SaTrace trace;   // (the stamps cost registers in the hot kernel: trace builds only)
+  if constexpr (kTraceBuild) trace.begin(tracing, g_rag_trace, blockIdx.x);
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int c1 = a.c1, c2 = a.c2, c3 = a.c3;
   // XCD-aware tile ranges: workgroup ids are dealt round-robin over the 8 XCDs (own L2 each); the flat tile list is
@@ -2021,7 +1966,7 @@ __global__ __launch_bounds__(kThreads) void sa_rag_kernel(RagArgs a) {
   const int4 td = flat[tile];
   const size_t b = (size_t)td.x;
   const int first = td.y;
-  PCR_MARK(0);
+  trace.mark(0);
   if constexpr (kL1M) {
     const bool hasp = a.pq != nullptr;
     tile_dense2<TB, 1, W1, true>(sdx8, 8, a.wap, ceil32(c1), false,
@@ -2076,9 +2021,9 @@ __global__ __launch_bounds__(kThreads) void sa_rag_kernel(RagArgs a) {
       }
     }
   }
-  PCR_MARK(1);
+  trace.mark(1);
   __syncthreads();
-  PCR_MARK(2);
+  trace.mark(2);
   fetch_row(tile + t_step);   // next tile's row entry: lands during layer 2
   if (!(a.dbg & 2)) {
   if constexpr (kImg)
@@ -2095,10 +2040,10 @@ __global__ __launch_bounds__(kThreads) void sa_rag_kernel(RagArgs a) {
                                   [&](float v, int o, int t) { buf[o * RP + t] = relu_bits(v); }, s_sh2,
                                   kRing && PCR_RING == 1 ? ring2 : nullptr, load_ring3);
   }
-  PCR_MARK(3);
+  trace.mark(3);
   if (pref || (kL1M && a.pq)) gather(tile + t_step);   // next tile's table pieces: land during layer 3
   __syncthreads();
-  PCR_MARK(4);
+  trace.mark(4);
   if (!(a.dbg & 4))
   tile_dense2p<PREC, TB, NR, W3, true, kImg>(buf, ceil8(c2), a.wp3, ceil32(c3), false,
                                             [&](const f32x16 &acc, int cb, int tb, int l31, int h) {
@@ -2110,7 +2055,7 @@ __global__ __launch_bounds__(kThreads) void sa_rag_kernel(RagArgs a) {
 #pragma unroll
     for (int rr = 0; rr < 16; rr++) {
       int v = __float_as_int(acc[rr]);
-      v = imax(v, dpp_i32<0xB1>(v));    // lane ^ 1
+      v = imax(v, wave_dpp<kDppXor1>(v));
       g4[rr >> 2][rr & 3] = __int_as_float(v);
     }
     if ((l31 & 1) == 0) {
@@ -2119,10 +2064,10 @@ __global__ __launch_bounds__(kThreads) void sa_rag_kernel(RagArgs a) {
       for (int g = 0; g < 4; g++) *reinterpret_cast<f32x4 *>(gq + 8 * g) = g4[g];
     }
   }, s_sh3, kRing ? ring3 : nullptr, load_ring2, 0, kBfR3 ? &bring3 : nullptr);
-  PCR_MARK(5);
+  trace.mark(5);
   if constexpr (kL1M) stash_dxyz();   // next tile's dxyz rows (layer 1 of this tile is long done)
   __syncthreads();
-  PCR_MARK(6);
+  trace.mark(6);
   if (!(a.dbg & 8)) {
     // one cout per thread; all quad maxima of the tile are read first (independent, conflict-free LDS reads),
     // then scanned with the wave-uniform `ends` mask: values are >= 0 after the ReLU, so 0 starts a segment
@@ -2156,8 +2101,8 @@ __global__ __launch_bounds__(kThreads) void sa_rag_kernel(RagArgs a) {
   }
   ends_lo = nxt_lo;
   ends_hi = nxt_hi;
-  PCR_MARK(7);
-  trace_it++;
+  trace.mark(7);
+  trace.next();
   // no barrier needed here: the next tile's layer 1 writes buf (dead since layer 3), its layer 3 writes gmax
   // only after two more barriers
   }
@@ -2459,27 +2404,9 @@ static int sa2_launch_tb(const Sa2Args &a, int nr, int nr2, int w2, int w3, bool
 
 extern "C" int pcr_dense_pm_f32(const float *, const float *, float *, int, int, int, int, int, pcr_stream_t);
 
-// diagnostics only (PCR_SA_TRACE): synchronises, appends one launch's phase stamps to the file
-static void rag_dump_trace(const char *path, const char *tag, int wgs) {
-  static int launches = 0;
-  static const int skip = pcr_tune_int("PCR_SA_TRACE_SKIP");   // (a freshly started process runs its first launches cold)
-  launches++;
-  if (launches <= skip || launches > skip + 8) return;   // a few launches are enough
-  static std::vector<unsigned long long> host(kTraceWgs * (2 + kTraceTiles * kTraceMarks));
-  if (hipDeviceSynchronize() != hipSuccess) return;
-  if (hipMemcpyFromSymbol(host.data(), HIP_SYMBOL(g_rag_trace), host.size() * sizeof(unsigned long long)) != hipSuccess)
-    return;
-  FILE *f = fopen(path, "a");
-  if (!f) return;
-  const int n = wgs < kTraceWgs ? wgs : kTraceWgs;
-  fprintf(f, "launch %d kernel %s wgs %d\n", launches, tag, wgs);
-  for (int w = 0; w < n; w++) {
-    const unsigned long long *t = host.data() + (size_t)w * (2 + kTraceTiles * kTraceMarks);
-    fprintf(f, "wg %d hwid %llu xcc %llu", w, t[0], t[1]);
-    for (int i = 0; i < kTraceTiles * kTraceMarks; i++) fprintf(f, " %llu", t[2 + i]);
-    fprintf(f, "\n");
-  }
-  fclose(f);
+// diagnostics only (PCR_SA_TRACE and its kin): one launch's stamps appended to the file, `recs` records of it
+static void rag_dump_trace(const char *path, const char *tag, int recs) {
+  wave_trace_dump<SaTrace>(path, HIP_SYMBOL(g_rag_trace), recs, "kernel %s wgs %d\n", tag, recs);
 }
 
 // fast path; returns -1 when the configuration is not covered (caller falls back to sa_mlp_kernel)

@@ -11,22 +11,6 @@
 
 namespace {
 
-template <int CTRL>
-__device__ __forceinline__ float dpp_f32(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
-}
-// sum over the 64 lanes of a wave (the same value in every lane): four DPP adds inside the 16-lane rows, then the four
-// row totals through v_readlane -- no LDS traffic (a __shfl_xor butterfly is six ds_bpermute round trips)
-__device__ __forceinline__ float wsum(float v) {
-  v += dpp_f32<0xB1>(v);     // quad_perm [1,0,3,2]
-  v += dpp_f32<0x4E>(v);     // quad_perm [2,3,0,1]
-  v += dpp_f32<0x141>(v);    // row_half_mirror
-  v += dpp_f32<0x140>(v);    // row_mirror
-  const int b = __float_as_int(v);     // (v_readlane moves 32-bit patterns: the builtin is typed int)
-  return (__int_as_float(__builtin_amdgcn_readlane(b, 0)) + __int_as_float(__builtin_amdgcn_readlane(b, 16))) +
-         (__int_as_float(__builtin_amdgcn_readlane(b, 32)) + __int_as_float(__builtin_amdgcn_readlane(b, 48)));
-}
-
 // ------------------------------------------------------------------ token norm (LayerNorm / GroupNorm) ----
 // x (B,C,L): every token is normalised over each of its G groups of C/G consecutive channels (LayerNorm: G = 1),
 // y = (x - mean) rstd gamma + beta [+ res].  One thread per (token, group); mean / rstd are kept for the backward.
@@ -111,7 +95,7 @@ __global__ __launch_bounds__(64) void tnorm_bwd_kernel(TNormBwd a, int B) {
     const float xh = ok ? (a.x[base + (size_t)i * a.L] - m) * r : 0.f;
     if (ok) a.dx[base + (size_t)i * a.L] = r * (go * a.gamma[c] - s1 * inv - xh * s2 * inv);
     if (ok && a.dres) a.dres[base + (size_t)i * a.L] = go;
-    const float w1 = wsum(go * xh), w2 = wsum(go);
+    const float w1 = wave_sum_dpp(go * xh), w2 = wave_sum_dpp(go);
     if (lane == 0) {
       part[c] = w1;
       part[a.C + c] = w2;
@@ -230,7 +214,7 @@ __global__ __launch_bounds__(256) void tnorm_bwd4_kernel(TNormBwd a, int B) {
     const int c = c0 + i;
     if (ok) a.dx[base + (size_t)i * a.L] = r * (go[i] * sgam[w * NC + i] - s1 * inv - xh[i] * s2 * inv);
     if (ok && a.dres) a.dres[base + (size_t)i * a.L] = go[i];
-    const float w1 = wsum(go[i] * xh[i]), w2 = wsum(go[i]);
+    const float w1 = wave_sum_dpp(go[i] * xh[i]), w2 = wave_sum_dpp(go[i]);
     if (lane == 0) {
       part[c] = w1;
       part[a.C + c] = w2;
@@ -745,7 +729,7 @@ __global__ __launch_bounds__(256) void pool_pair_fwd_kernel(const float *__restr
         am = oa;
       }
     }
-    sm = wsum(sm);
+    sm = wave_sum_dpp(sm);
     if (lane == 0) {
       pooled[p * 2 * C + c] = mx;
       pooled[p * 2 * C + C + c] = sm / (float)(2 * L);
@@ -794,7 +778,7 @@ __global__ __launch_bounds__(256) void pool_both_fwd_kernel(const float *__restr
         am = oa;
       }
     }
-    sm = wsum(sm);
+    sm = wave_sum_dpp(sm);
     if (lane == 0) {
       pooled[p * 2 * C + c] = mx;
       pooled[p * 2 * C + C + c] = sm / (float)L;

@@ -10,12 +10,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-
 // part [G][2][CP]: slice g of the clouds, channel c: (sum y, sum y^2)  -- or, with g2 given, (sum g', sum g' y) where
 // g' = g2 act'(scale y + shift), act' = 1 (z > 0) | slope (ReLU: slope 0, LeakyReLU(0.2): 0.2; `relu` = 0: g' = g2):
 // the two sums of the BatchNorm backward
@@ -47,8 +41,8 @@ __global__ __launch_bounds__(256) void bn_sums_kernel(const float *__restrict__ 
       }
     }
   }
-  s0 = wave_sum(s0);
-  s1 = wave_sum(s1);
+  s0 = wave_sum_shfl(s0);
+  s1 = wave_sum_shfl(s1);
   if (lane == 0) {
     red[0][wave] = s0;
     red[1][wave] = s1;
@@ -116,7 +110,7 @@ __global__ __launch_bounds__(256) void bmm_dt_kernel(const float *__restrict__ x
   const float *xr = x + (b * k + i) * N, *dr = dy + (b * k + j) * N;
   float s = 0.f;
   for (int n = lane; n < N; n += 64) s += xr[n] * dr[n];
-  s = wave_sum(s);
+  s = wave_sum_shfl(s);
   if (lane == 0) dT[b * k * k + e] = s;
 }
 

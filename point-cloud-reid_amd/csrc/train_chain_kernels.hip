@@ -44,16 +44,6 @@ constexpr int kChainPF = PCR_CHAIN_PF;
 #define PCR_DW_UNROLL 2
 #endif
 
-template <int CTRL>
-__device__ __forceinline__ float ck_dpp(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float ck_quad_sum(float v) {
-  v += ck_dpp<0xB1>(v);
-  v += ck_dpp<0x4E>(v);
-  return v;
-}
-
 // dense layer with a compile-time number of 32-row output blocks (wave / tile split and rounds follow from it)
 // PREC 0: f32-input MFMAs on a pcr_pack_weight image; 1: split bf16 (three bf16 MFMAs per product, f32 accumulation) on a
 // bf16 hi / lo image, the f32 tile converted where it is consumed (tile_dense.h)
@@ -145,7 +135,7 @@ __device__ __forceinline__ void ck_ln_bwd(const float *dy, const float *xh, floa
 }
 
 // per-row sums over the tile's 64 tokens, accumulated over the workgroup's tiles: thread (row (tid >> 2) + 64 p, token
-// quarter tid & 3); sa += sum X, sb += sum X * Y (Y may be null).  The quarters of a row meet once, at the end (ck_quad_sum).
+// quarter tid & 3); sa += sum X, sb += sum X * Y (Y may be null).  The quarters of a row meet once, at the end (quad_sum).
 template <int ROWS>
 __device__ __forceinline__ void ck_rowsum(const float *X, const float *Y, float (&sa)[(ROWS + 63) / 64],
                                           float (&sb)[(ROWS + 63) / 64]) {
@@ -186,7 +176,7 @@ __device__ __forceinline__ void ck_rowsum_store(float *dst_a, float *dst_b, cons
 #pragma unroll
   for (int p = 0; p < (ROWS + 63) / 64; p++) {
     const int r = (tid >> 2) + 64 * p;
-    const float a = ck_quad_sum(sa[p]), b = ck_quad_sum(sb[p]);
+    const float a = quad_sum(sa[p]), b = quad_sum(sb[p]);
     if ((tid & 3) == 0 && r < ROWS) {
       if (dst_a) dst_a[r] = a;
       if (dst_b) dst_b[r] = b;

@@ -89,16 +89,6 @@ __device__ __forceinline__ f32x4 ld4(const float *p) { return *reinterpret_cast<
 // the quad).  (One thread per row -- 64 dependent-ish iterations on a quarter of the threads -- was the longest serial
 // stretch of a tile.)
 constexpr int kRowPasses = 6;   // up to 384 rows
-template <int CTRL>
-__device__ __forceinline__ float tk_dpp(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float quad_sum(float v) {
-  v += tk_dpp<0xB1>(v);
-  v += tk_dpp<0x4E>(v);
-  return v;
-}
-
 // ---------------------------------------------------------------------------------- forward ----
 struct TFwd {
   const float *x, *x2;              // (B,cin1,L), (B,cin2,L) or null: the layer's input is [x ; x2] along the channels

@@ -16,20 +16,6 @@ namespace {
 
 constexpr int kLT = 256;   // four waves = four points per workgroup
 
-template <int CTRL>
-__device__ __forceinline__ float la_dpp(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
-}
-// sum over the dh lanes of a head (dh a power of two <= 64; heads are aligned lane groups)
-__device__ __forceinline__ float la_head_sum(float a, int dh) {
-  if (dh > 1) a += la_dpp<0xB1>(a);
-  if (dh > 2) a += la_dpp<0x4E>(a);
-  if (dh > 4) a += la_dpp<0x141>(a);
-  if (dh > 8) a += la_dpp<0x140>(a);
-  if (dh > 16) a += __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(a), 0x401F));   // lane ^ 16
-  if (dh > 32) a += __shfl_xor(a, 32, 64);
-  return a;
-}
 __device__ __forceinline__ float la_elu1(float x) { return x > 0.f ? x + 1.0f : __expf(x); }
 
 struct LAArgs {
@@ -60,7 +46,7 @@ __global__ __launch_bounds__(kLT) void local_attn_cm_kernel(LAArgs a) {
   for (int k = 0; k < K; k++) {
     const int j = nb[k];
     float av = Q * la_elu1(kk[j]);
-    av = la_head_sum(live ? av : 0.f, dh);
+    av = head_sum(live ? av : 0.f, dh);
     den += av;
     num = fmaf(av, vv[j], num);
   }
@@ -70,14 +56,14 @@ __global__ __launch_bounds__(kLT) void local_attn_cm_kernel(LAArgs a) {
     return;
   } else {
     const float gc = live ? a.g[(b * C + c) * N + i] : 0.f;
-    const float gm = la_head_sum(gc * m, dh);
+    const float gm = head_sum(gc * m, dh);
     float dQ = 0.f;
     float *ek = a.edge + ((b * 2 * C + c) * N + i) * K, *ev = ek + (size_t)C * N * K;
     for (int k = 0; k < K; k++) {
       const int j = nb[k];
       const float kraw = kk[j], Kf = la_elu1(kraw), v = vv[j];
-      const float av = la_head_sum(live ? Q * Kf : 0.f, dh);
-      const float gv = la_head_sum(gc * v, dh);
+      const float av = head_sum(live ? Q * Kf : 0.f, dh);
+      const float gv = head_sum(gc * v, dh);
       const float da = (gv - gm) / z;
       dQ = fmaf(da, Kf, dQ);
       if (live) {

@@ -29,20 +29,6 @@ struct L1Args {
   int N, S, K, c1, CS;
 };
 
-template <int CTRL>
-__device__ __forceinline__ float dpp_f32(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float wave_sum_f(float v) {   // four DPP adds inside the 16-lane rows + four v_readlane
-  v += dpp_f32<0xB1>(v);
-  v += dpp_f32<0x4E>(v);
-  v += dpp_f32<0x141>(v);
-  v += dpp_f32<0x140>(v);
-  const int b = __float_as_int(v);     // (v_readlane moves 32-bit patterns: the builtin is typed int)
-  return (__int_as_float(__builtin_amdgcn_readlane(b, 0)) + __int_as_float(__builtin_amdgcn_readlane(b, 16))) +
-         (__int_as_float(__builtin_amdgcn_readlane(b, 32)) + __int_as_float(__builtin_amdgcn_readlane(b, 48)));
-}
-
 // one workgroup per (cloud, chunk of CS channels); rows r = s*K + k across the lanes (coalesced idx reads / y writes)
 template <int CS>
 __global__ __launch_bounds__(kThreads) void sa_l1_fwd_kernel(L1Args a) {
@@ -135,7 +121,7 @@ __global__ __launch_bounds__(kThreads) void sa_l1_fwd_kernel(L1Args a) {
   if (!a.stats) return;
 #pragma unroll
   for (int c = 0; c < CS; c++) {
-    const float s = wave_sum_f(ssum[c]), q = wave_sum_f(ssq[c]);
+    const float s = wave_sum_dpp(ssum[c]), q = wave_sum_dpp(ssq[c]);
     if (lane == 0) {
       red[(wave * 2) * CS + c] = s;
       red[(wave * 2 + 1) * CS + c] = q;
@@ -415,8 +401,8 @@ __global__ __launch_bounds__(kThreads) void sa_pool_bwd_stats_kernel(const float
       s2 += gv * ymax[o + s];
     }
   }
-  s1 = wave_sum_f(s1);
-  s2 = wave_sum_f(s2);
+  s1 = wave_sum_dpp(s1);
+  s2 = wave_sum_dpp(s2);
   if (lane == 0) {
     part[(b * 2) * CP + c] = s1;
     part[(b * 2 + 1) * CP + c] = s2;

@@ -40,26 +40,6 @@ __device__ __forceinline__ void ts_st(rsrc_t r, float v, int voff, int soff) {
   __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, voff, soff, 0);
 }
 
-template <int CTRL>
-__device__ __forceinline__ float ts_dpp(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
-}
-// sum over the 32 lanes of each wave half; the result is valid in lanes 0 and 32 (all lanes of rows 0 / 2 in fact)
-__device__ __forceinline__ float ts_half_sum(float v) {
-  v += ts_dpp<0xB1>(v);
-  v += ts_dpp<0x4E>(v);
-  v += ts_dpp<0x141>(v);
-  v += ts_dpp<0x140>(v);                               // every lane: the sum of its 16-lane row
-  v += __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(v), 0x401F));   // xor 16: rows 0+1, 2+3
-  return v;
-}
-
-__device__ __forceinline__ void ts_wave_sync() {       // orders a wave's own LDS writes before its later LDS reads
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 constexpr int kTsWaves = 4;
 
 // Fused max over the K rows of every centre (the grouped MLP's pooling, reference pointnet2_utils.py:357: the max of
@@ -253,7 +233,7 @@ __global__ __launch_bounds__(64 * kTsWaves) void tstream_fwd_kernel(TSFwd a) {
         ts_st(ry, acc[nbo][r], vo, so + (nbo * 32 + (r & 3) + 8 * (r >> 2)) * L * 4);
         strip[(nbo * 32 + (r & 3) + 8 * (r >> 2) + 4 * h) * TP + j] = valid ? acc[nbo][r] : 0.f;
       }
-    ts_wave_sync();
+    wave_sync();
     if (want_stats || pool) {
 #pragma unroll
       for (int nbo = 0; nbo < NBO; nbo++) {
@@ -271,7 +251,7 @@ __global__ __launch_bounds__(64 * kTsWaves) void tstream_fwd_kernel(TSFwd a) {
         }
       }
     }
-    ts_wave_sync();
+    wave_sync();
   };
   auto next = [&](int &bb, int &tt, bool go) __attribute__((always_inline)) {      // scalar only
     const int t2 = tt + 1;
@@ -456,7 +436,7 @@ __global__ __launch_bounds__(64 * kTpWaves, 1) void tstream_fwd_pipe_kernel(TSFw
     }
       {    // cout block cb of the previous block is complete in the strip: its lane = channel sums (and pooling)
         const int s = cb * 16 + 15;
-        ts_wave_sync();
+        wave_sync();
         float t[16];
 #pragma unroll
         for (int q = 0; q < 16; q++) t[q] = strip[j * TP + 2 * q + h];
@@ -469,7 +449,7 @@ __global__ __launch_bounds__(64 * kTpWaves, 1) void tstream_fwd_pipe_kernel(TSFw
           ts_pool_block(t, psgn[s >> 4], h, pt * 32, a.poolK, pbest[s >> 4], praw[s >> 4], pk[s >> 4], rpy, rpa,
                         ((pb * C + (s >> 4) * 32 + j) * pS) * 4);
         }
-        ts_wave_sync();
+        wave_sync();
       }
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -523,7 +503,7 @@ __global__ __launch_bounds__(64 * kTpWaves, 1) void tstream_fwd_pipe_kernel(TSFw
       }
       {
         const int s = cb * 16 + 15;
-        ts_wave_sync();
+        wave_sync();
         float t[16];
 #pragma unroll
         for (int q = 0; q < 16; q++) t[q] = strip[j * TP + 2 * q + h];
@@ -536,7 +516,7 @@ __global__ __launch_bounds__(64 * kTpWaves, 1) void tstream_fwd_pipe_kernel(TSFw
           ts_pool_block(t, psgn[s >> 4], h, tP * 32, a.poolK, pbest[s >> 4], praw[s >> 4], pk[s >> 4], rpy, rpa,
                         ((bP * C + (s >> 4) * 32 + j) * pS) * 4);
         }
-        ts_wave_sync();
+        wave_sync();
       }
     }
   }
@@ -734,7 +714,7 @@ __global__ __launch_bounds__(64 * kTsWaves, NB == 1 ? 3 : 1) void tstream_bwd_ke
         __builtin_amdgcn_sched_barrier(0);
       }
     }
-    ts_wave_sync();
+    wave_sync();
     // 2. dy with lane = channel: token 2 s' + h of channel 32 nbo + j (all reads first, then the sums)
     float dyc[NB][16];
 #pragma unroll
@@ -746,7 +726,7 @@ __global__ __launch_bounds__(64 * kTsWaves, NB == 1 ? 3 : 1) void tstream_bwd_ke
     for (int nbo = 0; nbo < NB; nbo++)
 #pragma unroll
       for (int s = 0; s < 16; s++) db[nbo] += dyc[nbo][s];
-    ts_wave_sync();
+    wave_sync();
     // 3. masked dx: to memory and into strip A; f(x) into strip B
     const int so = (bb * C * L + tt * 32) * 4;
     const int vo = valid ? vd : 0x7FFFFF00;
@@ -767,7 +747,7 @@ __global__ __launch_bounds__(64 * kTsWaves, NB == 1 ? 3 : 1) void tstream_bwd_ke
         }
       }
     load_x(gb, gt);                        // the next block's forward input
-    ts_wave_sync();
+    wave_sync();
     // 4. lane = channel again: the two sums the next BatchNorm backward needs, and dW += dy f(x)^T
 #pragma unroll
     for (int nbi = 0; nbi < NB; nbi++) {
@@ -789,7 +769,7 @@ __global__ __launch_bounds__(64 * kTsWaves, NB == 1 ? 3 : 1) void tstream_bwd_ke
         s2[nbi] += dxc[s] * ((ac[s] - shl[nbi]) * invl[nbi]);      // (raw input where the mask is open; dxc = 0 elsewhere)
       }
     }
-    ts_wave_sync();
+    wave_sync();
   };
   auto next = [&](int &bb, int &tt, bool go) __attribute__((always_inline)) {      // scalar only
     const int t2 = tt + 1;

@@ -34,6 +34,19 @@ def hipcc():
     return exe
 
 
+def common_flags(csrc=CSRC, root=ROOT):
+    """the hipcc flags every source of the tree `root` (sources in `csrc`) is compiled with"""
+    return (["--offload-arch=gfx950", "-O3", "-fPIC", "-fvisibility=hidden", "-std=c++17",
+             "-I" + os.path.join(root, "include"), "-I" + csrc]
+            + os.environ.get("PCR_EXTRA_HIPCC_FLAGS", "").split())      # diagnostic builds only
+
+
+def compile_flags(src, root=ROOT):
+    """The hipcc flags build() compiles `src` with; `root` is the tree whose include/ the build reads.  tools/isa_same.py
+    and tools/isa_diff.py compile with the same call, so that what they compare is what the library holds."""
+    return common_flags(os.path.dirname(os.path.abspath(src)), root) + FLAGS.get(os.path.basename(src), [])
+
+
 def sources():
     return sorted(glob.glob(os.path.join(CSRC, "*.hip")))
 
@@ -69,9 +82,7 @@ def build(force=False, verbose=False):
     os.makedirs(LIBDIR, exist_ok=True)
     objdir = os.path.join(LIBDIR, "obj" + ("_" + _TAG if _TAG else ""))
     os.makedirs(objdir, exist_ok=True)
-    common = ["--offload-arch=gfx950", "-O3", "-fPIC", "-fvisibility=hidden", "-std=c++17",
-              "-I" + os.path.join(ROOT, "include"), "-I" + CSRC]
-    common += os.environ.get("PCR_EXTRA_HIPCC_FLAGS", "").split()      # diagnostic builds only
+    common = common_flags()
     objs = []
     procs = []
     # the objects of a directory were all built with ONE flag set, recorded beside them: another set (a tagged library
@@ -87,7 +98,7 @@ def build(force=False, verbose=False):
         if not force and same_flags and os.path.exists(obj) and \
                 all(os.path.getmtime(d) <= os.path.getmtime(obj) for d in includes_of(src)):
             continue        # incremental: this object is newer than its source and every header
-        cmd = [hipcc()] + common + FLAGS.get(os.path.basename(src), []) + ["-c", src, "-o", obj]
+        cmd = [hipcc()] + compile_flags(src) + ["-c", src, "-o", obj]
         if verbose:
             print(" ".join(cmd))
         procs.append((src, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))

@@ -21,8 +21,7 @@ def emit(outdir, srcs):
     for src in srcs:
         base = os.path.basename(src)
         stem = os.path.splitext(base)[0]
-        cmd = [build.hipcc(), "--offload-arch=gfx950", "-O3", "-fPIC", "-fvisibility=hidden", "-std=c++17",
-               "-I" + os.path.join(ROOT, "include"), "-I" + CSRC] + build.FLAGS.get(base, []) + \
+        cmd = [build.hipcc()] + build.compile_flags(src) + \
               ["--cuda-device-only", "-S", "-Rpass-analysis=kernel-resource-usage", src, "-o",
                os.path.join(outdir, stem + ".s")]
         r = subprocess.run(cmd, capture_output=True, text=True)

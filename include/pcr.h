@@ -766,6 +766,82 @@ int pcr_truth_cost_f32(const float *det_boxes, const int *det_labels, const floa
 int pcr_truth_decide_i32(const pcr_truth *p, pcr_stream_t stream);
 int pcr_truth_record_i32(const pcr_truth *p, pcr_stream_t stream);
 
+/* ------------------------------------------------------------ A8. ranking a gallery -------- */
+
+/* The other use of a re-identification model: for every query object, which gallery objects is it, and how often does
+ * the right one come first.  (The reference asks the question inside its tracker, VirtualTracker.
+ * log_reid_matching_score, trackers/deprecated/virtual_tracker.py:350-430; that code does not run.)  Three launches
+ * of fixed shape, no host read, no allocation, no atomic; the same bits on every run; every loop is bounded by an integer
+ * count.  The result is DEFINED by the rules below (tests/rank_ref.py restates them; the kernels equal it bit for bit).
+ * Pointers are checked against NULL only.
+ * pcr_rank_ok: 0 <= Q <= PCR_RANK_MAX_QUERIES, 0 <= G <= PCR_RANK_MAX_GALLERY, 1 <= K <= PCR_RANK_MAX_K,
+ * 0 <= cap <= Q * G (in 64-bit arithmetic).
+ *
+ * pcr_rank_scores_f32: logits (cap), pairs (cap,2), count (1, device) -> scores (Q,G), EVERY element written:
+ * scores[q][g] = logits[k] for the listed pairs k < min(count[0], cap) (a negative count is 0) with (q, g) = pairs[k]
+ * inside [0,Q) x [0,G); -inf ("not a candidate") elsewhere.  A pair outside the range is skipped.  The listed pairs must be
+ * distinct (pcr_assoc_pairs_i32's are).  This is the score image of pcr_assoc_cost_multi_f32's softmax kind, restated so
+ * that the ranking takes any dense score matrix as well.  Nothing to do: Q * G == 0.
+ *
+ * pcr_rank_gallery_f32: one wave per query q over its row of scores (Q,G), staged in LDS.  query_ids (Q), gallery_ids (G):
+ * a value < 0 is "no identity"; exclude (Q) or NULL.  Every element of every output is written.
+ *   candidates  gallery g is a CANDIDATE of q iff scores[q][g] != -inf and g != exclude[q] (NULL, or a value outside
+ *               [0,G): nothing is excluded).  +inf is an ordinary score.  If any candidate's score is a NaN, info[q] = 1 and
+ *               the query is not ranked: topk_idx -1, topk_score -inf, n_cand = n_true = 0, first_hit = -1, ap = 0.
+ *               Otherwise info[q] = 0.  (A NaN at an excluded slot is no candidate's.)
+ *   order       descending score; equal scores, lowest gallery index first.  Equality is the float compare: -0 == +0.
+ *   rank        rank(g) = #{candidates j : s_j > s_g, or s_j == s_g and j < g}.
+ *   top-k       topk_idx[q][r] (Q,K) = the candidate of rank r for r < min(K, n_cand[q]), -1 beyond; topk_score[q][r] its
+ *               score as stored (the sign of a zero included), -inf beyond.  n_cand (Q) = the number of candidates.
+ *   truth       the TRUE set = {candidates g : query_ids[q] >= 0 and gallery_ids[g] == query_ids[q]}; n_true (Q) its size,
+ *               first_hit (Q) its least rank, -1 when it is empty -- exact whatever K is.
+ *   ap          with the true candidates' ranks ascending r_0 < r_1 < ...: ap = (sum_i (i+1)/(r_i+1)) / n_true; each
+ *               quotient an IEEE binary64 division of two integers converted to binary64, the sum in ascending i in
+ *               binary64, the last division in binary64, rounded to binary32 once.  0 when n_true == 0.
+ * Cost: one read of the row, then min(K, n_cand) + n_true passes over it in LDS (top-k: rounds of a 64-bit wave maximum
+ * over (order-preserving score bits, inverted index); a true candidate's rank: ballot popcounts over the row).
+ * Nothing to do: Q == 0.  With G == 0 every query is empty and the outputs are still written.
+ *
+ * pcr_rank_accumulate: one launch (one wave) adds a chunk's per-query results to a persistent table, so that an
+ * evaluation over chunks of queries makes no host read.  valid (1, device) or NULL: only the queries
+ * q < clamp(valid[0], 0, Q) count; NULL = all Q.  A query is FLAGGED iff info[q] != 0, SCORED iff info[q] == 0 and
+ * n_true[q] > 0 (then first_hit[q] >= 0), UNSCORED otherwise.
+ *   counts (3 + nranks)   counts[0] += scored, counts[1] += unscored, counts[2] += flagged,
+ *                         counts[3 + i] += #{scored q : first_hit[q] < ranks[i]}; nranks <= PCR_RANK_MAX_RANKS values
+ *                         ranks[i] in [1, G].
+ *   sums (2, binary64)    for q ascending over the scored queries: sums[0] = sums[0] + (double)ap[q], sums[1] = sums[1] +
+ *                         1.0 / (double)(first_hit[q] + 1) -- each a running binary64 sum that starts at the table's value,
+ *                         so two chunks added one after the other equal their union added at once.
+ * Nothing to do: Q == 0. */
+#define PCR_RANK_MAX_QUERIES 65535
+#define PCR_RANK_MAX_GALLERY 4096
+#define PCR_RANK_MAX_K 64
+#define PCR_RANK_MAX_RANKS 8
+typedef struct pcr_rank {
+  int Q, G, K;
+  const float *scores;                                       /* (Q,G) */
+  const int *query_ids, *gallery_ids, *exclude;              /* (Q), (G), (Q) or NULL */
+  int *topk_idx;                                             /* (Q,K) */
+  float *topk_score;                                         /* (Q,K) */
+  int *n_cand, *n_true, *first_hit;                          /* (Q) */
+  float *ap;                                                 /* (Q) */
+  int *info;                                                 /* (Q) */
+} pcr_rank;
+typedef struct pcr_rank_acc {
+  int Q, G, nranks;
+  int ranks[8];                                              /* PCR_RANK_MAX_RANKS */
+  const int *n_true, *first_hit, *info;                      /* (Q): pcr_rank_gallery_f32's */
+  const float *ap;                                           /* (Q) */
+  const int *valid;                                          /* (1) device, or NULL */
+  int *counts;                                               /* (3 + nranks) */
+  double *sums;                                              /* (2) */
+} pcr_rank_acc;
+int pcr_rank_ok(int Q, int G, int K, int cap);
+int pcr_rank_scores_f32(const float *logits, const int *pairs, const int *count, float *scores, int Q, int G, int cap,
+                        pcr_stream_t stream);
+int pcr_rank_gallery_f32(const pcr_rank *p, pcr_stream_t stream);
+int pcr_rank_accumulate(const pcr_rank_acc *p, pcr_stream_t stream);
+
 /* ------------------------------------------------- B. fused model kernels ------------ */
 
 /* Neighbour search of the "Point-Transformer" set-abstraction layers: centres are the first S

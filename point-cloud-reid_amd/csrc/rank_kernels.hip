@@ -1,0 +1,222 @@
+// Ranking a gallery on the device (include/pcr.h, section A8): the score matrix from a pair list, the ranking of every query's
+// row -- top-k, the first hit and the average precision against identities -- and the table an evaluation over chunks of
+// queries adds them to.  Every entry is a fixed-shape launch without a host read, an allocation or an atomic, and writes
+// the same bits on every run.
+//
+// The file is built with -ffp-contract=off (pcr_amd/build.py): the binary64 quotients and sums are compared bit for bit
+// with the CPU restatement (tests/rank_ref.py).
+#include "pcr_common.h"
+
+namespace {
+
+constexpr float kNegInf = -__builtin_inff();
+
+// ---- the score matrix ------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void rank_fill_kernel(float *__restrict__ scores, long long total) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i < total) scores[i] = kNegInf;
+}
+
+__global__ __launch_bounds__(256) void rank_scatter_kernel(const float *__restrict__ logits, const int *__restrict__ pairs,
+                                                           const int *__restrict__ count, float *__restrict__ scores, int Q,
+                                                           int G, int cap) {
+  const int k = blockIdx.x * 256 + threadIdx.x;
+  int n = count[0];
+  n = n < 0 ? 0 : n > cap ? cap : n;
+  if (k >= n) return;
+  const int q = pairs[2 * (size_t)k], g = pairs[2 * (size_t)k + 1];
+  if (q < 0 || q >= Q || g < 0 || g >= G) return;
+  scores[(size_t)q * G + g] = logits[k];
+}
+
+// ---- the ranking -----------------------------------------------------------------------------------------------------------
+// (order-preserving score bits, inverted index): the larger key is the better candidate.  A zero of either sign is +0, as
+// the float compare has them equal; no key of a candidate is 0 (its low word is at least 2^32 - 1 - 4095).
+__device__ __forceinline__ unsigned long long rank_key(float s, int g) {
+  const float z = s == 0.0f ? 0.0f : s;
+  return ((unsigned long long)pcr_orderable(z) << 32) | (0xFFFFFFFFu - (uint32_t)g);
+}
+
+// a wave-uniform 64-bit word out of lane `l` (wave-uniform)
+__device__ __forceinline__ unsigned long long rank_lane_u64(unsigned long long v, int l) {
+  const uint32_t lo = wave_readlane((uint32_t)v, l), hi = wave_readlane((uint32_t)(v >> 32), l);
+  return ((unsigned long long)hi << 32) | lo;
+}
+
+// LDS of a query: row [G] f32, a non-candidate holds -inf | hit [G] i32: the true candidates' ranks, ascending
+__global__ __launch_bounds__(kWave) void rank_gallery_kernel(pcr_rank p) {
+  extern __shared__ float rank_lds[];
+  const int G = p.G, K = p.K, q = blockIdx.x, lane = threadIdx.x;
+  float *row = rank_lds;
+  int *hit = reinterpret_cast<int *>(rank_lds + G);
+  const int chunks = (G + kWave - 1) / kWave;               // <= 64: lane c keeps chunk c's word of the true set
+  const int qid = p.query_ids[q];
+  int ex = p.exclude != nullptr ? p.exclude[q] : -1;
+  if (ex < 0 || ex >= G) ex = -1;
+
+  // ---- 1. the row: candidates, NaNs, the true set --------------------------------------------------------------------------
+  int n_cand = 0, n_true = 0;
+  bool flagged = false;
+  unsigned long long true_word = 0ull;
+  for (int c = 0; c < chunks; ++c) {
+    const int g = c * kWave + lane;
+    float s = kNegInf;
+    if (g < G && g != ex) s = p.scores[(size_t)q * G + g];
+    const bool cand = s != kNegInf;                         // (true for a NaN)
+    const bool truth = cand && qid >= 0 && p.gallery_ids[g] == qid;
+    if (g < G) row[g] = s;
+    const unsigned long long nans = __ballot(cand && s != s);
+    flagged = flagged || nans != 0ull;
+    n_cand += __popcll(__ballot(cand));
+    const unsigned long long tb = __ballot(truth);
+    n_true += __popcll(tb);
+    if (lane == c) true_word = tb;
+  }
+  __syncthreads();                                          // (the workgroup is this one wave)
+
+  if (flagged) {
+    for (int r = lane; r < K; r += kWave) p.topk_idx[(size_t)q * K + r] = -1, p.topk_score[(size_t)q * K + r] = kNegInf;
+    if (lane == 0) p.n_cand[q] = 0, p.n_true[q] = 0, p.first_hit[q] = -1, p.ap[q] = 0.0f, p.info[q] = 1;
+    return;
+  }
+
+  // ---- 2. top-k: round r takes the largest key below round r - 1's; lane r keeps the winner ------------------------------
+  const int rounds = K < n_cand ? K : n_cand;
+  unsigned long long below = ~0ull;
+  int my_idx = -1;
+  float my_score = kNegInf;
+  for (int r = 0; r < rounds; ++r) {
+    unsigned long long best = 0ull;
+    for (int c = 0; c < chunks; ++c) {
+      const int g = c * kWave + lane;
+      const float s = g < G ? row[g] : kNegInf;
+      const unsigned long long key = s != kNegInf ? rank_key(s, g) : 0ull;
+      if (key < below && key > best) best = key;
+    }
+    below = pcr_wave_max_u64(best);                         // never 0: r < n_cand
+    const int g = (int)(0xFFFFFFFFu - (uint32_t)below);
+    if (lane == r && below != 0ull) my_idx = g, my_score = row[g];
+  }
+  if (lane < K) p.topk_idx[(size_t)q * K + lane] = my_idx, p.topk_score[(size_t)q * K + lane] = my_score;
+
+  // ---- 3. the true candidates: rank, and place among the true ones, by ballot popcounts over the row --------------------
+  for (int c = 0; c < chunks; ++c) {
+    unsigned long long todo = rank_lane_u64(true_word, c);
+    for (int n = __popcll(todo); n > 0; --n) {
+      const int g = c * kWave + __ffsll((long long)todo) - 1;
+      todo &= todo - 1ull;
+      const float sg = row[g];
+      int rank = 0, place = 0;
+      for (int c2 = 0; c2 < chunks; ++c2) {
+        const int j = c2 * kWave + lane;
+        const float sj = j < G ? row[j] : kNegInf;           // (-inf beats nothing and equals no candidate's score)
+        const unsigned long long beats = __ballot(sj > sg || (sj == sg && j < g));
+        rank += __popcll(beats);
+        place += __popcll(beats & rank_lane_u64(true_word, c2));
+      }
+      if (lane == 0) hit[place] = rank;                      // the places are a permutation of [0, n_true)
+    }
+  }
+  __syncthreads();
+
+  // ---- 4. average precision: the quotients by the lanes, the sum in ascending place by all of them alike -----------------
+  double sum = 0.0;
+  for (int base = 0; base < n_true; base += kWave) {
+    const int i = base + lane;
+    double quot = 0.0;
+    if (i < n_true) quot = (double)(i + 1) / (double)(hit[i] + 1);
+    const int m = n_true - base < kWave ? n_true - base : kWave;
+    for (int l = 0; l < m; ++l) sum = sum + __longlong_as_double((long long)rank_lane_u64((unsigned long long)__double_as_longlong(quot), l));
+  }
+  if (lane == 0) {
+    p.n_cand[q] = n_cand;
+    p.n_true[q] = n_true;
+    p.first_hit[q] = n_true > 0 ? hit[0] : -1;
+    p.ap[q] = n_true > 0 ? (float)(sum / (double)n_true) : 0.0f;
+    p.info[q] = 0;
+  }
+}
+
+// ---- the table -------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kWave) void rank_accumulate_kernel(pcr_rank_acc p) {
+  const int lane = threadIdx.x;
+  int n = p.Q;
+  if (p.valid != nullptr) {
+    const int v = p.valid[0];
+    n = v < 0 ? 0 : v > p.Q ? p.Q : v;
+  }
+  int scored = 0, unscored = 0, flagged = 0;
+  int cmc[PCR_RANK_MAX_RANKS];
+#pragma unroll
+  for (int i = 0; i < PCR_RANK_MAX_RANKS; ++i) cmc[i] = 0;
+  double sum_ap = p.sums[0], sum_rr = p.sums[1];
+  for (int base = 0; base < n; base += kWave) {
+    const int q = base + lane;
+    const bool in = q < n;
+    const int info = in ? p.info[q] : 0, nt = in ? p.n_true[q] : 0, fh = in ? p.first_hit[q] : 0;
+    const bool is_flagged = in && info != 0, is_scored = in && info == 0 && nt > 0;
+    double ap = 0.0, rr = 0.0;
+    if (is_scored) ap = (double)p.ap[q], rr = 1.0 / (double)(fh + 1);
+    unsigned long long todo = __ballot(is_scored);
+    scored += __popcll(todo);
+    flagged += __popcll(__ballot(is_flagged));
+    unscored += __popcll(__ballot(in && !is_flagged && !is_scored));
+#pragma unroll
+    for (int i = 0; i < PCR_RANK_MAX_RANKS; ++i)
+      if (i < p.nranks) cmc[i] += __popcll(__ballot(is_scored && fh < p.ranks[i]));
+    for (int k = __popcll(todo); k > 0; --k) {               // the scored queries, ascending
+      const int l = __ffsll((long long)todo) - 1;
+      todo &= todo - 1ull;
+      sum_ap = sum_ap + __longlong_as_double((long long)rank_lane_u64((unsigned long long)__double_as_longlong(ap), l));
+      sum_rr = sum_rr + __longlong_as_double((long long)rank_lane_u64((unsigned long long)__double_as_longlong(rr), l));
+    }
+  }
+  if (lane == 0) {
+    p.counts[0] += scored;
+    p.counts[1] += unscored;
+    p.counts[2] += flagged;
+    p.sums[0] = sum_ap;
+    p.sums[1] = sum_rr;
+  }
+#pragma unroll
+  for (int i = 0; i < PCR_RANK_MAX_RANKS; ++i)
+    if (lane == 0 && i < p.nranks) p.counts[3 + i] += cmc[i];
+}
+
+}  // namespace
+
+PCR_EXPORT int pcr_rank_ok(int Q, int G, int K, int cap) {
+  return Q >= 0 && Q <= PCR_RANK_MAX_QUERIES && G >= 0 && G <= PCR_RANK_MAX_GALLERY && K >= 1 && K <= PCR_RANK_MAX_K &&
+         cap >= 0 && (long long)cap <= (long long)Q * G;
+}
+
+PCR_EXPORT int pcr_rank_scores_f32(const float *logits, const int *pairs, const int *count, float *scores, int Q, int G,
+                                   int cap, pcr_stream_t stream) {
+  if (!pcr_rank_ok(Q, G, 1, cap)) return PCR_ERR_INVALID;
+  if (Q == 0 || G == 0) return PCR_OK;
+  if (!scores || (cap > 0 && (!logits || !pairs || !count))) return PCR_ERR_INVALID;
+  const long long total = (long long)Q * G;
+  const int st = pcr_launch<rank_fill_kernel>(dim3((unsigned)((total + 255) / 256)), dim3(256), 0, pcr_s(stream), scores, total);
+  if (st != PCR_OK || cap == 0) return st;
+  return pcr_launch<rank_scatter_kernel>(dim3((cap + 255) / 256), dim3(256), 0, pcr_s(stream), logits, pairs, count, scores, Q,
+                                         G, cap);
+}
+
+PCR_EXPORT int pcr_rank_gallery_f32(const pcr_rank *p, pcr_stream_t stream) {
+  if (!p || !pcr_rank_ok(p->Q, p->G, p->K, 0)) return PCR_ERR_INVALID;
+  if (p->Q == 0) return PCR_OK;
+  if (!p->query_ids || !p->topk_idx || !p->topk_score || !p->n_cand || !p->n_true || !p->first_hit || !p->ap || !p->info)
+    return PCR_ERR_INVALID;
+  if (p->G > 0 && (!p->scores || !p->gallery_ids)) return PCR_ERR_INVALID;
+  return pcr_launch<rank_gallery_kernel>(dim3(p->Q), dim3(kWave), (size_t)2 * p->G * sizeof(float), pcr_s(stream), *p);
+}
+
+PCR_EXPORT int pcr_rank_accumulate(const pcr_rank_acc *p, pcr_stream_t stream) {
+  if (!p || !pcr_rank_ok(p->Q, p->G, 1, 0) || p->nranks < 0 || p->nranks > PCR_RANK_MAX_RANKS) return PCR_ERR_INVALID;
+  for (int i = 0; i < p->nranks; ++i)
+    if (p->ranks[i] < 1 || p->ranks[i] > p->G) return PCR_ERR_INVALID;
+  if (!p->counts || !p->sums) return PCR_ERR_INVALID;
+  if (p->Q == 0) return PCR_OK;
+  if (!p->n_true || !p->first_hit || !p->info || !p->ap) return PCR_ERR_INVALID;
+  return pcr_launch<rank_accumulate_kernel>(dim3(1), dim3(kWave), 0, pcr_s(stream), *p);
+}

@@ -707,6 +707,36 @@ class ReIDNet(nn.Module):
                     det_to_track=torch.where(r < T, r, torch.full_like(r, -1)), pairs=pairs, count=count, logits=logits,
                     cost=cost, info=info, **({} if block_info is None else {"block_info": block_info}))
 
+    def retrieve(self, q_feats, q_xyz, q_labels, q_lengths, g_feats, g_xyz, g_labels, g_lengths, query_ids=None,
+                 gallery_ids=None, topk=10, exclude=None, min_points=2, num_classes=8, live_only=False):
+        """Rank a gallery for every query on the device (pcr_amd/retrieval.py; INTEGRATION.md "2h. Ranking a gallery"):
+        compare_pairs with the queries in the tracks' place (a pair of one class, both sides of at least min_points points
+        when lengths are given), match_gallery over [queries | gallery], score_matrix (-inf where no pair was listed) and
+        rank_gallery -- no host read beyond the guard's first-batch calibration that every inference entry point has.
+        q_feats (Q,C,N) / q_xyz (Q,N,3) and g_feats (G,C,N) / g_xyz (G,N,3) are what forward_inference returned;
+        query_ids (Q,) / gallery_ids (G,) int32 name identities (< 0, or None: none -- then only topk_* and n_cand mean
+        anything); exclude (Q,) int32 names the one gallery entry a query skips (its own observation in a gallery that
+        holds the queries).  live_only: match_gallery scores the count listed pairs only.
+        -> rank_gallery's dict (topk_idx, topk_score (Q, topk), n_cand, n_true, first_hit, ap, info (Q,)) plus pairs,
+        count, logits and scores (Q, G)."""
+        from pcr_amd import associate as A
+        from pcr_amd import retrieval as R
+        L.require_cuda(q_feats, q_xyz, g_feats, g_xyz)
+        Q, G = q_feats.shape[0], g_feats.shape[0]
+        if not R.rank_ok(Q, G, topk):
+            raise L.PcrError("retrieve: Q=%d G=%d topk=%d is out of range (pcr_rank_ok)" % (Q, G, topk))
+        pairs, count = A.compare_pairs(q_labels, g_labels, q_lengths, g_lengths, min_points=min_points,
+                                       num_classes=num_classes)
+        if Q == 0 or G == 0:
+            logits = torch.empty((pairs.shape[0],), dtype=torch.float32, device=q_feats.device)
+        else:
+            gallery_pairs = torch.stack([pairs[:, 0], pairs[:, 1] + Q], dim=1)       # the gallery follows the queries
+            logits = self.match_gallery(torch.cat([q_feats, g_feats], dim=0), torch.cat([q_xyz, g_xyz], dim=0),
+                                        gallery_pairs, count=count if live_only else None).contiguous()
+        scores = R.score_matrix(logits, pairs, count, Q, G)
+        out = R.rank_gallery(scores, query_ids, gallery_ids, topk=topk, exclude=exclude)
+        return dict(pairs=pairs, count=count, logits=logits, scores=scores, **out)
+
     def track_step(self, bank, sweep, boxes, labels, scores, carry=None, carry_inv=None, min_points=2, num_classes=8,
                    cap=None, n=None, crop_args=None, born=None, kill=None, frame_limit=10, replace_all=False,
                    reset_on_match=False, propagate=True, suppress_threshold=0.15, live_only=False, truth=None,

@@ -43,6 +43,12 @@ TruthParams = _block("TruthParams", """
     ptr gt_labels gt_ids gt_tte det_labels track_to_det det_to_track born kill;
     ptr det_gt true_t2d true_d2t det_truth track_truth det_slot det_id""")
 
+# ---- section A8 (pcr_rank, pcr_rank_acc) ----
+RankParams = _block("RankParams", """
+    int Q G K; ptr scores query_ids gallery_ids exclude topk_idx topk_score n_cand n_true first_hit ap info""")
+RankAccParams = _block("RankAccParams", """
+    int Q G nranks; int[8] ranks; ptr n_true first_hit info ap valid counts sums""")
+
 # ---- section A6 (pcr_store_tables) ----
 StoreTables = _block("StoreTables", """
     int num_objects num_classes; ptr obj_cls obj_fp obj_id nums_off nums_rows bucket_off bucket_rows pool_off pool_objs""")
@@ -86,7 +92,7 @@ _AttnHeadP = _block("_AttnHeadP", """
 
 # the header's name of every block (what the layout test compiles against)
 BLOCKS = {"pcr_assoc_multi": AssocMultiParams, "pcr_assoc_decode": AssocDecodeParams, "pcr_bank": BankParams,"pcr_truth": TruthParams, "pcr_store_tables": StoreTables, "pcr_sa_params": SaParams, "pcr_attn_params": AttnParams, "pcr_head_params": HeadParams,
-          "pcr_live": LiveParams,
+          "pcr_live": LiveParams, "pcr_rank": RankParams, "pcr_rank_acc": RankAccParams,
           "pcr_tdense_fwd": _TFwd, "pcr_tdense_bwd": _TBwd, "pcr_bn_fwd_fin": _BnFwd, "pcr_bn_bwd_fin": _BnBwd,
           "pcr_reduce_job": _ReduceJob, "pcr_linattn": _LinAttnP, "pcr_attn_tail": _AttnTailP,
           "pcr_attn_head": _AttnHeadP}
@@ -201,6 +207,11 @@ SIGNATURES = {
     "pcr_truth_cost_f32": "s FIFIIFFiiiiS",
     "pcr_truth_decide_i32": "s <TruthParams>S",
     "pcr_truth_record_i32": "s <TruthParams>S",
+    # A8. ranking a gallery
+    "pcr_rank_ok": "i iiii",
+    "pcr_rank_scores_f32": "s FIIFiiiS",
+    "pcr_rank_gallery_f32": "s <RankParams>S",
+    "pcr_rank_accumulate": "s <RankAccParams>S",
     # B. fused model kernels
     "pcr_knn_prefix_f32": "s FIiiiiS",
     "pcr_knn_prefix2_f32": "s FIIiiiiiiS",

@@ -24,6 +24,7 @@ FLAGS = {
     "nms_kernels.hip": ["-ffp-contract=off"],        # IoUs are compared with a threshold; the axis-aligned ones bit for bit
     "track_kernels.hip": ["-ffp-contract=off"],      # the propagated boxes and the distances are compared bit for bit
     "truth_kernels.hip": ["-ffp-contract=off"],      # the ground-truth matching cost is compared bit for bit
+    "rank_kernels.hip": ["-ffp-contract=off"],       # the binary64 average-precision sums are compared bit for bit
 }
 
 

@@ -1,0 +1,257 @@
+"""Ranking a gallery on the device (include/pcr.h section A8, csrc/rank_kernels.hip).
+
+`ReIDNet.match_gallery` scores any list of (i, j) combinations; its consumer so far is the tracker frame, which turns the
+logits into a cost matrix and an assignment.  The other thing one does with a re-identification model is retrieval: for
+every query object, which gallery objects is it, and how often does the right one come first.  Here that is three
+fixed-shape launches without a host read and with the same bits on every run, so a ranked chunk of queries can be captured
+in a HIP graph: `score_matrix` scatters the logits of a pair list onto -inf ("not a candidate"), `rank_gallery` ranks
+every row (top-k, the first hit and the average precision against identities; ties to the lowest gallery index, the rule of
+pcr_amd/nms.py), and `RankBook.add` adds a chunk's results to a table on the device.  `RankBook.metrics()` is the one host
+read.  `ReIDNet.retrieve` chains compare_pairs, match_gallery and the two launches; `evaluate_retrieval` walks a split of a
+`CropStore` through it.  INTEGRATION.md ("2h. Ranking a gallery") has the mapping and the rules.
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from . import abi
+
+MAX_QUERIES, MAX_GALLERY, MAX_K, MAX_RANKS = 65535, 4096, 64, 8      # PCR_RANK_MAX_*
+OUTPUTS = ("topk_idx", "topk_score", "n_cand", "n_true", "first_hit", "ap", "info")
+_FLOAT_OUTPUTS = ("topk_score", "ap")
+
+
+def _require(ok, what):
+    if not ok:
+        raise L.PcrError("pcr_amd.retrieval: " + what)
+
+
+def rank_ok(Q, G, K=1, cap=0):
+    """whether the section-A8 entry points take Q queries, G gallery entries, K ranks and a pair list of cap entries"""
+    return bool(L.load().pcr_rank_ok(int(Q), int(G), int(K), int(cap)))
+
+
+def _tensors(*ts):
+    for t in ts:
+        _require(t is None or isinstance(t, torch.Tensor), "every argument must be a tensor")
+    L.require_cuda(*ts)
+
+
+def score_matrix(logits, pairs, count, Q, G, out=None):
+    """pcr_rank_scores_f32: logits (cap,), pairs (cap, 2) int32, count (1,) int32 on the device -> scores (Q, G) float32,
+    every element written: logits[k] at pairs[k] = (q, g) for k < min(count, cap), -inf elsewhere; a pair outside
+    [0, Q) x [0, G) is skipped.  The pairs must be distinct (compare_pairs' are).  out = a (Q, G) tensor to write into."""
+    _tensors(logits, pairs, count, out)
+    L.require_f32(logits, out)
+    L.require_i32(pairs, count)
+    Q, G = int(Q), int(G)
+    _require(pairs is not None and pairs.dim() == 2 and pairs.shape[1] == 2 and pairs.is_contiguous(),
+             "pairs must be a contiguous (cap, 2) tensor")
+    cap = pairs.shape[0]
+    _require(logits is not None and logits.shape == (cap,) and logits.is_contiguous(), "logits must be a contiguous (%d,) tensor" % cap)
+    _require(count is not None and count.numel() == 1, "count must be a (1,) int32 device tensor")
+    _require(Q >= 0 and G >= 0 and cap <= Q * G and rank_ok(Q, G, 1, cap),
+             "Q=%d G=%d cap=%d is out of range (pcr_rank_ok)" % (Q, G, cap))
+    if out is None:
+        out = torch.empty((Q, G), dtype=torch.float32, device=logits.device)
+    _require(out.shape == (Q, G) and out.is_contiguous(), "out must be a contiguous (%d, %d) tensor" % (Q, G))
+    L.run.pcr_rank_scores_f32(logits, pairs, count, out, Q, G, cap, L.stream_ptr())
+    return out
+
+
+def rank_buffers(Q, K, device):
+    """the seven outputs of rank_gallery for Q queries and K ranks, to be passed as out= (a captured graph keeps them)"""
+    return {k: torch.empty((Q, K) if k.startswith("topk") else (Q,),
+                           dtype=torch.float32 if k in _FLOAT_OUTPUTS else torch.int32, device=device) for k in OUTPUTS}
+
+
+def rank_gallery(scores, query_ids, gallery_ids, topk=10, exclude=None, out=None):
+    """pcr_rank_gallery_f32: scores (Q, G) float32 (-inf = not a candidate), query_ids (Q,), gallery_ids (G,) int32 (a value
+    < 0, or None: no identity), exclude (Q,) int32 or None: the one gallery entry a query does not rank ->
+    dict(topk_idx (Q, K) int32, topk_score (Q, K), n_cand, n_true, first_hit (Q,) int32, ap (Q,) float32, info (Q,) int32),
+    every element written by the rules of include/pcr.h section A8: descending score, ties to the lowest gallery index;
+    info 1 = a candidate's score is a NaN, the query is not ranked.  With None ids only topk_* and n_cand are meaningful.
+    out = such a dict (`rank_buffers`) to write into."""
+    _tensors(scores, query_ids, gallery_ids, exclude)
+    L.require_f32(scores)
+    L.require_i32(query_ids, gallery_ids, exclude)
+    _require(scores is not None and scores.dim() == 2 and scores.is_contiguous(), "scores must be a contiguous (Q, G) tensor")
+    (Q, G), K = scores.shape, int(topk)
+    _require(rank_ok(Q, G, K), "Q=%d G=%d topk=%d is out of range (pcr_rank_ok)" % (Q, G, K))
+    dev = scores.device
+    if query_ids is None:
+        query_ids = torch.full((Q,), -1, dtype=torch.int32, device=dev)
+    if gallery_ids is None:
+        gallery_ids = torch.full((G,), -1, dtype=torch.int32, device=dev)
+    for t, n, name in ((query_ids, Q, "query_ids"), (gallery_ids, G, "gallery_ids"), (exclude, Q, "exclude")):
+        _require(t is None or (t.shape == (n,) and t.is_contiguous()), "%s must be a contiguous (%d,) tensor" % (name, n))
+    if out is None:
+        out = rank_buffers(Q, K, dev)
+    _require(isinstance(out, dict) and all(k in out for k in OUTPUTS), "out must hold %s" % ", ".join(OUTPUTS))
+    _tensors(*[out[k] for k in OUTPUTS])
+    L.require_f32(*[out[k] for k in _FLOAT_OUTPUTS])
+    L.require_i32(*[out[k] for k in OUTPUTS if k not in _FLOAT_OUTPUTS])
+    p = abi.RankParams()
+    p.Q, p.G, p.K = Q, G, K
+    for k in OUTPUTS:
+        shape = (Q, K) if k.startswith("topk") else (Q,)
+        _require(out[k].shape == shape and out[k].is_contiguous(), "out[%r] must be a contiguous %s tensor" % (k, shape))
+        setattr(p, k, L._p(out[k]) if Q else None)
+    p.scores = L._p(scores) if Q * G else None
+    p.query_ids = L._p(query_ids) if Q else None
+    p.gallery_ids = L._p(gallery_ids) if G else None
+    p.exclude = L._p(exclude) if exclude is not None and Q else None
+    L.run.pcr_rank_gallery_f32(ctypes.byref(p), L.stream_ptr())
+    return {k: out[k] for k in OUTPUTS}
+
+
+def metrics_of(counts, sums, ranks):
+    """the table on the host (counts: 3 + len(ranks) ints, sums: 2 floats) -> cmc@r per rank, mAP, mrr (NaN when no query
+    was scored) and the raw counters scored (a true candidate exists), unscored (none does), flagged (a NaN)"""
+    c = [int(v) for v in counts]
+    scored = c[0]
+    out = {"cmc@%d" % r: (c[3 + i] / scored if scored else float("nan")) for i, r in enumerate(ranks)}
+    out["mAP"] = float(sums[0]) / scored if scored else float("nan")
+    out["mrr"] = float(sums[1]) / scored if scored else float("nan")
+    out["scored"], out["unscored"], out["flagged"] = c[0], c[1], c[2]
+    return out
+
+
+class RankBook:
+    """The retrieval table of an evaluation, on the device: `counts` (3 + len(ranks),) int32 = scored, unscored, flagged
+    queries and, per rank r, the scored queries whose first hit lies below r; `sums` (2,) float64 = the running sums of the
+    average precision and of 1 / (first_hit + 1) over the scored queries, in the order they were added.  `add` is one launch
+    on the current stream without a host read; `metrics` is the host read.  One book per class gives per-class figures, as
+    for `TruthBook`."""
+
+    def __init__(self, ranks=(1, 5, 10), device="cuda"):
+        self.ranks = tuple(int(r) for r in ranks)
+        _require(len(self.ranks) <= MAX_RANKS and all(1 <= r <= MAX_GALLERY for r in self.ranks),
+                 "ranks must be at most %d values in [1, %d]" % (MAX_RANKS, MAX_GALLERY))
+        self.device = torch.device(device)
+        self.counts = torch.zeros(3 + len(self.ranks), dtype=torch.int32, device=self.device)
+        self.sums = torch.zeros(2, dtype=torch.float64, device=self.device)
+
+    def reset(self):
+        self.counts.zero_()
+        self.sums.zero_()
+
+    def add(self, result, valid=None, gallery=None):
+        """pcr_rank_accumulate: result = rank_gallery's (or retrieve's) dict; valid = a (1,) int32 device tensor (or an
+        int): only the first clamp(valid, 0, Q) queries count (the rest is a chunk's padding); gallery = the number of
+        gallery entries G the ranks are held against (every rank must lie in [1, G]); by default the width of
+        result['scores'] when retrieve returned it, the largest rank otherwise."""
+        ts = [result[k] for k in ("n_true", "first_hit", "info", "ap")]
+        if isinstance(valid, int):
+            valid = torch.tensor([valid], dtype=torch.int32, device=self.device)
+        _tensors(*ts, valid)
+        L.require_i32(ts[0], ts[1], ts[2], valid)
+        L.require_f32(ts[3])
+        Q = ts[0].shape[0]
+        for t in ts:
+            _require(t.shape == (Q,) and t.is_contiguous(), "the per-query results must be contiguous (Q,) tensors")
+        _require(valid is None or valid.numel() == 1, "valid must be a (1,) int32 device tensor")
+        if gallery is None:
+            gallery = result["scores"].shape[1] if "scores" in result else max(self.ranks, default=0)
+        G = int(gallery)
+        _require(rank_ok(Q, G) and all(r <= G for r in self.ranks),
+                 "Q=%d G=%d ranks=%s: out of range (pcr_rank_ok), or a rank above the gallery" % (Q, G, self.ranks))
+        p = abi.RankAccParams()
+        p.Q, p.G, p.nranks = Q, G, len(self.ranks)
+        for i, r in enumerate(self.ranks):
+            p.ranks[i] = r
+        p.n_true, p.first_hit, p.info, p.ap = (L._p(t) if Q else None for t in ts)
+        p.valid = L._p(valid)
+        p.counts, p.sums = L._p(self.counts), L._p(self.sums)
+        L.run.pcr_rank_accumulate(ctypes.byref(p), L.stream_ptr())
+
+    def metrics(self):
+        """THE host read: see `metrics_of`"""
+        return metrics_of(self.counts.cpu().tolist(), self.sums.cpu().tolist(), self.ranks)
+
+
+def retrieval_split(table, row_of, seed=0):
+    """One query and one gallery observation per true object of an `ObjectTable`, distractors from everything else, on the
+    host -> (query_rows, gallery_rows, query_cls, gallery_cls, query_ids, gallery_ids), int32 arrays.
+
+    For object index i of table.true_index, ascending, with obs = its `nums`: a, b = np.random.default_rng([seed, i]).
+    choice(len(obs), 2, replace=False); the query is row_of[(token, obs[a])], its partner in the gallery
+    row_of[(token, obs[b])], both with id i.  Every other object of a tracked class with at least one observation (the
+    false positives, the tracks too short to be queries) gives a distractor: the observation
+    obs[np.random.default_rng([seed, i]).integers(len(obs))] in the gallery with id -1.  The gallery is in object order."""
+    true = set(table.true_index)
+    q_rows, q_cls, q_ids, g_rows, g_cls, g_ids = [], [], [], [], [], []
+    for i, o in enumerate(table.objects):
+        obs = o["nums"]
+        rng = np.random.default_rng([int(seed), i])
+        if i in true:
+            a, b = rng.choice(len(obs), 2, replace=False)
+            q_rows.append(row_of[(o["token"], obs[a])])
+            q_cls.append(o["cls"])
+            q_ids.append(i)
+            g_rows.append(row_of[(o["token"], obs[b])])
+            g_cls.append(o["cls"])
+            g_ids.append(i)
+        elif o["cls"] != -1 and len(obs) > 0:
+            g_rows.append(row_of[(o["token"], obs[int(rng.integers(len(obs)))])])
+            g_cls.append(o["cls"])
+            g_ids.append(-1)
+    i32 = lambda a: np.asarray(a, dtype=np.int32)          # noqa: E731
+    return i32(q_rows), i32(g_rows), i32(q_cls), i32(g_cls), i32(q_ids), i32(g_ids)
+
+
+def _encode(model, clouds, batch):
+    """forward_inference over clouds (B, n, 3) in batches -> xyz (B, N, 3), feats (B, C, N)"""
+    xyz, feats = [], []
+    cm = model.use_dgcnn or type(model.backbone).__name__ == "PointNet"
+    for lo in range(0, clouds.shape[0], batch):
+        c = clouds[lo:lo + batch]
+        x, h = model.forward_inference(c.permute(0, 2, 1).contiguous() if cm else c)[:2]
+        xyz.append(x)
+        feats.append(h)
+    return torch.cat(xyz, dim=0).contiguous(), torch.cat(feats, dim=0).contiguous()
+
+
+def evaluate_retrieval(model, store, split, n=None, seed=0, topk=10, ranks=(1, 5, 10), query_chunk=64, min_points=2,
+                       num_classes=None, live_only=True, encode_batch=256):
+    """Retrieval over a `CropStore`: split = retrieval_split's six arrays.  The clouds come from store.gather(rows, n,
+    keys=rows, seed=seed) (a row's sample depends on the row and the seed alone), the gallery is encoded once, the queries
+    walk through `ReIDNet.retrieve` in chunks of query_chunk -- the last one padded with class -1, which joins nothing, the
+    real count going to the book as `valid` -- and each chunk is added to a `RankBook`.  -> book.metrics() (the one host
+    read) plus the per-query tensors of rank_gallery, (Q, ...) on the device, and the book itself under 'book'.
+    num_classes defaults to the store's table's."""
+    q_rows, g_rows, q_cls, g_cls, q_ids, g_ids = (np.asarray(a, dtype=np.int32) for a in split)
+    Q, G, chunk = len(q_rows), len(g_rows), int(query_chunk)
+    _require(1 <= G <= MAX_GALLERY, "a gallery of %d entries: 1 to PCR_RANK_MAX_GALLERY = %d can be ranked" % (G, MAX_GALLERY))
+    _require(chunk >= 1 and rank_ok(chunk, G, topk), "query_chunk=%d G=%d topk=%d is out of range (pcr_rank_ok)" % (chunk, G, topk))
+    _require(len(q_cls) == Q and len(q_ids) == Q and len(g_cls) == G and len(g_ids) == G, "the split's arrays do not agree")
+    if num_classes is None:
+        num_classes = int(store.table.num_classes) if getattr(store, "table", None) is not None else 8
+    n = int(n or store.n)
+    dev = store.device
+    put = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)      # noqa: E731
+    book = RankBook(ranks, dev)
+    per_query = {k: [] for k in OUTPUTS}
+    with torch.no_grad():
+        g_rows_t, g_cls_t, g_ids_t = put(g_rows), put(g_cls), put(g_ids)
+        g_clouds, g_sizes = store.gather(g_rows_t, n, keys=g_rows_t, seed=seed)
+        g_xyz, g_feats = _encode(model, g_clouds, encode_batch)
+        for lo in range(0, Q, chunk):
+            real = min(chunk, Q - lo)
+            pad = lambda a, fill: np.concatenate([a[lo:lo + real], np.full(chunk - real, fill, np.int32)])   # noqa: E731
+            rows_t, cls_t, ids_t = put(pad(q_rows, 0)), put(pad(q_cls, -1)), put(pad(q_ids, -1))
+            clouds, sizes = store.gather(rows_t, n, keys=rows_t, seed=seed)
+            xyz, feats = _encode(model, clouds, encode_batch)
+            res = model.retrieve(feats, xyz, cls_t, sizes, g_feats, g_xyz, g_cls_t, g_sizes, query_ids=ids_t,
+                                 gallery_ids=g_ids_t, topk=topk, min_points=min_points, num_classes=num_classes,
+                                 live_only=live_only)
+            book.add(res, valid=torch.tensor([real], dtype=torch.int32, device=dev), gallery=G)
+            for k in OUTPUTS:
+                per_query[k].append(res[k][:real])
+    out = book.metrics()
+    empty = rank_buffers(0, int(topk), dev)
+    out.update({k: torch.cat(v, dim=0) if v else empty[k] for k, v in per_query.items()})
+    out["book"] = book
+    return out

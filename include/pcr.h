@@ -842,6 +842,133 @@ int pcr_rank_scores_f32(const float *logits, const int *pairs, const int *count,
 int pcr_rank_gallery_f32(const pcr_rank *p, pcr_stream_t stream);
 int pcr_rank_accumulate(const pcr_rank_acc *p, pcr_stream_t stream);
 
+/* ------------------------------------------------------------ A9. identity preservation -------- */
+
+/* Did an object keep one identity over its whole life?  The MOT counters of A7 count a switch once, however long the wrong
+ * identity is then kept; this section keeps what the identity metrics need (IDF1 / IDP / IDR; per trajectory MT / PT / ML,
+ * FRAG, TID, LGD; MOTP) in persistent tables on the device: one launch per frame after pcr_truth_record_i32, and at the
+ * end of a scene a compaction, pcr_lsa_f32 of A3 as a (1, max_rows, max_cols) problem and a score launch.  (An addition:
+ * the reference keeps none of it.)  Fixed shapes, no host read, no allocation, no float atomic (integer sums, minima and
+ * maxima only: their result does not depend on the order); the same bits on every run; every loop is bounded by an integer
+ * count; every element of every output is written.  Pointers are checked against NULL only.  The result is DEFINED by the
+ * rules below (tests/ident_ref.py restates them; the kernels equal it bit for bit, the binary64 sums included).
+ * pcr_ident_ok: D and G as in pcr_truth_ok (0 <= D, G <= PCR_LSA_MAX), 1 <= gt_cap <= PCR_TRUTH_MAX_IDS, 1 <= gt_rows,
+ * id_cap <= PCR_IDENT_MAX_DIM, gt_rows * id_cap <= PCR_IDENT_MAX_CELLS, 1 <= max_rows, max_cols <= PCR_LSA_MAX.
+ *
+ * The notions are pcr_truth_record_i32's, unchanged: a detection d is VALID iff det_labels[d] >= 0, a ground-truth box j
+ * iff gt_labels[j] >= 0 and gt_ids[j] lies in [0, gt_cap); d is a TRUE POSITIVE iff it is valid, j = det_gt[d] lies in
+ * [0, G) and box j is valid; then g = gt_ids[j] is its track and i = det_id[d] the identity the tracker gave it.  Every
+ * index is checked against its range before it addresses memory: det_gt[d], gt_ids[j], det_id[d], g and i; a value out of
+ * range has the meaning stated here or counts as -1.
+ *
+ * Scene state.  cooc (gt_rows, id_cap) int32; gt_track (gt_rows, PCR_IDENT_TRACK_COLS) int32 with the columns
+ * PCR_IDENT_PRESENT .. PCR_IDENT_LAST; totals (PCR_IDENT_TOTALS) int32; dist_sum (1) binary64.  All start at zero.
+ *
+ * pcr_ident_record_i32: one launch (one workgroup) per frame, AFTER pcr_truth_record_i32, over its buffers as they stand.
+ *   tracks   an id g is PRESENT iff a valid ground-truth box carries it -- once, however many boxes do.  The LOWEST true
+ *            positive of g is the least d among the true positives whose track is g (over all boxes that carry g).  g is
+ *            TRACKED this frame iff that d exists and det_id[d] >= 0.  For every present g < gt_rows: PRESENT += 1; if
+ *            tracked: TRACKED += 1; if EVER and LAST == 0: FRAGS += 1; if not EVER: FIRST_GAP = CUR_GAP; then EVER = 1,
+ *            CUR_GAP = 0, LAST = 1; if not tracked: CUR_GAP += 1, LONGEST_GAP = max(LONGEST_GAP, CUR_GAP), LAST = 0.  An
+ *            absent g keeps its row.  A present g >= gt_rows has no row: totals[PCR_IDENT_T_DROPPED_GT] += 1 instead.
+ *   cooc     for every tracked g < gt_rows with i = det_id[d] of its lowest true positive: i < id_cap: cooc[g][i] += 1;
+ *            otherwise totals[PCR_IDENT_T_DROPPED_ID] += 1.  One writer per g: the writes do not race.
+ *   totals   FRAMES += 1; GT_TOTAL += the valid ground-truth boxes; PRED_TOTAL += the valid detections with det_id >= 0
+ *            (a propagated track without a detection is no prediction here); TP += the true positives;
+ *   dist_sum for the true positives in ascending d: dist_sum = dist_sum + (double)cost[d*G + det_gt[d]], a running binary64
+ *            sum that starts at the stored value (cost is pcr_truth_cost_f32's: the centre distance, or -iou).
+ * The D-sized pointers may be NULL when D == 0, the G-sized ones when G == 0, cost when D * G == 0.
+ *
+ * pcr_ident_compact_f32: the scene's problem, gathered.  Row g of cooc is ACTIVE iff it holds a non-zero count, column i
+ * likewise.  flags (gt_rows + id_cap) int32 is workspace (row then column activity, every element written).
+ *   counts (PCR_IDENT_COUNTS)  N_ROWS / N_COLS = the number of active rows / columns, whatever max_rows / max_cols are;
+ *            MAX_COUNT = the largest count of cooc (0 for an all-zero matrix); the last is written 0.
+ *   row_list (max_rows), col_list (max_cols)  the active rows / columns ascending, as many as fit; -1 beyond.
+ *   cost (max_rows, max_cols)  -(float)cooc[row_list[r]][col_list[c]] for r < N_ROWS and c < N_COLS, +0.0f in the padding;
+ *            all +0.0f when N_ROWS > max_rows or N_COLS > max_cols (OVERFLOW).  Zeros do not change the optimum total: every
+ *            count is >= 0.
+ * Launches: a clear, a sweep of the whole matrix (a row's activity by ballot, a column's by the thread that owns it over the
+ * rows of its workgroup, the maximum by an integer atomic), the ranks by one workgroup (ballot, lanes below, a prefix over
+ * its waves, a running base from chunk to chunk), the gather.
+ *
+ * pcr_ident_score_i32: one launch (one workgroup) after pcr_lsa_f32 over cost -> col4row (max_rows), info (1).
+ *   OVERFLOW iff N_ROWS > max_rows or N_COLS > max_cols; INEXACT iff info[0] != 0 or
+ *            (min(max_rows, max_cols) + 1) * MAX_COUNT >= 2^24 in 64-bit arithmetic: below that every solver operation is
+ *            exact in binary32 (all values are integers of magnitude < 2^24) and the total is the true optimum, whatever
+ *            the ties.
+ *   IDTP_scene = sum over r < N_ROWS with c = col4row[r] in [0, N_COLS) of cooc[row_list[r]][col_list[c]]; 0 on OVERFLOW or
+ *            info[0] != 0.
+ *   id_map (gt_rows)  id_map[row_list[r]] = col_list[c] for those pairs whose count is > 0; -1 everywhere else.
+ *   table (PCR_IDENT_TABLE) 64-bit integers, ADDED to, so that scene after scene gives the pooled figures: IDTP, the
+ *            four totals of the scene; over the rows g with PRESENT > 0: TRACKS += 1; MT += 1 iff 5 * TRACKED >= 4 *
+ *            PRESENT, ML += 1 iff 5 * TRACKED < PRESENT, PT += 1 otherwise; FRAG += FRAGS; TID_SUM += (EVER ? FIRST_GAP :
+ *            PRESENT); LGD_SUM += LONGEST_GAP; OVERFLOW / INEXACT += 1 for a scene so flagged; DROPPED_GT / DROPPED_ID +=
+ *            the scene's.
+ *   dist_total (1) binary64  dist_total = dist_total + dist_sum.
+ * The scene state is not changed: zeroing it (the caller's) opens the next scene. */
+#define PCR_IDENT_MAX_DIM 65536
+#define PCR_IDENT_MAX_CELLS 67108864                         /* 2^26 */
+#define PCR_IDENT_TRACK_COLS 8
+#define PCR_IDENT_PRESENT 0
+#define PCR_IDENT_TRACKED 1
+#define PCR_IDENT_FRAGS 2
+#define PCR_IDENT_FIRST_GAP 3
+#define PCR_IDENT_LONGEST_GAP 4
+#define PCR_IDENT_CUR_GAP 5
+#define PCR_IDENT_EVER 6
+#define PCR_IDENT_LAST 7
+#define PCR_IDENT_TOTALS 8
+#define PCR_IDENT_T_FRAMES 0
+#define PCR_IDENT_T_GT_TOTAL 1
+#define PCR_IDENT_T_PRED_TOTAL 2
+#define PCR_IDENT_T_TP 3
+#define PCR_IDENT_T_DROPPED_GT 4
+#define PCR_IDENT_T_DROPPED_ID 5
+#define PCR_IDENT_COUNTS 4
+#define PCR_IDENT_N_ROWS 0
+#define PCR_IDENT_N_COLS 1
+#define PCR_IDENT_MAX_COUNT 2
+#define PCR_IDENT_TABLE 16
+#define PCR_IDENT_IDTP 0
+#define PCR_IDENT_FRAMES 1
+#define PCR_IDENT_GT_TOTAL 2
+#define PCR_IDENT_PRED_TOTAL 3
+#define PCR_IDENT_TP 4
+#define PCR_IDENT_TRACKS 5
+#define PCR_IDENT_MT 6
+#define PCR_IDENT_PT 7
+#define PCR_IDENT_ML 8
+#define PCR_IDENT_FRAG 9
+#define PCR_IDENT_TID_SUM 10
+#define PCR_IDENT_LGD_SUM 11
+#define PCR_IDENT_OVERFLOW 12
+#define PCR_IDENT_INEXACT 13
+#define PCR_IDENT_DROPPED_GT 14
+#define PCR_IDENT_DROPPED_ID 15
+typedef struct pcr_ident {
+  int D, G, gt_cap, gt_rows, id_cap;
+  const int *det_labels, *det_gt, *det_id;                   /* (D): the frame's, pcr_truth_decide_i32's, the plan's */
+  const int *gt_labels, *gt_ids;                             /* (G) */
+  const float *cost;                                         /* (D,G): pcr_truth_cost_f32's */
+  int *cooc, *gt_track, *totals;                             /* the scene: (gt_rows,id_cap), (gt_rows,8), (PCR_IDENT_TOTALS) */
+  double *dist_sum;                                          /* (1) */
+} pcr_ident;
+typedef struct pcr_ident_close {
+  int gt_rows, id_cap, max_rows, max_cols;
+  const int *cooc, *gt_track, *totals;                       /* the scene */
+  const double *dist_sum;
+  int *flags, *counts, *row_list, *col_list;                 /* compact: (gt_rows + id_cap), (PCR_IDENT_COUNTS), (max_rows), (max_cols) */
+  float *cost;                                               /* (max_rows,max_cols) */
+  const int *col4row, *info;                                 /* score: pcr_lsa_f32's over cost, (max_rows), (1) */
+  int *id_map;                                               /* (gt_rows) */
+  long long *table;                                          /* (PCR_IDENT_TABLE) */
+  double *dist_total;                                        /* (1) */
+} pcr_ident_close;
+int pcr_ident_ok(int D, int G, int gt_cap, int gt_rows, int id_cap, int max_rows, int max_cols);
+int pcr_ident_record_i32(const pcr_ident *p, pcr_stream_t stream);
+int pcr_ident_compact_f32(const pcr_ident_close *p, pcr_stream_t stream);
+int pcr_ident_score_i32(const pcr_ident_close *p, pcr_stream_t stream);
+
 /* ------------------------------------------------- B. fused model kernels ------------ */
 
 /* Neighbour search of the "Point-Transformer" set-abstraction layers: centres are the first S

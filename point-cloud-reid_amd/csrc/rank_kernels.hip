@@ -37,12 +37,6 @@ __device__ __forceinline__ unsigned long long rank_key(float s, int g) {
   return ((unsigned long long)pcr_orderable(z) << 32) | (0xFFFFFFFFu - (uint32_t)g);
 }
 
-// a wave-uniform 64-bit word out of lane `l` (wave-uniform)
-__device__ __forceinline__ unsigned long long rank_lane_u64(unsigned long long v, int l) {
-  const uint32_t lo = wave_readlane((uint32_t)v, l), hi = wave_readlane((uint32_t)(v >> 32), l);
-  return ((unsigned long long)hi << 32) | lo;
-}
-
 // LDS of a query: row [G] f32, a non-candidate holds -inf | hit [G] i32: the true candidates' ranks, ascending
 __global__ __launch_bounds__(kWave) void rank_gallery_kernel(pcr_rank p) {
   extern __shared__ float rank_lds[];
@@ -101,7 +95,7 @@ __global__ __launch_bounds__(kWave) void rank_gallery_kernel(pcr_rank p) {
 
   // ---- 3. the true candidates: rank, and place among the true ones, by ballot popcounts over the row --------------------
   for (int c = 0; c < chunks; ++c) {
-    unsigned long long todo = rank_lane_u64(true_word, c);
+    unsigned long long todo = wave_readlane_u64(true_word, c);
     for (int n = __popcll(todo); n > 0; --n) {
       const int g = c * kWave + __ffsll((long long)todo) - 1;
       todo &= todo - 1ull;
@@ -112,7 +106,7 @@ __global__ __launch_bounds__(kWave) void rank_gallery_kernel(pcr_rank p) {
         const float sj = j < G ? row[j] : kNegInf;           // (-inf beats nothing and equals no candidate's score)
         const unsigned long long beats = __ballot(sj > sg || (sj == sg && j < g));
         rank += __popcll(beats);
-        place += __popcll(beats & rank_lane_u64(true_word, c2));
+        place += __popcll(beats & wave_readlane_u64(true_word, c2));
       }
       if (lane == 0) hit[place] = rank;                      // the places are a permutation of [0, n_true)
     }
@@ -126,7 +120,7 @@ __global__ __launch_bounds__(kWave) void rank_gallery_kernel(pcr_rank p) {
     double quot = 0.0;
     if (i < n_true) quot = (double)(i + 1) / (double)(hit[i] + 1);
     const int m = n_true - base < kWave ? n_true - base : kWave;
-    for (int l = 0; l < m; ++l) sum = sum + __longlong_as_double((long long)rank_lane_u64((unsigned long long)__double_as_longlong(quot), l));
+    for (int l = 0; l < m; ++l) sum = sum + wave_readlane_f64(quot, l);
   }
   if (lane == 0) {
     p.n_cand[q] = n_cand;
@@ -167,8 +161,8 @@ __global__ __launch_bounds__(kWave) void rank_accumulate_kernel(pcr_rank_acc p) 
     for (int k = __popcll(todo); k > 0; --k) {               // the scored queries, ascending
       const int l = __ffsll((long long)todo) - 1;
       todo &= todo - 1ull;
-      sum_ap = sum_ap + __longlong_as_double((long long)rank_lane_u64((unsigned long long)__double_as_longlong(ap), l));
-      sum_rr = sum_rr + __longlong_as_double((long long)rank_lane_u64((unsigned long long)__double_as_longlong(rr), l));
+      sum_ap = sum_ap + wave_readlane_f64(ap, l);
+      sum_rr = sum_rr + wave_readlane_f64(rr, l);
     }
   }
   if (lane == 0) {

@@ -53,12 +53,6 @@ __device__ __forceinline__ bool slot_matched(const pcr_truth &p, int s) {
   return p.det_labels[d] >= 0 && p.det_to_track[d] == s;
 }
 
-// counters[k] += the number of lanes with flag; every lane of the wave calls it
-__device__ __forceinline__ void count(int *counters, int k, bool flag, int lane) {
-  const unsigned long long bal = __ballot(flag);
-  if (lane == 0 && bal != 0ull) atomicAdd(&counters[k], __popcll(bal));
-}
-
 // the lowest index i < n with table[i] == key, by one wave (every lane calls it with the same key and n), or -1
 __device__ __forceinline__ int first_equal(const int *__restrict__ table, int n, int key, int lane) {
   for (int base = 0; base < n; base += kWave) {
@@ -130,15 +124,15 @@ __global__ __launch_bounds__(kTruthThreads) void truth_decide_kernel(pcr_truth p
     }
     if (in) p.true_t2d[s] = t2d, p.track_truth[s] = truth;
     const bool missed = active && !killed && !matched;
-    count(counters, kDmatchGt, truth == 0, lane);
-    count(counters, kDmatchPred, matched, lane);
-    count(counters, kDmatchBoth, matched && truth == 0 && (p.forced || p.track_to_det[s] == t2d), lane);
-    count(counters, kFnGt, truth == 1, lane);
-    count(counters, kFnPred, missed, lane);
-    count(counters, kFnBoth, missed && truth == 1, lane);
-    count(counters, kTfpGt, truth == 2, lane);
-    count(counters, kTfpPred, killed, lane);
-    count(counters, kTfpBoth, killed && truth == 2, lane);
+    wave_count(counters, kDmatchGt, truth == 0, lane);
+    wave_count(counters, kDmatchPred, matched, lane);
+    wave_count(counters, kDmatchBoth, matched && truth == 0 && (p.forced || p.track_to_det[s] == t2d), lane);
+    wave_count(counters, kFnGt, truth == 1, lane);
+    wave_count(counters, kFnPred, missed, lane);
+    wave_count(counters, kFnBoth, missed && truth == 1, lane);
+    wave_count(counters, kTfpGt, truth == 2, lane);
+    wave_count(counters, kTfpPred, killed, lane);
+    wave_count(counters, kTfpBoth, killed && truth == 2, lane);
   }
   for (int base = 0; base < D; base += kTruthThreads) {
     const int d = base + tid;
@@ -159,12 +153,12 @@ __global__ __launch_bounds__(kTruthThreads) void truth_decide_kernel(pcr_truth p
       }
     }
     if (d < D) p.true_d2t[d] = d2t, p.det_truth[d] = truth;
-    count(counters, kBornGt, truth == 1, lane);
-    count(counters, kBornPred, born, lane);
-    count(counters, kBornBoth, born && truth == 1, lane);
-    count(counters, kDfpGt, truth == 2, lane);
-    count(counters, kDfpPred, rejected, lane);
-    count(counters, kDfpBoth, rejected && truth == 2, lane);
+    wave_count(counters, kBornGt, truth == 1, lane);
+    wave_count(counters, kBornPred, born, lane);
+    wave_count(counters, kBornBoth, born && truth == 1, lane);
+    wave_count(counters, kDfpGt, truth == 2, lane);
+    wave_count(counters, kDfpPred, rejected, lane);
+    wave_count(counters, kDfpBoth, rejected && truth == 2, lane);
   }
   __syncthreads();
 
@@ -214,8 +208,8 @@ __global__ __launch_bounds__(kTruthThreads) void truth_record_kernel(pcr_truth p
       const int s = p.det_slot[d];
       if (s >= 0 && s < C) atomicMin(&slot_det[s], d);
     }
-    count(counters, kTp, g >= 0, lane);
-    count(counters, kFp, valid && g < 0, lane);
+    wave_count(counters, kTp, g >= 0, lane);
+    wave_count(counters, kFp, valid && g < 0, lane);
   }
   __syncthreads();
 
@@ -237,8 +231,8 @@ __global__ __launch_bounds__(kTruthThreads) void truth_record_kernel(pcr_truth p
   for (int base = 0; base < G; base += kTruthThreads) {
     const int j = base + tid;
     const bool valid = j < G && gt_valid(p, j);
-    count(counters, kGtTotal, valid, lane);
-    count(counters, kFn, valid && gt_hit[j] == 0, lane);
+    wave_count(counters, kGtTotal, valid, lane);
+    wave_count(counters, kFn, valid && gt_hit[j] == 0, lane);
   }
   for (int d = wave; d < D; d += kTruthWaves) {             // a wave per detection: is a lower true positive of its track?
     const int g = det_track[d];                             // uniform over the wave

@@ -149,6 +149,21 @@ __device__ __forceinline__ uint32_t pcr_lanes_below(unsigned long long mask) {
   return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
 }
 
+// counters[k] += the number of lanes with flag (counters: an LDS table of integer sums); every lane of the wave calls it
+__device__ __forceinline__ void wave_count(int *counters, int k, bool flag, int lane) {
+  const unsigned long long bal = __ballot(flag);
+  if (lane == 0 && bal != 0ull) atomicAdd(&counters[k], __popcll(bal));
+}
+
+// a wave-uniform 64-bit word / binary64 out of lane `l` (wave-uniform): two v_readlane
+__device__ __forceinline__ unsigned long long wave_readlane_u64(unsigned long long v, int l) {
+  const uint32_t lo = wave_readlane((uint32_t)v, l), hi = wave_readlane((uint32_t)(v >> 32), l);
+  return ((unsigned long long)hi << 32) | lo;
+}
+__device__ __forceinline__ double wave_readlane_f64(double v, int l) {
+  return __longlong_as_double((long long)wave_readlane_u64((unsigned long long)__double_as_longlong(v), l));
+}
+
 __device__ __forceinline__ unsigned long long pcr_wave_max_u64(unsigned long long k) {
 #pragma unroll
   for (int m = 32; m >= 1; m >>= 1) {

@@ -762,7 +762,9 @@ class ReIDNet(nn.Module):
         association drives bank.update in place of the tracker's own, det_truth == 1 as born and track_truth == 2 as
         kill (the reference's teacher forcing in mode 'gt': the upper bound a matching head is compared against), and
         the book's decision counters score those applied decisions; the returned track_to_det / det_to_track stay the
-        tracker's own.  Without truth= nothing new is launched.
+        tracker's own.  Without truth= nothing new is launched.  truth["identity"] = a pcr_amd.identity.IdentityBook made over
+        truth["book"] keeps the identity metrics (INTEGRATION.md "2i. Identity metrics"): its record runs right after
+        book.record, one launch; nothing else in the frame changes, and without the key nothing new is launched.
 
         decisions= (as in associate; det_values may be (dd, M) and is zero-padded to max_dets) runs the frame with any set of
         decisions: the matrix is association_cost_multi's (the margin kind takes dist, the softmax kind does not), the
@@ -784,6 +786,12 @@ class ReIDNet(nn.Module):
             book = truth.get("book") if isinstance(truth, dict) else None
             if not isinstance(book, TU.TruthBook) or book.bank is not bank:
                 raise L.PcrError("track_step: truth['book'] must be a pcr_amd.truth.TruthBook made over this bank")
+            identity = truth.get("identity")
+            if identity is not None:
+                from pcr_amd import identity as ID
+                if not isinstance(identity, ID.IdentityBook) or identity.book is not book:
+                    raise L.PcrError("track_step: truth['identity'] must be a pcr_amd.identity.IdentityBook made over "
+                                     "truth['book']")
         if not isinstance(bank, TR.TrackBank):
             raise L.PcrError("track_step: bank must be a pcr_amd.tracks.TrackBank")
         if decisions is not None and (born is not None or kill is not None):
@@ -853,6 +861,8 @@ class ReIDNet(nn.Module):
             bank.suppress(suppress_threshold)
         if truth is not None:
             book.record(det_slot, det_id)
+            if identity is not None:
+                identity.record(det_id)
         return dict(track_to_det=t2d, det_to_track=d2t, pairs=pairs, count=count, logits=logits, cost=cost, info=info,
                     det_slot=det_slot, det_id=det_id, bank_info=bank_info, dist=dist, lengths=lengths, **decoded, **truth_out)
 

@@ -49,6 +49,13 @@ RankParams = _block("RankParams", """
 RankAccParams = _block("RankAccParams", """
     int Q G nranks; int[8] ranks; ptr n_true first_hit info ap valid counts sums""")
 
+# ---- section A9 (pcr_ident, pcr_ident_close) ----
+IdentParams = _block("IdentParams", """
+    int D G gt_cap gt_rows id_cap; ptr det_labels det_gt det_id gt_labels gt_ids cost cooc gt_track totals dist_sum""")
+IdentCloseParams = _block("IdentCloseParams", """
+    int gt_rows id_cap max_rows max_cols; ptr cooc gt_track totals dist_sum flags counts row_list col_list cost;
+    ptr col4row info id_map table dist_total""")
+
 # ---- section A6 (pcr_store_tables) ----
 StoreTables = _block("StoreTables", """
     int num_objects num_classes; ptr obj_cls obj_fp obj_id nums_off nums_rows bucket_off bucket_rows pool_off pool_objs""")
@@ -93,6 +100,7 @@ _AttnHeadP = _block("_AttnHeadP", """
 # the header's name of every block (what the layout test compiles against)
 BLOCKS = {"pcr_assoc_multi": AssocMultiParams, "pcr_assoc_decode": AssocDecodeParams, "pcr_bank": BankParams,"pcr_truth": TruthParams, "pcr_store_tables": StoreTables, "pcr_sa_params": SaParams, "pcr_attn_params": AttnParams, "pcr_head_params": HeadParams,
           "pcr_live": LiveParams, "pcr_rank": RankParams, "pcr_rank_acc": RankAccParams,
+          "pcr_ident": IdentParams, "pcr_ident_close": IdentCloseParams,
           "pcr_tdense_fwd": _TFwd, "pcr_tdense_bwd": _TBwd, "pcr_bn_fwd_fin": _BnFwd, "pcr_bn_bwd_fin": _BnBwd,
           "pcr_reduce_job": _ReduceJob, "pcr_linattn": _LinAttnP, "pcr_attn_tail": _AttnTailP,
           "pcr_attn_head": _AttnHeadP}
@@ -212,6 +220,11 @@ SIGNATURES = {
     "pcr_rank_scores_f32": "s FIIFiiiS",
     "pcr_rank_gallery_f32": "s <RankParams>S",
     "pcr_rank_accumulate": "s <RankAccParams>S",
+    # A9. identity preservation
+    "pcr_ident_ok": "i iiiiiii",
+    "pcr_ident_record_i32": "s <IdentParams>S",
+    "pcr_ident_compact_f32": "s <IdentCloseParams>S",
+    "pcr_ident_score_i32": "s <IdentCloseParams>S",
     # B. fused model kernels
     "pcr_knn_prefix_f32": "s FIiiiiS",
     "pcr_knn_prefix2_f32": "s FIIiiiiiiS",

@@ -25,6 +25,7 @@ FLAGS = {
     "track_kernels.hip": ["-ffp-contract=off"],      # the propagated boxes and the distances are compared bit for bit
     "truth_kernels.hip": ["-ffp-contract=off"],      # the ground-truth matching cost is compared bit for bit
     "rank_kernels.hip": ["-ffp-contract=off"],       # the binary64 average-precision sums are compared bit for bit
+    "ident_kernels.hip": ["-ffp-contract=off"],      # the binary64 match-distance sums are compared bit for bit
 }
 
 

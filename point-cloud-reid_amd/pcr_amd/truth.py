@@ -171,7 +171,7 @@ class TruthBook:
         self._born, self._kill = i32(D), i32(C)
         if kind == "iou":
             self._det7, self._gt7, self._det_bev, self._gt_bev, self._iou = f32(D, 7), f32(G, 7), f32(D, 5), f32(G, 5), f32(D, G)
-        self._det_labels = None
+        self._det_labels = self._det_id = None
         self.reset()
 
     def reset(self):
@@ -179,6 +179,7 @@ class TruthBook:
         for t in (self.slot_gt, self.slot_tte, self.gt_last):
             t.fill_(-1)
         self.stats.zero_()
+        self._det_id = None                                 # (an IdentityBook's record follows a record of THIS book's life)
 
     def _load(self, gt):
         """the frame's ground truth into the book's buffers, padded to max_gt with label -1"""
@@ -260,6 +261,7 @@ class TruthBook:
         t = self._tensors(self._det_labels)
         t.update(det_slot=det_slot, det_id=det_id)
         record(t, self.gt_cap)
+        self._det_id = det_id                               # (what an IdentityBook over this book records next)
 
     def metrics(self):
         """THE host read: see `metrics_of`"""

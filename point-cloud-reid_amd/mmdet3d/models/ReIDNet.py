@@ -604,13 +604,11 @@ class ReIDNet(nn.Module):
                                  (trk_names, decisions.get("track_values"), T, "track_values")):
             if v is None:
                 v = torch.zeros((len(names), n), dtype=torch.float32, device=dev)
-            L.require_cuda(v)
-            L.require_f32(v)
+            v = L.tensor(v, who, "decisions[%r]" % key, torch.float32, copy=True)
             if key == "det_values" and M is not None and v.dim() == 2 and v.shape[1] == M and M < n:
                 v = torch.cat([v, v.new_zeros((v.shape[0], n - M))], dim=1)
-            if v.shape != (len(names), n):
-                raise L.PcrError("%s: decisions[%r] must be (%d, %d), got %s" % (who, key, len(names), n, tuple(v.shape)))
-            values.append(v.contiguous())
+            values.append(L.tensor(v, who, "decisions[%r]" % key, torch.float32, shape=(len(names), n)))
+        L.require_cuda(*values)
         return dict(det_names=det_names, trk_names=trk_names, det_values=values[0], trk_values=values[1],
                     kind=decisions.get("kind", "margin"), reduce=bool(decisions.get("reduce", False)),
                     born=det_names.index("det_newborn") if "det_newborn" in det_names else -1,
@@ -629,6 +627,19 @@ class ReIDNet(nn.Module):
                                                        reduce=reduce)
         col4row, row4col, block_info = A.linear_assignment_blocks(cost, row_block, col_block, G)
         return (col4row, row4col, block_info.amax(dim=0, keepdim=True)), block_info
+
+    @staticmethod
+    def _assign_one(cost, T, D, by_class):
+        """_assign over association_cost's one-decision matrix, the columns >= D and the rows >= T (the miss / new diagonals)
+        read as -1 -> track_to_det (T,), det_to_track (D,), info (1,), block_info or None"""
+        (col4row, row4col, info), block_info = ReIDNet._assign(cost, T, D, 1, 1, False, by_class)
+        c, r = col4row[:T], row4col[:D]
+        return torch.where(c < D, c, torch.full_like(c, -1)), torch.where(r < T, r, torch.full_like(r, -1)), info, block_info
+
+    def _match_across(self, feats, xyz, pairs, offset, count):
+        """match_gallery over a gallery [a | b] of `offset` rows of a followed by b's, for pairs (row of a, row of b)"""
+        gallery_pairs = torch.stack([pairs[:, 0], pairs[:, 1] + offset], dim=1)
+        return self.match_gallery(feats, xyz, gallery_pairs, count=count).contiguous()
 
     @staticmethod
     def _associate_decisions(logits, pairs, count, T, D, ds, dist, cost_args, by_class=None):
@@ -685,9 +696,8 @@ class ReIDNet(nn.Module):
             if T == 0 or D == 0:
                 pairs, logits = pairs[:0], torch.empty((0,), dtype=torch.float32, device=dev)
             else:
-                gallery_pairs = torch.stack([pairs[:, 0], pairs[:, 1] + T], dim=1)
-                logits = self.match_gallery(torch.cat([track_feats, det_feats], dim=0), torch.cat([track_xyz, det_xyz], dim=0),
-                                            gallery_pairs, count=count if live_only else None).contiguous()
+                logits = self._match_across(torch.cat([track_feats, det_feats], dim=0), torch.cat([track_xyz, det_xyz], dim=0),
+                                            pairs, T, count if live_only else None)
             dist = cost_args.pop("dist", None)
             return dict(pairs=pairs, count=count, logits=logits,
                         **self._associate_decisions(logits, pairs, count, T, D, ds, dist, cost_args, by_class=blocks))
@@ -697,15 +707,12 @@ class ReIDNet(nn.Module):
                         det_to_track=torch.full((D,), -1, dtype=torch.int32, device=dev), pairs=pairs, count=count,
                         logits=torch.empty((pairs.shape[0],), dtype=torch.float32, device=dev), cost=None,
                         info=torch.zeros((1,), dtype=torch.int32, device=dev), **empty)
-        gallery_pairs = torch.stack([pairs[:, 0], pairs[:, 1] + T], dim=1)       # detections follow the tracks
-        logits = self.match_gallery(torch.cat([track_feats, det_feats], dim=0), torch.cat([track_xyz, det_xyz], dim=0),
-                                    gallery_pairs, count=count if live_only else None).contiguous()
+        logits = self._match_across(torch.cat([track_feats, det_feats], dim=0), torch.cat([track_xyz, det_xyz], dim=0),
+                                    pairs, T, count if live_only else None)                # detections follow the tracks
         cost = A.association_cost(logits, pairs, count, T, D, **cost_args)
-        (col4row, row4col, info), block_info = self._assign(cost, T, D, 1, 1, False, blocks)
-        c, r = col4row[:T], row4col[:D]
-        return dict(track_to_det=torch.where(c < D, c, torch.full_like(c, -1)),
-                    det_to_track=torch.where(r < T, r, torch.full_like(r, -1)), pairs=pairs, count=count, logits=logits,
-                    cost=cost, info=info, **({} if block_info is None else {"block_info": block_info}))
+        t2d, d2t, info, block_info = self._assign_one(cost, T, D, blocks)
+        return dict(track_to_det=t2d, det_to_track=d2t, pairs=pairs, count=count, logits=logits, cost=cost, info=info,
+                    **({} if block_info is None else {"block_info": block_info}))
 
     def retrieve(self, q_feats, q_xyz, q_labels, q_lengths, g_feats, g_xyz, g_labels, g_lengths, query_ids=None,
                  gallery_ids=None, topk=10, exclude=None, min_points=2, num_classes=8, live_only=False):
@@ -730,9 +737,8 @@ class ReIDNet(nn.Module):
         if Q == 0 or G == 0:
             logits = torch.empty((pairs.shape[0],), dtype=torch.float32, device=q_feats.device)
         else:
-            gallery_pairs = torch.stack([pairs[:, 0], pairs[:, 1] + Q], dim=1)       # the gallery follows the queries
-            logits = self.match_gallery(torch.cat([q_feats, g_feats], dim=0), torch.cat([q_xyz, g_xyz], dim=0),
-                                        gallery_pairs, count=count if live_only else None).contiguous()
+            logits = self._match_across(torch.cat([q_feats, g_feats], dim=0), torch.cat([q_xyz, g_xyz], dim=0),
+                                        pairs, Q, count if live_only else None)            # the gallery follows the queries
         scores = R.score_matrix(logits, pairs, count, Q, G)
         out = R.rank_gallery(scores, query_ids, gallery_ids, topk=topk, exclude=exclude)
         return dict(pairs=pairs, count=count, logits=logits, scores=scores, **out)
@@ -797,14 +803,13 @@ class ReIDNet(nn.Module):
         if decisions is not None and (born is not None or kill is not None):
             raise L.PcrError("track_step: with decisions= the born / kill masks come from the decoded decisions; pass one or "
                              "the other")
-        L.require_cuda(sweep, boxes, labels, scores)
-        L.require_f32(boxes, scores)
         C, D, W = bank.capacity, bank.max_dets, bank.box_width
-        if boxes.dim() != 2 or boxes.shape[1] != W or boxes.shape[0] > D:
-            raise L.PcrError("track_step: boxes must be (M <= %d, %d), got %s" % (D, W, tuple(boxes.shape)))
+        boxes = L.tensor(boxes, "track_step", "boxes", torch.float32, shape=(None, W), copy=True)
         M = boxes.shape[0]
-        if labels.shape != (M,) or scores.shape != (M,):
-            raise L.PcrError("track_step: labels and scores must be (M,)")
+        L.require(M <= D, "track_step", "boxes must be (M <= %d, %d), got %s", D, W, tuple(boxes.shape))
+        scores = L.tensor(scores, "track_step", "scores", torch.float32, shape=(M,), copy=True)
+        L.require(isinstance(labels, torch.Tensor) and labels.shape == (M,), "track_step", "labels must be (M,)")
+        L.require_cuda(sweep, boxes, labels, scores)
         ds = None if decisions is None else self._decision_set(decisions, C, D, cost_args, "track_step", M=M)
         if ds is None and not L.load().pcr_lsa_ok(1, C + D, C + D):
             raise L.PcrError("track_step: capacity + max_dets = %d is beyond linear_assignment (PCR_LSA_MAX)" % (C + D))
@@ -830,9 +835,8 @@ class ReIDNet(nn.Module):
         dist = bank.distances(boxes, carry_inv)
         pairs, count = A.compare_pairs(bank.labels, labels, bank.lengths, lengths, min_points=min_points,
                                        num_classes=num_classes, cap=cap)
-        gallery_pairs = torch.stack([pairs[:, 0], pairs[:, 1] + C], dim=1)       # detections follow the bank's rows
-        logits = self.match_gallery(bank.gallery, bank.gallery_xyz, gallery_pairs,
-                                    count=count if live_only else None).contiguous()
+        logits = self._match_across(bank.gallery, bank.gallery_xyz, pairs, C,
+                                    count if live_only else None)                          # detections follow the bank's rows
         blocks = (bank.labels, labels, num_classes) if by_class else None
         decoded = {}
         if ds is not None:
@@ -842,12 +846,9 @@ class ReIDNet(nn.Module):
             born, kill = decoded["born"], decoded["kill"]
         else:
             cost = A.association_cost(logits, pairs, count, C, D, dist=dist, **cost_args)
-            (col4row, row4col, info), block_info = self._assign(cost, C, D, 1, 1, False, blocks)
+            t2d, d2t, info, block_info = self._assign_one(cost, C, D, blocks)
             if block_info is not None:
                 decoded["block_info"] = block_info
-            c, r = col4row[:C], row4col[:D]
-            t2d = torch.where(c < D, c, torch.full_like(c, -1))
-            d2t = torch.where(r < C, r, torch.full_like(r, -1))
         decisions, truth_out = (t2d, d2t), {}
         if truth is not None:
             book.match(boxes, labels, truth)

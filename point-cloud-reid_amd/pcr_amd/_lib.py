@@ -102,15 +102,18 @@ def check(status, what):
 def require_cuda(*tensors):
     """device tensors only (no CPU fallback), all on the CURRENT device: the launch goes to the current device's
     stream (mmdet3d.ops switches to the tensor's device first, as the reference's KNN wrapper does)"""
+    current = None
     for t in tensors:
         if t is None:
             continue
         if not t.is_cuda:
             raise PcrError("pcr_amd ops run only on an MI355X device tensor (got %s); there is no CPU "
                            "fallback in the product path" % t.device)
-        if t.device.index != torch.cuda.current_device():
+        if current is None:                              # (asked once per call: a block's fill passes two dozen tensors)
+            current = torch.cuda.current_device()
+        if t.device.index != current:
             raise PcrError("tensor on %s but the current device is cuda:%d: call torch.cuda.set_device / "
-                           "torch.cuda.device(...) first" % (t.device, torch.cuda.current_device()))
+                           "torch.cuda.device(...) first" % (t.device, current))
 
 
 def require_f32(*tensors):
@@ -126,23 +129,52 @@ def require_i32(*tensors):
             raise PcrError("expected an int32 index tensor, got %s" % t.dtype)
 
 
-def as_vec(t, dtype, n, name, who="pcr_amd"):
-    """a contiguous (n,) device tensor of dtype torch.int32 / torch.float32 (int64 labels, lengths and masks are converted
-    on the device), or None; `who` prefixes the error"""
-    if t is None:
+def refuse(who, what):
+    """every refused call is a PcrError that names the entry and the argument (an assert would vanish under python -O)"""
+    raise PcrError("%s: %s" % (who, what))
+
+
+def require(ok, who, what, *args):
+    """`what % args`, put together only when the call is refused"""
+    if not ok:
+        refuse(who, what % args if args else what)
+
+
+def tensor(t, who, name, dtype, shape=None, numel=None, optional=False, cast_int64=False, copy=False):
+    """The argument `name` of `who` as a kernel reads it: a contiguous tensor of `dtype` and of `shape` (None = a dimension
+    of any size) or of `numel` elements; returns it.  optional: None passes.  cast_int64: int64 labels, lengths and masks
+    are converted to int32 (on the tensor's device).  copy: a strided tensor is made contiguous instead of refused.  What
+    is wrong with the argument comes before where it lives: the device is not looked at, `require_cuda` over all the
+    arguments follows the last of these."""
+    if t is None and optional:
         return None
     if not isinstance(t, torch.Tensor):
-        raise PcrError("%s: %s must be a tensor" % (who, name))
-    require_cuda(t)
-    if dtype is torch.int32:
-        if t.dtype == torch.int64:
-            t = t.to(torch.int32)
-        require_i32(t)
-    else:
-        require_f32(t)
-    if t.shape != (n,):
-        raise PcrError("%s: %s must be (%d,), got %s" % (who, name, n, tuple(t.shape)))
-    return t.contiguous()
+        refuse(who, "%s must be a tensor" % name)
+    if cast_int64 and t.dtype == torch.int64:
+        t = t.to(torch.int32)
+    if t.dtype != dtype:
+        refuse(who, "%s must be a %s tensor, got %s" % (name, dtype, t.dtype))
+    if shape is not None and t.shape != shape:           # (equal: done; otherwise a None may still let it pass)
+        ok = t.dim() == len(shape)
+        for want, got in zip(shape, t.shape) if ok else ():
+            ok = ok and (want is None or want == got)
+        if not ok:
+            refuse(who, "%s must be (%s), got %s" % (name, ", ".join("*" if n is None else str(n) for n in shape) +
+                                                   ("," if len(shape) == 1 else ""), tuple(t.shape)))
+    if numel is not None and t.numel() != numel:
+        refuse(who, "%s must hold %d elements, got %s" % (name, numel, tuple(t.shape)))
+    if not t.is_contiguous():
+        if not copy:
+            refuse(who, "%s must be contiguous" % name)
+        t = t.contiguous()
+    return t
+
+
+def out_tensor(out, who, name, dtype, shape, device):
+    """the out= pattern: the caller's buffer held to `tensor`'s checks, or a new uninitialised tensor on `device`"""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    return tensor(out, who, name, dtype, shape=shape)
 
 
 def require_default_eps(*norms):

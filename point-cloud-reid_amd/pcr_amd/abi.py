@@ -7,94 +7,131 @@ import ctypes
 import numpy as np
 import torch
 
-_CTYPES = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "long": ctypes.c_long,
-           "ptr": ctypes.c_void_p}
+_CTYPES = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "long": ctypes.c_long}
+_POINTERS = {"iptr": torch.int32, "fptr": torch.float32, "dptr": torch.float64, "lptr": torch.int64, "ptr": None}
 
 
 def _block(name, decl):
     """ctypes mirror of a pcr.h parameter block.  `decl` follows the header's struct body, one `type field field ...`
-    group per `;` (ptr = any data pointer: the launches fill them with addresses, `_lib._p`; ptr[n] = an array of n)."""
-    fields = []
+    group per `;`.  A data pointer is named by what it points at: iptr = int *, fptr = float *, dptr = double *, lptr =
+    long long *, ptr = void *; kind[n] = an array of n.  Every pointer is a c_void_p in the layout (the launches fill them
+    with addresses: `fill`, `_lib._p`); the class keeps the element types as ELEM = {pointer field: torch dtype or None}."""
+    fields, elem = [], {}
     for group in decl.split(";"):
         ty, *names = group.split()
         base, _, n = ty.partition("[")
-        ct = _CTYPES[base] * int(n[:-1]) if n else _CTYPES[base]
-        fields += [(f, ct) for f in names]
-    return type(name, (ctypes.Structure,), {"_fields_": fields})
+        if base in _POINTERS:
+            elem.update(dict.fromkeys(names, _POINTERS[base]))
+        ct = ctypes.c_void_p if base in _POINTERS else _CTYPES[base]
+        fields += [(f, ct * int(n[:-1]) if n else ct) for f in names]
+    return type(name, (ctypes.Structure,), {"_fields_": fields, "ELEM": elem})
+
+
+def fill(p, tensors, sizes, required=(), who="pcr_amd"):
+    """Checks the dict `tensors` over the pointer fields of the block `p` against the block's element types and the element
+    counts `sizes`, writes the addresses into `p` (None and an empty tensor: NULL) and returns it.  What is wrong with the
+    call itself comes before where a tensor lives, so every refusal but the last can be met without a device; a field not
+    named in `required` may be None (the library's own NULL checks stay the authority).  Nothing here reads the device,
+    allocates or converts: it is legal inside a graph capture."""
+    from . import _lib as L
+    elem = type(p).ELEM
+    for k in tensors:
+        if k not in elem:
+            L.refuse(who, "unknown tensor %r" % (k,))
+    for k, x in tensors.items():
+        if x is not None and not isinstance(x, torch.Tensor):
+            L.refuse(who, "%s must be a tensor" % k)
+    for k in required:
+        if tensors.get(k) is None and sizes[k] != 0:
+            L.refuse(who, "%s is missing" % k)
+    for k, x in tensors.items():
+        if x is not None and elem[k] is not None and x.dtype != elem[k]:
+            L.refuse(who, "%s must be a %s tensor, got %s" % (k, elem[k], x.dtype))
+    for k, x in tensors.items():
+        if x is not None and (x.numel() != sizes[k] or not x.is_contiguous()):
+            L.refuse(who, "%s must be contiguous and hold %d elements, got %s" % (k, sizes[k], tuple(x.shape)))
+    L.require_cuda(*tensors.values())
+    for k, x in tensors.items():
+        setattr(p, k, x.data_ptr() if x is not None and x.numel() else None)
+    return p
 
 
 # ---- section A5 (pcr_bank) ----
 BankParams = _block("BankParams", """
     int C D W frame_limit replace_all reset_on_match propagate;
-    ptr lengths boxes scores labels ids steps misses next_id info;
-    ptr track_to_det det_to_track det_labels det_lengths det_boxes det_scores born kill carry; ptr src det_slot det_id""")
+    iptr lengths; fptr boxes scores; iptr labels ids steps misses next_id info;
+    iptr track_to_det det_to_track det_labels det_lengths; fptr det_boxes det_scores; iptr born kill; fptr carry;
+    iptr src det_slot det_id""")
 
 # ---- section A3 (pcr_assoc_multi, pcr_assoc_decode) ----
 AssocMultiParams = _block("AssocMultiParams", """
-    int T D dd td cap kind reduce; float dist_max dist_penalty fill; ptr logits pairs count det_dec trk_dec dist ws cost;
-    ptr det_choice trk_choice""")
+    int T D dd td cap kind reduce; float dist_max dist_penalty fill; fptr logits; iptr pairs count;
+    fptr det_dec trk_dec dist; ptr ws; fptr cost; iptr det_choice trk_choice""")
 AssocDecodeParams = _block("AssocDecodeParams", """
-    int T D dd td reduce born_dec kill_dec; float fill; ptr cost col4row row4col solver_info det_choice trk_choice;
-    ptr track_to_det det_to_track det_decision track_decision born kill info""")
+    int T D dd td reduce born_dec kill_dec; float fill; fptr cost; iptr col4row row4col solver_info det_choice trk_choice;
+    iptr track_to_det det_to_track det_decision track_decision born kill info""")
 
 # ---- section A7 (pcr_truth) ----
 TruthParams = _block("TruthParams", """
-    int C D G gt_cap skip_empty forced; ptr ids slot_gt slot_tte gt_last stats col4row row4col info cost thresh;
-    ptr gt_labels gt_ids gt_tte det_labels track_to_det det_to_track born kill;
-    ptr det_gt true_t2d true_d2t det_truth track_truth det_slot det_id""")
+    int C D G gt_cap skip_empty forced; iptr ids slot_gt slot_tte gt_last stats col4row row4col info; fptr cost thresh;
+    iptr gt_labels gt_ids gt_tte det_labels track_to_det det_to_track born kill;
+    iptr det_gt true_t2d true_d2t det_truth track_truth det_slot det_id""")
 
 # ---- section A8 (pcr_rank, pcr_rank_acc) ----
 RankParams = _block("RankParams", """
-    int Q G K; ptr scores query_ids gallery_ids exclude topk_idx topk_score n_cand n_true first_hit ap info""")
+    int Q G K; fptr scores; iptr query_ids gallery_ids exclude topk_idx; fptr topk_score; iptr n_cand n_true first_hit;
+    fptr ap; iptr info""")
 RankAccParams = _block("RankAccParams", """
-    int Q G nranks; int[8] ranks; ptr n_true first_hit info ap valid counts sums""")
+    int Q G nranks; int[8] ranks; iptr n_true first_hit info; fptr ap; iptr valid counts; dptr sums""")
 
 # ---- section A9 (pcr_ident, pcr_ident_close) ----
 IdentParams = _block("IdentParams", """
-    int D G gt_cap gt_rows id_cap; ptr det_labels det_gt det_id gt_labels gt_ids cost cooc gt_track totals dist_sum""")
+    int D G gt_cap gt_rows id_cap; iptr det_labels det_gt det_id gt_labels gt_ids; fptr cost; iptr cooc gt_track totals;
+    dptr dist_sum""")
 IdentCloseParams = _block("IdentCloseParams", """
-    int gt_rows id_cap max_rows max_cols; ptr cooc gt_track totals dist_sum flags counts row_list col_list cost;
-    ptr col4row info id_map table dist_total""")
+    int gt_rows id_cap max_rows max_cols; iptr cooc gt_track totals; dptr dist_sum; iptr flags counts row_list col_list;
+    fptr cost; iptr col4row info id_map; lptr table; dptr dist_total""")
 
 # ---- section A6 (pcr_store_tables) ----
 StoreTables = _block("StoreTables", """
-    int num_objects num_classes; ptr obj_cls obj_fp obj_id nums_off nums_rows bucket_off bucket_rows pool_off pool_objs""")
+    int num_objects num_classes;
+    iptr obj_cls obj_fp obj_id nums_off nums_rows bucket_off bucket_rows pool_off pool_objs""")
 
 # ---- section B (pcr_sa_params, pcr_attn_params, pcr_head_params) ----
 SaParams = _block("SaParams", """
-    int mode B N S K D c1 c2 c3; ptr xyz feat idx centre_idx; ptr[3] wp scale shift; ptr wa wpq; ptr[2] wps shift_pad;
-    ptr cnt tile_ws pq_ws; int pq_ready feat_point_major out_point_major; ptr out wa_packed; int precision;
-    ptr[2] wps_bf; ptr wa_shift_packed row_tab claim_ws; int pq_has_xyz""")
+    int mode B N S K D c1 c2 c3; fptr xyz feat; iptr idx centre_idx; fptr[3] wp scale shift; fptr wa wpq;
+    fptr[2] wps shift_pad; iptr cnt tile_ws; fptr pq_ws; int pq_ready feat_point_major out_point_major; fptr out wa_packed;
+    int precision; fptr[2] wps_bf; fptr wa_shift_packed row_tab; iptr claim_ws; int pq_has_xyz""")
 AttnParams = _block("AttnParams", """
-    int B Lq Sk c1 c2 d cout nhead q_pos residual; ptr feat_q xyz_q feat_k xyz_k kv_index q_index pos0_w pos0_b;
-    ptr wq bq wkv bkv wmerge wmlp0 wmlp2 ln1_g ln1_b ln2_g ln2_b wfinal bfinal; int cfinal;
-    ptr wkv_wide bkv_wide wmerge_packed kv out; int precision; ptr wq_bf wmlp0_bf wmlp2_bf wfinal_bf; int kv_splits;
-    ptr kv_part wkv_bf wmlp0_bf_xpad pool_out""")
+    int B Lq Sk c1 c2 d cout nhead q_pos residual; fptr feat_q xyz_q feat_k xyz_k; iptr kv_index q_index; fptr pos0_w pos0_b;
+    fptr wq bq wkv bkv wmerge wmlp0 wmlp2 ln1_g ln1_b ln2_g ln2_b wfinal bfinal; int cfinal;
+    fptr wkv_wide bkv_wide wmerge_packed kv out; int precision; fptr wq_bf wmlp0_bf wmlp2_bf wfinal_bf; int kv_splits;
+    fptr kv_part wkv_bf wmlp0_bf_xpad pool_out""")
 HeadParams = _block("HeadParams", """
-    int P C L groups; ptr o w1 w2 gn1_g gn1_b gn2_g gn2_b w_out b_out pooled logits w1t w2t""")
-LiveParams = _block("LiveParams", "ptr count; int period offset")      # pcr_live: the gate of the _live launches
+    int P C L groups; fptr o w1 w2 gn1_g gn1_b gn2_g gn2_b w_out b_out pooled logits w1t w2t""")
+LiveParams = _block("LiveParams", "iptr count; int period offset")     # pcr_live: the gate of the _live launches
 
 # ---- section C (pcr_tdense_fwd / _bwd, pcr_bn_fwd_fin / _bwd_fin, pcr_reduce_job, pcr_linattn, pcr_attn_tail / _head) ----
 _TFwd = _block("_TFwd", """
-    int B cin1 cin2 cout L; ptr x x2 isc ish; int in_relu; ptr wp bias res; int out_relu; ptr y stats; int pool_K;
-    ptr pool_gamma pool_ymax pool_arg""")
+    int B cin1 cin2 cout L; fptr x x2 isc ish; int in_relu; fptr wp bias res; int out_relu; fptr y stats; int pool_K;
+    fptr pool_gamma pool_ymax; iptr pool_arg""")
 _TBwd = _block("_TBwd", """
-    int B cin1 cin2 cout L; ptr g y; int dy_mode; ptr ka kb kc argmax pooled; int K S; ptr x x2 isc ish iinv; int in_relu;
-    ptr wpT dx dx2 dstats dwp dbp; long part_stride; int precision; ptr wpT_bf""")
+    int B cin1 cin2 cout L; fptr g y; int dy_mode; fptr ka kb kc; iptr argmax; fptr pooled; int K S;
+    fptr x x2 isc ish iinv; int in_relu; fptr wpT dx dx2 dstats dwp dbp; long part_stride; int precision; fptr wpT_bf""")
 _BnFwd = _block("_BnFwd", """
-    ptr part; int nparts C; double R; ptr gamma beta; float eps momentum;
-    ptr running_mean running_var scale shift inv_scale mean invstd shift0; int shift0_stride""")
+    fptr part; int nparts C; double R; fptr gamma beta; float eps momentum;
+    fptr running_mean running_var scale shift inv_scale mean invstd shift0; int shift0_stride""")
 _BnBwd = _block("_BnBwd", """
-    ptr part; int nparts C; double R; ptr gamma mean invstd ka kb kc dgamma dbeta centre""")
-_ReduceJob = _block("_ReduceJob", "ptr part out; long stride; int nparts rows cols ld")
+    fptr part; int nparts C; double R; fptr gamma mean invstd ka kb kc dgamma dbeta centre""")
+_ReduceJob = _block("_ReduceJob", "fptr part out; long stride; int nparts rows cols ld")
 _LinAttnP = _block("_LinAttnP", """
-    int B Lq Sk d H; float eps; ptr q k v; long q_bs k_bs v_bs; ptr out A ks dout dq dk dv; long dq_bs dk_bs dv_bs;
+    int B Lq Sk d H; float eps; fptr q k v; long q_bs k_bs v_bs; fptr out A ks dout dq dk dv; long dq_bs dk_bs dv_bs;
     int kv_roll""")
 _AttnTailP = _block("_AttnTailP", """
-    int B L d c1 hid out residual; float eps; ptr msg res wm w0 w2 wmT w0T w2T g1 b1 g2 b2 outp dout dmsg dres parts;
+    int B L d c1 hid out residual; float eps; fptr msg res wm w0 w2 wmT w0T w2T g1 b1 g2 b2 outp dout dmsg dres parts;
     long part_stride; int precision fwd_precision""")
 _AttnHeadP = _block("_AttnHeadP", """
-    int B L c hd d np src; ptr x xyz p1 p2 c1 c2 p2T; ptr[3] w wT; ptr outp dout dx parts; long part_stride;
+    int B L c hd d np src; fptr x xyz p1 p2 c1 c2 p2T; fptr[3] w wT; fptr outp dout dx parts; long part_stride;
     int precision fwd_precision""")
 
 # the header's name of every block (what the layout test compiles against)

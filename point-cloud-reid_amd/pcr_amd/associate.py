@@ -15,14 +15,17 @@ from . import _lib as L
 from . import abi
 
 
-def _i32(t):
-    """labels / lengths as the kernels read them; int64 is converted on the device"""
-    if t is None:
-        return None
-    if t.dtype == torch.int64:
-        t = t.to(torch.int32)
-    L.require_i32(t)
-    return t.contiguous()
+def _labels(t, who, name, n=None, optional=False):
+    """labels / lengths as the kernels read them: (n,) int32, contiguous; int64 is converted on the device"""
+    return L.tensor(t, who, name, torch.int32, shape=(n,), optional=optional, cast_int64=True, copy=True)
+
+
+def _pair_list(logits, pairs, count, who):
+    """logits (cap,) float32, pairs (cap, 2), count (1,) int32 as compare_pairs returns them -> the three and cap"""
+    pairs = L.tensor(pairs, who, "pairs", torch.int32, shape=(None, 2))
+    cap = pairs.shape[0]
+    return (L.tensor(logits, who, "logits", torch.float32, shape=(cap,)), pairs,
+            L.tensor(count, who, "count", torch.int32, numel=1), cap)
 
 
 def compare_pairs(track_labels, det_labels, track_lengths=None, det_lengths=None, min_points=2, num_classes=8, cap=None,
@@ -35,25 +38,19 @@ def compare_pairs(track_labels, det_labels, track_lengths=None, det_lengths=None
     are written); slots from count on hold (0, 0), valid indices, so the padded list can go to match_gallery as it is.
     cap defaults to T * D.  out = (pairs, count) to write into.
     """
-    L.require_cuda(track_labels, det_labels, track_lengths, det_lengths)
-    assert track_labels.dim() == 1 and det_labels.dim() == 1, "labels must be (T,) and (D,)"
-    tl, dl, tn, dn = _i32(track_labels), _i32(det_labels), _i32(track_lengths), _i32(det_lengths)
+    who = "compare_pairs"
+    tl, dl = _labels(track_labels, who, "track_labels"), _labels(det_labels, who, "det_labels")
     T, D = tl.shape[0], dl.shape[0]
-    assert tn is None or tn.shape == (T,), "track_lengths must be (T,)"
-    assert dn is None or dn.shape == (D,), "det_lengths must be (D,)"
+    tn = _labels(track_lengths, who, "track_lengths", T, optional=True)
+    dn = _labels(det_lengths, who, "det_lengths", D, optional=True)
     cap = T * D if cap is None else int(cap)
-    lib = L.load()
-    if not lib.pcr_assoc_pairs_ok(T, D, int(num_classes), cap):
-        raise L.PcrError("compare_pairs: T=%d D=%d num_classes=%d cap=%d is out of range (pcr_assoc_pairs_ok)"
-                         % (T, D, num_classes, cap))
-    if out is not None:
-        pairs, count = out
-        L.require_cuda(pairs, count)
-        L.require_i32(pairs, count)
-        assert pairs.shape == (cap, 2) and pairs.is_contiguous() and count.shape == (1,)
-    else:
-        pairs = torch.empty((cap, 2), dtype=torch.int32, device=tl.device)
-        count = torch.empty((1,), dtype=torch.int32, device=tl.device)
+    L.require(L.load().pcr_assoc_pairs_ok(T, D, int(num_classes), cap), who,
+              "T=%d D=%d num_classes=%d cap=%d is out of range (pcr_assoc_pairs_ok)", T, D, num_classes, cap)
+    L.require(out is None or len(out) == 2, who, "out must be (pairs, count)")
+    pairs, count = out if out is not None else (None, None)
+    pairs = L.out_tensor(pairs, who, "out[0] (pairs)", torch.int32, (cap, 2), tl.device)
+    count = L.out_tensor(count, who, "out[1] (count)", torch.int32, (1,), tl.device)
+    L.require_cuda(tl, dl, tn, dn, pairs, count)
     if T == 0 or D == 0:                 # the entry launches nothing for an empty side: the list is empty
         pairs.zero_()
         count.zero_()
@@ -71,25 +68,40 @@ def association_cost(logits, pairs, count, T, D, track_miss=None, det_new=None, 
     reference's distance prior), fill elsewhere; top-right (T, T): track_miss on the diagonal; bottom-left (D, D):
     det_new on the diagonal; bottom-right (D, T): the transpose of the top-left block.  None for track_miss / det_new
     means zeros."""
-    L.require_cuda(logits, pairs, count, track_miss, det_new, dist, out)
-    L.require_f32(logits, track_miss, det_new, dist, out)
-    L.require_i32(pairs, count)
+    who, f32 = "association_cost", torch.float32
     T, D = int(T), int(D)
-    assert pairs.dim() == 2 and pairs.shape[1] == 2 and pairs.is_contiguous(), "pairs must be a contiguous (cap, 2) tensor"
-    cap = pairs.shape[0]
-    assert logits.shape == (cap,) and logits.is_contiguous() and count.numel() == 1
-    assert track_miss is None or (track_miss.shape == (T,) and track_miss.is_contiguous())
-    assert det_new is None or (det_new.shape == (D,) and det_new.is_contiguous())
-    assert dist is None or (dist.shape == (T, D) and dist.is_contiguous())
-    lib = L.load()
-    if not lib.pcr_assoc_pairs_ok(T, D, 1, cap):
-        raise L.PcrError("association_cost: T=%d D=%d cap=%d is out of range (pcr_assoc_pairs_ok)" % (T, D, cap))
-    if out is None:
-        out = torch.empty((T + D, D + T), dtype=torch.float32, device=logits.device)
-    assert out.shape == (T + D, D + T) and out.is_contiguous()
+    logits, pairs, count, cap = _pair_list(logits, pairs, count, who)
+    track_miss = L.tensor(track_miss, who, "track_miss", f32, shape=(T,), optional=True)
+    det_new = L.tensor(det_new, who, "det_new", f32, shape=(D,), optional=True)
+    dist = L.tensor(dist, who, "dist", f32, shape=(T, D), optional=True)
+    L.require(L.load().pcr_assoc_pairs_ok(T, D, 1, cap), who,
+              "T=%d D=%d cap=%d is out of range (pcr_assoc_pairs_ok)", T, D, cap)
+    out = L.out_tensor(out, who, "out", f32, (T + D, D + T), logits.device)
+    L.require_cuda(logits, pairs, count, track_miss, det_new, dist, out)
     L.run.pcr_assoc_cost_f32(logits, pairs, count, track_miss, det_new, dist, dist_max, dist_penalty, fill, out, T, D, cap,
                              L.stream_ptr())
     return out
+
+
+_ASSIGNMENT = (("out[0] (col4row)", torch.int32), ("out[1] (row4col)", torch.int32), ("out[2] (info)", torch.int32),
+               ("out[3] (u)", torch.float32), ("out[4] (v)", torch.float32))
+
+
+def _assignment_out(out, return_duals, rows, cols, info, device, who):
+    """the outputs of an assignment, [col4row, row4col, info, u, v] of the shapes rows, cols, info, rows, cols: the first
+    three (five with duals) of the caller's out=, or new tensors; u = v = None without duals"""
+    shapes = (rows, cols, info, rows, cols) if return_duals else (rows, cols, info)
+    if out is None:
+        res = [torch.empty(s, dtype=d, device=device) for s, (_, d) in zip(shapes, _ASSIGNMENT)]
+    else:
+        ok = len(out) >= len(shapes)
+        res = [L.tensor(t, who, name, d) for t, (name, d), _ in zip(out, _ASSIGNMENT, shapes)]
+        for t, s in zip(res, shapes):
+            ok = ok and t.shape == s
+        if not ok:
+            L.refuse(who, "out must hold col4row %s, row4col %s and info %s" % shapes[:3] +
+                     (", u %s and v %s" % shapes[3:] if return_duals else ""))
+    return res if return_duals else res + [None, None]
 
 
 def linear_assignment(cost, return_duals=False, out=None):
@@ -100,31 +112,13 @@ def linear_assignment(cost, return_duals=False, out=None):
     by the shortest augmenting path rules include/pcr.h writes down (ties to the lowest column index).  info 0 = solved;
     1 = the problem holds a NaN or an infinity: its indices are -1 and the solver did not run.  out = (col4row, row4col,
     info[, u, v]) to write into."""
-    L.require_cuda(cost)
-    L.require_f32(cost)
-    if cost.dim() == 2:
-        cost = cost.unsqueeze(0)
-    assert cost.dim() == 3 and cost.is_contiguous(), "cost must be a contiguous (B, R, C) or (R, C) tensor"
+    who = "linear_assignment"
+    L.require(isinstance(cost, torch.Tensor) and cost.dim() in (2, 3), who, "cost must be a (B, R, C) or (R, C) tensor")
+    cost = L.tensor(cost if cost.dim() == 3 else cost.unsqueeze(0), who, "cost", torch.float32)
     B, R, C = cost.shape
-    lib = L.load()
-    if not lib.pcr_lsa_ok(B, R, C):
-        raise L.PcrError("linear_assignment: B=%d R=%d C=%d is out of range (pcr_lsa_ok)" % (B, R, C))
-    dev = cost.device
-    if out is not None:
-        col4row, row4col, info = out[0], out[1], out[2]
-        u, v = (out[3], out[4]) if return_duals else (None, None)
-        L.require_cuda(col4row, row4col, info, u, v)
-        L.require_i32(col4row, row4col, info)
-        L.require_f32(u, v)
-    else:
-        col4row = torch.empty((B, R), dtype=torch.int32, device=dev)
-        row4col = torch.empty((B, C), dtype=torch.int32, device=dev)
-        info = torch.empty((B,), dtype=torch.int32, device=dev)
-        u = torch.empty((B, R), dtype=torch.float32, device=dev) if return_duals else None
-        v = torch.empty((B, C), dtype=torch.float32, device=dev) if return_duals else None
-    assert col4row.shape == (B, R) and row4col.shape == (B, C) and info.shape == (B,)
-    assert col4row.is_contiguous() and row4col.is_contiguous()
-    assert u is None or (u.shape == (B, R) and v.shape == (B, C) and u.is_contiguous() and v.is_contiguous())
+    L.require(L.load().pcr_lsa_ok(B, R, C), who, "B=%d R=%d C=%d is out of range (pcr_lsa_ok)", B, R, C)
+    col4row, row4col, info, u, v = _assignment_out(out, return_duals, (B, R), (B, C), (B,), cost.device, who)
+    L.require_cuda(cost, col4row, row4col, info, u, v)
     if B == 0 or R == 0 or C == 0:       # the entry launches nothing for an empty problem: nothing is assigned
         col4row.fill_(-1)
         row4col.fill_(-1)
@@ -146,37 +140,16 @@ def linear_assignment_blocks(cost, row_block, col_block, num_blocks, return_dual
     indices; a row or column with any other id takes no part (-1, dual 0) and only the sub-problems' entries are read.
     info[g] 0 = solved, 1 = block g holds a NaN or an infinity (its rows and columns are -1; the other blocks are solved).
     One launch for all blocks.  out = (col4row, row4col, info[, u, v]) to write into."""
-    L.require_cuda(cost, row_block, col_block)
-    L.require_f32(cost)
-    L.require_i32(row_block, col_block)
-    if cost.dim() != 2 or not cost.is_contiguous():
-        raise L.PcrError("linear_assignment_blocks: cost must be a contiguous (R, C) tensor, got %s" % (tuple(cost.shape),))
+    who = "linear_assignment_blocks"
+    cost = L.tensor(cost, who, "cost", torch.float32, shape=(None, None))
     R, C = cost.shape
     G = int(num_blocks)
-    if row_block.shape != (R,) or col_block.shape != (C,) or not row_block.is_contiguous() or not col_block.is_contiguous():
-        raise L.PcrError("linear_assignment_blocks: row_block must be a contiguous (%d,) and col_block a (%d,) tensor"
-                         % (R, C))
-    lib = L.load()
-    if not lib.pcr_lsa_blocks_ok(R, C, G):
-        raise L.PcrError("linear_assignment_blocks: R=%d C=%d num_blocks=%d is out of range (pcr_lsa_blocks_ok)" % (R, C, G))
-    dev = cost.device
-    if out is not None:
-        col4row, row4col, info = out[0], out[1], out[2]
-        u, v = (out[3], out[4]) if return_duals else (None, None)
-        L.require_cuda(col4row, row4col, info, u, v)
-        L.require_i32(col4row, row4col, info)
-        L.require_f32(u, v)
-    else:
-        col4row = torch.empty((R,), dtype=torch.int32, device=dev)
-        row4col = torch.empty((C,), dtype=torch.int32, device=dev)
-        info = torch.empty((G,), dtype=torch.int32, device=dev)
-        u = torch.empty((R,), dtype=torch.float32, device=dev) if return_duals else None
-        v = torch.empty((C,), dtype=torch.float32, device=dev) if return_duals else None
-    if col4row.shape != (R,) or row4col.shape != (C,) or info.shape != (G,) or not col4row.is_contiguous() \
-            or not row4col.is_contiguous() or not info.is_contiguous():
-        raise L.PcrError("linear_assignment_blocks: out must hold col4row (%d,), row4col (%d,) and info (%d,)" % (R, C, G))
-    if u is not None and (u.shape != (R,) or v.shape != (C,) or not u.is_contiguous() or not v.is_contiguous()):
-        raise L.PcrError("linear_assignment_blocks: the duals must be u (%d,) and v (%d,)" % (R, C))
+    row_block = L.tensor(row_block, who, "row_block", torch.int32, shape=(R,))
+    col_block = L.tensor(col_block, who, "col_block", torch.int32, shape=(C,))
+    L.require(L.load().pcr_lsa_blocks_ok(R, C, G), who,
+              "R=%d C=%d num_blocks=%d is out of range (pcr_lsa_blocks_ok)", R, C, G)
+    col4row, row4col, info, u, v = _assignment_out(out, return_duals, (R,), (C,), (G,), cost.device, who)
+    L.require_cuda(cost, row_block, col_block, col4row, row4col, info, u, v)
     L.run.pcr_lsa_blocks_f32(cost, row_block, col_block, col4row, row4col, u, v, info, R, C, G, L.stream_ptr())
     return (col4row, row4col, info, u, v) if return_duals else (col4row, row4col, info)
 
@@ -186,15 +159,16 @@ def association_blocks(track_labels, det_labels, T, D, dd, td, num_classes=8, re
     num_classes + 1: the block ids of association_cost's (dd = td = 1) or association_cost_multi's matrix for
     linear_assignment_blocks.  An object's block is its label when that lies in [0, num_classes), the rest block num_classes
     otherwise (free bank slots, padded detections, foreign labels); a decision row or column takes its object's block."""
-    L.require_cuda(track_labels, det_labels)
+    who = "association_blocks"
     T, D, dd, td = int(T), int(D), int(dd), int(td)
-    if track_labels.shape != (T,) or det_labels.shape != (D,):
-        raise L.PcrError("association_blocks: labels must be (T,) = (%d,) and (D,) = (%d,)" % (T, D))
-    tl, dl = _i32(track_labels), _i32(det_labels)
+    L.require(all(isinstance(t, torch.Tensor) for t in (track_labels, det_labels)) and track_labels.shape == (T,)
+              and det_labels.shape == (D,), who, "labels must be (T,) = (%d,) and (D,) = (%d,)", T, D)
+    tl, dl = _labels(track_labels, who, "track_labels", T), _labels(det_labels, who, "det_labels", D)
     lib = L.load()
-    if not lib.pcr_assoc_multi_ok(T, D, dd, td, 0) or not lib.pcr_assoc_pairs_ok(0, 0, int(num_classes), 0):
-        raise L.PcrError("association_blocks: T=%d D=%d dd=%d td=%d num_classes=%d is out of range (pcr_assoc_multi_ok, "
-                         "pcr_assoc_pairs_ok)" % (T, D, dd, td, num_classes))
+    L.require(lib.pcr_assoc_multi_ok(T, D, dd, td, 0) and lib.pcr_assoc_pairs_ok(0, 0, int(num_classes), 0), who,
+              "T=%d D=%d dd=%d td=%d num_classes=%d is out of range (pcr_assoc_multi_ok, pcr_assoc_pairs_ok)",
+              T, D, dd, td, num_classes)
+    L.require_cuda(tl, dl)
     R, C = multi_shape(T, D, dd, td, reduce)
     de, te = (int(dd > 0), int(td > 0)) if reduce else (dd, td)
     row_block = torch.empty((R,), dtype=torch.int32, device=tl.device)
@@ -214,11 +188,7 @@ def _decision_rows(values, n, what):
     """decision values (k, n) -> (k, tensor or None); None = no decision on this side"""
     if values is None:
         return 0, None
-    L.require_cuda(values)
-    L.require_f32(values)
-    if values.dim() != 2 or values.shape[1] != n or not values.is_contiguous():
-        raise L.PcrError("association_cost_multi: %s must be a contiguous (decisions, %d) tensor, got %s"
-                         % (what, n, tuple(values.shape)))
+    values = L.tensor(values, "association_cost_multi", what, torch.float32, shape=(None, n))
     return values.shape[0], (values if values.shape[0] else None)
 
 
@@ -242,46 +212,30 @@ def association_cost_multi(logits, pairs, count, T, D, det_decisions=None, track
     (cost, det_choice (D,), track_choice (T,)) with the chosen decision indices (zeros for a side without decisions).
     None for det_decisions / track_decisions means no decision on that side.  out = cost, or (cost, det_choice,
     track_choice) under reduce, to write into."""
-    if kind not in KINDS:
-        raise L.PcrError("association_cost_multi: kind must be 'margin' or 'softmax', got %r" % (kind,))
+    who, f32, i32 = "association_cost_multi", torch.float32, torch.int32
+    L.require(kind in KINDS, who, "kind must be 'margin' or 'softmax', got %r", kind)
     reduce = bool(reduce)
-    if kind == "softmax" and dist is not None:
-        raise L.PcrError("association_cost_multi: the softmax kind takes no distance prior (dist must be None)")
-    if kind == "softmax" and reduce:
-        raise L.PcrError("association_cost_multi: reduce goes with the margin kind only")
-    L.require_cuda(logits, pairs, count, dist)
-    L.require_f32(logits, dist)
-    L.require_i32(pairs, count)
+    L.require(kind != "softmax" or dist is None, who, "the softmax kind takes no distance prior (dist must be None)")
+    L.require(kind != "softmax" or not reduce, who, "reduce goes with the margin kind only")
     T, D = int(T), int(D)
-    if pairs.dim() != 2 or pairs.shape[1] != 2 or not pairs.is_contiguous():
-        raise L.PcrError("association_cost_multi: pairs must be a contiguous (cap, 2) tensor")
-    cap = pairs.shape[0]
-    if logits.shape != (cap,) or not logits.is_contiguous() or count.numel() != 1:
-        raise L.PcrError("association_cost_multi: logits must be a contiguous (cap,) tensor and count hold one int")
-    if dist is not None and (dist.shape != (T, D) or not dist.is_contiguous()):
-        raise L.PcrError("association_cost_multi: dist must be a contiguous (T, D) tensor")
+    logits, pairs, count, cap = _pair_list(logits, pairs, count, who)
+    dist = L.tensor(dist, who, "dist", f32, shape=(T, D), optional=True)
     dd, det_dec = _decision_rows(det_decisions, D, "det_decisions")
     td, trk_dec = _decision_rows(track_decisions, T, "track_decisions")
     lib = L.load()
-    if not lib.pcr_assoc_multi_ok(T, D, dd, td, cap):
-        raise L.PcrError("association_cost_multi: T=%d D=%d dd=%d td=%d cap=%d is out of range (pcr_assoc_multi_ok)"
-                         % (T, D, dd, td, cap))
+    L.require(lib.pcr_assoc_multi_ok(T, D, dd, td, cap), who,
+              "T=%d D=%d dd=%d td=%d cap=%d is out of range (pcr_assoc_multi_ok)", T, D, dd, td, cap)
     R, C = multi_shape(T, D, dd, td, reduce)
     dev = logits.device
+    L.require(out is None or not reduce or len(out) == 3, who, "under reduce out must be (cost, det_choice, track_choice)")
     cost, det_choice, trk_choice = (out if reduce else (out, None, None)) if out is not None else (None, None, None)
-    if cost is None:
-        cost = torch.empty((R, C), dtype=torch.float32, device=dev)
-    if reduce and det_choice is None:
-        det_choice = torch.zeros((D,), dtype=torch.int32, device=dev)
-    if reduce and trk_choice is None:
-        trk_choice = torch.zeros((T,), dtype=torch.int32, device=dev)
-    L.require_cuda(cost, det_choice, trk_choice)
-    L.require_f32(cost)
-    L.require_i32(det_choice, trk_choice)
-    if cost.shape != (R, C) or not cost.is_contiguous():
-        raise L.PcrError("association_cost_multi: out must be a contiguous (%d, %d) tensor" % (R, C))
-    if reduce and (det_choice.shape != (D,) or trk_choice.shape != (T,)):
-        raise L.PcrError("association_cost_multi: det_choice must be (D,) and track_choice (T,)")
+    cost = L.out_tensor(cost, who, "out", f32, (R, C), dev)
+    if reduce:
+        det_choice = torch.zeros((D,), dtype=i32, device=dev) if det_choice is None else \
+            L.tensor(det_choice, who, "det_choice", i32, shape=(D,))
+        trk_choice = torch.zeros((T,), dtype=i32, device=dev) if trk_choice is None else \
+            L.tensor(trk_choice, who, "track_choice", i32, shape=(T,))
+    L.require_cuda(logits, pairs, count, dist, det_dec, trk_dec, cost, det_choice, trk_choice)
     if R * C:                            # the entry launches nothing for an empty matrix
         p = abi.AssocMultiParams()
         p.T, p.D, p.dd, p.td, p.cap, p.kind, p.reduce = T, D, dd, td, cap, KINDS[kind], int(reduce)
@@ -296,9 +250,10 @@ def association_cost_multi(logits, pairs, count, T, D, det_decisions=None, track
                                      "capture" % (key,))
                 ws = _WS[key] = torch.empty((max(lib.pcr_assoc_multi_ws_bytes(T, D, dd, td), 8),), dtype=torch.uint8,
                                             device=dev)
-        for k, t in (("logits", logits), ("pairs", pairs), ("count", count), ("det_dec", det_dec), ("trk_dec", trk_dec),
-                     ("dist", dist), ("ws", ws), ("cost", cost), ("det_choice", det_choice), ("trk_choice", trk_choice)):
-            setattr(p, k, L._p(t))
+        sizes = dict(logits=cap, pairs=2 * cap, count=1, det_dec=dd * D, trk_dec=td * T, dist=T * D,
+                     ws=0 if ws is None else ws.numel(), cost=R * C, det_choice=D, trk_choice=T)
+        abi.fill(p, dict(logits=logits, pairs=pairs, count=count, det_dec=det_dec, trk_dec=trk_dec, dist=dist, ws=ws,
+                         cost=cost, det_choice=det_choice, trk_choice=trk_choice), sizes, who=who)
         L.run.pcr_assoc_cost_multi_f32(ctypes.byref(p), L.stream_ptr())
     return (cost, det_choice, trk_choice) if reduce else cost
 
@@ -317,37 +272,26 @@ def decode_assignment(cost, assignment, T, D, dd, td, fill=10000.0, choices=None
     T, D, dd, td = int(T), int(D), int(dd), int(td)
     reduce = choices is not None
     det_choice, trk_choice = choices if reduce else (None, None)
-    col4row, row4col, sinfo = assignment[0], assignment[1], assignment[2]
-    L.require_cuda(cost, col4row, row4col, sinfo, det_choice, trk_choice)
-    L.require_f32(cost)
-    L.require_i32(col4row, row4col, sinfo, det_choice, trk_choice)
-    lib = L.load()
-    if not lib.pcr_assoc_multi_ok(T, D, dd, td, 0):
-        raise L.PcrError("decode_assignment: T=%d D=%d dd=%d td=%d is out of range (pcr_assoc_multi_ok)" % (T, D, dd, td))
-    if not (-1 <= int(born_decision) < dd and -1 <= int(kill_decision) < td):
-        raise L.PcrError("decode_assignment: born_decision must be -1 or below dd = %d, kill_decision -1 or below td = %d"
-                         % (dd, td))
+    who = "decode_assignment"
+    L.require(len(assignment) >= 3, who, "assignment must be linear_assignment's (col4row, row4col, info)")
+    L.require(L.load().pcr_assoc_multi_ok(T, D, dd, td, 0), who,
+              "T=%d D=%d dd=%d td=%d is out of range (pcr_assoc_multi_ok)", T, D, dd, td)
+    L.require(-1 <= int(born_decision) < dd and -1 <= int(kill_decision) < td, who,
+              "born_decision must be -1 or below dd = %d, kill_decision -1 or below td = %d", dd, td)
     R, C = multi_shape(T, D, dd, td, reduce)
-    if tuple(cost.shape[-2:]) != (R, C) or cost.numel() != R * C or not cost.is_contiguous():
-        raise L.PcrError("decode_assignment: cost must be a contiguous (%d, %d) tensor, got %s" % (R, C, tuple(cost.shape)))
-    if col4row.numel() != R or row4col.numel() != C or sinfo.numel() != 1 or not col4row.is_contiguous() \
-            or not row4col.is_contiguous():
-        raise L.PcrError("decode_assignment: the assignment must hold col4row (%d,), row4col (%d,) and info (1,)" % (R, C))
-    if reduce and (det_choice.shape != (D,) or trk_choice.shape != (T,)):
-        raise L.PcrError("decode_assignment: choices must be (det_choice (D,), track_choice (T,))")
-    dev = cost.device
-    sizes = dict(track_to_det=T, det_to_track=D, det_decision=D, track_decision=T, born=D, kill=T, info=4)
-    out = {k: torch.empty((sizes[k],), dtype=torch.int32, device=dev) for k in DECODE_OUTPUTS}
-    if T + D == 0:                       # the entry launches nothing
-        out["info"].zero_()
-        return out
+    L.require(isinstance(cost, torch.Tensor) and tuple(cost.shape[-2:]) == (R, C), who,
+              "cost must be a contiguous (%d, %d) tensor, got %s", R, C, tuple(getattr(cost, "shape", ())))
+    sizes = dict(cost=R * C, col4row=R, row4col=C, solver_info=1, det_choice=D, trk_choice=T, track_to_det=T,
+                 det_to_track=D, det_decision=D, track_decision=T, born=D, kill=T, info=4)
+    out = {k: torch.empty((sizes[k],), dtype=torch.int32, device=cost.device) for k in DECODE_OUTPUTS}
+    given = dict(cost=cost, col4row=assignment[0], row4col=assignment[1], solver_info=assignment[2], det_choice=det_choice,
+                 trk_choice=trk_choice)
     p = abi.AssocDecodeParams()
     p.T, p.D, p.dd, p.td, p.reduce = T, D, dd, td, int(reduce)
     p.born_dec, p.kill_dec, p.fill = int(born_decision), int(kill_decision), float(fill)
-    for k, t in (("cost", cost), ("col4row", col4row), ("row4col", row4col), ("solver_info", sinfo),
-                 ("det_choice", det_choice), ("trk_choice", trk_choice)):
-        setattr(p, k, L._p(t))
-    for k in DECODE_OUTPUTS:
-        setattr(p, k, L._p(out[k]))
+    abi.fill(p, dict(given, **out), sizes, required=[k for k in given if reduce or not k.endswith("choice")], who=who)
+    if T + D == 0:                       # the entry launches nothing
+        out["info"].zero_()
+        return out
     L.run.pcr_assoc_decode_i32(ctypes.byref(p), L.stream_ptr())
     return out

@@ -10,6 +10,7 @@ import torch
 
 from . import _lib as L
 
+_WHO = "pcr_amd.crops"
 FRAMES = {"sensor": 0, "centred": 1, "box": 2}
 RULES = {"tracker": 0, "dataset": 1}
 
@@ -21,13 +22,10 @@ def crop_boxes_ok(P, M, n, stride=3):
 
 def box_frames(boxes, out=None):
     """boxes (T, 7) -> (T, 2) float32 = (cos(rz + pi/2), sin(rz + pi/2)) as the kernels evaluate them"""
-    L.require_cuda(boxes, out)
-    L.require_f32(boxes, out)
-    assert boxes.dim() == 2 and boxes.shape[1] == 7 and boxes.is_contiguous()
+    boxes = L.tensor(boxes, _WHO, "boxes", torch.float32, shape=(None, 7))
     T = boxes.shape[0]
-    if out is None:
-        out = torch.empty((T, 2), dtype=torch.float32, device=boxes.device)
-    assert out.shape == (T, 2) and out.is_contiguous()
+    out = L.out_tensor(out, _WHO, "out", torch.float32, (T, 2), boxes.device)
+    L.require_cuda(boxes, out)
     L.run.pcr_box_frames_f32(boxes, out, T, L.stream_ptr())
     return out
 
@@ -52,36 +50,26 @@ def crops_from_boxes(points, boxes, n, frame="box", rule="tracker", rand=None, s
     if rule not in RULES:
         raise ValueError("rule must be one of %s, got %r" % (sorted(RULES), rule))
     seed_t = seed if isinstance(seed, torch.Tensor) else None
-    L.require_cuda(points, boxes, rand, seed_t)
-    L.require_f32(points, boxes)
-    L.require_i32(rand)
-    assert points.dim() == 2 and points.shape[1] >= 3, "points must be (P, C >= 3), got %s" % (tuple(points.shape),)
-    assert boxes.dim() == 2 and boxes.shape[1] == 7, "boxes must be (M, 7), got %s" % (tuple(boxes.shape),)
-    assert points.is_contiguous() and boxes.is_contiguous()
-    assert points.device == boxes.device, "points and boxes should be put on the same device"
+    points = L.tensor(points, _WHO, "points", torch.float32, shape=(None, None))
+    L.require(points.shape[1] >= 3, _WHO, "points must be (P, C >= 3), got %s", tuple(points.shape))
+    boxes = L.tensor(boxes, _WHO, "boxes", torch.float32, shape=(None, 7))
     P, stride = points.shape
     M, n = boxes.shape[0], int(n)
+    rand = L.tensor(rand, _WHO, "rand", torch.int32, shape=(M, n), optional=True)
     if not crop_boxes_ok(P, M, n, stride):
         raise L.PcrError("crops_from_boxes: launch shape P=%d M=%d n=%d stride=%d is out of range (pcr_crop_boxes_ok)"
                          % (P, M, n, stride))
     dev = points.device
-    if rand is not None:
-        assert rand.shape == (M, n) and rand.is_contiguous(), "rand must be a contiguous (M, n) int32 tensor"
     if seed_t is not None:
         if seed_t.dtype != torch.int64 or seed_t.numel() != 1:
             raise L.PcrError("seed must be a device int64 tensor of one element or a Python int")
     elif seed is not None:
         s = int(seed) & 0xFFFFFFFFFFFFFFFF
         seed_t = torch.full((1,), s - (1 << 64) if s >= (1 << 63) else s, dtype=torch.int64, device=dev)
-    if out is not None:
-        clouds, lengths = out[0], out[1]
-        L.require_cuda(clouds, lengths)
-        L.require_f32(clouds)
-        L.require_i32(lengths)
-        assert clouds.shape == (M, n, 3) and clouds.is_contiguous() and lengths.shape == (M,) and lengths.is_contiguous()
-    else:
-        clouds = torch.empty((M, n, 3), dtype=torch.float32, device=dev)
-        lengths = torch.empty((M,), dtype=torch.int32, device=dev)
+    L.require(out is None or len(out) >= 2, _WHO, "out must be (clouds, lengths[, frames])")
+    clouds = L.out_tensor(None if out is None else out[0], _WHO, "out[0] (clouds)", torch.float32, (M, n, 3), dev)
+    lengths = L.out_tensor(None if out is None else out[1], _WHO, "out[1] (lengths)", torch.int32, (M,), dev)
+    L.require_cuda(points, boxes, rand, seed_t, clouds, lengths)
     L.run.pcr_crop_boxes_f32(points, stride, boxes, rand, L.ptr(seed_t), clouds, lengths, P, M, n, FRAMES[frame],
                              RULES[rule], int(bool(z_is_centre)), L.stream_ptr())
     if return_frames:

@@ -23,15 +23,7 @@ N_TOTALS, N_COUNTS = 8, 4
 COUNTS = dict(n_rows=0, n_cols=1, max_count=2)
 TABLE = ("idtp", "frames", "gt_total", "pred_total", "tp", "tracks", "mt", "pt", "ml", "frag", "tid_sum", "lgd_sum",
          "overflow", "inexact", "dropped_gt", "dropped_id")                                         # PCR_IDENT_IDTP ..
-_RECORD = ("det_labels", "det_gt", "det_id", "gt_labels", "gt_ids", "cost", "cooc", "gt_track", "totals", "dist_sum")
-_CLOSE = ("cooc", "gt_track", "totals", "dist_sum", "flags", "counts", "row_list", "col_list", "cost", "col4row", "info",
-          "id_map", "table", "dist_total")
-_DTYPES = dict(cost=torch.float32, dist_sum=torch.float64, dist_total=torch.float64, table=torch.int64)
-
-
-def _require(ok, what):
-    if not ok:
-        raise L.PcrError("pcr_amd.identity: " + what)
+_WHO = "pcr_amd.identity"
 
 
 def ident_ok(D, G, gt_cap, gt_rows, id_cap, max_rows=1, max_cols=1):
@@ -40,67 +32,48 @@ def ident_ok(D, G, gt_cap, gt_rows, id_cap, max_rows=1, max_cols=1):
     return bool(L.load().pcr_ident_ok(int(D), int(G), int(gt_cap), int(gt_rows), int(id_cap), int(max_rows), int(max_cols)))
 
 
-def _fill(p, t, names, sizes, optional=()):
-    """checks the dict of explicit tensors `t` and writes their addresses into the parameter block"""
-    for k in t:
-        _require(k in names, "unknown tensor %r" % k)
-    for k in names:                                          # what is wrong with the call itself comes before where it lives
-        x = t.get(k)
-        _require(x is None or isinstance(x, torch.Tensor), "%s must be a tensor" % k)
-        if x is None:
-            _require(k in optional or sizes[k] == 0, "%s is missing" % k)
-            continue
-        want = _DTYPES.get(k, torch.int32)
-        _require(x.dtype == want, "%s must be a %s tensor, got %s" % (k, want, x.dtype))
-        _require(x.numel() == sizes[k] and x.is_contiguous(), "%s must be contiguous and hold %d elements, got %s"
-                 % (k, sizes[k], tuple(x.shape)))
-    L.require_cuda(*[t.get(k) for k in names])
-    for k in names:
-        x = t.get(k)
-        setattr(p, k, L._p(x) if x is not None and x.numel() else None)
-    return p
-
-
 def record(tensors, gt_cap, gt_rows, id_cap):
     """pcr_ident_record_i32 on explicit tensors: a dict with det_labels, det_gt, det_id (D,), gt_labels, gt_ids (G,), cost
     (D, G) float32 and the scene state cooc (gt_rows, id_cap), gt_track (gt_rows, 8), totals (8,) int32, dist_sum (1,)
     float64.  The scene state is added to in place."""
     t = tensors
     for k in ("det_labels", "gt_labels"):
-        _require(isinstance(t.get(k), torch.Tensor) and t[k].dim() == 1, "%s must be a 1-D tensor" % k)
+        L.require(isinstance(t.get(k), torch.Tensor) and t[k].dim() == 1, _WHO, "%s must be a 1-D tensor", k)
     D, G = t["det_labels"].shape[0], t["gt_labels"].shape[0]
-    _require(ident_ok(D, G, gt_cap, gt_rows, id_cap), "D=%d G=%d gt_cap=%d gt_rows=%d id_cap=%d is out of range (pcr_ident_ok)"
-             % (D, G, gt_cap, gt_rows, id_cap))
+    L.require(ident_ok(D, G, gt_cap, gt_rows, id_cap), _WHO, "D=%d G=%d gt_cap=%d gt_rows=%d id_cap=%d is out of range (pcr_ident_ok)",
+              D, G, gt_cap, gt_rows, id_cap)
     sizes = dict(det_labels=D, det_gt=D, det_id=D, gt_labels=G, gt_ids=G, cost=D * G, cooc=gt_rows * id_cap,
                  gt_track=gt_rows * len(TRACK_COLS), totals=N_TOTALS, dist_sum=1)
     p = abi.IdentParams()
     p.D, p.G, p.gt_cap, p.gt_rows, p.id_cap = D, G, int(gt_cap), int(gt_rows), int(id_cap)
-    L.run.pcr_ident_record_i32(ctypes.byref(_fill(p, t, _RECORD, sizes)), L.stream_ptr())
+    L.run.pcr_ident_record_i32(ctypes.byref(abi.fill(p, t, sizes, required=sizes, who=_WHO)), L.stream_ptr())
 
 
-def _close_params(t, gt_rows, id_cap, max_rows, max_cols, optional):
-    _require(ident_ok(0, 0, 1, gt_rows, id_cap, max_rows, max_cols),
-             "gt_rows=%d id_cap=%d max_rows=%d max_cols=%d is out of range (pcr_ident_ok)" % (gt_rows, id_cap, max_rows, max_cols))
+def _close_params(t, gt_rows, id_cap, max_rows, max_cols, required):
+    L.require(ident_ok(0, 0, 1, gt_rows, id_cap, max_rows, max_cols), _WHO,
+              "gt_rows=%d id_cap=%d max_rows=%d max_cols=%d is out of range (pcr_ident_ok)", gt_rows, id_cap, max_rows, max_cols)
     sizes = dict(cooc=gt_rows * id_cap, gt_track=gt_rows * len(TRACK_COLS), totals=N_TOTALS, dist_sum=1,
                  flags=gt_rows + id_cap, counts=N_COUNTS, row_list=max_rows, col_list=max_cols, cost=max_rows * max_cols,
                  col4row=max_rows, info=1, id_map=gt_rows, table=len(TABLE), dist_total=1)
     p = abi.IdentCloseParams()
     p.gt_rows, p.id_cap, p.max_rows, p.max_cols = int(gt_rows), int(id_cap), int(max_rows), int(max_cols)
-    return _fill(p, t, _CLOSE, sizes, optional)
+    return abi.fill(p, t, sizes, required=required, who=_WHO)
 
 
 def compact(tensors, gt_rows, id_cap, max_rows, max_cols):
     """pcr_ident_compact_f32 on explicit tensors: cooc (gt_rows, id_cap) -> flags (gt_rows + id_cap,) workspace, counts (4,),
     row_list (max_rows,), col_list (max_cols,) int32 and cost (max_rows, max_cols) float32, every element written"""
     p = _close_params(tensors, gt_rows, id_cap, max_rows, max_cols,
-                      ("gt_track", "totals", "dist_sum", "col4row", "info", "id_map", "table", "dist_total"))
+                      ("cooc", "flags", "counts", "row_list", "col_list", "cost"))
     L.run.pcr_ident_compact_f32(ctypes.byref(p), L.stream_ptr())
 
 
 def score(tensors, gt_rows, id_cap, max_rows, max_cols):
     """pcr_ident_score_i32 on explicit tensors: the scene state, compact's counts, row_list and col_list, the assignment's
     col4row (max_rows,) and info (1,) -> id_map (gt_rows,) written; table (16,) int64 and dist_total (1,) float64 added to"""
-    p = _close_params(tensors, gt_rows, id_cap, max_rows, max_cols, ("flags", "cost"))
+    p = _close_params(tensors, gt_rows, id_cap, max_rows, max_cols,
+                      ("cooc", "gt_track", "totals", "dist_sum", "counts", "row_list", "col_list", "col4row", "info", "id_map",
+                       "table", "dist_total"))
     L.run.pcr_ident_score_i32(ctypes.byref(p), L.stream_ptr())
 
 
@@ -136,13 +109,13 @@ class IdentityBook:
 
     def __init__(self, truth_book, id_cap, gt_rows=None, max_rows=256, max_cols=512):
         from . import truth as TU
-        _require(isinstance(truth_book, TU.TruthBook), "truth_book must be a pcr_amd.truth.TruthBook")
+        L.require(isinstance(truth_book, TU.TruthBook), _WHO, "truth_book must be a pcr_amd.truth.TruthBook")
         book = self.book = truth_book
-        _require(book.bank.device.type == "cuda", "the book lives on %s; there is no CPU fallback" % book.bank.device)
+        L.require(book.bank.device.type == "cuda", _WHO, "the book lives on %s; there is no CPU fallback", book.bank.device)
         gt_rows = book.gt_cap if gt_rows is None else int(gt_rows)
         D, G = book.bank.max_dets, book.max_gt
-        _require(ident_ok(D, G, book.gt_cap, gt_rows, id_cap, max_rows, max_cols),
-                 "gt_rows=%d id_cap=%d max_rows=%d max_cols=%d is out of range (pcr_ident_ok)" % (gt_rows, id_cap, max_rows, max_cols))
+        L.require(ident_ok(D, G, book.gt_cap, gt_rows, id_cap, max_rows, max_cols), _WHO,
+                  "gt_rows=%d id_cap=%d max_rows=%d max_cols=%d is out of range (pcr_ident_ok)", gt_rows, id_cap, max_rows, max_cols)
         self.gt_rows, self.id_cap, self.max_rows, self.max_cols = gt_rows, int(id_cap), int(max_rows), int(max_cols)
         dev = book.bank.device
         z = lambda dtype, *shape: torch.zeros(shape, dtype=dtype, device=dev)
@@ -163,10 +136,10 @@ class IdentityBook:
         """pcr_ident_record_i32 right AFTER `TruthBook.record`, over the book's buffers as they stand; det_id (max_dets,):
         the update's (default: the one the book's `record` was given)"""
         book = self.book
-        _require(book._det_labels is not None, "record follows TruthBook.decide")
+        L.require(book._det_labels is not None, _WHO, "record follows TruthBook.decide")
         if det_id is None:
             det_id = getattr(book, "_det_id", None)
-            _require(det_id is not None, "record follows TruthBook.record")
+            L.require(det_id is not None, _WHO, "record follows TruthBook.record")
         t = self._scene()
         t.update(det_labels=book._det_labels, det_gt=book.det_gt, det_id=det_id, gt_labels=book.gt_labels, gt_ids=book.gt_ids,
                  cost=book.cost)

@@ -26,10 +26,7 @@ _THRESH = {}      # (device index, value) -> (1,) float32
 _THRESH_MAX = 64  # distinct Python-float thresholds kept per process; a caller that sweeps more passes a device tensor
 
 
-def _require(ok, what):
-    """argument checks raise PcrError like the dtype and device checks (an assert would vanish under python -O)"""
-    if not ok:
-        raise L.PcrError("pcr_amd.nms: " + what)
+_WHO = "pcr_amd.nms"
 
 
 def _cached(table, key, make):
@@ -45,10 +42,8 @@ def _thresh(thresh, device):
     """a Python number -> its cached (1,) device tensor; a device tensor of one float32 is taken as it is (and re-read by
     every replay of a captured launch)"""
     if isinstance(thresh, torch.Tensor):
+        thresh = L.tensor(thresh, _WHO, "thresh", torch.float32, numel=1)
         L.require_cuda(thresh)
-        L.require_f32(thresh)
-        if thresh.numel() != 1:
-            raise L.PcrError("thresh must hold one float, got shape %s" % (tuple(thresh.shape),))
         return thresh
     v = float(thresh)
     make = lambda: torch.full((1,), v, dtype=torch.float32, device=device)
@@ -62,10 +57,7 @@ def _thresh(thresh, device):
 
 
 def _boxes(t, width, name):
-    L.require_cuda(t)
-    L.require_f32(t)
-    _require(t.dim() == 2 and t.shape[1] == width, "%s must be (N, %d), got %s" % (name, width, tuple(t.shape)))
-    return t.contiguous()
+    return L.tensor(t, _WHO, name, torch.float32, shape=(None, width), copy=True)
 
 
 def nms_ok(N):
@@ -78,11 +70,8 @@ def nearest_bev(boxes7, out=None):
     turned to the nearer axis) with a zero angle column, so that the result goes to every op here as it is"""
     boxes7 = _boxes(boxes7, 7, "boxes7")
     N = boxes7.shape[0]
-    if out is None:
-        out = torch.empty((N, 5), dtype=torch.float32, device=boxes7.device)
-    L.require_cuda(out)
-    L.require_f32(out)
-    _require(out.shape == (N, 5) and out.is_contiguous(), "a tensor has the wrong shape or is not contiguous")
+    out = L.out_tensor(out, _WHO, "out", torch.float32, (N, 5), boxes7.device)
+    L.require_cuda(boxes7, out)
     L.run.pcr_nearest_bev_f32(boxes7, out, N, L.stream_ptr())
     return out
 
@@ -91,11 +80,8 @@ def bev_frames(boxes5, out=None):
     """boxes5 (N, 5) -> (N, 2) float32 = (cos(angle), sin(angle)) as the rotated kernels evaluate them"""
     boxes5 = _boxes(boxes5, 5, "boxes5")
     N = boxes5.shape[0]
-    if out is None:
-        out = torch.empty((N, 2), dtype=torch.float32, device=boxes5.device)
-    L.require_cuda(out)
-    L.require_f32(out)
-    _require(out.shape == (N, 2) and out.is_contiguous(), "a tensor has the wrong shape or is not contiguous")
+    out = L.out_tensor(out, _WHO, "out", torch.float32, (N, 2), boxes5.device)
+    L.require_cuda(boxes5, out)
     L.run.pcr_bev_frames_f32(boxes5, out, N, L.stream_ptr())
     return out
 
@@ -109,11 +95,8 @@ def iou_bev(a, b, kind="rotated", out=None):
         raise ValueError("kind must be one of %s, got %r" % (sorted(KINDS), kind))
     a, b = _boxes(a, 5, "a"), _boxes(b, 5, "b")
     A, B = a.shape[0], b.shape[0]
-    if out is None:
-        out = torch.empty((A, B), dtype=torch.float32, device=a.device)
-    L.require_cuda(out)
-    L.require_f32(out)
-    _require(out.shape == (A, B) and out.is_contiguous(), "a tensor has the wrong shape or is not contiguous")
+    out = L.out_tensor(out, _WHO, "out", torch.float32, (A, B), a.device)
+    L.require_cuda(a, b, out)
     L.run.pcr_iou_bev_f32(a, b, out, A, B, KINDS[kind], L.stream_ptr())
     return out
 
@@ -133,28 +116,21 @@ def nms(boxes5, scores, thresh, kind="rotated", pre_max=None, out=None, return_o
     if kind not in ("rotated", "axis"):
         raise ValueError("kind must be 'rotated' or 'axis', got %r" % (kind,))
     boxes5 = _boxes(boxes5, 5, "boxes5")
-    L.require_cuda(scores)
-    L.require_f32(scores)
     N = boxes5.shape[0]
-    _require(scores.shape == (N,), "scores must be (N,)")
-    scores = scores.contiguous()
-    if not nms_ok(N):
-        raise L.PcrError("nms: N=%d is out of range (pcr_nms_ok)" % N)
-    dev = boxes5.device
+    scores = L.tensor(scores, _WHO, "scores", torch.float32, shape=(N,), copy=True)
+    L.require(nms_ok(N), "nms", "N=%d is out of range (pcr_nms_ok)", N)
+    dev, i32 = boxes5.device, torch.int32
     if out is not None:
-        keep, count, info = out[0], out[1], out[2]
+        L.require(len(out) >= 3, _WHO, "out must be (keep (N,), count (1,), info (1,)[, order (N,)])")
+        keep = L.tensor(out[0], _WHO, "out[0] (keep)", i32, shape=(N,))
+        count, info = L.tensor(out[1], _WHO, "out[1] (count)", i32, numel=1), L.tensor(out[2], _WHO, "out[2] (info)", i32, numel=1)
         order = out[3] if len(out) > 3 else None
-        L.require_cuda(keep, count, info, order)
-        L.require_i32(keep, count, info, order)
-        _require(keep.shape == (N,) and keep.is_contiguous() and count.numel() == 1 and info.numel() == 1,
-                 "out must be (keep (N,), count (1,), info (1,)[, order (N,)]), contiguous")
     else:
-        keep = torch.empty((N,), dtype=torch.int32, device=dev)
-        both = torch.empty((2,), dtype=torch.int32, device=dev)           # adjacent: one read fetches both
+        keep = torch.empty((N,), dtype=i32, device=dev)
+        both = torch.empty((2,), dtype=i32, device=dev)                   # adjacent: one read fetches both
         count, info, order = both[0:1], both[1:2], None
-    if order is None:
-        order = torch.empty((N,), dtype=torch.int32, device=dev)
-    _require(order.shape == (N,) and order.is_contiguous(), "a tensor has the wrong shape or is not contiguous")
+    order = L.out_tensor(order, _WHO, "out[3] (order)", i32, (N,), dev)
+    L.require_cuda(boxes5, scores, keep, count, info, order)
     if N == 0:                           # the entry launches nothing for no boxes: nothing is kept
         count.zero_()
         info.zero_()
@@ -170,20 +146,13 @@ def track_nms(boxes5, classes, scores, thresh, out=None):
     """The tracker's pairwise rule on BEV boxes (N, 5) (the angle is ignored) -> suppressed (N,) int32, 0 or 1: for every
     i < j of one class with iou_normal > thresh, i is suppressed if scores[i] - scores[j] <= 0, otherwise j."""
     boxes5 = _boxes(boxes5, 5, "boxes5")
-    L.require_cuda(classes, scores, out)
-    L.require_f32(scores)
-    L.require_i32(out)
     N = boxes5.shape[0]
-    if classes.dtype == torch.int64:     # the tracker's class tensor is int64; converted on the device
-        classes = classes.to(torch.int32)
-    L.require_i32(classes)
-    _require(classes.shape == (N,) and scores.shape == (N,), "classes and scores must be (N,)")
-    if not nms_ok(N):
-        raise L.PcrError("track_nms: N=%d is out of range (pcr_nms_ok)" % N)
-    if out is None:
-        out = torch.empty((N,), dtype=torch.int32, device=boxes5.device)
-    _require(out.shape == (N,) and out.is_contiguous(), "a tensor has the wrong shape or is not contiguous")
-    L.run.pcr_track_nms_f32(boxes5, classes.contiguous(), scores.contiguous(), _thresh(thresh, boxes5.device), out, N,
+    classes = L.tensor(classes, _WHO, "classes", torch.int32, shape=(N,), cast_int64=True, copy=True)    # the tracker's is int64
+    scores = L.tensor(scores, _WHO, "scores", torch.float32, shape=(N,), copy=True)
+    L.require(nms_ok(N), "track_nms", "N=%d is out of range (pcr_nms_ok)", N)
+    out = L.out_tensor(out, _WHO, "out", torch.int32, (N,), boxes5.device)
+    L.require_cuda(boxes5, classes, scores, out)
+    L.run.pcr_track_nms_f32(boxes5, classes, scores, _thresh(thresh, boxes5.device), out, N,
                             L.stream_ptr())
     return out
 

@@ -20,12 +20,7 @@ from . import abi
 
 MAX_QUERIES, MAX_GALLERY, MAX_K, MAX_RANKS = 65535, 4096, 64, 8      # PCR_RANK_MAX_*
 OUTPUTS = ("topk_idx", "topk_score", "n_cand", "n_true", "first_hit", "ap", "info")
-_FLOAT_OUTPUTS = ("topk_score", "ap")
-
-
-def _require(ok, what):
-    if not ok:
-        raise L.PcrError("pcr_amd.retrieval: " + what)
+_WHO = "pcr_amd.retrieval"
 
 
 def rank_ok(Q, G, K=1, cap=0):
@@ -33,38 +28,27 @@ def rank_ok(Q, G, K=1, cap=0):
     return bool(L.load().pcr_rank_ok(int(Q), int(G), int(K), int(cap)))
 
 
-def _tensors(*ts):
-    for t in ts:
-        _require(t is None or isinstance(t, torch.Tensor), "every argument must be a tensor")
-    L.require_cuda(*ts)
-
-
 def score_matrix(logits, pairs, count, Q, G, out=None):
     """pcr_rank_scores_f32: logits (cap,), pairs (cap, 2) int32, count (1,) int32 on the device -> scores (Q, G) float32,
     every element written: logits[k] at pairs[k] = (q, g) for k < min(count, cap), -inf elsewhere; a pair outside
     [0, Q) x [0, G) is skipped.  The pairs must be distinct (compare_pairs' are).  out = a (Q, G) tensor to write into."""
-    _tensors(logits, pairs, count, out)
-    L.require_f32(logits, out)
-    L.require_i32(pairs, count)
     Q, G = int(Q), int(G)
-    _require(pairs is not None and pairs.dim() == 2 and pairs.shape[1] == 2 and pairs.is_contiguous(),
-             "pairs must be a contiguous (cap, 2) tensor")
+    pairs = L.tensor(pairs, _WHO, "pairs", torch.int32, shape=(None, 2))
     cap = pairs.shape[0]
-    _require(logits is not None and logits.shape == (cap,) and logits.is_contiguous(), "logits must be a contiguous (%d,) tensor" % cap)
-    _require(count is not None and count.numel() == 1, "count must be a (1,) int32 device tensor")
-    _require(Q >= 0 and G >= 0 and cap <= Q * G and rank_ok(Q, G, 1, cap),
-             "Q=%d G=%d cap=%d is out of range (pcr_rank_ok)" % (Q, G, cap))
-    if out is None:
-        out = torch.empty((Q, G), dtype=torch.float32, device=logits.device)
-    _require(out.shape == (Q, G) and out.is_contiguous(), "out must be a contiguous (%d, %d) tensor" % (Q, G))
+    logits = L.tensor(logits, _WHO, "logits", torch.float32, shape=(cap,))
+    count = L.tensor(count, _WHO, "count", torch.int32, numel=1)
+    L.require(Q >= 0 and G >= 0 and cap <= Q * G and rank_ok(Q, G, 1, cap), _WHO,
+              "Q=%d G=%d cap=%d is out of range (pcr_rank_ok)", Q, G, cap)
+    out = L.out_tensor(out, _WHO, "out", torch.float32, (Q, G), logits.device)
+    L.require_cuda(logits, pairs, count, out)
     L.run.pcr_rank_scores_f32(logits, pairs, count, out, Q, G, cap, L.stream_ptr())
     return out
 
 
 def rank_buffers(Q, K, device):
     """the seven outputs of rank_gallery for Q queries and K ranks, to be passed as out= (a captured graph keeps them)"""
-    return {k: torch.empty((Q, K) if k.startswith("topk") else (Q,),
-                           dtype=torch.float32 if k in _FLOAT_OUTPUTS else torch.int32, device=device) for k in OUTPUTS}
+    return {k: torch.empty((Q, K) if k.startswith("topk") else (Q,), dtype=abi.RankParams.ELEM[k], device=device)
+            for k in OUTPUTS}
 
 
 def rank_gallery(scores, query_ids, gallery_ids, topk=10, exclude=None, out=None):
@@ -74,35 +58,23 @@ def rank_gallery(scores, query_ids, gallery_ids, topk=10, exclude=None, out=None
     every element written by the rules of include/pcr.h section A8: descending score, ties to the lowest gallery index;
     info 1 = a candidate's score is a NaN, the query is not ranked.  With None ids only topk_* and n_cand are meaningful.
     out = such a dict (`rank_buffers`) to write into."""
-    _tensors(scores, query_ids, gallery_ids, exclude)
-    L.require_f32(scores)
-    L.require_i32(query_ids, gallery_ids, exclude)
-    _require(scores is not None and scores.dim() == 2 and scores.is_contiguous(), "scores must be a contiguous (Q, G) tensor")
+    scores = L.tensor(scores, _WHO, "scores", torch.float32, shape=(None, None))
     (Q, G), K = scores.shape, int(topk)
-    _require(rank_ok(Q, G, K), "Q=%d G=%d topk=%d is out of range (pcr_rank_ok)" % (Q, G, K))
+    L.require(rank_ok(Q, G, K), _WHO, "Q=%d G=%d topk=%d is out of range (pcr_rank_ok)", Q, G, K)
     dev = scores.device
     if query_ids is None:
         query_ids = torch.full((Q,), -1, dtype=torch.int32, device=dev)
     if gallery_ids is None:
         gallery_ids = torch.full((G,), -1, dtype=torch.int32, device=dev)
-    for t, n, name in ((query_ids, Q, "query_ids"), (gallery_ids, G, "gallery_ids"), (exclude, Q, "exclude")):
-        _require(t is None or (t.shape == (n,) and t.is_contiguous()), "%s must be a contiguous (%d,) tensor" % (name, n))
     if out is None:
         out = rank_buffers(Q, K, dev)
-    _require(isinstance(out, dict) and all(k in out for k in OUTPUTS), "out must hold %s" % ", ".join(OUTPUTS))
-    _tensors(*[out[k] for k in OUTPUTS])
-    L.require_f32(*[out[k] for k in _FLOAT_OUTPUTS])
-    L.require_i32(*[out[k] for k in OUTPUTS if k not in _FLOAT_OUTPUTS])
+    L.require(isinstance(out, dict) and all(k in out for k in OUTPUTS), _WHO, "out must hold %s", ", ".join(OUTPUTS))
+    sizes = dict(scores=Q * G, query_ids=Q, gallery_ids=G, exclude=Q, topk_idx=Q * K, topk_score=Q * K, n_cand=Q, n_true=Q,
+                 first_hit=Q, ap=Q, info=Q)
     p = abi.RankParams()
     p.Q, p.G, p.K = Q, G, K
-    for k in OUTPUTS:
-        shape = (Q, K) if k.startswith("topk") else (Q,)
-        _require(out[k].shape == shape and out[k].is_contiguous(), "out[%r] must be a contiguous %s tensor" % (k, shape))
-        setattr(p, k, L._p(out[k]) if Q else None)
-    p.scores = L._p(scores) if Q * G else None
-    p.query_ids = L._p(query_ids) if Q else None
-    p.gallery_ids = L._p(gallery_ids) if G else None
-    p.exclude = L._p(exclude) if exclude is not None and Q else None
+    abi.fill(p, dict({k: out[k] for k in OUTPUTS}, scores=scores, query_ids=query_ids, gallery_ids=gallery_ids,
+                     exclude=exclude), sizes, who=_WHO)
     L.run.pcr_rank_gallery_f32(ctypes.byref(p), L.stream_ptr())
     return {k: out[k] for k in OUTPUTS}
 
@@ -128,8 +100,8 @@ class RankBook:
 
     def __init__(self, ranks=(1, 5, 10), device="cuda"):
         self.ranks = tuple(int(r) for r in ranks)
-        _require(len(self.ranks) <= MAX_RANKS and all(1 <= r <= MAX_GALLERY for r in self.ranks),
-                 "ranks must be at most %d values in [1, %d]" % (MAX_RANKS, MAX_GALLERY))
+        L.require(len(self.ranks) <= MAX_RANKS and all(1 <= r <= MAX_GALLERY for r in self.ranks), _WHO,
+                  "ranks must be at most %d values in [1, %d]", MAX_RANKS, MAX_GALLERY)
         self.device = torch.device(device)
         self.counts = torch.zeros(3 + len(self.ranks), dtype=torch.int32, device=self.device)
         self.sums = torch.zeros(2, dtype=torch.float64, device=self.device)
@@ -143,28 +115,22 @@ class RankBook:
         int): only the first clamp(valid, 0, Q) queries count (the rest is a chunk's padding); gallery = the number of
         gallery entries G the ranks are held against (every rank must lie in [1, G]); by default the width of
         result['scores'] when retrieve returned it, the largest rank otherwise."""
-        ts = [result[k] for k in ("n_true", "first_hit", "info", "ap")]
+        t = {k: result[k] for k in ("n_true", "first_hit", "info", "ap")}
         if isinstance(valid, int):
             valid = torch.tensor([valid], dtype=torch.int32, device=self.device)
-        _tensors(*ts, valid)
-        L.require_i32(ts[0], ts[1], ts[2], valid)
-        L.require_f32(ts[3])
-        Q = ts[0].shape[0]
-        for t in ts:
-            _require(t.shape == (Q,) and t.is_contiguous(), "the per-query results must be contiguous (Q,) tensors")
-        _require(valid is None or valid.numel() == 1, "valid must be a (1,) int32 device tensor")
+        L.require(isinstance(t["n_true"], torch.Tensor) and t["n_true"].dim() == 1, _WHO, "n_true must be a (Q,) tensor")
+        Q = t["n_true"].shape[0]
         if gallery is None:
             gallery = result["scores"].shape[1] if "scores" in result else max(self.ranks, default=0)
         G = int(gallery)
-        _require(rank_ok(Q, G) and all(r <= G for r in self.ranks),
-                 "Q=%d G=%d ranks=%s: out of range (pcr_rank_ok), or a rank above the gallery" % (Q, G, self.ranks))
+        L.require(rank_ok(Q, G) and all(r <= G for r in self.ranks), _WHO,
+                  "Q=%d G=%d ranks=%s: out of range (pcr_rank_ok), or a rank above the gallery", Q, G, self.ranks)
+        sizes = dict(n_true=Q, first_hit=Q, info=Q, ap=Q, valid=1, counts=3 + len(self.ranks), sums=2)
         p = abi.RankAccParams()
         p.Q, p.G, p.nranks = Q, G, len(self.ranks)
         for i, r in enumerate(self.ranks):
             p.ranks[i] = r
-        p.n_true, p.first_hit, p.info, p.ap = (L._p(t) if Q else None for t in ts)
-        p.valid = L._p(valid)
-        p.counts, p.sums = L._p(self.counts), L._p(self.sums)
+        abi.fill(p, dict(t, valid=valid, counts=self.counts, sums=self.sums), sizes, required=t, who=_WHO)
         L.run.pcr_rank_accumulate(ctypes.byref(p), L.stream_ptr())
 
     def metrics(self):
@@ -224,9 +190,9 @@ def evaluate_retrieval(model, store, split, n=None, seed=0, topk=10, ranks=(1, 5
     num_classes defaults to the store's table's."""
     q_rows, g_rows, q_cls, g_cls, q_ids, g_ids = (np.asarray(a, dtype=np.int32) for a in split)
     Q, G, chunk = len(q_rows), len(g_rows), int(query_chunk)
-    _require(1 <= G <= MAX_GALLERY, "a gallery of %d entries: 1 to PCR_RANK_MAX_GALLERY = %d can be ranked" % (G, MAX_GALLERY))
-    _require(chunk >= 1 and rank_ok(chunk, G, topk), "query_chunk=%d G=%d topk=%d is out of range (pcr_rank_ok)" % (chunk, G, topk))
-    _require(len(q_cls) == Q and len(q_ids) == Q and len(g_cls) == G and len(g_ids) == G, "the split's arrays do not agree")
+    L.require(1 <= G <= MAX_GALLERY, _WHO, "a gallery of %d entries: 1 to PCR_RANK_MAX_GALLERY = %d can be ranked", G, MAX_GALLERY)
+    L.require(chunk >= 1 and rank_ok(chunk, G, topk), _WHO, "query_chunk=%d G=%d topk=%d is out of range (pcr_rank_ok)", chunk, G, topk)
+    L.require(len(q_cls) == Q and len(q_ids) == Q and len(g_cls) == G and len(g_ids) == G, _WHO, "the split's arrays do not agree")
     if num_classes is None:
         num_classes = int(store.table.num_classes) if getattr(store, "table", None) is not None else 8
     n = int(n or store.n)

@@ -25,6 +25,7 @@ NB = len(BUCKETS)
 PAIR_WORDS = 40                  # PCR_STORE_PAIR_WORDS
 INFO_RETRY, INFO_ITEM, INFO_ROW = 1, 2, 4
 POOLS = ("tp", "fp")
+_WHO = "pcr_amd.store"
 
 
 def pair_tables(table, row_of, ids=None):
@@ -143,21 +144,16 @@ class CropStore:
         """rows (B,) int32 -> clouds (B, n, 3) f32, sizes (B,) int32 (pcr_store_gather_f32)"""
         seed_t = _seed_tensor(seed, self.device) if seed is not None else None
         info = self.info if info is None else info
-        L.require_cuda(self.points, rows, keys, rand, seed_t, info)
-        L.require_i32(rows, keys, rand, info)
+        i32 = torch.int32
+        rows = L.tensor(rows, _WHO, "rows", i32, shape=(None,))
         B, n = rows.numel(), int(n)
-        assert rows.dim() == 1 and rows.is_contiguous(), "rows must be a contiguous (B,) tensor"
-        assert keys is None or (keys.shape == (B,) and keys.is_contiguous()), "keys must be a contiguous (B,) tensor"
-        assert rand is None or (rand.numel() == B * n and rand.is_contiguous()), "rand must hold B * n contiguous words"
-        if out is not None:
-            clouds, sizes = out
-            L.require_cuda(clouds, sizes)
-            L.require_f32(clouds)
-            L.require_i32(sizes)
-            assert clouds.shape == (B, n, 3) and clouds.is_contiguous() and sizes.shape == (B,) and sizes.is_contiguous()
-        else:
-            clouds = torch.empty((B, n, 3), dtype=torch.float32, device=self.device)
-            sizes = torch.empty((B,), dtype=torch.int32, device=self.device)
+        keys = L.tensor(keys, _WHO, "keys", i32, shape=(B,), optional=True)
+        rand = L.tensor(rand, _WHO, "rand", i32, numel=B * n, optional=True)
+        info = L.tensor(info, _WHO, "info", i32, numel=1)
+        L.require(out is None or len(out) == 2, _WHO, "out must be (clouds, sizes)")
+        clouds = L.out_tensor(None if out is None else out[0], _WHO, "out[0] (clouds)", torch.float32, (B, n, 3), self.device)
+        sizes = L.out_tensor(None if out is None else out[1], _WHO, "out[1] (sizes)", i32, (B,), self.device)
+        L.require_cuda(self.points, rows, keys, rand, seed_t, info, clouds, sizes)
         L.run.pcr_store_gather_f32(self.points, L.ptr(self.offsets), self.num_rows, rows, keys, rand, L.ptr(seed_t),
                                    clouds, sizes, info, B, n, L.stream_ptr())
         return clouds, sizes
@@ -168,14 +164,14 @@ class CropStore:
             raise L.PcrError("this CropStore was built without an ObjectTable: it holds no pair-rule tables")
         seed_t = _seed_tensor(seed, self.device) if seed is not None else None
         info = self.info if info is None else info
-        L.require_cuda(items, keys, rand, seed_t, info)
-        L.require_i32(items, keys, rand, info)
+        i32 = torch.int32
+        items = L.tensor(items, _WHO, "items", i32, shape=(None,))
         B = items.numel()
-        assert items.dim() == 1 and items.is_contiguous() and keys.shape == (B,) and keys.is_contiguous()
-        assert rand is None or (rand.numel() == B * PAIR_WORDS and rand.is_contiguous())
-        if out is None:
-            out = torch.empty((3, B, 2), dtype=torch.int32, device=self.device)
-        assert out.shape == (3, B, 2) and out.is_contiguous() and out.dtype == torch.int32
+        keys = L.tensor(keys, _WHO, "keys", i32, shape=(B,))
+        rand = L.tensor(rand, _WHO, "rand", i32, numel=B * PAIR_WORDS, optional=True)
+        info = L.tensor(info, _WHO, "info", i32, numel=1)
+        out = L.out_tensor(out, _WHO, "out", i32, (3, B, 2), self.device)
+        L.require_cuda(items, keys, rand, seed_t, info, out)
         L.run.pcr_store_train_pairs_i32(ctypes.byref(self._block), items, keys, rand, L.ptr(seed_t), out[0], out[1],
                                         out[2], info, B, L.stream_ptr())
         return out[0], out[1], out[2]
@@ -244,7 +240,8 @@ class CropStore:
             raise L.PcrError("CropStore.val_batch: no pair list (set_val_pairs)")
         v = self.val
         lo, hi = int(lo), int(hi)
-        assert 0 <= lo <= hi <= v["num_pairs"]
+        L.require(0 <= lo <= hi <= v["num_pairs"], _WHO, "lo, hi = %d, %d must lie in 0 <= lo <= hi <= %d pairs",
+                  lo, hi, v["num_pairs"])
         n = int(self.n if n is None else n)
         B = hi - lo
         clouds, sizes = self.gather(v["rows"][lo:hi].view(-1), n, keys=v["keys"][lo:hi].view(-1),

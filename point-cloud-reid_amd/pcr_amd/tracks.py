@@ -18,9 +18,8 @@ from . import abi
 from . import nms as NMS
 
 
-def _require(ok, what):
-    if not ok:
-        raise L.PcrError("pcr_amd.tracks: " + what)
+_WHO = "pcr_amd.tracks"
+STATE = ("lengths", "boxes", "scores", "labels", "ids", "steps", "misses", "next_id", "info")
 
 
 def bank_ok(C, D, W=9, feat_floats=0, xyz_floats=0):
@@ -29,60 +28,31 @@ def bank_ok(C, D, W=9, feat_floats=0, xyz_floats=0):
 
 
 def _vec(t, dtype, n, name):
-    """a contiguous (n,) device tensor of dtype (int64 labels / lengths are converted on the device), or None"""
-    return L.as_vec(t, dtype, n, name, who="pcr_amd.tracks")
-
-
-def _affine(t, name):
-    """a row-major 3 x 4 affine as the kernels read it: (12,) or (3, 4) float32 on the device, or None (identity)"""
-    if t is None:
-        return None
-    _require(isinstance(t, torch.Tensor), "%s must be a tensor" % name)
-    L.require_cuda(t)
-    L.require_f32(t)
-    _require(t.numel() == 12 and t.is_contiguous(), "%s must be a contiguous (12,) or (3, 4) tensor" % name)
-    return t
+    """a contiguous (n,) tensor of dtype (int64 labels / lengths are converted on the device), or None"""
+    return L.tensor(t, _WHO, name, dtype, shape=(n,), optional=True, cast_int64=dtype is torch.int32, copy=True)
 
 
 def plan(state, track_to_det, det_to_track, det_labels, det_lengths, det_boxes, det_scores, src, det_slot, det_id,
          born=None, kill=None, carry=None, frame_limit=10, replace_all=False, reset_on_match=False, propagate=True):
     """pcr_bank_plan_i32 on explicit tensors.  state = dict(lengths, boxes, scores, labels, ids, steps, misses, next_id,
     info), updated in place; src (C,), det_slot (D,), det_id (D,) are written."""
-    names_i = ("lengths", "labels", "ids", "steps", "misses", "next_id", "info")
-    tensors = [state[k] for k in names_i] + [state["boxes"], state["scores"], track_to_det, det_to_track, det_labels,
-                                             det_lengths, det_boxes, det_scores, src, det_slot, det_id, born, kill, carry]
-    for t in tensors:
-        _require(t is None or isinstance(t, torch.Tensor), "every argument must be a tensor")
-    L.require_cuda(*tensors)
-    L.require_i32(*[state[k] for k in names_i], track_to_det, det_to_track, det_labels, det_lengths, src, det_slot, det_id,
-                  born, kill)
-    L.require_f32(state["boxes"], state["scores"], det_boxes, det_scores, carry)
+    L.require(isinstance(state, dict) and all(k in state for k in STATE), _WHO, "state must hold %s", ", ".join(STATE))
     boxes = state["boxes"]
-    _require(boxes.dim() == 2, "boxes must be (C, W)")
-    C, W = boxes.shape
-    D = det_boxes.shape[0]
-    _require(bank_ok(C, D, W), "C=%d D=%d W=%d is out of range (pcr_bank_ok)" % (C, D, W))
-    _require(int(frame_limit) >= 1, "frame_limit must be at least 1")
-    for k in ("lengths", "labels", "ids", "steps", "misses", "scores"):
-        _require(state[k].shape == (C,) and state[k].is_contiguous(), "state[%r] must be a contiguous (C,) tensor" % k)
-    _require(state["next_id"].numel() == 1 and state["info"].numel() == 1, "next_id and info hold one int each")
-    _require(boxes.is_contiguous() and det_boxes.shape == (D, W) and det_boxes.is_contiguous(),
-             "boxes (C, W) and det_boxes (D, W) must be contiguous and of one width")
-    for t, n, name in ((track_to_det, C, "track_to_det"), (kill, C, "kill"), (src, C, "src"), (det_to_track, D, "det_to_track"),
-                       (det_labels, D, "det_labels"), (det_lengths, D, "det_lengths"), (det_scores, D, "det_scores"),
-                       (born, D, "born"), (det_slot, D, "det_slot"), (det_id, D, "det_id")):
-        _require(t is None or (t.shape == (n,) and t.is_contiguous()), "%s must be a contiguous (%d,) tensor" % (name, n))
-    carry = _affine(carry, "carry")
+    L.require(isinstance(boxes, torch.Tensor) and boxes.dim() == 2, _WHO, "boxes must be (C, W)")
+    L.require(isinstance(det_boxes, torch.Tensor) and det_boxes.dim() == 2, _WHO, "det_boxes must be (D, W)")
+    (C, W), D = boxes.shape, det_boxes.shape[0]
+    L.require(bank_ok(C, D, W), _WHO, "C=%d D=%d W=%d is out of range (pcr_bank_ok)", C, D, W)
+    L.require(int(frame_limit) >= 1, _WHO, "frame_limit must be at least 1")
+    sizes = dict(lengths=C, boxes=C * W, scores=C, labels=C, ids=C, steps=C, misses=C, next_id=1, info=1, track_to_det=C,
+                 det_to_track=D, det_labels=D, det_lengths=D, det_boxes=D * W, det_scores=D, born=D, kill=C, carry=12, src=C,
+                 det_slot=D, det_id=D)
     p = abi.BankParams()
     p.C, p.D, p.W = C, D, W
     p.frame_limit, p.replace_all, p.reset_on_match, p.propagate = int(frame_limit), int(bool(replace_all)), \
         int(bool(reset_on_match)), int(bool(propagate))
-    for k in names_i + ("boxes", "scores"):
-        setattr(p, k, L._p(state[k]))
-    for k, t in (("track_to_det", track_to_det), ("det_to_track", det_to_track), ("det_labels", det_labels),
-                 ("det_lengths", det_lengths), ("det_boxes", det_boxes), ("det_scores", det_scores), ("born", born),
-                 ("kill", kill), ("carry", carry), ("src", src), ("det_slot", det_slot), ("det_id", det_id)):
-        setattr(p, k, L._p(t))
+    abi.fill(p, dict({k: state[k] for k in STATE}, track_to_det=track_to_det, det_to_track=det_to_track,
+                     det_labels=det_labels, det_lengths=det_lengths, det_boxes=det_boxes, det_scores=det_scores, born=born,
+                     kill=kill, carry=carry, src=src, det_slot=det_slot, det_id=det_id), sizes, who=_WHO)
     L.run.pcr_bank_plan_i32(ctypes.byref(p), L.stream_ptr())
     return src, det_slot, det_id
 
@@ -90,21 +60,19 @@ def plan(state, track_to_det, det_to_track, det_labels, det_lengths, det_boxes, 
 def move(src, det_feats, det_xyz, feats, xyz):
     """pcr_bank_move_f32: feats[s] = det_feats[src[s]] and xyz[s] = det_xyz[src[s]] for every slot with src[s] in [0, D);
     feats (C, ...), det_feats (D, ...) of one row shape, likewise xyz; rows must be dense (a view may start anywhere)"""
-    for t in (src, det_feats, det_xyz, feats, xyz):
-        _require(isinstance(t, torch.Tensor), "every argument must be a tensor")
-    L.require_cuda(src, det_feats, det_xyz, feats, xyz)
-    L.require_i32(src)
-    L.require_f32(det_feats, det_xyz, feats, xyz)
+    f32 = torch.float32
+    feats, det_feats = L.tensor(feats, _WHO, "feats", f32), L.tensor(det_feats, _WHO, "det_feats", f32)
+    xyz, det_xyz = L.tensor(xyz, _WHO, "xyz", f32), L.tensor(det_xyz, _WHO, "det_xyz", f32)
+    L.require(feats.dim() >= 1 and det_feats.dim() >= 1, _WHO, "feats and det_feats must have rows")
     C, D = feats.shape[0], det_feats.shape[0]
-    _require(src.shape == (C,) and src.is_contiguous(), "src must be a contiguous (C,) tensor")
-    _require(xyz.shape[0] == C and det_xyz.shape[0] == D, "feats / xyz must agree on C, det_feats / det_xyz on D")
-    _require(feats.shape[1:] == det_feats.shape[1:] and xyz.shape[1:] == det_xyz.shape[1:],
-             "the bank's rows and the detections' rows must have one shape")
-    for t in (det_feats, det_xyz, feats, xyz):
-        _require(t.is_contiguous(), "a tensor is not contiguous")
+    src = L.tensor(src, _WHO, "src", torch.int32, shape=(C,))
+    L.require(xyz.shape[:1] == (C,) and det_xyz.shape[:1] == (D,), _WHO, "feats / xyz must agree on C, det_feats / det_xyz on D")
+    L.require(feats.shape[1:] == det_feats.shape[1:] and xyz.shape[1:] == det_xyz.shape[1:], _WHO,
+              "the bank's rows and the detections' rows must have one shape")
     ff = feats[0].numel() if C else 0
     xf = xyz[0].numel() if C else 0
-    _require(bank_ok(C, D, 7, ff, xf), "C=%d D=%d rows of %d and %d floats are out of range (pcr_bank_ok)" % (C, D, ff, xf))
+    L.require(bank_ok(C, D, 7, ff, xf), _WHO, "C=%d D=%d rows of %d and %d floats are out of range (pcr_bank_ok)", C, D, ff, xf)
+    L.require_cuda(src, det_feats, det_xyz, feats, xyz)
     L.run.pcr_bank_move_f32(src, det_feats, det_xyz, feats, xyz, C, D, ff, xf, L.stream_ptr())
 
 
@@ -112,36 +80,28 @@ def distances(boxes, ids, det_boxes, carry_inv=None, out=None):
     """pcr_bank_dist_f32: boxes (C, W), ids (C,), det_boxes (D, W) -> (C, D) float32, every element written: the BEV
     distance between a stored centre and a detection's centre taken back into the previous frame by carry_inv (3 x 4,
     None = identity); 0 in a free slot's row.  It is the `dist=` operand of associate.association_cost."""
-    for t in (boxes, ids, det_boxes):
-        _require(isinstance(t, torch.Tensor), "every argument must be a tensor")
-    L.require_cuda(boxes, ids, det_boxes, carry_inv, out)
-    L.require_f32(boxes, det_boxes, carry_inv, out)
-    L.require_i32(ids)
-    _require(boxes.dim() == 2 and det_boxes.dim() == 2 and boxes.shape[1] == det_boxes.shape[1],
-             "boxes (C, W) and det_boxes (D, W) must be of one width")
+    f32 = torch.float32
+    boxes = L.tensor(boxes, _WHO, "boxes", f32, shape=(None, None))
     C, W = boxes.shape
+    det_boxes = L.tensor(det_boxes, _WHO, "det_boxes", f32, shape=(None, W))
     D = det_boxes.shape[0]
-    _require(bank_ok(C, D, W), "C=%d D=%d W=%d is out of range (pcr_bank_ok)" % (C, D, W))
-    _require(boxes.is_contiguous() and det_boxes.is_contiguous() and ids.shape == (C,) and ids.is_contiguous(),
-             "a tensor has the wrong shape or is not contiguous")
-    carry_inv = _affine(carry_inv, "carry_inv")
-    if out is None:
-        out = torch.empty((C, D), dtype=torch.float32, device=boxes.device)
-    _require(out.shape == (C, D) and out.is_contiguous(), "out must be a contiguous (C, D) tensor")
+    ids = L.tensor(ids, _WHO, "ids", torch.int32, shape=(C,))
+    carry_inv = L.tensor(carry_inv, _WHO, "carry_inv", f32, numel=12, optional=True)
+    L.require(bank_ok(C, D, W), _WHO, "C=%d D=%d W=%d is out of range (pcr_bank_ok)", C, D, W)
+    out = L.out_tensor(out, _WHO, "out", f32, (C, D), boxes.device)
+    L.require_cuda(boxes, ids, det_boxes, carry_inv, out)
     L.run.pcr_bank_dist_f32(boxes, ids, det_boxes, carry_inv, out, C, D, W, L.stream_ptr())
     return out
 
 
 def retire(mask, labels, ids, lengths):
     """pcr_bank_retire_i32: the active slots with mask != 0 are freed"""
-    for t in (mask, labels, ids, lengths):
-        _require(isinstance(t, torch.Tensor), "every argument must be a tensor")
-    L.require_cuda(mask, labels, ids, lengths)
-    L.require_i32(mask, labels, ids, lengths)
+    ids = L.tensor(ids, _WHO, "ids", torch.int32, shape=(None,))
     C = ids.shape[0]
-    _require(bank_ok(C, 0), "C=%d is out of range (pcr_bank_ok)" % C)
-    for t in (mask, labels, ids, lengths):
-        _require(t.shape == (C,) and t.is_contiguous(), "mask, labels, ids and lengths must be contiguous (C,) tensors")
+    mask, labels, lengths = (L.tensor(t, _WHO, name, torch.int32, shape=(C,))
+                             for t, name in ((mask, "mask"), (labels, "labels"), (lengths, "lengths")))
+    L.require(bank_ok(C, 0), _WHO, "C=%d is out of range (pcr_bank_ok)", C)
+    L.require_cuda(mask, labels, ids, lengths)
     L.run.pcr_bank_retire_i32(mask, labels, ids, lengths, C, L.stream_ptr())
 
 
@@ -158,18 +118,18 @@ class TrackBank:
     Every method launches on the current stream, returns fixed-shape tensors and never reads the device.  The tensors
     `update` returns are the bank's own and are overwritten by the next update."""
 
-    STATE = ("lengths", "boxes", "scores", "labels", "ids", "steps", "misses", "next_id", "info")
+    STATE = STATE
 
     def __init__(self, capacity, max_dets, feat_shape=(64, 128), box_width=9, device=None):
         C, D = int(capacity), int(max_dets)
-        _require(len(feat_shape) == 2 and min(feat_shape) >= 1, "feat_shape must be (channels, points)")
+        L.require(len(feat_shape) == 2 and min(feat_shape) >= 1, _WHO, "feat_shape must be (channels, points)")
         ch, n = int(feat_shape[0]), int(feat_shape[1])
         device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         if device.type != "cuda":
             raise L.PcrError("pcr_amd.tracks: the bank lives on an MI355X device (got %s); there is no CPU fallback" % device)
-        _require(bank_ok(C, D, box_width, ch * n, n * 3),
-                 "capacity=%d max_dets=%d box_width=%d feat_shape=%s is out of range (pcr_bank_ok)"
-                 % (C, D, box_width, tuple(feat_shape)))
+        L.require(bank_ok(C, D, box_width, ch * n, n * 3), _WHO,
+                  "capacity=%d max_dets=%d box_width=%d feat_shape=%s is out of range (pcr_bank_ok)",
+                  C, D, box_width, tuple(feat_shape))
         self.capacity, self.max_dets, self.box_width, self.feat_shape, self.device = C, D, int(box_width), (ch, n), device
         f32 = dict(dtype=torch.float32, device=device)
         i32 = dict(dtype=torch.int32, device=device)
@@ -199,9 +159,9 @@ class TrackBank:
 
     def distances(self, det_boxes, carry_inv=None):
         """det_boxes (D <= max_dets, box_width) -> (capacity, D): see `distances`; the bank's own buffer when D == max_dets"""
-        _require(isinstance(det_boxes, torch.Tensor) and det_boxes.dim() == 2, "det_boxes must be a (D, W) tensor")
+        L.require(isinstance(det_boxes, torch.Tensor) and det_boxes.dim() == 2, _WHO, "det_boxes must be a (D, W) tensor")
         D = det_boxes.shape[0]
-        _require(D <= self.max_dets, "%d detections, the bank was made for %d" % (D, self.max_dets))
+        L.require(D <= self.max_dets, _WHO, "%d detections, the bank was made for %d", D, self.max_dets)
         return distances(self.boxes, self.ids, det_boxes, carry_inv, out=self._dist if D == self.max_dets else None)
 
     def update(self, assignment, dets, born=None, kill=None, carry=None, frame_limit=10, replace_all=False,
@@ -221,22 +181,19 @@ class TrackBank:
         else:
             t2d, d2t = assignment
         C = self.capacity
-        boxes = dets["boxes"]
-        _require(isinstance(boxes, torch.Tensor) and boxes.dim() == 2, "dets['boxes'] must be a (D, W) tensor")
-        L.require_cuda(boxes)
+        boxes = L.tensor(dets["boxes"], _WHO, "dets['boxes']", torch.float32, shape=(None, self.box_width), copy=True)
         D = boxes.shape[0]
-        _require(D <= self.max_dets, "%d detections, the bank was made for %d" % (D, self.max_dets))
-        _require(boxes.shape[1] == self.box_width, "dets['boxes'] must be (D, %d)" % self.box_width)
+        L.require(D <= self.max_dets, _WHO, "%d detections, the bank was made for %d", D, self.max_dets)
         labels, lengths = _vec(dets["labels"], torch.int32, D, "dets['labels']"), _vec(dets["lengths"], torch.int32, D, "dets['lengths']")
         scores = _vec(dets["scores"], torch.float32, D, "dets['scores']")
         t2d, d2t = _vec(t2d, torch.int32, C, "track_to_det"), _vec(d2t, torch.int32, D, "det_to_track")
         born, kill = _vec(born, torch.int32, D, "born"), _vec(kill, torch.int32, C, "kill")
         feats, xyz = dets.get("feats"), dets.get("xyz")
-        _require((feats is None) == (xyz is None), "dets['feats'] and dets['xyz'] come together")
+        L.require((feats is None) == (xyz is None), _WHO, "dets['feats'] and dets['xyz'] come together")
         if feats is None:
             feats, xyz = self.det_feats[:D], self.det_xyz[:D]
         det_slot, det_id = self.det_slot[:D], self.det_id[:D]
-        plan(self.state(), t2d, d2t, labels, lengths, boxes.contiguous(), scores, self.src, det_slot, det_id, born=born,
+        plan(self.state(), t2d, d2t, labels, lengths, boxes, scores, self.src, det_slot, det_id, born=born,
              kill=kill, carry=carry, frame_limit=frame_limit, replace_all=replace_all, reset_on_match=reset_on_match,
              propagate=propagate)
         move(self.src, feats, xyz, self.feats, self.xyz)

@@ -22,15 +22,7 @@ KINDS = ("det_match", "det_newborn", "det_false_positive", "track_false_negative
 STATS = 24                                                  # PCR_TRUTH_STATS
 TOTAL_GT, TOTAL_CORRECT = 15, 16
 MOT = dict(frames=17, gt_total=18, tp=19, fp=20, fn=21, switches=22, untracked=23)
-_INPUTS = ("ids", "slot_gt", "slot_tte", "gt_last", "stats", "col4row", "row4col", "info", "cost", "thresh", "gt_labels",
-           "gt_ids", "gt_tte", "det_labels", "track_to_det", "det_to_track", "born", "kill", "det_gt", "true_t2d",
-           "true_d2t", "det_truth", "track_truth", "det_slot", "det_id")
-_FLOATS = ("cost", "thresh")
-
-
-def _require(ok, what):
-    if not ok:
-        raise L.PcrError("pcr_amd.truth: " + what)
+_WHO = "pcr_amd.truth"
 
 
 def truth_ok(C, D, G, W=9, gt_cap=1):
@@ -42,23 +34,17 @@ def cost(det_boxes, det_labels, gt_boxes, gt_labels, gt_ids, gt_cap, iou=None, o
     """pcr_truth_cost_f32: det_boxes (D, W), det_labels (D,), gt_boxes (G, W), gt_labels / gt_ids (G,) [, iou (D, G)] ->
     cost (D, G) float32, every element written: the BEV centre distance (or -iou) plus 10000 where the labels differ or a
     side is padding (a label < 0, a ground-truth id outside [0, gt_cap))"""
-    tensors = (det_boxes, det_labels, gt_boxes, gt_labels, gt_ids, iou, out)
-    for t in tensors:
-        _require(t is None or isinstance(t, torch.Tensor), "every argument must be a tensor")
-    L.require_cuda(*tensors)
-    L.require_f32(det_boxes, gt_boxes, iou, out)
-    L.require_i32(det_labels, gt_labels, gt_ids)
-    _require(det_boxes.dim() == 2 and gt_boxes.dim() == 2 and det_boxes.shape[1] == gt_boxes.shape[1],
-             "det_boxes (D, W) and gt_boxes (G, W) must be of one width")
-    (D, W), G = det_boxes.shape, gt_boxes.shape[0]
-    _require(truth_ok(1, D, G, W, gt_cap), "D=%d G=%d W=%d gt_cap=%d is out of range (pcr_truth_ok)" % (D, G, W, gt_cap))
-    _require(det_boxes.is_contiguous() and gt_boxes.is_contiguous(), "the boxes must be contiguous")
-    for t, n, name in ((det_labels, D, "det_labels"), (gt_labels, G, "gt_labels"), (gt_ids, G, "gt_ids")):
-        _require(t.shape == (n,) and t.is_contiguous(), "%s must be a contiguous (%d,) tensor" % (name, n))
-    _require(iou is None or (iou.shape == (D, G) and iou.is_contiguous()), "iou must be a contiguous (D, G) tensor")
-    if out is None:
-        out = torch.empty((D, G), dtype=torch.float32, device=det_boxes.device)
-    _require(out.shape == (D, G) and out.is_contiguous(), "out must be a contiguous (D, G) tensor")
+    f32, i32 = torch.float32, torch.int32
+    det_boxes = L.tensor(det_boxes, _WHO, "det_boxes", f32, shape=(None, None))
+    D, W = det_boxes.shape
+    gt_boxes = L.tensor(gt_boxes, _WHO, "gt_boxes", f32, shape=(None, W))
+    G = gt_boxes.shape[0]
+    det_labels = L.tensor(det_labels, _WHO, "det_labels", i32, shape=(D,))
+    gt_labels, gt_ids = L.tensor(gt_labels, _WHO, "gt_labels", i32, shape=(G,)), L.tensor(gt_ids, _WHO, "gt_ids", i32, shape=(G,))
+    iou = L.tensor(iou, _WHO, "iou", f32, shape=(D, G), optional=True)
+    L.require(truth_ok(1, D, G, W, gt_cap), _WHO, "D=%d G=%d W=%d gt_cap=%d is out of range (pcr_truth_ok)", D, G, W, gt_cap)
+    out = L.out_tensor(out, _WHO, "out", f32, (D, G), det_boxes.device)
+    L.require_cuda(det_boxes, det_labels, gt_boxes, gt_labels, gt_ids, iou, out)
     L.run.pcr_truth_cost_f32(det_boxes, det_labels, gt_boxes, gt_labels, gt_ids, iou, out, D, G, W, int(gt_cap),
                              L.stream_ptr())
     return out
@@ -66,30 +52,16 @@ def cost(det_boxes, det_labels, gt_boxes, gt_labels, gt_ids, gt_cap, iou=None, o
 
 def _params(t, gt_cap, skip_empty, forced=False):
     """the parameter block over a dict of explicit tensors (None = NULL); shapes are read off ids, det_labels, gt_labels"""
-    for k in t:
-        _require(k in _INPUTS, "unknown tensor %r" % k)
-    tensors = [t.get(k) for k in _INPUTS]
-    for x in tensors:
-        _require(x is None or isinstance(x, torch.Tensor), "every argument must be a tensor")
-    L.require_cuda(*tensors)
-    L.require_f32(*[t.get(k) for k in _FLOATS])
-    L.require_i32(*[t.get(k) for k in _INPUTS if k not in _FLOATS])
     for k in ("ids", "det_labels", "gt_labels"):
-        _require(t.get(k) is not None and t[k].dim() == 1, "%s must be a 1-D tensor" % k)
+        L.require(isinstance(t.get(k), torch.Tensor) and t[k].dim() == 1, _WHO, "%s must be a 1-D tensor", k)
     C, D, G = t["ids"].shape[0], t["det_labels"].shape[0], t["gt_labels"].shape[0]
-    _require(truth_ok(C, D, G, 7, gt_cap), "C=%d D=%d G=%d gt_cap=%d is out of range (pcr_truth_ok)" % (C, D, G, gt_cap))
+    L.require(truth_ok(C, D, G, 7, gt_cap), _WHO, "C=%d D=%d G=%d gt_cap=%d is out of range (pcr_truth_ok)", C, D, G, gt_cap)
     sizes = dict(ids=C, slot_gt=C, slot_tte=C, gt_last=int(gt_cap), stats=STATS, col4row=D, row4col=G, info=1, cost=D * G,
                  thresh=1, gt_labels=G, gt_ids=G, gt_tte=G, det_labels=D, track_to_det=C, det_to_track=D, born=D, kill=C,
                  det_gt=D, true_t2d=C, true_d2t=D, det_truth=D, track_truth=C, det_slot=D, det_id=D)
     p = abi.TruthParams()
     p.C, p.D, p.G, p.gt_cap, p.skip_empty, p.forced = C, D, G, int(gt_cap), int(bool(skip_empty)), int(bool(forced))
-    for k in _INPUTS:
-        x = t.get(k)
-        if x is not None:
-            _require(x.numel() == sizes[k] and x.is_contiguous(), "%s must be contiguous and hold %d elements, got %s"
-                     % (k, sizes[k], tuple(x.shape)))
-        setattr(p, k, L._p(x) if x is not None and x.numel() else None)
-    return p
+    return abi.fill(p, t, sizes, who=_WHO)
 
 
 def decide(tensors, gt_cap, skip_empty=True, forced=False):
@@ -153,11 +125,11 @@ class TruthBook:
 
     def __init__(self, bank, max_gt, gt_cap, kind="centre", thresh=2.0, skip_empty=True):
         from . import tracks as TR
-        _require(isinstance(bank, TR.TrackBank), "bank must be a pcr_amd.tracks.TrackBank")
-        _require(kind in ("centre", "iou"), "kind must be 'centre' or 'iou', got %r" % (kind,))
+        L.require(isinstance(bank, TR.TrackBank), _WHO, "bank must be a pcr_amd.tracks.TrackBank")
+        L.require(kind in ("centre", "iou"), _WHO, "kind must be 'centre' or 'iou', got %r", kind)
         C, D, G = bank.capacity, bank.max_dets, int(max_gt)
-        _require(truth_ok(C, D, G, bank.box_width, gt_cap),
-                 "capacity=%d max_dets=%d max_gt=%d gt_cap=%d is out of range (pcr_truth_ok)" % (C, D, G, gt_cap))
+        L.require(truth_ok(C, D, G, bank.box_width, gt_cap), _WHO,
+                  "capacity=%d max_dets=%d max_gt=%d gt_cap=%d is out of range (pcr_truth_ok)", C, D, G, gt_cap)
         self.bank, self.max_gt, self.gt_cap, self.kind, self.skip_empty = bank, G, int(gt_cap), kind, bool(skip_empty)
         dev = bank.device
         i32 = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)
@@ -183,20 +155,17 @@ class TruthBook:
 
     def _load(self, gt):
         """the frame's ground truth into the book's buffers, padded to max_gt with label -1"""
-        boxes = gt["boxes"]
-        _require(isinstance(boxes, torch.Tensor) and boxes.dim() == 2 and boxes.shape[1] == self.bank.box_width,
-                 "gt['boxes'] must be (G, %d)" % self.bank.box_width)
+        boxes = L.tensor(gt["boxes"], _WHO, "gt['boxes']", torch.float32, shape=(None, self.bank.box_width), copy=True)
         n = boxes.shape[0]
-        _require(n <= self.max_gt, "%d ground-truth boxes, the book was made for %d" % (n, self.max_gt))
+        L.require(n <= self.max_gt, _WHO, "%d ground-truth boxes, the book was made for %d", n, self.max_gt)
         L.require_cuda(boxes)
-        L.require_f32(boxes)
         self.gt_boxes.zero_()
         self.gt_boxes[:n].copy_(boxes)
         for k, buf in (("labels", self.gt_labels), ("ids", self.gt_ids), ("tte", self.gt_tte)):
             t = gt[k]
-            _require(isinstance(t, torch.Tensor) and t.shape == (n,), "gt[%r] must be a (%d,) tensor" % (k, n))
+            L.require(isinstance(t, torch.Tensor) and t.shape == (n,), _WHO, "gt[%r] must be a (%d,) tensor", k, n)
             L.require_cuda(t)
-            _require(t.dtype in (torch.int32, torch.int64), "gt[%r] must be an integer tensor" % k)
+            L.require(t.dtype in (torch.int32, torch.int64), _WHO, "gt[%r] must be an integer tensor", k)
             buf.fill_(-1)
             buf[:n].copy_(t)
 
@@ -205,7 +174,7 @@ class TruthBook:
         dict(boxes (G <= max_gt, W), labels, ids, tte (G,)) -> (col4row (max_dets,), row4col (max_gt,), info (1,)) of the
         linear assignment over the cost (max_dets, max_gt), which stays in `self.cost`"""
         D, W = self.bank.max_dets, self.bank.box_width
-        _require(isinstance(det_boxes, torch.Tensor) and det_boxes.shape == (D, W), "det_boxes must be (%d, %d)" % (D, W))
+        L.require(isinstance(det_boxes, torch.Tensor) and det_boxes.shape == (D, W), _WHO, "det_boxes must be (%d, %d)", D, W)
         self._load(gt)
         iou = None
         if self.kind == "iou":
@@ -234,7 +203,7 @@ class TruthBook:
         else:
             t2d, d2t = assignment
         C, D = self.bank.capacity, self.bank.max_dets
-        vec = lambda t, n, name: L.as_vec(t, torch.int32, n, name, who="pcr_amd.truth")
+        vec = lambda t, n, name: L.tensor(t, _WHO, name, torch.int32, shape=(n,), optional=True, cast_int64=True, copy=True)
         det_labels = vec(det_labels, D, "det_labels")
         t2d, d2t = vec(t2d, C, "track_to_det"), vec(d2t, D, "det_to_track")
         born, kill = vec(born, D, "born"), vec(kill, C, "kill")
@@ -257,7 +226,7 @@ class TruthBook:
     def record(self, det_slot, det_id):
         """pcr_truth_record_i32 AFTER `bank.update` and `bank.suppress`: det_slot / det_id (max_dets,) as the update
         returned them.  The book moves on one frame and the MOT counters are added to."""
-        _require(self._det_labels is not None, "record follows decide")
+        L.require(self._det_labels is not None, _WHO, "record follows decide")
         t = self._tensors(self._det_labels)
         t.update(det_slot=det_slot, det_id=det_id)
         record(t, self.gt_cap)

@@ -38,17 +38,20 @@ def header_text():
     return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "pcr.h")).read(), flags=re.S)
 
 
-def header_structs():
-    """{struct name: [field names in order]} of every `typedef struct NAME { ... } NAME;` of the header"""
+def header_structs(types=False):
+    """{struct name: [field names in order]} of every `typedef struct NAME { ... } NAME;` of the header; with types, {struct
+    name: {field: what a pointer field points at ("float", "int", "double", "long long", "void"), None for a scalar}}"""
     out = {}
     for name, body in re.findall(r"typedef struct (\w+) \{(.*?)\} \w+;", header_text(), flags=re.S):
-        names = []
+        names, elem = [], {}
         for decl in body.split(";"):
+            ty = re.match(r"\s*(?:const\s+)?(long long|\w+)", decl)
             for d in decl.split(","):
-                m = re.search(r"(\w+)\s*(?:\[\d+\])?\s*$", d)
+                m = re.search(r"(\*?)\s*(?:const\s+)?(\w+)\s*(?:\[\d+\])?\s*$", d)
                 if m:
-                    names.append(m.group(1))
-        out[name] = names
+                    names.append(m.group(2))
+                    elem[m.group(2)] = ty.group(1) if m.group(1) else None
+        out[name] = elem if types else names
     return out
 
 
@@ -92,6 +95,28 @@ def test_signature_table_matches_the_header():
         restype, argtypes = abi.prototype(abi.SIGNATURES[name])
         assert len(argtypes) == len(want)
     assert (n_float, n_long) == (22, 5)                  # (what the header holds today: the kinds are really told apart)
+
+
+def test_block_pointer_fields_carry_the_header_element_types():
+    """ELEM of every parameter block (what `abi.fill` checks a tensor's dtype against) is the header's pointer type, field
+    by field; a scalar field has no entry"""
+    import torch
+    from pcr_amd import abi
+    kinds = {"float": torch.float32, "int": torch.int32, "double": torch.float64, "long long": torch.int64, "void": None}
+    fields = header_structs(types=True)
+    total = dict.fromkeys(kinds, 0)
+    for s, elem in fields.items():
+        for f, ty in elem.items():
+            if ty is not None:
+                assert ty in kinds, (s, f, ty)
+                total[ty] += 1
+        if s in abi.BLOCKS:
+            want = {f: kinds[ty] for f, ty in elem.items() if ty is not None}
+            assert abi.BLOCKS[s].ELEM == want, (s, {f: (abi.BLOCKS[s].ELEM.get(f, "scalar"), want.get(f, "scalar"))
+                                                    for f in set(want) | set(abi.BLOCKS[s].ELEM)
+                                                    if abi.BLOCKS[s].ELEM.get(f, "scalar") != want.get(f, "scalar")})
+    # (what the header holds today, the two device-table records included: the regex misses no kind)
+    assert total == {"float": 177, "int": 105, "double": 4, "long long": 1, "void": 1}, total
 
 
 def _host_clang():

@@ -113,6 +113,38 @@ def test_pair_rule_equals_the_restatement(hand_store):
     store.info.zero_()
 
 
+def test_gather_and_train_pairs_refuse_a_bad_argument(hand_store):
+    """B = 2, n = 8: strided rows, keys of the wrong length and an out of the wrong shape are a PcrError that names the
+    argument, not an assert; nothing is launched and the info word stays clear"""
+    store, _ = hand_store
+    store.info.zero_()
+    B, n = 2, 8
+    rows, keys = i32(np.zeros(B)), i32(np.arange(B))
+    wide = i32(np.zeros(2 * B))
+    clouds, sizes = torch.zeros((B, n, 3), device=DEV), torch.zeros(B, dtype=torch.int32, device=DEV)
+    for kw, what in ((dict(rows=wide[::2]), "rows must be contiguous"), (dict(keys=i32(np.arange(B + 1))), r"keys must be \(2,\)"),
+                     (dict(out=(clouds[:, :n - 1], sizes)), r"out\[0\] \(clouds\) must be \(2, 8, 3\)"),
+                     (dict(out=(clouds, i32(np.zeros(B + 1)))), r"out\[1\] \(sizes\) must be \(2,\)"),
+                     (dict(rows=rows.long()), "rows must be a torch.int32 tensor"),
+                     (dict(rows=rows.cpu()), "MI355X device tensor")):
+        a = dict(dict(rows=rows, keys=keys), **kw)
+        with pytest.raises(L.PcrError, match=what):
+            store.gather(a["rows"], n, keys=a["keys"], seed=1, out=a.get("out"))
+    true = int(store.table.true_index[0])
+    items = i32(np.full(B, true))
+    for kw, what in ((dict(items=i32(np.full(2 * B, true))[::2]), "items must be contiguous"),
+                     (dict(keys=i32(np.arange(B + 1))), r"keys must be \(2,\)"),
+                     (dict(out=torch.zeros((3, B, 3), dtype=torch.int32, device=DEV)), r"out must be \(3, 2, 2\)"),
+                     (dict(out=torch.zeros((3, B, 2), device=DEV)), "out must be a torch.int32 tensor"),
+                     (dict(rand=i32(np.zeros(B * ST.PAIR_WORDS - 1))), "rand must hold 80 elements")):
+        a = dict(dict(items=items, keys=keys), **kw)
+        with pytest.raises(L.PcrError, match=what):
+            store.train_pairs(a["items"], a["keys"], 3, rand=a.get("rand"), out=a.get("out"))
+    assert store.flags() == 0
+    got = store.gather(rows, n, keys=keys, seed=1, out=(clouds, sizes))       # and the right call still goes through
+    assert got[0] is clouds and got[1] is sizes
+
+
 def test_thirty_two_failed_attempts_take_the_first_other_entry(hand_store):
     """the kernel is fed the same words as the restatement through its `rand` input: every candidate pick hits the item's
     own object"""

@@ -115,6 +115,31 @@ def test_cost_decide_record_equal_the_restatement(C, D, G, masks):
         assert seen == 0
 
 
+def test_the_filler_writes_device_addresses_and_nulls():
+    """abi.fill over pcr_truth on device tensors at C = 4, D = 3, G = 2: every field holds its tensor's address; an empty
+    tensor (D = 0) and a None are NULL; a scalar field is not touched"""
+    from pcr_amd import abi
+    i32 = lambda n: torch.zeros(n, dtype=torch.int32, device="cuda")     # noqa: E731
+    f32 = lambda *s: torch.zeros(s, device="cuda")                       # noqa: E731
+    for C, D, G in ((4, 3, 2), (4, 0, 2)):
+        sizes = dict(ids=C, slot_gt=C, slot_tte=C, gt_last=8, stats=24, col4row=D, row4col=G, info=1, cost=D * G, thresh=1,
+                     gt_labels=G, gt_ids=G, gt_tte=G, det_labels=D, track_to_det=C, det_to_track=D, born=D, kill=C,
+                     det_gt=D, true_t2d=C, true_d2t=D, det_truth=D, track_truth=C, det_slot=D, det_id=D)
+        assert set(sizes) == set(abi.TruthParams.ELEM)
+        t = {k: (f32(D, G) if k == "cost" else f32(1) if k == "thresh" else i32(n)) for k, n in sizes.items()}
+        t["born"] = t["kill"] = None
+        p = abi.TruthParams()
+        p.C, p.D, p.G = C, D, G
+        assert abi.fill(p, t, sizes, required=("ids",), who="test") is p
+        assert (p.C, p.D, p.G) == (C, D, G)
+        for k, x in t.items():
+            want = x.data_ptr() if x is not None and x.numel() else None
+            assert getattr(p, k) == want, (k, D)
+            assert (want is None) == (k in ("born", "kill") or sizes[k] == 0), (k, D)
+    with pytest.raises(Exception, match="cost must be a torch.float32 tensor"):
+        abi.fill(abi.TruthParams(), dict(cost=f32(3, 2).double()), sizes, who="test")
+
+
 def test_book_matches_by_iou_through_its_own_buffers():
     """TruthBook(kind="iou"): nearest_bev + iou_bev(kind="axis") into the book's buffers, the threshold held negated"""
     from pcr_amd import tracks as T

@@ -1242,6 +1242,7 @@ static int dense_launch(const float *x, const float *wp, long w_bstride, const f
   if (!x || !wp || !y || B < 0 || cin < 1 || cout < 1 || L < 1) return PCR_ERR_INVALID;
   if (B == 0) return PCR_OK;
   if (B > 65535) return PCR_ERR_INVALID;
+  pcr_note_arith(PCR_PREC_F32);   // (every form below is the f32 unit)
   DenseArgs a{x, wp, scale, shift, y, cin, cout, L, act, w_bstride, x_pm, gn_gs, res};
   if (!w_bstride && !x_pm && !gn_gs && dense_rw_ok(cin, cout, L) && !pcr_tune_str("PCR_DENSE_NO_RW"))
     return dense_rw_launch<false>(a, B, pcr_s(stream));
@@ -1290,6 +1291,7 @@ static int dense_bf_launch(const float *x, const float *wp_bf, const float *scal
     return PCR_ERR_INVALID;
   if (B == 0) return PCR_OK;
   if (B > 65535) return PCR_ERR_INVALID;
+  pcr_note_arith(precision);   // (both forms below run the requested bf16 mode)
   DenseArgs a{x, wp_bf, scale, shift, y, cin, cout, L, act, 0, 0, gn_gs, res};
   if ((cin == 256 || cin == 512 || cin == 1024) && L % kPcT == 0 && (reinterpret_cast<size_t>(x) & 15) == 0 && cout > 128 &&
       (size_t)cin * L * 4 < 0x7FFFFFFFull &&
@@ -1428,6 +1430,7 @@ PCR_EXPORT int pcr_dense_max_f32(const float *x, const float *wp, const float *s
   if (!x || !wp || !out || B < 0 || !pcr_dense_max_ok(cin, cout, L)) return PCR_ERR_INVALID;
   if (B == 0) return PCR_OK;
   if (B > 65535) return PCR_ERR_INVALID;
+  pcr_note_arith(PCR_PREC_F32);
   DenseArgs a{x, wp, scale, shift, out, cin, cout, L, act, 0, 0, 0, nullptr};
   if (dense_rw_ok(cin, cout, L) && !pcr_tune_str("PCR_DENSE_NO_RW")) return dense_rw_launch<true>(a, B, pcr_s(stream));
   const size_t lds = ((size_t)ceil8(cin) * 65 + 512) * sizeof(float);

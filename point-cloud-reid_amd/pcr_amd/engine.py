@@ -666,7 +666,7 @@ def dense(x, wp, cout, scale=None, shift=None, act=0):
     if PRECISION != "f32" and bf is not None and not x_pm and lib.pcr_dense_prec_ok(cin, cout, Ln):
         # the wide per-point layers (PointNet convs, DGCNN conv5, LinearRes rows) on the bf16 matrix core
         with _prof("dense[cin=%d,cout=%d,L=%d]" % (cin, cout, Ln), 2.0 * B * Ln * cin * cout, 4.0 * B * Ln * (cin + cout),
-                   arith=PRECISION):
+                   arith="lib"):
             L.run.pcr_dense_prec_f32(x, bf, scale, shift, y, B, cin, cout, Ln, act, PRECISIONS[PRECISION],
                                      L.stream_ptr())
         return y
@@ -679,6 +679,6 @@ def dense(x, wp, cout, scale=None, shift=None, act=0):
         return y
     fn = L.run.pcr_dense_xpm_f32 if x_pm else L.run.pcr_dense_f32
     with _prof("dense[cin=%d,cout=%d,L=%d]" % (cin, cout, Ln), 2.0 * B * Ln * cin * cout, 4.0 * B * Ln * (cin + cout),
-               arith="f32"):
+               arith="lib"):
         fn(x, wp, scale, shift, y, B, cin, cout, Ln, act, L.stream_ptr())
     return y

@@ -78,12 +78,12 @@ def dense_gn(x, wp, cout, gn, res=None, relu=False):
     bf = getattr(wp, "_pcr_bf", None)
     if _E.PRECISION != "f32" and bf is not None and L.load().pcr_dense_prec_ok(cin, cout, Ln):
         with _E._prof("dense_gn[cin=%d,cout=%d,L=%d]" % (cin, cout, Ln), 2.0 * B * Ln * cin * cout,
-                      4.0 * B * Ln * (cin + cout * (2 if res is not None else 1)), arith=_E.PRECISION):
+                      4.0 * B * Ln * (cin + cout * (2 if res is not None else 1)), arith="lib"):
             L.run.pcr_dense_gn_prec_f32(x, bf, g, b, res, y, B, cin, cout, Ln, gn.num_groups, 1 if relu else 0,
                                         _E.PRECISIONS[_E.PRECISION], L.stream_ptr())
         return y
     with _E._prof("dense_gn[cin=%d,cout=%d,L=%d]" % (cin, cout, Ln), 2.0 * B * Ln * cin * cout,
-                  4.0 * B * Ln * (cin + cout * (2 if res is not None else 1)), arith="f32"):
+                  4.0 * B * Ln * (cin + cout * (2 if res is not None else 1)), arith="lib"):
         L.run.pcr_dense_gn_f32(x, wp, g, b, res, y, B, cin, cout, Ln, gn.num_groups, 1 if relu else 0, L.stream_ptr())
     return y
 

@@ -969,6 +969,45 @@ int pcr_ident_record_i32(const pcr_ident *p, pcr_stream_t stream);
 int pcr_ident_compact_f32(const pcr_ident_close *p, pcr_stream_t stream);
 int pcr_ident_score_i32(const pcr_ident_close *p, pcr_stream_t stream);
 
+/* ------------------------------------------------------------ A10. pair head over embeddings -------- */
+
+/* The `concat` matching head of a gallery (additive to ABI 17; reid_pts_point-transformer_baseline.py: match_type
+ * 'concat', models/ReIDNet.py:455-458): a pair's input is [e_i | e_j], e = pool_channel_max(h) (M, F), and the head is
+ * LinearRes(n, n, GroupNorm) + Linear(n, 1) with n = 2F (models/lanegcn_nets.py:228-241).  linear1 has no bias, so its
+ * product splits into two per-OBJECT tables, W1 [e_i ; e_j] = W1[:, :F] e_i + W1[:, F:] e_j = u[i] + v[j], which the
+ * caller computes once per object (pcr_dense_f32).  Per live pair p = (i, j) the launch computes
+ *     z = relu(GN1(u[i] + v[j]));   y = GN2(W2 z) + [e_i | e_j];   logits[p] = w_out . relu(y) + b_out
+ * (GroupNorm: biased variance, eps 1e-5).  pairs[p] = (i, j), i the FIRST argument of match_forward_inference: the head is
+ * not symmetric.
+ *   Arithmetic.  W2 z runs on the matrix core as f32-input MFMA (v_mfma_f32_32x32x2_f32) whatever the precision mode of
+ *     the model launches; pcr_last_launch_arith() says PCR_PREC_F32 afterwards.
+ *   Shapes.  pcr_pair_head_ok (shape only, never M or P): F in {32, 64, 128} and a GroupNorm group of n / groups = 4, 8, 16
+ *     or 32 channels (pcr_dense_gn_f32's rule).  Anything else, n != 2F, a NULL tensor or a table that is not 16-byte
+ *     aligned returns PCR_ERR_INVALID before anything is written.
+ *   Batch independence.  A pair's bits never depend on the batch it travels in: not on P, not on its position in the
+ *     list, not on *count.
+ *   Gating (pcr_live, pairs in place of clouds, as pcr_pool_head_live_f32).  A dead pair reads nothing -- its two indices
+ *     included -- and gets *dead_value (a HOST float, read when the call is made; NULL: 0.0f).  live == NULL scores all P
+ *     pairs.  *count is read by the launch, so a captured graph follows it.
+ *   Out-of-range indices.  A live pair with an index outside [0, M) reads nothing of the tables and gets NaN.
+ *   Grid.  One launch, one-dimensional and strided over tiles of 32 pairs: P is bounded by memory alone.
+ * (The block is a tagged struct followed by its typedef; the layout is the plain C one.) */
+struct pcr_pair_head_params {
+  int M, F, n, groups;              /* objects; embedding width; n = 2F = head width; GroupNorm groups of LinearRes */
+  long P;                           /* pairs in the list */
+  const float *emb;                 /* (M, F)  e = pool_channel_max(h) */
+  const float *u, *v;               /* (M, n)  u = emb W1[:, :F]^T, v = emb W1[:, F:]^T */
+  const int *pairs;                 /* (P, 2) int32 */
+  const float *w2p;                 /* linear2 (n, n): pcr_pack_weight_f32 image */
+  const float *gn1_g, *gn1_b, *gn2_g, *gn2_b, *w_out, *b_out;   /* (n) x 5, (1) */
+  float *logits;                    /* (P) */
+};
+typedef struct pcr_pair_head_params pcr_pair_head_params;
+struct pcr_live;                    /* section B, "Gated launches" */
+int pcr_pair_head_ok(int F, int groups);
+int pcr_pair_head_f32(const pcr_pair_head_params *p, const struct pcr_live *live, const float *dead_value,
+                      pcr_stream_t stream);
+
 /* ------------------------------------------------- B. fused model kernels ------------ */
 
 /* Neighbour search of the "Point-Transformer" set-abstraction layers: centres are the first S

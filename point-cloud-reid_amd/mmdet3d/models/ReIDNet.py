@@ -514,9 +514,25 @@ class ReIDNet(nn.Module):
         compare_pairs.  The pair launches read the count themselves and do no work for the rest (engine.AttnPlan live=:
         nothing of a pair beyond count is read, its indices included); logits[:count] are bit for bit those of the un-gated
         call, logits[count:] are dead_value exactly.  No host read: a captured graph follows the count from replay to
-        replay."""
+        replay.
+
+        Heads.  xcorr_eff / point-cat / both (symmetric: both directions of a pair are evaluated), and the three one-way
+        heads of the reference's baseline configs, for which pair (i, j) is NOT pair (j, i) -- i is the search side, the
+        first argument of match_forward_inference:
+          concat          the embedding head (embed / match_embeddings): pooled once per object, one launch for the list;
+                          count= gates that launch.
+          xcorr-baseline  both cross stages take the template's ORIGINAL features, so the key/value state of both stages
+                          is per object and a pair is one virtual cloud; count= gates the two applies.
+          xcorr           as xcorr-baseline with the local stages in between.  The local stages have no gated form: with
+                          count= the whole list is scored (the padding (0, 0) of compare_pairs is a valid pair) and the
+                          logits beyond count are replaced by dead_value -- this head saves no work for padding."""
+        if self.match_type == "concat":
+            return self.match_embeddings(self.embed(h), pairs, count=count, dead_value=dead_value)
+        if self.match_type in ("xcorr", "xcorr-baseline"):
+            return self._match_gallery_one_way(h, xyz, pairs, count, dead_value)
         if self.match_type != "xcorr_eff" or self.combine != "point-cat" or self.pool_type != "both":
-            raise NotImplementedError("match_gallery covers the xcorr_eff / point-cat / both matching head")
+            raise NotImplementedError("match_gallery covers the xcorr_eff / point-cat / both matching head and the concat, "
+                                      "xcorr-baseline and xcorr heads")
         h, xyz = h.contiguous(), xyz.contiguous()
         n_pts = h.shape[2]
         p1 = self.cross_stage1.plan(h.device)
@@ -583,6 +599,85 @@ class ReIDNet(nn.Module):
         logits = self._head_rows(feat)
         alive = torch.arange(lo, lo + n_pairs, device=h.device, dtype=torch.int32) < count
         return torch.where(alive, logits, logits.new_full((), float(dead_value)))
+
+    @staticmethod
+    def _gallery_count(count):
+        if count is None:
+            return None
+        L.require_cuda(count)
+        if count.dtype != torch.int32 or count.numel() != 1:
+            raise L.PcrError("match_gallery: count must be a (1,) int32 device tensor")
+        return count.reshape(1).contiguous()
+
+    def _match_gallery_one_way(self, h, xyz, pairs, count, dead_value):
+        """match_gallery for match_type 'xcorr-baseline' / 'xcorr' (xcorr_baseline / xcorr above): the template of both
+        cross stages is object j's original features, so kv1 and kv2 are per OBJECT and pair (i, j) is ONE virtual cloud:
+        object i's tokens against object j's state, twice"""
+        local = self.match_type == "xcorr"
+        if local and (self.local_stage1 is None or self.local_stage2 is None):
+            raise L.PcrError("match_type='xcorr' needs local_stage1 / local_stage2 (local_self_attention)")
+        h, xyz = h.contiguous(), xyz.contiguous()
+        n_pts = h.shape[2]
+        p1 = self.cross_stage1.plan(h.device)
+        p2 = self.cross_stage2.plan(h.device)
+        count = self._gallery_count(count)
+        gated = count is not None and not local
+        if gated and not (p1.live_ok() and p2.live_ok()):
+            raise L.PcrError("match_gallery: count= needs matching stages the gated launches cover "
+                             "(pcr_attn_live_ok: d_model = 64 with 64-channel features)")
+        kv1, kv2 = p1.kv(h, xyz), p2.kv(h, xyz)
+        out = []
+        for lo in range(0, pairs.shape[0], self.GALLERY_CHUNK):
+            pc = pairs[lo:lo + self.GALLERY_CHUNK]
+            n_pairs = pc.shape[0]
+            i = pc[:, 0].to(device=h.device, dtype=torch.int32).contiguous()
+            j = pc[:, 1].to(device=h.device, dtype=torch.int32).contiguous()
+            live = (count, n_pairs, lo) if gated else None
+            s = p1.apply(h, None, kv1, n_pts, kv_index=j, q_index=i, n_out=n_pairs, live=live)
+            if local:
+                xyz_v = xyz.index_select(0, i.long()).contiguous()
+                s = self.local_stage1(s, xyz_v)
+            # (a dead pair's rows of the gated stage-2 output are zeros: pooling and the head read every row, and a row's
+            # logit depends on that row alone)
+            buf = torch.zeros((n_pairs, p2.cfinal or p2.cout, n_pts), dtype=torch.float32, device=h.device) if gated else None
+            s = p2.apply(s, None, kv2, n_pts, kv_index=j, live=live, out=buf)
+            if local:
+                s = self.local_stage2(s, xyz_v)
+            logits = self._head_rows(self.get_pooled_feats(s))
+            if count is not None:
+                alive = torch.arange(lo, lo + n_pairs, device=h.device, dtype=torch.int32) < count
+                logits = torch.where(alive, logits, logits.new_full((), float(dead_value)))
+            out.append(logits)
+        if not out:
+            return torch.empty(0, dtype=torch.float32, device=h.device)
+        return out[0] if len(out) == 1 else torch.cat(out, dim=0)
+
+    def embed(self, h):
+        """h (M,C,N) from forward_inference -> (M,F) embeddings of the 'concat' head, F = N: what the inference entry point
+        pools each side with (self.maxpool whatever pool_type, reference ReIDNet.py:455-457) -- 4 F bytes per object to
+        store instead of the (C,N) features.  C > output_sequence_size (a 3-D pool) is refused."""
+        from pcr_amd import rows
+        if self.match_type != "concat":
+            raise L.PcrError("embed: the embedding form is the match_type='concat' head (got %r)" % self.match_type)
+        L.require_cuda(h)
+        if h.dim() != 3 or h.shape[1] > self.output_sequence_size:
+            raise L.PcrError("embed: features (M, C, N) with C <= output_sequence_size = %d expected, got %s"
+                             % (self.output_sequence_size, tuple(h.shape)))
+        return rows.pool_channel_max(h, self.output_sequence_size)
+
+    def match_embeddings(self, emb, pairs, count=None, dead_value=0.0):
+        """emb (M,F) from embed, pairs (P,2) -> logits (P): pair (i, j) scores as match_forward_inference(h[i:i+1],
+        h[j:j+1], ...) does (i first: the head is not symmetric).  The per-object tables of the head's first layer are made
+        once, the rest is one launch over the whole list (pcr_amd/pairs_head.py), f32 arithmetic in every precision mode.
+        count / dead_value as in match_gallery: pairs[count:] are neither read nor scored.  A pair with an index outside
+        [0, M) gets NaN."""
+        from pcr_amd import pairs_head
+        if self.match_type != "concat":
+            raise L.PcrError("match_embeddings: the embedding form is the match_type='concat' head (got %r)" % self.match_type)
+        L.require_cuda(emb)
+        pl = pairs_head.plan(self.match_head, emb.device)
+        u, v = pairs_head.tables(pl, emb)
+        return pairs_head.pair_logits(pl, emb, u, v, pairs, count=self._gallery_count(count), dead_value=dead_value)
 
     @staticmethod
     def _decision_set(decisions, T, D, cost_args, who, M=None):

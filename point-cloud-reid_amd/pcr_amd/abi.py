@@ -92,6 +92,10 @@ IdentCloseParams = _block("IdentCloseParams", """
     int gt_rows id_cap max_rows max_cols; iptr cooc gt_track totals; dptr dist_sum; iptr flags counts row_list col_list;
     fptr cost; iptr col4row info id_map; lptr table; dptr dist_total""")
 
+# ---- section A10 (pcr_pair_head_params) ----
+PairHeadParams = _block("PairHeadParams", """
+    int M F n groups; long P; fptr emb u v; iptr pairs; fptr w2p gn1_g gn1_b gn2_g gn2_b w_out b_out logits""")
+
 # ---- section A6 (pcr_store_tables) ----
 StoreTables = _block("StoreTables", """
     int num_objects num_classes;
@@ -262,6 +266,9 @@ SIGNATURES = {
     "pcr_ident_record_i32": "s <IdentParams>S",
     "pcr_ident_compact_f32": "s <IdentCloseParams>S",
     "pcr_ident_score_i32": "s <IdentCloseParams>S",
+    # A10. pair head over embeddings (the block is passed as a plain pointer: byref(PairHeadParams))
+    "pcr_pair_head_ok": "i ii",
+    "pcr_pair_head_f32": "s P<LiveParams>FS",
     # B. fused model kernels
     "pcr_knn_prefix_f32": "s FIiiiiS",
     "pcr_knn_prefix2_f32": "s FIIiiiiiiS",

@@ -1008,6 +1008,106 @@ int pcr_pair_head_ok(int F, int groups);
 int pcr_pair_head_f32(const pcr_pair_head_params *p, const struct pcr_live *live, const float *dead_value,
                       pcr_stream_t stream);
 
+/* ------------------------------------------------------------ A11. the updater as configured; the scene log ---- */
+
+/* The reference's TrackingUpdater (models/trackers/deprecated/tracking_updater.py:22-203) applies an `update_config` to
+ * every decision of a frame -- `match`, the detection decisions, the tracking decisions, each with output / active / decom
+ * flags -- and returns the tracks to output, propagated ones included (virtual_tracker.py:847, 923, 1044-1071).  The two
+ * entries below (additive to ABI 17) are that step and the record it feeds, as fixed-shape launches of ONE workgroup
+ * without a host read, an allocation or an atomic; they write the same bits on every run.  pcr_bank_plan_i32 (A5) is
+ * untouched: it stays the one-flag form.
+ *
+ * pcr_bank_plan_rules_i32: the bank, the frame inputs, carry, frame_limit, replace_all, reset_on_match, src, det_slot and
+ * det_id of pcr_bank_plan_i32 with the same meaning.  born, kill and propagate are replaced by
+ *   det_decision (D), track_decision (C)  as pcr_assoc_decode_i32 writes them: 0 = matched, 1 + i = decision i, 1 + dd /
+ *                 1 + td = unmatched; any value outside that range reads as unmatched;
+ *   dd, td        the decisions per side, 0 .. PCR_ASSOC_MAX_DECISIONS;
+ *   match_rule, det_rule[i], trk_rule[j]  rule words of the bits PCR_RULE_OUTPUT, PCR_RULE_ACTIVE, PCR_RULE_DECOM (only
+ *                 the first dd / td entries are read).  ACTIVE and DECOM together in a word that is read is
+ *                 PCR_ERR_INVALID (the reference raises, update_, :190-191);
+ *   trk_kind[j]   PCR_TRK_KEEP (track_false_positive: update_ only) or PCR_TRK_MISS (track_false_negative).
+ * The result is DEFINED by these rules over the state as it was BEFORE the launch (tests/update_ref.py::plan_rules restates
+ * them; the kernel equals it bit for bit).  "Freed" means ids = labels = -1, lengths = 0.
+ *   matched  slot s is active and track_decision[s] == 0, d = track_to_det[s] lies in [0, D), det_labels[d] >= 0,
+ *            det_to_track[d] == s and det_decision[d] == 0.  The slot takes A5's matched update word for word (box, score,
+ *            label, steps += 1, reset_on_match, the replace_all / lengths rule for src, det_slot / det_id); then match_rule
+ *            applies;
+ *   keep     s is active, track_decision[s] == 1 + j, j < td, trk_kind[j] == PCR_TRK_KEEP: the state is unchanged, src = -1;
+ *            then trk_rule[j] applies;
+ *   miss     as keep, but trk_kind[j] == PCR_TRK_MISS: misses += 1; if misses >= frame_limit the slot is freed and not
+ *            output (:136-138).  Otherwise the box is propagated by exactly the arithmetic of A5's missed rule with
+ *            propagate set (carry included), scores *= 0.01f, steps += 1, src = -1; then trk_rule[j] applies;
+ *   wait     every other active slot (decision 1 + td, a matched code whose maps disagree, a code out of range):
+ *            misses += 1, freed at frame_limit, otherwise unchanged; never output (update_track_unmatched, :161-186);
+ *   a rule   OUTPUT: row s of the output table is valid and holds the slot's id, label, score and box as they are after the
+ *            update above.  Not ACTIVE: the slot is freed after its row was taken (src stays as the update left it).
+ *            DECOM changes nothing in the bank; it is bit 0 of the row's flags;
+ *   new      a detection d with det_labels[d] >= 0 and det_decision[d] == 1 + i, i < dd, is numbered as the reference
+ *            numbers it (:36-52): grouped by decision in ascending i, by ascending d within a decision; the k-th of that
+ *            order gets id = next_id + k, and next_id advances by their number whether or not they get a slot.  With ACTIVE
+ *            in det_rule[i] it takes a slot as A5's born: the k-th ACTIVE one of that same order takes the k-th slot that
+ *            was free BEFORE the launch (steps = 1, misses = 0, fields from the detection, src = d, det_slot / det_id
+ *            written).  ACTIVE ones beyond the free slots are dropped: det_slot = -1, info[0] counts them, det_id still
+ *            names the id.  With OUTPUT a slotted newborn is output in its slot's row, an unslotted one (not ACTIVE, or
+ *            dropped) in row C + d from the detection's own fields.  A detection with label < 0, or with any other
+ *            decision that is not a match, takes no part: det_slot = det_id = -1, no id is consumed.
+ * Output table, C + D rows, EVERY element written: out_valid, out_ids, out_labels (int32), out_scores, out_boxes (C + D, W),
+ * out_flags (int32: bit 0 = the rule's DECOM, bit 1 = the row is a propagated track).  An invalid row has ids = labels = -1
+ * and zeros elsewhere.  info (2): [0] = dropped newborns, [1] = valid output rows.
+ * The kernel follows pcr_bank_plan_i32's: every cross-thread read of the old state happens before the first barrier; the
+ * ranks are ballots and popcounts per 64-entry word, one set per detection decision, with a prefix over words and decisions
+ * in LDS; a slot and a row are written by their owner thread only.
+ * pcr_bank_rules_ok: pcr_bank_ok(C, D, W, 0, 0) and 0 <= dd, td <= PCR_ASSOC_MAX_DECISIONS.  The det_* pointers,
+ * det_decision, det_slot and det_id may be NULL when D == 0; carry may be NULL (identity).
+ *
+ * pcr_scene_log_append_i32: the device-side record a result file is written from.  The log has the columns frame, id,
+ * label, flags (int32), score (float), box (W floats) of rows_max rows each, and cursor, dropped, frame_no (1 each, int32).
+ * One append takes an R-row table in the form above (R = C + D for a bank): the valid rows (in_valid != 0) are compacted
+ * in row order by ballot, popcount and a prefix over the words, and written from row cursor[0] on with frame =
+ * frame_no[0].  Rows that do not fit are dropped and added to dropped[0]; cursor advances by the rows written, frame_no by
+ * 1 -- a device counter, so a captured frame replays correctly.  A cursor outside [0, rows_max] reads as a full log.  One
+ * writer, no atomics.  pcr_scene_log_ok: 1 <= rows_max <= PCR_LOG_MAX_ROWS, 1 <= R <= 2 * PCR_ASSOC_MAX_OBJECTS, W == 7 or 9.
+ * (Both blocks are tagged structs followed by their typedefs, as in A10; the layout is the plain C one.) */
+#define PCR_RULE_OUTPUT 1
+#define PCR_RULE_ACTIVE 2
+#define PCR_RULE_DECOM 4
+#define PCR_TRK_KEEP 0
+#define PCR_TRK_MISS 1
+#define PCR_LOG_MAX_ROWS 16777216
+struct pcr_bank_rules {
+  int C, D, W;
+  int frame_limit, replace_all, reset_on_match;
+  int dd, td;
+  int match_rule;
+  int det_rule[4], trk_rule[4], trk_kind[4];                  /* PCR_ASSOC_MAX_DECISIONS each */
+  int *lengths;   /* state (C ...), updated in place */
+  float *boxes, *scores;
+  int *labels, *ids, *steps, *misses, *next_id;
+  const int *track_to_det, *det_to_track, *det_labels, *det_lengths;   /* the frame */
+  const float *det_boxes, *det_scores;
+  const int *det_decision, *track_decision;
+  const float *carry;
+  int *src, *det_slot, *det_id, *info;   /* the decisions; info (2) */
+  int *out_valid, *out_ids, *out_labels;   /* the output table (C + D ...) */
+  float *out_scores, *out_boxes;
+  int *out_flags;
+};
+typedef struct pcr_bank_rules pcr_bank_rules;
+struct pcr_scene_log {
+  int rows_max, R, W;
+  const int *in_valid, *in_ids, *in_labels;   /* the table (R ...) */
+  const float *in_scores, *in_boxes;
+  const int *in_flags;
+  int *frame, *id, *label, *flags;   /* the log (rows_max ...) */
+  float *score, *box;
+  int *cursor, *dropped, *frame_no;   /* (1) each */
+};
+typedef struct pcr_scene_log pcr_scene_log;
+int pcr_bank_rules_ok(int C, int D, int W, int dd, int td);
+int pcr_bank_plan_rules_i32(const pcr_bank_rules *p, pcr_stream_t stream);
+int pcr_scene_log_ok(int rows_max, int R, int W);
+int pcr_scene_log_append_i32(const pcr_scene_log *p, pcr_stream_t stream);
+
 /* ------------------------------------------------- B. fused model kernels ------------ */
 
 /* Neighbour search of the "Point-Transformer" set-abstraction layers: centres are the first S

@@ -841,7 +841,7 @@ class ReIDNet(nn.Module):
     def track_step(self, bank, sweep, boxes, labels, scores, carry=None, carry_inv=None, min_points=2, num_classes=8,
                    cap=None, n=None, crop_args=None, born=None, kill=None, frame_limit=10, replace_all=False,
                    reset_on_match=False, propagate=True, suppress_threshold=0.15, live_only=False, truth=None,
-                   force_truth=False, decisions=None, by_class=False, **cost_args):
+                   force_truth=False, decisions=None, by_class=False, update_config=None, log=None, **cost_args):
         """One whole tracker frame on the device without a host read (pcr_amd/tracks.py; INTEGRATION.md "2e. Track
         state"; the split-bf16 guard calibrates on the first batch of a weight version, as in every inference entry
         point: run a frame eagerly before capturing): the sweep (P, C >= 3) and this frame's boxes (M <= bank.max_dets, bank.box_width) with labels and
@@ -872,7 +872,18 @@ class ReIDNet(nn.Module):
         decoded born / kill masks -- 'det_newborn' and 'track_false_positive', nothing is born or killed when the name is
         absent, as in the reference, whose updater makes tracks from decision lists only -- drive bank.update, and the dict
         gains det_decision, track_decision, born, kill and decode_info.  born= / kill= cannot be passed with it.  truth= /
-        force_truth= work on top unchanged.  propagate stays the bank's one flag for every missed track.
+        force_truth= work on top unchanged.  Without update_config, propagate stays the bank's one flag for every missed track.
+
+        update_config= (needs decisions=; the reference's dict: match, det_newborn, det_false_positive,
+        track_false_positive, track_false_negative, each dict(output=, active=, decom=)) runs the updater as the reference
+        configures it (pcr_amd.tracks.UpdateRules): bank.update_rules on the decoded det_decision /
+        track_decision takes bank.update's place -- a track that took track_false_negative is propagated, an unmatched one
+        waits -- and the dict gains the frame's output table out_valid, out_ids, out_labels, out_scores, out_boxes,
+        out_flags (capacity + max_dets rows, the bank's own); bank_info becomes (2,): the dropped newborns and the valid
+        rows.  It cannot be combined with born= / kill=, propagate=False or force_truth.  log= a pcr_amd.tracks.SceneLog
+        of capacity + max_dets rows per frame: the table is appended after the update and before bank.suppress, as the
+        reference forms its output before the track NMS.  truth= and identity= keep working; book.decide still gets the
+        decoded born / kill.  Without both arguments nothing new is launched.
 
         by_class: as in associate -- the assignment runs class by class over block ids made from the bank's and the frame's
         labels on the device each frame (free slots and padded detections share the rest block), so one captured graph
@@ -899,6 +910,18 @@ class ReIDNet(nn.Module):
             raise L.PcrError("track_step: with decisions= the born / kill masks come from the decoded decisions; pass one or "
                              "the other")
         C, D, W = bank.capacity, bank.max_dets, bank.box_width
+        if update_config is not None:
+            if decisions is None:
+                raise L.PcrError("track_step: update_config applies to decoded decisions; pass decisions= with it")
+            if born is not None or kill is not None or not propagate or force_truth:
+                raise L.PcrError("track_step: update_config cannot be combined with born= / kill=, propagate= or "
+                                 "force_truth=: the rules decide what is born, dropped and propagated")
+        if log is not None:
+            if update_config is None:
+                raise L.PcrError("track_step: log= records the output table; pass update_config= with it")
+            if not isinstance(log, TR.SceneLog) or (log.rows_per_frame, log.box_width) != (C + D, W):
+                raise L.PcrError("track_step: log must be a pcr_amd.tracks.SceneLog of %d rows per frame and box width %d"
+                                 % (C + D, W))
         boxes = L.tensor(boxes, "track_step", "boxes", torch.float32, shape=(None, W), copy=True)
         M = boxes.shape[0]
         L.require(M <= D, "track_step", "boxes must be (M <= %d, %d), got %s", D, W, tuple(boxes.shape))
@@ -906,6 +929,7 @@ class ReIDNet(nn.Module):
         L.require(isinstance(labels, torch.Tensor) and labels.shape == (M,), "track_step", "labels must be (M,)")
         L.require_cuda(sweep, boxes, labels, scores)
         ds = None if decisions is None else self._decision_set(decisions, C, D, cost_args, "track_step", M=M)
+        rules = None if update_config is None else TR.UpdateRules(update_config, ds["det_names"], ds["trk_names"])
         if ds is None and not L.load().pcr_lsa_ok(1, C + D, C + D):
             raise L.PcrError("track_step: capacity + max_dets = %d is beyond linear_assignment (PCR_LSA_MAX)" % (C + D))
         if ds is not None:
@@ -950,9 +974,18 @@ class ReIDNet(nn.Module):
             truth_out = book.decide(decisions, labels, born=born, kill=kill, forced=force_truth)
             if force_truth:
                 decisions, born, kill = book.forced()
-        det_slot, det_id, bank_info = bank.update(
-            decisions, dict(labels=labels, lengths=lengths, boxes=boxes, scores=scores), born=born, kill=kill, carry=carry,
-            frame_limit=frame_limit, replace_all=replace_all, reset_on_match=reset_on_match, propagate=propagate)
+        dets = dict(labels=labels, lengths=lengths, boxes=boxes, scores=scores)
+        if rules is not None:
+            det_slot, det_id, bank_info, table = bank.update_rules(
+                decisions, dets, decoded["det_decision"], decoded["track_decision"], rules, carry=carry,
+                frame_limit=frame_limit, replace_all=replace_all, reset_on_match=reset_on_match)
+            decoded = dict(decoded, **table)
+            if log is not None:
+                log.append(table)
+        else:
+            det_slot, det_id, bank_info = bank.update(decisions, dets, born=born, kill=kill, carry=carry,
+                                                      frame_limit=frame_limit, replace_all=replace_all,
+                                                      reset_on_match=reset_on_match, propagate=propagate)
         if suppress_threshold is not None:
             bank.suppress(suppress_threshold)
         if truth is not None:

@@ -96,6 +96,16 @@ IdentCloseParams = _block("IdentCloseParams", """
 PairHeadParams = _block("PairHeadParams", """
     int M F n groups; long P; fptr emb u v; iptr pairs; fptr w2p gn1_g gn1_b gn2_g gn2_b w_out b_out logits""")
 
+# ---- section A11 (pcr_bank_rules, pcr_scene_log) ----
+BankRulesParams = _block("BankRulesParams", """
+    int C D W frame_limit replace_all reset_on_match dd td match_rule; int[4] det_rule trk_rule trk_kind;
+    iptr lengths; fptr boxes scores; iptr labels ids steps misses next_id;
+    iptr track_to_det det_to_track det_labels det_lengths; fptr det_boxes det_scores; iptr det_decision track_decision;
+    fptr carry; iptr src det_slot det_id info; iptr out_valid out_ids out_labels; fptr out_scores out_boxes; iptr out_flags""")
+SceneLogParams = _block("SceneLogParams", """
+    int rows_max R W; iptr in_valid in_ids in_labels; fptr in_scores in_boxes; iptr in_flags;
+    iptr frame id label flags; fptr score box; iptr cursor dropped frame_no""")
+
 # ---- section A6 (pcr_store_tables) ----
 StoreTables = _block("StoreTables", """
     int num_objects num_classes;
@@ -269,6 +279,11 @@ SIGNATURES = {
     # A10. pair head over embeddings (the block is passed as a plain pointer: byref(PairHeadParams))
     "pcr_pair_head_ok": "i ii",
     "pcr_pair_head_f32": "s P<LiveParams>FS",
+    # A11. the updater as configured, the scene log (plain pointers as A10: byref(BankRulesParams / SceneLogParams))
+    "pcr_bank_rules_ok": "i iiiii",
+    "pcr_bank_plan_rules_i32": "s PS",
+    "pcr_scene_log_ok": "i iii",
+    "pcr_scene_log_append_i32": "s PS",
     # B. fused model kernels
     "pcr_knn_prefix_f32": "s FIiiiiS",
     "pcr_knn_prefix2_f32": "s FIIiiiiiiS",

@@ -1674,7 +1674,7 @@ int pcr_tnorm_bwd_f32(const float *g, const float *x, const float *gamma, const 
 /* Linear-attention core (LinearAttention.forward, models/pointnet2_utils.py:26-47), forward and backward, one workgroup
  * per (cloud, head): Q' = elu(q)+1, K' = elu(k)+1, V' = v/Sk, A = sum_s K'_s V'_s^T, ks = sum_s K'_s,
  * out_l = (Q'_l^T A) Sk / (Q'_l . ks + eps).  q / k / v (and dq / dk / dv) are (d, L) channel-major blocks per cloud
- * addressed with a batch stride, so slices of a fused (B,3d,L) projection need no copies.  d / H in {16, 32, 64}.
+ * addressed with a batch stride, so slices of a fused (B,3d,L) projection need no copies.  d / H in {16, 32, 64, 128}.
  * A (B,H,dh,dh) and ks (B,H,dh) are written by the forward and read by the backward. */
 typedef struct pcr_linattn {
   int B, Lq, Sk, d, H;

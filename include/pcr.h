@@ -1108,6 +1108,50 @@ int pcr_bank_plan_rules_i32(const pcr_bank_rules *p, pcr_stream_t stream);
 int pcr_scene_log_ok(int rows_max, int R, int W);
 int pcr_scene_log_append_i32(const pcr_scene_log *p, pcr_stream_t stream);
 
+/* ------------------------------------------------------------ A12. ranking a wide gallery -------- */
+
+/* Section A8 beyond PCR_RANK_MAX_GALLERY entries: the score matrix is built from gallery blocks of at most
+ * PCR_ASSOC_MAX_OBJECTS entries (one pair list and one scatter per block, into the block's column window), and the ranking
+ * reads a query's row from global memory instead of staging it in LDS.  (An addition: a validation set of nuScenes or Waymo
+ * detections gives a gallery of tens of thousands of entries.)  Fixed-shape launches, no host read, no allocation, no float
+ * atomic and no global atomic (integer LDS adds only: their sum does not depend on the order); the same bits on every run;
+ * every loop is bounded by an integer count.  Pointers are checked against NULL only.  Nothing of section A8 changes, and a
+ * caller that stays below its limits has no reason to come here.
+ * pcr_rank_wide_ok: 0 <= Q <= PCR_RANK_MAX_QUERIES, 0 <= G <= PCR_RANK_WIDE_MAX_GALLERY, 1 <= K <= PCR_RANK_MAX_K.  The
+ * products Q * G and Q * width are formed in 64-bit arithmetic everywhere.
+ *
+ * pcr_rank_fill_f32: every element of scores (Q,G) becomes -inf ("not a candidate").  Nothing to do: Q * G == 0.
+ *
+ * pcr_rank_scatter_f32: the scatter half of pcr_rank_scores_f32 with a column window [col0, col0 + width): logits (cap),
+ * pairs (cap,2), count (1, device); for k < min(max(count[0], 0), cap) with (q, g) = pairs[k], 0 <= q < Q and
+ * 0 <= g < width: scores[q * G + col0 + g] = logits[k].  Every other element of scores is left as it is.  A pair outside the
+ * range is skipped.  The listed pairs must be distinct.  Invalid without a launch: col0 < 0, width < 0, col0 + width > G,
+ * cap < 0, cap > Q * width, or a NULL pointer while there is work to do (cap > 0).  Nothing to do: cap == 0.
+ *
+ * pcr_rank_wide_f32: pcr_rank_gallery_f32's block, fields and rules -- candidates, the NaN rule, order, rank, top-k, truth,
+ * first_hit and ap with its binary64 order of operations are section A8's, word for word, and every element of every output
+ * is written -- with one rule added:
+ *   true cap    if no candidate's score is a NaN and the true set has more than PCR_RANK_WIDE_MAX_TRUE members, info[q] = 2
+ *               and the query is not ranked: topk_idx -1, topk_score -inf, n_cand = n_true = 0, first_hit = -1, ap = 0.  A
+ *               NaN among the candidates takes precedence (info[q] = 1).  pcr_rank_accumulate counts info != 0 as flagged,
+ *               so such a query never reads as a miss.
+ * For G <= PCR_RANK_MAX_GALLERY the true set cannot exceed the cap, and the outputs equal pcr_rank_gallery_f32's bit for bit
+ * on every input.
+ * Cost: one workgroup (four waves) per query, 57.6 KiB of LDS whatever G is.  The row is read from memory at most twice,
+ * whatever K and n_true are, plus one read per top-k entry: sweep 1 counts the candidates, looks for NaNs, collects the true
+ * candidates' keys (order-preserving score bits, inverted index) and carries the K best keys from step to step of 1024
+ * columns -- only the keys above the carried K-th one are looked at again, by section A8's rounds of a 64-bit wave maximum, in
+ * LDS; the true keys are then sorted in LDS; sweep 2 (only when the true set is not empty) has every candidate find by
+ * binary search the first true key below its own and add one there, so that a prefix sum gives every true candidate's rank.
+ * Nothing to do: Q == 0.  With G == 0 every query is empty and the outputs are still written. */
+#define PCR_RANK_WIDE_MAX_GALLERY 4194304
+#define PCR_RANK_WIDE_MAX_TRUE 4096
+int pcr_rank_wide_ok(int Q, int G, int K);
+int pcr_rank_fill_f32(float *scores, int Q, int G, pcr_stream_t stream);
+int pcr_rank_scatter_f32(const float *logits, const int *pairs, const int *count, float *scores, int Q, int G, int cap,
+                         int col0, int width, pcr_stream_t stream);
+int pcr_rank_wide_f32(const pcr_rank *p, pcr_stream_t stream);
+
 /* ------------------------------------------------- B. fused model kernels ------------ */
 
 /* Neighbour search of the "Point-Transformer" set-abstraction layers: centres are the first S

@@ -826,7 +826,8 @@ class ReIDNet(nn.Module):
         L.require_cuda(q_feats, q_xyz, g_feats, g_xyz)
         Q, G = q_feats.shape[0], g_feats.shape[0]
         if not R.rank_ok(Q, G, topk):
-            raise L.PcrError("retrieve: Q=%d G=%d topk=%d is out of range (pcr_rank_ok)" % (Q, G, topk))
+            raise L.PcrError("retrieve: Q=%d G=%d topk=%d is out of range (pcr_rank_ok)%s" % (
+                Q, G, topk, "; retrieve_wide ranks a gallery above %d entries" % R.MAX_GALLERY if G > R.MAX_GALLERY else ""))
         pairs, count = A.compare_pairs(q_labels, g_labels, q_lengths, g_lengths, min_points=min_points,
                                        num_classes=num_classes)
         if Q == 0 or G == 0:
@@ -837,6 +838,47 @@ class ReIDNet(nn.Module):
         scores = R.score_matrix(logits, pairs, count, Q, G)
         out = R.rank_gallery(scores, query_ids, gallery_ids, topk=topk, exclude=exclude)
         return dict(pairs=pairs, count=count, logits=logits, scores=scores, **out)
+
+    def retrieve_wide(self, q_feats, q_xyz, q_labels, q_lengths, g_feats, g_xyz, g_labels, g_lengths, query_ids=None,
+                      gallery_ids=None, topk=10, exclude=None, min_points=2, num_classes=8, live_only=False,
+                      gallery_block=4096, scores=None):
+        """`retrieve` for a gallery of up to pcr_amd.retrieval.WIDE_MAX_GALLERY entries (INTEGRATION.md "2h. Ranking a
+        gallery"; include/pcr.h section A12).  The gallery is walked in blocks of gallery_block entries (1 to 4096; block b
+        covers the columns [b * gallery_block, min(G, (b + 1) * gallery_block))): fill_scores once, then per block
+        compare_pairs of the queries against the block's labels and lengths, match_gallery over [queries | the block's
+        rows] (the block's count when live_only) and scatter_scores into the block's column window; rank_gallery_wide over
+        the whole matrix at the end.  The arguments are retrieve's; exclude and the ids are global gallery indices; scores =
+        a (Q, G) float32 buffer to write into.  The per-block pair lists and logits are not kept.
+        -> rank_gallery's seven outputs plus scores (Q, G) and counts (blocks,) int32, the blocks' pair counts on the device.
+        The number of launches depends on the shapes alone.  For G <= 4096 scores and the seven outputs equal retrieve's bit
+        for bit whatever gallery_block is: the logit of a pair does not depend on what else is in its batch."""
+        from pcr_amd import associate as A
+        from pcr_amd import retrieval as R
+        L.require_cuda(q_feats, q_xyz, g_feats, g_xyz)
+        Q, G, block = q_feats.shape[0], g_feats.shape[0], int(gallery_block)
+        if not 1 <= block <= R.MAX_GALLERY:
+            raise L.PcrError("retrieve_wide: gallery_block=%d: 1 to %d" % (block, R.MAX_GALLERY))
+        if not R.rank_wide_ok(Q, G, topk):
+            raise L.PcrError("retrieve_wide: Q=%d G=%d topk=%d is out of range (pcr_rank_wide_ok)" % (Q, G, topk))
+        dev = q_feats.device
+        scores = R.fill_scores(L.out_tensor(scores, "retrieve_wide", "scores", torch.float32, (Q, G), dev))
+        counts = []
+        g_labels = L.tensor(g_labels, "retrieve_wide", "g_labels", torch.int32, shape=(G,), cast_int64=True, copy=True)
+        g_lengths = L.tensor(g_lengths, "retrieve_wide", "g_lengths", torch.int32, shape=(G,), optional=True, cast_int64=True,
+                             copy=True)
+        for lo in range(0, G, block):
+            hi = min(G, lo + block)
+            pairs, count = A.compare_pairs(q_labels, g_labels[lo:hi], q_lengths, None if g_lengths is None else g_lengths[lo:hi],
+                                           min_points=min_points, num_classes=num_classes)
+            counts.append(count)
+            if Q == 0:
+                continue
+            logits = self._match_across(torch.cat([q_feats, g_feats[lo:hi]], dim=0), torch.cat([q_xyz, g_xyz[lo:hi]], dim=0),
+                                        pairs, Q, count if live_only else None)            # the block follows the queries
+            R.scatter_scores(logits, pairs, count, scores, lo, hi - lo)
+        out = R.rank_gallery_wide(scores, query_ids, gallery_ids, topk=topk, exclude=exclude)
+        counts = torch.cat(counts) if counts else torch.zeros((0,), dtype=torch.int32, device=dev)
+        return dict(scores=scores, counts=counts, **out)
 
     def track_step(self, bank, sweep, boxes, labels, scores, carry=None, carry_inv=None, min_points=2, num_classes=8,
                    cap=None, n=None, crop_args=None, born=None, kill=None, frame_limit=10, replace_all=False,

@@ -284,6 +284,11 @@ SIGNATURES = {
     "pcr_bank_plan_rules_i32": "s PS",
     "pcr_scene_log_ok": "i iii",
     "pcr_scene_log_append_i32": "s PS",
+    # A12. ranking a wide gallery
+    "pcr_rank_wide_ok": "i iii",
+    "pcr_rank_fill_f32": "s FiiS",
+    "pcr_rank_scatter_f32": "s FIIFiiiiiS",
+    "pcr_rank_wide_f32": "s <RankParams>S",
     # B. fused model kernels
     "pcr_knn_prefix_f32": "s FIiiiiS",
     "pcr_knn_prefix2_f32": "s FIIiiiiiiS",

@@ -9,6 +9,10 @@ every row (top-k, the first hit and the average precision against identities; ti
 pcr_amd/nms.py), and `RankBook.add` adds a chunk's results to a table on the device.  `RankBook.metrics()` is the one host
 read.  `ReIDNet.retrieve` chains compare_pairs, match_gallery and the two launches; `evaluate_retrieval` walks a split of a
 `CropStore` through it.  INTEGRATION.md ("2h. Ranking a gallery") has the mapping and the rules.
+
+A gallery above MAX_GALLERY entries takes the wide route (section A12), opt-in: `fill_scores` once, `scatter_scores` per
+gallery block into the block's column window, `rank_gallery_wide` over the whole matrix (the row read from memory, not
+staged in LDS); `ReIDNet.retrieve_wide` chains them and `evaluate_retrieval(gallery_block=)` walks a split through it.
 """
 import ctypes
 
@@ -19,6 +23,7 @@ from . import _lib as L
 from . import abi
 
 MAX_QUERIES, MAX_GALLERY, MAX_K, MAX_RANKS = 65535, 4096, 64, 8      # PCR_RANK_MAX_*
+WIDE_MAX_GALLERY, WIDE_MAX_TRUE = 4194304, 4096                      # PCR_RANK_WIDE_MAX_* (section A12)
 OUTPUTS = ("topk_idx", "topk_score", "n_cand", "n_true", "first_hit", "ap", "info")
 _WHO = "pcr_amd.retrieval"
 
@@ -79,6 +84,65 @@ def rank_gallery(scores, query_ids, gallery_ids, topk=10, exclude=None, out=None
     return {k: out[k] for k in OUTPUTS}
 
 
+def rank_wide_ok(Q, G, K=1):
+    """whether the section-A12 entry points take Q queries, G gallery entries (up to WIDE_MAX_GALLERY) and K ranks"""
+    return bool(L.load().pcr_rank_wide_ok(int(Q), int(G), int(K)))
+
+
+def fill_scores(scores):
+    """pcr_rank_fill_f32: every element of scores (Q, G) float32 becomes -inf ("not a candidate"); -> scores"""
+    scores = L.tensor(scores, _WHO, "scores", torch.float32, shape=(None, None))
+    Q, G = scores.shape
+    L.require(rank_wide_ok(Q, G), _WHO, "Q=%d G=%d is out of range (pcr_rank_wide_ok)", Q, G)
+    L.require_cuda(scores)
+    L.run.pcr_rank_fill_f32(scores, Q, G, L.stream_ptr())
+    return scores
+
+
+def scatter_scores(logits, pairs, count, scores, col0, width):
+    """pcr_rank_scatter_f32: the scatter of `score_matrix` into the column window [col0, col0 + width) of scores (Q, G):
+    logits (cap,), pairs (cap, 2) int32 with the gallery index counted from col0, count (1,) int32 on the device;
+    scores[q, col0 + g] = logits[k] for k < min(count, cap) and pairs[k] = (q, g) inside [0, Q) x [0, width); every other
+    element is left as it is (`fill_scores` first).  The pairs must be distinct.  -> scores"""
+    scores = L.tensor(scores, _WHO, "scores", torch.float32, shape=(None, None))
+    (Q, G), col0, width = scores.shape, int(col0), int(width)
+    pairs = L.tensor(pairs, _WHO, "pairs", torch.int32, shape=(None, 2))
+    cap = pairs.shape[0]
+    logits = L.tensor(logits, _WHO, "logits", torch.float32, shape=(cap,))
+    count = L.tensor(count, _WHO, "count", torch.int32, numel=1)
+    L.require(rank_wide_ok(Q, G) and col0 >= 0 and width >= 0 and col0 + width <= G and cap <= Q * width, _WHO,
+              "Q=%d G=%d cap=%d col0=%d width=%d is out of range (pcr_rank_scatter_f32)", Q, G, cap, col0, width)
+    L.require_cuda(logits, pairs, count, scores)
+    L.run.pcr_rank_scatter_f32(logits, pairs, count, scores, Q, G, cap, col0, width, L.stream_ptr())
+    return scores
+
+
+def rank_gallery_wide(scores, query_ids, gallery_ids, topk=10, exclude=None, out=None):
+    """pcr_rank_wide_f32: `rank_gallery` for a gallery of up to WIDE_MAX_GALLERY entries -- the same arguments, the same
+    dict, the same rules and, for G <= MAX_GALLERY, the same bits; the row is read from memory (twice at the most) instead
+    of staged in LDS.  One rule more: a query with more than WIDE_MAX_TRUE true candidates is not ranked and gets info 2
+    (its outputs are a flagged query's; a NaN candidate, info 1, takes precedence)."""
+    scores = L.tensor(scores, _WHO, "scores", torch.float32, shape=(None, None))
+    (Q, G), K = scores.shape, int(topk)
+    L.require(rank_wide_ok(Q, G, K), _WHO, "Q=%d G=%d topk=%d is out of range (pcr_rank_wide_ok)", Q, G, K)
+    dev = scores.device
+    if query_ids is None:
+        query_ids = torch.full((Q,), -1, dtype=torch.int32, device=dev)
+    if gallery_ids is None:
+        gallery_ids = torch.full((G,), -1, dtype=torch.int32, device=dev)
+    if out is None:
+        out = rank_buffers(Q, K, dev)
+    L.require(isinstance(out, dict) and all(k in out for k in OUTPUTS), _WHO, "out must hold %s", ", ".join(OUTPUTS))
+    sizes = dict(scores=Q * G, query_ids=Q, gallery_ids=G, exclude=Q, topk_idx=Q * K, topk_score=Q * K, n_cand=Q, n_true=Q,
+                 first_hit=Q, ap=Q, info=Q)
+    p = abi.RankParams()
+    p.Q, p.G, p.K = Q, G, K
+    abi.fill(p, dict({k: out[k] for k in OUTPUTS}, scores=scores, query_ids=query_ids, gallery_ids=gallery_ids,
+                     exclude=exclude), sizes, who=_WHO)
+    L.run.pcr_rank_wide_f32(ctypes.byref(p), L.stream_ptr())
+    return {k: out[k] for k in OUTPUTS}
+
+
 def metrics_of(counts, sums, ranks):
     """the table on the host (counts: 3 + len(ranks) ints, sums: 2 floats) -> cmc@r per rank, mAP, mrr (NaN when no query
     was scored) and the raw counters scored (a true candidate exists), unscored (none does), flagged (a NaN)"""
@@ -114,7 +178,9 @@ class RankBook:
         """pcr_rank_accumulate: result = rank_gallery's (or retrieve's) dict; valid = a (1,) int32 device tensor (or an
         int): only the first clamp(valid, 0, Q) queries count (the rest is a chunk's padding); gallery = the number of
         gallery entries G the ranks are held against (every rank must lie in [1, G]); by default the width of
-        result['scores'] when retrieve returned it, the largest rank otherwise."""
+        result['scores'] when retrieve returned it, the largest rank otherwise.  The launch uses G only to bound the
+        ranks, and a book's ranks are at most MAX_GALLERY already: for a wide gallery (rank_gallery_wide, retrieve_wide)
+        pass gallery=min(G, MAX_GALLERY), as evaluate_retrieval does."""
         t = {k: result[k] for k in ("n_true", "first_hit", "info", "ap")}
         if isinstance(valid, int):
             valid = torch.tensor([valid], dtype=torch.int32, device=self.device)
@@ -181,17 +247,30 @@ def _encode(model, clouds, batch):
 
 
 def evaluate_retrieval(model, store, split, n=None, seed=0, topk=10, ranks=(1, 5, 10), query_chunk=64, min_points=2,
-                       num_classes=None, live_only=True, encode_batch=256):
+                       num_classes=None, live_only=True, encode_batch=256, gallery_block=None):
     """Retrieval over a `CropStore`: split = retrieval_split's six arrays.  The clouds come from store.gather(rows, n,
     keys=rows, seed=seed) (a row's sample depends on the row and the seed alone), the gallery is encoded once, the queries
     walk through `ReIDNet.retrieve` in chunks of query_chunk -- the last one padded with class -1, which joins nothing, the
     real count going to the book as `valid` -- and each chunk is added to a `RankBook`.  -> book.metrics() (the one host
     read) plus the per-query tensors of rank_gallery, (Q, ...) on the device, and the book itself under 'book'.
-    num_classes defaults to the store's table's."""
+    num_classes defaults to the store's table's.
+
+    gallery_block = an integer in [1, MAX_GALLERY] takes the wide route: a gallery of up to WIDE_MAX_GALLERY entries, every
+    chunk through `ReIDNet.retrieve_wide` in gallery blocks of that many entries, one (query_chunk, G) score buffer reused
+    by all chunks, the book's ranks held against min(G, MAX_GALLERY).  None is the narrow route, G <= MAX_GALLERY."""
     q_rows, g_rows, q_cls, g_cls, q_ids, g_ids = (np.asarray(a, dtype=np.int32) for a in split)
     Q, G, chunk = len(q_rows), len(g_rows), int(query_chunk)
-    L.require(1 <= G <= MAX_GALLERY, _WHO, "a gallery of %d entries: 1 to PCR_RANK_MAX_GALLERY = %d can be ranked", G, MAX_GALLERY)
-    L.require(chunk >= 1 and rank_ok(chunk, G, topk), _WHO, "query_chunk=%d G=%d topk=%d is out of range (pcr_rank_ok)", chunk, G, topk)
+    wide = gallery_block is not None
+    if wide:
+        L.require(1 <= int(gallery_block) <= MAX_GALLERY, _WHO, "gallery_block=%s: 1 to %d", gallery_block, MAX_GALLERY)
+        L.require(1 <= G <= WIDE_MAX_GALLERY, _WHO, "a gallery of %d entries: 1 to PCR_RANK_WIDE_MAX_GALLERY = %d can be ranked",
+                  G, WIDE_MAX_GALLERY)
+        L.require(chunk >= 1 and rank_wide_ok(chunk, G, topk), _WHO,
+                  "query_chunk=%d G=%d topk=%d is out of range (pcr_rank_wide_ok)", chunk, G, topk)
+    else:
+        L.require(1 <= G <= MAX_GALLERY, _WHO, "a gallery of %d entries: 1 to PCR_RANK_MAX_GALLERY = %d can be ranked; "
+                  "gallery_block= takes the wide route (up to %d entries)", G, MAX_GALLERY, WIDE_MAX_GALLERY)
+        L.require(chunk >= 1 and rank_ok(chunk, G, topk), _WHO, "query_chunk=%d G=%d topk=%d is out of range (pcr_rank_ok)", chunk, G, topk)
     L.require(len(q_cls) == Q and len(q_ids) == Q and len(g_cls) == G and len(g_ids) == G, _WHO, "the split's arrays do not agree")
     if num_classes is None:
         num_classes = int(store.table.num_classes) if getattr(store, "table", None) is not None else 8
@@ -204,16 +283,22 @@ def evaluate_retrieval(model, store, split, n=None, seed=0, topk=10, ranks=(1, 5
         g_rows_t, g_cls_t, g_ids_t = put(g_rows), put(g_cls), put(g_ids)
         g_clouds, g_sizes = store.gather(g_rows_t, n, keys=g_rows_t, seed=seed)
         g_xyz, g_feats = _encode(model, g_clouds, encode_batch)
+        wide_scores = torch.empty((chunk, G), dtype=torch.float32, device=dev) if wide else None
         for lo in range(0, Q, chunk):
             real = min(chunk, Q - lo)
             pad = lambda a, fill: np.concatenate([a[lo:lo + real], np.full(chunk - real, fill, np.int32)])   # noqa: E731
             rows_t, cls_t, ids_t = put(pad(q_rows, 0)), put(pad(q_cls, -1)), put(pad(q_ids, -1))
             clouds, sizes = store.gather(rows_t, n, keys=rows_t, seed=seed)
             xyz, feats = _encode(model, clouds, encode_batch)
-            res = model.retrieve(feats, xyz, cls_t, sizes, g_feats, g_xyz, g_cls_t, g_sizes, query_ids=ids_t,
-                                 gallery_ids=g_ids_t, topk=topk, min_points=min_points, num_classes=num_classes,
-                                 live_only=live_only)
-            book.add(res, valid=torch.tensor([real], dtype=torch.int32, device=dev), gallery=G)
+            if wide:
+                res = model.retrieve_wide(feats, xyz, cls_t, sizes, g_feats, g_xyz, g_cls_t, g_sizes, query_ids=ids_t,
+                                          gallery_ids=g_ids_t, topk=topk, min_points=min_points, num_classes=num_classes,
+                                          live_only=live_only, gallery_block=int(gallery_block), scores=wide_scores)
+            else:
+                res = model.retrieve(feats, xyz, cls_t, sizes, g_feats, g_xyz, g_cls_t, g_sizes, query_ids=ids_t,
+                                     gallery_ids=g_ids_t, topk=topk, min_points=min_points, num_classes=num_classes,
+                                     live_only=live_only)
+            book.add(res, valid=torch.tensor([real], dtype=torch.int32, device=dev), gallery=min(G, MAX_GALLERY))
             for k in OUTPUTS:
                 per_query[k].append(res[k][:real])
     out = book.metrics()

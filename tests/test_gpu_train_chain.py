@@ -1,7 +1,8 @@
 """GPU: the fused per-token chains of the attention blocks in training mode (csrc/train_chain_kernels.hip, round 5)
 against the unfused launches they replace (one launch per layer: train_ops.dense / tnorm, themselves pinned to torch
 autograd and to the reference's train_step goldens) and against plain torch autograd -- forward values, every
-gradient, ragged token counts, bit-reproducibility."""
+gradient, ragged token counts, bit-reproducibility.  The bounds of both chains against a float64 restatement, tile by
+tile and with no token masked out, are held by test_gpu_train_chain_forms.py."""
 import pytest
 import torch
 import torch.nn as nn

@@ -1888,6 +1888,81 @@ int pcr_grad_sumsq_f32(const pcr_opt_tensor *tab, const int *chunk_tensor, const
 int pcr_adamw_step_f32(const pcr_opt_tensor *tab, const int *chunk_tensor, const int *chunk_first, int n_chunks,
                        const double *part, float max_norm, float *grad_norm, pcr_stream_t stream);
 
+/* ------------------------------------------------- C2. auxiliary training losses ------------ */
+
+/* The two auxiliary losses of ReIDNet.forward_train with a hot path: get_kl_loss (ReIDNet.py:467-482) and
+ * get_triplet_loss (:538-582).  (cls and fp are two small heads composed from the launches of section C.)  Common rules:
+ * no host read, no allocation; every sum has one order fixed by the launch shape (per-thread strides in index order, a
+ * shuffle tree, the waves left to right) and the only atomics are integer ones, so every output is reproducible bit for
+ * bit; every launch can be captured.  No entry point takes a float or long scalar: margin and alpha travel in
+ * hyper (2) f32 ON THE DEVICE = (margin, alpha), like the upstream gradient gout (1) and the seed.
+ * info (1) is a word of sticky flags that the launches OR into and never clear:
+ *   PCR_AUX_INFO_KL_EMPTY      the batch holds no match or only matches: the empty group's mean counts as 0;
+ *   PCR_AUX_INFO_TRIPLET_NONE  no triplet was formed (no matching pair with a pool): the loss is 0;
+ *   PCR_AUX_INFO_TRIPLET_POOL  a matching pair found no row with another id: its row of neg is -1 (inactive).
+ * The reference gives NaN in the first two cases and raises in the third; that is the one deviation.
+ *
+ * kl.  h (2B, D) f32: row i is h1[i].flat, row B + i is h2[i].flat (the two halves of the contiguous (2B, C, N) tensor,
+ * D = C N); match (B) int32, nonzero = a match.  With x = log_softmax(h1[i]), t = log_softmax(h2[i]), p2 = exp(t):
+ *   kl[i] = (1/D) sum_j p2_j (t_j - x_j) = (1/D) [cross[i] - (lse[B + i] - lse[i])],  cross[i] = sum_j p2_j (h2_j - h1_j)
+ *   loss  = mean over non-matches of -kl[i]  +  mean over matches of kl[i]            (unscaled: alpha is the caller's)
+ * pcr_kl_pairs_fwd_f32 -> lse (2B), cross (B), kl (B), loss (1), counts (2) int32 = (non-matches, matches).  One workgroup
+ * per pair makes ONE pass over the two rows with an online maximum and sum (any D >= 1); one finalising workgroup counts
+ * the groups and adds the pairs in index order in binary64.
+ * pcr_kl_pairs_bwd_f32: with w_i = +-gout[0] / (counts[group of i] * D) (minus for a non-match), in closed form
+ *   dh[i][k]     = w_i (p1_k - p2_k)
+ *   dh[B + i][k] = w_i p2_k [(h2_k - h1_k) - cross[i]]
+ * every element of dh (2B, D) is written. */
+#define PCR_AUX_INFO_KL_EMPTY 1
+#define PCR_AUX_INFO_TRIPLET_NONE 2
+#define PCR_AUX_INFO_TRIPLET_POOL 4
+int pcr_kl_pairs_fwd_f32(const float *h, const int *match, float *lse, float *cross, float *kl, float *loss, int *counts,
+                         int *info, int B, int D, pcr_stream_t stream);
+int pcr_kl_pairs_bwd_f32(const float *h, const int *match, const float *lse, const float *cross, const int *counts,
+                         const float *gout, float *dh, int B, int D, pcr_stream_t stream);
+
+/* triplet.  For every matching pair i the anchor is row i of h (2B, D), the positive row B + i, and T negatives are
+ * rows whose id differs from ids[i]; the loss is TripletMarginLoss(margin, p = 2) over all triplets,
+ * d(x, y) = || (x - y) + PCR_PAIR_DIST_EPS ||_2.  pcr_triplet_ok(B, T): 2B <= PCR_TRIPLET_MAX_ROWS (the pool and the
+ * counters of a pair live in LDS) and B T < 2^31.
+ *
+ * pcr_triplet_draw_i32: ids (2B) int32, match (B) int32 -> neg (B, T) int32, one wave per pair.  The row of a
+ * non-matching pair is -1.  For a matching pair the pool is the list of rows r in [0, 2B) with ids[r] != ids[i], in index
+ * order, P entries; with W_t = rand[i T + t] (rand (B T) int32 read as bits, for tests) or W(seed, 3, i, t) of section A6
+ * and pick(u, len) = ((uint64)u * len) >> 32:
+ *   P == 0: the row is -1 and PCR_AUX_INFO_TRIPLET_POOL is set;
+ *   P <  T: neg[i][t] = pool[pick(W_t, P)]                                     (with replacement)
+ *   P >= T: for t = 0 .. T - 1: j = t + pick(W_t, P - t); swap(pool[t], pool[j]); neg[i][t] = pool[t]
+ *           (T steps of a Fisher-Yates shuffle: without replacement) -- torch.multinomial's replacement= rule of the
+ *           reference (:554).  seed is a DEVICE pointer to one int64 (NULL = 0) that the caller advances after the draw,
+ *           so a replayed graph draws afresh.  The stream of samples is not torch's; the distribution is.
+ *
+ * pcr_pair_dist_f32: a (B, D), h (R, D) -> dist (B, R) = || (a_i - h_r) + eps ||_2 by direct differences: a 32 x 32 tile per
+ * workgroup, D in chunks of 32 through LDS, one f32 accumulator per entry that walks d = 0 .. D - 1.  (Not the Gram form:
+ * |a|^2 + |h|^2 - 2 a.h cancels where anchor and positive converge.)  Any D >= 1.  The positive's distance is column B + i.
+ *
+ * pcr_triplet_select_f32: dist (B, 2B), neg (B, T), match (B), hyper -> E (B, 2B), pair_loss (B), loss (1), count (1)
+ * int32.  A row takes part when match[i] != 0 and neg[i][0] >= 0; its triplet t is ACTIVE when
+ * v = dist[i][B + i] - dist[i][neg[i][t]] + margin > 0 (an entry of neg outside [0, 2B) is skipped).
+ *   pair_loss[i] = sum of the active v;  count = T * (rows taking part);  loss = alpha * sum_i pair_loss[i] / count
+ *   E[i][r]      = #{t active, neg[i][t] = r} / dist[i][r];   E[i][B + i] -= k_i / dist[i][B + i], k_i = #{t active}
+ *   a coefficient whose distance is exactly 0 is 0.  count == 0: loss 0, PCR_AUX_INFO_TRIPLET_NONE.
+ *
+ * pcr_pair_dist_bwd_f32: with g = gout[0] * alpha / count (0 when count == 0), all read on the device,
+ *   da[i] = -g sum_r E[i][r] ((a_i - h_r) + eps)          dh[r] = +g sum_i E[i][r] ((a_i - h_r) + eps)
+ * by direct differences; an output row belongs to one workgroup per 1024 columns, which adds the other side's rows in
+ * index order (coefficients through LDS, zero ones skipped).  The anchors are rows of h: the caller adds da into dh[:B]. */
+#define PCR_PAIR_DIST_EPS 1e-6f
+#define PCR_TRIPLET_MAX_ROWS 8192
+int pcr_triplet_ok(int B, int T);
+int pcr_triplet_draw_i32(const int *ids, const int *match, const int *rand, const long long *seed, int *neg, int *info,
+                         int B, int T, pcr_stream_t stream);
+int pcr_pair_dist_f32(const float *a, const float *h, float *dist, int B, int R, int D, pcr_stream_t stream);
+int pcr_triplet_select_f32(const float *dist, const int *neg, const int *match, const float *hyper, float *E,
+                           float *pair_loss, float *loss, int *count, int *info, int B, int T, pcr_stream_t stream);
+int pcr_pair_dist_bwd_f32(const float *a, const float *h, const float *E, const float *gout, const float *hyper,
+                          const int *count, float *da, float *dh, int B, int R, int D, pcr_stream_t stream);
+
 /* ---- measurement aid (bench.py; not on the hot path) ---- */
 
 /* Sustained f32-MFMA probe: n_wg workgroups (one per CU: pass the CU count) each run iters * 16

@@ -92,6 +92,19 @@ __device__ __forceinline__ uint32_t pcr_mix32(uint32_t x) {
   return x;
 }
 
+// h of pcr.h (section A6) after (seed, stream, key): W(seed, stream, key, k) = pcr_mix32(h ^ k); pick(u, len) beside it.
+// The crop store draws with streams 1 and 2, the triplet draw of section C2 with stream 3.
+__device__ __forceinline__ uint32_t pcr_word_prefix(unsigned long long seed, uint32_t stream, uint32_t key) {
+  uint32_t h = pcr_mix32((uint32_t)seed ^ 0x9e3779b9u);
+  h = pcr_mix32(h ^ (uint32_t)(seed >> 32));
+  h = pcr_mix32(h ^ stream);
+  return pcr_mix32(h ^ key);
+}
+
+__device__ __forceinline__ uint32_t pcr_pick(uint32_t u, uint32_t len) {
+  return (uint32_t)(((unsigned long long)u * len) >> 32);
+}
+
 #include "wave_ops.h"   // the cross-lane primitives: DPP move, row / wave reductions, scans, the wave sorting network
 
 // ---- MFMA token (round 6).  The counters say the wave-autonomous kernels overlap almost nothing: matrix pipe busy 0.57 +

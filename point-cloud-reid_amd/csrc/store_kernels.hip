@@ -10,17 +10,7 @@ constexpr int kGatherWaves = 4;          // clouds per workgroup: one wave each
 constexpr int kPairThreads = 64;         // items per workgroup: one thread each
 constexpr uint32_t kStreamPairs = 1u, kStreamGather = 2u;
 
-// h of pcr.h after (seed, stream, key): W = pcr_mix32(h ^ k)
-__device__ __forceinline__ uint32_t store_prefix(unsigned long long seed, uint32_t stream, uint32_t key) {
-  uint32_t h = pcr_mix32((uint32_t)seed ^ 0x9e3779b9u);
-  h = pcr_mix32(h ^ (uint32_t)(seed >> 32));
-  h = pcr_mix32(h ^ stream);
-  return pcr_mix32(h ^ key);
-}
-
-__device__ __forceinline__ uint32_t store_pick(uint32_t u, uint32_t len) {
-  return (uint32_t)(((unsigned long long)u * len) >> 32);
-}
+// (the word's prefix h and pick are pcr_common.h's pcr_word_prefix / pcr_pick: W = pcr_mix32(h ^ k))
 
 // One wave per cloud.  The lanes walk the cloud's 3n output floats, so every store of the wave is 64 consecutive words;
 // the three lanes of a slot derive the same word and read the three neighbouring floats of the same stored point.
@@ -57,12 +47,12 @@ __global__ __launch_bounds__(kGatherWaves *kWave) void store_gather_kernel(
     for (int f = lane; f < nf; f += kWave) out[f] = src[f];
     return;
   }
-  const uint32_t h = store_prefix(seed ? seed[0] : 0ull, kStreamGather, keys ? (uint32_t)keys[b] : (uint32_t)b);
+  const uint32_t h = pcr_word_prefix(seed ? seed[0] : 0ull, kStreamGather, keys ? (uint32_t)keys[b] : (uint32_t)b);
   const uint32_t *r = rnd ? rnd + (size_t)b * n : nullptr;
   for (int f = lane; f < nf; f += kWave) {
     const int s = f / 3, c = f - 3 * s;
     const uint32_t u = r ? r[s] : pcr_mix32(h ^ (uint32_t)s);
-    out[f] = src[3 * (size_t)store_pick(u, len) + c];
+    out[f] = src[3 * (size_t)pcr_pick(u, len) + c];
   }
 }
 
@@ -109,22 +99,22 @@ __global__ __launch_bounds__(kPairThreads) void store_train_pairs_kernel(
   } else {
     Draws d;
     d.r = rnd ? rnd + (size_t)b * PCR_STORE_PAIR_WORDS : nullptr;
-    d.h = store_prefix(seed ? seed[0] : 0ull, kStreamPairs, (uint32_t)keys[b]);
+    d.h = pcr_word_prefix(seed ? seed[0] : 0ull, kStreamPairs, (uint32_t)keys[b]);
     d.k = 0;
     l1 = c;
     i1 = t.obj_id[o];
     if (d.next() >> 31) {
-      const uint32_t ia = store_pick(d.next(), (uint32_t)n);
-      const uint32_t j = store_pick(d.next(), (uint32_t)(n - 1));
+      const uint32_t ia = pcr_pick(d.next(), (uint32_t)n);
+      const uint32_t j = pcr_pick(d.next(), (uint32_t)(n - 1));
       const uint32_t ib = j + (j >= ia ? 1u : 0u);
       r1 = t.nums_rows[nb + ia];
       r2 = t.nums_rows[nb + ib];
       l2 = c;
       i2 = i1;
     } else {
-      r1 = t.nums_rows[nb + store_pick(d.next(), (uint32_t)n)];
+      r1 = t.nums_rows[nb + pcr_pick(d.next(), (uint32_t)n)];
       // the bucket of the r-th observation in bucket order: the host's draw from the object's own distribution
-      const int r = (int)store_pick(d.next(), (uint32_t)n);
+      const int r = (int)pcr_pick(d.next(), (uint32_t)n);
       const int *bo = t.bucket_off + (size_t)o * NB;
       int dens = 0;
       while (dens < NB - 1 && bo[dens + 1] - bo[0] <= r) ++dens;
@@ -135,7 +125,7 @@ __global__ __launch_bounds__(kPairThreads) void store_train_pairs_kernel(
       if (db >= 0) {
         const int cb = po[db], cl = po[db + 1] - cb;
         for (int a = 0; a < PCR_STORE_PAIR_ATTEMPTS; ++a) {
-          const int cand = t.pool_objs[cb + store_pick(d.next(), (uint32_t)cl)];
+          const int cand = t.pool_objs[cb + pcr_pick(d.next(), (uint32_t)cl)];
           if (cand != o) {
             other = cand;
             break;
@@ -157,7 +147,7 @@ __global__ __launch_bounds__(kPairThreads) void store_train_pairs_kernel(
         flags |= PCR_STORE_INFO_ITEM;      // (a table CropStore refuses to build)
         r1 = l1 = i1 = -1;
       } else {
-        r2 = t.bucket_rows[oo[fb] + store_pick(d.next(), (uint32_t)(oo[fb + 1] - oo[fb]))];
+        r2 = t.bucket_rows[oo[fb] + pcr_pick(d.next(), (uint32_t)(oo[fb + 1] - oo[fb]))];
         l2 = use_tp ? c : c + C;
         i2 = t.obj_fp[other] ? -1 : t.obj_id[other];
       }

@@ -126,6 +126,11 @@ class ReIDNet(nn.Module):
         self.use_dgcnn = use_dgcnn
         self.combine = combine
         self.triplet_sample_num = triplet_sample_num
+        self.triplet_cfg = dict(triplet_loss or {})
+        # the triplet draw's own seed (its device copy advances by one per draw) and, for tests, the words that take the
+        # generator's place: (B * triplet_sample_num) int32 on the device (pcr_triplet_draw_i32's rand)
+        self.triplet_seed = 0
+        self.triplet_rand = None
         self._head_plan = None
         self._head_key = None
 
@@ -1073,12 +1078,51 @@ class ReIDNet(nn.Module):
         return match_preds, match_loss, (o[:b], o[b:])
 
     def _check_losses(self):
-        # the constructor default enables every auxiliary loss (as in the reference), but every ReID
-        # config switches them off and builds no heads for them; only the match loss is on the hot path
-        for k in ("kl", "cls", "shape", "fp", "dense", "triplet"):
+        # match, cls, fp, kl and triplet run (pcr_amd/train_graph.py aux_losses); shape (chamfer distance over dense
+        # clouds, a Conv1d / BatchNorm1d head) and dense (a second encoder pass) have no HIP form
+        for k in ("shape", "dense"):
             if self.losses_to_use.get(k, False):
-                raise NotImplementedError("loss '%s' is not part of the siamese matching hot path; the ReID "
-                                          "configs train/evaluate with match only (SURVEY.md section 8)" % k)
+                raise NotImplementedError("loss '%s' is not part of the siamese matching hot path; the ReID configs "
+                                          "train with match, cls, fp, kl and triplet at most (SURVEY.md section 8)" % k)
+        if self.losses_to_use.get("triplet", False) and self.triplet_cfg.get("p", 2) != 2:
+            raise L.PcrError("triplet_loss: p = %r; the distance kernels implement p = 2 only" % (self.triplet_cfg.get("p"),))
+
+    def _aux_on(self):
+        return any(self.losses_to_use.get(k, False) for k in ("cls", "fp", "kl", "triplet"))
+
+    def _object_head(self, name, pooled):
+        head = getattr(self, name + "_head")
+        if not (isinstance(head, nn.Sequential) and len(head) == 2 and isinstance(head[0], LinearRes)
+                and isinstance(head[1], nn.Linear)):
+            raise L.PcrError("%s_head must be [LinearRes, Linear] (the reference's configs); got %s"
+                             % (name, "None" if head is None else [type(m).__name__ for m in head]
+                                if isinstance(head, nn.Sequential) else type(head).__name__))
+        if self.training:
+            from pcr_amd import train_graph
+            return train_graph.rows_head(head, pooled)
+        from pcr_amd import rows
+        x = pooled.t().contiguous().unsqueeze(0)                 # (1, F, M): channel-major, objects as tokens
+        return rows.downsample_points(head, x)[0].t()
+
+    def object_heads(self, h):
+        """the per-object heads of cls_forward / fp_forward (reference ReIDNet.py:348-384) on encoded objects h (M, C, N)
+        -- siamese_forward's cat(h1, h2), forward_inference's features, the tracker's bank -- -> dict(cls=(M, classes)
+        logits or None, fp=(M,) logits or None); a head is evaluated when its loss is switched on.  Pooled once for both
+        (get_pooled_feats).  In training mode every launch has a backward (pcr_amd/train_graph.py)."""
+        out = dict(cls=None, fp=None)
+        want = [k for k in ("cls", "fp") if self.losses_to_use.get(k, False)]
+        if not want:
+            return out
+        L.require_cuda(h)
+        if self.training:
+            from pcr_amd import train_graph
+            pooled = train_graph.pooled_feats(self, h)
+        else:
+            pooled = self.get_pooled_feats(h)
+        for k in want:
+            y = self._object_head(k, pooled)
+            out[k] = y if k == "cls" else y.reshape(-1)
+        return out
 
     # ------------------------------------------------------------------ mmdet-style entry points
     def forward(self, return_loss=True, **kwargs):
@@ -1096,8 +1140,17 @@ class ReIDNet(nn.Module):
         device = sparse_1.device
         xyz1, xyz2, h1, h2 = self.siamese_forward(sparse_1, sparse_2)
         h1, h2, xyz1, xyz2, match = self.get_match_supervision(h1, h2, xyz1, xyz2, id_1, id_2)
-        _, match_loss, _ = self.match_forward(h1, h2, xyz1, xyz2, match, log_vars, device)
-        losses["reid_loss"] = match_loss
+        _, match_loss, o = self.match_forward(h1, h2, xyz1, xyz2, match, log_vars, device)
+        loss = match_loss
+        if self._aux_on():
+            # match + cls + kl + fp + triplet, the reference's order (:632); with the four switches off nothing is launched
+            # or added and the match-only step keeps its bits
+            from pcr_amd import train_graph
+            for extra in train_graph.aux_losses(self, h1, h2, o, torch.cat([label_1, label_2], dim=0),
+                                                torch.cat([id_1, id_2], dim=0), match, log_vars):
+                if extra is not None:
+                    loss = loss + extra
+        losses["reid_loss"] = loss
         return losses, log_vars
 
     def forward_test(self, sparse_1, sparse_2, dense_1, dense_2, label_1, label_2, id_1, id_2, size_1, size_2,
@@ -1114,18 +1167,34 @@ class ReIDNet(nn.Module):
         match_preds, match_loss, _ = self.match_forward(h1, h2, xyz1, xyz2, match, None, device)
         labels = torch.cat([label_1, label_2], dim=0)
         zero = torch.tensor([0.0])
+        # cls, fp and kl as forward_train computes them (no triplet at test time, as in the reference :637-689)
+        cls_preds = fp_preds = None
+        cls_loss = fp_loss = kl_loss = None
+        if self._aux_on():
+            import torch.nn.functional as F
+            from pcr_amd import train_graph, train_ops
+            feats = train_graph._joined(h1, h2)
+            preds = self.object_heads(feats)
+            cls_preds, fp_preds = preds["cls"], preds["fp"]
+            if cls_preds is not None:
+                cls_loss = F.cross_entropy(cls_preds, labels.long()) * self.alpha["cls"]
+            if fp_preds is not None:
+                fp_loss = self.bce(fp_preds, (labels > 9).float()) * self.alpha["fp"]
+            if self.losses_to_use.get("kl", False):
+                st = train_graph.aux_state(self, feats.device)
+                kl_loss = train_ops.KlPairs.apply(feats, match.to(torch.int32), st.info)[0] * self.alpha["kl"]
         results = OrderedDict()
         results["val_dense_loss"] = zero.clone()
-        results["val_fp_loss"] = zero.clone()
+        results["val_fp_loss"] = zero.clone() if fp_loss is None else torch.tensor([fp_loss])
         results["val_match_loss"] = torch.tensor([match_loss])
         results["val_shape_loss"] = zero.clone()
-        results["val_cls_loss"] = zero.clone()
-        results["val_kl_loss"] = zero.clone()
+        results["val_cls_loss"] = zero.clone() if cls_loss is None else torch.tensor([cls_loss])
+        results["val_kl_loss"] = zero.clone() if kl_loss is None else torch.tensor([kl_loss])
         results["val_match_preds"] = match_preds
         results["val_match_gt"] = match
-        results["val_cls_preds"] = None
+        results["val_cls_preds"] = cls_preds
         results["val_cls_gt"] = labels
-        results["val_fp_preds"] = None
+        results["val_fp_preds"] = fp_preds
         results["val_fp_gt"] = (labels > 9).float()
         results["match_classes"] = torch.cat([label_1.unsqueeze(1), label_2.unsqueeze(1)], dim=1)
         results["is_fp"] = torch.logical_or(label_1 > 9, label_2 > 9)

@@ -385,6 +385,14 @@ SIGNATURES = {
     "pcr_opt_chunk": "i ",
     "pcr_grad_sumsq_f32": "s PIIiPS",
     "pcr_adamw_step_f32": "s PIIiPfFS",
+    # C2. auxiliary training losses
+    "pcr_kl_pairs_fwd_f32": "s FIFFFFIIiiS",
+    "pcr_kl_pairs_bwd_f32": "s FIFFIFFiiS",
+    "pcr_triplet_ok": "i ii",
+    "pcr_triplet_draw_i32": "s IIIPIIiiS",
+    "pcr_pair_dist_f32": "s FFFiiiS",
+    "pcr_triplet_select_f32": "s FIIFFFFIIiiS",
+    "pcr_pair_dist_bwd_f32": "s FFFFFIFFiiiS",
     # measurement aid
     "pcr_wall_clock_khz": "i ",
     "pcr_last_launch_arith": "i ",

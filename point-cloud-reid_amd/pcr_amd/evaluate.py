@@ -127,12 +127,19 @@ def build_val_set(val_cfg, crop_root, meta=None, max_combinations=None, seed=Non
     return ds, table
 
 
+def _head_width(model, name):
+    """outputs per object of a [LinearRes, Linear] head, 0 without one"""
+    head = getattr(model, name + "_head", None)
+    return int(head[-1].out_features) if isinstance(head, torch.nn.Sequential) and hasattr(head[-1], "out_features") else 0
+
+
 def evaluate_model(model, dataset, batch_size, seed=0, device="cuda", rank=None, world=None, cls_to_idx=None,
                    num_classes=None, on_batch=None, store=None):
     """multi_gpu_test + dataset.evaluate for one model over one ValPairs: this rank's contiguous shard of the pairs in
     batches of `batch_size` through forward_test, logits gathered in pair order on every rank, metrics from the gathered
     set.  -> dict(val_match_acc, f1 / precision / recall, per-class and per-bucket accuracies, `tables`, `logits`,
-    `targets`, `num_pairs`, `world`)
+    `targets`, `num_pairs`, `world`; val_cls_acc / val_fp_acc when the model's cls / fp loss is on: forward_test's
+    per-object predictions are gathered like the logits)
     store: a pcr_amd.store.CropStore over the dataset's crops -- the batches then come from `store.val_batch` (two
     launches, no host read; the dataset's pair list is uploaded once if the store holds none), keyed by the GLOBAL pair
     index, so a pair's clouds are the same bits on any number of ranks and at any batch size.  Its samples are another
@@ -166,7 +173,15 @@ def evaluate_model(model, dataset, batch_size, seed=0, device="cuda", rank=None,
             (res,) = model(return_loss=False, **batch)
             if on_batch is not None:
                 on_batch(b0, batch, res)
-            local.append({k: res[k].detach() for k in ("val_match_preds",) + keep})
+            row = {k: res[k].detach() for k in ("val_match_preds",) + keep}
+            # the per-object heads, when their losses are on: forward_test returns cat(side 1, side 2) rows; kept per PAIR
+            # (b, 2 * width) so that they shard and gather like every other per-pair tensor
+            for k in ("cls", "fp"):
+                if res.get("val_%s_preds" % k) is not None:
+                    for key in ("val_%s_preds" % k, "val_%s_gt" % k):
+                        t = res[key].detach()
+                        row[key] = t.reshape(2, t.shape[0] // 2, -1).transpose(0, 1).reshape(t.shape[0] // 2, -1)
+            local.append(row)
     if was_training:
         model.train()
     dev = torch.device(device)
@@ -185,6 +200,18 @@ def evaluate_model(model, dataset, batch_size, seed=0, device="cuda", rank=None,
             "match_classes": gathered("match_classes", 2, torch.float32).long(),
             "num_points": gathered("num_points", 2, torch.float32).long(),
             "val_vis_gt_all": gathered("val_vis_gt_all", 2, torch.float32).long()}
+    # (every rank runs the same model: a head is on everywhere or nowhere; a rank without pairs learns the width from
+    # the model)
+    widths = {"cls": _head_width(model, "cls"), "fp": 1}
+    for k in ("cls", "fp"):
+        if getattr(model, "losses_to_use", {}).get(k, False) and widths[k]:
+            w = widths[k]
+            full["val_%s_preds" % k] = gathered("val_%s_preds" % k, 2 * w, torch.float32).reshape(2 * n, w)
+            full["val_%s_gt" % k] = gathered("val_%s_gt" % k, 2, torch.float32).reshape(2 * n)
+    if "val_fp_preds" in full:
+        full["val_fp_preds"] = full["val_fp_preds"][:, 0]
+    if "val_cls_gt" in full:
+        full["val_cls_gt"] = full["val_cls_gt"].long()
     full = {k: v.cpu() for k, v in full.items()}
     out = metrics.evaluate([full], cls_to_idx={k: v for k, v in (cls_to_idx or {}).items() if v != -1} or None,
                            num_classes=num_classes)

@@ -86,6 +86,20 @@ def evaluate(results, cls_to_idx=None, num_classes=None):
         out.update(per_class_accuracy(logits, gt, r["match_classes"].cpu(), cls_to_idx, num_classes))
     if "num_points" in r:
         out.update(per_point_bucket_accuracy(logits, gt, r["num_points"].cpu()))
+    out.update(object_head_accuracy(r))
+    return out
+
+
+def object_head_accuracy(r):
+    """val_cls_acc / val_fp_acc of the per-object heads, by the reference's two lines (reidentification_base.py:150, :156),
+    for the predictions forward_test returned (a head whose loss is off returns None and has no entry here).  Rows are
+    objects; predictions and targets only have to be in the same order.  (The reference drops an accuracy of exactly
+    0 from its log -- `if cls_acc:` -- this reports it.)"""
+    out = {}
+    if "val_cls_preds" in r and "val_cls_gt" in r:
+        out["val_cls_acc"] = r["val_cls_preds"].cpu().argmax(dim=1).eq(r["val_cls_gt"].cpu()).float().mean().item()
+    if "val_fp_preds" in r and "val_fp_gt" in r:
+        out["val_fp_acc"] = decisions(r["val_fp_preds"].float().cpu()).eq(r["val_fp_gt"].float().cpu()).float().mean().item()
     return out
 
 

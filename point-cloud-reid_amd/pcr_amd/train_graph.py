@@ -243,6 +243,109 @@ def _head(model, pooled):
     return TO.dense(x, model.match_head[1].weight, model.match_head[1].bias).reshape(-1)   # (1, 1, B)
 
 
+def rows_head(head, pooled):
+    """a [LinearRes, Linear] head on pooled rows (M, F), samples as tokens -> (M, n_out)"""
+    x = pooled.t().contiguous().unsqueeze(0)                               # (1, F, M)
+    x = linear_res_rows(head[0], x)
+    return TO.dense(x, head[1].weight, head[1].bias)[0].t()                # (1, n_out, M) -> (M, n_out)
+
+
+def pooled_feats(model, h):
+    """ReIDNet.get_pooled_feats (ReIDNet.py:526-534) with a backward: (M, C, N) -> (M, 2C) for 'both', (M, N) for 'max'"""
+    if model.pool_type == "both":
+        return TO.PoolBoth.apply(h)
+    if model.pool_type == "max":
+        if h.shape[1] != model.output_sequence_size:
+            from . import _lib as L
+            raise L.PcrError("pool 'max' pools one window of %d channels per point; the features have %d"
+                             % (model.output_sequence_size, h.shape[1]))
+        return TO.ChannelMax.apply(h, model.output_sequence_size).reshape(h.shape[0], -1)
+    raise NotImplementedError("pool_type=%r" % model.pool_type)
+
+
+class AuxState:
+    """what the auxiliary-loss launches of one model read on the device: hyper = (margin, alpha['triplet']), the draw's
+    seed word (advanced in place after every draw, so a replayed graph draws afresh) and the sticky info word
+    (train_ops.AUX_INFO_*).  Filled by launches, never by a host copy."""
+
+    def __init__(self, model, device):
+        self.key = self.key_of(model, device)
+        margin, alpha, seed = self.key[1:]
+        self.hyper = torch.empty(2, dtype=torch.float32, device=device)
+        self.hyper[0].fill_(margin)
+        self.hyper[1].fill_(alpha)
+        self.seed = torch.full((1,), seed, dtype=torch.int64, device=device)
+        self.info = torch.zeros(1, dtype=torch.int32, device=device)
+
+    @staticmethod
+    def key_of(model, device):
+        return (str(device), float(model.triplet_cfg.get("margin", 1.0)), float(model.alpha.get("triplet", 1)),
+                int(model.triplet_seed))
+
+
+def aux_state(model, device):
+    st = model.__dict__.get("_pcr_aux")
+    if st is None or st.key != AuxState.key_of(model, device):
+        st = model.__dict__["_pcr_aux"] = AuxState(model, device)
+    return st
+
+
+def aux_losses(model, h1, h2, o, labels, ids, match, log_vars):
+    """The auxiliary losses of ReIDNet.forward_train (ReIDNet.py:606-630) that are switched on, each times its alpha:
+    -> [cls, kl, fp, triplet], None for one that is off -- the order in which the reference adds them to the match loss.
+    h1, h2 (B, C, N): the two encodings; o = (o1, o2): the stage-2 features of the matching (the triplet's rows with
+    use_o); labels, ids (2B) of cat(side 1, side 2); match (B) float.  No host read: the logged scalars go to
+    log_vars (a LazyScalars) as one device tensor.
+
+    cls / fp: get_pooled_feats over all 2B clouds, the [LinearRes, Linear] head through the dense and token-norm
+    launches, ATen for the scalar loss.  kl / triplet: train_ops.KlPairs / TripletLoss.  The triplet's negatives come
+    from pcr_triplet_draw_i32 and the model's own seed word (ReIDNet.triplet_seed; ReIDNet.triplet_rand replaces the
+    words): the stream of samples is not torch.multinomial's, the distribution is."""
+    import torch.nn.functional as F
+    from . import _lib as L
+    use = model.losses_to_use
+    out = [None, None, None, None]
+    names, vals = [], []
+    feats = _joined(h1, h2)
+    if use.get("cls") or use.get("fp"):
+        preds = model.object_heads(feats)
+        if use.get("cls"):
+            tgt = labels.long()
+            out[0] = F.cross_entropy(preds["cls"], tgt) * model.alpha["cls"]
+            names += ["cls_loss", "cls_acc"]
+            vals += [out[0].detach(), preds["cls"].detach().argmax(dim=1).eq(tgt).float().mean()]
+        if use.get("fp"):
+            tgt = (labels > 9).float()
+            out[2] = model.bce(preds["fp"], tgt) * model.alpha["fp"]
+            names += ["fp_loss", "fp_acc"]
+            vals += [out[2].detach(), (preds["fp"].detach() > 0).float().eq(tgt).float().mean()]       # sigmoid(x) > 0.5
+    if use.get("kl") or use.get("triplet"):
+        st = aux_state(model, feats.device)
+        match_i = match.detach().to(torch.int32)
+    if use.get("kl"):
+        out[1] = TO.KlPairs.apply(feats, match_i, st.info)[0] * model.alpha["kl"]
+        names.append("kl_loss")
+        vals.append(out[1].detach())
+    if use.get("triplet"):
+        if model.use_o:
+            if o is None or o[0] is None or not torch.is_tensor(o[0]):
+                raise L.PcrError("use_o: the triplet loss takes the matching's stage-2 features, which match_type=%r "
+                                 "does not return" % model.match_type)
+            oo = _joined(o[0], o[1])
+            rows = pooled_feats(model, oo) if model.training else model.get_pooled_feats(oo)
+        else:
+            rows = feats
+        ids_i = ids.detach().to(torch.int32)
+        neg = TO.triplet_draw(ids_i, match_i, model.triplet_sample_num, st.info, seed=st.seed, rand=model.triplet_rand)
+        st.seed.add_(1)
+        out[3] = TO.TripletLoss.apply(rows, neg, match_i, st.hyper, st.info)[0]      # (alpha is in hyper)
+        names.append("triplet_loss")
+        vals.append(out[3].detach())
+    if model.compute_summary and log_vars is not None and names:
+        log_vars.add_device(names, torch.stack([v.reshape(()).float() for v in vals]))
+    return out
+
+
 def supports(model):
     """the training graph covers: xcorr_eff + point-cat + pool 'both' (every point-cat config), xcorr-baseline + pool
     'both' (reid_pts_point-transformer_baseline_stnet.py), xcorr + pool 'both' (..._baseline_orig.py) and concat + pool 'max'

@@ -1197,3 +1197,114 @@ class Bmm(Function):
             dT = _f32(B, k, k, device=x.device)
             L.run.pcr_bmm_dt_f32(x, g, dT, B, k, N, L.stream_ptr())
         return dx, dT
+
+
+# ------------------------------------------------------------------------------- auxiliary losses (pcr.h C2) --
+AUX_INFO_KL_EMPTY, AUX_INFO_TRIPLET_NONE, AUX_INFO_TRIPLET_POOL = 1, 2, 4
+_AUX = "pcr_amd.train_ops"
+
+
+def _i32_dev(t, name, n):
+    return L.tensor(t, _AUX, name, torch.int32, numel=n)
+
+
+class KlPairs(Function):
+    """h (2B, ...) = [h1 ; h2], match (B) int32, info (1) int32 -> (the unscaled kl term of get_kl_loss, ReIDNet.py:467-482,
+    a 0-d tensor; kl (B) per pair, no gradient).  Forward and closed-form backward are pcr_kl_pairs_fwd / _bwd_f32."""
+
+    @staticmethod
+    def forward(ctx, h, match, info):
+        h = _dev(h)
+        L.require(h.dim() >= 2 and h.shape[0] >= 2 and h.shape[0] % 2 == 0, _AUX, "KlPairs: h must be (2B, ...), got %s",
+                  tuple(h.shape))
+        B = h.shape[0] // 2
+        D = h[0].numel()
+        match, info = _i32_dev(match, "match", B), _i32_dev(info, "info", 1)
+        L.require_cuda(match, info)
+        dev = h.device
+        lse, cross, kl, loss = _f32(2 * B, device=dev), _f32(B, device=dev), _f32(B, device=dev), _f32(1, device=dev)
+        counts = torch.empty(2, dtype=torch.int32, device=dev)
+        L.run.pcr_kl_pairs_fwd_f32(h, match, lse, cross, kl, loss, counts, info, B, D, L.stream_ptr())
+        ctx.save_for_backward(h, match, lse, cross, counts)
+        ctx.mark_non_differentiable(kl)
+        return loss.reshape(()), kl
+
+    @staticmethod
+    def backward(ctx, g, _gkl):
+        h, match, lse, cross, counts = ctx.saved_tensors
+        B = h.shape[0] // 2
+        dh = torch.empty_like(h)
+        L.run.pcr_kl_pairs_bwd_f32(h, match, lse, cross, counts, g.reshape(1).float().contiguous(), dh, B, h[0].numel(),
+                                   L.stream_ptr())
+        return dh, None, None
+
+
+def triplet_draw(ids, match, T, info, seed=None, rand=None):
+    """ids (2B) int32, match (B) int32 -> neg (B, T) int32 (pcr_triplet_draw_i32).  seed: a device int64 tensor of one
+    element (None: 0); rand (B T) int32: the words, in the place of W(seed, 3, pair, t)"""
+    B, T = match.numel(), int(T)
+    ids, match, info = _i32_dev(ids, "ids", 2 * B), _i32_dev(match, "match", B), _i32_dev(info, "info", 1)
+    rand = L.tensor(rand, _AUX, "rand", torch.int32, numel=B * T, optional=True)
+    if seed is not None:
+        L.require(isinstance(seed, torch.Tensor) and seed.dtype == torch.int64 and seed.numel() == 1, _AUX,
+                  "seed must be a device int64 tensor of one element")
+    L.require(B >= 1 and bool(L.load().pcr_triplet_ok(B, T)), _AUX,
+              "triplet: %d pairs with %d negatives each are beyond pcr_triplet_ok", B, T)
+    L.require_cuda(ids, match, info, rand, seed)
+    neg = torch.empty((B, T), dtype=torch.int32, device=ids.device)
+    L.run.pcr_triplet_draw_i32(ids, match, rand, L.ptr(seed), neg, info, B, T, L.stream_ptr())
+    return neg
+
+
+def pair_dist(a, h):
+    """a (B, D), h (R, D) -> dist (B, R) = || (a_i - h_r) + 1e-6 ||_2 (pcr_pair_dist_f32; no gradient: TripletLoss owns it)"""
+    a, h = _dev(a), _dev(h)
+    L.require(a.dim() == 2 and h.dim() == 2 and a.shape[1] == h.shape[1] and a.shape[0] and h.shape[0] and a.shape[1],
+              _AUX, "pair_dist: a (B, D) and h (R, D) of one width, got %s and %s", tuple(a.shape), tuple(h.shape))
+    dist = _f32(a.shape[0], h.shape[0], device=a.device)
+    L.run.pcr_pair_dist_f32(a, h, dist, a.shape[0], h.shape[0], a.shape[1], L.stream_ptr())
+    return dist
+
+
+class TripletLoss(Function):
+    """h (2B, ...) = [anchors ; positives], neg (B, T) int32, match (B) int32, hyper (2) f32 = (margin, alpha), info (1)
+    -> (alpha * TripletMarginLoss(margin, p = 2) over the triplets (pair i, row B + i, row neg[i][t]) of the matching
+    pairs, a 0-d tensor; dist (B, 2B) and count (1) int32, no gradient).  The anchors are rows of h: one gradient."""
+
+    @staticmethod
+    def forward(ctx, h, neg, match, hyper, info):
+        h = _dev(h)
+        L.require(h.dim() >= 2 and h.shape[0] >= 2 and h.shape[0] % 2 == 0, _AUX, "TripletLoss: h must be (2B, ...), got %s",
+                  tuple(h.shape))
+        B = h.shape[0] // 2
+        hf = h.reshape(2 * B, -1)
+        D = hf.shape[1]
+        L.require(isinstance(neg, torch.Tensor) and neg.dim() == 2 and neg.shape[0] == B and neg.shape[1] >= 1, _AUX,
+                  "TripletLoss: neg must be (%d, T)", B)
+        T = neg.shape[1]
+        neg, match, info = _i32_dev(neg, "neg", B * T), _i32_dev(match, "match", B), _i32_dev(info, "info", 1)
+        hyper = L.tensor(hyper, _AUX, "hyper", torch.float32, numel=2)
+        L.require(bool(L.load().pcr_triplet_ok(B, T)), _AUX,
+                  "triplet: %d pairs with %d negatives each are beyond pcr_triplet_ok", B, T)
+        L.require_cuda(neg, match, info, hyper)
+        dev = h.device
+        dist = _f32(B, 2 * B, device=dev)
+        L.run.pcr_pair_dist_f32(hf, hf, dist, B, 2 * B, D, L.stream_ptr())
+        E, pair_loss, loss = _f32(B, 2 * B, device=dev), _f32(B, device=dev), _f32(1, device=dev)
+        count = torch.empty(1, dtype=torch.int32, device=dev)
+        L.run.pcr_triplet_select_f32(dist, neg, match, hyper, E, pair_loss, loss, count, info, B, T, L.stream_ptr())
+        ctx.save_for_backward(hf, E, hyper, count)
+        ctx.shape = h.shape
+        ctx.mark_non_differentiable(dist, count)
+        return loss.reshape(()), dist, count
+
+    @staticmethod
+    def backward(ctx, g, _gd, _gc):
+        hf, E, hyper, count = ctx.saved_tensors
+        R, D = hf.shape
+        B = R // 2
+        da, dh = _f32(B, D, device=hf.device), _f32(R, D, device=hf.device)
+        L.run.pcr_pair_dist_bwd_f32(hf, hf, E, g.reshape(1).float().contiguous(), hyper, count, da, dh, B, R, D,
+                                    L.stream_ptr())
+        dh[:B] += da
+        return dh.view(ctx.shape), None, None, None, None

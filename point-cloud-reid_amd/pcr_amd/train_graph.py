@@ -22,15 +22,20 @@ def _cm(xyz):
     return xyz.transpose(1, 2).contiguous()
 
 
+def _tail_layers(merge, norm1, mlp, norm2, msg, res, residual):
+    """merge, LayerNorm, feed-forward on [res ; .], LayerNorm (+ res): one launch per layer"""
+    n1 = TO.tnorm(TO.dense(msg, merge.weight), norm1)
+    f0 = TO.dense(res, mlp[0].weight, x2=n1, relu=True)
+    return TO.tnorm(TO.dense(f0, mlp[2].weight), norm2, res=res if residual else None)
+
+
 def _tail(m, msg, res_in, residual):
-    """merge, LayerNorm, feed-forward on [res_in ; msg], LayerNorm (+ residual): ONE launch each way where the chain
-    kernel is instantiated (train_ops.attn_tail, round 5), else one launch per layer"""
+    """the tail of an attention block on [res_in ; msg]: ONE launch each way where the chain kernel is instantiated
+    (train_ops.attn_tail, round 5), else one launch per layer"""
     fused = TO.attn_tail(m, msg, res_in, residual)
     if fused is not None:
         return fused
-    n1 = TO.tnorm(TO.dense(msg, m.merge.weight), m.norm1)
-    f0 = TO.dense(res_in, m.mlp[0].weight, x2=n1, relu=True)
-    return TO.tnorm(TO.dense(f0, m.mlp[2].weight), m.norm2, res=res_in if residual else None)
+    return _tail_layers(m.merge, m.norm1, m.mlp, m.norm2, msg, res_in, residual)
 
 
 def _pos(pos_mlp, xyz_cm, add_to):
@@ -118,9 +123,8 @@ def local_self_attention(m, feat, xyz_cm):
     fp = _pos(m.pos_mlp_knn, xyz_cm, feat)
     qkv = TO.dense(fp, torch.cat([m.q_proj_knn.weight, m.k_proj_knn.weight, m.v_proj_knn.weight], dim=0))
     msg = TO.LocalAttn.apply(qkv, idx, int(m.nhead), ATTN_EPS)
-    n1 = TO.tnorm(TO.dense(msg, m.merge_knn.weight), m.norm1_knn)
-    f0 = TO.dense(feat, m.mlp_knn[0].weight, x2=n1, relu=True)
-    return TO.tnorm(TO.dense(f0, m.mlp_knn[2].weight), m.norm2_knn, res=feat)
+    # (the *_knn members never take the fused chain: no attn_tail here)
+    return _tail_layers(m.merge_knn, m.norm1_knn, m.mlp_knn, m.norm2_knn, msg, feat, True)
 
 
 def sa_edge_layer(sa, xyz, feats, s, knn_idx=None):

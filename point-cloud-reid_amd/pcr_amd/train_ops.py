@@ -4,219 +4,26 @@ ctypes parameter blocks, launches, and the torch.autograd.Functions that put the
 What runs where: every dense layer of the training graph -- the grouped set-abstraction MLPs with BatchNorm in
 batch-statistics mode (reference pointnet2_utils.py:333-360), the per-point tables of their first layer, the attention
 projections / feed-forward layers and the match head -- is a HIP launch forward and a HIP launch backward on the
-matrix core; autograd only strings the Functions together.  Nothing here has a CPU path.
+matrix core; autograd only strings the Functions together.  Nothing here has a CPU path.  The packed weight images the
+launches read, and their cache, are pcr_amd/train_pack.py's.
 """
 import ctypes
 import os
-import weakref
 
 import torch
 from torch.autograd import Function
 
 from . import _lib as L
-from ._lib import _c8, _c32, _f32, _p
-from .abi import _AttnHeadP, _AttnTailP, _BnBwd, _BnFwd, _LinAttnP, _ReduceJob, _TBwd, _TFwd, pcr_pack_desc
+from ._lib import _c32, _f32, _p
+from .abi import _AttnHeadP, _AttnTailP, _BnBwd, _BnFwd, _LinAttnP, _ReduceJob, _TBwd, _TFwd
 from .engine import _prof
+from .train_pack import (_PAD_CACHE, _PREPACKS, _Prepack, _dev, _lookup, pack_bf_T, pack_both, pack_both_bf,  # noqa: F401
+                         pack_dev, pad32, prepack)
 
 FUSE_POOL = True       # SaEdgeTrain: take the max over K inside the last layer's launch where the library offers it
 
 
-def _dev(t):
-    L.require_cuda(t)
-    L.require_f32(t)
-    return t.contiguous()
-
-
 # ------------------------------------------------------------------------------------------- launches --
-class _Prepack:
-    """Packed images (W and W^T) of every conv / linear weight of a model, refreshed by ONE launch per optimizer step
-    (`prepack(model)`, called by the Trainer) instead of one small launch per layer.  Looked up by storage address +
-    shape + Tensor._version: a weight that was not registered, or that changed since the refresh, simply misses and is
-    packed on the spot."""
-
-    def __init__(self):
-        self.key = None
-        self.entries = {}          # data_ptr -> [param, rows, cols, version, wp, wpT, wp_bf, wpT_bf]
-        self.descs = None
-        self.ndesc = 0
-        self.params = []
-        self.biases = {}
-        self.want_bf = set()       # data_ptrs whose bf16 hi / lo images are refreshed too (asked for once: pack_both_bf)
-
-    def build(self, params, biases):
-        import numpy as np
-        dev = params[0].device
-        self.params = params
-        old = self.entries
-        self.entries = {}
-        self.biases = {}           # id(bias) -> [param, version, zero-padded image]
-        self.want_bf &= {p.data_ptr() for p in params}
-        desc = np.zeros(len(params) + len(biases) + len(self.want_bf),
-                        dtype=pcr_pack_desc)
-        nbf = 0
-        for i, p in enumerate(params):
-            rows, cols = p.shape[0], p.numel() // p.shape[0]
-            n0, n1 = _c8(cols) * _c32(rows), _c8(rows) * _c32(cols)
-            prev = old.get(p.data_ptr())
-            if prev is not None and prev[0] is p and prev[1] == rows and prev[2] == cols:
-                e = list(prev)         # (a rebuild that only adds bf images keeps the f32 images where they are)
-                e[3] = -1
-                out = e[4]._base if e[4]._base is not None else e[4]
-            else:
-                out = _f32(n0 + n1, device=dev)
-                e = [p, rows, cols, -1, out[:n0], out[n0:], None, None]
-            desc[i] = (p.data_ptr(), out.data_ptr(), rows, cols, 0, 0)
-            if p.data_ptr() in self.want_bf:
-                b0 = L.load().pcr_packed_weight_bf16_floats(rows, cols)
-                b1 = L.load().pcr_packed_weight_bf16_floats(cols, rows)
-                if e[6] is None:
-                    ob = _f32(b0 + b1, device=dev)
-                    e[6], e[7] = ob[:b0], ob[b0:]
-                base = e[6]._base if e[6]._base is not None else e[6]
-                desc[len(params) + len(biases) + nbf] = (p.data_ptr(), base.data_ptr(), rows, cols, 1, 0)
-                nbf += 1
-            else:
-                e[6] = e[7] = None
-            self.entries[p.data_ptr()] = e
-        for i, b in enumerate(biases):          # cols = 0: a bias, copied into its zero-padded image by the same launch
-            out = torch.zeros(_c32(b.numel()), dtype=torch.float32, device=dev)
-            desc[len(params) + i] = (b.data_ptr(), out.data_ptr(), b.numel(), 0, 0, 0)
-            self.biases[id(b)] = [b, -1, out, b.data_ptr()]
-        self.ndesc = len(desc)
-        self.descs = torch.from_numpy(desc.view(np.uint8).copy()).to(dev)
-        self.key = tuple(id(p) for p in params) + tuple(id(b) for b in biases)
-
-    def refresh(self, params, biases=(), build_only=False):
-        params = [p for p in params if p.is_cuda and p.dim() >= 2 and p.dtype == torch.float32 and p.is_contiguous()]
-        biases = [b for b in biases if b.is_cuda and b.dim() == 1 and b.dtype == torch.float32 and b.is_contiguous()]
-        if not params:
-            return
-        if self.key != tuple(id(p) for p in params) + tuple(id(b) for b in biases) or \
-                any(e[0].data_ptr() != k for k, e in self.entries.items()) or \
-                any(e[0].data_ptr() != e[3] for e in self.biases.values()) or \
-                any((k in self.want_bf) != (e[6] is not None) for k, e in self.entries.items()):
-            self.build(params, biases)
-            if build_only:
-                return
-        elif build_only or all(e[3] == e[0]._version for e in self.entries.values()) and \
-                all(e[1] == e[0]._version for e in self.biases.values()):
-            return        # nothing changed since the last refresh (micro-steps of a gradient accumulation)
-        L.run.pcr_pack_weights_multi_f32(L.ptr(self.descs), self.ndesc, L.stream_ptr())
-        for e in self.entries.values():
-            e[3] = e[0]._version
-        for e in self.biases.values():
-            e[1] = e[0]._version
-
-    def lookup_bias(self, v, n):
-        e = self.biases.get(id(v))
-        if e is None or e[0] is not v or e[1] != v._version or e[2].numel() != _c32(n):
-            return None
-        return e[2]
-
-    def lookup(self, w):
-        e = self.entries.get(w.data_ptr())
-        if e is None or e[3] != w._version or w.dim() != 2 or w.shape[0] != e[1] or w.shape[1] != e[2] or \
-                not w.is_contiguous():
-            return None
-        return e[4], e[5]
-
-    def lookup_bf(self, w):
-        """-> (bf image of W, of W^T) | None (not registered / stale); registers the weight for the NEXT refresh"""
-        e = self.entries.get(w.data_ptr())
-        if e is None or w.dim() != 2 or w.shape[0] != e[1] or w.shape[1] != e[2] or not w.is_contiguous():
-            return None
-        self.want_bf.add(w.data_ptr())
-        if e[6] is None or e[3] != w._version:
-            return None
-        return e[6], e[7]
-
-
-# one table per model, owned by the model (dropped with it); `lookup` below searches the live tables
-_PREPACKS = weakref.WeakKeyDictionary()
-
-
-def _lookup(w):
-    for t in _PREPACKS.values():
-        hit = t.lookup(w)
-        if hit is not None:
-            return hit
-    return None
-
-
-def prepack(model, build_only=False):
-    """refresh the packed images of every conv / linear weight of `model` in one launch (Trainer.step calls this once
-    per iteration, after the previous update); pack_dev / pack_both then hit the cache.  Note for callers that keep an
-    autograd graph across iterations: the images are overwritten in place by the next refresh.
-    build_only: only (re)build the descriptor table and the image buffers if the set of weights or of requested bf16
-    images changed -- allocations and a host-to-device copy, which a stream capture cannot take: the Trainer calls this
-    right before it captures an iteration, whose own prepack() then is the one launch and nothing else."""
-    mods = [m for m in model.modules()
-            if isinstance(m, (torch.nn.Linear, torch.nn.Conv1d, torch.nn.Conv2d)) and m.weight is not None]
-    tab = _PREPACKS.get(model)
-    if tab is None:
-        tab = _PREPACKS[model] = _Prepack()
-    tab.refresh([m.weight for m in mods], [m.bias for m in mods if m.bias is not None], build_only=build_only)
-
-
-def pack_dev(w, transpose=False):
-    """(rows, cols) device matrix -> packed MFMA A-operand image of W or W^T (weights change every step, so the
-    pack runs on the device; inference packs once on the host)"""
-    hit = _lookup(w)
-    if hit is not None:
-        return hit[1] if transpose else hit[0]
-    w = _dev(w.detach())
-    rows, cols = w.shape
-    cout, cin = (cols, rows) if transpose else (rows, cols)
-    out = _f32(_c8(cin) * _c32(cout), device=w.device)
-    L.run.pcr_pack_weight_dev_f32(w, rows, cols, cols, int(transpose), out, L.stream_ptr())
-    return out
-
-
-def pack_both(w):
-    """-> (image of W, image of W^T) from ONE launch (forward and backward operands of a layer)"""
-    hit = _lookup(w)
-    if hit is not None:
-        return hit
-    w = _dev(w.detach())
-    rows, cols = w.shape
-    n0, n1 = _c8(cols) * _c32(rows), _c8(rows) * _c32(cols)
-    out = _f32(n0 + n1, device=w.device)
-    L.run.pcr_pack_weight_dev_f32(w, rows, cols, cols, 2, out, L.stream_ptr())
-    return out[:n0], out[n0:]
-
-
-_PAD_CACHE = {}
-
-
-def pad32(v, n):
-    """(n) vector -> zero-padded to a multiple of 32 (accumulator seeds are read 16 bytes at a time); cached per
-    (tensor, version): a bias is padded once per optimizer step, not once per launch"""
-    if v is None:
-        return None
-    for t in _PREPACKS.values():         # refreshed with the weights by the one launch per iteration
-        hit = t.lookup_bias(v, n)
-        if hit is not None:
-            return hit
-    # keyed by the tensor OBJECT (kept alive by the entry, so its id and storage cannot be recycled under the cache: a
-    # (data_ptr, version) key returned another tensor's bias once the allocator had reused the address) and its version
-    hit = _PAD_CACHE.get(id(v))
-    if hit is not None and hit[0] is v and hit[2].numel() == _c32(n) and hit[2].device == v.device:
-        if hit[1] != v._version:          # updated since (optimizer step): refresh the live part in place, one small copy
-            hit[2][:n].copy_(v.detach())
-            _PAD_CACHE[id(v)] = (v, v._version, hit[2])
-        return hit[2]
-    out = torch.zeros(_c32(n), dtype=torch.float32, device=v.device)
-    out[:n] = v.detach()
-    if len(_PAD_CACHE) > 256:
-        _PAD_CACHE.clear()
-    _PAD_CACHE[id(v)] = (v, v._version, out)
-    return out
-
-
-def groups(B, Ln):
-    return L.load().pcr_train_groups(B, Ln)
-
-
 def tdense_fwd(x, wp, cout, x2=None, isc=None, ish=None, in_relu=False, bias=None, res=None, out_relu=False,
                want_stats=False, pool=None):
     """-> (y, stats partials or None[, (ymax, argmax) or None when `pool` = (K, gamma) is given: the fused max over the K
@@ -310,36 +117,6 @@ def _bwd_bf():
     return TRAIN_PRECISION != "f32"
 
 
-def pack_both_bf(w):
-    """-> (bf16 hi / lo image of W, of W^T): the operands of the fused chains on the bf16 matrix core.  A weight of a
-    prepacked model is registered on its first request and refreshed by the one launch per iteration from then on; a
-    miss packs on the spot (two small launches)"""
-    for t in _PREPACKS.values():
-        hit = t.lookup_bf(w)
-        if hit is not None:
-            return hit
-    wd = _dev(w.detach())
-    if wd.dim() != 2:                     # (a 1x1 Conv1d / Conv2d weight (d, c, 1[, 1]): its matrix, as _Prepack.build takes it)
-        wd = wd.reshape(wd.shape[0], -1)
-    rows, cols = wd.shape
-    lib = L.load()
-    a = _f32(lib.pcr_packed_weight_bf16_floats(rows, cols), device=wd.device)
-    b = _f32(lib.pcr_packed_weight_bf16_floats(cols, rows), device=wd.device)
-    L.run.pcr_pack_weight_bf16_dev_f32(wd, rows, cols, cols, 0, a, L.stream_ptr())
-    L.run.pcr_pack_weight_bf16_dev_f32(wd, rows, cols, cols, 1, b, L.stream_ptr())
-    return a, b
-
-
-def pack_bf_T(w):
-    """(rows, cols) device weight -> bf16 hi / lo image of W^T (the dx operand of the bf16 backward), packed on the device:
-    one small launch per layer and iteration (the weights change every step)"""
-    wd = _dev(w.detach())
-    rows, cols = wd.shape
-    out = _f32(L.load().pcr_packed_weight_bf16_floats(cols, rows), device=wd.device)
-    L.run.pcr_pack_weight_bf16_dev_f32(wd, rows, cols, cols, 1, out, L.stream_ptr())
-    return out
-
-
 def tdense_bwd(g, x, cout, dy_mode=0, y=None, k=None, argmax=None, pooled=None, K=0, S=0, x2=None, isc=None, ish=None,
                iinv=None, in_relu=False, wpT=None, want_dstats=False, want_dw=True, wpT_bf=None):
     """-> dict(dx, dx2, dstats, dW (cout, cin1+cin2), db (cout)); see pcr_tdense_bwd in include/pcr.h"""
@@ -423,6 +200,42 @@ def bn_bwd_finalize(part, nparts, C, R, gamma, mean, invstd, centre=None):
     for k, v in o.items():
         setattr(p, k, _p(v))
     L.run.pcr_bn_bwd_finalize_f32(ctypes.byref(p), L.stream_ptr())
+    return o
+
+
+def _bn_nparts(B, C):
+    """rows of the partial sums pcr_bn_sums_f32 leaves over (B, C, L); a backward uses the value of its forward"""
+    return max(1, min(B, 2048 // max(C, 1)))
+
+
+def _require_batch(R, shape):
+    """torch's training-mode BatchNorm refuses a single value per channel (there is no variance to normalise by); so
+    does this path, before any launch, rather than return beta and update the running statistics"""
+    if R <= 1:
+        raise L.PcrError("Expected more than 1 value per channel when training, got input size %s" % (tuple(shape),))
+
+
+def _bn_refuse(*bns):
+    for bn in bns:
+        if bn.momentum is None:
+            # nn.BatchNorm2d(momentum=None) is the cumulative average 1 / num_batches_tracked (a device counter: a
+            # host read per layer and step); no reference config uses it -- refused rather than approximated
+            raise L.PcrError("BatchNorm with momentum=None (cumulative average) is not supported by the HIP training path")
+
+
+def _bn_batch_step(part, nparts, C, R, gamma, beta, bn, shift0=None, shift0_stride=1):
+    """The batch-statistics step of module `bn` (an nn.BatchNorm*d in training mode), the one copy of it: the refusal
+    (a Function with launches in front of this step calls _bn_refuse itself, ahead of them), pcr_bn_fwd_finalize over
+    the partial sums of R values per channel, the running statistics updated in place as the module does"""
+    _bn_refuse(bn)
+    track = bn.track_running_stats
+    o = bn_fwd_finalize(part, nparts, C, R, gamma, beta, bn.eps, bn.momentum, bn.running_mean if track else None,
+                        bn.running_var if track else None, shift0=shift0, shift0_stride=shift0_stride)
+    if track:
+        # (written through raw pointers by the finalize launch: keep Tensor._version honest for the caches)
+        torch.autograd.graph.increment_version([bn.running_mean, bn.running_var])
+        if bn.num_batches_tracked is not None:
+            bn.num_batches_tracked += 1
     return o
 
 
@@ -525,36 +338,22 @@ class SaEdgeTrain(Function):
         c1, c2, c3 = wa.shape[0], w2.shape[0], w3.shape[0]
         dev = xyz.device
         tab = None if tab is None else _dev(tab)
+        _bn_refuse(*bns)                                  # (all three, before the first layer's statistics are tracked)
         y1 = _f32(B, c1, Ln, device=dev)
         st1 = _f32(B, 2, _c32(c1), device=dev)
         with _prof("sa_l1_fwd[c1=%d,N=%d,S=%d,K=%d]" % (c1, N, S, K), 8.0 * B * Ln * c1, 4.0 * B * (Ln * (c1 + 1) + 2 * c1 * N)):
             L.run.pcr_sa_l1_fwd_f32(xyz, idx, tab, _dev(wa.detach()), b1.detach(), y1, st1, B, N, S, K, c1,
                                     L.stream_ptr())
-
-        def fin(st, nparts, C, gamma, beta, bn):
-            if bn.momentum is None:
-                # nn.BatchNorm2d(momentum=None) is the cumulative average 1 / num_batches_tracked (a device counter: a
-                # host read per layer and step); no reference config uses it -- refused rather than approximated
-                raise L.PcrError("BatchNorm with momentum=None (cumulative average) is not supported by the HIP training path")
-            o = bn_fwd_finalize(st, nparts, C, R, gamma, beta, bn.eps, bn.momentum,
-                                bn.running_mean if bn.track_running_stats else None,
-                                bn.running_var if bn.track_running_stats else None)
-            if bn.track_running_stats:
-                # (written through raw pointers by the finalize launch: keep Tensor._version honest for the caches)
-                torch.autograd.graph.increment_version([bn.running_mean, bn.running_var])
-                if bn.num_batches_tracked is not None:
-                    bn.num_batches_tracked += 1
-            return o
-        n1 = fin(st1, B, c1, g1, be1, bns[0])
+        n1 = _bn_batch_step(st1, B, c1, R, g1, be1, bns[0])
         y2, st2 = tdense_fwd(y1, pack_dev(w2), c2, isc=n1["scale"], ish=n1["shift"], in_relu=True, bias=b2, want_stats=True)
-        n2 = fin(st2, st2.shape[0], c2, g2, be2, bns[1])
+        n2 = _bn_batch_step(st2, st2.shape[0], c2, R, g2, be2, bns[1])
         # the last layer's launch also finds every centre's winning row where it can (max of the raw output for
         # gamma >= 0, min otherwise: relu(scale y + shift) is monotone in y); the pooled activation is then one affine +
         # ReLU over the (B,c3,S) winners instead of a second pass over the (B,c3,S K) tensor
-        y3, st3, won = tdense_fwd(y2, pack_dev(w3), c3, isc=n2["scale"], ish=n2["shift"], in_relu=True, bias=b3,
-                                  want_stats=True, pool=(K, g3) if FUSE_POOL else None) if FUSE_POOL else \
-            tdense_fwd(y2, pack_dev(w3), c3, isc=n2["scale"], ish=n2["shift"], in_relu=True, bias=b3, want_stats=True) + (None,)
-        n3 = fin(st3, st3.shape[0], c3, g3, be3, bns[2])
+        y3, st3, *won = tdense_fwd(y2, pack_dev(w3), c3, isc=n2["scale"], ish=n2["shift"], in_relu=True, bias=b3,
+                                   want_stats=True, pool=(K, g3) if FUSE_POOL else None)
+        won = won[0] if won else None                     # (tdense_fwd returns the third value only where it was asked)
+        n3 = _bn_batch_step(st3, st3.shape[0], c3, R, g3, be3, bns[2])
         pooled = _f32(B, c3, S, device=dev)
         if won is not None:
             ymax, argmax = won
@@ -792,6 +591,72 @@ def _chain_images(w, bf):
     return (b16[0] if bf[1] else f32[0]), (b16[1] if (bf[0] or bf[1]) else f32[1])
 
 
+def _chain_precision(p, bf):
+    p.precision, p.fwd_precision = int(bf[0] or bf[1]), int(bf[1])
+
+
+# The backward of a chain leaves one partial record per workgroup; the two functions below say where its fields lie, as
+# [(offset in floats, rows, cols, ld)] in the order the Function returns the gradients.  They restate TailShape::O_* /
+# HeadShape::O_* of csrc/train_chain_kernels.hip, whose last field closes the record: check_part_regions holds them to it.
+def tail_regions(d, c1, hid, out):
+    """dWm (d, d) | dW0 (hid, c1 + d), rows padded to ceil32 | dW2 (out, hid) | dg1, db1 (d) | dg2, db2 (out)"""
+    cup = _c32(c1 + d)
+    o0, o2 = d * d, d * d + hid * cup
+    og = o2 + out * hid
+    return [(0, d, d, d), (o0, hid, c1 + d, cup), (o2, out, hid, hid), (og, 1, d, d), (og + d, 1, d, d),
+            (og + 2 * d, 1, out, out), (og + 2 * d + out, 1, out, out)]
+
+
+def head_regions(C, hd, d, n):
+    """dP1 (hd, 3), rows padded to 32 | dP2 (C, hd) | dW_j (d, C), j < n | dc1 (hd) | dc2 (C) in the record; returned as
+    dP1, dc1, dP2, dc2, dW_0 .. dW_{n-1}"""
+    o_p2 = hd * 32
+    o_w = o_p2 + C * hd
+    o_c1 = o_w + n * d * C
+    return [(0, hd, 3, 32), (o_c1, 1, hd, hd), (o_p2, C, hd, hd), (o_c1 + hd, 1, C, C)] + \
+           [(o_w + j * d * C, d, C, C) for j in range(n)]
+
+
+def check_part_regions(regions, rec, what):
+    """`regions` must end where the library's partial record of `rec` floats ends (rec = 0: no such instantiation).  A
+    field added on one side only would otherwise put weight gradients at wrong offsets behind a plausible loss."""
+    off, rows, _, ld = max(regions)
+    if off + rows * ld != rec:
+        raise L.PcrError("%s: the gradient regions end at float %d of a partial record, the library's record has %d"
+                         % (what, off + rows * ld, rec))
+
+
+# ---- what AttnTail / AttnHead share ----
+def _chain_fwd(ctx, launch, p, tag, flops, nbytes, out_shape, tensors, images):
+    """launch the forward of parameter block `p` into a new tensor; keep `tensors` and the image pairs for the backward"""
+    out = _f32(*out_shape, device=tensors[0].device)
+    p.outp = _p(out)
+    with _prof(tag, flops, nbytes, arith="lib"):
+        launch(ctypes.byref(p), L.stream_ptr())
+    ctx.save_for_backward(*tensors, *[t for im in images for t in im])
+    ctx.nkept = len(tensors)
+    return out
+
+
+def _chain_saved(ctx):
+    """-> (the tensors _chain_fwd kept, the image pairs)"""
+    saved = ctx.saved_tensors
+    flat = saved[ctx.nkept:]
+    return saved[:ctx.nkept], list(zip(flat[0::2], flat[1::2]))
+
+
+def _chain_bwd(launch, groups, p, tag, flops, nbytes, g, rec, regions):
+    """launch the backward of `p` (its input-gradient pointers set) for the output gradient g over groups(p) partial
+    records of `rec` floats -> the `regions` of the record, each summed over the records"""
+    check_part_regions(regions, rec, tag)
+    nwg = groups(ctypes.byref(p))
+    parts = _f32(nwg, rec, device=g.device)
+    p.dout, p.parts, p.part_stride = _p(g), _p(parts), rec
+    with _prof(tag, flops, nbytes, arith="lib"):
+        launch(ctypes.byref(p), L.stream_ptr())
+    return reduce_regions(parts, nwg, rec, regions)
+
+
 def _tail_params(msg, res, Wm, g1, b1, W0, W2, g2, b2, residual, eps, images, bf):
     B, d, Ln = msg.shape
     c1, hid, out = res.shape[1], W0.shape[0], W2.shape[0]
@@ -800,8 +665,14 @@ def _tail_params(msg, res, Wm, g1, b1, W0, W2, g2, b2, residual, eps, images, bf
     p.msg, p.res = _p(msg), _p(res)
     (p.wm, p.wmT), (p.w0, p.w0T), (p.w2, p.w2T) = [(_p(a), _p(b)) for a, b in images]
     p.g1, p.b1, p.g2, p.b2 = _p(g1.detach()), _p(b1.detach()), _p(g2.detach()), _p(b2.detach())
-    p.precision, p.fwd_precision = int(bf[0] or bf[1]), int(bf[1])
+    _chain_precision(p, bf)
     return p, (B, d, Ln, c1, hid, out)
+
+
+def _tail_work(B, d, Ln, c1, hid, out):
+    """-> (profile tag with the direction left open, flops of the forward)"""
+    return "attn_tail_%%s[d=%d,c1=%d,hid=%d,out=%d,L=%d]" % (d, c1, hid, out, Ln), \
+        2.0 * B * Ln * (d * d + (c1 + d) * hid + hid * out)
 
 
 class AttnTail(Function):
@@ -814,49 +685,34 @@ class AttnTail(Function):
         bf = _chain_bf()
         images = [_chain_images(Wm, bf), _chain_images(W0, bf), _chain_images(W2, bf)]
         p, (B, d, Ln, c1, hid, out) = _tail_params(msg, res, Wm, g1, b1, W0, W2, g2, b2, residual, eps, images, bf)
-        y = _f32(B, out, Ln, device=msg.device)
-        p.outp = _p(y)
-        flops = 2.0 * B * Ln * (d * d + (c1 + d) * hid + hid * out)
-        with _prof("attn_tail_fwd[d=%d,c1=%d,hid=%d,out=%d,L=%d]" % (d, c1, hid, out, Ln), flops,
-                   4.0 * B * Ln * (d + c1 + out), arith="lib"):
-            L.run.pcr_attn_tail_fwd_f32(ctypes.byref(p), L.stream_ptr())
-        ctx.save_for_backward(msg, res, Wm, g1, b1, W0, W2, g2, b2, *[t for im in images for t in im])
         ctx.meta = (residual, eps, bf)
-        return y
+        tag, flops = _tail_work(B, d, Ln, c1, hid, out)
+        return _chain_fwd(ctx, L.run.pcr_attn_tail_fwd_f32, p, tag % "fwd", flops, 4.0 * B * Ln * (d + c1 + out),
+                          (B, out, Ln), (msg, res, Wm, g1, b1, W0, W2, g2, b2), images)
 
     @staticmethod
     def backward(ctx, g):
-        msg, res, Wm, g1, b1, W0, W2, g2, b2, *flat = ctx.saved_tensors
+        (msg, res, Wm, g1, b1, W0, W2, g2, b2), images = _chain_saved(ctx)
         residual, eps, bf = ctx.meta
-        images = [(flat[0], flat[1]), (flat[2], flat[3]), (flat[4], flat[5])]
         p, (B, d, Ln, c1, hid, out) = _tail_params(msg, res, Wm, g1, b1, W0, W2, g2, b2, residual, eps, images, bf)
-        lib = L.load()
         g = _dev(g)
-        dev = msg.device
         dmsg, dres = torch.empty_like(msg), torch.empty_like(res)
-        rec = lib.pcr_attn_tail_part_floats(d, c1, hid, out)
-        nwg = lib.pcr_attn_tail_groups(ctypes.byref(p))
-        parts = _f32(nwg, rec, device=dev)
-        p.dout, p.dmsg, p.dres, p.parts, p.part_stride = _p(g), _p(dmsg), _p(dres), _p(parts), rec
-        flops = 2.0 * B * Ln * (d * d + (c1 + d) * hid + hid * out)
-        with _prof("attn_tail_bwd[d=%d,c1=%d,hid=%d,out=%d,L=%d]" % (d, c1, hid, out, Ln), 3.0 * flops,
-                   4.0 * B * Ln * (2 * d + 2 * c1 + out), arith="lib"):
-            L.run.pcr_attn_tail_bwd_f32(ctypes.byref(p), L.stream_ptr())
-        cup = _c32(c1 + d)
-        o0, o2 = d * d, d * d + hid * cup
-        og = o2 + out * hid
-        dWm, dW0, dW2, dg1, db1, dg2, db2 = reduce_regions(
-            parts, nwg, rec, [(0, d, d, d), (o0, hid, c1 + d, cup), (o2, out, hid, hid), (og, 1, d, d), (og + d, 1, d, d),
-                              (og + 2 * d, 1, out, out), (og + 2 * d + out, 1, out, out)])
+        p.dmsg, p.dres = _p(dmsg), _p(dres)
+        tag, flops = _tail_work(B, d, Ln, c1, hid, out)
+        lib = L.load()
+        dWm, dW0, dW2, dg1, db1, dg2, db2 = _chain_bwd(
+            L.run.pcr_attn_tail_bwd_f32, lib.pcr_attn_tail_groups, p, tag % "bwd", 3.0 * flops,
+            4.0 * B * Ln * (2 * d + 2 * c1 + out), g, lib.pcr_attn_tail_part_floats(d, c1, hid, out),
+            tail_regions(d, c1, hid, out))
         return dmsg, dres, dWm, dg1.view(d), db1.view(d), dW0, dW2, dg2.view(out), db2.view(out), None, None
 
 
-def attn_tail(m, msg, res, residual, names=("merge", "norm1", "mlp", "norm2")):
-    """fused tail of attention block `m` (merge / norm1 / mlp[0], mlp[2] / norm2; `names` for local_self_attention's
-    *_knn members), or None when the shape has no fused instantiation (the caller then runs the unfused graph)"""
+def attn_tail(m, msg, res, residual):
+    """fused tail of attention block `m` (merge / norm1 / mlp[0], mlp[2] / norm2), or None when the shape has no fused
+    instantiation (the caller then runs the unfused graph)"""
     if not FUSED_CHAINS:
         return None
-    merge, n1, mlp, n2 = (getattr(m, k) for k in names)
+    merge, n1, mlp, n2 = m.merge, m.norm1, m.mlp, m.norm2
     d, c1 = msg.shape[1], res.shape[1]
     hid, out = mlp[0].weight.shape[0], mlp[2].weight.shape[0]
     if (merge.weight.shape != (d, d) or mlp[0].weight.shape[1] != c1 + d or mlp[2].weight.shape[1] != hid or
@@ -879,8 +735,13 @@ def _head_params(x, xyz, P1, c1, P2, c2, src, Ws, images, bf):
     p.c1, p.c2 = _p(pad32(c1, hd)), _p(pad32(c2, C))
     for j in range(n):
         p.w[j], p.wT[j] = _p(images[2 + j][0]), _p(images[2 + j][1])
-    p.precision, p.fwd_precision = int(bf[0] or bf[1]), int(bf[1])
+    _chain_precision(p, bf)
     return p, (B, C, Ln, hd, d, n)
+
+
+def _head_work(B, C, Ln, hd, d, n):
+    """-> (profile tag with the direction left open, flops of the forward)"""
+    return "attn_head_%%s[c=%d,hd=%d,d=%d,n=%d,L=%d]" % (C, hd, d, n, Ln), 2.0 * B * Ln * (3 * hd + hd * C + n * d * C)
 
 
 class AttnHead(Function):
@@ -893,40 +754,25 @@ class AttnHead(Function):
         bf = _chain_bf()                                  # (P1: three input channels, an f32 image either way)
         images = [pack_both(P1), _chain_images(P2, bf)] + [_chain_images(W, bf) for W in Ws]
         p, (B, C, Ln, hd, d, n) = _head_params(x, xyz, P1, c1, P2, c2, src, Ws, images, bf)
-        out = _f32(B, n * d, Ln, device=x.device)
-        p.outp = _p(out)
-        flops = 2.0 * B * Ln * (3 * hd + hd * C + n * d * C)
-        with _prof("attn_head_fwd[c=%d,hd=%d,d=%d,n=%d,L=%d]" % (C, hd, d, n, Ln), flops, 4.0 * B * Ln * (C + 3 + n * d),
-                   arith="lib"):
-            L.run.pcr_attn_head_fwd_f32(ctypes.byref(p), L.stream_ptr())
-        ctx.save_for_backward(x, xyz, P1, c1, P2, c2, *Ws, *[t for im in images for t in im])
-        ctx.meta = (src, len(Ws), bf)
-        return out
+        ctx.meta = (src, bf)
+        tag, flops = _head_work(B, C, Ln, hd, d, n)
+        return _chain_fwd(ctx, L.run.pcr_attn_head_fwd_f32, p, tag % "fwd", flops, 4.0 * B * Ln * (C + 3 + n * d),
+                          (B, n * d, Ln), (x, xyz, P1, c1, P2, c2, *Ws), images)
 
     @staticmethod
     def backward(ctx, g):
-        src, n, bf = ctx.meta
-        x, xyz, P1, c1, P2, c2, *rest = ctx.saved_tensors
-        Ws, flat = rest[:n], rest[n:]
-        images = [(flat[2 * i], flat[2 * i + 1]) for i in range(2 + n)]
+        (x, xyz, P1, c1, P2, c2, *Ws), images = _chain_saved(ctx)
+        src, bf = ctx.meta
         p, (B, C, Ln, hd, d, n) = _head_params(x, xyz, P1, c1, P2, c2, src, Ws, images, bf)
-        lib = L.load()
         g = _dev(g)
         dx = torch.empty_like(x)
-        rec = lib.pcr_attn_head_part_floats(C, hd, d, n, src)
-        nwg = lib.pcr_attn_head_groups(ctypes.byref(p))
-        parts = _f32(nwg, rec, device=x.device)
-        p.dout, p.dx, p.parts, p.part_stride = _p(g), _p(dx), _p(parts), rec
-        flops = 2.0 * B * Ln * (3 * hd + hd * C + n * d * C)
-        with _prof("attn_head_bwd[c=%d,hd=%d,d=%d,n=%d,L=%d]" % (C, hd, d, n, Ln), 3.0 * flops,
-                   4.0 * B * Ln * (2 * C + 3 + n * d), arith="lib"):
-            L.run.pcr_attn_head_bwd_f32(ctypes.byref(p), L.stream_ptr())
-        o_p2 = hd * 32
-        o_w = o_p2 + C * hd
-        o_c1 = o_w + n * d * C
-        regs = [(0, hd, 3, 32), (o_c1, 1, hd, hd), (o_p2, C, hd, hd), (o_c1 + hd, 1, C, C)] + \
-               [(o_w + j * d * C, d, C, C) for j in range(n)]
-        dP1, dc1, dP2, dc2, *dWs = reduce_regions(parts, nwg, rec, regs)
+        p.dx = _p(dx)
+        tag, flops = _head_work(B, C, Ln, hd, d, n)
+        lib = L.load()
+        dP1, dc1, dP2, dc2, *dWs = _chain_bwd(
+            L.run.pcr_attn_head_bwd_f32, lib.pcr_attn_head_groups, p, tag % "bwd", 3.0 * flops,
+            4.0 * B * Ln * (2 * C + 3 + n * d), g, lib.pcr_attn_head_part_floats(C, hd, d, n, src),
+            head_regions(C, hd, d, n))
         return (dx, None, dP1, dc1.view(hd), dP2, dc2.view(C), None, *dWs)
 
 
@@ -1047,13 +893,6 @@ class ChannelMax(Function):
 
 
 # --------------------------------------------------------------- PointNet pieces (csrc/train_bn_kernels.hip) --
-def _require_batch(R, shape):
-    """torch's training-mode BatchNorm refuses a single value per channel (there is no variance to normalise by); so
-    does this path, before any launch, rather than return beta and update the running statistics"""
-    if R <= 1:
-        raise L.PcrError("Expected more than 1 value per channel when training, got input size %s" % (tuple(shape),))
-
-
 class BnAct(Function):
     """act(BatchNorm(y)) with BATCH statistics over (B, L) per channel on a (B,C,L) tensor; act: None, "relu" or
     ("leaky", slope).  Running statistics are updated in place as nn.BatchNorm1d does in training mode.  (The
@@ -1064,20 +903,13 @@ class BnAct(Function):
     def forward(ctx, y, gamma, beta, bn, act, slope):
         y = _dev(y)
         B, C, Ln = y.shape
-        if bn.momentum is None:
-            raise L.PcrError("BatchNorm with momentum=None (cumulative average) is not supported by the HIP training path")
+        _bn_refuse(bn)
         _require_batch(B * Ln, y.shape)
-        nparts = max(1, min(B, 2048 // max(C, 1)))
+        nparts = _bn_nparts(B, C)
         part = _f32(nparts, 2, _c32(C), device=y.device)
         # sums of y - y[0][c][0] (first element of the channel as the offset): see pcr_bn_fwd_fin.shift0
         L.run.pcr_bn_sums_f32(y, None, None, None, 0, 0.0, None, 1, part, nparts, B, C, Ln, L.stream_ptr())
-        n = bn_fwd_finalize(part, nparts, C, B * Ln, gamma, beta, bn.eps, bn.momentum,
-                            bn.running_mean if bn.track_running_stats else None,
-                            bn.running_var if bn.track_running_stats else None, shift0=y, shift0_stride=Ln)
-        if bn.track_running_stats:
-            torch.autograd.graph.increment_version([bn.running_mean, bn.running_var])
-            if bn.num_batches_tracked is not None:
-                bn.num_batches_tracked += 1
+        n = _bn_batch_step(part, nparts, C, B * Ln, gamma, beta, bn, shift0=y, shift0_stride=Ln)
         z = _f32(B, C, Ln, device=y.device)
         L.run.pcr_bn_affine_f32(y, None, n["scale"], n["shift"], None, None, None, None, int(act), slope, z, B, C, Ln,
                                 L.stream_ptr())
@@ -1123,8 +955,7 @@ class EdgeConvTrain(Function):
         Co = two_co // 2
         K = idx.shape[2]
         dev = tab.device
-        if bn.momentum is None:
-            raise L.PcrError("BatchNorm with momentum=None (cumulative average) is not supported by the HIP training path")
+        _bn_refuse(bn)
         _require_batch(B * N * K, (B, Co, N, K))
         xyz0 = torch.zeros((B, N, 3), dtype=torch.float32, device=dev)       # (no coordinate term: zero weights below)
         wa0 = torch.zeros((Co, 3), dtype=torch.float32, device=dev)
@@ -1132,14 +963,7 @@ class EdgeConvTrain(Function):
         y = _f32(B, Co, N * K, device=dev)
         st = _f32(B, 2, _c32(Co), device=dev)
         L.run.pcr_sa_l1_fwd_f32(xyz0, idx, tab, wa0, b0, y, st, B, N, N, K, Co, L.stream_ptr())
-        R = B * N * K
-        n = bn_fwd_finalize(st, B, Co, R, gamma, beta, bn.eps, bn.momentum,
-                            bn.running_mean if bn.track_running_stats else None,
-                            bn.running_var if bn.track_running_stats else None)
-        if bn.track_running_stats:
-            torch.autograd.graph.increment_version([bn.running_mean, bn.running_var])
-            if bn.num_batches_tracked is not None:
-                bn.num_batches_tracked += 1
+        n = _bn_batch_step(st, B, Co, B * N * K, gamma, beta, bn)
         pooled = _f32(B, Co, N, device=dev)
         arg = torch.empty((B, Co, N), dtype=torch.int32, device=dev)
         yraw = _f32(B, Co, N, device=dev)
@@ -1157,7 +981,7 @@ class EdgeConvTrain(Function):
         gp = gp.contiguous()
         R = B * N * K
         # the two sums of the BatchNorm backward: the routed gradient is non-zero on ONE edge per (channel, point)
-        nparts = max(1, min(B, 2048 // max(Co, 1)))
+        nparts = _bn_nparts(B, Co)
         part = _f32(nparts, 2, _c32(Co), device=dev)
         L.run.pcr_bn_sums_f32(yraw, gp, n["scale"], n["shift"], 1, slope, n["mean"], 0, part, nparts, B, Co, N,
                               L.stream_ptr())
@@ -1169,7 +993,6 @@ class EdgeConvTrain(Function):
         L.run.pcr_sa_l1_bwd_f32(xyz0, idx, g, y, k["ka"], k["kb"], k["kc"], dtab, dwa_p, B, N, N, K, Co,
                                 L.stream_ptr())
         return dtab, None, k["dgamma"], k["dbeta"], None, None
-
 
 
 class Bmm(Function):

@@ -442,7 +442,7 @@ def test_prepacked_bf16_images_equal_fresh_packs_and_follow_updates():
         assert hit is not None and torch.equal(hit[0], f0) and torch.equal(hit[1], f1)
         c0, c1 = TO.pack_both(w)                 # the f32 images stayed where they were, same bits
         assert torch.equal(c0, g0) and torch.equal(c1, g1)
-    assert tab.entries[ws[3].data_ptr()][6] is None          # never requested: no bf16 image kept for it
+    assert tab.entries[ws[3].data_ptr()].wp_bf is None         # never requested: no bf16 image kept for it
     with torch.no_grad():
         ws[0].mul_(0.5)
     assert tab.lookup_bf(ws[0]) is None          # stale: not handed out

@@ -282,6 +282,71 @@ def test_batch_norm_refuses_what_torch_refuses():
             assert torch.equal(a, b)
 
 
+def _bn_step_caller(name):
+    """-> (the BatchNorm modules whose statistics the Function tracks, a function that runs ONE training-mode forward):
+    the three callers of train_ops._bn_batch_step at the smallest shapes their own tests use"""
+    from pcr_amd import train_ops as TO
+    g = _gen(29, len(name))
+    if name == "BnAct":
+        B, C, Ln = 3, 7, 1
+        bn = _bn_layer(torch.nn.BatchNorm1d, C, *_affine(C, g), 0.1, True, g).cuda()
+        y = torch.randn(B, C, Ln, generator=g).cuda()
+        return [bn], lambda: TO.BnAct.apply(y, bn.weight, bn.bias, bn, True, 0.0)
+    if name == "EdgeConvTrain":
+        B, Co, N, K = 2, 32, 64, 1
+        bn = _bn_layer(torch.nn.BatchNorm2d, Co, *_affine(Co, g), 0.1, True, g).cuda()
+        tab = torch.randn(B, 2 * Co, N, generator=g).cuda()
+        idx = torch.randint(0, N, (B, N, K), generator=g).to(torch.int32).cuda()
+        return [bn], lambda: TO.EdgeConvTrain.apply(tab, idx, bn.weight, bn.bias, bn, SLOPE)
+    from mmdet3d.models.pointnet2_utils import PointNetSetAbstractionEdgeSA
+    from pcr_amd import engine
+    from pcr_amd import testing as T
+    B, N, S, K = 3, 128, 128, 32
+    sa = PointNetSetAbstractionEdgeSA(npoint=None, radius=0.3, nsample=K, mlp=[0, 32, 32, 32], sampling="RANDOM",
+                                      use_xyz=True, use_knn=True)
+    sa.load_state_dict(T.seeded_state_dict(T.manifest_of(sa), 5))
+    sa = sa.cuda().train()
+    xyz = T.synthetic_clouds(B, N, seed=3, kind="randn").cuda()
+    idx = engine.knn_prefix(xyz, S, K)
+    return list(sa.mlp_bns), lambda: TO.sa_edge_train(sa, xyz, None, idx)
+
+
+def _bn_state(bns):
+    return [(t._version, t.clone()) for bn in bns for t in (bn.running_mean, bn.running_var, bn.num_batches_tracked)]
+
+
+def _same_state(before, bns):
+    return all(v == w and torch.equal(a, b) for (v, a), (w, b) in zip(before, _bn_state(bns)))
+
+
+@pytest.mark.parametrize("name", ["SaEdgeTrain", "BnAct", "EdgeConvTrain"])
+def test_the_batch_statistics_step_keeps_the_modules_books(name):
+    """one training-mode forward of each Function that normalises by batch statistics: the running buffers -- written
+    through raw pointers by the finalize launch -- show it in Tensor._version (what the caches are keyed by) and
+    num_batches_tracked counts exactly one batch; a module that does not track is left alone, buffers and counter, bit
+    for bit; momentum=None (on the LAST of the modules) is refused before any module's statistics have moved"""
+    from pcr_amd import _lib as L
+    bns, forward = _bn_step_caller(name)
+    assert all(bn.training and bn.track_running_stats and bn.num_batches_tracked is not None for bn in bns)
+    before = _bn_state(bns)
+    forward()
+    for bn, i in zip(bns, range(0, len(before), 3)):
+        assert bn.running_mean._version > before[i][0] and bn.running_var._version > before[i + 1][0]
+        assert not torch.equal(bn.running_mean, before[i][1]) and not torch.equal(bn.running_var, before[i + 1][1])
+        assert int(bn.num_batches_tracked) == int(before[i + 2][1]) + 1
+    before = _bn_state(bns)
+    for bn in bns:
+        bn.track_running_stats = False
+    forward()
+    assert _same_state(before, bns)
+    for bn in bns:
+        bn.track_running_stats = True
+    bns[-1].momentum = None
+    with pytest.raises(L.PcrError, match="momentum=None"):
+        forward()
+    assert _same_state(before, bns)
+
+
 # -------------------------------------------------------------------------------------- EdgeConvTrain --
 def _device_knn(feat, K):
     from pcr_amd import dgcnn_engine

@@ -1963,6 +1963,62 @@ int pcr_triplet_select_f32(const float *dist, const int *neg, const int *match, 
 int pcr_pair_dist_bwd_f32(const float *a, const float *h, const float *E, const float *gout, const float *hyper,
                           const int *count, float *da, float *dh, int B, int R, int D, pcr_stream_t stream);
 
+/* ------------------------------------------------- C3. training on a pair list -------------- */
+
+/* The training twin of match_gallery: every object of a step is encoded ONCE and a list of (i, j) slots is matched,
+ * differentiably (pcr_amd/train_graph.py match_logits_list, ReIDNet.match_gallery_train).  Rules:
+ *   objects  h (M, C, N), xyz (M, N, 3): the encoded objects of the current step, with their autograd history.
+ *   list     pairs (cap, 2) int32 on the device; count (1) int32 on the device, or NULL = cap.  Only
+ *            pairs[:min(count, cap)] are live.  Slots from count on must hold valid indices (compare_pairs writes (0, 0));
+ *            a slot with an index outside [0, M) is dead.  Dead slots contribute exactly zero to every gradient and to
+ *            the loss.
+ *   logits   slot p scores as the training graph scores the one pair (h[i], xyz[i]) against (h[j], xyz[j]), i first.
+ *            xcorr_eff is symmetric; xcorr-baseline, xcorr and concat are one-way, as in match_gallery.
+ *   loss     sum_{p < count} bce(logit_p, match_p) / max(count, 1), formed on the device over a mask arange(cap) < count.
+ *   cartesian rule (the reference's sampling == 'cartesian', models/ReIDNet.py:339-344): the list is
+ *            cartesian_prod(arange(b), arange(b)) in that order; slot (i, j) is object i of side 1 against object j of
+ *            side 2, rows i and b + j of cat(h1, h2); match = (id_1[i] == id_2[j]); the loss is the BCE-with-logits mean
+ *            over the b^2 slots times alpha['match'].
+ *
+ * pcr_index_sum_f32 is the one scatter primitive: src (P, R), idx (P) int32, count as above, dst (M, R):
+ *   dst[m][r] = sum over p < min(count, P) with idx[p] == m of src[p][r]
+ * in f32, added in increasing p, starting from +0; a row no live slot names is written as 0.  An index outside [0, M)
+ * names no row.  Every (m, chunk of R) accumulator has one owning workgroup, which compacts the slots that name m into
+ * LDS in list order and then adds their rows: no float atomics, the same bits on every run.  It is the backward of
+ * out[p] = x[idx[p]].  R <= 65535 * 1024. */
+int pcr_index_sum_f32(const float *src, const int *idx, const int *count, float *dst, int P, int M, int R,
+                      pcr_stream_t stream);
+
+/* The linear-attention core of pcr_linattn split in two and addressed by index lists (csrc/train_pair_kernels.hip).  The
+ * fused core keeps A | ks per (cloud, head) and writes dk / dv of the cloud it read, which needs the query -> key mapping
+ * to be a permutation (kv_roll).  A pair list is many-to-one, so the state and its gradient are per OBJECT:
+ *   state_fwd  per (object m, head): A_m = sum_s K'_s V'_s^T, ks_m = sum_s K'_s from the object's own k, v.
+ *   apply_fwd  per (slot r, head):   out_r = (Q'_{qi[r]}^T A_{si[r]}) L / (Q'_{qi[r]} . ks_{si[r]} + eps)      (R, d, L)
+ *   apply_bwd  per (slot r, head):   dqs_r (R, d, L), the slot's query gradient, and its record
+ *                                    rec_r = [dA_r (dh x dh) | dks_r (dh)]                          (R, H, dh (dh + 1))
+ *   state_bwd  per (object m, head): dk, dv of the object from drec_m = the sum of the records of the slots with
+ *                                    si[r] == m (pcr_index_sum_f32) and its own k, v.
+ * The per-object query gradient is pcr_index_sum_f32 of dqs over qi.  Launch order: state_fwd, apply_fwd; apply_bwd, the
+ * two index sums, state_bwd.  For a list of cap pairs R = 2 cap, qi = [i.. ; j..], si = [j.. ; i..]: direction 1 of every
+ * pair, then direction 2, so slots p and p + cap are pair p -- the layout pcr_pool_pair and kv_roll = cap of the next
+ * stage expect.  A slot with qi or si outside [0, M) is dead: apply_fwd writes zeros for it, apply_bwd writes nothing.
+ * q / k / v / dk / dv are (d, L) channel-major blocks per object addressed with a batch stride in floats (q_bs; kv_bs for
+ * k and v; dkv_bs for dk and dv: slices of a fused (M, 3d, L) projection); Lq = Sk = L.  A (M,H,dh,dh) and ks (M,H,dh)
+ * are written by state_fwd.  eps is a DEVICE pointer to one f32: as in section C2 no entry point takes a float scalar.
+ * Same arithmetic as pcr_linattn's matrix-core form, tile for tile: f32,
+ * v_mfma_f32_32x32x2_f32.  pcr_linattn_pairs_ok(d, H): d / H in {32, 64} (every point-cat matching stage: d = 64,
+ * H = 2); other shapes take the gathered route (pcr_linattn on gathered per-slot tensors). */
+int pcr_linattn_pairs_ok(int d, int H);
+int pcr_linattn_state_fwd_f32(const float *k, const float *v, int kv_bs, float *A, float *ks, int M, int L, int d, int H,
+                              pcr_stream_t stream);
+int pcr_linattn_apply_fwd_f32(const float *q, int q_bs, const float *A, const float *ks, const int *qi, const int *si,
+                              const float *eps, float *out, int M, int R, int L, int d, int H, pcr_stream_t stream);
+int pcr_linattn_apply_bwd_f32(const float *q, int q_bs, const float *A, const float *ks, const int *qi, const int *si,
+                              const float *eps, const float *dout, float *dqs, float *rec, int M, int R, int L, int d, int H,
+                              pcr_stream_t stream);
+int pcr_linattn_state_bwd_f32(const float *k, const float *v, int kv_bs, const float *drec, float *dk, float *dv,
+                              int dkv_bs, int M, int L, int d, int H, pcr_stream_t stream);
+
 /* ---- measurement aid (bench.py; not on the hot path) ---- */
 
 /* Sustained f32-MFMA probe: n_wg workgroups (one per CU: pass the CU count) each run iters * 16

@@ -95,7 +95,7 @@ class ReIDNet(nn.Module):
                  losses_to_use=dict(kl=True, match=True, cls=True, shape=True, fp=True, dense=False),
                  output_sequence_size=32, alpha=dict(kl=1, match=1, cls=1, shape=1, fp=1, triplet=1, dense=1),
                  triplet_sample_num=5, triplet_loss=dict(margin=0.2, p=2), eval_only=False, use_o=False,
-                 eval_flip=False):
+                 eval_flip=False, sampling=None):
         super().__init__()
         self.eval_only = eval_only
         self.hidden_size = hidden_size
@@ -121,7 +121,7 @@ class ReIDNet(nn.Module):
         self.use_o = use_o
         self.eval_flip = eval_flip
         self.verbose = False
-        self.sampling = None
+        self.sampling = sampling        # None: pair p is cloud p of each side; 'cartesian': all b x b pairs (forward_train)
         self.compute_summary = compute_summary
         self.use_dgcnn = use_dgcnn
         self.combine = combine
@@ -657,6 +657,20 @@ class ReIDNet(nn.Module):
             return torch.empty(0, dtype=torch.float32, device=h.device)
         return out[0] if len(out) == 1 else torch.cat(out, dim=0)
 
+    def match_gallery_train(self, h, xyz, pairs, count=None):
+        """The differentiable twin of match_gallery, for training on a pair list (include/pcr.h section C3; INTEGRATION.md
+        "training on a pair list"): h (M,C,N), xyz (M,N,3) are the objects of THIS step as the training-mode encoder
+        returned them (siamese_forward; h carries its autograd history), pairs (cap,2) int32 on the device, count a (1,)
+        int32 device tensor or None = cap -> logits (cap,).  Slot p scores as the training graph scores the one pair
+        (h[i], h[j]), i first; a dead slot (p >= count, or an index outside [0, M)) has logit 0.0 and sends exactly zero to
+        every gradient.  Objects are encoded once however many slots name them; their gradients are summed in list order
+        (pcr_index_sum_f32: no float atomics, bit-reproducible).  No host read: Trainer(graph=True) captures it.
+        pcr_amd.train_graph.list_loss forms the masked loss.  Training mode only -- match_gallery is the inference form."""
+        if not self.training:
+            raise L.PcrError("match_gallery_train: the model is in eval mode; match_gallery is the inference form")
+        from pcr_amd import train_graph
+        return train_graph.match_logits_list(self, h, xyz, pairs, count)[0]
+
     def embed(self, h):
         """h (M,C,N) from forward_inference -> (M,F) embeddings of the 'concat' head, F = N: what the inference entry point
         pools each side with (self.maxpool whatever pool_type, reference ReIDNet.py:455-457) -- 4 F bytes per object to
@@ -1058,6 +1072,26 @@ class ReIDNet(nn.Module):
         match_loss = self.bce(match_preds, match) * self.alpha["match"]
         if o is None:
             o = [None] * (2 * b)
+        self._log_match(match_preds, match, match_loss, log_vars, prefix)
+        return match_preds, match_loss, (o[:b], o[b:])
+
+    def match_forward_cartesian(self, h1, h2, xyz1, xyz2, id_1, id_2, log_vars, device, prefix=""):
+        """match_forward under sampling == 'cartesian' (the reference's rule, ReIDNet.py:339-344): all b x b combinations of
+        the two sides, slot i b + j = object i of side 1 against object j of side 2, match = (id_1[i] == id_2[j]), the BCE
+        mean over the b^2 slots.  The 2b clouds are encoded once; the list is matched by train_graph.match_logits_list."""
+        if not self.losses_to_use["match"]:
+            return None, torch.tensor(0.0, requires_grad=True, device=device), (None, None)
+        from pcr_amd import train_graph
+        b = h1.shape[0]
+        pairs = train_graph.cartesian_pairs(b, h1.device)
+        match = (id_1[pairs[:, 0].long()] == id_2[(pairs[:, 1] - b).long()]).float()
+        match_preds, _ = train_graph.match_logits_list(self, train_graph._joined(h1, h2), train_graph._joined(xyz1, xyz2),
+                                                       pairs)
+        match_loss = self.bce(match_preds, match) * self.alpha["match"]
+        self._log_match(match_preds, match, match_loss, log_vars, prefix)
+        return match_preds, match_loss, (None, None)
+
+    def _log_match(self, match_preds, match, match_loss, log_vars, prefix):
         if self.compute_summary and log_vars is not None:
             # the reference's six log entries (ReIDNet.py:426-435: `.item()` each), computed on the device as ONE small
             # tensor and read lazily (pcr_amd/lazylog.py): same keys -- including the reference's swapped
@@ -1075,7 +1109,6 @@ class ReIDNet(nn.Module):
             else:
                 for k, i, v in zip(names, ints, stats.tolist()):
                     log_vars[k] = int(round(v)) if i else v
-        return match_preds, match_loss, (o[:b], o[b:])
 
     def _check_losses(self):
         # match, cls, fp, kl and triplet run (pcr_amd/train_graph.py aux_losses); shape (chamfer distance over dense
@@ -1086,6 +1119,11 @@ class ReIDNet(nn.Module):
                                           "train with match, cls, fp, kl and triplet at most (SURVEY.md section 8)" % k)
         if self.losses_to_use.get("triplet", False) and self.triplet_cfg.get("p", 2) != 2:
             raise L.PcrError("triplet_loss: p = %r; the distance kernels implement p = 2 only" % (self.triplet_cfg.get("p"),))
+        if self.sampling == "cartesian" and self._aux_on():
+            # (the reference feeds these losses b^2 duplicated rows under cartesian sampling; what they should mean there
+            # is undecided)
+            raise L.PcrError("sampling='cartesian' trains the match loss only; switch off %s"
+                             % ", ".join(k for k in ("cls", "fp", "kl", "triplet") if self.losses_to_use.get(k, False)))
 
     def _aux_on(self):
         return any(self.losses_to_use.get(k, False) for k in ("cls", "fp", "kl", "triplet"))
@@ -1139,6 +1177,10 @@ class ReIDNet(nn.Module):
             sparse_1, sparse_2, dense_1, dense_2, label_1, label_2, id_1, id_2)
         device = sparse_1.device
         xyz1, xyz2, h1, h2 = self.siamese_forward(sparse_1, sparse_2)
+        if self.sampling == "cartesian" and self.training:
+            # (a training rule: val_step's eval-mode pass and forward_test keep the paired evaluation)
+            losses["reid_loss"] = self.match_forward_cartesian(h1, h2, xyz1, xyz2, id_1, id_2, log_vars, device)[1]
+            return losses, log_vars
         h1, h2, xyz1, xyz2, match = self.get_match_supervision(h1, h2, xyz1, xyz2, id_1, id_2)
         _, match_loss, o = self.match_forward(h1, h2, xyz1, xyz2, match, log_vars, device)
         loss = match_loss

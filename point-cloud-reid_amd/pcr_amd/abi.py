@@ -393,6 +393,13 @@ SIGNATURES = {
     "pcr_pair_dist_f32": "s FFFiiiS",
     "pcr_triplet_select_f32": "s FIIFFFFIIiiS",
     "pcr_pair_dist_bwd_f32": "s FFFFFIFFiiiS",
+    # C3. training on a pair list
+    "pcr_index_sum_f32": "s FIIFiiiS",
+    "pcr_linattn_pairs_ok": "i ii",
+    "pcr_linattn_state_fwd_f32": "s FFiFFiiiiS",
+    "pcr_linattn_apply_fwd_f32": "s FiFFIIFFiiiiiS",
+    "pcr_linattn_apply_bwd_f32": "s FiFFIIFFFFiiiiiS",
+    "pcr_linattn_state_bwd_f32": "s FFiFFFiiiiiS",
     # measurement aid
     "pcr_wall_clock_khz": "i ",
     "pcr_last_launch_arith": "i ",

@@ -412,3 +412,103 @@ def match_logits(model, h1, xyz1, h2, xyz2):
         a = cross_attention(model.cross_stage1, feats, swap(feats), swap(xyz_cm))
         o = cross_attention(model.cross_stage2, a, swap(a), swap(xyz_cm))
     return _head(model, TO.PoolPair.apply(o)), o
+
+
+# ---------------------------------------------------------------------------------------- pair lists --
+# The training twin of ReIDNet.match_gallery (include/pcr.h section C3; INTEGRATION.md "training on a pair list"): the
+# objects of a step are encoded once, a list of (i, j) slots is matched.  A slot's operands are gathered from the
+# per-object features (train_ops.PairGather); their gradients come back to the objects through pcr_index_sum_f32, one
+# owner per accumulator, in list order -- no float atomics, no host read, every launch capturable.
+def list_alive(pairs, count, M):
+    """(cap,) bool on the device: slot p < min(count, cap) and both of its indices inside [0, M)"""
+    cap = pairs.shape[0]
+    ok = ((pairs >= 0) & (pairs < M)).all(dim=1)
+    if count is not None:
+        ok = ok & (torch.arange(cap, device=pairs.device, dtype=torch.int32) < count)
+    return ok
+
+
+def cartesian_pairs(b, device):
+    """torch.cartesian_prod(arange(b), arange(b)) of the reference's sampling == 'cartesian' (ReIDNet.py:340), made on the
+    device, as rows of cat(side 1, side 2): slot i b + j = (i, b + j) -> (b b, 2) int32"""
+    r = torch.arange(b, device=device, dtype=torch.int32)
+    return torch.stack([r.repeat_interleave(b), r.repeat(b) + b], dim=1)
+
+
+def list_loss(logits, match, count=None):
+    """the masked match loss of a pair list: sum_{p < count} bce(logit_p, match_p) / max(count, 1), formed on the device
+    (torch ops on a mask of arange(cap) < count; count None: the mean over the list)"""
+    import torch.nn.functional as F
+    per = F.binary_cross_entropy_with_logits(logits, match, reduction="none")
+    if count is None:
+        return per.mean()
+    cap = logits.shape[0]
+    live = torch.arange(cap, device=logits.device, dtype=torch.int32) < count
+    n = count.clamp(1, max(cap, 1)).to(per.dtype)
+    return (torch.where(live, per, torch.zeros_like(per)).sum() / n).reshape(())
+
+
+# xcorr_eff: stage 1 once per OBJECT (False: every slot's operands gathered, stage 1 per slot -- the route the other heads
+# take; tools/bench_pair_training.py times one against the other)
+PAIR_AMORTISED = True
+
+
+def _stage1_amortised(m, h, xyz, res, qi, si):
+    """stage 1 of xcorr_eff over a pair list: q | k | v of every OBJECT from ONE head launch (q, k of x; v of x + position
+    code), the core per slot against the state of the slot's partner object (train_ops.LinAttnPairs), the tail over the
+    slots with res = the gathered features.  None: no fused head instantiation or a head width the indexed core does not
+    cover (pcr_linattn_pairs_ok) -- the caller takes the gathered route."""
+    d = m.q_proj.weight.shape[0]
+    if not TO.linattn_pairs_ok(d, m.nhead):
+        return None
+    qkv = TO.attn_head(m.pos_mlp, h, _cm(xyz), (m.q_proj.weight, m.k_proj.weight, m.v_proj.weight), 4)
+    if qkv is None:
+        return None
+    return _tail(m, TO.LinAttnPairs.apply(qkv, qi, si, m.nhead, ATTN_EPS), res, True)
+
+
+def match_logits_list(model, h, xyz, pairs, count=None):
+    """h (M, C, N), xyz (M, N, 3): the encoded objects of this step (h with its autograd history); pairs (cap, 2) int32 on
+    the device, count (1,) int32 on the device or None = cap -> (logits (cap,), stage-2 features (2 cap, C, N) or None).
+    Slot p scores as match_logits(model, h[i:i+1], xyz[i:i+1], h[j:j+1], xyz[j:j+1]) does, i first (xcorr_eff is
+    symmetric, the other three heads one-way, as in match_gallery).  A dead slot -- p >= count, or an index outside
+    [0, M) -- has logit 0.0 exactly and sends exactly zero to every gradient: its rows are gathered with a dead index,
+    which pcr_index_sum_f32 gives to no object, and its logit is replaced before anything reads it.
+    xcorr_eff works on 2 cap virtual clouds [i.. ; j..], direction 1 of every pair, then direction 2: the layout the matching
+    stages' kv_roll = cap and PoolPair expect (clouds p and p + cap are pair p).  Stage 1 runs once per OBJECT where the
+    indexed attention core covers the stage (_stage1_amortised); else, and for the one-way heads, every slot's operands are
+    gathered and match_logits runs on the gathered batch."""
+    from . import _lib as L
+    why = supports(model)
+    if why is not None:
+        raise L.PcrError(why)
+    L.require_cuda(h, xyz, pairs)
+    if pairs.dim() != 2 or pairs.shape[1] != 2 or pairs.dtype != torch.int32:
+        raise L.PcrError("match_logits_list: pairs must be a (cap, 2) int32 device tensor, got %s %s"
+                         % (tuple(pairs.shape), pairs.dtype))
+    count = TO._list_count(count, "match_logits_list")
+    M, cap = h.shape[0], pairs.shape[0]
+    if cap == 0 or M == 0:
+        raise L.PcrError("match_logits_list: an empty list or no objects (cap = %d, M = %d)" % (cap, M))
+    alive = list_alive(pairs, count, M)
+    dead = torch.full_like(pairs[:, 0], -1)
+    i, j = torch.where(alive, pairs[:, 0], dead), torch.where(alive, pairs[:, 1], dead)
+    xyz = xyz.detach()
+    if model.match_type == "xcorr_eff":
+        qi = torch.cat([i, j])
+        g = TO.pair_gather(h, qi)
+        xv = xyz.index_select(0, qi.clamp(min=0).long())                 # (a dead slot reads object 0: never used)
+        o = _stage1_amortised(model.cross_stage1, h, xyz, g, qi, torch.cat([j, i])) if PAIR_AMORTISED else None
+        if o is None:
+            logits, o = match_logits(model, g[:cap], xv[:cap], g[cap:], xv[cap:])
+        else:
+            xv_cm = _cm(xv)
+            a, o = o, cross_attention_pairs(model.cross_stage2, o, xv_cm, cap)
+            if o is None:
+                swap = lambda t: torch.roll(t, cap, 0)                # noqa: E731
+                o = cross_attention(model.cross_stage2, a, swap(a), swap(xv_cm))
+            logits = _head(model, TO.PoolPair.apply(o))
+    else:
+        x1, x2 = xyz.index_select(0, i.clamp(min=0).long()), xyz.index_select(0, j.clamp(min=0).long())
+        logits, o = match_logits(model, TO.pair_gather(h, i), x1, TO.pair_gather(h, j), x2)
+    return torch.where(alive, logits, torch.zeros_like(logits)), o

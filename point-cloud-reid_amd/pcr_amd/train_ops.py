@@ -892,6 +892,124 @@ class ChannelMax(Function):
         return dx, None
 
 
+# ------------------------------------------------------------ pair lists (csrc/train_pair_kernels.hip) --
+def _list_count(count, who):
+    """count of a pair list: None (every slot) or a (1,) int32 device tensor"""
+    if count is None:
+        return None
+    L.require_cuda(count)
+    if count.dtype != torch.int32 or count.numel() != 1:
+        raise L.PcrError("%s: count must be a (1,) int32 device tensor" % who)
+    return count.reshape(1).contiguous()
+
+
+def index_sum(src, idx, count, M):
+    """src (P, ...) f32, idx (P) int32, count (1,) int32 or None -> dst (M, ...): dst[m] = the sum of the rows src[p] with
+    idx[p] == m over p < min(count, P), added in increasing p from +0 (pcr_index_sum_f32: one owner per accumulator, no
+    float atomics).  A row no live slot names is 0; an index outside [0, M) names no row."""
+    src, idx = _dev(src), idx.contiguous()
+    L.require_cuda(idx)
+    L.require_i32(idx)
+    P = src.shape[0]
+    if idx.numel() != P:
+        raise L.PcrError("index_sum: %d indices for %d rows" % (idx.numel(), P))
+    R = 1
+    for s in src.shape[1:]:
+        R *= s
+    dst = _f32(M, *src.shape[1:], device=src.device)
+    if M and dst.numel():
+        with _prof("index_sum[P=%d,M=%d,R=%d]" % (P, M, R), float(P) * R, 4.0 * (P + M) * R):
+            L.run.pcr_index_sum_f32(src, idx, _list_count(count, "index_sum"), dst, P, M, R, L.stream_ptr())
+    return dst
+
+
+class PairGather(Function):
+    """out[p] = x[idx[p]] over the first axis: x (M, ...) f32, idx (P) int32 on the device, count (1,) int32 or None ->
+    (P, ...).  A slot whose index lies outside [0, M) is dead: it reads row 0 (its values are never used) and sends no
+    gradient anywhere; neither does a slot from count on.  Backward: index_sum -- the gradient of object m is the sum of
+    its slots' gradients in list order, bit-reproducible.  idx and count get no gradient."""
+
+    @staticmethod
+    def forward(ctx, x, idx, count=None):
+        x = _dev(x)
+        L.require_cuda(idx)
+        L.require_i32(idx)
+        idx = idx.contiguous()
+        M = x.shape[0]
+        safe = torch.where((idx >= 0) & (idx < M), idx, torch.zeros_like(idx))
+        ctx.save_for_backward(idx, *(() if count is None else (_list_count(count, "PairGather"),)))
+        ctx.M = M
+        return x.index_select(0, safe.long())
+
+    @staticmethod
+    def backward(ctx, g):
+        idx, *count = ctx.saved_tensors
+        return index_sum(g, idx, count[0] if count else None, ctx.M), None, None
+
+
+IndexSum = PairGather     # (named by its backward)
+
+
+def pair_gather(x, idx, count=None):
+    return PairGather.apply(x, idx, count)
+
+
+def linattn_pairs_ok(d, H):
+    """does the indexed attention core cover (d_model, heads)?  (pcr_linattn_pairs_ok: head widths 32 and 64)"""
+    return bool(L.load().pcr_linattn_pairs_ok(int(d), int(H)))
+
+
+class LinAttnPairs(Function):
+    """The linear-attention core over a pair list (include/pcr.h section C3): qkv (M,3d,L) = the fused q | k | v projection
+    per OBJECT, qi, si (R) int32 on the device -> (R,d,L): slot r = the queries of object qi[r] against the key / value
+    state of object si[r].  The state A | ks is made once per object (state_fwd) however many slots read it.  Backward:
+    apply_bwd leaves the slots' query gradients and [dA | dks] records, two index_sums carry them to the objects (list
+    order, no float atomics), state_bwd turns the summed records into dk, dv; the gradient comes back as one (M,3d,L)
+    buffer.  A slot with an index outside [0, M) is dead: zeros out, nothing back.  qi, si get no gradient."""
+
+    @staticmethod
+    def forward(ctx, qkv, qi, si, H, eps):
+        qkv, qi, si = _dev(qkv), qi.contiguous(), si.contiguous()
+        L.require_cuda(qi, si)
+        L.require_i32(qi, si)
+        M, d3, Ln = qkv.shape
+        d, R = d3 // 3, qi.numel()
+        if si.numel() != R or not linattn_pairs_ok(d, H):
+            raise L.PcrError("LinAttnPairs: d = %d, H = %d, %d / %d indices (pcr_linattn_pairs_ok)" % (d, H, R, si.numel()))
+        dev, dh = qkv.device, d // H
+        A, ks = _f32(M, H, dh, dh, device=dev), _f32(M, H, dh, device=dev)
+        out = _f32(R, d, Ln, device=dev)
+        eps_t = torch.full((1,), float(eps), dtype=torch.float32, device=dev)
+        bs = d3 * Ln
+        with _prof("linattn_state_fwd[d=%d,L=%d]" % (d, Ln), 2.0 * M * Ln * d * dh, 4.0 * M * (2 * d * Ln + d * dh)):
+            L.run.pcr_linattn_state_fwd_f32(qkv[:, d:2 * d], qkv[:, 2 * d:], bs, A, ks, M, Ln, d, H, L.stream_ptr())
+        with _prof("linattn_apply_fwd[d=%d,L=%d]" % (d, Ln), 2.0 * R * Ln * d * dh, 4.0 * R * (2 * d * Ln + d * dh)):
+            L.run.pcr_linattn_apply_fwd_f32(qkv, bs, A, ks, qi, si, eps_t, out, M, R, Ln, d, H, L.stream_ptr())
+        ctx.save_for_backward(qkv, A, ks, qi, si, eps_t)
+        ctx.H = H
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        qkv, A, ks, qi, si, eps_t = ctx.saved_tensors
+        H = ctx.H
+        M, d3, Ln = qkv.shape
+        d, R = d3 // 3, qi.numel()
+        dev, dh = qkv.device, d // H
+        dqs, rec = _f32(R, d, Ln, device=dev), _f32(R, H, dh * (dh + 1), device=dev)
+        bs = d3 * Ln
+        with _prof("linattn_apply_bwd[d=%d,L=%d]" % (d, Ln), 6.0 * R * Ln * d * dh, 4.0 * R * (3 * d * Ln + 2 * d * dh)):
+            L.run.pcr_linattn_apply_bwd_f32(qkv, bs, A, ks, qi, si, eps_t, g.contiguous(), dqs, rec, M, R, Ln, d, H,
+                                            L.stream_ptr())
+        buf = torch.empty_like(qkv)
+        buf[:, :d] = index_sum(dqs, qi, None, M)
+        drec = index_sum(rec, si, None, M)
+        with _prof("linattn_state_bwd[d=%d,L=%d]" % (d, Ln), 4.0 * M * Ln * d * dh, 4.0 * M * (4 * d * Ln + d * dh)):
+            L.run.pcr_linattn_state_bwd_f32(qkv[:, d:2 * d], qkv[:, 2 * d:], bs, drec, buf[:, d:2 * d], buf[:, 2 * d:], bs,
+                                            M, Ln, d, H, L.stream_ptr())
+        return buf, None, None, None, None
+
+
 # --------------------------------------------------------------- PointNet pieces (csrc/train_bn_kernels.hip) --
 class BnAct(Function):
     """act(BatchNorm(y)) with BATCH statistics over (B, L) per channel on a (B,C,L) tensor; act: None, "relu" or

@@ -8,13 +8,14 @@ What runs where: both clouds of every pair go through the backbone in one batch
 'point-cat' + pool 'both' + match head (ref :526-534, :444-462) is a single launch.  All of it
 is libpcr_hip.so; this file only owns parameters, shapes and the mmdet-style entry points.
 """
+import contextlib
 import copy
 from collections import OrderedDict
 
 import torch
 import torch.nn as nn
 
-from pcr_amd import engine
+from pcr_amd import engine, frame, gallery, retrieval
 from pcr_amd import _lib as L
 from pcr_amd.lazylog import LazyScalars
 from .attention import corss_attention, cross_lin_attn, local_self_attention
@@ -208,6 +209,15 @@ class ReIDNet(nn.Module):
             return None
         return {k: v for k, v in st.items() if k != "key"}
 
+    _INHERIT = contextlib.nullcontext()
+
+    @staticmethod
+    def _at_level(lvl):
+        """with self._at_level(self.precision_level() / self._match_level(..)): the launches inside run at this model's guard
+        level.  Level 0 INHERITS the surrounding level instead of setting 0: calibrate_precision and _sentinel call the hot
+        path inside a guard_level of their own"""
+        return engine.guard_level(lvl) if lvl else ReIDNet._INHERIT
+
     def _hot(self, s1, s2):
         xyz1, xyz2, h1, h2 = self._siamese_forward(s1, s2)
         return self._match_logits(h1, h2, xyz1, xyz2, inference=True)[0]
@@ -314,11 +324,7 @@ class ReIDNet(nn.Module):
         # (PointNet / DGCNN take channel-major clouds (B,3,N); the guard's pairs are point-major like siamese_forward's)
         cm = self.use_dgcnn or isinstance(self.backbone, PointNet)
         self._guard_tick(*self._halves(pts_batched.permute(0, 2, 1) if cm else pts_batched))
-        lvl = self.precision_level()
-        with torch.no_grad():
-            if lvl:
-                with engine.guard_level(lvl):
-                    return self.backbone(pts_batched, self.backbone_list)
+        with torch.no_grad(), self._at_level(self.precision_level()):
             return self.backbone(pts_batched, self.backbone_list)
 
     def forward_inference_boxes(self, points, boxes, n=None, **crop_args):
@@ -342,11 +348,8 @@ class ReIDNet(nn.Module):
 
     def siamese_forward(self, sparse_1, sparse_2):
         self._guard_tick(sparse_1, sparse_2)
-        lvl = self.precision_level()
-        if lvl:
-            with engine.guard_level(lvl):
-                return self._siamese_forward(sparse_1, sparse_2)
-        return self._siamese_forward(sparse_1, sparse_2)
+        with self._at_level(self.precision_level()):
+            return self._siamese_forward(sparse_1, sparse_2)
 
     def _siamese_forward(self, sparse_1, sparse_2):
         """(B,N,3) x 2 -> xyz1, xyz2 (B,N,3), h1, h2 (B,C,N); one backbone pass over 2B clouds"""
@@ -493,23 +496,13 @@ class ReIDNet(nn.Module):
         return self.precision_level()
 
     def match_forward_inference(self, h1, h2, xyz1, xyz2):
-        lvl = self._match_level(xyz1, xyz2)
-        if lvl:
-            with engine.guard_level(lvl):
-                return self._match_logits(h1, h2, xyz1, xyz2, inference=True)[0]
-        return self._match_logits(h1, h2, xyz1, xyz2, inference=True)[0]
+        with self._at_level(self._match_level(xyz1, xyz2)):
+            return self._match_logits(h1, h2, xyz1, xyz2, inference=True)[0]
 
     # the launches index clouds by a 16-bit grid dimension: at most 32 k pairs (64 k virtual clouds) per pass of match_gallery
     GALLERY_CHUNK = 32000
 
     def match_gallery(self, h, xyz, pairs, count=None, dead_value=0.0):
-        lvl = self._match_level(*self._halves(xyz))
-        if lvl:
-            with engine.guard_level(lvl):
-                return self._match_gallery(h, xyz, pairs, count, dead_value)
-        return self._match_gallery(h, xyz, pairs, count, dead_value)
-
-    def _match_gallery(self, h, xyz, pairs, count=None, dead_value=0.0):
         """Amortised matching (the reference's tracker use-case of forward_inference +
         match_forward_inference, ReIDNet.py:189-191, 444-462): every object is encoded ONCE, then any list
         of (i, j) combinations is scored.  h (M,C,N), xyz (M,N,3) from forward_inference / siamese_forward;
@@ -531,131 +524,13 @@ class ReIDNet(nn.Module):
           xcorr           as xcorr-baseline with the local stages in between.  The local stages have no gated form: with
                           count= the whole list is scored (the padding (0, 0) of compare_pairs is a valid pair) and the
                           logits beyond count are replaced by dead_value -- this head saves no work for padding."""
-        if self.match_type == "concat":
-            return self.match_embeddings(self.embed(h), pairs, count=count, dead_value=dead_value)
-        if self.match_type in ("xcorr", "xcorr-baseline"):
-            return self._match_gallery_one_way(h, xyz, pairs, count, dead_value)
-        if self.match_type != "xcorr_eff" or self.combine != "point-cat" or self.pool_type != "both":
+        with self._at_level(self._match_level(*self._halves(xyz))):
+            if self.match_type == "concat":
+                return self.match_embeddings(self.embed(h), pairs, count=count, dead_value=dead_value)
+            if self.match_type in ("xcorr", "xcorr-baseline") or self._fused_matching():
+                return gallery.match_pairs(self, h, xyz, pairs, count, dead_value)
             raise NotImplementedError("match_gallery covers the xcorr_eff / point-cat / both matching head and the concat, "
                                       "xcorr-baseline and xcorr heads")
-        h, xyz = h.contiguous(), xyz.contiguous()
-        n_pts = h.shape[2]
-        p1 = self.cross_stage1.plan(h.device)
-        p2 = self.cross_stage2.plan(h.device)
-        kv1 = p1.kv(h, xyz)                                  # stage-1 key/value state: once per OBJECT
-        # round 6: the stage-2 apply launch leaves every virtual cloud's per-channel maximum and sum (512 bytes) instead of
-        # its 32 KB output for pool_head to read back; the head then runs over the pooled ROWS on the matrix core
-        # (pcr_attn_apply_pool_ok: the launch shape and the arithmetic decide, never the number of pairs)
-        pooled_ok = p2.pool_ok(n_pts, n_pts)
-        out = []
-        chunk = self.GALLERY_CHUNK
-        if count is not None:
-            L.require_cuda(count)
-            if count.dtype != torch.int32 or count.numel() != 1:
-                raise L.PcrError("match_gallery: count must be a (1,) int32 device tensor")
-            if not (p1.live_ok() and p2.live_ok()):
-                raise L.PcrError("match_gallery: count= needs matching stages the gated launches cover "
-                                 "(pcr_attn_live_ok: d_model = 64 with 64-channel features)")
-            count = count.reshape(1).contiguous()
-        for lo in range(0, pairs.shape[0], chunk):
-            pc = pairs[lo:lo + chunk]
-            n_pairs = pc.shape[0]
-            i = pc[:, 0].to(device=h.device, dtype=torch.int32)
-            j = pc[:, 1].to(device=h.device, dtype=torch.int32)
-            q_idx = torch.cat([i, j]).contiguous()        # virtual cloud b < P: object i queries object j ...
-            k_idx = torch.cat([j, i]).contiguous()        # ... and b >= P: object j queries object i
-            if count is not None:
-                out.append(self._match_chunk_live(p1, p2, h, xyz, kv1, q_idx, k_idx, n_pairs, pooled_ok,
-                                                  (count, n_pairs, lo), dead_value))
-                continue
-            s1 = p1.apply(h, None, kv1, n_pts, kv_index=k_idx, q_index=q_idx, n_out=2 * n_pairs)
-            xyz_v = xyz.index_select(0, q_idx.long()).contiguous()
-            partner = torch.cat([torch.arange(n_pairs, 2 * n_pairs, device=h.device, dtype=torch.int32),
-                                 torch.arange(0, n_pairs, device=h.device, dtype=torch.int32)])
-            if pooled_ok:
-                pl = p2.apply(s1, None, p2.kv(s1, xyz_v), n_pts, kv_index=partner, pooled=True)     # (2n, 2, C): [max | sum]
-                a, b2 = pl[:n_pairs], pl[n_pairs:]
-                feat = torch.cat([torch.maximum(a[:, 0], b2[:, 0]), (a[:, 1] + b2[:, 1]) / float(2 * n_pts)], dim=1)
-                out.append(self._head_rows(feat))
-            else:
-                o = p2.apply(s1, None, p2.kv(s1, xyz_v), n_pts, kv_index=partner)
-                out.append(self._head(o.device).run(o))
-        if not out:
-            return torch.empty(0, dtype=torch.float32, device=h.device)
-        return out[0] if len(out) == 1 else torch.cat(out, dim=0)
-
-    def _match_chunk_live(self, p1, p2, h, xyz, kv1, q_idx, k_idx, n_pairs, pooled_ok, live, dead_value):
-        """one pass of _match_gallery over a chunk whose pairs from live = (count, period = n_pairs, offset = lo) on are
-        padding: the stage-1 apply, the stage-2 kv and apply and, on the un-pooled route, the head are gated"""
-        n_pts = h.shape[2]
-        count, _, lo = live
-        s1 = p1.apply(h, None, kv1, n_pts, kv_index=k_idx, q_index=q_idx, n_out=2 * n_pairs, live=live)
-        xyz_v = xyz.index_select(0, q_idx.long()).contiguous()
-        partner = torch.cat([torch.arange(n_pairs, 2 * n_pairs, device=h.device, dtype=torch.int32),
-                             torch.arange(0, n_pairs, device=h.device, dtype=torch.int32)])
-        kv2 = p2.kv(s1, xyz_v, live=live)
-        if not pooled_ok:
-            o = p2.apply(s1, None, kv2, n_pts, kv_index=partner, live=live)
-            return self._head(o.device).run(o, live=live, dead_value=dead_value)
-        # (the pooled rows of dead pairs are zeros: the row kernels read every row, and a row's logit depends on that row alone)
-        pl = p2.apply(s1, None, kv2, n_pts, kv_index=partner, pooled=True, live=live)
-        a, b2 = pl[:n_pairs], pl[n_pairs:]
-        feat = torch.cat([torch.maximum(a[:, 0], b2[:, 0]), (a[:, 1] + b2[:, 1]) / float(2 * n_pts)], dim=1)
-        logits = self._head_rows(feat)
-        alive = torch.arange(lo, lo + n_pairs, device=h.device, dtype=torch.int32) < count
-        return torch.where(alive, logits, logits.new_full((), float(dead_value)))
-
-    @staticmethod
-    def _gallery_count(count):
-        if count is None:
-            return None
-        L.require_cuda(count)
-        if count.dtype != torch.int32 or count.numel() != 1:
-            raise L.PcrError("match_gallery: count must be a (1,) int32 device tensor")
-        return count.reshape(1).contiguous()
-
-    def _match_gallery_one_way(self, h, xyz, pairs, count, dead_value):
-        """match_gallery for match_type 'xcorr-baseline' / 'xcorr' (xcorr_baseline / xcorr above): the template of both
-        cross stages is object j's original features, so kv1 and kv2 are per OBJECT and pair (i, j) is ONE virtual cloud:
-        object i's tokens against object j's state, twice"""
-        local = self.match_type == "xcorr"
-        if local and (self.local_stage1 is None or self.local_stage2 is None):
-            raise L.PcrError("match_type='xcorr' needs local_stage1 / local_stage2 (local_self_attention)")
-        h, xyz = h.contiguous(), xyz.contiguous()
-        n_pts = h.shape[2]
-        p1 = self.cross_stage1.plan(h.device)
-        p2 = self.cross_stage2.plan(h.device)
-        count = self._gallery_count(count)
-        gated = count is not None and not local
-        if gated and not (p1.live_ok() and p2.live_ok()):
-            raise L.PcrError("match_gallery: count= needs matching stages the gated launches cover "
-                             "(pcr_attn_live_ok: d_model = 64 with 64-channel features)")
-        kv1, kv2 = p1.kv(h, xyz), p2.kv(h, xyz)
-        out = []
-        for lo in range(0, pairs.shape[0], self.GALLERY_CHUNK):
-            pc = pairs[lo:lo + self.GALLERY_CHUNK]
-            n_pairs = pc.shape[0]
-            i = pc[:, 0].to(device=h.device, dtype=torch.int32).contiguous()
-            j = pc[:, 1].to(device=h.device, dtype=torch.int32).contiguous()
-            live = (count, n_pairs, lo) if gated else None
-            s = p1.apply(h, None, kv1, n_pts, kv_index=j, q_index=i, n_out=n_pairs, live=live)
-            if local:
-                xyz_v = xyz.index_select(0, i.long()).contiguous()
-                s = self.local_stage1(s, xyz_v)
-            # (a dead pair's rows of the gated stage-2 output are zeros: pooling and the head read every row, and a row's
-            # logit depends on that row alone)
-            buf = torch.zeros((n_pairs, p2.cfinal or p2.cout, n_pts), dtype=torch.float32, device=h.device) if gated else None
-            s = p2.apply(s, None, kv2, n_pts, kv_index=j, live=live, out=buf)
-            if local:
-                s = self.local_stage2(s, xyz_v)
-            logits = self._head_rows(self.get_pooled_feats(s))
-            if count is not None:
-                alive = torch.arange(lo, lo + n_pairs, device=h.device, dtype=torch.int32) < count
-                logits = torch.where(alive, logits, logits.new_full((), float(dead_value)))
-            out.append(logits)
-        if not out:
-            return torch.empty(0, dtype=torch.float32, device=h.device)
-        return out[0] if len(out) == 1 else torch.cat(out, dim=0)
 
     def match_gallery_train(self, h, xyz, pairs, count=None):
         """The differentiable twin of match_gallery, for training on a pair list (include/pcr.h section C3; INTEGRATION.md
@@ -696,83 +571,7 @@ class ReIDNet(nn.Module):
         L.require_cuda(emb)
         pl = pairs_head.plan(self.match_head, emb.device)
         u, v = pairs_head.tables(pl, emb)
-        return pairs_head.pair_logits(pl, emb, u, v, pairs, count=self._gallery_count(count), dead_value=dead_value)
-
-    @staticmethod
-    def _decision_set(decisions, T, D, cost_args, who, M=None):
-        """decisions=dict(detection=(names...), tracking=(names...), det_values=(dd, D) or None, track_values=(td, T) or
-        None, kind="margin", reduce=False) -> what _associate_decisions takes.  The names are sorted, as the reference sorts
-        them (trackers/deprecated/virtual_tracker.py:114-115), and the rows of det_values / track_values follow the sorted
-        order; None values are zeros.  det_values of width M < D (track_step's padding) are zero-padded."""
-        if not isinstance(decisions, dict) or set(decisions) - {"detection", "tracking", "det_values", "track_values", "kind",
-                                                                "reduce"}:
-            raise L.PcrError("%s: decisions must be dict(detection=, tracking=, det_values=, track_values=, kind=, reduce=)"
-                             % who)
-        if "track_miss" in cost_args or "det_new" in cost_args:
-            raise L.PcrError("%s: track_miss / det_new belong to the one-decision matrix; with decisions= the values are "
-                             "det_values / track_values" % who)
-        det_names, trk_names = sorted(decisions.get("detection", ())), sorted(decisions.get("tracking", ()))
-        dev = torch.device("cuda", torch.cuda.current_device())
-        values = []
-        for names, v, n, key in ((det_names, decisions.get("det_values"), D, "det_values"),
-                                 (trk_names, decisions.get("track_values"), T, "track_values")):
-            if v is None:
-                v = torch.zeros((len(names), n), dtype=torch.float32, device=dev)
-            v = L.tensor(v, who, "decisions[%r]" % key, torch.float32, copy=True)
-            if key == "det_values" and M is not None and v.dim() == 2 and v.shape[1] == M and M < n:
-                v = torch.cat([v, v.new_zeros((v.shape[0], n - M))], dim=1)
-            values.append(L.tensor(v, who, "decisions[%r]" % key, torch.float32, shape=(len(names), n)))
-        L.require_cuda(*values)
-        return dict(det_names=det_names, trk_names=trk_names, det_values=values[0], trk_values=values[1],
-                    kind=decisions.get("kind", "margin"), reduce=bool(decisions.get("reduce", False)),
-                    born=det_names.index("det_newborn") if "det_newborn" in det_names else -1,
-                    kill=trk_names.index("track_false_positive") if "track_false_positive" in trk_names else -1)
-
-    @staticmethod
-    def _assign(cost, T, D, dd, td, reduce, by_class):
-        """linear_assignment over cost, or -- by_class = (track_labels, det_labels, num_classes) -- the block rule: the ids
-        from the labels on the device, one wave per class (linear_assignment_blocks) and the solver's one word as the
-        maximum over the blocks -> (col4row (R,), row4col (C,), info (1,)), block_info (G,) or None"""
-        from pcr_amd import associate as A
-        if by_class is None:
-            col4row, row4col, info = A.linear_assignment(cost)
-            return (col4row[0], row4col[0], info), None
-        row_block, col_block, G = A.association_blocks(by_class[0], by_class[1], T, D, dd, td, num_classes=by_class[2],
-                                                       reduce=reduce)
-        col4row, row4col, block_info = A.linear_assignment_blocks(cost, row_block, col_block, G)
-        return (col4row, row4col, block_info.amax(dim=0, keepdim=True)), block_info
-
-    @staticmethod
-    def _assign_one(cost, T, D, by_class):
-        """_assign over association_cost's one-decision matrix, the columns >= D and the rows >= T (the miss / new diagonals)
-        read as -1 -> track_to_det (T,), det_to_track (D,), info (1,), block_info or None"""
-        (col4row, row4col, info), block_info = ReIDNet._assign(cost, T, D, 1, 1, False, by_class)
-        c, r = col4row[:T], row4col[:D]
-        return torch.where(c < D, c, torch.full_like(c, -1)), torch.where(r < T, r, torch.full_like(r, -1)), info, block_info
-
-    def _match_across(self, feats, xyz, pairs, offset, count):
-        """match_gallery over a gallery [a | b] of `offset` rows of a followed by b's, for pairs (row of a, row of b)"""
-        gallery_pairs = torch.stack([pairs[:, 0], pairs[:, 1] + offset], dim=1)
-        return self.match_gallery(feats, xyz, gallery_pairs, count=count).contiguous()
-
-    @staticmethod
-    def _associate_decisions(logits, pairs, count, T, D, ds, dist, cost_args, by_class=None):
-        """the matrix for the decision set ds, its assignment and the decode (pcr_amd/associate.py) -> the entries that
-        associate / track_step return"""
-        from pcr_amd import associate as A
-        dd, td = len(ds["det_names"]), len(ds["trk_names"])
-        R, C = A.multi_shape(T, D, dd, td, ds["reduce"])
-        if not L.load().pcr_lsa_ok(1, R, C):
-            raise L.PcrError("decisions: the (%d, %d) matrix is beyond linear_assignment (PCR_LSA_MAX)" % (R, C))
-        out = A.association_cost_multi(logits, pairs, count, T, D, ds["det_values"], ds["trk_values"], kind=ds["kind"],
-                                       reduce=ds["reduce"], dist=dist, **cost_args)
-        cost, choices = (out[0], (out[1], out[2])) if ds["reduce"] else (out, None)
-        assignment, block_info = ReIDNet._assign(cost, T, D, dd, td, ds["reduce"], by_class)
-        dec = A.decode_assignment(cost, assignment, T, D, dd, td, fill=cost_args.get("fill", 10000.0), choices=choices,
-                                  born_decision=ds["born"], kill_decision=ds["kill"])
-        return dict(track_to_det=dec["track_to_det"], det_to_track=dec["det_to_track"], cost=cost, info=assignment[2],
-                    det_decision=dec["det_decision"], track_decision=dec["track_decision"], born=dec["born"],
-                    kill=dec["kill"], decode_info=dec["info"], **({} if block_info is None else {"block_info": block_info}))
+        return pairs_head.pair_logits(pl, emb, u, v, pairs, count=gallery.pair_count(count), dead_value=dead_value)
 
     def associate(self, track_feats, track_xyz, track_labels, track_lengths, det_feats, det_xyz, det_labels, det_lengths,
                   min_points=2, num_classes=8, cap=None, live_only=False, decisions=None, by_class=False, **cost_args):
@@ -798,35 +597,8 @@ class ReIDNet(nn.Module):
         (D,) = the detections that took 'det_newborn', kill (T,) = the tracks that took 'track_false_positive' (all zero when
         the name is absent) and decode_info (4,).  An empty side is no special case then: the detections of a first frame
         still take their decisions."""
-        from pcr_amd import associate as A
-        L.require_cuda(track_feats, track_xyz, det_feats, det_xyz)
-        T, D = track_feats.shape[0], det_feats.shape[0]
-        ds = None if decisions is None else self._decision_set(decisions, T, D, cost_args, "associate")
-        pairs, count = A.compare_pairs(track_labels, det_labels, track_lengths, det_lengths, min_points=min_points,
-                                       num_classes=num_classes, cap=cap)
-        dev = track_feats.device
-        blocks = (track_labels, det_labels, num_classes) if by_class else None
-        if ds is not None:
-            if T == 0 or D == 0:
-                pairs, logits = pairs[:0], torch.empty((0,), dtype=torch.float32, device=dev)
-            else:
-                logits = self._match_across(torch.cat([track_feats, det_feats], dim=0), torch.cat([track_xyz, det_xyz], dim=0),
-                                            pairs, T, count if live_only else None)
-            dist = cost_args.pop("dist", None)
-            return dict(pairs=pairs, count=count, logits=logits,
-                        **self._associate_decisions(logits, pairs, count, T, D, ds, dist, cost_args, by_class=blocks))
-        if T == 0 or D == 0:
-            empty = {"block_info": torch.zeros((num_classes + 1,), dtype=torch.int32, device=dev)} if by_class else {}
-            return dict(track_to_det=torch.full((T,), -1, dtype=torch.int32, device=dev),
-                        det_to_track=torch.full((D,), -1, dtype=torch.int32, device=dev), pairs=pairs, count=count,
-                        logits=torch.empty((pairs.shape[0],), dtype=torch.float32, device=dev), cost=None,
-                        info=torch.zeros((1,), dtype=torch.int32, device=dev), **empty)
-        logits = self._match_across(torch.cat([track_feats, det_feats], dim=0), torch.cat([track_xyz, det_xyz], dim=0),
-                                    pairs, T, count if live_only else None)                # detections follow the tracks
-        cost = A.association_cost(logits, pairs, count, T, D, **cost_args)
-        t2d, d2t, info, block_info = self._assign_one(cost, T, D, blocks)
-        return dict(track_to_det=t2d, det_to_track=d2t, pairs=pairs, count=count, logits=logits, cost=cost, info=info,
-                    **({} if block_info is None else {"block_info": block_info}))
+        return frame.associate(self, track_feats, track_xyz, track_labels, track_lengths, det_feats, det_xyz, det_labels,
+                               det_lengths, min_points, num_classes, cap, live_only, decisions, by_class, cost_args)
 
     def retrieve(self, q_feats, q_xyz, q_labels, q_lengths, g_feats, g_xyz, g_labels, g_lengths, query_ids=None,
                  gallery_ids=None, topk=10, exclude=None, min_points=2, num_classes=8, live_only=False):
@@ -840,23 +612,8 @@ class ReIDNet(nn.Module):
         holds the queries).  live_only: match_gallery scores the count listed pairs only.
         -> rank_gallery's dict (topk_idx, topk_score (Q, topk), n_cand, n_true, first_hit, ap, info (Q,)) plus pairs,
         count, logits and scores (Q, G)."""
-        from pcr_amd import associate as A
-        from pcr_amd import retrieval as R
-        L.require_cuda(q_feats, q_xyz, g_feats, g_xyz)
-        Q, G = q_feats.shape[0], g_feats.shape[0]
-        if not R.rank_ok(Q, G, topk):
-            raise L.PcrError("retrieve: Q=%d G=%d topk=%d is out of range (pcr_rank_ok)%s" % (
-                Q, G, topk, "; retrieve_wide ranks a gallery above %d entries" % R.MAX_GALLERY if G > R.MAX_GALLERY else ""))
-        pairs, count = A.compare_pairs(q_labels, g_labels, q_lengths, g_lengths, min_points=min_points,
-                                       num_classes=num_classes)
-        if Q == 0 or G == 0:
-            logits = torch.empty((pairs.shape[0],), dtype=torch.float32, device=q_feats.device)
-        else:
-            logits = self._match_across(torch.cat([q_feats, g_feats], dim=0), torch.cat([q_xyz, g_xyz], dim=0),
-                                        pairs, Q, count if live_only else None)            # the gallery follows the queries
-        scores = R.score_matrix(logits, pairs, count, Q, G)
-        out = R.rank_gallery(scores, query_ids, gallery_ids, topk=topk, exclude=exclude)
-        return dict(pairs=pairs, count=count, logits=logits, scores=scores, **out)
+        return retrieval.retrieve(self, q_feats, q_xyz, q_labels, q_lengths, g_feats, g_xyz, g_labels, g_lengths, query_ids,
+                                  gallery_ids, topk, exclude, min_points, num_classes, live_only)
 
     def retrieve_wide(self, q_feats, q_xyz, q_labels, q_lengths, g_feats, g_xyz, g_labels, g_lengths, query_ids=None,
                       gallery_ids=None, topk=10, exclude=None, min_points=2, num_classes=8, live_only=False,
@@ -871,33 +628,9 @@ class ReIDNet(nn.Module):
         -> rank_gallery's seven outputs plus scores (Q, G) and counts (blocks,) int32, the blocks' pair counts on the device.
         The number of launches depends on the shapes alone.  For G <= 4096 scores and the seven outputs equal retrieve's bit
         for bit whatever gallery_block is: the logit of a pair does not depend on what else is in its batch."""
-        from pcr_amd import associate as A
-        from pcr_amd import retrieval as R
-        L.require_cuda(q_feats, q_xyz, g_feats, g_xyz)
-        Q, G, block = q_feats.shape[0], g_feats.shape[0], int(gallery_block)
-        if not 1 <= block <= R.MAX_GALLERY:
-            raise L.PcrError("retrieve_wide: gallery_block=%d: 1 to %d" % (block, R.MAX_GALLERY))
-        if not R.rank_wide_ok(Q, G, topk):
-            raise L.PcrError("retrieve_wide: Q=%d G=%d topk=%d is out of range (pcr_rank_wide_ok)" % (Q, G, topk))
-        dev = q_feats.device
-        scores = R.fill_scores(L.out_tensor(scores, "retrieve_wide", "scores", torch.float32, (Q, G), dev))
-        counts = []
-        g_labels = L.tensor(g_labels, "retrieve_wide", "g_labels", torch.int32, shape=(G,), cast_int64=True, copy=True)
-        g_lengths = L.tensor(g_lengths, "retrieve_wide", "g_lengths", torch.int32, shape=(G,), optional=True, cast_int64=True,
-                             copy=True)
-        for lo in range(0, G, block):
-            hi = min(G, lo + block)
-            pairs, count = A.compare_pairs(q_labels, g_labels[lo:hi], q_lengths, None if g_lengths is None else g_lengths[lo:hi],
-                                           min_points=min_points, num_classes=num_classes)
-            counts.append(count)
-            if Q == 0:
-                continue
-            logits = self._match_across(torch.cat([q_feats, g_feats[lo:hi]], dim=0), torch.cat([q_xyz, g_xyz[lo:hi]], dim=0),
-                                        pairs, Q, count if live_only else None)            # the block follows the queries
-            R.scatter_scores(logits, pairs, count, scores, lo, hi - lo)
-        out = R.rank_gallery_wide(scores, query_ids, gallery_ids, topk=topk, exclude=exclude)
-        counts = torch.cat(counts) if counts else torch.zeros((0,), dtype=torch.int32, device=dev)
-        return dict(scores=scores, counts=counts, **out)
+        return retrieval.retrieve_wide(self, q_feats, q_xyz, q_labels, q_lengths, g_feats, g_xyz, g_labels, g_lengths,
+                                       query_ids, gallery_ids, topk, exclude, min_points, num_classes, live_only,
+                                       gallery_block, scores)
 
     def track_step(self, bank, sweep, boxes, labels, scores, carry=None, carry_inv=None, min_points=2, num_classes=8,
                    cap=None, n=None, crop_args=None, born=None, kill=None, frame_limit=10, replace_all=False,
@@ -950,111 +683,10 @@ class ReIDNet(nn.Module):
         labels on the device each frame (free slots and padded detections share the rest block), so one captured graph
         follows changing classes; the dict gains block_info (num_classes + 1,).  It composes with live_only, decisions=
         and truth=."""
-        from pcr_amd import associate as A
-        from pcr_amd import tracks as TR
-        if truth is None and force_truth:
-            raise L.PcrError("track_step: force_truth needs truth=")
-        if truth is not None:
-            from pcr_amd import truth as TU
-            book = truth.get("book") if isinstance(truth, dict) else None
-            if not isinstance(book, TU.TruthBook) or book.bank is not bank:
-                raise L.PcrError("track_step: truth['book'] must be a pcr_amd.truth.TruthBook made over this bank")
-            identity = truth.get("identity")
-            if identity is not None:
-                from pcr_amd import identity as ID
-                if not isinstance(identity, ID.IdentityBook) or identity.book is not book:
-                    raise L.PcrError("track_step: truth['identity'] must be a pcr_amd.identity.IdentityBook made over "
-                                     "truth['book']")
-        if not isinstance(bank, TR.TrackBank):
-            raise L.PcrError("track_step: bank must be a pcr_amd.tracks.TrackBank")
-        if decisions is not None and (born is not None or kill is not None):
-            raise L.PcrError("track_step: with decisions= the born / kill masks come from the decoded decisions; pass one or "
-                             "the other")
-        C, D, W = bank.capacity, bank.max_dets, bank.box_width
-        if update_config is not None:
-            if decisions is None:
-                raise L.PcrError("track_step: update_config applies to decoded decisions; pass decisions= with it")
-            if born is not None or kill is not None or not propagate or force_truth:
-                raise L.PcrError("track_step: update_config cannot be combined with born= / kill=, propagate= or "
-                                 "force_truth=: the rules decide what is born, dropped and propagated")
-        if log is not None:
-            if update_config is None:
-                raise L.PcrError("track_step: log= records the output table; pass update_config= with it")
-            if not isinstance(log, TR.SceneLog) or (log.rows_per_frame, log.box_width) != (C + D, W):
-                raise L.PcrError("track_step: log must be a pcr_amd.tracks.SceneLog of %d rows per frame and box width %d"
-                                 % (C + D, W))
-        boxes = L.tensor(boxes, "track_step", "boxes", torch.float32, shape=(None, W), copy=True)
-        M = boxes.shape[0]
-        L.require(M <= D, "track_step", "boxes must be (M <= %d, %d), got %s", D, W, tuple(boxes.shape))
-        scores = L.tensor(scores, "track_step", "scores", torch.float32, shape=(M,), copy=True)
-        L.require(isinstance(labels, torch.Tensor) and labels.shape == (M,), "track_step", "labels must be (M,)")
-        L.require_cuda(sweep, boxes, labels, scores)
-        ds = None if decisions is None else self._decision_set(decisions, C, D, cost_args, "track_step", M=M)
-        rules = None if update_config is None else TR.UpdateRules(update_config, ds["det_names"], ds["trk_names"])
-        if ds is None and not L.load().pcr_lsa_ok(1, C + D, C + D):
-            raise L.PcrError("track_step: capacity + max_dets = %d is beyond linear_assignment (PCR_LSA_MAX)" % (C + D))
-        if ds is not None:
-            from pcr_amd.associate import multi_shape
-            if not L.load().pcr_lsa_ok(1, *multi_shape(C, D, len(ds["det_names"]), len(ds["trk_names"]), ds["reduce"])):
-                raise L.PcrError("track_step: the decisions' matrix for capacity %d and max_dets %d is beyond "
-                                 "linear_assignment (PCR_LSA_MAX)" % (C, D))
-        labels = labels.to(torch.int32)
-        if M < D:                                   # padding: a box of size zero holds no point, label -1 joins nothing
-            boxes = torch.cat([boxes, boxes.new_zeros((D - M, W))], dim=0)
-            labels = torch.cat([labels, labels.new_full((D - M,), -1)], dim=0)
-            scores = torch.cat([scores, scores.new_zeros((D - M,))], dim=0)
-            if born is not None and born.shape == (M,):
-                born = torch.cat([born, born.new_zeros((D - M,))], dim=0)
-        boxes, labels, scores = boxes.contiguous(), labels.contiguous(), scores.contiguous()
-        xyz, feats, lengths = self.forward_inference_boxes(sweep, boxes[:, :7].contiguous(), n=n, **(crop_args or {}))
-        if tuple(feats.shape[1:]) != bank.feat_shape or tuple(xyz.shape[1:]) != (bank.feat_shape[1], 3):
-            raise L.PcrError("track_step: the encoder returns features %s, the bank was made for %s"
-                             % (tuple(feats.shape[1:]), bank.feat_shape))
-        bank.det_feats.copy_(feats)
-        bank.det_xyz.copy_(xyz)
-        dist = bank.distances(boxes, carry_inv)
-        pairs, count = A.compare_pairs(bank.labels, labels, bank.lengths, lengths, min_points=min_points,
-                                       num_classes=num_classes, cap=cap)
-        logits = self._match_across(bank.gallery, bank.gallery_xyz, pairs, C,
-                                    count if live_only else None)                          # detections follow the bank's rows
-        blocks = (bank.labels, labels, num_classes) if by_class else None
-        decoded = {}
-        if ds is not None:
-            decoded = self._associate_decisions(logits, pairs, count, C, D, ds, dist if ds["kind"] == "margin" else None,
-                                                cost_args, by_class=blocks)
-            t2d, d2t, cost, info = (decoded.pop(k) for k in ("track_to_det", "det_to_track", "cost", "info"))
-            born, kill = decoded["born"], decoded["kill"]
-        else:
-            cost = A.association_cost(logits, pairs, count, C, D, dist=dist, **cost_args)
-            t2d, d2t, info, block_info = self._assign_one(cost, C, D, blocks)
-            if block_info is not None:
-                decoded["block_info"] = block_info
-        decisions, truth_out = (t2d, d2t), {}
-        if truth is not None:
-            book.match(boxes, labels, truth)
-            truth_out = book.decide(decisions, labels, born=born, kill=kill, forced=force_truth)
-            if force_truth:
-                decisions, born, kill = book.forced()
-        dets = dict(labels=labels, lengths=lengths, boxes=boxes, scores=scores)
-        if rules is not None:
-            det_slot, det_id, bank_info, table = bank.update_rules(
-                decisions, dets, decoded["det_decision"], decoded["track_decision"], rules, carry=carry,
-                frame_limit=frame_limit, replace_all=replace_all, reset_on_match=reset_on_match)
-            decoded = dict(decoded, **table)
-            if log is not None:
-                log.append(table)
-        else:
-            det_slot, det_id, bank_info = bank.update(decisions, dets, born=born, kill=kill, carry=carry,
-                                                      frame_limit=frame_limit, replace_all=replace_all,
-                                                      reset_on_match=reset_on_match, propagate=propagate)
-        if suppress_threshold is not None:
-            bank.suppress(suppress_threshold)
-        if truth is not None:
-            book.record(det_slot, det_id)
-            if identity is not None:
-                identity.record(det_id)
-        return dict(track_to_det=t2d, det_to_track=d2t, pairs=pairs, count=count, logits=logits, cost=cost, info=info,
-                    det_slot=det_slot, det_id=det_id, bank_info=bank_info, dist=dist, lengths=lengths, **decoded, **truth_out)
+        return frame.track_step(self, bank, sweep, boxes, labels, scores, carry, carry_inv, min_points, num_classes, cap, n,
+                                crop_args, born, kill, frame_limit, replace_all, reset_on_match, propagate,
+                                suppress_threshold, live_only, truth, force_truth, decisions, by_class, update_config, log,
+                                cost_args)
 
     def get_match_supervision(self, h1, h2, xyz1, xyz2, id_1, id_2):
         return h1, h2, xyz1, xyz2, (id_1 == id_2).float()
@@ -1063,11 +695,7 @@ class ReIDNet(nn.Module):
         if not self.losses_to_use["match"]:
             return None, torch.tensor(0.0, requires_grad=True, device=device), (None, None)
         b = h1.shape[0]
-        lvl = self.precision_level()
-        if lvl:
-            with engine.guard_level(lvl):
-                match_preds, o = self._match_logits(h1, h2, xyz1, xyz2)
-        else:
+        with self._at_level(self.precision_level()):
             match_preds, o = self._match_logits(h1, h2, xyz1, xyz2)
         match_loss = self.bce(match_preds, match) * self.alpha["match"]
         if o is None:

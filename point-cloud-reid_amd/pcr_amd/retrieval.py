@@ -21,6 +21,8 @@ import torch
 
 from . import _lib as L
 from . import abi
+from . import associate as A
+from .frame import match_across
 
 MAX_QUERIES, MAX_GALLERY, MAX_K, MAX_RANKS = 65535, 4096, 64, 8      # PCR_RANK_MAX_*
 WIDE_MAX_GALLERY, WIDE_MAX_TRUE = 4194304, 4096                      # PCR_RANK_WIDE_MAX_* (section A12)
@@ -232,6 +234,56 @@ def retrieval_split(table, row_of, seed=0):
             g_ids.append(-1)
     i32 = lambda a: np.asarray(a, dtype=np.int32)          # noqa: E731
     return i32(q_rows), i32(g_rows), i32(q_cls), i32(g_cls), i32(q_ids), i32(g_ids)
+
+
+def retrieve(model, q_feats, q_xyz, q_labels, q_lengths, g_feats, g_xyz, g_labels, g_lengths, query_ids, gallery_ids, topk,
+             exclude, min_points, num_classes, live_only):
+    """ReIDNet.retrieve, which has the contract and the defaults"""
+    L.require_cuda(q_feats, q_xyz, g_feats, g_xyz)
+    Q, G = q_feats.shape[0], g_feats.shape[0]
+    if not rank_ok(Q, G, topk):
+        raise L.PcrError("retrieve: Q=%d G=%d topk=%d is out of range (pcr_rank_ok)%s" % (
+            Q, G, topk, "; retrieve_wide ranks a gallery above %d entries" % MAX_GALLERY if G > MAX_GALLERY else ""))
+    pairs, count = A.compare_pairs(q_labels, g_labels, q_lengths, g_lengths, min_points=min_points,
+                                   num_classes=num_classes)
+    if Q == 0 or G == 0:
+        logits = torch.empty((pairs.shape[0],), dtype=torch.float32, device=q_feats.device)
+    else:
+        logits = match_across(model, torch.cat([q_feats, g_feats], dim=0), torch.cat([q_xyz, g_xyz], dim=0),
+                              pairs, Q, count if live_only else None)                      # the gallery follows the queries
+    scores = score_matrix(logits, pairs, count, Q, G)
+    out = rank_gallery(scores, query_ids, gallery_ids, topk=topk, exclude=exclude)
+    return dict(pairs=pairs, count=count, logits=logits, scores=scores, **out)
+
+
+def retrieve_wide(model, q_feats, q_xyz, q_labels, q_lengths, g_feats, g_xyz, g_labels, g_lengths, query_ids, gallery_ids,
+                  topk, exclude, min_points, num_classes, live_only, gallery_block, scores):
+    """ReIDNet.retrieve_wide, which has the contract and the defaults"""
+    L.require_cuda(q_feats, q_xyz, g_feats, g_xyz)
+    Q, G, block = q_feats.shape[0], g_feats.shape[0], int(gallery_block)
+    if not 1 <= block <= MAX_GALLERY:
+        raise L.PcrError("retrieve_wide: gallery_block=%d: 1 to %d" % (block, MAX_GALLERY))
+    if not rank_wide_ok(Q, G, topk):
+        raise L.PcrError("retrieve_wide: Q=%d G=%d topk=%d is out of range (pcr_rank_wide_ok)" % (Q, G, topk))
+    dev = q_feats.device
+    scores = fill_scores(L.out_tensor(scores, "retrieve_wide", "scores", torch.float32, (Q, G), dev))
+    counts = []
+    g_labels = L.tensor(g_labels, "retrieve_wide", "g_labels", torch.int32, shape=(G,), cast_int64=True, copy=True)
+    g_lengths = L.tensor(g_lengths, "retrieve_wide", "g_lengths", torch.int32, shape=(G,), optional=True, cast_int64=True,
+                         copy=True)
+    for lo in range(0, G, block):
+        hi = min(G, lo + block)
+        pairs, count = A.compare_pairs(q_labels, g_labels[lo:hi], q_lengths, None if g_lengths is None else g_lengths[lo:hi],
+                                       min_points=min_points, num_classes=num_classes)
+        counts.append(count)
+        if Q == 0:
+            continue
+        logits = match_across(model, torch.cat([q_feats, g_feats[lo:hi]], dim=0), torch.cat([q_xyz, g_xyz[lo:hi]], dim=0),
+                              pairs, Q, count if live_only else None)                      # the block follows the queries
+        scatter_scores(logits, pairs, count, scores, lo, hi - lo)
+    out = rank_gallery_wide(scores, query_ids, gallery_ids, topk=topk, exclude=exclude)
+    counts = torch.cat(counts) if counts else torch.zeros((0,), dtype=torch.int32, device=dev)
+    return dict(scores=scores, counts=counts, **out)
 
 
 def _encode(model, clouds, batch):

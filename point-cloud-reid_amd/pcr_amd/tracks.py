@@ -72,7 +72,7 @@ class UpdateRules:
 
     update_config  the keys match, det_newborn, det_false_positive, track_false_positive, track_false_negative, each
                    dict(output=, active=, decom=); every decision name in use and `match` need an entry
-    det_names, trk_names  the sorted decision names of the frame, as `ReIDNet._decision_set` produces them
+    det_names, trk_names  the sorted decision names of the frame, as `pcr_amd.frame.decision_set` produces them
     -> match_rule, det_rule (dd,), trk_rule (td,), trk_kind (td,): `track_false_negative` is TRK_MISS (the track is
     propagated), every other tracking decision TRK_KEEP.  active and decom together are refused, as the reference does."""
 

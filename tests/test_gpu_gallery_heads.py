@@ -148,8 +148,9 @@ def test_xcorr_baseline_gallery_equals_the_pairwise_entry():
     assert not torch.equal(f32_gallery[0], f32_gallery[1])               # logits(0, 4) != logits(4, 0)
 
 
-@pytest.mark.parametrize("head", ["concat", "xcorr-baseline", "xcorr"])
-def test_count_gates_the_list(head):
+@pytest.mark.parametrize("head,chunk", [pytest.param(h, c, id=h if c is None else "%s-chunk%d" % (h, c))
+                                        for c in (None, 5) for h in ("concat", "xcorr-baseline", "xcorr")])
+def test_count_gates_the_list(head, chunk, monkeypatch):
     m = model_of(head)
     clouds = T.synthetic_clouds(7, 128, seed=21, kind="randn").cuda()
     with torch.no_grad():
@@ -162,6 +163,8 @@ def test_count_gates_the_list(head):
     count = torch.tensor([7], dtype=torch.int32, device="cuda")
     with torch.no_grad():
         full = m.match_gallery(h, xyz, pairs)
+        if chunk is not None:        # four passes over the 20 slots: the count falls inside the second, two are wholly dead
+            monkeypatch.setattr(type(m), "GALLERY_CHUNK", chunk)
         gated = m.match_gallery(h, xyz, pairs, count=count, dead_value=-3.25)
         # the padded object's features poisoned: NaN where the gate reads nothing of a dead pair; for 'xcorr', whose
         # local stages run on every pair, other finite features (its dead logits are replaced, not skipped)

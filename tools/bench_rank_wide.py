@@ -97,6 +97,7 @@ def main():
         raise SystemExit("bench_rank_wide: no GPU (this tool measures on the device only)")
     import bench
     from pcr_amd import associate as A
+    from pcr_amd import frame
     from pcr_amd import retrieval as RT
     from pcr_amd import testing as PT
     rec = {"tool": "tools/bench_rank_wide.py", "window_s": args.window, "repeats": args.repeats,
@@ -157,8 +158,8 @@ def main():
         kept = []
         for lo in range(0, G, BLOCK):                                   # the pair lists and logits retrieve_wide does not keep
             pairs, count = A.compare_pairs(q_cls, g_cls[lo:lo + BLOCK], num_classes=CLASSES)
-            logits = model._match_across(torch.cat([h[:Q], h[Q + lo:Q + lo + BLOCK]]),
-                                         torch.cat([xyz[:Q], xyz[Q + lo:Q + lo + BLOCK]]), pairs, Q, count)
+            logits = frame.match_across(model, torch.cat([h[:Q], h[Q + lo:Q + lo + BLOCK]]),
+                                        torch.cat([xyz[:Q], xyz[Q + lo:Q + lo + BLOCK]]), pairs, Q, count)
             kept.append((logits, pairs, count, lo, min(BLOCK, G - lo)))
         check = torch.empty_like(scores)
 

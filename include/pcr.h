@@ -1239,7 +1239,7 @@ typedef struct pcr_sa_params {
    * (wps); PCR_PREC_BF16X3 = split bf16, three bf16 MFMAs per product with f32 accumulation; PCR_PREC_BF16 = plain bf16
    * activations and weights, f32 accumulation (BASELINE config 2 as stated).  wps_bf[l]: pcr_pack_weight_bf16x2_f32
    * images of the matrices wps[l] holds.  Shapes the bf16 kernels do not cover run in f32 (pcr_last_launch_arith says
-   * so).  Among them, not exhaustively (sa2_try is the rule, tests/sa_ref.py restates it): c1 or c2 no multiple of 32; a
+   * so).  Among them, not exhaustively (sa_make_plan is the rule, tests/sa_ref.py restates it): c1 or c2 no multiple of 32; a
    * layer wider than 256; in the K-row kernel K no multiple of 16, and a layer 2 of up to 128 channels (one cout-block
    * round) whose layer 1 cannot share its class on the matrix core (32 / 64 / 64, 64 / 32 / 32, 64 / 128 / 256); layer classes
    * other than equal ones and (64 -> up to 128 channels) -- in particular 64 / 64 / c3 with 129 <= c3 <= 256, whose last
@@ -1279,6 +1279,30 @@ long pcr_sa_tile_ws_ints(int B, int S, int K, int c2, int c3);
 int pcr_sa_krow_uses_tiles(int c1, int c2, int c3, int K, int precision);
 /* 1: a ball-query layer of this shape with hit counts reads pcr_sa_params.row_tab when given (shape-only) */
 int pcr_sa_uses_row_table(int c1, int c2, int c3, int K, int precision);
+/* Which kernel would pcr_sa_mlp_f32 launch for *p?  The dispatcher's own plan (csrc/sa_kernels_impl.h: sa_make_plan) and
+ * nothing else; no device is touched, pointers are read against NULL only, nothing is launched and
+ * pcr_last_launch_arith is left alone.  Returns what the launch would return before its first kernel (PCR_ERR_INVALID
+ * for a block it refuses) and writes PCR_SA_FORM_INTS ints:
+ *   form[0]  the arithmetic unit that runs layers 2 and 3 (PCR_PREC_*: a shape the asked bf16 unit does not hold says F32)
+ *   form[1]  the kernel family, PCR_SA_*
+ *   form[2]  PCR_SA_STREAM_RAG: 0 = index form on 8 waves, 1 = row-table form on 8 waves, 2 = row-table form on 12; else 0
+ *   form[3]  n = the number of template arguments that follow
+ *   form[4 .. 4 + n)  the kernel's template arguments in the kernel's order, defaults filled in, bools as 0 / 1:
+ *     PCR_SA_GENERIC     sa_mlp_kernel            none
+ *     PCR_SA_KROW_TILE   sa_fused_kernel          TB, NR, W2, W3, MAXE, NR2, RKB, PREC, IMG
+ *     PCR_SA_RAG_TILE    sa_rag_kernel            TB, NR, W2, W3, NR2, W1, PREC
+ *     PCR_SA_STREAM      sa_stream_kernel         NCB, NCB3, LO
+ *     PCR_SA_STREAM_RAG  sa_stream_rag_kernel     NCB, NCB3, LO, TAB, WAVES
+ *     PCR_SA_WSPLIT      sa_wsplit_rag_kernel     NCB, NCB3, LO
+ * the rest is zero. */
+#define PCR_SA_FORM_INTS 16
+#define PCR_SA_GENERIC 0
+#define PCR_SA_KROW_TILE 1
+#define PCR_SA_RAG_TILE 2
+#define PCR_SA_STREAM 3
+#define PCR_SA_STREAM_RAG 4
+#define PCR_SA_WSPLIT 5
+int pcr_sa_launch_form(const pcr_sa_params *p, int *form);
 
 /* Per-point linear map with POINT-major output: x (B,cin,L) channel-major (or (B,L,cin) when x_point_major)
  * -> y (B,L,cout) = W x, wp packed (cout,cin), cout <= 1024 (a multiple of 4 beyond 256).  This is the table builder of the decomposed first

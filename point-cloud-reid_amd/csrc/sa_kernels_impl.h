@@ -2,13 +2,14 @@
 //   sa_kernels.hip      PCR_SA_PREC 0  f32-input MFMA (exact fmaf chains), every shape, and the C-ABI entry points
 //   sa_kernels_bf3.hip  PCR_SA_PREC 1  split bf16 (three v_mfma_f32_32x32x16_bf16 per product, ~2e-6 of the f32 result)
 //   sa_kernels_bf1.hip  PCR_SA_PREC 2  plain bf16 activations / weights, f32 accumulate (BASELINE config 2 as stated)
-// The bf16 units instantiate the explicit-shape kernels only and export pcr_sa2_try_bf3 / _bf1 to the first one.
+// The bf16 units instantiate the explicit-shape kernels only and export pcr_sa2_unit_bf3 / _bf1 to the first one.
 #pragma once
 #ifndef PCR_SA_PREC
 #define PCR_SA_PREC 0
 #endif
 #include <stdio.h>
 
+#include <initializer_list>
 #include <vector>
 
 #include "tile_dense.h"
@@ -446,8 +447,10 @@ using SaSkipTrace = WaveTrace<2, kTraceTiles, kTraceMarks, kTraceWgs, true>;
 __device__ unsigned long long g_rag_trace[SaTrace::kCap * SaTrace::kWords];
 constexpr int kSasWaves = 8;
 
-// ---- launch shapes: ONE definition of each rule, read by sa2_try in all three units and by the f32 unit's exported shape
-// queries (what engine.py asks before it builds row tables, tables with the coordinate term and workspaces)
+// ---- launch shapes: ONE definition of each rule, read by sa_make_plan in all three units and by the f32 unit's exported
+// shape queries (what engine.py asks before it builds row tables, tables with the coordinate term and workspaces)
+// dynamic LDS a workgroup of the tile kernels (generic, K-row, ragged) may ask for: 150 of the chip's 160 KiB (kMaxDynLds)
+constexpr size_t kSaTileLdsBudget = 150 * 1024;
 // the "ways" class of a layer of n 32-channel cout blocks
 static int sa_ways(int n) { return n >= 3 ? 1 : (n == 2 ? 2 : 4); }
 // rows of a tile of the ragged tile kernel: 64 when a layer has more than four cout blocks
@@ -489,6 +492,11 @@ static size_t sas_rag_lds(int c1, int c3, int K, int waves, bool tab) {
 static bool sas_shape(int c1, int c2, int c3, int K, bool both_forms) {
   if (c1 != c2 || !(c3 == c2 || c3 == 2 * c2) || !(c1 == 32 || c1 == 64 || c1 == 128) || !sas_k_ok(K)) return false;
   return sas_krow_lds(c1, c3) <= (size_t)kMaxDynLds && (!both_forms || sas_rag_lds(c1, c3, K, kSasWaves, false) <= (size_t)kMaxDynLds);
+}
+// a ball-query layer with hit counts runs the wave-autonomous ragged form (bf16 units): the plan asks for a tile-kernel
+// instantiation of the shape before it looks at that form
+__attribute__((unused)) static bool sa_rag_streams(int c1, int c2, int c3, int K) {
+  return sa_tile_shape_ok(c2, c3) && sas_shape(c1, c2, c3, K, true);
 }
 
 #if PCR_SA_PREC != 0
@@ -1102,6 +1110,11 @@ __host__ __device__ inline size_t rag_rowtab_off(int B, int maxT, int rows) {
 }
 __host__ __device__ inline size_t rag_ws_ints(int B, int maxT, int rows) {
   return rag_rowtab_off(B, maxT, rows) + (size_t)B * maxT * rows * 4;
+}
+// tiles of `rows` rows a cloud of S centres needs in the worst case (K <= rows): whole centres per tile
+inline int rag_max_tiles(int S, int K, int rows) {
+  const int per_tile = rows / rag_ceil(K);
+  return (S + per_tile - 1) / per_tile;
 }
 
 // one WAVE per cloud: the counts arrive 64 at a time with one coalesced load, the greedy walk itself runs
@@ -2347,61 +2360,255 @@ void dense_pm_xyz_res_kernel(DensePmArgs a, int tpc, long ntile) {
 
 }  // namespace
 
-template <int TB, int NR, int W2, int W3, int NR2 = NR, int RKB = 0>
-static int sa2_launch_one(const Sa2Args &a, bool maxe, size_t lds, hipStream_t st, dim3 grid) {
-  // bf16 forms: layers whose first layer runs on the matrix core (NR2 == 1; the launcher has checked a.l1m) keep their
-  // activations as bf images
-  constexpr bool kImgK = kPrec != 0 && NR2 == 1;
-  if (maxe) return pcr_launch_lds<sa_fused_kernel<TB, NR, W2, W3, true, NR2, RKB, kPrec, kImgK>>(grid, dim3(kThreads), lds, st, a);
-  if constexpr (kPrec == 0)
-    return pcr_launch_lds<sa_fused_kernel<TB, NR, W2, W3, false, NR2, RKB, kPrec>>(grid, dim3(kThreads), lds, st, a);
+// ---- the dispatch, compiled once per arithmetic unit.  sa_make_plan is the single statement of what a unit decides for a
+// launch -- kernel family, template arguments, everything shape-derived the launch needs -- and touches neither the device
+// nor the chip's size; one launcher per family turns a plan into launches.  The f32 unit also holds the order of the units,
+// the exported queries (which ask the plan's own predicates) and pcr_sa_mlp_f32.
+
+// tuning builds' knobs (0 / null in production builds: pcr_common.h), gathered once per process and unit; PCR_SA_DBG is
+// re-read for every launch (in-process A/Bs: tools/ab/ab_dbg_inproc.py)
+struct SaTune {
+  int no_stream, no_w12, no_wsplit, no_l1m;   // diagnostics: a form switched off
+  int cpw;                                    // tuning aid: centres per workgroup of the K-row tile kernel
+  int small_items;                            // diagnostics: the K-row stream kernel's smallest item instead of its largest
+  int no_xyz_tables;                          // diagnostics: pcr_sa_tables_take_xyz answers 0
+  const char *trace;                          // PCR_SA_TRACE: file the persistent kernels' stamps are appended to
+  int dbg;                                    // PCR_SA_DBG ablation mask
+};
+static SaTune sa_tune() {
+  static const SaTune once = {pcr_tune_int("PCR_SA_NO_STREAM"), pcr_tune_int("PCR_SA_NO_W12"), pcr_tune_int("PCR_SA_NO_WSPLIT"),
+                              pcr_tune_int("PCR_SA_NO_L1M"),    pcr_tune_int("PCR_SA_CPW"),    pcr_tune_int("PCR_SAS_SMALL_ITEMS"),
+                              pcr_tune_int("PCR_SA_NO_XYZ_TABLES"), pcr_tune_str("PCR_SA_TRACE"), 0};
+  SaTune t = once;
+  t.dbg = pcr_tune_int("PCR_SA_DBG");
+  return t;
+}
+
+// What one launch does.  family / variant / targ are pcr_sa_launch_form's encoding (pcr.h); the rest is what the family's
+// launcher reads besides the parameter block.  Grid sizes depend on the chip and are the launchers' business.
+struct SaPlan {
+  int unit = -1;              // PCR_PREC_* of the unit that takes the launch; set as soon as the unit has all its operands
+  int family = 0, variant = 0;
+  int ntarg = 0, targ[9] = {};   // the kernel's template arguments, defaults filled in
+  bool tables = false;        // layer 1's per-point tables are built first (features given, pq_ready not set), pqw floats a row
+  bool plan_kernels = false;  // the ragged tile plan's four helper kernels run first
+  bool claims = false;        // sa_stream_kernel: items are claimed from counters in claim_ws
+  bool xt = false;            // sa_stream_kernel: the tables carry the coordinate term (pq_has_xyz)
+  int pqw = 0, dbg = 0;
+  int cpw = 0, tb = 0;        // tile kernels: centres per workgroup, 32-row blocks per tile
+  int l1m = 0, maxe = 0;      // K-row tile kernel: layer 1 on the matrix core; K % 16 == 0 (max from the accumulators)
+  int nblk_item = 0, ncen_item = 0;   // sa_stream_kernel: 32-row blocks and centres per item
+  int rows = 0, maxT = 0;     // ragged tile plan: rows per tile, tiles per cloud in the worst case
+  int waves = 0;              // sa_stream_rag_kernel: 8 or 12
+  size_t lds = 0;             // dynamic LDS of the main kernel
+};
+
+constexpr int kSaNext = -1;   // refusal: the next unit, or the generic kernel
+constexpr int kSaFall = -2;   // (inside sa_make_plan) the tile plan does not take the launch: on to the K-row forms
+
+static int sa_plan_form(SaPlan *pl, int family, std::initializer_list<int> targ, int variant = 0) {
+  pl->family = family;
+  pl->variant = variant;
+  pl->ntarg = 0;
+  for (int v : targ) pl->targ[pl->ntarg++] = v;
   return PCR_OK;
 }
 
-// wsel: 1 / 2 / 4 when both MFMA layers have the same cout class (specialised bodies), else 0
-// nr2 / nr: cout-block rounds of layer 2 / of the wider of the two layers
-// bf16 units: the mixed class (2 ways in layer 2, 1 way in layer 3) exists with ONE cout-block round only, <TB,1,2,1> --
-// with W3 = 1, NR = 1 wave w computes cout block w and nothing else, four blocks = 128 channels.  A last layer of 129 ..
-// 256 channels behind two 64-channel layers (nr == 2) is therefore refused here and in sa2_try, and runs in the f32
-// unit's <TB,2,0,0,1>.
-template <int TB>
-static int sa2_launch_tb(const Sa2Args &a, int nr, int nr2, int w2, int w3, bool maxe, size_t lds, hipStream_t st,
-                         dim3 grid) {
-  const int wsel = kPrec != 0 ? 10 * w2 + w3 : (w2 == w3 ? w2 : 0);
-  // resident weight fragments for 32-channel layers (2 x 16 VGPRs).  For 64-channel layers the 2 x 32 VGPRs cost
-  // more residency than the saved L2 round trips are worth (measured: 6.4 -> 7.9 ms on the 64/64/64 layer).
-  const bool narrow4 = a.c1 <= 32 && a.c2 <= 32;
-  if constexpr (kPrec != 0) {
-    // bf16 forms: explicit shapes, max-from-accumulators epilogue, at most two cout-block rounds (the callers checked);
-    // w23 = 10 * (ways of layer 2) + (ways of layer 3)
-    (void)narrow4;
-    if (!maxe || nr > 2) return -1;
-    if (nr2 == 1 && !a.l1m) return -1;     // (the one-round instantiations are the bf-image ones: layer 1 on the matrix core)
-    if (wsel == 44) return sa2_launch_one<TB, 1, 4, 4>(a, maxe, lds, st, grid);
-    else if (wsel == 22) return sa2_launch_one<TB, 1, 2, 2>(a, maxe, lds, st, grid);
-    else if (wsel == 21 && nr == 1) return sa2_launch_one<TB, 1, 2, 1>(a, maxe, lds, st, grid);
-    else if (wsel == 11 && nr == 1) return sa2_launch_one<TB, 1, 1, 1>(a, maxe, lds, st, grid);
-    else if (wsel == 11 && nr2 == 1) return sa2_launch_one<TB, 2, 1, 1, 1>(a, maxe, lds, st, grid);
-    else if (wsel == 11) return sa2_launch_one<TB, 2, 1, 1>(a, maxe, lds, st, grid);
-    else return -1;
-    return 0;
-  } else {
-  if (nr == 4) {
-    if constexpr (TB <= 2) return sa2_launch_one<TB, 4, 1, 1, 4>(a, maxe, lds, st, grid);
-    else return -1;
-  } else if (wsel == 4 && narrow4) return sa2_launch_one<TB, 1, 4, 4, 1, 4>(a, maxe, lds, st, grid);
-  else if (wsel == 4) return sa2_launch_one<TB, 1, 4, 4>(a, maxe, lds, st, grid);
-  else if (wsel == 2) return sa2_launch_one<TB, 1, 2, 2>(a, maxe, lds, st, grid);
-  else if (wsel == 1 && nr == 1) return sa2_launch_one<TB, 1, 1, 1>(a, maxe, lds, st, grid);
-  else if (wsel == 1 && nr2 == 1) return sa2_launch_one<TB, 2, 1, 1, 1>(a, maxe, lds, st, grid);
-  else if (wsel == 1) return sa2_launch_one<TB, 2, 1, 1>(a, maxe, lds, st, grid);
-  else if (nr == 1) return sa2_launch_one<TB, 1, 0, 0>(a, maxe, lds, st, grid);
-  else if (nr2 == 1) return sa2_launch_one<TB, 2, 0, 0, 1>(a, maxe, lds, st, grid);
-  else return sa2_launch_one<TB, 2, 0, 0>(a, maxe, lds, st, grid);
-  return 0;
-  }
+// what the wave-autonomous forms ask of a launch besides its shape (sas_shape / sa_rag_streams)
+static bool sas_launch_ok(const pcr_sa_params &p, const SaTune &t) {
+  if (t.no_stream || p.B < 1 || !p.wa_packed) return false;
+  return (long)p.B * p.S < 0x7FFFFFFFl;    // (the kernels count items in 32 bits)
 }
 
+// The K-row tile kernel's instantiation for a pair of layer classes: {NR, W2, W3, NR2, RKB}; false: the unit holds none.
+// nr2 / nr: cout-block rounds of layer 2 / of the wider of the two layers; W2 / W3: 1 / 2 / 4 ways (specialised bodies), 0:
+// the general body, f32 unit only.
+// bf16 units: explicit shapes, max-from-accumulators epilogue, at most two cout-block rounds.  The mixed class (2 ways in
+// layer 2, 1 way in layer 3) exists with ONE cout-block round only, <TB,1,2,1> -- with W3 = 1, NR = 1 wave w computes cout
+// block w and nothing else, four blocks = 128 channels.  A last layer of 129 .. 256 channels behind two 64-channel layers
+// (nr == 2) is therefore refused, and runs in the f32 unit's <TB,2,0,0,1>.
+static bool sa_krow_class(int nr, int nr2, int w2, int w3, bool maxe, bool narrow4, int *c) {
+  auto set = [&](int NR, int W2, int W3, int NR2, int RKB) { c[0] = NR; c[1] = W2; c[2] = W3; c[3] = NR2; c[4] = RKB; return true; };
+  if (kPrec != 0 && (!maxe || nr > 2)) return false;
+  if (kPrec == 0 && nr == 4) return set(4, 1, 1, 4, 0);   // (instantiated for both layers together, TB <= 2)
+  if (w2 == w3 && w2 != 1) {
+    // resident weight fragments for 32-channel layers (2 x 16 VGPRs), f32 unit.  For 64-channel layers the 2 x 32 VGPRs
+    // cost more residency than the saved L2 round trips are worth (measured: 6.4 -> 7.9 ms on the 64/64/64 layer).
+    return set(1, w2, w3, 1, kPrec == 0 && w2 == 4 && narrow4 ? 4 : 0);
+  }
+  if (kPrec != 0 && w2 == 2 && w3 == 1 && nr == 1) return set(1, 2, 1, 1, 0);
+  if (kPrec != 0 && w2 != w3) return false;
+  const int w = w2 == w3 ? 1 : 0;
+  return nr == 1 ? set(1, w, w, 1, 0) : set(2, w, w, nr2 == 1 ? 1 : 2, 0);
+}
+
+// Tile choice of the K-row tile kernel.  Measured on MI355X (re-fitted after the epilogue / k-loop work,
+// which halved what a low residency costs): time per row ~ padding x wave imbalance x (1 + 1.0 / resident workgroups per
+// CU); residency is bounded by LDS (160 KiB, 2 KiB granules), by registers (accumulator tiles + ~70 VGPRs against 512 per
+// SIMD lane) and by 8 workgroups.
+static size_t sa_krow_lds(const pcr_sa_params &p, bool maxe, int tb, int cpw) {
+  int rowsC = p.c1 > ceil32(p.c2) ? p.c1 : ceil32(p.c2);
+  if (!maxe && ceil32(p.c3) > rowsC) rowsC = ceil32(p.c3);
+  size_t stage = (size_t)6 * 32 * tb + (size_t)cpw * p.c1 + 32;   // (sq read in 16-byte pieces up to ceil32(c1))
+  const size_t gm = maxe ? (size_t)ceil32(p.c3) * 2 * tb : 0;
+  if (gm > stage) stage = gm;
+  return ((size_t)rowsC * (32 * tb + 1) + stage) * sizeof(float);
+}
+static bool sa_krow_tile_choice(const pcr_sa_params &p, const SaTune &t, bool maxe, int nr, int ways, int *cpw_out, int *tb_out) {
+  int best_cpw = 0, best_tb = 0;
+  double best_cost = 1e30;
+  const int cpw_max = 192 / p.K > 0 ? 192 / p.K : 1;
+  for (int cpw = 1; cpw <= cpw_max; cpw++) {
+    const int tb = (cpw * p.K + 31) / 32;
+    if (tb > 6 || (nr == 4 && tb > 2)) continue;
+    const size_t lds = sa_krow_lds(p, maxe, tb, cpw);
+    if (lds > kSaTileLdsBudget) continue;
+    const int tbw = (tb + ways - 1) / ways;
+    const int regs = nr * tbw * 16 + 70;
+    if (regs > 250) continue;
+    int wgs = (int)((160 * 1024) / ((lds + 2047) / 2048 * 2048));
+    const int by_regs = 512 / ((regs + 7) / 8 * 8);
+    if (by_regs < wgs) wgs = by_regs;
+    if (wgs > 8) wgs = 8;
+    if (wgs < 1) continue;
+    const double pad = (double)(32 * tb) / (double)(cpw * p.K);
+    const double imb = (double)(tbw * ways) / (double)tb;
+    const double cost = pad * imb * (1.0 + 1.0 / wgs);
+    if (cost < best_cost - 1e-9) { best_cost = cost; best_cpw = cpw; best_tb = tb; }
+  }
+  if (t.cpw > 0) {
+    const int tb = (t.cpw * p.K + 31) / 32;
+    if (tb <= (nr == 4 ? 2 : 6) && sa_krow_lds(p, maxe, tb, t.cpw) <= kSaTileLdsBudget) { best_cpw = t.cpw; best_tb = tb; }
+  }
+  *cpw_out = best_cpw;
+  *tb_out = best_tb;
+  return best_cpw != 0;
+}
+
+// Ball-query groups with hit counts: only the distinct rows are evaluated.  (The ragged kernels would also run count-less
+// featureless layers -- all K rows -- but the K-row kernel with resident weights is faster there: 2.2 vs 2.9 ms on the
+// 32-channel kNN layer, its row tables are 0.5 GB of extra traffic.)  The cout-split kernel's shape also takes count-less
+// launches -- all K rows of every centre -- through the same tile plan, so that ragged and K-row evaluation of that layer
+// share one kernel and one arithmetic.
+static int sa_plan_ragged(const pcr_sa_params &p, const SaTune &t, SaPlan *pl) {
+  const bool wsplit_shape = kPrec != 0 && sa_wsplit_shape(p.c1, p.c2, p.c3, p.K) && p.wa_shift_packed &&
+                            (size_t)p.B * ((p.S + (64 / rag_ceil(p.K)) - 1) / (64 / rag_ceil(p.K))) * 64 * 16 < 0x7FFFFFFFull;
+  if (!(p.tile_ws && (p.cnt || wsplit_shape) && p.mode == 1 && p.c1 <= 256 && p.c2 <= 256 && p.c3 <= 256)) return kSaFall;
+  if (kPrec != 0 && !sa_tile_shape_ok(p.c2, p.c3)) return kSaNext;
+  const int rows = sa_tile_rows(p.c2, p.c3), tb = rows / 32;
+  // wave-autonomous ragged form (shape-only choice, the same shapes as the K-row form so that both paths share one
+  // arithmetic): equal widths of layers 1 / 2, c3 = c2 or 2 c2, weights + per-wave areas within LDS
+  if (kPrec != 0 && sas_launch_ok(p, t) && sa_rag_streams(p.c1, p.c2, p.c3, p.K)) {
+    if (!p.row_tab && (!p.idx || !p.cnt)) return PCR_ERR_INVALID;
+    const size_t lds8 = sas_rag_lds(p.c1, p.c3, p.K, 8, p.row_tab != nullptr), lds12 = sas_rag_lds(p.c1, p.c3, p.K, 12, true);
+    const bool w12 = p.row_tab && lds12 <= (size_t)kMaxDynLds && !t.no_w12;    // three waves per SIMD (see the kernel)
+    const int ncb = p.c1 >> 5, ncb3 = p.c3 >> 5;
+    pl->waves = w12 ? 12 : 8;
+    pl->lds = w12 ? lds12 : lds8;
+    pl->dbg = t.trace ? 256 : 0;
+    // (four cout blocks of layer 3 go to <2,4>: sa_rag_streams' LDS rule keeps every 128-wide layer out)
+    return sa_plan_form(pl, PCR_SA_STREAM_RAG,
+                        {ncb == 1 ? 1 : 2, ncb == 1 ? (ncb3 == 1 ? 1 : 2) : (ncb3 == 2 ? 2 : 4), kPrec == 1, p.row_tab != nullptr, pl->waves},
+                        w12 ? 2 : (p.row_tab ? 1 : 0));
+  }
+  if (!p.idx) return kSaNext;
+  if (p.K > rows) return kSaFall;
+  const int rowsCr = p.c1 > ceil32(p.c2) ? p.c1 : ceil32(p.c2);
+  const size_t lds = ((size_t)rowsCr * (rows + 1) + (size_t)ceil32(p.c3) * (rows / kRagG) + 3 * (size_t)p.c1 + ceil32(p.c1) +
+                      ceil32(p.c2) + ceil32(p.c3) + 8 * (rows + 1)) *
+                     sizeof(float);
+  if (lds > kSaTileLdsBudget) return kSaFall;
+  pl->rows = rows;
+  pl->tb = tb;
+  pl->maxT = rag_max_tiles(p.S, p.K, rows);
+  pl->plan_kernels = true;
+  pl->dbg = t.dbg | (t.trace ? 256 : 0);
+  // cout-split form with register-resident weights (shape-only choice): 128 / 128 / 256 on 64-row tiles
+  if (kPrec != 0 && !t.no_wsplit && tb == 2 && wsplit_shape) {
+    pl->lds = ((size_t)3 * 128 * 64 + (size_t)32 * 256 + 2 * 128 + 64) * sizeof(float);   // X1 x 2, X2, obuf, seeds, coff
+    return sa_plan_form(pl, PCR_SA_WSPLIT, {4, 8, kPrec == 1});
+  }
+  pl->lds = lds;
+  const int n1 = ceil32(p.c1) >> 5, n2 = ceil32(p.c2) >> 5, n3 = ceil32(p.c3) >> 5;
+  const int w1 = sa_ways(n1), w2 = sa_ways(n2), w3 = sa_ways(n3);
+  const bool l1m = p.wa_packed && n1 <= 4;   // layer 1 on the matrix core
+  // specialised bodies for the classes of sa_tile_shape_ok (on 64-row tiles equal classes are (1, 1): one layer is wider
+  // than 128); every other pair runs the general body <.., 0, 0, ..>, which only the f32 unit holds
+  const bool special = w2 == w3 || (tb == 4 && w2 == 2 && w3 == 1);
+  if (kPrec != 0 && !special) return kSaNext;   // (not reached: sa_tile_shape_ok above)
+  const int A2 = special ? w2 : 0, A3 = special ? w3 : 0;
+  const int NR2 = (tb == 2 && n2 > 4) ? 2 : 1;   // cout-block rounds of layer 2
+  int W1 = 0;
+  if (tb == 2 && special && NR2 == 1 && l1m && w1 == 1) W1 = 1;
+  if (tb == 4 && A2 == 2 && A3 == 1 && l1m && w1 == 2 && !p.D) W1 = 2;
+  return sa_plan_form(pl, PCR_SA_RAG_TILE, {tb, tb == 2 ? 2 : 1, A2, A3, NR2, W1, kPrec});
+}
+
+// One unit's decision for a launch: kSaNext (the next unit, or the generic kernel), PCR_ERR_INVALID, or PCR_OK and *pl.
+static int sa_make_plan(const pcr_sa_params &p, const SaTune &t, SaPlan *pl) {
+  if (!p.wa || !p.wps[0] || !p.wps[1] || !p.shift_pad[0] || !p.shift_pad[1] || (p.D && (!p.wpq || !p.pq_ws))) return kSaNext;
+  if (kPrec == 0) {
+    if (!p.idx) return kSaNext;
+  } else {
+    if (!p.wps_bf[0] || !p.wps_bf[1] || (p.c1 & 31) || (p.c2 & 31)) return kSaNext;
+    if (!p.idx && !(p.row_tab && p.cnt && p.tile_ws && p.mode == 1 && sas_launch_ok(p, t) && sas_shape(p.c1, p.c2, p.c3, p.K, true)))
+      return kSaNext;
+  }
+  pl->unit = kPrec;   // (every launch below runs layers 2 / 3 in this unit's arithmetic)
+  if ((p.c1 & 7) || p.c1 > 512 || p.c2 > 512 || p.c3 > 512) return kSaNext;
+  pl->pqw = p.mode == 0 ? 2 * p.c1 : p.c1;
+  if (p.D && pl->pqw > 1024) return kSaNext;
+  pl->tables = p.D && !p.pq_ready;
+  const int ragged = sa_plan_ragged(p, t, pl);
+  if (ragged != kSaFall) return ragged;
+
+  // K-row forms: all K rows of every centre
+  const bool maxe = (p.K & 15) == 0;
+  const int n1 = ceil32(p.c1) >> 5, n2 = ceil32(p.c2) >> 5, n3 = ceil32(p.c3) >> 5;
+  const int w1 = sa_ways(n1), w2 = sa_ways(n2), w3 = sa_ways(n3);
+  // cout-block rounds per wave: 2 for 129-256 couts, 4 for 257-512 (the 1.5M / 7M Point-Transformer configs'
+  // 256- / 512-channel layers, backbone_net.py:43-46); the four-round form is instantiated for both layers together
+  const int nr = (n2 > 8 || n3 > 8) ? 4 : ((n2 > 4 || n3 > 4) ? 2 : 1);
+  const int nr2 = nr == 4 ? 4 : (n2 > 4 ? 2 : 1);
+  int cls[5];
+  if (!sa_krow_class(nr, nr2, w2, w3, maxe, p.c1 <= 32 && p.c2 <= 32, cls)) return kSaNext;
+  if (!sa_krow_tile_choice(p, t, maxe, nr, sa_ways(n2 < n3 ? n2 : n3), &pl->cpw, &pl->tb)) return kSaNext;
+  pl->maxe = maxe;
+  pl->dbg = t.dbg;
+  // (the kernel deals layer 1's tiles with layer 2's compile-time shape: explicit shapes only, same class)
+  // (f32 forms are instantiated for equal classes of layers 2 and 3 only; the bf16 units also hold (2, 1))
+  pl->l1m = (!t.no_l1m && p.wa_packed && n1 <= 4 && n2 <= 4 && w1 == w2 && (kPrec != 0 || w2 == w3) && (p.c1 & 3) == 0) ? 1 : 0;
+  if (kPrec != 0) {
+    // wave-autonomous form (shape-only choice): equal widths of 32 / 64 / 128, K in whole 16-row groups, at most three
+    // 32-row blocks per item (K = 16, 32, 48, 64, 96).  (The LARGEST item of whole centres within three blocks: K = 32 / 16
+    // take three blocks = 3 / 6 centres per item, so the per-item work -- the maxima's fold and store, the item walk -- is
+    // paid once per 96 rows)
+    int nblk_item = 0, ncen_item = 0;
+    for (int nb = 3; nb >= 1; nb--)
+      if ((32 * nb) % p.K == 0 && (!nblk_item || t.small_items)) { nblk_item = nb; ncen_item = 32 * nb / p.K; }
+    if (maxe && nblk_item && sas_launch_ok(p, t) && sas_shape(p.c1, p.c2, p.c3, p.K, p.mode == 1) &&
+        sas_krow_spans(p.B, p.N, p.S, p.K, p.D ? pl->pqw : 0, p.c3)) {
+      pl->nblk_item = nblk_item;
+      pl->ncen_item = ncen_item;
+      pl->lds = sas_krow_lds(p.c1, p.c3);
+      if (t.trace) pl->dbg |= 256;
+      pl->xt = p.pq_has_xyz && p.D && p.pq_ready && p.mode == 0;
+      if (p.pq_has_xyz && !pl->xt) return PCR_ERR_INVALID;
+      // claimed items (shape-only: pcr_sa_claim_ws_ints says when; PCR_SA_DBG bit 4096 of a tuning build switches them off)
+      pl->claims = p.claim_ws && sas_claims(p.c1, p.c3, p.N) && !(pl->dbg & 4096);
+      const int ncb = p.c1 >> 5, ncb3 = p.c3 >> 5;
+      return sa_plan_form(pl, PCR_SA_STREAM, {ncb, ncb == 4 ? 4 : (ncb3 == ncb ? ncb : 2 * ncb), kPrec == 1});
+    }
+  }
+  if (p.pq_has_xyz) return PCR_ERR_INVALID;   // (tables with the coordinate term: the K-row stream kernel is their only reader)
+  // (bf16 units: the one-round instantiations are the bf-image ones, layer 1 on the matrix core)
+  if (kPrec != 0 && nr2 == 1 && !pl->l1m) return kSaNext;
+  pl->lds = sa_krow_lds(p, maxe, pl->tb, pl->cpw);
+  // bf16 forms whose first layer runs on the matrix core (NR2 == 1) keep their activations as bf images
+  return sa_plan_form(pl, PCR_SA_KROW_TILE, {pl->tb, cls[0], cls[1], cls[2], maxe, cls[3], cls[4], kPrec, kPrec != 0 && cls[3] == 1});
+}
+
+// ---- launchers: one per family.  Each fills its argument struct once, sizes the grid, launches, dumps the trace. ---------
 extern "C" int pcr_dense_pm_f32(const float *, const float *, float *, int, int, int, int, int, pcr_stream_t);
 
 // diagnostics only (PCR_SA_TRACE and its kin): one launch's stamps appended to the file, `recs` records of it
@@ -2409,11 +2616,105 @@ static void rag_dump_trace(const char *path, const char *tag, int recs) {
   wave_trace_dump<SaTrace>(path, HIP_SYMBOL(g_rag_trace), recs, "kernel %s wgs %d\n", tag, recs);
 }
 
-// fast path; returns -1 when the configuration is not covered (caller falls back to sa_mlp_kernel)
-#if PCR_SA_PREC == 0
-int pcr_sa2_try_bf3(const pcr_sa_params *p, pcr_stream_t st);   // sa_kernels_bf3.hip / sa_kernels_bf1.hip
-int pcr_sa2_try_bf1(const pcr_sa_params *p, pcr_stream_t st);
-#endif
+static RagArgs rag_args(const SaPlan &pl, const pcr_sa_params &p) {
+  RagArgs r;
+  r.B = p.B; r.N = p.N; r.S = p.S; r.K = p.K; r.c1 = p.c1; r.c2 = p.c2; r.c3 = p.c3;
+  r.maxT = pl.maxT;
+  r.xyz = p.xyz; r.idx = p.idx; r.cnt = p.cnt; r.centre_idx = p.centre_idx; r.ws = p.tile_ws;
+  r.wa = p.wa; r.pq = p.D ? p.pq_ws : nullptr; r.pqw = pl.pqw;
+  r.wap = p.wa_packed;
+  r.wap4 = p.wa_shift_packed;
+  r.rowtab = p.row_tab;
+  r.wp2 = kPrec == 0 ? p.wps[0] : p.wps_bf[0]; r.wp3 = kPrec == 0 ? p.wps[1] : p.wps_bf[1];
+  r.sh1 = p.shift[0]; r.sh2 = p.shift_pad[0]; r.sh3 = p.shift_pad[1];
+  r.dbg = pl.dbg;
+  r.out = p.out;
+  r.out_pm = p.out_point_major;
+  return r;
+}
+
+static Sa2Args sa2_args(const SaPlan &pl, const pcr_sa_params &p) {
+  Sa2Args a;
+  a.B = p.B; a.N = p.N; a.S = p.S; a.K = p.K; a.c1 = p.c1; a.c2 = p.c2; a.c3 = p.c3; a.CPW = pl.cpw;
+  a.xyz = p.xyz; a.idx = p.idx; a.centre_idx = p.centre_idx; a.wa = p.wa;
+  a.pq = p.D ? p.pq_ws : nullptr;
+  a.pqw = pl.pqw;
+  a.qoff = p.mode == 0 ? p.c1 : -1;
+  a.dbg = pl.dbg;
+  a.claim = pl.claims ? p.claim_ws : nullptr;
+  a.xt = pl.xt ? 1 : 0;
+  a.wp2 = kPrec == 0 ? p.wps[0] : p.wps_bf[0]; a.wp3 = kPrec == 0 ? p.wps[1] : p.wps_bf[1];
+  a.sh1 = p.shift[0]; a.sh2 = p.shift_pad[0]; a.sh3 = p.shift_pad[1];
+  a.out = p.out;
+  a.out_pm = p.out_point_major;
+  a.wap = p.wa_packed;
+  a.l1m = pl.l1m;
+  return a;
+}
+
+// K-row tile kernel: a fan-out over the instantiations sa_krow_class names
+template <int TB, int NR, int W2, int W3, int NR2 = NR, int RKB = 0>
+static int sa2_launch_one(const Sa2Args &a, bool maxe, size_t lds, hipStream_t st, dim3 grid) {
+  constexpr bool kImgK = kPrec != 0 && NR2 == 1;
+  if (maxe) return pcr_launch_lds<sa_fused_kernel<TB, NR, W2, W3, true, NR2, RKB, kPrec, kImgK>>(grid, dim3(kThreads), lds, st, a);
+  if constexpr (kPrec == 0)
+    return pcr_launch_lds<sa_fused_kernel<TB, NR, W2, W3, false, NR2, RKB, kPrec>>(grid, dim3(kThreads), lds, st, a);
+  return PCR_ERR_INVALID;
+}
+template <int TB>
+static int sa2_launch_tb(const SaPlan &pl, const Sa2Args &a, hipStream_t st, dim3 grid) {
+  const int *t = pl.targ;   // TB, NR, W2, W3, MAXE, NR2, RKB, PREC, IMG
+  const bool maxe = t[4] != 0;
+  const int key = 10000 * t[1] + 1000 * t[2] + 100 * t[3] + 10 * t[5] + t[6];   // NR W2 W3 NR2 RKB
+  switch (key) {
+    case 14410: return sa2_launch_one<TB, 1, 4, 4>(a, maxe, pl.lds, st, grid);
+    case 12210: return sa2_launch_one<TB, 1, 2, 2>(a, maxe, pl.lds, st, grid);
+    case 11110: return sa2_launch_one<TB, 1, 1, 1>(a, maxe, pl.lds, st, grid);
+    case 21110: return sa2_launch_one<TB, 2, 1, 1, 1>(a, maxe, pl.lds, st, grid);
+    case 21120: return sa2_launch_one<TB, 2, 1, 1>(a, maxe, pl.lds, st, grid);
+    default: break;
+  }
+  if constexpr (kPrec != 0) {
+    if (key == 12110) return sa2_launch_one<TB, 1, 2, 1>(a, maxe, pl.lds, st, grid);
+  } else {
+    switch (key) {
+      case 41140:
+        if constexpr (TB <= 2) return sa2_launch_one<TB, 4, 1, 1, 4>(a, maxe, pl.lds, st, grid);
+        break;
+      case 14414: return sa2_launch_one<TB, 1, 4, 4, 1, 4>(a, maxe, pl.lds, st, grid);
+      case 10010: return sa2_launch_one<TB, 1, 0, 0>(a, maxe, pl.lds, st, grid);
+      case 20010: return sa2_launch_one<TB, 2, 0, 0, 1>(a, maxe, pl.lds, st, grid);
+      case 20020: return sa2_launch_one<TB, 2, 0, 0>(a, maxe, pl.lds, st, grid);
+      default: break;
+    }
+  }
+  return PCR_ERR_INVALID;   // (not reached: the plan names instantiations of this list only)
+}
+static int sa_launch_krow_tile(const SaPlan &pl, const pcr_sa_params &p, hipStream_t st) {
+  const Sa2Args a = sa2_args(pl, p);
+  const dim3 grid((p.S + pl.cpw - 1) / pl.cpw, p.B);
+  switch (pl.tb) {
+    case 1: return sa2_launch_tb<1>(pl, a, st, grid);
+    case 2: return sa2_launch_tb<2>(pl, a, st, grid);
+    case 3: return sa2_launch_tb<3>(pl, a, st, grid);
+    case 4: return sa2_launch_tb<4>(pl, a, st, grid);
+    case 5: return sa2_launch_tb<5>(pl, a, st, grid);
+    default: return sa2_launch_tb<6>(pl, a, st, grid);
+  }
+}
+
+// the ragged tile plan: per-cloud tile descriptors, their scan, the flat list, the tiles' row tables (above)
+static int sa_launch_plan_kernels(const SaPlan &pl, const RagArgs &r, hipStream_t st) {
+  long long wgs_rows = ((long long)r.B * r.maxT + 3) / 4;
+  if (wgs_rows > 4096) wgs_rows = 4096;
+  int rc = pcr_launch<sa_rag_plan_kernel>(dim3((r.B + 3) / 4), dim3(256), 0, st, r, pl.rows);
+  if (rc == PCR_OK) rc = pcr_launch<sa_rag_scan_kernel>(dim3(1), dim3(1024), 0, st, r.B, r.ws);
+  if (rc == PCR_OK) rc = pcr_launch<sa_rag_flatten_kernel>(dim3((r.B + 3) / 4), dim3(256), 0, st, r.B, r.maxT, r.ws);
+  if (rc == PCR_OK)
+    rc = pl.rows == 64 ? pcr_launch<sa_rag_rows_kernel<64>>(dim3((unsigned)wgs_rows), dim3(256), 0, st, r)
+                       : pcr_launch<sa_rag_rows_kernel<128>>(dim3((unsigned)wgs_rows), dim3(256), 0, st, r);
+  return rc;
+}
 
 // the ragged tile kernel, persistent: as many workgroups as are resident on the chip (registers and LDS), at most one per tile
 template <int TB, int NR, int A2, int A3, int NR2, int W1>
@@ -2434,333 +2735,191 @@ static int rag_launch(const RagArgs &r, size_t lds, long long max_tiles, hipStre
   if (rtrace) rag_dump_trace(rtrace, TB == 2 ? "2,2" : "4,1", (int)want);
   return rc;
 }
-
-#if PCR_SA_PREC != 0
-template <int NCB, int NCB3>
-static int sasr_launch(bool w12, dim3 gg, dim3 bb, size_t lds_r8, size_t lds_r12, hipStream_t st, const RagArgs &r) {
-  constexpr bool kLoS = kPrec == 1;
-  if (w12) return pcr_launch_lds<sa_stream_rag_kernel<NCB, NCB3, kLoS, true, 12>>(gg, bb, lds_r12, st, r);
-  if (r.rowtab) return pcr_launch_lds<sa_stream_rag_kernel<NCB, NCB3, kLoS, true>>(gg, bb, lds_r8, st, r);
-  return pcr_launch_lds<sa_stream_rag_kernel<NCB, NCB3, kLoS>>(gg, bb, lds_r8, st, r);
-}
-
-static bool sas_shape_ok(const pcr_sa_params &p, bool ragged) {
-  static const int no_stream = pcr_tune_int("PCR_SA_NO_STREAM");   // diagnostics
-  if (no_stream || p.B < 1 || !p.wa_packed) return false;
-  if ((long)p.B * p.S >= 0x7FFFFFFFl) return false;    // (the kernels count items in 32 bits)
-  return sas_shape(p.c1, p.c2, p.c3, p.K, ragged || p.mode == 1);
-}
-#endif
-
-static int sa2_try(const pcr_sa_params &p, pcr_stream_t st_) {
-  hipStream_t st = pcr_s(st_);
-  if (!p.wa || !p.wps[0] || !p.wps[1] || !p.shift_pad[0] || !p.shift_pad[1] || (p.D && (!p.wpq || !p.pq_ws)))
-    return -1;
+static int sa_launch_rag_tile(const SaPlan &pl, const pcr_sa_params &p, hipStream_t st, const char *trace) {
+  const RagArgs r = rag_args(pl, p);
+  const int rc = sa_launch_plan_kernels(pl, r, st);
+  if (rc != PCR_OK) return rc;
+  const long long max_tiles = (long long)p.B * r.maxT;
+  const int *t = pl.targ;   // TB, NR, A2, A3, NR2, W1, PREC
+  switch (10000 * t[0] + 1000 * t[2] + 100 * t[3] + 10 * t[4] + t[5]) {
+    case 21111: return rag_launch<2, 2, 1, 1, 1, 1>(r, pl.lds, max_tiles, st, trace);
+    case 21110: return rag_launch<2, 2, 1, 1, 1, 0>(r, pl.lds, max_tiles, st, trace);
+    case 21120: return rag_launch<2, 2, 1, 1, 2, 0>(r, pl.lds, max_tiles, st, trace);
+    case 41110: return rag_launch<4, 1, 1, 1, 1, 0>(r, pl.lds, max_tiles, st, trace);
+    case 42112: return rag_launch<4, 1, 2, 1, 1, 2>(r, pl.lds, max_tiles, st, trace);
+    case 42110: return rag_launch<4, 1, 2, 1, 1, 0>(r, pl.lds, max_tiles, st, trace);
+    case 42210: return rag_launch<4, 1, 2, 2, 1, 0>(r, pl.lds, max_tiles, st, trace);
+    case 44410: return rag_launch<4, 1, 4, 4, 1, 0>(r, pl.lds, max_tiles, st, trace);
 #if PCR_SA_PREC == 0
-  // precision 1 / 2: layers 2 and 3 on the bf16 matrix core (their own translation units); shapes those units do not
-  // instantiate come back with -1 and run here in f32, which is never less accurate than what was asked for
-  if (p.precision != 0 && p.wps_bf[0] && p.wps_bf[1]) {
-    const int rc = p.precision == 1 ? pcr_sa2_try_bf3(&p, st_) : pcr_sa2_try_bf1(&p, st_);
-    if (rc >= 0) return rc;
+    case 20010: return rag_launch<2, 2, 0, 0, 1, 0>(r, pl.lds, max_tiles, st, trace);
+    case 20020: return rag_launch<2, 2, 0, 0, 2, 0>(r, pl.lds, max_tiles, st, trace);
+    case 40010: return rag_launch<4, 1, 0, 0, 1, 0>(r, pl.lds, max_tiles, st, trace);
+#endif
+    default: return PCR_ERR_INVALID;   // (not reached: the plan names instantiations of this list only)
   }
-  if (!p.idx) return -1;
-  const float *const wl2 = p.wps[0], *const wl3 = p.wps[1];
+}
+
+#if PCR_SA_PREC != 0
+// the cout-split kernel, persistent: one 8-wave workgroup per CU, over the tile plan's tiles
+static int sa_launch_wsplit(const SaPlan &pl, const pcr_sa_params &p, hipStream_t st, const char *trace) {
+  const RagArgs r = rag_args(pl, p);
+  int rc = sa_launch_plan_kernels(pl, r, st);
+  if (rc != PCR_OK) return rc;
+  const long long max_tiles = (long long)p.B * r.maxT;
+  long long want = pcr_cu_count();
+  if (want > max_tiles) want = max_tiles;
+  rc = pcr_launch_lds<sa_wsplit_rag_kernel<4, 8, kPrec == 1>>(dim3((unsigned)want), dim3(512), pl.lds, st, r);
+  if (trace) rag_dump_trace(trace, "wsplit", (int)(2 * want));
+  return rc;
+}
+
+template <int NCB, int NCB3>
+static int sasr_launch(int variant, dim3 gg, dim3 bb, size_t lds, hipStream_t st, const RagArgs &r) {
+  constexpr bool kLoS = kPrec == 1;
+  if (variant == 2) return pcr_launch_lds<sa_stream_rag_kernel<NCB, NCB3, kLoS, true, 12>>(gg, bb, lds, st, r);
+  if (variant == 1) return pcr_launch_lds<sa_stream_rag_kernel<NCB, NCB3, kLoS, true>>(gg, bb, lds, st, r);
+  return pcr_launch_lds<sa_stream_rag_kernel<NCB, NCB3, kLoS>>(gg, bb, lds, st, r);
+}
+static int sa_launch_stream_rag(const SaPlan &pl, const pcr_sa_params &p, hipStream_t st, const char *trace) {
+  const RagArgs r = rag_args(pl, p);
+  const long items = (long)p.B * ((p.S + kSasCpi - 1) / kSasCpi);
+  long wgs = (items + pl.waves - 1) / pl.waves;
+  if (wgs > pcr_cu_count()) wgs = pcr_cu_count();
+  wgs = (wgs + 7) / 8 * 8;
+  const dim3 gg((unsigned)wgs), bb(64 * pl.waves);
+  int rc;
+  switch (10 * pl.targ[0] + pl.targ[1]) {
+    case 11: rc = sasr_launch<1, 1>(pl.variant, gg, bb, pl.lds, st, r); break;
+    case 12: rc = sasr_launch<1, 2>(pl.variant, gg, bb, pl.lds, st, r); break;
+    case 22: rc = sasr_launch<2, 2>(pl.variant, gg, bb, pl.lds, st, r); break;
+    default: rc = sasr_launch<2, 4>(pl.variant, gg, bb, pl.lds, st, r); break;
+  }
+  if (trace) rag_dump_trace(trace, "stream", (int)(2 * wgs));
+  return rc;
+}
+
+static int sa_launch_stream(const SaPlan &pl, const pcr_sa_params &p, hipStream_t st, const char *trace) {
+  const Sa2Args a = sa2_args(pl, p);
+  const int ncb = pl.targ[0], ncb3 = pl.targ[1];
+  const long items = (long)p.B * ((p.S + pl.ncen_item - 1) / pl.ncen_item);
+  long wgs = (items + kSasWaves - 1) / kSasWaves;
+  const long resident = (long)pcr_cu_count() * ((ncb + ncb3 >= 6 || pl.lds > (size_t)80 * 1024) ? 1 : 2);
+  if (wgs > resident) wgs = resident;
+  wgs = (wgs + 7) / 8 * 8;                         // every XCD gets workgroups (the item order is per XCD)
+  const dim3 gg((unsigned)wgs), bb(64 * kSasWaves);
+  constexpr bool kLoS = kPrec == 1;
+  if (a.claim && hipMemsetAsync(a.claim, 0, (size_t)kSasClaimInts * sizeof(int), st) != hipSuccess) return PCR_ERR_LAUNCH;
+  int rc;
+  switch (10 * ncb + ncb3) {
+    case 11: rc = pcr_launch_lds<sa_stream_kernel<1, 1, kLoS>>(gg, bb, pl.lds, st, a, pl.nblk_item, pl.ncen_item); break;
+    case 12: rc = pcr_launch_lds<sa_stream_kernel<1, 2, kLoS>>(gg, bb, pl.lds, st, a, pl.nblk_item, pl.ncen_item); break;
+    case 22: rc = pcr_launch_lds<sa_stream_kernel<2, 2, kLoS>>(gg, bb, pl.lds, st, a, pl.nblk_item, pl.ncen_item); break;
+    case 24: rc = pcr_launch_lds<sa_stream_kernel<2, 4, kLoS>>(gg, bb, pl.lds, st, a, pl.nblk_item, pl.ncen_item); break;
+    default: rc = pcr_launch_lds<sa_stream_kernel<4, 4, kLoS>>(gg, bb, pl.lds, st, a, pl.nblk_item, pl.ncen_item); break;
+  }
+  if (trace) rag_dump_trace(trace, "krow", (int)(2 * wgs));
+  return rc;
+}
 #else
-  if (!p.wps_bf[0] || !p.wps_bf[1] || (p.c1 & 31) || (p.c2 & 31)) return -1;
-  const float *const wl2 = p.wps_bf[0], *const wl3 = p.wps_bf[1];
-  if (!p.idx && !(p.row_tab && p.cnt && p.tile_ws && p.mode == 1 && sas_shape_ok(p, true))) return -1;
+// the generic kernel: any shape, layer 1 from the grouped rows themselves
+static SaArgs sa_args(const pcr_sa_params &p, int cpw) {
+  SaArgs a;
+  a.p = p;
+  a.C0 = 3 + (p.mode == 0 ? 2 * p.D : p.D);
+  a.C0P = ceil8(a.C0);
+  a.rowsA = a.C0P > ceil8(p.c2) ? a.C0P : ceil8(p.c2);
+  a.rowsB = ceil8(p.c1) > p.c3 ? ceil8(p.c1) : p.c3;
+  a.CPW = cpw;
+  a.TB = (cpw * p.K + 31) / 32;
+  a.RP = 32 * a.TB + 1;
+  return a;
+}
+static size_t sa_generic_lds(const SaArgs &a) { return ((size_t)(a.rowsA + a.rowsB) * a.RP + 32 * a.TB) * sizeof(float); }
+static int sa_plan_generic(const pcr_sa_params &p, SaPlan *pl) {
+  if (p.pq_has_xyz) return PCR_ERR_INVALID;   // (only the wave-autonomous K-row kernel reads such tables)
+  if (!p.idx) return PCR_ERR_INVALID;   // (a row table without an index tensor: only the kernel that reads the table will do)
+  *pl = SaPlan();
+  pl->unit = PCR_PREC_F32;
+  // centres per workgroup: as many as keep rows <= 128 (at least one) and LDS within the budget
+  int cpw = 128 / p.K;
+  if (cpw < 1) cpw = 1;
+  for (;; cpw--) {
+    pl->lds = sa_generic_lds(sa_args(p, cpw));
+    if (pl->lds <= kSaTileLdsBudget || cpw == 1) break;
+  }
+  if (pl->lds > (size_t)kMaxDynLds) return PCR_ERR_INVALID;
+  pl->cpw = cpw;
+  pl->tb = (cpw * p.K + 31) / 32;
+  return sa_plan_form(pl, PCR_SA_GENERIC, {});
+}
+static int sa_launch_generic(const SaPlan &pl, const pcr_sa_params &p, hipStream_t st) {
+  return pcr_launch_lds<sa_mlp_kernel>(dim3((p.S + pl.cpw - 1) / pl.cpw, p.B), dim3(kThreads), pl.lds, st, sa_args(p, pl.cpw));
+}
 #endif
-  pcr_note_arith(kPrec);   // (every launch below runs layers 2 / 3 in this unit's arithmetic)
-  if ((p.c1 & 7) || p.c1 > 512 || p.c2 > 512 || p.c3 > 512) return -1;
-  const int pqw = p.mode == 0 ? 2 * p.c1 : p.c1;
-  if (p.D && pqw > 1024) return -1;
-  // the persistent, register-pipelined kernel: ball-query groups with hit counts (only the distinct rows are
-  // evaluated).  (It also runs count-less featureless layers -- all K rows -- but the K-row kernel with resident
-  // weights is faster there: 2.2 vs 2.9 ms on the 32-channel kNN layer, its row tables are 0.5 GB of extra traffic.)
-  // (the cout-split kernel's shape also takes count-less launches -- all K rows of every centre -- through the same tile
-  // plan, so that ragged and K-row evaluation of that layer share one kernel and one arithmetic)
-  const bool wsplit_shape = kPrec != 0 && sa_wsplit_shape(p.c1, p.c2, p.c3, p.K) && p.wa_shift_packed &&
-                            (size_t)p.B * ((p.S + (64 / rag_ceil(p.K)) - 1) / (64 / rag_ceil(p.K))) * 64 * 16 < 0x7FFFFFFFull;
-  if (p.tile_ws && (p.cnt || wsplit_shape) && p.mode == 1 && p.c1 <= 256 && p.c2 <= 256 && p.c3 <= 256) {
-    const int n2r = ceil32(p.c2) >> 5, n3r = ceil32(p.c3) >> 5;
-    const int ROWS = sa_tile_rows(p.c2, p.c3), tb = ROWS / 32;
-    if (kPrec != 0 && !sa_tile_shape_ok(p.c2, p.c3)) return -1;
+
+static int sa_launch(const SaPlan &pl, const pcr_sa_params &p, const SaTune &t, pcr_stream_t st_) {
+  hipStream_t st = pcr_s(st_);
+  if (pl.tables) {
+    const int rc = pcr_dense_pm_f32(p.feat, p.wpq, p.pq_ws, p.B, p.D, pl.pqw, p.N, p.feat_point_major, st_);
+    if (rc != PCR_OK) return rc == PCR_ERR_INVALID ? kSaNext : rc;
+  }
+  switch (pl.family) {
+    case PCR_SA_KROW_TILE: return sa_launch_krow_tile(pl, p, st);
+    case PCR_SA_RAG_TILE: return sa_launch_rag_tile(pl, p, st, t.trace);
 #if PCR_SA_PREC != 0
-    {
-      // wave-autonomous ragged form (shape-only choice, the same shapes as the K-row form so that both paths share one
-      // arithmetic): equal widths of layers 1 / 2, c3 = c2 or 2 c2, weights + per-wave areas within LDS
-      const int ncb = p.c1 >> 5, ncb3 = p.c3 >> 5;
-      if (sas_shape_ok(p, true)) {
-        if (p.D && !p.pq_ready) {
-          const int rc = pcr_dense_pm_f32(p.feat, p.wpq, p.pq_ws, p.B, p.D, p.c1, p.N, p.feat_point_major, st_);
-          if (rc != PCR_OK) return rc == PCR_ERR_INVALID ? -1 : rc;
-        }
-        RagArgs r;
-        r.B = p.B; r.N = p.N; r.S = p.S; r.K = p.K; r.c1 = p.c1; r.c2 = p.c2; r.c3 = p.c3; r.maxT = 0;
-        r.xyz = p.xyz; r.idx = p.idx; r.cnt = p.cnt; r.centre_idx = p.centre_idx; r.ws = p.tile_ws;
-        r.wa = p.wa; r.pq = p.D ? p.pq_ws : nullptr; r.pqw = p.c1;
-        r.wap = p.wa_packed;
-        r.rowtab = p.row_tab;
-        if (!p.row_tab && (!p.idx || !p.cnt)) return PCR_ERR_INVALID;
-        r.wp2 = wl2; r.wp3 = wl3; r.sh1 = p.shift[0]; r.sh2 = p.shift_pad[0]; r.sh3 = p.shift_pad[1];
-        static const char *strace = pcr_tune_str("PCR_SA_TRACE");
-        r.dbg = strace ? 256 : 0; r.out = p.out; r.out_pm = p.out_point_major;
-        const long items = (long)p.B * ((p.S + kSasCpi - 1) / kSasCpi);
-        const size_t lds_r8 = sas_rag_lds(p.c1, p.c3, p.K, 8, r.rowtab != nullptr);
-        const size_t lds_r12 = sas_rag_lds(p.c1, p.c3, p.K, 12, true);
-        static const int no12 = pcr_tune_int("PCR_SA_NO_W12");   // diagnostics
-        const bool w12 = r.rowtab && lds_r12 <= (size_t)kMaxDynLds && !no12;    // three waves per SIMD (see the kernel)
-        const int nw = w12 ? 12 : 8;
-        long wgs = (items + nw - 1) / nw;
-        if (wgs > pcr_cu_count()) wgs = pcr_cu_count();
-        wgs = (wgs + 7) / 8 * 8;
-        const dim3 gg((unsigned)wgs), bb(64 * nw);
-        int rc;
-        if (ncb == 1 && ncb3 == 1) rc = sasr_launch<1, 1>(w12, gg, bb, lds_r8, lds_r12, st, r);
-        else if (ncb == 1) rc = sasr_launch<1, 2>(w12, gg, bb, lds_r8, lds_r12, st, r);
-        else if (ncb3 == 2) rc = sasr_launch<2, 2>(w12, gg, bb, lds_r8, lds_r12, st, r);
-        else rc = sasr_launch<2, 4>(w12, gg, bb, lds_r8, lds_r12, st, r);
-        if (strace) rag_dump_trace(strace, "stream", (int)(2 * wgs));
-        return rc;
-      }
-    }
+    case PCR_SA_STREAM: return sa_launch_stream(pl, p, st, t.trace);
+    case PCR_SA_STREAM_RAG: return sa_launch_stream_rag(pl, p, st, t.trace);
+    case PCR_SA_WSPLIT: return sa_launch_wsplit(pl, p, st, t.trace);
+#else
+    case PCR_SA_GENERIC: return sa_launch_generic(pl, p, st);
 #endif
-    if (!p.idx) return -1;
-    if (p.K <= ROWS) {
-      const int per_tile = ROWS / rag_ceil(p.K);               // whole centres a tile holds in the worst case
-      RagArgs r;
-      r.B = p.B; r.N = p.N; r.S = p.S; r.K = p.K; r.c1 = p.c1; r.c2 = p.c2; r.c3 = p.c3;
-      r.maxT = (p.S + per_tile - 1) / per_tile;
-      r.xyz = p.xyz; r.idx = p.idx; r.cnt = p.cnt; r.centre_idx = p.centre_idx; r.ws = p.tile_ws;
-      r.wa = p.wa; r.pq = p.D ? p.pq_ws : nullptr; r.pqw = p.c1;
-      r.wap = p.wa_packed;
-      r.wap4 = p.wa_shift_packed;
-      r.wp2 = wl2; r.wp3 = wl3; r.sh1 = p.shift[0]; r.sh2 = p.shift_pad[0]; r.sh3 = p.shift_pad[1];
-      static const int rdbg = pcr_tune_int("PCR_SA_DBG");
-      static const char *rtrace = pcr_tune_str("PCR_SA_TRACE");
-      r.dbg = rdbg | (rtrace ? 256 : 0);
-      r.out = p.out;
-      r.out_pm = p.out_point_major;
-      const int rowsCr = p.c1 > ceil32(p.c2) ? p.c1 : ceil32(p.c2);
-      const size_t lds = ((size_t)rowsCr * (ROWS + 1) +
-                          (size_t)ceil32(p.c3) * (ROWS / kRagG) + 3 * (size_t)p.c1 + ceil32(p.c1) + ceil32(p.c2) +
-                          ceil32(p.c3) + 8 * (ROWS + 1)) *
-                         sizeof(float);
-      if (lds <= 150 * 1024) {
-        if (p.D && !p.pq_ready) {
-          const int rc = pcr_dense_pm_f32(p.feat, p.wpq, p.pq_ws, p.B, p.D, p.c1, p.N, p.feat_point_major, st_);
-          if (rc != PCR_OK) return rc == PCR_ERR_INVALID ? -1 : rc;
-        }
-        long long wgs_rows = ((long long)p.B * r.maxT + 3) / 4;
-        if (wgs_rows > 4096) wgs_rows = 4096;
-        int rc = pcr_launch<sa_rag_plan_kernel>(dim3((p.B + 3) / 4), dim3(256), 0, st, r, ROWS);
-        if (rc == PCR_OK) rc = pcr_launch<sa_rag_scan_kernel>(dim3(1), dim3(1024), 0, st, p.B, r.ws);
-        if (rc == PCR_OK) rc = pcr_launch<sa_rag_flatten_kernel>(dim3((p.B + 3) / 4), dim3(256), 0, st, p.B, r.maxT, r.ws);
-        if (rc == PCR_OK)
-          rc = tb == 2 ? pcr_launch<sa_rag_rows_kernel<64>>(dim3((unsigned)wgs_rows), dim3(256), 0, st, r)
-                       : pcr_launch<sa_rag_rows_kernel<128>>(dim3((unsigned)wgs_rows), dim3(256), 0, st, r);
-        if (rc != PCR_OK) return rc;
-        const long long max_tiles = (long long)p.B * r.maxT;
-        const int w2 = sa_ways(n2r), w3 = sa_ways(n3r);
-#if PCR_SA_PREC != 0
-        {
-          // cout-split form with register-resident weights (shape-only choice): 128 / 128 / 256 on 64-row tiles
-          static const int no_wsplit = pcr_tune_int("PCR_SA_NO_WSPLIT");   // diagnostics
-          if (!no_wsplit && tb == 2 && wsplit_shape) {
-            constexpr bool kLoW = kPrec == 1;
-            const size_t lds_w = ((size_t)3 * 128 * 64 + (size_t)32 * 256 + 2 * 128 + 64) * sizeof(float);   // X1 x 2, X2, obuf, seeds, coff
-            long long want = pcr_cu_count();                                 // persistent: one 8-wave workgroup per CU
-            if (want > max_tiles) want = max_tiles;
-            rc = pcr_launch_lds<sa_wsplit_rag_kernel<4, 8, kLoW>>(dim3((unsigned)want), dim3(512), lds_w, st, r);
-            if (rtrace) rag_dump_trace(rtrace, "wsplit", (int)(2 * want));
-            return rc;
-          }
-        }
-#endif
-        const int n1r = ceil32(p.c1) >> 5;
-        const int w1 = sa_ways(n1r);
-        const bool l1m = p.wa_packed && n1r <= 4;   // layer 1 on the matrix core
-        if (tb == 2) {
-          const bool narrow2 = n2r <= 4;   // layer 2 needs one cout-block round only
-          if (w2 == 1 && w3 == 1 && narrow2 && l1m && w1 == 1) return rag_launch<2, 2, 1, 1, 1, 1>(r, lds, max_tiles, st, rtrace);
-          else if (w2 == 1 && w3 == 1 && narrow2) return rag_launch<2, 2, 1, 1, 1, 0>(r, lds, max_tiles, st, rtrace);
-          else if (w2 == 1 && w3 == 1) return rag_launch<2, 2, 1, 1, 2, 0>(r, lds, max_tiles, st, rtrace);
-          else if constexpr (kPrec == 0) {
-            if (narrow2) return rag_launch<2, 2, 0, 0, 1, 0>(r, lds, max_tiles, st, rtrace);
-            else return rag_launch<2, 2, 0, 0, 2, 0>(r, lds, max_tiles, st, rtrace);
-          }
-        } else {
-          if (w2 == 1 && w3 == 1) return rag_launch<4, 1, 1, 1, 1, 0>(r, lds, max_tiles, st, rtrace);
-          else if (w2 == 2 && w3 == 1 && l1m && w1 == 2 && !p.D) return rag_launch<4, 1, 2, 1, 1, 2>(r, lds, max_tiles, st, rtrace);
-          else if (w2 == 2 && w3 == 1) return rag_launch<4, 1, 2, 1, 1, 0>(r, lds, max_tiles, st, rtrace);
-          else if (w2 == 2 && w3 == 2) return rag_launch<4, 1, 2, 2, 1, 0>(r, lds, max_tiles, st, rtrace);
-          else if (w2 == 4 && w3 == 4) return rag_launch<4, 1, 4, 4, 1, 0>(r, lds, max_tiles, st, rtrace);
-          else if constexpr (kPrec == 0) return rag_launch<4, 1, 0, 0, 1, 0>(r, lds, max_tiles, st, rtrace);
-        }
-        return PCR_OK;
-      }
-    }
+    default: return PCR_ERR_INVALID;
   }
-  const bool maxe = (p.K & 15) == 0;
-  int rowsC = p.c1 > ceil32(p.c2) ? p.c1 : ceil32(p.c2);
-  if (!maxe && ceil32(p.c3) > rowsC) rowsC = ceil32(p.c3);
-  auto lds_bytes = [&](int tb, int cpw) {
-    size_t stage = (size_t)6 * 32 * tb + (size_t)cpw * p.c1 + 32;   // (sq read in 16-byte pieces up to ceil32(c1))
-    const size_t gm = maxe ? (size_t)ceil32(p.c3) * 2 * tb : 0;
-    if (gm > stage) stage = gm;
-    return ((size_t)rowsC * (32 * tb + 1) + stage) * sizeof(float);
-  };
-  const int n2 = ceil32(p.c2) >> 5, n3 = ceil32(p.c3) >> 5;
-  const int nmin = n2 < n3 ? n2 : n3;
-  const int ways = sa_ways(nmin);
-  // cout-block rounds per wave: 2 for 129-256 couts, 4 for 257-512 (the 1.5M / 7M Point-Transformer configs'
-  // 256- / 512-channel layers, backbone_net.py:43-46); the four-round form is instantiated for both layers together
-  const int nr = (n2 > 8 || n3 > 8) ? 4 : ((n2 > 4 || n3 > 4) ? 2 : 1);
-  const int nr2 = nr == 4 ? 4 : (n2 > 4 ? 2 : 1);
-  if (kPrec != 0) {   // the bf16 units: max-from-accumulators epilogue, explicit shapes, at most two cout-block rounds
-    const int v2 = sa_ways(n2), v3 = sa_ways(n3);
-    // (the mixed class has a single-round instantiation only: see sa2_launch_tb)
-    if (!maxe || nr > 2 || !((v2 == v3) || (v2 == 2 && v3 == 1 && nr == 1))) return -1;
-  }
-  // Tile choice.  Measured on MI355X (re-fitted after the epilogue / k-loop work, which halved what
-  // a low residency costs): time per row ~ padding x wave imbalance x (1 + 1.0 / resident workgroups per CU); residency is bounded by LDS (160 KiB, 2 KiB granules),
-  // by registers (accumulator tiles + ~70 VGPRs against 512 per SIMD lane) and by 8 workgroups.
-  int best_cpw = 0, best_tb = 0;
-  double best_cost = 1e30;
-  const int cpw_max = 192 / p.K > 0 ? 192 / p.K : 1;
-  for (int cpw = 1; cpw <= cpw_max; cpw++) {
-    const int tb = (cpw * p.K + 31) / 32;
-    if (tb > 6 || (nr == 4 && tb > 2)) continue;
-    const size_t lds = lds_bytes(tb, cpw);
-    if (lds > 150 * 1024) continue;
-    const int tbw = (tb + ways - 1) / ways;
-    const int regs = nr * tbw * 16 + 70;
-    if (regs > 250) continue;
-    int wgs = (int)((160 * 1024) / ((lds + 2047) / 2048 * 2048));
-    const int by_regs = 512 / ((regs + 7) / 8 * 8);
-    if (by_regs < wgs) wgs = by_regs;
-    if (wgs > 8) wgs = 8;
-    if (wgs < 1) continue;
-    const double pad = (double)(32 * tb) / (double)(cpw * p.K);
-    const double imb = (double)(tbw * ways) / (double)tb;
-    const double cost = pad * imb * (1.0 + 1.0 / wgs);
-    if (cost < best_cost - 1e-9) { best_cost = cost; best_cpw = cpw; best_tb = tb; }
-  }
-  static const int force_cpw = pcr_tune_int("PCR_SA_CPW");   // tuning aid
-  if (force_cpw > 0) {
-    const int tb = (force_cpw * p.K + 31) / 32;
-    if (tb <= (nr == 4 ? 2 : 6) && lds_bytes(tb, force_cpw) <= 150 * 1024) { best_cpw = force_cpw; best_tb = tb; }
-  }
-  if (!best_cpw) return -1;
-  if (p.D && !p.pq_ready) {
-    const int rc = pcr_dense_pm_f32(p.feat, p.wpq, p.pq_ws, p.B, p.D, pqw, p.N, p.feat_point_major, st_);
-    if (rc != PCR_OK) return rc == PCR_ERR_INVALID ? -1 : rc;
-  }
-  Sa2Args a;
-  a.B = p.B; a.N = p.N; a.S = p.S; a.K = p.K; a.c1 = p.c1; a.c2 = p.c2; a.c3 = p.c3; a.CPW = best_cpw;
-  a.xyz = p.xyz; a.idx = p.idx; a.centre_idx = p.centre_idx; a.wa = p.wa;
-  a.pq = p.D ? p.pq_ws : nullptr;
-  a.pqw = pqw;
-  a.qoff = p.mode == 0 ? p.c1 : -1;
-  const int dbg = pcr_tune_int("PCR_SA_DBG");    // (0 in production; a tuning build re-reads it per launch: in-process A/Bs)
-  a.dbg = dbg;
-  a.claim = nullptr;
-  a.xt = 0;
-  a.wp2 = wl2; a.wp3 = wl3;
-  a.sh1 = p.shift[0]; a.sh2 = p.shift_pad[0]; a.sh3 = p.shift_pad[1];
-  a.out = p.out;
-  a.out_pm = p.out_point_major;
-  a.wap = p.wa_packed;
-  {
-    static const int no_l1m = pcr_tune_int("PCR_SA_NO_L1M");   // diagnostics
-    const int n1 = ceil32(p.c1) >> 5;
-    const int w1 = sa_ways(n1);
-    const int w2c = sa_ways(n2), w3c = sa_ways(n3);
-    // (the kernel deals layer 1's tiles with layer 2's compile-time shape: explicit shapes only, same class)
-    // (f32 forms are instantiated for equal classes of layers 2 and 3 only; the bf16 units also hold (2, 1))
-    a.l1m = (!no_l1m && p.wa_packed && n1 <= 4 && n2 <= 4 && w1 == w2c && (kPrec != 0 || w2c == w3c) && (p.c1 & 3) == 0) ? 1 : 0;
-  }
-#if PCR_SA_PREC != 0
-  {
-    // wave-autonomous form (shape-only choice): equal widths of 32 / 64 / 128, K in whole 16-row groups, at most three
-    // 32-row blocks per item (K = 16, 32, 48, 64, 96)
-    const int ncb = p.c1 >> 5, ncb3 = p.c3 >> 5;
-    int nblk_item = 0, ncen_item = 0;
-    // (the LARGEST item of whole centres within three blocks: K = 32 / 16 take three blocks = 3 / 6 centres per item, so the
-    // per-item work -- the maxima's fold and store, the item walk -- is paid once per 96 rows)
-    static const int small_items = pcr_tune_int("PCR_SAS_SMALL_ITEMS");   // diagnostics: the smallest item instead
-    for (int nb = 3; nb >= 1; nb--)
-      if ((32 * nb) % p.K == 0 && (!nblk_item || small_items)) { nblk_item = nb; ncen_item = 32 * nb / p.K; }
-    const size_t lds_s = sas_krow_lds(p.c1, p.c3);
-    if (maxe && nblk_item && sas_shape_ok(p, false) && sas_krow_spans(p.B, p.N, p.S, p.K, p.D ? pqw : 0, p.c3)) {
-      const long items = (long)p.B * ((p.S + ncen_item - 1) / ncen_item);
-      long wgs = (items + kSasWaves - 1) / kSasWaves;
-      const long resident = (long)pcr_cu_count() * ((ncb + ncb3 >= 6 || lds_s > (size_t)80 * 1024) ? 1 : 2);
-      if (wgs > resident) wgs = resident;
-      wgs = (wgs + 7) / 8 * 8;                         // every XCD gets workgroups (the item order is per XCD)
-      const dim3 gg((unsigned)wgs), bb(64 * kSasWaves);
-      constexpr bool kLoS = kPrec == 1;
-      static const char *ktrace = pcr_tune_str("PCR_SA_TRACE");
-      if (ktrace) a.dbg |= 256;
-      // claimed items (shape-only: pcr_sa_claim_ws_ints says when; PCR_SA_DBG bit 4096 of a tuning build switches them off)
-      a.xt = (p.pq_has_xyz && p.D && p.pq_ready && p.mode == 0) ? 1 : 0;
-      if (p.pq_has_xyz && !a.xt) return PCR_ERR_INVALID;
-      a.claim = (p.claim_ws && sas_claims(p.c1, p.c3, p.N) && !(a.dbg & 4096)) ? p.claim_ws : nullptr;
-      if (a.claim && hipMemsetAsync(a.claim, 0, (size_t)kSasClaimInts * sizeof(int), st) != hipSuccess) return PCR_ERR_LAUNCH;
-      int rc;
-      if (ncb == 1 && ncb3 == 1) rc = pcr_launch_lds<sa_stream_kernel<1, 1, kLoS>>(gg, bb, lds_s, st, a, nblk_item, ncen_item);
-      else if (ncb == 1) rc = pcr_launch_lds<sa_stream_kernel<1, 2, kLoS>>(gg, bb, lds_s, st, a, nblk_item, ncen_item);
-      else if (ncb == 2 && ncb3 == 2) rc = pcr_launch_lds<sa_stream_kernel<2, 2, kLoS>>(gg, bb, lds_s, st, a, nblk_item, ncen_item);
-      else if (ncb == 2) rc = pcr_launch_lds<sa_stream_kernel<2, 4, kLoS>>(gg, bb, lds_s, st, a, nblk_item, ncen_item);
-      else rc = pcr_launch_lds<sa_stream_kernel<4, 4, kLoS>>(gg, bb, lds_s, st, a, nblk_item, ncen_item);
-      if (ktrace) rag_dump_trace(ktrace, "krow", (int)(2 * wgs));
-      return rc;
-    }
-  }
-#endif
-  if (p.pq_has_xyz) return PCR_ERR_INVALID;   // (tables with the coordinate term: the K-row kernel above is their only reader)
-  const size_t lds = lds_bytes(best_tb, best_cpw);
-  dim3 grid((p.S + best_cpw - 1) / best_cpw, p.B);
-  const int w2 = sa_ways(n2), w3 = sa_ways(n3);
-  int lrc = 0;
-  switch (best_tb) {
-    case 1: lrc = sa2_launch_tb<1>(a, nr, nr2, w2, w3, maxe, lds, st, grid); break;
-    case 2: lrc = sa2_launch_tb<2>(a, nr, nr2, w2, w3, maxe, lds, st, grid); break;
-    case 3: lrc = sa2_launch_tb<3>(a, nr, nr2, w2, w3, maxe, lds, st, grid); break;
-    case 4: lrc = sa2_launch_tb<4>(a, nr, nr2, w2, w3, maxe, lds, st, grid); break;
-    case 5: lrc = sa2_launch_tb<5>(a, nr, nr2, w2, w3, maxe, lds, st, grid); break;
-    default: lrc = sa2_launch_tb<6>(a, nr, nr2, w2, w3, maxe, lds, st, grid); break;
-  }
-  return lrc < 0 ? -1 : lrc;
+}
+
+// One unit: its plan, and the launch when one is asked for (pcr_sa_launch_form asks for none and leaves the device and
+// pcr_last_launch_arith alone).  kSaNext: the launch is not this unit's.
+static int sa_unit(const pcr_sa_params &p, SaPlan *pl, bool launch, pcr_stream_t st) {
+  const SaTune t = sa_tune();
+  *pl = SaPlan();
+  const int rc = sa_make_plan(p, t, pl);
+  if (!launch) return rc;
+  if (pl->unit >= 0) pcr_note_arith(pl->unit);
+  return rc == PCR_OK ? sa_launch(*pl, p, t, st) : rc;
 }
 
 #if PCR_SA_PREC == 1
-int pcr_sa2_try_bf3(const pcr_sa_params *p, pcr_stream_t st) { return sa2_try(*p, st); }
+int pcr_sa2_unit_bf3(const pcr_sa_params *p, SaPlan *pl, bool launch, pcr_stream_t st) { return sa_unit(*p, pl, launch, st); }
 #elif PCR_SA_PREC == 2
-int pcr_sa2_try_bf1(const pcr_sa_params *p, pcr_stream_t st) { return sa2_try(*p, st); }
+int pcr_sa2_unit_bf1(const pcr_sa_params *p, SaPlan *pl, bool launch, pcr_stream_t st) { return sa_unit(*p, pl, launch, st); }
 #else
+int pcr_sa2_unit_bf3(const pcr_sa_params *p, SaPlan *pl, bool launch, pcr_stream_t st);   // sa_kernels_bf3.hip / sa_kernels_bf1.hip
+int pcr_sa2_unit_bf1(const pcr_sa_params *p, SaPlan *pl, bool launch, pcr_stream_t st);
 
+// ---- the exported shape queries: the plan's own predicates (the launch shapes above) --------------------------------------------------
 // does a ball-query layer with hit counts of this shape read the ball query's row table (pcr_ball_query_rows_f32)?
-// = the wave-autonomous ragged form runs it (sas_shape_ok, shape only)
+// = the wave-autonomous ragged form runs it
 PCR_EXPORT int pcr_sa_uses_row_table(int c1, int c2, int c3, int K, int precision) {
-  // (sa2_try asks for a tile-kernel instantiation of the shape before it looks at the wave-autonomous form)
-  return precision != 0 && sa_tile_shape_ok(c2, c3) && sas_shape(c1, c2, c3, K, true);
+  return precision != 0 && sa_rag_streams(c1, c2, c3, K);
 }
 
 // 1: launches of this shape WITHOUT hit counts (all K rows of every group) also run on the tile plan and want the
-// workspace of pcr_sa_tile_ws_ints -- the cout-split kernel's shape, sa2_try's `wsplit_shape` (bf16 modes)
+// workspace of pcr_sa_tile_ws_ints -- the cout-split kernel's shape (bf16 modes)
 PCR_EXPORT int pcr_sa_krow_uses_tiles(int c1, int c2, int c3, int K, int precision) {
   return precision != 0 && sa_wsplit_shape(c1, c2, c3, K);
 }
 
-// sa2_try's K-row dispatch for the shapes whose tables may carry the coordinate term (pcr_sa_params.pq_has_xyz)
+// the shapes whose tables may carry the coordinate term (pcr_sa_params.pq_has_xyz): the K-row stream form's.  (Narrower
+// than the plan, which would also read such tables at c3 = 2 c2: the answer is kept, engine.py builds them for c2 == c3.)
 PCR_EXPORT int pcr_sa_tables_take_xyz(int mode, int D, int c1, int c2, int c3, int K, int precision) {
-  static const int no_stream = pcr_tune_int("PCR_SA_NO_STREAM"), no_xt = pcr_tune_int("PCR_SA_NO_XYZ_TABLES");   // diagnostics
-  return !no_stream && !no_xt && precision != 0 && mode == 0 && D >= 1 && c2 == c3 && sas_shape(c1, c2, c3, K, false);
+  const SaTune t = sa_tune();
+  return !t.no_stream && !t.no_xyz_tables && precision != 0 && mode == 0 && D >= 1 && c2 == c3 && sas_shape(c1, c2, c3, K, false);
 }
 
+// the K-row stream form's equal-width shapes (whole 16-row groups) in a bf16 mode, on large clouds.  (Wider than the plan:
+// sas_k_ok and sas_shape's LDS rule are not asked, so some shapes get a workspace their launch -- on another kernel --
+// leaves untouched; the answer is kept.)
 PCR_EXPORT long pcr_sa_claim_ws_ints(int c1, int c2, int c3, int K, int N, int precision) {
-  // the wave-autonomous K-row form's shapes (equal widths, whole 16-row groups) in a bf16 mode, on large clouds
   if (precision == 0 || c1 != c2 || c2 != c3 || (K & 15) || K < 16) return 0;
   return sas_claims(c1, c3, N) ? (long)kSasClaimInts : 0;
 }
@@ -2769,9 +2928,7 @@ PCR_EXPORT long pcr_sa_tile_ws_ints(int B, int S, int K, int c2, int c3) {
   if (B < 1 || S < 1 || K < 1 || c2 < 1 || c3 < 1) return 0;
   const int rows = sa_tile_rows(c2, c3);
   if (K > rows) return 0;
-  const int per_tile = rows / rag_ceil(K);
-  const int maxT = (S + per_tile - 1) / per_tile;
-  return (long)rag_ws_ints(B, maxT, rows);
+  return (long)rag_ws_ints(B, rag_max_tiles(S, K, rows), rows);
 }
 
 // the persistent dense_pm forms' fan-out over their template shapes
@@ -2874,43 +3031,57 @@ PCR_EXPORT int pcr_dense_pm_xyz_f32(const float *x, const float *wp_bf, const fl
   return dense_pm_launch(x, wp_bf, y, B, cin, cout, L, x_point_major, precision, stream, xyz, wxyz, q_rows, q_off);
 }
 
-PCR_EXPORT int pcr_sa_mlp_f32(const pcr_sa_params *pp, pcr_stream_t stream) {
-  if (!pp) return PCR_ERR_INVALID;
-  const pcr_sa_params &p = *pp;
+// ---- the entry points -----------------------------------------------------------------------------------------------
+static int sa_validate(const pcr_sa_params &p) {
   if (p.B < 0 || p.N < 1 || p.S < 0 || p.K < 1 || p.D < 0 || p.c1 < 1 || p.c2 < 1 || p.c3 < 1 ||
       !p.xyz || (!p.idx && !(p.row_tab && p.cnt)) || !p.out || (p.D && !p.feat) || (p.mode != 0 && p.mode != 1))
     return PCR_ERR_INVALID;
   for (int l = 0; l < 3; l++)
     if (!p.wp[l] || !p.scale[l] || !p.shift[l]) return PCR_ERR_INVALID;
-  if (p.B == 0 || p.S == 0) return PCR_OK;
   if (p.B > 65535) return PCR_ERR_INVALID;
   // tables with the coordinate term (ABI 17): edge mode with features, built by the caller, a shape the query accepts
   if (p.pq_has_xyz && (p.mode != 0 || !p.D || !p.pq_ready || !p.pq_ws ||
                        !pcr_sa_tables_take_xyz(p.mode, p.D, p.c1, p.c2, p.c3, p.K, p.precision)))
     return PCR_ERR_INVALID;
-  const int fast = sa2_try(p, stream);
-  if (fast >= 0) return fast;
-  if (p.pq_has_xyz) return PCR_ERR_INVALID;   // (only the wave-autonomous K-row kernel reads such tables)
-  if (!p.idx) return PCR_ERR_INVALID;   // (a row table without an index tensor: only the kernel that reads the table will do)
-  pcr_note_arith(PCR_PREC_F32);
-  SaArgs a;
-  a.p = p;
-  a.C0 = 3 + (p.mode == 0 ? 2 * p.D : p.D);
-  a.C0P = ceil8(a.C0);
-  a.rowsA = a.C0P > ceil8(p.c2) ? a.C0P : ceil8(p.c2);
-  a.rowsB = ceil8(p.c1) > p.c3 ? ceil8(p.c1) : p.c3;
-  // centres per workgroup: as many as keep rows <= 128 (at least one) and LDS <= 150 KiB
-  int cpw = 128 / p.K;
-  if (cpw < 1) cpw = 1;
-  size_t lds = 0;
-  for (;; cpw--) {
-    a.CPW = cpw;
-    a.TB = (cpw * p.K + 31) / 32;
-    a.RP = 32 * a.TB + 1;
-    lds = ((size_t)(a.rowsA + a.rowsB) * a.RP + 32 * a.TB) * sizeof(float);
-    if (lds <= 150 * 1024 || cpw == 1) break;
-  }
-  if (lds > (size_t)kMaxDynLds) return PCR_ERR_INVALID;
-  return pcr_launch_lds<sa_mlp_kernel>(dim3((p.S + a.CPW - 1) / a.CPW, p.B), dim3(kThreads), lds, pcr_s(stream), a);
+  return PCR_OK;
 }
-#endif   // PCR_SA_PREC == 0 (C-ABI entry points)
+
+// The units in the order a launch asks them: the bf16 unit of the requested precision (layers 2 and 3 on the bf16 matrix
+// core; shapes it does not instantiate come back with kSaNext), the f32 unit, which is never less accurate than what was
+// asked for, and the generic kernel.
+static int sa_dispatch(const pcr_sa_params &p, SaPlan *pl, bool launch, pcr_stream_t st) {
+  int rc = kSaNext;
+  if (p.precision != 0 && p.wps_bf[0] && p.wps_bf[1])
+    rc =p.precision == 1 ? pcr_sa2_unit_bf3(&p, pl, launch, st) : pcr_sa2_unit_bf1(&p, pl, launch, st);
+  if (rc < 0) rc = sa_unit(p, pl, launch, st);
+  if (rc < 0) {
+    rc = sa_plan_generic(p, pl);
+    if (launch && rc == PCR_OK) {
+      pcr_note_arith(PCR_PREC_F32);
+      rc = sa_launch_generic(*pl, p, pcr_s(st));
+    }
+  }
+  return rc;
+}
+
+PCR_EXPORT int pcr_sa_mlp_f32(const pcr_sa_params *pp, pcr_stream_t stream) {
+  if (!pp || sa_validate(*pp) != PCR_OK) return PCR_ERR_INVALID;
+  if (pp->B == 0 || pp->S == 0) return PCR_OK;
+  SaPlan pl;
+  return sa_dispatch(*pp, &pl, true, stream);
+}
+
+PCR_EXPORT int pcr_sa_launch_form(const pcr_sa_params *pp, int *form) {
+  if (!pp || !form || sa_validate(*pp) != PCR_OK) return PCR_ERR_INVALID;
+  SaPlan pl;
+  const int rc = sa_dispatch(*pp, &pl, false, nullptr);
+  if (rc != PCR_OK) return rc;
+  for (int i = 0; i < PCR_SA_FORM_INTS; i++) form[i] = 0;
+  form[0] = pl.unit;
+  form[1] = pl.family;
+  form[2] = pl.variant;
+  form[3] = pl.ntarg;
+  for (int i = 0; i < pl.ntarg; i++) form[4 + i] = pl.targ[i];
+  return PCR_OK;
+}
+#endif   // PCR_SA_PREC == 0 (queries and C-ABI entry points)

@@ -301,6 +301,7 @@ SIGNATURES = {
     "pcr_sa_tile_ws_ints": "l iiiii",
     "pcr_sa_krow_uses_tiles": "i iiiii",
     "pcr_sa_uses_row_table": "i iiiii",
+    "pcr_sa_launch_form": "i <SaParams>I",
     "pcr_dense_pm_f32": "s FFFiiiiiS",
     "pcr_dense_pm_prec_f32": "s FFFiiiiiiS",
     "pcr_dense_pm_xyz_f32": "s FFFFFiiiiiiiiS",

@@ -293,7 +293,7 @@ class SaPlan:
 
     def wants_row_table(self, N, K, min_radius, B=1, S=1):
         """does the ragged launch of this layer read the ball query's row table (ops.ball_query_rows)?  Everything the
-        library's own dispatch (sa2_try / sas_shape_ok) looks at besides the shape is honoured here too -- the
+        library's own dispatch (sa_make_plan / sas_launch_ok) looks at besides the shape is honoured here too -- the
         PCR_SA_NO_STREAM diagnostic and the 32-bit centre count -- so that a caller which drops its index tensor on this
         answer is never refused by the launch."""
         lib = L.load()

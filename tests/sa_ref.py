@@ -1,8 +1,9 @@
 """The grouped set-abstraction layer (gather, three 1x1 convolutions with eval-mode BatchNorm, ReLU, max over K) in float64,
-stated from models/pointnet2_utils.py:242-288, 333-360 -- and the shape rules of the library's dispatcher (sa2_try,
-csrc/sa_kernels_impl.h) restated as pure functions, so that a test can say which kernel instantiation a shape reaches
-without running it.  tests/test_sa_ref_cpu.py holds both to a second formulation and to the library's exported shape
-queries; tests/test_gpu_sa_forms.py holds every launch form to `sa_ref`."""
+stated from models/pointnet2_utils.py:242-288, 333-360 -- and the shape rules of the library's dispatcher (sa_make_plan and
+the launch-shape rules of csrc/sa_kernels_impl.h) restated as pure functions, so that a test can say which kernel
+instantiation a shape reaches without running it.  tests/test_sa_ref_cpu.py holds both to a second formulation, to the
+library's exported shape queries and to the form the library itself reports (pcr_sa_launch_form);
+tests/test_gpu_sa_forms.py holds every launch form to `sa_ref`."""
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -144,7 +145,7 @@ def row_table(xyz, idx, cnt, centre_idx=None):
     return torch.from_numpy(tab).reshape(-1)
 
 
-# ---- the dispatcher's shape rules (sa2_try and the helpers above it, csrc/sa_kernels_impl.h) ---------------------------
+# ---- the dispatcher's shape rules (sa_make_plan and the helpers above it, csrc/sa_kernels_impl.h) ---------------------
 MAX_LDS = 160 * 1024
 
 
@@ -244,7 +245,7 @@ def krow_tile_choice(c1, c2, c3, K):
 
 
 def _unit(prec, mode, D, c1, c2, c3, K, has_cnt, asked):
-    """one arithmetic unit's sa2_try: (family, template arguments) or None (= -1, the caller goes on)"""
+    """one arithmetic unit's sa_make_plan: (family, template arguments) or None (= -1, the caller goes on)"""
     if prec != 0 and ((c1 & 31) or (c2 & 31)):
         return None
     if (c1 & 7) or max(c1, c2, c3) > 512 or (D and (2 * c1 if mode == 0 else c1) > 1024):
@@ -325,11 +326,53 @@ def dispatch(mode, D, c1, c2, c3, K, precision, has_cnt, fast=True):
     return (0, "generic", ())
 
 
+def generic_fits(mode, D, c1, c2, c3, K):
+    """does the generic kernel hold one centre's K rows in LDS?  Where dispatch() says `generic` and this says no, the
+    launch is refused (PCR_ERR_INVALID: sa_plan_generic) -- e.g. 128/128/128 without the fast operands at K >= 129
+    (two 128-row buffers of 161 columns are 165 504 bytes)."""
+    c8 = lambda x: (x + 7) & ~7                                                          # noqa: E731
+    rows = max(c8(3 + (2 * D if mode == 0 else D)), c8(c2)) + max(c8(c1), c3)
+    tb = (K + 31) // 32
+    return (rows * (32 * tb + 1) + 32 * tb) * 4 <= MAX_LDS
+
+
 def stream_rag_variant(c1, c3, K, with_table):
     """which of the ragged stream kernel's three forms: 12-wave table, 8-wave table, 8-wave index"""
     if not with_table:
         return "idx8"
     return "tab12" if sas_rag_lds(c1, c3, K, 12, True) <= MAX_LDS else "tab8"
+
+
+FAMILIES = ("generic", "krow_tile", "rag_tile", "stream", "stream_rag", "wsplit")      # PCR_SA_* of include/pcr.h
+VARIANTS = ("idx8", "tab8", "tab12")                                                  # form[2] of a stream_rag launch
+
+
+def from_library(form):
+    """pcr_sa_launch_form's ints -> (a dispatch() result, the ragged stream kernel's variant or None).  The library fills
+    every template default in and adds the arguments the unit fixes (PREC, IMG, LO, TAB, WAVES), which are checked and
+    dropped here.  dispatch() spells a K-row tile form the way its launcher does -- NR2 where it differs from NR, where
+    RKB follows it, and in the four-round form -- so those defaults are taken out again."""
+    unit, family, variant, n = form[:4]
+    a, fam = tuple(form[4:4 + n]), FAMILIES[family]
+    assert all(v == 0 for v in form[4 + n:]) and (variant == 0 or fam == "stream_rag")
+    lo = int(unit == 1)
+    if fam == "krow_tile":
+        tb, nr, w2, w3, maxe, nr2, rkb, prec, img = a
+        assert prec == unit and img == int(unit != 0 and nr2 == 1) and maxe in (0, 1)
+        args = (tb, nr, w2, w3) + ((nr2, rkb) if rkb else (nr2,) if (nr2 != nr or nr == 4) else ()) + ("maxe" if maxe else "full",)
+    elif fam == "rag_tile":
+        args = a[:6]
+        assert a[6:] == (unit,)
+    elif fam in ("stream", "wsplit"):
+        args = a[:2]
+        assert a[2:] == (lo,)
+    elif fam == "stream_rag":
+        args = a[:2]
+        assert a[2:] == (lo,) + ((0, 8), (1, 8), (1, 12))[variant]
+    else:
+        args = a
+        assert a == () and unit == 0
+    return (unit, fam, args), (VARIANTS[variant] if fam == "stream_rag" else None)
 
 
 def form_name(d):

@@ -29,7 +29,7 @@ layer-1 table is a code path of its own in each kernel (`hasp` / `pref` in sa_ra
 the reset of `acc1` in the cout-split kernel); a K-row tile form counts without its TB and epilogue flag -- and one
 B = 11 row per kernel family and unit: both held by tests/test_sa_ref_cpu.py.
 
-FOUND.  64 / 64 / c3 with 129 <= c3 <= 256 and K % 16 == 0 in a bf16 mode: sa2_launch_tb sent the class (2 ways, 1 way) to
+FOUND.  64 / 64 / c3 with 129 <= c3 <= 256 and K % 16 == 0 in a bf16 mode: the K-row fan-out (then sa2_launch_tb) sent the class (2 ways, 1 way) to
 sa_fused_kernel<TB,1,2,1> whatever the number of cout-block rounds, and with NR = 1, W3 = 1 wave w computes cout block w
 only.  Channels 128 and up of layer 3 were never computed and their maxima read from LDS nobody wrote: before the fix the
 eight rows 64_64_160 / 64_64_256 at K = 16 / 48 (bf16x3 and bf16) failed with err 1.4 .. 3.1 of the scale (70 000 ..
@@ -73,7 +73,7 @@ sa_rag_kernel, f32 | bf16x3 | bf16 (`-` = not instantiated there):
 sa_stream_rag_kernel, bf16x3 | bf16, index form <..,false,8> then table form <..,true,12>:
   <1,1> .49 .41 | .11 .13      <2,2> .44 .48 | .16 .18      <2,4> .26 .34 | .10 .12
 sa_stream_kernel <1,1> .36 | .20   <2,2> .33 | .14   <2,4> .32 | .09   <4,4> .48 | .12      sa_wsplit_rag_kernel<4,8> .43 | .12
-sa_mlp_kernel (fast=False on three shapes; 20/40/72, whose c1 % 8 != 0 sa2_try refuses) .13
+sa_mlp_kernel (fast=False on three shapes; 20/40/72, whose c1 % 8 != 0 sa_make_plan refuses) .13
 """
 import zlib
 
@@ -540,7 +540,7 @@ ROWS = [
     ('bf16', 0, 0, (64, 64, 64), 32, 7, None, 3, 0, 1, 'bf16 stream<2,2>'),
     ('bf16', 0, 0, (64, 64, 128), 32, 7, None, 3, 0, 1, 'bf16 stream<2,4>'),
     ('bf16', 0, 0, (128, 128, 128), 32, 7, None, 3, 0, 1, 'bf16 stream<4,4>'),
-    # ---- generic kernel sa_mlp_kernel: fast=False, and c1 % 8 != 0 which sa2_try refuses
+    # ---- generic kernel sa_mlp_kernel: fast=False, and c1 % 8 != 0 which sa_make_plan refuses
     ('f32', 0, 8, (64, 64, 64), 20, 5, None, 3, 0, 0, 'f32 generic<>'),
     ('bf16x3', 1, 5, (32, 64, 128), 16, 5, None, 3, 0, 0, 'f32 generic<>'),
     ('f32', 1, 0, (24, 40, 72), 7, 5, None, 11, 0, 0, 'f32 generic<>'),

@@ -251,10 +251,128 @@ def test_restated_rules_equal_the_exported_shape_queries():
                     assert lib.pcr_sa_claim_ws_ints(w[0], w[1], w[2], K, N, prec) == R.claim_ws_ints(w[0], w[1], w[2], K, N, prec)
             for B, S in ((1, 1), (3, 33), (11, 129), (2, 1000)):
                 assert lib.pcr_sa_tile_ws_ints(B, S, K, w[1], w[2]) == R.tile_ws_ints(B, S, K, w[1], w[2]), (w, K, B, S)
-    # the ragged stream launcher's final `else` sends four cout blocks to <2,4>: right only because no 128-wide layer
+    # the ragged stream plan sends every layer 3 of more than two cout blocks to <2,4>: right only because no 128-wide layer
     # reads the row table (the LDS rule of sas_shape keeps them out), at any K
     for K in range(1, 1025):
         for c3 in (128, 256):
             for prec in (1, 2):
                 assert lib.pcr_sa_uses_row_table(128, 128, c3, K, prec) == 0
                 assert not R.sas_shape(128, 128, c3, K, True)
+
+
+_DUMMY = 64         # any address that is not NULL: pcr_sa_launch_form reads pointers against NULL only
+
+
+def _launch_block(lib, mode, D, w, K, asked, feed, fast, B=3, S=5, N=256):
+    """the parameter block engine.SaPlan.run hands pcr_sa_mlp_f32 for such a call, every pointer a dummy.  feed: None (no hit
+    counts) | "idx" (hit counts and the index tensor) | "tab" (hit counts and the ball query's row table; the index tensor
+    is left out where the shape reads the table, as the engine's callers do).  Hit counts are passed in mode 1 only."""
+    from pcr_amd import abi
+    p = abi.SaParams()
+    p.mode, p.B, p.N, p.S, p.K, p.D = mode, B, N, S, K, D
+    p.c1, p.c2, p.c3 = w
+    p.xyz = p.out = _DUMMY
+    p.feat = _DUMMY if D else None
+    for i in range(3):
+        p.wp[i] = p.scale[i] = p.shift[i] = _DUMMY
+    asked = asked if fast else 0
+    ragged = bool(feed) and bool(fast) and mode == 1
+    reads_table = ragged and feed == "tab" and lib.pcr_sa_uses_row_table(w[0], w[1], w[2], K, asked)
+    p.idx = None if reads_table else _DUMMY
+    tiled = ragged or bool(fast and mode == 1 and lib.pcr_sa_krow_uses_tiles(w[0], w[1], w[2], K, asked))
+    if tiled and lib.pcr_sa_tile_ws_ints(B, S, K, w[1], w[2]) > 0:
+        p.tile_ws = _DUMMY
+    if ragged:
+        p.cnt = _DUMMY
+        p.row_tab = _DUMMY if feed == "tab" else None
+    if fast:
+        p.wa = p.wa_packed = p.wa_shift_packed = _DUMMY
+        p.precision = asked
+        if not ragged and lib.pcr_sa_claim_ws_ints(w[0], w[1], w[2], K, N, asked) > 0:
+            p.claim_ws = _DUMMY
+        for i in range(2):
+            p.wps[i] = p.shift_pad[i] = p.wps_bf[i] = _DUMMY
+        if D:
+            p.wpq = p.pq_ws = _DUMMY
+            p.pq_ready = 1
+            p.pq_has_xyz = int(asked != 0 and not ragged and not tiled and
+                               lib.pcr_sa_tables_take_xyz(mode, D, w[0], w[1], w[2], K, asked))
+    return p
+
+
+def _reported(lib, p):
+    """the form the library reports for a block, as the row tables spell it; None: the launch would be refused"""
+    import ctypes
+    form = (ctypes.c_int * 16)(*([-1] * 16))
+    status = lib.pcr_sa_launch_form(ctypes.byref(p), form)
+    if status != 0:
+        assert status == 1 and list(form) == [-1] * 16
+        return None
+    d, variant = R.from_library(list(form))
+    return R.form_name(d) + (":" + variant if variant else "")
+
+
+def _restated(mode, D, w, K, asked, feed, fast):
+    d = R.dispatch(mode, D, w[0], w[1], w[2], K, asked, bool(feed), bool(fast))
+    if d[1] == "generic" and not R.generic_fits(mode, D, w[0], w[1], w[2], K):
+        return None                 # (no kernel holds the shape: PCR_ERR_INVALID)
+    name = R.form_name(d)
+    if d[1] == "stream_rag":
+        name += ":" + R.stream_rag_variant(w[0], w[2], K, feed == "tab")
+    return name
+
+
+def test_the_library_reports_the_form_the_restatement_names():
+    """pcr_sa_launch_form (the dispatcher's own plan, no device) against sa_ref.dispatch over WIDTHS x K = 1 .. 192 x the
+    three precisions x (mode, D) x {no counts, counts with the index, counts with the row table} x fast operands or none"""
+    lib = _lib()
+    n = 0
+    for w in WIDTHS:
+        for K in range(1, 193):
+            for asked in (0, 1, 2):
+                for mode, D in ((0, 8), (0, 0), (1, 5)):
+                    for feed in (None, "idx", "tab"):
+                        want = {fast: _restated(mode, D, w, K, asked, feed, fast) for fast in (1, 0)}
+                        for fast in (1, 0):
+                            got = _reported(lib, _launch_block(lib, mode, D, w, K, asked, feed, fast))
+                            assert got == want[fast], (w, K, asked, mode, D, feed, fast)
+                            n += 1
+    assert n == len(WIDTHS) * 192 * 3 * 3 * 3 * 2
+
+
+def test_the_library_reports_every_row_of_the_gpu_file():
+    lib = _lib()
+    for row in G.ROWS:
+        prec, mode, D, w, K, S, kind, B, table, fast, expect = row
+        feed = None if kind is None else ("tab" if table else "idx")
+        p = _launch_block(lib, mode, D, w, K, R.PREC[prec], feed, fast, B=B, S=S, N=max(64, K + 8, S if mode == 0 else 0))
+        assert _reported(lib, p) == expect, G.row_id(row)
+        assert _kernel_args(p, lib) == _kernel_name(expect), G.row_id(row)
+
+
+def _kernel_args(p, lib):
+    """the reported template arguments spelled as a kernel trace spells them (`_kernel_name`)"""
+    import ctypes
+    form = (ctypes.c_int * 16)()
+    assert lib.pcr_sa_launch_form(ctypes.byref(p), form) == 0
+    family, n = form[1], form[3]
+    if family == 0:
+        return "sa_mlp_kernel("
+    bools = {1: (4, 8), 2: (), 3: (2,), 4: (2, 3), 5: (2,)}[family]
+    args = [("true" if form[4 + i] else "false") if i in bools else str(form[4 + i]) for i in range(n)]
+    kernel = ("", "sa_fused_kernel", "sa_rag_kernel", "sa_stream_kernel", "sa_stream_rag_kernel", "sa_wsplit_rag_kernel")[family]
+    return "%s<%s>" % (kernel, ", ".join(args))
+
+
+def test_the_form_query_refuses_what_the_launch_refuses():
+    import ctypes
+    lib = _lib()
+    form = (ctypes.c_int * 16)()
+    assert lib.pcr_sa_launch_form(None, form) == 1
+    p = _launch_block(lib, 0, 8, (64, 64, 64), 16, 1, None, 1)
+    assert lib.pcr_sa_launch_form(ctypes.byref(p), None) == 1
+    p.pq_has_xyz, p.pq_ready = 1, 0                  # tables with the coordinate term that nobody built
+    assert lib.pcr_sa_launch_form(ctypes.byref(p), form) == 1
+    p = _launch_block(lib, 1, 5, (24, 40, 72), 16, 0, "tab", 1)
+    p.idx = None                                     # a row table alone where only the generic kernel is left
+    assert lib.pcr_sa_launch_form(ctypes.byref(p), form) == 1

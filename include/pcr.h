@@ -2026,6 +2026,10 @@ int pcr_index_sum_f32(const float *src, const int *idx, const int *count, float 
  * two index sums, state_bwd.  For a list of cap pairs R = 2 cap, qi = [i.. ; j..], si = [j.. ; i..]: direction 1 of every
  * pair, then direction 2, so slots p and p + cap are pair p -- the layout pcr_pool_pair and kv_roll = cap of the next
  * stage expect.  A slot with qi or si outside [0, M) is dead: apply_fwd writes zeros for it, apply_bwd writes nothing.
+ * Its dqs and rec rows keep whatever the buffers held, so the caller of pcr_index_sum_f32 must pass lists in which a dead
+ * slot is dead in BOTH: -1 in qi and in si wherever either was outside [0, M) (train_ops.LinAttnPairs forms them).
+ * eps >= 0, 0 included: the padding tokens of a partial 64-token chunk (Q' = 0, so 1 / (Q'.ks + eps) = 1 / eps) are inert
+ * in both apply launches -- their reciprocal is taken as 0 -- and a live token has Q'.ks > 0.
  * q / k / v / dk / dv are (d, L) channel-major blocks per object addressed with a batch stride in floats (q_bs; kv_bs for
  * k and v; dkv_bs for dk and dv: slices of a fused (M, 3d, L) projection); Lq = Sk = L.  A (M,H,dh,dh) and ks (M,H,dh)
  * are written by state_fwd.  eps is a DEVICE pointer to one f32: as in section C2 no entry point takes a float scalar.

@@ -320,7 +320,7 @@ __global__ __launch_bounds__(256) void linattn_fwd_kernel(LinAttn a) {
     if (tid < KAT) {
       float z = 0.f;
       for (int i = 0; i < DH; i++) z += Qt[i * RP + tid] * ksl[i];
-      zl[tid] = 1.0f / (z + a.eps);
+      zl[tid] = tid < nl ? 1.0f / (z + a.eps) : 0.f;      // (padding tokens inert at every eps: no inf 0)
     }
     __syncthreads();
     for (int e = tid; e < DH * KAT; e += 256) {
@@ -372,7 +372,7 @@ __global__ __launch_bounds__(256) void linattn_bwd_kernel(LinAttn a) {
     if (tid < KAT) {
       float z = 0.f;
       for (int i = 0; i < DH; i++) z += Qt[i * RP + tid] * ksl[i];
-      zl[tid] = 1.0f / (z + a.eps);
+      zl[tid] = tid < nl ? 1.0f / (z + a.eps) : 0.f;      // (padding tokens inert at every eps: no inf 0)
     }
     __syncthreads();
     // num[v][l] = Q'_l . A[:,v];  dnum = dout z S;  dz_l = sum_v dout num S  (accumulated per token below)
@@ -514,7 +514,7 @@ __global__ __launch_bounds__(256) void linattn_fwd_mfma_kernel(LinAttn a) {
     if (tid < kAT) {
       float z = 0.f;
       for (int i = 0; i < DH; i++) z += Qt[i * RP + tid] * ksl[i];
-      zl[tid] = 1.0f / (z + a.eps);
+      zl[tid] = tid < nl ? 1.0f / (z + a.eps) : 0.f;      // (padding tokens inert at every eps: no inf 0)
     }
     __syncthreads();
     for (int tile = wave; tile < MT * NT; tile += 4) {      // out[v][l] = sum_i A[i][v] Q'[i][l]
@@ -575,7 +575,7 @@ __global__ __launch_bounds__(256) void linattn_bwd_mfma_kernel(LinAttn a) {
     if (tid < kAT) {
       float z = 0.f;
       for (int i = 0; i < DH; i++) z += Qt[i * RP + tid] * ksl[i];
-      zl[tid] = 1.0f / (z + a.eps);
+      zl[tid] = tid < nl ? 1.0f / (z + a.eps) : 0.f;      // (padding tokens inert at every eps: no inf 0)
     }
     __syncthreads();
     // num[v][l] = Q'_l . A[:,v];  dnum = dout z S;  dout * num * S is summed over v into dz below

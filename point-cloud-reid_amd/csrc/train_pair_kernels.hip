@@ -72,7 +72,8 @@ __global__ __launch_bounds__(kSumThreads) void index_sum_kernel(const float *__r
 // V' = v / L, A = sum_s K'_s V'_s^T, ks = sum_s K'_s, out_l = (Q'_l^T A) L / (Q'_l . ks + eps); Lq = Sk = L.
 // q / k / v are per-OBJECT (M, ., L) blocks addressed by a batch stride.  Slot r reads the queries of object qi[r] and the
 // state of object si[r]; a slot with either index outside [0, M) is dead: its output block is zeros, its backward writes
-// nothing (pcr_index_sum_f32 gives such a slot to no object).  blockIdx.x = object or slot, blockIdx.y = head.
+// nothing (pcr_index_sum_f32 gives such a slot to no object, given lists in which it is dead in BOTH: the caller masks
+// them).  blockIdx.x = object or slot, blockIdx.y = head.
 struct PairAttn {
   const float *q, *k, *v;
   long q_bs, k_bs, v_bs;       // floats between objects
@@ -175,7 +176,7 @@ __global__ __launch_bounds__(256) void pair_apply_fwd_kernel(PairAttn a) {
     if (tid < kAT) {
       float z = 0.f;
       for (int i = 0; i < DH; i++) z += Qt[i * RP + tid] * ksl[i];
-      zl[tid] = 1.0f / (z + eps);
+      zl[tid] = tid < nl ? 1.0f / (z + eps) : 0.f;       // (a padding token has Q' = 0: 1 / eps, inf at eps = 0)
     }
     __syncthreads();
     for (int tile = wave; tile < MT * NT; tile += 4) {      // out[v][l] = sum_i A[i][v] Q'[i][l]
@@ -222,7 +223,7 @@ __global__ __launch_bounds__(256) void pair_apply_bwd_kernel(PairAttn a) {
     if (tid < kAT) {
       float z = 0.f;
       for (int i = 0; i < DH; i++) z += Qt[i * RP + tid] * ksl[i];
-      zl[tid] = 1.0f / (z + eps);
+      zl[tid] = tid < nl ? 1.0f / (z + eps) : 0.f;       // padding tokens inert at every eps: Dn = ddl = 0, never inf 0
     }
     __syncthreads();
     // num[v][l] = Q'_l . A[:,v];  dnum = dout z L;  dout * num * L is summed over v into dz below

@@ -985,13 +985,16 @@ class LinAttnPairs(Function):
             L.run.pcr_linattn_state_fwd_f32(qkv[:, d:2 * d], qkv[:, 2 * d:], bs, A, ks, M, Ln, d, H, L.stream_ptr())
         with _prof("linattn_apply_fwd[d=%d,L=%d]" % (d, Ln), 2.0 * R * Ln * d * dh, 4.0 * R * (2 * d * Ln + d * dh)):
             L.run.pcr_linattn_apply_fwd_f32(qkv, bs, A, ks, qi, si, eps_t, out, M, R, Ln, d, H, L.stream_ptr())
-        ctx.save_for_backward(qkv, A, ks, qi, si, eps_t)
+        # a slot is dead when EITHER index is: apply_bwd leaves its dqs / rec rows unwritten, so neither index_sum of the
+        # backward may name an object for it (on the device: no host read, the launches stay capturable)
+        live = (qi >= 0) & (qi < M) & (si >= 0) & (si < M)
+        ctx.save_for_backward(qkv, A, ks, qi, si, eps_t, live)
         ctx.H = H
         return out
 
     @staticmethod
     def backward(ctx, g):
-        qkv, A, ks, qi, si, eps_t = ctx.saved_tensors
+        qkv, A, ks, qi, si, eps_t, live = ctx.saved_tensors
         H = ctx.H
         M, d3, Ln = qkv.shape
         d, R = d3 // 3, qi.numel()
@@ -1002,8 +1005,9 @@ class LinAttnPairs(Function):
             L.run.pcr_linattn_apply_bwd_f32(qkv, bs, A, ks, qi, si, eps_t, g.contiguous(), dqs, rec, M, R, Ln, d, H,
                                             L.stream_ptr())
         buf = torch.empty_like(qkv)
-        buf[:, :d] = index_sum(dqs, qi, None, M)
-        drec = index_sum(rec, si, None, M)
+        sum_q, sum_s = torch.where(live, torch.stack([qi, si]), -1)     # dead in one list: dead in both
+        buf[:, :d] = index_sum(dqs, sum_q, None, M)
+        drec = index_sum(rec, sum_s, None, M)
         with _prof("linattn_state_bwd[d=%d,L=%d]" % (d, Ln), 4.0 * M * Ln * d * dh, 4.0 * M * (4 * d * Ln + d * dh)):
             L.run.pcr_linattn_state_bwd_f32(qkv[:, d:2 * d], qkv[:, 2 * d:], bs, drec, buf[:, d:2 * d], buf[:, 2 * d:], bs,
                                             M, Ln, d, H, L.stream_ptr())

@@ -9,9 +9,17 @@ The attention comes in two forms that test_pair_list_ref_cpu.py holds to each ot
   * INDEXED: the decomposition the kernels use -- state per object (A, ks), apply per slot, per-slot records
     [dA | dks], their index_sum per object, dk / dv per object.
 
-`fault=` plants one of three mistakes in the indexed form, so that the checks can be seen to catch them:
-"dead" (dead slots are summed), "swap" (qi and si exchanged), "one_direction" (only the first half of the slots sends
-gradients back)."""
+The indexed form is written launch by launch, every output in the kernel's own layout (pairs_state_fwd, pairs_apply_fwd,
+pairs_apply_bwd, pairs_state_bwd), so that test_gpu_pair_list_ops.py can hold each launch on its own;
+linattn_pairs_indexed chains them, and linattn_pairs_scales gives the sums of absolute per-slot contributions that a
+float32 list-order sum rounds in proportion to.
+
+`fault=` plants one mistake in the indexed form, so that the checks can be seen to catch it: "dead" (dead slots are
+summed), "swap" (qi and si exchanged), "one_direction" (only the first half of the slots sends gradients back);
+"pad_one" (the padding keys of the last 64-token chunk counted as K' = elu(0) + 1 = 1 in ks), "half_dead" (a slot with ONE
+index outside [0, M) still sends dqs and rec back, to the object its other index names), "rec_layout" (the record
+interleaved as (dh, dh + 1) rows [dA_i | dks_i] but read as the kernel's [dA | dks]), "round_1024" (the index sums stop
+after their first 1024 slots)."""
 import numpy as np
 import torch
 
@@ -86,44 +94,125 @@ def linattn_pairs_gathered(q, k, v, qi, si, H, eps, dout=None):
     return out, index_sum_ref(dqs, ql, None, M), index_sum_ref(dks_, sl, None, M), index_sum_ref(dvs, sl, None, M)
 
 
-def linattn_pairs_indexed(q, k, v, qi, si, H, eps, dout=None, fault=None):
-    """the same through the kernels' decomposition: state per object, apply per slot, records per slot, index sums, state
-    backward per object -> out [, dq, dk, dv, rec (R,H,dh,dh+1)]"""
-    M, d, Ln = q.shape
-    Rn = qi.shape[0]
-    dh = d // H
-    if fault == "swap":
-        qi, si = si, qi
-    heads = lambda t: t.reshape(t.shape[0], H, dh, Ln)                      # noqa: E731
-    # state_fwd, per object
-    Kp, Vp = R._elu1(heads(k)), heads(v) / Ln
+CHUNK = 64        # tokens per staged chunk of the kernels (kAT)
+
+
+def _heads(t, H):
+    n, d, Ln = t.shape
+    return t.reshape(n, H, d // H, Ln)
+
+
+def pairs_state_fwd(k, v, H, fault=None):
+    """k, v (M,d,L) -> A (M,H,dh,dh), ks (M,H,dh): A = sum_s K'_s V'_s^T, ks = sum_s K'_s, K' = elu(k) + 1, V' = v / L"""
+    Ln = k.shape[2]
+    Kp, Vp = R._elu1(_heads(k, H)), _heads(v, H) / Ln
     A = torch.einsum("mhis,mhvs->mhiv", Kp, Vp)
     ks = Kp.sum(dim=3)
-    # apply_fwd, per slot
+    if fault == "pad_one":
+        ks = ks + float(-Ln % CHUNK)
+    return A, ks
+
+
+def _slot_operands(q, A, ks, qi, si, H):
+    M = q.shape[0]
     alive = _alive(qi, si, M)
     qs, ss = qi.clamp(0, M - 1), si.clamp(0, M - 1)
-    qh = heads(q)[qs]
-    Qp = R._elu1(qh)
-    z = 1.0 / (torch.einsum("rhil,rhi->rhl", Qp, ks[ss]) + eps)
-    num = torch.einsum("rhil,rhiv->rhvl", Qp, A[ss])
-    out = (num * Ln * z.unsqueeze(2)).reshape(Rn, d, Ln) * alive.view(-1, 1, 1).to(q.dtype)
-    if dout is None:
-        return out
-    # apply_bwd, per slot: dq of the slot and its record [dA | dks]
-    g = heads(dout)
+    qh = _heads(q, H)[qs]
+    return alive, qh, R._elu1(qh), A[ss], ks[ss]
+
+
+def pairs_apply_fwd(q, A, ks, qi, si, H, eps):
+    """q (M,d,L), A, ks of pairs_state_fwd, qi, si (R) -> out (R,d,L): out_r = (Q'_{qi[r]}^T A_{si[r]}) L / (Q'_{qi[r]} .
+    ks_{si[r]} + eps); a dead slot's block is 0"""
+    M, d, Ln = q.shape
+    alive, qh, Qp, As, kss = _slot_operands(q, A, ks, qi, si, H)
+    z = 1.0 / (torch.einsum("rhil,rhi->rhl", Qp, kss) + eps)
+    num = torch.einsum("rhil,rhiv->rhvl", Qp, As)
+    return (num * Ln * z.unsqueeze(2)).reshape(-1, d, Ln) * alive.view(-1, 1, 1).to(q.dtype)
+
+
+def pairs_apply_bwd(q, A, ks, qi, si, H, eps, dout, fault=None):
+    """-> dqs (R,d,L), rec (R,H,dh (dh + 1)) = [dA_r (dh x dh, row-major) | dks_r (dh)], (t1, t2): the slot's query gradient
+    dqs = t1 + t2 (through the numerator, through the denominator: with ONE token they cancel, train_attn_ref) and its
+    record, from the GIVEN A and ks.  The launch writes nothing for a dead slot; its rows are 0 here."""
+    M, d, Ln = q.shape
+    Rn, dh = qi.shape[0], d // H
+    alive, qh, Qp, As, kss = _slot_operands(q, A, ks, qi, si, H)
+    if fault == "half_dead":                    # only a slot with BOTH indices outside [0, M) counts as dead
+        alive = ((qi >= 0) & (qi < M)) | ((si >= 0) & (si < M))
+    if fault == "dead":                         # no slot is: each computes with its indices clamped into [0, M)
+        alive = torch.ones_like(alive)
+    g = _heads(dout, H)
+    z = 1.0 / (torch.einsum("rhil,rhi->rhl", Qp, kss) + eps)
+    num = torch.einsum("rhil,rhiv->rhvl", Qp, As)
     dnum = g * z.unsqueeze(2) * Ln
     dden = -z * z * Ln * (g * num).sum(dim=2)
-    dqs = (torch.einsum("rhiv,rhvl->rhil", A[ss], dnum) + dden.unsqueeze(2) * ks[ss].unsqueeze(3)) * R._elu1_grad(qh)
-    rec = torch.cat([torch.einsum("rhil,rhvl->rhiv", Qp, dnum), torch.einsum("rhl,rhil->rhi", dden, Qp).unsqueeze(3)],
-                    dim=3)                                                  # (R,H,dh,dh+1)
-    # the two index sums; a dead slot names no object
-    dead = torch.full_like(qi, -1)
-    sum_q, sum_s = (qs, ss) if fault == "dead" else (torch.where(alive, qi, dead), torch.where(alive, si, dead))
-    n = Rn // 2 if fault == "one_direction" else None
-    dq = index_sum_ref(dqs.reshape(Rn, d, Ln), sum_q, n, M)
-    drec = index_sum_ref(rec, sum_s, n, M)
-    # state_bwd, per object
-    dA, dks = drec[..., :dh], drec[..., dh]
-    dk = (torch.einsum("mhiv,mhvs->mhis", dA, Vp) + dks.unsqueeze(3)) * R._elu1_grad(heads(k))
+    t1 = torch.einsum("rhiv,rhvl->rhil", As, dnum) * R._elu1_grad(qh)
+    t2 = dden.unsqueeze(2) * kss.unsqueeze(3) * R._elu1_grad(qh)
+    dA = torch.einsum("rhil,rhvl->rhiv", Qp, dnum)
+    dks = torch.einsum("rhl,rhil->rhi", dden, Qp)
+    if fault == "rec_layout":
+        rec = torch.cat([dA, dks.unsqueeze(3)], dim=3).reshape(Rn, H, dh * (dh + 1))
+    else:
+        rec = torch.cat([dA.reshape(Rn, H, dh * dh), dks], dim=2)
+    a3, a4 = alive.view(-1, 1, 1).to(q.dtype), alive.view(-1, 1, 1, 1).to(q.dtype)
+    return (t1 + t2).reshape(Rn, d, Ln) * a3, rec * a3, ((t1 * a4).reshape(Rn, d, Ln), (t2 * a4).reshape(Rn, d, Ln))
+
+
+def pairs_state_bwd(k, v, drec, H):
+    """k, v (M,d,L), drec (M,H,dh (dh + 1)) GIVEN -> dk, dv (M,d,L), (u1, u2): dk = u1 + u2 = elu'(k) (dA V' + dks),
+    dv = dA^T K' / L"""
+    M, d, Ln = k.shape
+    dh = d // H
+    kh = _heads(k, H)
+    Kp, Vp = R._elu1(kh), _heads(v, H) / Ln
+    dA, dks = drec[..., :dh * dh].reshape(M, H, dh, dh), drec[..., dh * dh:]
+    u1 = torch.einsum("mhiv,mhvs->mhis", dA, Vp) * R._elu1_grad(kh)
+    u2 = dks.unsqueeze(3) * R._elu1_grad(kh)
     dv = torch.einsum("mhis,mhiv->mhvs", Kp, dA) / Ln
-    return out, dq, dk.reshape(M, d, Ln), dv.reshape(M, d, Ln), rec
+    return (u1 + u2).reshape(M, d, Ln), dv.reshape(M, d, Ln), (u1.reshape(M, d, Ln), u2.reshape(M, d, Ln))
+
+
+def _sum_lists(qi, si, M, fault=None):
+    """the lists the two index sums run over: a dead slot names no object in EITHER"""
+    if fault == "dead":
+        return qi.clamp(0, M - 1), si.clamp(0, M - 1)
+    if fault == "half_dead":                    # the lists as they came: the live index of a half-dead slot names its object
+        return qi, si
+    dead = torch.full_like(qi, -1)
+    alive = _alive(qi, si, M)
+    return torch.where(alive, qi, dead), torch.where(alive, si, dead)
+
+
+def linattn_pairs_indexed(q, k, v, qi, si, H, eps, dout=None, fault=None):
+    """the same through the kernels' decomposition: state per object, apply per slot, records per slot, index sums, state
+    backward per object -> out [, dq, dk, dv, rec (R,H,dh (dh + 1)), drec (M,H,dh (dh + 1))]"""
+    M = q.shape[0]
+    Rn = qi.shape[0]
+    if fault == "swap":
+        qi, si = si, qi
+    A, ks = pairs_state_fwd(k, v, H, fault)
+    out = pairs_apply_fwd(q, A, ks, qi, si, H, eps)
+    if dout is None:
+        return out
+    dqs, rec, _ = pairs_apply_bwd(q, A, ks, qi, si, H, eps, dout, fault)
+    sum_q, sum_s = _sum_lists(qi, si, M, fault)
+    n = Rn // 2 if fault == "one_direction" else 1024 if fault == "round_1024" else None
+    dq = index_sum_ref(dqs, sum_q, n, M)
+    drec = index_sum_ref(rec, sum_s, n, M)
+    dk, dv, _ = pairs_state_bwd(k, v, drec, H)
+    return out, dq, dk, dv, rec, drec
+
+
+def linattn_pairs_scales(q, k, v, qi, si, H, eps, dout):
+    """-> dict(dq, dk, dv) (M,d,L): per element, the sum over the live slots of the ABSOLUTE contributions that the
+    gradient is the sum of -- |t1| + |t2| of every slot for dq, |u1| + |u2| of every slot's own record for dk, |dv| of it
+    for dv.  A float32 sum in list order rounds in proportion to this, not to the (possibly cancelling) result."""
+    M = q.shape[0]
+    A, ks = pairs_state_fwd(k, v, H)
+    _, rec, (t1, t2) = pairs_apply_bwd(q, A, ks, qi, si, H, eps, dout)
+    sum_q, sum_s = _sum_lists(qi, si, M)
+    ss = si.clamp(0, M - 1)
+    dks_, dvs, (u1, u2) = pairs_state_bwd(k[ss], v[ss], rec, H)       # every slot's record against its own object
+    return dict(dq=index_sum_ref(t1.abs() + t2.abs(), sum_q, None, M),
+                dk=index_sum_ref(u1.abs() + u2.abs(), sum_s, None, M), dv=index_sum_ref(dvs.abs(), sum_s, None, M))

@@ -439,6 +439,32 @@ def test_linattn_functions_match_float64_and_each_other(case):
         _same(one, [out, torch.cat([dq, dk, dv], dim=1)])
 
 
+# eps = 0: a padding token of a partial chunk has Q' = 0, so 1 / (Q'.ks + eps) = 1 / 0 there; one case per kernel form with
+# a partial query chunk (the MFMA forms also with a full chunk before a 16-token tail)
+EPS0_CASES = [(2, 64, 2, 33, 33), (2, 64, 2, 80, 80), (2, 128, 2, 33, 33), (2, 128, 2, 80, 80), (2, 32, 2, 65, 33),
+              (2, 256, 2, 17, 17)]
+
+
+@pytest.mark.parametrize("case", EPS0_CASES)
+def test_linattn_at_eps_zero_is_finite_and_matches_float64(case):
+    """the padding tokens are inert: no inf 0 reaches dq, dk or dv"""
+    from pcr_amd import train_ops as TO
+    B, d, H, Lq, Sk = case
+    inp = make_lin_input(case)
+    q, k, v, go = (inp[n].to(F64) for n in ("q", "k", "v", "go"))
+    want = dict(zip(("out", "dq", "dk", "dv"), (R.linattn_ref(q, k, v, H, 0.0)[0],) + R.linattn_bwd_ref(q, k, v, H, 0.0, go)[:3]))
+    f32 = (R.linattn_ref(inp["q"], inp["k"], inp["v"], H, 0.0)[0],) + R.linattn_bwd_ref(inp["q"], inp["k"], inp["v"], H, 0.0,
+                                                                                     inp["go"])[:3]
+    bounds = {n: max(BOUND, YARD * _rel(a.to(F64), want[n])) for n, a in zip(want, f32)}
+    got = _fn_run(lambda a, b, c: TO.LinAttn.apply(a, b, c, H, 0.0), [inp[n].cuda().requires_grad_(True) for n in "qkv"],
+                  inp["go"].cuda())
+    worst = {n: _vs(t, want[n]) for n, t in zip(want, got)}
+    _report("LinAttn eps 0", case, worst, bounds)
+    for n, t in zip(want, got):
+        assert bool(torch.isfinite(t).all()), (case, n)
+        assert worst[n] < bounds[n], (case, n, worst[n], bounds[n])
+
+
 @pytest.mark.parametrize("kv_roll", [1, -1])
 @pytest.mark.parametrize("case", ROLL_CASES)
 def test_linattn_kv_roll_matches_float64(case, kv_roll):

@@ -1,7 +1,9 @@
 """CPU: the float64 restatements of training on a pair list (tests/pair_list_ref.py) hold each other -- the indexed
-decomposition against the gathered form, against autograd, index_sum against a Python loop -- three planted faults make the
-checks fail, ReIDNet refuses cartesian sampling with an auxiliary loss, and the golden files of the reference's cartesian
-train_step (tools/make_cartesian_golden.py) say what the cartesian rule says."""
+decomposition against the gathered form, against autograd, its per-slot records and query gradients against autograd with
+A and ks as leaves, index_sum against a Python loop -- planted faults make the checks fail, the ones the per-launch GPU
+tests are there for by more than the bounds test_gpu_pair_list_ops.py holds the kernels to, ReIDNet refuses cartesian
+sampling with an auxiliary loss, and the golden files of the reference's cartesian train_step
+(tools/make_cartesian_golden.py) say what the cartesian rule says."""
 import copy
 import json
 
@@ -10,6 +12,7 @@ import pytest
 import torch
 
 import pair_list_ref as PL
+import test_gpu_pair_list_ops as G          # case tables, inputs and references: plain CPU data
 import train_attn_ref as R
 from conftest import load_golden
 
@@ -73,6 +76,109 @@ def test_planted_faults_are_caught(fault):
     assert not all(_close(a, b) for a, b in zip(bad[:4], ga))
     if fault == "dead":                                                   # object 0 took the dead slots' gradients
         assert not _close(bad[1], ga[1]) or not _close(bad[2], ga[2])
+
+
+# ------------------------------------------------------------------------------------- the launches, one by one --
+RECORD_CASES = [(64, 2, 33, "randn", "fused", EPS), (128, 2, 97, "near_eps", "fused", EPS), (64, 1, 65, "randn", "fused", EPS), (64, 2, 80, "stress", "fused", EPS),
+                (64, 2, 33, "randn", "fused", 0.0)]
+
+
+@pytest.mark.parametrize("case", RECORD_CASES)
+def test_slot_records_and_query_gradients_equal_autograd_with_the_state_as_leaves(case):
+    """apply_fwd in float64 with q, A and ks of every live slot as leaf tensors: their gradients are the slot's dqs and
+    its record [dA | dks], in the kernel's layout"""
+    d, Hn, Ln, draw, layout, eps = case
+    dh = d // Hn
+    inp = {n: t.to(F64) for n, t in G.make_pair_input(case).items()}
+    qi, si = G.slot_lists_of_the_launch_cases()
+    A, ks = PL.pairs_state_fwd(inp["k"], inp["v"], Hn)
+    dqs, rec, (t1, t2) = PL.pairs_apply_bwd(inp["q"], A, ks, qi, si, Hn, eps, inp["dout"])
+    alive = PL._alive(qi, si, G.SLOT_M)
+    assert int(alive.sum()) == 7
+    qg, Ag, kg = (t.clone().requires_grad_(True) for t in (inp["q"][qi[alive]], A[si[alive]], ks[si[alive]]))
+    each = torch.arange(7)
+    PL.pairs_apply_fwd(qg, Ag, kg, each, each, Hn, eps).backward(inp["dout"][alive])
+    assert _close(dqs[alive], qg.grad) and _close(t1 + t2, dqs)
+    assert _close(rec[alive][..., :dh * dh], Ag.grad.reshape(7, Hn, dh * dh))
+    assert _close(rec[alive][..., dh * dh:], kg.grad)
+    assert float(dqs[~alive].abs().max()) == 0.0 and float(rec[~alive].abs().max()) == 0.0
+    # and the state backward from the summed records is autograd of the state forward
+    drec = PL.index_sum_ref(rec, PL._sum_lists(qi, si, G.SLOT_M)[1], None, G.SLOT_M)
+    kk, vv = (inp[n].clone().requires_grad_(True) for n in ("k", "v"))
+    A2, ks2 = PL.pairs_state_fwd(kk, vv, Hn)
+    torch.autograd.backward([A2, ks2], [drec[..., :dh * dh].reshape(A2.shape), drec[..., dh * dh:]])
+    dk, dv, (u1, u2) = PL.pairs_state_bwd(inp["k"], inp["v"], drec, Hn)
+    assert _close(dk, kk.grad) and _close(dv, vv.grad) and _close(u1 + u2, dk)
+    assert float(dk[3].abs().max()) == 0.0 and float(dv[3].abs().max()) == 0.0
+
+
+def test_every_launch_case_has_a_finite_reference_and_names_its_bound():
+    """the float64 reference and the float32 yardstick of every case the GPU tests run; the stressed draws print how close
+    the smallest denominator comes to eps and which outputs the yardstick, not BOUND, bounds"""
+    for case in G.APPLY_CASES:
+        want = G.pair_want(case)
+        assert all(bool(torch.isfinite(want[n]).all()) for n in G.LAUNCH_NAMES), case
+        assert all(np.isfinite(b) and b >= G.BOUND for b in want["bound"].values()), case
+        yard = [n for n in G.LAUNCH_NAMES if want["bound"][n] > G.BOUND]
+        if case[3] == "near_eps":
+            assert 1.0 < want["den_min"] < 100.0, (case, want["den_min"])
+        if case[3] != "randn" or yard:
+            print(json.dumps(dict(case=str(case), den_min_over_eps=want["den_min"], y32=want["y32"], yard=yard)))
+        if case[3] == "randn":
+            assert not yard, (case, yard)          # a float32 evaluation holds 2e-5 / 8 on plain draws
+
+
+def _launch_fault_error(case, fault):
+    """the error, in the GPU test's own measure and against its own reference, of the named launch output computed with
+    the planted mistake -> (error, bound)"""
+    d, Hn, Ln, draw, layout, eps = case
+    dh = d // Hn
+    want = G.pair_want(case)
+    inp = {n: t.to(F64) for n, t in G.make_pair_input(case).items()}
+    qi, si = G.slot_lists_of_the_launch_cases()
+    if fault == "pad_one":
+        bad = PL.pairs_state_fwd(inp["k"], inp["v"], Hn, fault)[1]
+        return G._launch_err(case, "ks", bad, want), want["bound"]["ks"]
+    A, ks = (want["given"][n].to(F64) for n in ("A", "ks"))
+    rec = PL.pairs_apply_bwd(inp["q"], A, ks, qi, si, Hn, eps, inp["dout"], fault)[1]
+    return G._launch_err(case, "dA", rec[..., :dh * dh], want), want["bound"]["dA"]
+
+
+@pytest.mark.parametrize("fault,case", [("pad_one", (64, 2, 33, "randn", "fused", EPS)),
+                                        ("pad_one", (64, 1, 130, "randn", "fused", EPS)),
+                                        ("rec_layout", (64, 2, 33, "randn", "fused", EPS)),
+                                        ("rec_layout", (128, 2, 80, "stress", "fused", EPS))])
+def test_planted_launch_faults_pass_the_gpu_bound(fault, case):
+    err, bound = _launch_fault_error(case, fault)
+    assert err > 10 * bound, (fault, case, err, bound)
+    assert _launch_fault_error(case, None)[0] == 0.0
+
+
+def _fn_fault_errors(qkv, dout, Mn, qi, si, D, Hn, fault):
+    q, k, v = (qkv[:, n * D:(n + 1) * D].contiguous() for n in range(3))
+    want = G.fn_want(q, k, v, dout, qi, si, Hn, EPS)
+    bad = PL.linattn_pairs_indexed(q.to(F64), k.to(F64), v.to(F64), qi, si, Hn, EPS, dout.to(F64), fault=fault)
+    return {n: float((bad[i] - want[n]).abs().max()) / want["scale"][n] for i, n in enumerate(G.FN_NAMES)}, want["bound"]
+
+
+@pytest.mark.parametrize("D,Hn,Ln", [(64, 2, 33), (64, 1, 65)])
+def test_a_half_dead_slot_that_sends_gradients_back_passes_the_gpu_bound(D, Hn, Ln):
+    Mn, qi, si = G.fn_lists("half_dead")
+    g = torch.Generator().manual_seed(D + Ln)
+    qkv = torch.randn(Mn, 3 * D, Ln, generator=g)
+    dout = torch.randn(qi.numel(), D, Ln, generator=g)
+    err, bound = _fn_fault_errors(qkv, dout, Mn, qi, si, D, Hn, "half_dead")
+    assert err["out"] == 0.0                       # the forward already kills the slot: only the backward shows it
+    assert err["dq"] > 10 * bound["dq"] and err["dk"] > 10 * bound["dk"] and err["dv"] > 10 * bound["dv"], (err, bound)
+    assert max(_fn_fault_errors(qkv, dout, Mn, qi, si, D, Hn, None)[0].values()) == 0.0
+
+
+def test_the_fan_in_case_needs_the_second_compaction_round():
+    """index sums that stop after 1024 of the 1200 slots miss the bound on every gradient"""
+    qkv, dout, qi, si = G.fan_in_case()
+    err, bound = _fn_fault_errors(qkv, dout, G.FAN_M, qi, si, G.FAN_D, 2, "round_1024")
+    assert all(err[n] > 10 * bound[n] for n in ("dq", "dk", "dv")), (err, bound)
+    assert all(b == G.BOUND for b in bound.values()), bound
 
 
 def _loop_sum(src, idx, count, Mn):

@@ -1434,6 +1434,45 @@ typedef struct pcr_live {
 int pcr_attn_live_ok(const pcr_attn_params *p);
 int pcr_attn_kv_live_f32(const pcr_attn_params *p, const pcr_live *live, pcr_stream_t stream);
 int pcr_attn_apply_live_f32(const pcr_attn_params *p, const pcr_live *live, pcr_stream_t stream);
+/* Which kernel would pcr_attn_kv_f32 (apply == 0) or pcr_attn_apply_f32 (apply != 0) launch for *p -- with live != NULL,
+ * their _live forms?  The dispatcher's own plan (csrc/attn_kernels_impl.h: attn_plan_kv / attn_plan_apply behind the
+ * entry's checks) and nothing else; no device is touched, pointers are read against NULL only, nothing is launched and
+ * pcr_last_launch_arith is left alone.  Returns what the launch would return before its first kernel (PCR_ERR_INVALID for
+ * a block it refuses; form is then left untouched); B = 0, where the launch returns PCR_OK without a kernel, reports the
+ * plan.  Writes PCR_ATTN_FORM_INTS ints:
+ *   form[0]  the arithmetic the launch notes (PCR_PREC_*: what pcr_last_launch_arith() says after it)
+ *   form[1]  the kernel family, PCR_ATTN_*
+ *   form[2]  1: the gated twin is launched (GATE = true as the kernel's last template argument; attn_kv_kernel_o3_live)
+ *   form[3]  n = the number of template arguments that follow
+ *   form[4 .. 4 + n)  the kernel's template arguments in the kernel's order, defaults filled in, bools as 0 / 1, GATE
+ *            left out (n <= 6):
+ *     PCR_ATTN_KV_TILE          attn_kv_kernel               TB, NR, WSEL, NTW
+ *     PCR_ATTN_KV_TILE_O3       attn_kv_kernel_o3            TB, NR, WSEL, NTW
+ *     PCR_ATTN_KV_TILE_O2       attn_kv_kernel_o2            TB, NR, WSEL, NTW, BFP
+ *     PCR_ATTN_KV_STREAM64      attn_kv_stream64_kernel      DIAG, BF, XS, ONEW
+ *     PCR_ATTN_KV_STREAM32      attn_kv_stream32_kernel      none
+ *     PCR_ATTN_KV_STREAM128     attn_kv_stream128_kernel     NH
+ *     PCR_ATTN_KV_WIDE          attn_kv_wide_kernel          NRW
+ *     PCR_ATTN_APPLY_TILE       attn_apply_kernel            TB, NR
+ *     PCR_ATTN_APPLY_STREAM64   attn_apply_stream64_kernel   QPOS, C1S, CF, NOB, ND, POOL
+ *     PCR_ATTN_APPLY_STREAM128  attn_apply_stream128_kernel  NH
+ *   form[10] kv: the effective token split (kv_splits cut to the number of tiles; 1 = whole clouds)
+ *   form[11] kv: 1 = attn_kv_fold_kernel follows
+ *   form[12] kv: waves per cloud of attn_kv_stream128_kernel, else 0
+ *   form[13] dynamic LDS bytes of the kernel
+ * the rest is zero. */
+#define PCR_ATTN_FORM_INTS 16
+#define PCR_ATTN_KV_TILE 0
+#define PCR_ATTN_KV_TILE_O3 1
+#define PCR_ATTN_KV_TILE_O2 2
+#define PCR_ATTN_KV_STREAM64 3
+#define PCR_ATTN_KV_STREAM32 4
+#define PCR_ATTN_KV_STREAM128 5
+#define PCR_ATTN_KV_WIDE 6
+#define PCR_ATTN_APPLY_TILE 7
+#define PCR_ATTN_APPLY_STREAM64 8
+#define PCR_ATTN_APPLY_STREAM128 9
+int pcr_attn_launch_form(const pcr_attn_params *p, const pcr_live *live, int apply, int *form);
 
 /* Matching head tail: pool 'both' over the point-concatenated pair (get_pooled_feats,
  * models/ReIDNet.py:526-534: [max over 2L points, mean over 2L points]) followed by

@@ -12,6 +12,7 @@
 
 #include <stdio.h>
 
+#include <initializer_list>
 #include <vector>
 
 namespace {
@@ -2217,144 +2218,169 @@ static void attn_dump_trace(const char *path, const char *tag, int wgs, int B, i
                              Sk);
 }
 
-// gated launches (pcr_live): the caller's count, period and offset travel in AttnArgs; false = not a valid gate
-static bool attn_set_live(AttnArgs &a, const pcr_live *live) {
-  a.live_count = nullptr;
-  a.live_period = a.live_offset = 0;
-  if (!live) return true;
-  if (!live->count || live->period < 1 || live->offset < 0) return false;
-  a.live_count = live->count;
-  a.live_period = live->period;
-  a.live_offset = live->offset;
-  return true;
+// ---- the dispatch, compiled once per arithmetic unit.  attn_plan_kv / attn_plan_apply are the single statement of what a
+// unit decides for a launch -- kernel family, template arguments, everything shape-derived the launch needs -- and touch
+// neither the device nor the chip's size; one launcher per family turns a plan into the launch.  The f32 unit also holds the
+// order of the units (attn_bf), the gate, the exported queries and the C-ABI entry points.
+
+// tuning builds' knobs (0 / null in production builds: pcr_common.h), gathered once per process and unit
+struct AttnTune {
+  int no_onew;         // PCR_ATTN_NO_ONEW: short key sets keep several waves per cloud
+  int no_kv128;        // PCR_ATTN_NO_KV128: the d = 128 stream kv shapes back to the tile kernel
+  int kv128_wpc;       // PCR_ATTN_KV128_WPC: 1 / 2 / 4 waves per cloud of attn_kv_stream128_kernel whatever Sk says
+  int no_stream128;    // PCR_ATTN_NO_STREAM128: the d = 128 stream apply shapes back to the tile kernel
+  const char *trace;   // PCR_ATTN_TRACE: file the d = 64 stream kernels' stamps are appended to
+};
+static const AttnTune &attn_tune() {
+  static const AttnTune once = {pcr_tune_int("PCR_ATTN_NO_ONEW"), pcr_tune_int("PCR_ATTN_NO_KV128"), pcr_tune_int("PCR_ATTN_KV128_WPC"),
+                                pcr_tune_int("PCR_ATTN_NO_STREAM128"), pcr_tune_str("PCR_ATTN_TRACE")};
+  return once;
 }
-// the blocks a gated launch covers: the matching stages' (d = c1 = c2 = cout = 64, whole launches) -- every kernel the
-// dispatchers below choose for them has a GATE form.  Shape only.
+
+// What one launch does.  arith / family / targ / gated / splits / fold / wpc / lds are pcr_attn_launch_form's encoding
+// (pcr.h); the rest is what the launchers read besides the parameter block.
+struct AttnPlan {
+  int arith = -1;               // PCR_PREC_* the launch notes: set as soon as the unit knows it (a later refusal still notes it)
+  int family = 0;               // PCR_ATTN_*
+  int ntarg = 0, targ[6] = {};  // the kernel's template arguments in the kernel's order, defaults filled in, GATE left out
+  bool gated = false;           // the gated twin (GATE = true, attn_kv_kernel_o3_live) is taken
+  bool trace = false;           // the kernel stamps the shader clock (AttnArgs.dbg = 256)
+  int threads = 0;              // per workgroup
+  size_t lds = 0;               // dynamic LDS of the main kernel
+  // the grid without the chip: (gx, gy) as it stands, or persistent -- `work` workgroups of work, at most per_cu per CU
+  bool persistent = false;
+  unsigned gx = 1, gy = 1;
+  long work = 0;
+  int per_cu = 0;
+  // kv side
+  int splits = 1;               // effective token split (AttnArgs.p.kv_splits of the narrow families)
+  bool fold = false;            // attn_kv_fold_kernel follows, one workgroup per cloud, fold_lds bytes
+  size_t fold_lds = 0;
+  int wpc = 0;                  // attn_kv_stream128_kernel: waves per cloud (AttnArgs.wpc)
+};
+
+// the plan's last step: the form, refused where a gated launch meets a family (or instantiation) without a gated twin
+static int attn_plan_form(AttnPlan *pl, int family, std::initializer_list<int> targ, bool twin, bool gated) {
+  pl->family = family;
+  pl->ntarg = 0;
+  for (int v : targ) pl->targ[pl->ntarg++] = v;
+  if (gated && !twin) return PCR_ERR_INVALID;
+  pl->gated = gated;
+  return PCR_OK;
+}
+// a persistent grid: `items` units of work, per_wg of them a workgroup round
+static void attn_plan_persistent(AttnPlan *pl, long items, int per_wg, int per_cu, int threads, size_t lds) {
+  pl->persistent = true;
+  pl->work = (items + per_wg - 1) / per_wg;
+  pl->per_cu = per_cu;
+  pl->threads = threads;
+  pl->lds = lds;
+}
+static void attn_plan_grid(AttnPlan *pl, unsigned gx, unsigned gy, size_t lds) {
+  pl->gx = gx;
+  pl->gy = gy;
+  pl->threads = kThreads;
+  pl->lds = lds;
+}
+// waves a cloud of nblk 32-token blocks takes in the stream kv kernels: the largest power of two within min(nblk, cap),
+// at least minw (the kernels' comments)
+static int attn_waves_per_cloud(int nblk, int cap, int minw) {
+  int w = 1;
+  while (w * 2 <= (nblk < cap ? nblk : cap)) w *= 2;
+  return w < minw ? minw : w;
+}
+
+// the blocks a gated launch covers: the matching stages' (d = c1 = c2 = cout = 64, whole launches).  Shape only.  Every
+// kernel the plans choose for them has a gated twin (tests/test_attn_ref_cpu.py enumerates them), so attn_plan_form's
+// refusal is never met behind this predicate.
 static bool attn_live_shape(const pcr_attn_params &p) {
   return p.d == 64 && p.c1 == 64 && p.c2 == 64 && p.cout == 64 && p.kv_splits <= 1;
 }
-// KERN, or its gated form when the launch carries a pcr_live
-template <auto KERN, auto KERN_LIVE>
-static inline int attn_launch_g(dim3 grid, dim3 block, size_t lds, hipStream_t st, const AttnArgs &a) {
-  return a.live_count ? pcr_launch_lds<KERN_LIVE>(grid, block, lds, st, a) : pcr_launch_lds<KERN>(grid, block, lds, st, a);
-}
 
-// d_model <= 128: one workgroup per key-side cloud (both precisions; wq / wkv / ... are images of THIS unit's kind)
-static int attn_kv_narrow(const pcr_attn_params *pp, const pcr_live *live, pcr_stream_t stream) {
-  AttnArgs a;
-  a.p = *pp;
-  a.dbg = 0;
-  a.wpc = 0;
-  if (!attn_set_live(a, live) || (live && !attn_live_shape(*pp))) return PCR_ERR_INVALID;
-  const int d = pp->d;
-  if (pp->c2 < pp->d) return PCR_ERR_INVALID;   // the in-place K/V projection needs 2d <= c2 + d rows
+// The kv launch of one unit (wq / wkv / ... are images of THIS unit's kind).  d_model <= 128: one workgroup per key-side
+// cloud and token split (tile families) or persistent wave-autonomous workgroups (stream families); wider: d / 64
+// workgroups per cloud (f32 unit only).
+static int attn_plan_kv(const pcr_attn_params &p, bool gated, const AttnTune &t, AttnPlan *pl) {
+  constexpr bool kBfUnit = kAPrec != 0;
+  const int d = p.d;
+  if (d > 128) {
+    if (kBfUnit || !p.wkv_wide || !p.bkv_wide || !p.wmerge_packed || p.B > 65535) return PCR_ERR_INVALID;
+    pl->arith = PCR_PREC_F32;
+    const int dh = d / p.nhead;
+    size_t lds = ((size_t)(p.c2 + d + 3) * 33 + 4 * d + kThreads) * sizeof(float);
+    const size_t lds2 = (size_t)dh * 65 * sizeof(float);
+    if (lds2 > lds) lds = lds2;
+    if (lds > (size_t)kMaxDynLds) return PCR_ERR_INVALID;
+    attn_plan_grid(pl, d / 64, p.B, lds);
+    return attn_plan_form(pl, PCR_ATTN_KV_WIDE, {64 + dh <= 256 ? 2 : 3}, false, gated);
+  }
+  if (p.c2 < d) return PCR_ERR_INVALID;   // the in-place K/V projection needs 2d <= c2 + d rows
+  // RULE: the tile kernel's LDS and the token split are judged first, whichever family then takes the launch -- a block the
+  // tile kernel could not hold, or a split without its workspace, is refused even where a stream form would run it
   const int tb = d <= 64 ? 2 : 1, RP = 32 * tb + 1;
-  size_t lds = (size_t)(pp->c2 + d + 3) * RP + 4 * d;
+  size_t lds = (size_t)(p.c2 + d + 3) * RP + 4 * d;
   const size_t lds2 = (size_t)d * (d + 1) + d;
   if (lds2 > lds) lds = lds2;
   lds = (lds + kThreads) * sizeof(float);
   if (lds > (size_t)kMaxDynLds) return PCR_ERR_INVALID;
-  const int ntile = (pp->Sk + 32 * tb - 1) / (32 * tb);
-  int ns = pp->kv_splits > 1 ? pp->kv_splits : 1;
-  if (ns > 1 && (!pp->kv_part || ns > 64)) return PCR_ERR_INVALID;
+  const int ntile = (p.Sk + 32 * tb - 1) / (32 * tb);
+  int ns = p.kv_splits > 1 ? p.kv_splits : 1;
+  if (ns > 1 && (!p.kv_part || ns > 64)) return PCR_ERR_INVALID;
   if (ns > ntile) ns = ntile;                 // (kv_part is sized for the requested count: fewer splits use its head)
-  a.p.kv_splits = ns;
-  dim3 g(pp->B, ns), blk(kThreads);
-  hipStream_t st = pcr_s(stream);
-  constexpr bool kBfUnit = kAPrec != 0;
-  const bool bfk = kBfUnit && pp->wkv_bf != nullptr;
-  if (ns == 1 && d == 64 && (pp->c2 == 64 || (pp->c2 == 128 && bfk && pp->Sk >= 128)) && (pp->Sk & 31) == 0 && pp->nhead >= 1 &&
-      64 % pp->nhead == 0) {
-    // wave-autonomous form (shape-only choice; an explicit token split keeps the tile kernel)
-    const bool bf = bfk;
-    const bool wide = pp->c2 == 128;
-    pcr_note_arith(bf ? PCR_PREC_BF16X3 : PCR_PREC_F32);   // (the projection; the KV accumulation and the fold are f32)
-    const int nblk = pp->Sk >> 5;
-    const int minw = wide ? 4 : 2;
-    int wpc2 = 1;
-    while (wpc2 * 2 <= (nblk < 4 ? nblk : 4)) wpc2 *= 2;      // (at most four waves per cloud: the kernel's comment)
-    if (wpc2 < minw) wpc2 = minw;
-    // short key sets: one wave per cloud (ONEW; shape-only, the bf16 unit's image only)
-    static const int no_onew = pcr_tune_int("PCR_ATTN_NO_ONEW");   // diagnostics
-    const bool onew = kBfUnit && bf && !wide && nblk <= 4 && !no_onew;
-    if (onew) wpc2 = 1;
-    const int cpg = kKvsWaves / wpc2;
-    const size_t wu = bf ? (size_t)((wide ? 8 : 4) + 4) * 512 : 4096;
+  pl->splits = ns;
+  // the stream families take whole clouds of whole 32-token blocks (shape-only choices; an explicit token split keeps the
+  // tile kernel); bfk: this unit projects in split bf16 from the wkv_bf image
+  const bool whole = ns == 1 && (p.Sk & 31) == 0, bfk = kBfUnit && p.wkv_bf != nullptr;
+  const int nblk = p.Sk >> 5;
+  if (whole && d == 64 && (p.c2 == 64 || (p.c2 == 128 && bfk && p.Sk >= 128)) && 64 % p.nhead == 0) {
+    // c2 = 128 (XS = 8): not a matching-stage block, no gated twin.  ONEW: short key sets, one wave per cloud (the bf16
+    // unit's image only).  At most four waves per cloud.
+    const bool wide = p.c2 == 128, onew = bfk && !wide && nblk <= 4 && !t.no_onew;
+    pl->arith = bfk ? PCR_PREC_BF16X3 : PCR_PREC_F32;   // (the projection; the KV accumulation and the fold are f32)
+    const int cpg = kKvsWaves / (onew ? 1 : attn_waves_per_cloud(nblk, 4, wide ? 4 : 2));
+    const size_t wu = bfk ? (size_t)((wide ? 8 : 4) + 4) * 512 : 4096;
     const size_t lds_s = (wu * 4 + 256 + 128 + 64 * 65 + (onew ? (size_t)0 : (size_t)cpg * (64 * 65 + 64))) * sizeof(float);
-    const long rounds = ((long)pp->B + cpg - 1) / cpg;
-    const int gs = (int)(rounds < pcr_cu_count() ? rounds : pcr_cu_count());        // persistent: one workgroup per CU
-    const dim3 gg(gs), bb(64 * kKvsWaves);
-    const bool mh = pp->nhead >= 2;
-    if (bf && wide) {
-      if (live) return PCR_ERR_INVALID;   // (c2 = 128: not a matching-stage block)
-      constexpr int W = kBfUnit ? 8 : 4;
-      return mh ? pcr_launch_lds<attn_kv_stream64_kernel<true, kBfUnit, W>>(gg, bb, lds_s, st, a)
-                : pcr_launch_lds<attn_kv_stream64_kernel<false, kBfUnit, W>>(gg, bb, lds_s, st, a);
-    }
-    if (!bf)
-      return mh ? attn_launch_g<attn_kv_stream64_kernel<true, false>, attn_kv_stream64_kernel<true, false, 4, false, true>>(gg, bb, lds_s, st, a)
-                : attn_launch_g<attn_kv_stream64_kernel<false, false>, attn_kv_stream64_kernel<false, false, 4, false, true>>(gg, bb, lds_s, st, a);
-    static const char *atrace = pcr_tune_str("PCR_ATTN_TRACE");
-    if (atrace) a.dbg |= 256;
-    int rc;
-    if (onew)
-      rc = mh ? attn_launch_g<attn_kv_stream64_kernel<true, kBfUnit, 4, kBfUnit>, attn_kv_stream64_kernel<true, kBfUnit, 4, kBfUnit, true>>(gg, bb, lds_s, st, a)
-              : attn_launch_g<attn_kv_stream64_kernel<false, kBfUnit, 4, kBfUnit>, attn_kv_stream64_kernel<false, kBfUnit, 4, kBfUnit, true>>(gg, bb, lds_s, st, a);
-    else
-      rc = mh ? attn_launch_g<attn_kv_stream64_kernel<true, kBfUnit>, attn_kv_stream64_kernel<true, kBfUnit, 4, false, true>>(gg, bb, lds_s, st, a)
-              : attn_launch_g<attn_kv_stream64_kernel<false, kBfUnit>, attn_kv_stream64_kernel<false, kBfUnit, 4, false, true>>(gg, bb, lds_s, st, a);
-    if (atrace) attn_dump_trace(atrace, "kv64", gs, (int)pp->B, pp->Sk);
-    return rc;
+    attn_plan_persistent(pl, p.B, cpg, 1, 64 * kKvsWaves, lds_s);
+    pl->trace = bfk && !wide && t.trace != nullptr;
+    return attn_plan_form(pl, PCR_ATTN_KV_STREAM64, {p.nhead >= 2, bfk, wide ? 8 : 4, onew}, !wide, gated);
   }
 #if PCR_ATTN_PREC != 0
-  if (ns == 1 && d == 32 && pp->c2 == 32 && pp->wkv_bf && (pp->Sk & 31) == 0 && pp->nhead >= 1 && 32 % pp->nhead == 0) {
-    pcr_note_arith(PCR_PREC_BF16X3);
-    const int nblk = pp->Sk >> 5;
-    int wpc2 = 1;
-    while (wpc2 * 2 <= (nblk < kKvsWaves ? nblk : kKvsWaves)) wpc2 *= 2;
-    if (wpc2 < 2) wpc2 = 2;
-    const int cpg = kKvsWaves / wpc2;
+  if (whole && d == 32 && p.c2 == 32 && p.wkv_bf && 32 % p.nhead == 0) {
+    pl->arith = PCR_PREC_BF16X3;
+    const int cpg = kKvsWaves / attn_waves_per_cloud(nblk, kKvsWaves, 2);
     const size_t lds_s = (size_t)(4096 + 128 + 64 + 32 * 33 + cpg * (32 * 33 + 32)) * sizeof(float);
-    const long rounds = ((long)pp->B + cpg - 1) / cpg;
-    const long cap = 2L * pcr_cu_count();                                // (small footprint: two workgroups per CU)
-    return pcr_launch_lds<attn_kv_stream32_kernel>(dim3((unsigned)(rounds < cap ? rounds : cap)), dim3(64 * kKvsWaves), lds_s, st, a);
+    attn_plan_persistent(pl, p.B, cpg, 2, 64 * kKvsWaves, lds_s);        // (small footprint: two workgroups per CU)
+    return attn_plan_form(pl, PCR_ATTN_KV_STREAM32, {}, false, gated);
   }
-  static const int no_kv128 = pcr_tune_int("PCR_ATTN_NO_KV128");   // diagnostics: these shapes back to the tile kernel
-  if (ns == 1 && d == 128 && pp->c2 == 128 && pp->wkv_bf && (pp->Sk & 31) == 0 && pp->Sk >= 256 &&
-      (pp->nhead == 2 || pp->nhead == 4) && !no_kv128) {
-    // SA3's self-attention (d_model 128): the wave-autonomous form with the weights streamed through an LDS ring
-    // (shape-only choice, the split-projection rule below: key sets of >= 256 tokens); persistent, one workgroup of four
-    // waves per CU
-    pcr_note_arith(PCR_PREC_BF16X3);   // (the projection; the KV accumulation and the fold are f32)
-    a.wpc = attn_kv128_wpc(pp->Sk >> 5);
-    static const int wpc_t = pcr_tune_int("PCR_ATTN_KV128_WPC");   // diagnostics: 1 / 2 / 4 waves per cloud
-    if (wpc_t == 1 || wpc_t == 2 || wpc_t == 4) a.wpc = wpc_t;
-    const int cpg = kAp128Waves / a.wpc;
-    const size_t lds_s = kKv128Lds0 + (a.wpc > 1 ? (size_t)cpg * (16 * (16 / pp->nhead) + 4) * 64 * sizeof(float) : 0);
-    const long nwg = ((long)pp->B + cpg - 1) / cpg;
-    const dim3 gg((unsigned)(nwg < pcr_cu_count() ? nwg : pcr_cu_count())), bb(64 * kAp128Waves);
-    return pp->nhead == 2 ? pcr_launch_lds<attn_kv_stream128_kernel<2>>(gg, bb, lds_s, st, a)
-                          : pcr_launch_lds<attn_kv_stream128_kernel<4>>(gg, bb, lds_s, st, a);
+  if (whole && d == 128 && p.c2 == 128 && p.wkv_bf && p.Sk >= 256 && (p.nhead == 2 || p.nhead == 4) && !t.no_kv128) {
+    // SA3's self-attention (d_model 128): the wave-autonomous form with the weights streamed through an LDS ring (the
+    // split-projection rule below: key sets of >= 256 tokens); one workgroup of four waves per CU
+    pl->arith = PCR_PREC_BF16X3;   // (the projection; the KV accumulation and the fold are f32)
+    pl->wpc = (t.kv128_wpc == 1 || t.kv128_wpc == 2 || t.kv128_wpc == 4) ? t.kv128_wpc : attn_kv128_wpc(nblk);
+    const int cpg = kAp128Waves / pl->wpc;
+    const size_t lds_s = kKv128Lds0 + (pl->wpc > 1 ? (size_t)cpg * (16 * (16 / p.nhead) + 4) * 64 * sizeof(float) : 0);
+    attn_plan_persistent(pl, p.B, cpg, 1, 64 * kAp128Waves, lds_s);
+    return attn_plan_form(pl, PCR_ATTN_KV_STREAM128, {p.nhead}, false, gated);
   }
 #endif
-  if (live && (d != 64 || ns != 1)) return PCR_ERR_INVALID;
-  pcr_note_arith(PCR_PREC_F32);   // the tile kernel projects in f32 in both units (only the form of M differs)
+  // the tile families project in f32 in both units (only the form of M differs)
+  attn_plan_grid(pl, p.B, ns, lds);
+  pl->fold = ns > 1;
+  pl->fold_lds = ((size_t)d * (d + 1) + d) * sizeof(float);
   int rc;
-  if (d == 32) rc = pcr_launch_lds<attn_kv_kernel<2, 1, 2, 1>>(g, blk, lds, st, a);        // 2d = 64: two cout blocks
-  else if (d == 64) rc = attn_launch_g<attn_kv_kernel_o3<2, 1, 1, 1>, attn_kv_kernel_o3_live<2, 1, 1, 1>>(g, blk, lds, st, a);   // four, one per wave
-  else if (d == 128) {
+  if (d == 32) rc = attn_plan_form(pl, PCR_ATTN_KV_TILE, {2, 1, 2, 1}, false, gated);            // 2d = 64: two cout blocks
+  else if (d == 64) rc = attn_plan_form(pl, PCR_ATTN_KV_TILE_O3, {2, 1, 1, 1}, ns == 1, gated);   // four, one per wave
+  else if (d == 128)
     // eight cout blocks, two rounds.  NOT the three-workgroups-per-CU form: this shape's fold buffer (d (d + 1) floats =
     // 66 KB) allows two workgroups per CU whatever the registers say, and held to a third of the register file the body
     // spilled 93 registers inside its tile loop for nothing (round 5, tools/kres.py)
-    // (split-bf16 projection for key sets of >= 256 tokens -- a shape-only rule: the KV state is a mean over the key
+    // (BFP, split-bf16 projection for key sets of >= 256 tokens -- a shape-only rule: the KV state is a mean over the key
     // tokens, so the projection's rounding averages out with their number; at Sk = 32 (the Point-Transformer @128) the
     // guard's sweep of tests/test_gpu_precision.py went from 4.5e-5 to 5.2e-5 with it, for 0.014 ms)
-    if (kBfUnit && pp->wkv_bf && pp->Sk >= 256) rc = pcr_launch_lds<attn_kv_kernel_o2<1, 2, 1, 4, true>>(g, blk, lds, st, a);
-    else rc = pcr_launch_lds<attn_kv_kernel_o2<1, 2, 1, 4>>(g, blk, lds, st, a);
-  }
-  else rc = pcr_launch_lds<attn_kv_kernel<1, 2, 0, 4>>(g, blk, lds, st, a);                // d = 96: generic shape
-  if (rc != PCR_OK || ns == 1) return rc;
-  return pcr_launch_lds<attn_kv_fold_kernel>(dim3(pp->B), blk, ((size_t)d * (d + 1) + d) * sizeof(float), st, a);
+    rc = attn_plan_form(pl, PCR_ATTN_KV_TILE_O2, {1, 2, 1, 4, bfk && p.Sk >= 256}, false, gated);
+  else rc = attn_plan_form(pl, PCR_ATTN_KV_TILE, {1, 2, 0, 4}, false, gated);                     // d = 96: generic shape
+  if (rc == PCR_OK) pl->arith = PCR_PREC_F32;
+  return rc;
 }
 
 // the d = 64 wave-autonomous apply form (attn_apply_stream64_kernel), shapes: (c1 = 64 | 32 | < 16 with the padded
@@ -2367,13 +2393,10 @@ static bool aps64_shape(const pcr_attn_params &p) {
   return p.d == 64 && aps_in && aps_out && (p.Lq & 31) == 0 && (p.nhead == 1 || p.nhead == 2 || p.nhead == 4);
 }
 
-static int attn_apply_launch(const pcr_attn_params *pp, const pcr_live *live, pcr_stream_t stream) {
-  const pcr_attn_params &p = *pp;
-  AttnArgs a;
-  a.p = p;
-  a.dbg = 0;
-  a.wpc = 0;
-  if (!attn_set_live(a, live) || (live && !attn_live_shape(p))) return PCR_ERR_INVALID;
+// The apply launch of one unit: 32 tb-token tiles per workgroup (tile family) or persistent wave-autonomous workgroups over
+// 32-token blocks (stream families, bf16 unit only).
+static int attn_plan_apply(const pcr_attn_params &p, bool gated, const AttnTune &t, AttnPlan *pl) {
+  (void)t;
   // (round 6, measured and dropped: 64-token tiles for d = 128 -- half the weight traffic from L2, half the waves per CU:
   // pt1024's attn_apply[d=128] 0.455 -> 0.518 ms, profiles/r06_inproc_ab.txt)
   const int tb = p.d <= 32 ? 4 : (p.d <= 64 ? 2 : 1), T = 32 * tb, RP = T + 1;
@@ -2381,98 +2404,233 @@ static int attn_apply_launch(const pcr_attn_params *pp, const pcr_live *live, pc
   int rowsU = catP > 2 * p.d ? catP : 2 * p.d;
   if (ceil32(p.cout) > rowsU) rowsU = ceil32(p.cout);
   if (ceil32(p.cfinal) > rowsU) rowsU = ceil32(p.cfinal);
-  size_t lds = ((size_t)(rowsU + 3 + p.nhead) * RP + 2 * (kThreads / T) * T + 7 * p.d + 2 * p.cout) *
-               sizeof(float);
+  const size_t lds = ((size_t)(rowsU + 3 + p.nhead) * RP + 2 * (kThreads / T) * T + 7 * p.d + 2 * p.cout) * sizeof(float);
+  // RULE: the tile kernel's LDS is judged first, whichever family then takes the launch
   if (lds > (size_t)kMaxDynLds) return PCR_ERR_INVALID;
-  dim3 g((p.Lq + T - 1) / T, p.B), blk(kThreads);
-  hipStream_t st = pcr_s(stream);
-  pcr_note_arith(kAPrec != 0 ? PCR_PREC_BF16X3 : PCR_PREC_F32);   // (the bf unit is split bf16 whatever was requested)
+  pl->arith = kAPrec != 0 ? PCR_PREC_BF16X3 : PCR_PREC_F32;   // (the bf unit is split bf16 whatever was requested)
 #if PCR_ATTN_PREC != 0
+  const long nitem = (long)p.B * (p.Lq >> 5);   // (the stream shapes: whole 32-token blocks)
+  if (p.d == 128 && p.c1 == 128 && p.cout == 128 && !p.cfinal && p.q_pos && p.residual && (p.Lq & 31) == 0 && p.Lq >= 256 &&
+      (p.nhead == 1 || p.nhead == 2 || p.nhead == 4) && !t.no_stream128) {
+    // SA3's self-attention (d_model 128): the wave-autonomous form with the weights streamed through an LDS ring
+    // (shape-only choice); one workgroup of four waves per CU.  Query sets of >= 256 tokens only, the kv kernel's
+    // split-projection rule: at Lq = 32 (the Point-Transformer @128) its other rounding took one case of
+    // tests/test_gpu_precision.py's margin sweep from under 5e-5 to 5.4e-5
+    attn_plan_persistent(pl, nitem, kAp128Waves, 1, 64 * kAp128Waves, kAp128Lds);
+    return attn_plan_form(pl, PCR_ATTN_APPLY_STREAM128, {p.nhead}, false, gated);
+  }
   const int aps_c1s = (p.c1 + 15) >> 4, aps_nd = p.d >> 5;
   const size_t aps_lds = (size_t)((aps_c1s + (p.q_pos ? 2 * aps_nd : 0)) * aps_nd * 128 + (aps_c1s + 2 * aps_nd) * aps_nd * 256 +
                                   aps_nd * (p.cout >> 5) * 512) * 16 +
                          (size_t)(448 + 256 + 64 * kApsWaves) * sizeof(float);
-  static const int no_s128 = pcr_tune_int("PCR_ATTN_NO_STREAM128");   // diagnostics: these shapes back to the tile kernel
-  if (p.d == 128 && p.c1 == 128 && p.cout == 128 && !p.cfinal && p.q_pos && p.residual && (p.Lq & 31) == 0 && p.Lq >= 256 &&
-      (p.nhead == 1 || p.nhead == 2 || p.nhead == 4) && !no_s128) {
-    // SA3's self-attention (d_model 128): the wave-autonomous form with the weights streamed through an LDS ring
-    // (shape-only choice); persistent, one workgroup of four waves per CU.  Query sets of >= 256 tokens only, the kv
-    // kernel's split-projection rule: at Lq = 32 (the Point-Transformer @128) its other rounding took one case of
-    // tests/test_gpu_precision.py's margin sweep from under 5e-5 to 5.4e-5
-    const long nitem = (long)p.B * (p.Lq >> 5);
-    const long nwg = (nitem + kAp128Waves - 1) / kAp128Waves;
-    const dim3 gg((unsigned)(nwg < pcr_cu_count() ? nwg : pcr_cu_count())), bb(64 * kAp128Waves);
-    if (p.nhead == 1) return pcr_launch_lds<attn_apply_stream128_kernel<1>>(gg, bb, kAp128Lds, st, a);
-    if (p.nhead == 2) return pcr_launch_lds<attn_apply_stream128_kernel<2>>(gg, bb, kAp128Lds, st, a);
-    return pcr_launch_lds<attn_apply_stream128_kernel<4>>(gg, bb, kAp128Lds, st, a);
-  }
   if (p.d == 32 && p.c1 == 32 && p.cout == 32 && !p.cfinal && (p.Lq & 31) == 0 && (p.nhead == 1 || p.nhead == 2)) {
-    // the SA1 self-attention (d_model 32): the same kernel with one 32-channel block
-    const long nitem = (long)p.B * (p.Lq >> 5);
-    const long nwg = (nitem + kApsWaves - 1) / kApsWaves;
-    const dim3 gg((unsigned)(nwg < pcr_cu_count() ? nwg : pcr_cu_count())), bb(64 * kApsWaves);
-    return p.q_pos ? pcr_launch_lds<attn_apply_stream64_kernel<true, 2, 0, 1, 1>>(gg, bb, aps_lds, st, a)
-                   : pcr_launch_lds<attn_apply_stream64_kernel<false, 2, 0, 1, 1>>(gg, bb, aps_lds, st, a);
+    // the SA1 self-attention (d_model 32): the d = 64 kernel with one 32-channel block
+    attn_plan_persistent(pl, nitem, kApsWaves, 1, 64 * kApsWaves, aps_lds);
+    return attn_plan_form(pl, PCR_ATTN_APPLY_STREAM64, {p.q_pos != 0, 2, 0, 1, 1, 0}, false, gated);
   }
   if (aps64_shape(p) && aps_lds <= (size_t)kMaxDynLds) {
-    // wave-autonomous form (shape-only choice)
-    const int nob = p.cout >> 5;
-    const long nitem = (long)p.B * (p.Lq >> 5);
-    const long nwg = (nitem + kApsWaves - 1) / kApsWaves;
-    const dim3 gg((unsigned)(nwg < pcr_cu_count() ? nwg : pcr_cu_count())), bb(64 * kApsWaves);
-    const bool cf = p.cfinal != 0;
-    static const char *aptrace = pcr_tune_str("PCR_ATTN_TRACE");
-    if (aptrace) a.dbg = 256;
-    if (pp->pool_out) {
+    pl->trace = t.trace != nullptr;
+    const int cf = p.cfinal ? 4 : 0;
+    if (p.pool_out) {
       // pooled output (pcr_attn_apply_pool_ok said yes): whole clouds per wave
-      const long nwgp = ((long)p.B + kApsWaves - 1) / kApsWaves;
-      const dim3 ggp((unsigned)(nwgp < pcr_cu_count() ? nwgp : pcr_cu_count()));
-      return attn_launch_g<attn_apply_stream64_kernel<false, 4, 0, 2, 2, true>, attn_apply_stream64_kernel<false, 4, 0, 2, 2, true, true>>(ggp, bb, aps_lds, st, a);
+      attn_plan_persistent(pl, p.B, kApsWaves, 1, 64 * kApsWaves, aps_lds);
+      return attn_plan_form(pl, PCR_ATTN_APPLY_STREAM64, {0, 4, 0, 2, 2, 1}, true, gated);
     }
-    int rc;
-    if (nob == 4)
-      rc = p.q_pos ? pcr_launch_lds<attn_apply_stream64_kernel<true, 4, 0, 4>>(gg, bb, aps_lds, st, a)
-                   : pcr_launch_lds<attn_apply_stream64_kernel<false, 4, 0, 4>>(gg, bb, aps_lds, st, a);
-    else if (p.c1 < 16) rc = pcr_launch_lds<attn_apply_stream64_kernel<false, 1, 2, 1>>(gg, bb, aps_lds, st, a);
-    else if (p.c1 == 32)
-      rc = cf ? pcr_launch_lds<attn_apply_stream64_kernel<false, 2, 4>>(gg, bb, aps_lds, st, a)
-              : pcr_launch_lds<attn_apply_stream64_kernel<false, 2, 0>>(gg, bb, aps_lds, st, a);
-    else if (p.q_pos)
-      rc = cf ? attn_launch_g<attn_apply_stream64_kernel<true, 4, 4>, attn_apply_stream64_kernel<true, 4, 4, 2, 2, false, true>>(gg, bb, aps_lds, st, a)
-              : attn_launch_g<attn_apply_stream64_kernel<true, 4, 0>, attn_apply_stream64_kernel<true, 4, 0, 2, 2, false, true>>(gg, bb, aps_lds, st, a);
-    else
-      rc = cf ? attn_launch_g<attn_apply_stream64_kernel<false, 4, 4>, attn_apply_stream64_kernel<false, 4, 4, 2, 2, false, true>>(gg, bb, aps_lds, st, a)
-              : attn_launch_g<attn_apply_stream64_kernel<false, 4, 0>, attn_apply_stream64_kernel<false, 4, 0, 2, 2, false, true>>(gg, bb, aps_lds, st, a);
-    if (aptrace) attn_dump_trace(aptrace, "apply64", (int)gg.x, (int)p.B, p.Lq);
-    return rc;
+    attn_plan_persistent(pl, nitem, kApsWaves, 1, 64 * kApsWaves, aps_lds);
+    if (p.cout == 128) return attn_plan_form(pl, PCR_ATTN_APPLY_STREAM64, {p.q_pos != 0, 4, 0, 4, 2, 0}, false, gated);
+    if (p.c1 < 16) return attn_plan_form(pl, PCR_ATTN_APPLY_STREAM64, {0, 1, 2, 1, 2, 0}, false, gated);
+    if (p.c1 == 32) return attn_plan_form(pl, PCR_ATTN_APPLY_STREAM64, {0, 2, cf, 2, 2, 0}, false, gated);
+    return attn_plan_form(pl, PCR_ATTN_APPLY_STREAM64, {p.q_pos != 0, 4, cf, 2, 2, 0}, true, gated);   // the matching stages'
   }
 #endif
+  attn_plan_grid(pl, (p.Lq + T - 1) / T, p.B, lds);
   const bool wide = 2 * p.d > 128 || p.cout > 128 || p.cfinal > 128;   // some layer has > 4 cout blocks
-  if (tb == 4 && !live)
-    return wide ? pcr_launch_lds<attn_apply_kernel<4, 2>>(g, blk, lds, st, a) : pcr_launch_lds<attn_apply_kernel<4, 1>>(g, blk, lds, st, a);
-  if (tb == 2)
-    return wide ? attn_launch_g<attn_apply_kernel<2, 2>, attn_apply_kernel<2, 2, true>>(g, blk, lds, st, a)
-                : attn_launch_g<attn_apply_kernel<2, 1>, attn_apply_kernel<2, 1, true>>(g, blk, lds, st, a);
-  if (live) return PCR_ERR_INVALID;
+  if (tb == 4) return attn_plan_form(pl, PCR_ATTN_APPLY_TILE, {4, wide ? 2 : 1}, false, gated);
+  if (tb == 2) return attn_plan_form(pl, PCR_ATTN_APPLY_TILE, {2, wide ? 2 : 1}, true, gated);
   // cout blocks of the widest layer: up to 8 -> two rounds per wave, up to 16 -> four, up to 32 (d_model 512) -> eight
   int widest = 2 * p.d > p.cout ? 2 * p.d : p.cout;
   if (p.cfinal > widest) widest = p.cfinal;
-#if PCR_ATTN_PREC == 0
-  if (widest > 512) return pcr_launch_lds<attn_apply_kernel<1, 8>>(g, blk, lds, st, a);
-  if (widest > 256) return pcr_launch_lds<attn_apply_kernel<1, 4>>(g, blk, lds, st, a);
-#else
-  if (widest > 256) return PCR_ERR_INVALID;
+  if (kAPrec != 0 && widest > 256) return PCR_ERR_INVALID;   // (the bf16 unit holds two rounds only)
+  return attn_plan_form(pl, PCR_ATTN_APPLY_TILE, {1, widest > 512 ? 8 : (widest > 256 ? 4 : 2)}, false, gated);
+}
+
+// ---- one launcher per family: every kernel instantiation is named here and nowhere else, its gated twin beside it -----------
+static dim3 attn_grid(const AttnPlan &pl) {
+  if (!pl.persistent) return dim3(pl.gx, pl.gy);
+  const long cap = (long)pl.per_cu * pcr_cu_count();
+  return dim3((unsigned)(pl.work < cap ? pl.work : cap));
+}
+// KERN, or its gated twin when the plan says so
+template <auto KERN, auto KERN_LIVE>
+static inline int attn_launch_g(const AttnPlan &pl, dim3 grid, hipStream_t st, const AttnArgs &a) {
+  return pl.gated ? pcr_launch_lds<KERN_LIVE>(grid, dim3(pl.threads), pl.lds, st, a)
+                  : pcr_launch_lds<KERN>(grid, dim3(pl.threads), pl.lds, st, a);
+}
+
+// attn_kv_kernel<TB, NR, WSEL, NTW>
+static int attn_launch_kv_tile(const AttnPlan &pl, const AttnArgs &a, hipStream_t st) {
+  const dim3 g = attn_grid(pl), blk(pl.threads);
+  if (pl.targ[0] == 2) return pcr_launch_lds<attn_kv_kernel<2, 1, 2, 1>>(g, blk, pl.lds, st, a);
+  return pcr_launch_lds<attn_kv_kernel<1, 2, 0, 4>>(g, blk, pl.lds, st, a);
+}
+// attn_kv_kernel_o3<TB, NR, WSEL, NTW> / attn_kv_kernel_o3_live
+static int attn_launch_kv_tile_o3(const AttnPlan &pl, const AttnArgs &a, hipStream_t st) {
+  return attn_launch_g<attn_kv_kernel_o3<2, 1, 1, 1>, attn_kv_kernel_o3_live<2, 1, 1, 1>>(pl, attn_grid(pl), st, a);
+}
+// attn_kv_kernel_o2<TB, NR, WSEL, NTW, BFP>
+static int attn_launch_kv_tile_o2(const AttnPlan &pl, const AttnArgs &a, hipStream_t st) {
+  const dim3 g = attn_grid(pl), blk(pl.threads);
+  if (pl.targ[4]) return pcr_launch_lds<attn_kv_kernel_o2<1, 2, 1, 4, true>>(g, blk, pl.lds, st, a);
+  return pcr_launch_lds<attn_kv_kernel_o2<1, 2, 1, 4>>(g, blk, pl.lds, st, a);
+}
+// attn_kv_stream64_kernel<DIAG, BF, XS, ONEW, GATE>
+template <bool DIAG>
+static int attn_launch_kv_stream64(const AttnPlan &pl, const AttnArgs &a, const AttnTune &t, hipStream_t st) {
+  const dim3 g = attn_grid(pl);
+  int rc = PCR_ERR_INVALID;
+  if (!pl.targ[1])
+    rc = attn_launch_g<attn_kv_stream64_kernel<DIAG, false>, attn_kv_stream64_kernel<DIAG, false, 4, false, true>>(pl, g, st, a);
+#if PCR_ATTN_PREC != 0
+  else if (pl.targ[2] == 8) rc = pcr_launch_lds<attn_kv_stream64_kernel<DIAG, true, 8>>(g, dim3(pl.threads), pl.lds, st, a);
+  else if (pl.targ[3])
+    rc = attn_launch_g<attn_kv_stream64_kernel<DIAG, true, 4, true>, attn_kv_stream64_kernel<DIAG, true, 4, true, true>>(pl, g, st, a);
+  else rc = attn_launch_g<attn_kv_stream64_kernel<DIAG, true>, attn_kv_stream64_kernel<DIAG, true, 4, false, true>>(pl, g, st, a);
 #endif
-  return pcr_launch_lds<attn_apply_kernel<1, 2>>(g, blk, lds, st, a);
+  if (pl.trace) attn_dump_trace(t.trace, "kv64", (int)g.x, (int)a.p.B, a.p.Sk);
+  return rc;
+}
+#if PCR_ATTN_PREC != 0
+static int attn_launch_kv_stream32(const AttnPlan &pl, const AttnArgs &a, hipStream_t st) {
+  return pcr_launch_lds<attn_kv_stream32_kernel>(attn_grid(pl), dim3(pl.threads), pl.lds, st, a);
+}
+// attn_kv_stream128_kernel<NH>
+static int attn_launch_kv_stream128(const AttnPlan &pl, const AttnArgs &a, hipStream_t st) {
+  const dim3 g = attn_grid(pl), blk(pl.threads);
+  if (pl.targ[0] == 2) return pcr_launch_lds<attn_kv_stream128_kernel<2>>(g, blk, pl.lds, st, a);
+  return pcr_launch_lds<attn_kv_stream128_kernel<4>>(g, blk, pl.lds, st, a);
+}
+#else
+// attn_kv_wide_kernel<NRW>
+static int attn_launch_kv_wide(const AttnPlan &pl, const AttnArgs &a, hipStream_t st) {
+  const dim3 g = attn_grid(pl), blk(pl.threads);
+  if (pl.targ[0] == 2) return pcr_launch_lds<attn_kv_wide_kernel<2>>(g, blk, pl.lds, st, a);
+  return pcr_launch_lds<attn_kv_wide_kernel<3>>(g, blk, pl.lds, st, a);
+}
+#endif
+
+static int attn_launch_kv(const AttnPlan &pl, AttnArgs &a, const AttnTune &t, hipStream_t st) {
+  int rc = PCR_ERR_INVALID;
+  if (pl.family != PCR_ATTN_KV_WIDE) a.p.kv_splits = pl.splits;
+  switch (pl.family) {
+    case PCR_ATTN_KV_TILE: rc = attn_launch_kv_tile(pl, a, st); break;
+    case PCR_ATTN_KV_TILE_O3: rc = attn_launch_kv_tile_o3(pl, a, st); break;
+    case PCR_ATTN_KV_TILE_O2: rc = attn_launch_kv_tile_o2(pl, a, st); break;
+    case PCR_ATTN_KV_STREAM64:
+      return pl.targ[0] ? attn_launch_kv_stream64<true>(pl, a, t, st) : attn_launch_kv_stream64<false>(pl, a, t, st);
+#if PCR_ATTN_PREC != 0
+    case PCR_ATTN_KV_STREAM32: return attn_launch_kv_stream32(pl, a, st);
+    case PCR_ATTN_KV_STREAM128: return attn_launch_kv_stream128(pl, a, st);
+#else
+    case PCR_ATTN_KV_WIDE: return attn_launch_kv_wide(pl, a, st);
+#endif
+    default: return PCR_ERR_INVALID;
+  }
+  if (rc != PCR_OK || !pl.fold) return rc;
+  return pcr_launch_lds<attn_kv_fold_kernel>(dim3(a.p.B), dim3(pl.threads), pl.fold_lds, st, a);
+}
+
+// attn_apply_kernel<TB, NR, GATE>
+static int attn_launch_apply_tile(const AttnPlan &pl, const AttnArgs &a, hipStream_t st) {
+  const dim3 g = attn_grid(pl), blk(pl.threads);
+  switch (pl.targ[0] * 10 + pl.targ[1]) {
+    case 41: return pcr_launch_lds<attn_apply_kernel<4, 1>>(g, blk, pl.lds, st, a);
+    case 42: return pcr_launch_lds<attn_apply_kernel<4, 2>>(g, blk, pl.lds, st, a);
+    case 21: return attn_launch_g<attn_apply_kernel<2, 1>, attn_apply_kernel<2, 1, true>>(pl, g, st, a);
+    case 22: return attn_launch_g<attn_apply_kernel<2, 2>, attn_apply_kernel<2, 2, true>>(pl, g, st, a);
+    case 12: return pcr_launch_lds<attn_apply_kernel<1, 2>>(g, blk, pl.lds, st, a);
+#if PCR_ATTN_PREC == 0
+    case 14: return pcr_launch_lds<attn_apply_kernel<1, 4>>(g, blk, pl.lds, st, a);
+    case 18: return pcr_launch_lds<attn_apply_kernel<1, 8>>(g, blk, pl.lds, st, a);
+#endif
+    default: return PCR_ERR_INVALID;
+  }
+}
+#if PCR_ATTN_PREC != 0
+// attn_apply_stream64_kernel<QPOS, C1S, CF, NOB, ND, POOL, GATE>
+template <bool QPOS>
+static int attn_launch_apply_stream64(const AttnPlan &pl, const AttnArgs &a, const AttnTune &t, hipStream_t st) {
+  const dim3 g = attn_grid(pl), blk(pl.threads);
+  const int c1s = pl.targ[1], cf = pl.targ[2], nob = pl.targ[3], nd = pl.targ[4];
+  int rc = PCR_ERR_INVALID;
+  if (nd == 1) rc = pcr_launch_lds<attn_apply_stream64_kernel<QPOS, 2, 0, 1, 1>>(g, blk, pl.lds, st, a);
+  else if (nob == 4) rc = pcr_launch_lds<attn_apply_stream64_kernel<QPOS, 4, 0, 4>>(g, blk, pl.lds, st, a);
+  else if (c1s == 4 && cf && !pl.targ[5])
+    rc = attn_launch_g<attn_apply_stream64_kernel<QPOS, 4, 4>, attn_apply_stream64_kernel<QPOS, 4, 4, 2, 2, false, true>>(pl, g, st, a);
+  else if (c1s == 4 && !pl.targ[5])
+    rc = attn_launch_g<attn_apply_stream64_kernel<QPOS, 4, 0>, attn_apply_stream64_kernel<QPOS, 4, 0, 2, 2, false, true>>(pl, g, st, a);
+  else if constexpr (!QPOS) {
+    if (pl.targ[5])   // (the pooled form stamps with a trace file set, but has never dumped)
+      return attn_launch_g<attn_apply_stream64_kernel<false, 4, 0, 2, 2, true>, attn_apply_stream64_kernel<false, 4, 0, 2, 2, true, true>>(pl, g, st, a);
+    if (c1s == 1) rc = pcr_launch_lds<attn_apply_stream64_kernel<false, 1, 2, 1>>(g, blk, pl.lds, st, a);
+    else if (cf) rc = pcr_launch_lds<attn_apply_stream64_kernel<false, 2, 4>>(g, blk, pl.lds, st, a);
+    else rc = pcr_launch_lds<attn_apply_stream64_kernel<false, 2, 0>>(g, blk, pl.lds, st, a);
+  }
+  if (pl.trace) attn_dump_trace(t.trace, "apply64", (int)g.x, (int)a.p.B, a.p.Lq);
+  return rc;
+}
+// attn_apply_stream128_kernel<NH>
+static int attn_launch_apply_stream128(const AttnPlan &pl, const AttnArgs &a, hipStream_t st) {
+  const dim3 g = attn_grid(pl), blk(pl.threads);
+  if (pl.targ[0] == 1) return pcr_launch_lds<attn_apply_stream128_kernel<1>>(g, blk, pl.lds, st, a);
+  if (pl.targ[0] == 2) return pcr_launch_lds<attn_apply_stream128_kernel<2>>(g, blk, pl.lds, st, a);
+  return pcr_launch_lds<attn_apply_stream128_kernel<4>>(g, blk, pl.lds, st, a);
+}
+#endif
+
+static int attn_launch_apply(const AttnPlan &pl, const AttnArgs &a, const AttnTune &t, hipStream_t st) {
+  (void)t;
+  switch (pl.family) {
+    case PCR_ATTN_APPLY_TILE: return attn_launch_apply_tile(pl, a, st);
+#if PCR_ATTN_PREC != 0
+    case PCR_ATTN_APPLY_STREAM64:
+      return pl.targ[0] ? attn_launch_apply_stream64<true>(pl, a, t, st) : attn_launch_apply_stream64<false>(pl, a, t, st);
+    case PCR_ATTN_APPLY_STREAM128: return attn_launch_apply_stream128(pl, a, st);
+#endif
+    default: return PCR_ERR_INVALID;
+  }
+}
+
+// One unit: its plan, and the launch when one is asked for (pcr_attn_launch_form asks for none and leaves the device and
+// pcr_last_launch_arith alone).  live, when given, has passed attn_entry's checks.
+static int attn_unit(const pcr_attn_params &p, const pcr_live *live, bool apply, AttnPlan *pl, bool launch, pcr_stream_t stream) {
+  const AttnTune &t = attn_tune();
+  *pl = AttnPlan();
+  const int rc = apply ? attn_plan_apply(p, live != nullptr, t, pl) : attn_plan_kv(p, live != nullptr, t, pl);
+  if (!launch) return rc;
+  if (pl->arith >= 0) pcr_note_arith(pl->arith);
+  if (rc != PCR_OK) return rc;
+  AttnArgs a;
+  a.p = p;
+  a.dbg = pl->trace ? 256 : 0;
+  a.wpc = pl->wpc;
+  // gated launches (pcr_live): the caller's count, period and offset travel in AttnArgs
+  a.live_count = live ? live->count : nullptr;
+  a.live_period = live ? live->period : 0;
+  a.live_offset = live ? live->offset : 0;
+  return apply ? attn_launch_apply(*pl, a, t, pcr_s(stream)) : attn_launch_kv(*pl, a, t, pcr_s(stream));
 }
 
 #if PCR_ATTN_PREC == 1
 // (the caller -- attn_kernels.hip -- has validated the parameters and swapped the bf16 images into wq / wkv / ...)
-int pcr_attn_kv_bf3(const pcr_attn_params *pp, const pcr_live *live, pcr_stream_t stream) { return attn_kv_narrow(pp, live, stream); }
-int pcr_attn_apply_bf3(const pcr_attn_params *pp, const pcr_live *live, pcr_stream_t stream) { return attn_apply_launch(pp, live, stream); }
+int pcr_attn_kv_bf3(const pcr_attn_params *pp, const pcr_live *live, AttnPlan *pl, bool launch, pcr_stream_t stream) {
+  return attn_unit(*pp, live, false, pl, launch, stream);
+}
+int pcr_attn_apply_bf3(const pcr_attn_params *pp, const pcr_live *live, AttnPlan *pl, bool launch, pcr_stream_t stream) {
+  return attn_unit(*pp, live, true, pl, launch, stream);
+}
 #else
-int pcr_attn_kv_bf3(const pcr_attn_params *pp, const pcr_live *live, pcr_stream_t stream);      // attn_kernels_bf3.hip
-int pcr_attn_apply_bf3(const pcr_attn_params *pp, const pcr_live *live, pcr_stream_t stream);
+int pcr_attn_kv_bf3(const pcr_attn_params *pp, const pcr_live *live, AttnPlan *pl, bool launch, pcr_stream_t stream);      // attn_kernels_bf3.hip
+int pcr_attn_apply_bf3(const pcr_attn_params *pp, const pcr_live *live, AttnPlan *pl, bool launch, pcr_stream_t stream);
 
 // precision != f32, d_model <= 128 and bf16 images given: the same parameters with the images swapped in
 static bool attn_bf(const pcr_attn_params &p, pcr_attn_params &q) {
@@ -2499,62 +2657,66 @@ PCR_EXPORT int pcr_attn_kv_splits(int B, int Sk, int d) {
   return ntile >= 16 ? 4 : (ntile >= 8 ? 2 : 1);
 }
 
-static int attn_kv_entry(const pcr_attn_params *pp, const pcr_live *live, pcr_stream_t stream) {
-  if (!pp || attn_check(*pp)) return PCR_ERR_INVALID;
-  if (live && !attn_live_shape(*pp)) return PCR_ERR_INVALID;   // (never a silent un-gated launch)
-  if (pp->B == 0) return PCR_OK;
-  const int d = pp->d;
-  if (d > 128) {   // wide: d / 64 workgroups per cloud (attn_kv_wide_kernel)
-    AttnArgs a;
-    a.p = *pp;
-    a.dbg = 0;
-    a.wpc = 0;
-    if (!pp->wkv_wide || !pp->bkv_wide || !pp->wmerge_packed || pp->B > 65535) return PCR_ERR_INVALID;
-    pcr_note_arith(PCR_PREC_F32);
-    const int dh = d / pp->nhead;
-    size_t lds = ((size_t)(pp->c2 + d + 3) * 33 + 4 * d + kThreads) * sizeof(float);
-    const size_t lds2 = (size_t)dh * 65 * sizeof(float);
-    if (lds2 > lds) lds = lds2;
-    if (lds > (size_t)kMaxDynLds) return PCR_ERR_INVALID;
-    dim3 g(d / 64, pp->B), blk(kThreads);
-    if (64 + dh <= 256) return pcr_launch_lds<attn_kv_wide_kernel<2>>(g, blk, lds, pcr_s(stream), a);
-    return pcr_launch_lds<attn_kv_wide_kernel<3>>(g, blk, lds, pcr_s(stream), a);
-  }
-  pcr_attn_params q;
-  if (attn_bf(*pp, q)) return pcr_attn_kv_bf3(&q, live, stream);
-  return attn_kv_narrow(pp, live, stream);
-}
-
-PCR_EXPORT int pcr_attn_kv_f32(const pcr_attn_params *pp, pcr_stream_t stream) { return attn_kv_entry(pp, nullptr, stream); }
-PCR_EXPORT int pcr_attn_kv_live_f32(const pcr_attn_params *pp, const pcr_live *live, pcr_stream_t stream) {
-  return attn_kv_entry(pp, live, stream);
-}
-PCR_EXPORT int pcr_attn_live_ok(const pcr_attn_params *pp) {
-  return (pp && !attn_check(*pp) && attn_live_shape(*pp)) ? 1 : 0;
-}
-
 static bool attn_pool_ok(const pcr_attn_params &p) {
   pcr_attn_params q;
   return aps64_shape(p) && p.c1 == 64 && p.cout == 64 && !p.cfinal && !p.q_pos && attn_bf(p, q);
 }
 
+// Both launches and the form query: what is refused whichever unit would run it, the gate (checked HERE and nowhere else:
+// never a silent un-gated launch), then the unit -- the bf16 unit where attn_bf says so, else this one.
+static int attn_entry(const pcr_attn_params *pp, const pcr_live *live, bool apply, AttnPlan *pl, bool launch, pcr_stream_t stream) {
+  if (!pp || attn_check(*pp)) return PCR_ERR_INVALID;
+  if (apply && ((!pp->out && !pp->pool_out) || (pp->pool_out && !attn_pool_ok(*pp)))) return PCR_ERR_INVALID;
+  if (live && !attn_live_shape(*pp)) return PCR_ERR_INVALID;
+  if (launch && pp->B == 0) return PCR_OK;   // (the query reports the plan of an empty launch)
+  if (apply && pp->B > 65535) return PCR_ERR_INVALID;
+  if (live && (!live->count || live->period < 1 || live->offset < 0)) return PCR_ERR_INVALID;
+  pcr_attn_params q;
+  if (attn_bf(*pp, q)) return apply ? pcr_attn_apply_bf3(&q, live, pl, launch, stream) : pcr_attn_kv_bf3(&q, live, pl, launch, stream);
+  return attn_unit(*pp, live, apply, pl, launch, stream);
+}
+
+PCR_EXPORT int pcr_attn_kv_f32(const pcr_attn_params *pp, pcr_stream_t stream) {
+  AttnPlan pl;
+  return attn_entry(pp, nullptr, false, &pl, true, stream);
+}
+PCR_EXPORT int pcr_attn_kv_live_f32(const pcr_attn_params *pp, const pcr_live *live, pcr_stream_t stream) {
+  AttnPlan pl;
+  return attn_entry(pp, live, false, &pl, true, stream);
+}
+PCR_EXPORT int pcr_attn_apply_f32(const pcr_attn_params *pp, pcr_stream_t stream) {
+  AttnPlan pl;
+  return attn_entry(pp, nullptr, true, &pl, true, stream);
+}
+PCR_EXPORT int pcr_attn_apply_live_f32(const pcr_attn_params *pp, const pcr_live *live, pcr_stream_t stream) {
+  AttnPlan pl;
+  return attn_entry(pp, live, true, &pl, true, stream);
+}
+PCR_EXPORT int pcr_attn_live_ok(const pcr_attn_params *pp) {
+  return (pp && !attn_check(*pp) && attn_live_shape(*pp)) ? 1 : 0;
+}
 PCR_EXPORT int pcr_attn_apply_pool_ok(const pcr_attn_params *pp) {
   return (pp && !attn_check(*pp) && attn_pool_ok(*pp)) ? 1 : 0;
 }
 
-static int attn_apply_entry(const pcr_attn_params *pp, const pcr_live *live, pcr_stream_t stream) {
-  if (!pp || attn_check(*pp) || (!pp->out && !pp->pool_out)) return PCR_ERR_INVALID;
-  if (pp->pool_out && !attn_pool_ok(*pp)) return PCR_ERR_INVALID;
-  if (live && !attn_live_shape(*pp)) return PCR_ERR_INVALID;   // (never a silent un-gated launch)
-  if (pp->B == 0) return PCR_OK;
-  if (pp->B > 65535) return PCR_ERR_INVALID;
-  pcr_attn_params q;
-  if (attn_bf(*pp, q)) return pcr_attn_apply_bf3(&q, live, stream);
-  return attn_apply_launch(pp, live, stream);
-}
-
-PCR_EXPORT int pcr_attn_apply_f32(const pcr_attn_params *pp, pcr_stream_t stream) { return attn_apply_entry(pp, nullptr, stream); }
-PCR_EXPORT int pcr_attn_apply_live_f32(const pcr_attn_params *pp, const pcr_live *live, pcr_stream_t stream) {
-  return attn_apply_entry(pp, live, stream);
+PCR_EXPORT int pcr_attn_launch_form(const pcr_attn_params *pp, const pcr_live *live, int apply, int *form) {
+  if (!form) return PCR_ERR_INVALID;
+  AttnPlan pl;
+  const int rc = attn_entry(pp, live, apply != 0, &pl, false, nullptr);
+  if (rc != PCR_OK) return rc;
+  for (int i = 0; i < PCR_ATTN_FORM_INTS; i++) form[i] = 0;
+  form[0] = pl.arith;
+  form[1] = pl.family;
+  form[2] = pl.gated;
+  form[3] = pl.ntarg;
+  for (int i = 0; i < pl.ntarg; i++) form[4 + i] = pl.targ[i];
+  if (!apply) {
+    form[10] = pl.splits;
+    form[11] = pl.fold;
+    form[12] = pl.wpc;
+  }
+  form[13] = (int)pl.lds;
+  return PCR_OK;
 }
 #endif
+

@@ -314,6 +314,7 @@ SIGNATURES = {
     "pcr_attn_live_ok": "i <AttnParams>",
     "pcr_attn_kv_live_f32": "s <AttnParams><LiveParams>S",
     "pcr_attn_apply_live_f32": "s <AttnParams><LiveParams>S",
+    "pcr_attn_launch_form": "i <AttnParams><LiveParams>iI",
     "pcr_pool_head_f32": "s <HeadParams>S",
     "pcr_pool_head_live_f32": "s <HeadParams><LiveParams>FS",
     "pcr_pool_both_f32": "s FFiiiS",

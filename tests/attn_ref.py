@@ -10,7 +10,10 @@ every tensor is taken to float64 on entry.
 Every matrix product goes through ONE hook, mm(x, w) = x w^T (w (cout, cin) or a batch of them), exact float64 by
 default.  `split_mm` is the operand model of the split-bf16 mode: both operands as hi = bf16(x), lo = bf16(x - hi)
 (round to nearest even), y = x_hi w_hi + x_hi w_lo + x_lo w_hi accumulated in float64, the lo x lo term dropped.  The
-3-input first layer of the position MLP is never split (the kernels keep it in f32 fmaf chains)."""
+3-input first layer of the position MLP is never split (the kernels keep it in f32 fmaf chains).
+
+The second half restates WHICH KERNEL a block gets (`kv_form`, `apply_form`): the dispatch rules written from
+include/pcr.h and DESIGN.md 4.2, held to the library's own report (pcr_attn_launch_form) by tests/test_attn_ref_cpu.py."""
 import torch
 import torch.nn.functional as F
 
@@ -144,3 +147,224 @@ def cross_attention(sd, search, search_xyz, template, template_xyz, nhead=2, mm=
 def fp_sa(sd, feat1, xyz1, feat2, xyz2, nhead=2, final=None, mm=exact_mm, stages=None, **kw):
     """FP_SA: fine <- coarse, position encoding (pos_mlp2) on the values only, no residual, optional trailing conv"""
     return _block(sd, FLAGS["fp"][0], feat1, None, feat2, xyz2, nhead, *FLAGS["fp"][1:], mm, stages, final=final, **kw)
+
+
+# ---- which kernel a block gets: the dispatch rules restated from include/pcr.h (pcr_attn_params, pcr_live,
+# pcr_attn_launch_form) and DESIGN.md 4.2.  tests/test_attn_ref_cpu.py holds them to what the library itself reports. ------
+PREC_F32, PREC_BF16X3 = 0, 1
+MAX_DYN_LDS = 160 * 1024
+# pcr_attn_launch_form's families: kernel name, positions of the bool template arguments
+KERNELS = (("attn_kv_kernel", ()), ("attn_kv_kernel_o3", ()), ("attn_kv_kernel_o2", (4,)),
+           ("attn_kv_stream64_kernel", (0, 1, 3)), ("attn_kv_stream32_kernel", ()), ("attn_kv_stream128_kernel", ()),
+           ("attn_kv_wide_kernel", ()), ("attn_apply_kernel", ()), ("attn_apply_stream64_kernel", (0, 5)),
+           ("attn_apply_stream128_kernel", ()))
+(KV_TILE, KV_TILE_O3, KV_TILE_O2, KV_STREAM64, KV_STREAM32, KV_STREAM128, KV_WIDE, APPLY_TILE, APPLY_STREAM64,
+ APPLY_STREAM128) = range(10)
+BF_IMAGES = ("wq_bf", "wmlp0_bf", "wmlp2_bf", "wfinal_bf", "wkv_bf")
+WIDE_IMAGES = ("wkv_wide", "bkv_wide", "wmerge_packed")
+
+
+class Block:
+    """what the dispatch reads of a pcr_attn_params block: the shape, the asked precision and WHICH optional operands it
+    carries (`has`: names of the non-NULL ones among xyz_q, wfinal, bfinal, the WIDE_IMAGES, the BF_IMAGES, wmlp0_bf_xpad,
+    kv_part, out, pool_out; every other pointer is taken as given)"""
+    __slots__ = ("B", "Lq", "Sk", "c1", "c2", "d", "cout", "nhead", "q_pos", "residual", "cfinal", "kv_splits", "precision",
+                 "has")
+
+    def __init__(self, **kw):
+        self.B, self.Lq, self.Sk, self.kv_splits, self.precision = 3, 32, 32, 0, 0
+        self.q_pos = self.residual = self.cfinal = 0
+        self.has = frozenset(("out",))
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
+def images_of_plan(d, c1, c2, nhead, q_pos, cfinal):
+    """the optional operands engine.AttnPlan builds for a block of this shape (its __init__), `out` included"""
+    has = {"out"}
+    if q_pos:
+        has.add("xyz_q")
+    if cfinal:
+        has.update(("wfinal", "bfinal"))
+    if d <= 128:
+        if d % 32 == 0 and (d // nhead) % 32 == 0:
+            has.add("wmerge_packed")
+        if (d == 64 and c2 in (64, 128)) or (d == 32 and c2 == 32) or d == 128:
+            has.add("wkv_bf")
+        if d == 64 and c1 % 16:
+            has.add("wmlp0_bf_xpad")
+        has.update(("wq_bf", "wmlp0_bf", "wmlp2_bf"))
+        if cfinal:
+            has.add("wfinal_bf")
+    else:
+        has.update(WIDE_IMAGES)
+    return frozenset(has)
+
+
+def block_valid(b):
+    """pcr.h: d_model in {32, 64, 96, 128} or wide (heads of 64 n <= 256 channels); c2 % 8 == 0; q_pos requires xyz_q and
+    c1 == c2 == d; residual requires cout == c1; a trailing conv its weights and cout % 8 == 0; widths up to 512"""
+    if b.B < 0 or min(b.Lq, b.Sk, b.c1, b.c2, b.cout, b.nhead) < 1:
+        return False
+    if b.d < 32 or b.d > 512 or b.d % 32 or b.d % b.nhead:
+        return False
+    dh = b.d // b.nhead
+    if b.d > 128 and (b.d % 64 or dh % 64 or dh > 256):
+        return False
+    if b.c2 % 8 or b.cout > 512 or b.cfinal > 512:
+        return False
+    if b.q_pos and ("xyz_q" not in b.has or not b.c1 == b.c2 == b.d):
+        return False
+    if b.residual and b.cout != b.c1:
+        return False
+    if b.cfinal and ("wfinal" not in b.has or "bfinal" not in b.has or b.cout % 8):
+        return False
+    return True
+
+
+def bf_unit(b):
+    """pcr.h: precision != f32 and d <= 128 run the dense phases as split bf16 on the bf16 images -- where all of them are
+    given and no layer is wider than 256"""
+    return (b.precision != 0 and b.d <= 128 and max(2 * b.d, b.cout, b.cfinal) <= 256 and
+            all(k in b.has for k in ("wq_bf", "wmlp0_bf", "wmlp2_bf")) and (not b.cfinal or "wfinal_bf" in b.has))
+
+
+def live_ok(b):
+    """pcr_attn_live_ok: d = c1 = c2 = cout = 64 without kv_splits"""
+    return block_valid(b) and b.d == b.c1 == b.c2 == b.cout == 64 and b.kv_splits <= 1
+
+
+def _stream64_apply_shape(b):
+    """DESIGN.md 4.2, attn_apply_stream64_kernel at d = 64: (c1 = 64 | 32 | < 16 with the padded mlp[0] image) x
+    (cout = 64 [+ trailing conv to 128] | cout = 128 | cout = 32 + trailing conv to 64), whole 32-token blocks"""
+    plain = not b.q_pos and not b.residual
+    c_in = b.c1 == 64 or (plain and (b.c1 == 32 or (b.c1 < 16 and "wmlp0_bf_xpad" in b.has)))
+    c_out = ((b.cout == 64 and b.cfinal in (0, 128) and b.c1 >= 32) or
+             (b.cout == 128 and not b.cfinal and not b.residual and b.c1 == 64) or
+             (b.cout == 32 and b.cfinal == 64 and not b.residual and b.c1 < 16))
+    return b.d == 64 and c_in and c_out and b.Lq % 32 == 0 and b.nhead in (1, 2, 4)
+
+
+def pool_ok(b):
+    """pcr_attn_apply_pool_ok: the wave-autonomous d = c1 = cout = 64 form without q_pos / trailing conv, bf16 unit"""
+    return (block_valid(b) and _stream64_apply_shape(b) and b.c1 == 64 and b.cout == 64 and not b.cfinal and not b.q_pos
+            and bf_unit(b))
+
+
+def kv_tile_lds(b):
+    """dynamic LDS of the tile kv kernel: [feat_k ; h] and the projection in place, (c2 + d + 3) rows of a 64-token
+    (d <= 64) or 32-token tile + 4 d, or the fold buffer d (d + 1) + d if larger; + one float per thread"""
+    rp = 32 * (2 if b.d <= 64 else 1) + 1
+    return 4 * (max((b.c2 + b.d + 3) * rp + 4 * b.d, b.d * (b.d + 1) + b.d) + 256)
+
+
+def apply_tile_lds(b):
+    """dynamic LDS of the tile apply kernel: 128 / 64 / 32-token tiles for d <= 32 / <= 64 / wider"""
+    T = 32 * (4 if b.d <= 32 else (2 if b.d <= 64 else 1))
+    up = lambda x, m: (x + m - 1) // m * m      # noqa: E731
+    rows = max(up(b.c1 + b.d, 8), 2 * b.d, up(b.cout, 32), up(b.cfinal, 32))
+    return 4 * ((rows + 3 + b.nhead) * (T + 1) + 2 * (256 // T) * T + 7 * b.d + 2 * b.cout)
+
+
+def apply_stream64_lds(b):
+    """dynamic LDS of attn_apply_stream64_kernel: the bf16 weight images in 16-byte units (Q, mlp[0], mlp[2]) + scalars"""
+    c1s, nd = (b.c1 + 15) // 16, b.d // 32
+    units = (c1s + (2 * nd if b.q_pos else 0)) * nd * 128 + (c1s + 2 * nd) * nd * 256 + nd * (b.cout // 32) * 512
+    return units * 16 + (448 + 256 + 64 * 8) * 4
+
+
+def _form(arith, family, targs, twin, gated, splits=0, fold=0):
+    """(arithmetic noted, family, template arguments, gated, effective splits, fold follows); a gated launch of a family
+    without a gated twin is refused"""
+    if gated and not twin:
+        return None
+    return (arith, family, tuple(int(x) for x in targs), int(gated), splits, fold)
+
+
+def kv_form(b, gated=False):
+    """the kv launch of block b (pcr_attn_kv_f32; gated: pcr_attn_kv_live_f32) -> _form, or None where it is refused"""
+    if not block_valid(b) or (gated and not live_ok(b)):
+        return None
+    d, Sk, H = b.d, b.Sk, b.nhead
+    if d > 128:                                      # wide: d / 64 workgroups per cloud, f32
+        if not all(k in b.has for k in WIDE_IMAGES) or b.B > 65535:
+            return None
+        return _form(PREC_F32, KV_WIDE, (2 if 64 + d // H <= 256 else 3,), False, gated, 1, 0)
+    if b.c2 < d or kv_tile_lds(b) > MAX_DYN_LDS:     # (the tile kernel's LDS decides whichever kernel would run)
+        return None
+    ns = max(b.kv_splits, 1)
+    if ns > 1 and ("kv_part" not in b.has or ns > 64):
+        return None
+    ns = min(ns, -(-Sk // (64 if d <= 64 else 32)))  # at most one split per tile
+    bf = bf_unit(b)
+    bfk = bf and "wkv_bf" in b.has                   # split-bf16 projection
+    whole = ns == 1 and Sk % 32 == 0                 # the wave-autonomous forms: whole clouds of whole 32-token blocks
+    if whole and d == 64 and (b.c2 == 64 or (b.c2 == 128 and bfk and Sk >= 128)) and 64 % H == 0:
+        wide = b.c2 == 128
+        onew = bfk and not wide and Sk <= 128        # ONEW: one wave per cloud
+        return _form(PREC_BF16X3 if bfk else PREC_F32, KV_STREAM64, (H >= 2, bfk, 8 if wide else 4, onew), not wide, gated, 1, 0)
+    if whole and bfk and d == 32 and b.c2 == 32 and 32 % H == 0:
+        return _form(PREC_BF16X3, KV_STREAM32, (), False, gated, 1, 0)
+    if whole and bfk and d == 128 and b.c2 == 128 and Sk >= 256 and H in (2, 4):
+        return _form(PREC_BF16X3, KV_STREAM128, (H,), False, gated, 1, 0)
+    fold = int(ns > 1)                               # the tile kernels project in f32 in both units
+    if d == 32:
+        return _form(PREC_F32, KV_TILE, (2, 1, 2, 1), False, gated, ns, fold)
+    if d == 64:
+        return _form(PREC_F32, KV_TILE_O3, (2, 1, 1, 1), ns == 1, gated, ns, fold)
+    if d == 128:
+        return _form(PREC_F32, KV_TILE_O2, (1, 2, 1, 4, bfk and Sk >= 256), False, gated, ns, fold)
+    return _form(PREC_F32, KV_TILE, (1, 2, 0, 4), False, gated, ns, fold)
+
+
+def apply_form(b, gated=False):
+    """the apply launch of block b (pcr_attn_apply_f32 / _live_f32; pooled where b carries pool_out) -> _form or None"""
+    if not block_valid(b) or not ({"out", "pool_out"} & b.has):
+        return None
+    pooled = "pool_out" in b.has
+    if (pooled and not pool_ok(b)) or (gated and not live_ok(b)) or b.B > 65535:
+        return None
+    if apply_tile_lds(b) > MAX_DYN_LDS:              # (the tile kernel's LDS decides whichever kernel would run)
+        return None
+    d, H, bf = b.d, b.nhead, bf_unit(b)
+    arith = PREC_BF16X3 if bf else PREC_F32          # (the bf16 unit is split bf16 whatever was requested)
+    if bf and b.Lq % 32 == 0:
+        if d == b.c1 == b.cout == 128 and not b.cfinal and b.q_pos and b.residual and b.Lq >= 256 and H in (1, 2, 4):
+            return _form(arith, APPLY_STREAM128, (H,), False, gated)
+        if d == b.c1 == b.cout == 32 and not b.cfinal and H in (1, 2):
+            return _form(arith, APPLY_STREAM64, (b.q_pos, 2, 0, 1, 1, 0), False, gated)
+        if _stream64_apply_shape(b) and apply_stream64_lds(b) <= MAX_DYN_LDS:
+            cf = 4 if b.cfinal else 0
+            if pooled:
+                return _form(arith, APPLY_STREAM64, (0, 4, 0, 2, 2, 1), True, gated)
+            if b.cout == 128:
+                return _form(arith, APPLY_STREAM64, (b.q_pos, 4, 0, 4, 2, 0), False, gated)
+            if b.c1 < 16:
+                return _form(arith, APPLY_STREAM64, (0, 1, 2, 1, 2, 0), False, gated)
+            return _form(arith, APPLY_STREAM64, (b.q_pos, b.c1 // 16, cf, 2, 2, 0), b.c1 == 64, gated)
+    wide = 2 * d > 128 or b.cout > 128 or b.cfinal > 128      # some layer has more than four 32-channel blocks
+    if d <= 32:
+        return _form(arith, APPLY_TILE, (4, 2 if wide else 1), False, gated)
+    if d <= 64:
+        return _form(arith, APPLY_TILE, (2, 2 if wide else 1), True, gated)
+    widest = max(2 * d, b.cout, b.cfinal)            # rounds per wave: 8 blocks -> 2, 16 -> 4, 32 -> 8
+    return _form(arith, APPLY_TILE, (1, 8 if widest > 512 else (4 if widest > 256 else 2)), False, gated)
+
+
+def kernel_name(form):
+    """a _form spelled as a kernel trace spells the instantiation, defaults filled in: `attn_kv_stream64_kernel<true, true,
+    4, true>`; the gated twin carries GATE = true as one more argument (`attn_kv_kernel_o3_live` for the o3 tile kernel)"""
+    _, family, targs, gated = form[:4]
+    name, bools = KERNELS[family]
+    args = [("true" if v else "false") if i in bools else str(v) for i, v in enumerate(targs)]
+    if gated and family == KV_TILE_O3:
+        name += "_live"
+    elif gated:
+        args.append("true")
+    return "%s<%s>" % (name, ", ".join(args)) if args else name
+
+
+def from_library(ints, apply):
+    """pcr_attn_launch_form's ints -> a _form"""
+    n = ints[3]
+    return (ints[0], ints[1], tuple(ints[4:4 + n]), ints[2], 0 if apply else ints[10], 0 if apply else ints[11])

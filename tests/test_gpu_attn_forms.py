@@ -10,42 +10,15 @@ folded weights, another accumulation order, hardware exp / rsqrt).  bf16x3 mode,
 2 ysplit + 4 y32) -- 2 for the spread of a maximum over ~1e4 elements and for kernels that split fewer phases than the
 model (the tile kv kernel projects in f32).  No bound is read off a kernel.
 
-Also, per row: a second run is bit-equal; the first and the last cloud alone give the bits they give in the batch; after
-the kv launch pcr_last_launch_arith() says f32 where the tile kv form ran and bf16x3 where a wave-autonomous form with a
-split projection ran (`kv_family` restates the dispatcher's rule).  And the key-side state by itself: M and ksum are
+Also, per row: a second run is bit-equal; the first and the last cloud alone give the bits they give in the batch; the
+kernels the library reports (pcr_attn_launch_form) for the very blocks AttnPlan.kv / .apply launched are the row's entry
+of EXPECT below -- the map of rows to kernel instantiations, as data -- and after the kv launch pcr_last_launch_arith()
+says the arithmetic that report names.  And the key-side state by itself: M and ksum are
 unpacked from the kv launch's image (`unpack_state`) and held to attn_ref.kv_state by the same two yardsticks taken on M
 and ksum (`state_bounds`) -- norm1 cancels a uniform scale of M Q', so a wrong normaliser of the mean over the key tokens
 is invisible in the block's output and visible only here.
 
-Launch sites -> rows (`f32:` = what the row runs in f32 mode; otherwise bf16x3 mode).  attn_kv_narrow:
-  attn_kv_stream64_kernel<true|false, bf, 8> (c2 = 128)      fp-32-128-64-64-k128 / fp-32-128-64-64-h1
-  attn_kv_stream64_kernel<true|false, false> (f32 unit)      f32: self-d64-h2-L96, self-d64-h1-L64
-  attn_kv_stream64_kernel<.,bf,4,ONEW> (<= 4 blocks)          self-d64-h2-L96 / self-d64-h1-L64
-  attn_kv_stream64_kernel<.,bf> (several waves per cloud)    self-d64-h2-L160 / cross-d64-h1-32x160
-  attn_kv_stream32_kernel                                    self-d32-h1-L64, self-d32-h4-L64, cross-d32-96x256
-  attn_kv_stream128_kernel<2> / <4>                          self-d128-h2-L256 (wpc 1) / self-d128-h4-L512 (wpc 2)
-  attn_kv_kernel<2,1,2,1>                                    self-d32-h2-L45, self-d32-h2-L1; f32: every d = 32 row
-  attn_kv_kernel_o3<2,1,1,1>                                 self-d64-h2-L45, cross-d64-33x70, fp-32-128-64-64-k96
-  attn_kv_kernel_o2<1,2,1,4,true>                            self-d128-h1-L256, self-d128-h2-L270
-  attn_kv_kernel_o2<1,2,1,4>                                 self-d128-h2-L32, fp-64-256-128-128; f32: every d = 128 row
-  attn_kv_kernel<1,2,0,4>                                    self-d96-h2 (scalar merge), self-d96-h3 (packed merge image)
-  attn_kv_fold_kernel                                        test_token_split_is_held_to_the_same_bound
-attn_kv_entry:  attn_kv_wide_kernel<2>  self-d256-h2, self-d256-h4, self-d512-h4;  attn_kv_wide_kernel<3>  self-d512-h2
-attn_apply_launch:
-  attn_apply_stream128_kernel<1> / <2> / <4>                 self-d128-h1-L256 / -h2-L256 / -h4-L512
-  attn_apply_stream64_kernel<true,2,0,1,1> / <false,..>      self-d32-h1-L64 / cross-d32-96x256
-  attn_apply_stream64_kernel<false,4,0,2,2,true> (pooled)    test_pooled_forms, test_more_work_than_workgroups[cross]
-  attn_apply_stream64_kernel<false,4,0,4>                    fp-64-128-64-128
-  attn_apply_stream64_kernel<false,1,2,1>                    fp-3-64-64-32-f64, test_more_work_than_workgroups[fp]
-  attn_apply_stream64_kernel<false,2,4> / <false,2,0>        fp-32-128-64-64-f128 / fp-32-128-64-64-k128
-  attn_apply_stream64_kernel<true,4,0>                       self-d64-h2-L96 ...
-  attn_apply_stream64_kernel<false,4,4> / <false,4,0>        fp-64-64-64-64-f128 / cross-d64-h2-64x32, the indexed rows
-  attn_apply_kernel<4,1> / <4,2>                             self-d32-h4-L64, self-d32-h2-L45 / fp-32-32-32-160
-  attn_apply_kernel<2,1> / <2,2>                             self-d64-h2-L45, cross-gallery-L33 / fp-64-128-64-160
-  attn_apply_kernel<1,2>                                     the d = 96 rows, self-d128-h2-L270, cross-d128-h2-64x256
-  attn_apply_kernel<1,4> / <1,8>                             self-d256-* / self-d512-*
-  attn_apply_stream64_kernel<true,4,0,4> / <true,4,4>        fpq-64-64-64-128 / fpq-64-64-64-64-f128
-The gated twins (attn_launch_g's second argument) are held bit-equal to these by test_gpu_match_live.py.  The two `fpq`
+The gated twins (GATE = true) are held bit-equal to these by test_gpu_match_live.py.  The two `fpq`
 rows are forms no shipped module builds -- q_pos with cout = 128 or a trailing conv, while the only q_pos block,
 Self_Attention, has a residual (cout = c1 = d) and no conv -- so they go through engine.AttnPlan itself: an FP_SA's
 weights with q_pos = 1, the query features carrying pos_mlp2 of their own coordinates.
@@ -162,6 +135,92 @@ SCALE_CASES = ["self-d64-h2-L96", "self-d128-h2-L256", "fp-32-128-64-64-k128"]
 TWIN_CASES = ["self-d64-h2-L160", "fp-3-64-64-32-f64"]              # bf16 == bf16x3, bit for bit
 POOL_CASES = ["cross-reversed", "cross-gallery-L64"]
 MANY = {"self": _self(32, 2, 32, B=5), "cross": _cross(64, 2, 32, 32, B=5), "fp": _fp(3, 64, 64, 32, 32, 32, cfinal=64, B=5)}
+
+# ---- which kernels a row runs: row -> ((kv, apply) in f32 mode, (kv, apply) in bf16x3 mode), each spelled as a kernel
+# trace spells the instantiation (attn_ref.kernel_name).  The x16 rows (SCALE_CASES) and the B = 8 CUs + 3 rows (MANY) run
+# their row's kernels: the batch and the values never enter the choice.  tests/test_attn_ref_cpu.py holds every entry to
+# what the library reports for the row's block, and every instantiation the dispatch can reach to an entry here (or, for
+# the gated twins, in tests/test_gpu_match_live.py).  Compiled but out of reach, so in no row:
+#   attn_apply_stream64_kernel<true, 4, 0, 4, 2, false>   q_pos with cout = 128: its weight images need 168 704 bytes of
+#       LDS, 4 864 more than a workgroup can have, so `fpq-64-64-64-128` runs the tile kernel
+#   attn_apply_kernel<2, 2, true>   a gated block has cout = 64, and no shipped trailing conv is wider than 128
+#   attn_kv_kernel_o2<1, 2, 1, 4, true> of the f32 unit   BFP needs the bf16 unit's image
+_KT32, _KT96, _KO3 = "attn_kv_kernel<2, 1, 2, 1>", "attn_kv_kernel<1, 2, 0, 4>", "attn_kv_kernel_o3<2, 1, 1, 1>"
+_KO2, _KO2B = "attn_kv_kernel_o2<1, 2, 1, 4, false>", "attn_kv_kernel_o2<1, 2, 1, 4, true>"
+_KS_F1, _KS_F2 = "attn_kv_stream64_kernel<false, false, 4, false>", "attn_kv_stream64_kernel<true, false, 4, false>"
+_KS_1W1, _KS_1W2 = "attn_kv_stream64_kernel<false, true, 4, true>", "attn_kv_stream64_kernel<true, true, 4, true>"
+_KS_B1, _KS_B2 = "attn_kv_stream64_kernel<false, true, 4, false>", "attn_kv_stream64_kernel<true, true, 4, false>"
+_KS_X1, _KS_X2 = "attn_kv_stream64_kernel<false, true, 8, false>", "attn_kv_stream64_kernel<true, true, 8, false>"
+_K32, _K128_2, _K128_4 = "attn_kv_stream32_kernel", "attn_kv_stream128_kernel<2>", "attn_kv_stream128_kernel<4>"
+_KW2, _KW3 = "attn_kv_wide_kernel<2>", "attn_kv_wide_kernel<3>"
+_AT41, _AT42, _AT21, _AT22 = ("attn_apply_kernel<%s>" % a for a in ("4, 1", "4, 2", "2, 1", "2, 2"))
+_AT12, _AT14, _AT18 = ("attn_apply_kernel<%s>" % a for a in ("1, 2", "1, 4", "1, 8"))
+_AS32Q, _AS32 = "attn_apply_stream64_kernel<true, 2, 0, 1, 1, false>", "attn_apply_stream64_kernel<false, 2, 0, 1, 1, false>"
+_ASQ, _ASX = "attn_apply_stream64_kernel<true, 4, 0, 2, 2, false>", "attn_apply_stream64_kernel<false, 4, 0, 2, 2, false>"
+_ASQF, _ASXF = "attn_apply_stream64_kernel<true, 4, 4, 2, 2, false>", "attn_apply_stream64_kernel<false, 4, 4, 2, 2, false>"
+_ASH, _ASHF = "attn_apply_stream64_kernel<false, 2, 0, 2, 2, false>", "attn_apply_stream64_kernel<false, 2, 4, 2, 2, false>"
+_AS3, _ASW = "attn_apply_stream64_kernel<false, 1, 2, 1, 2, false>", "attn_apply_stream64_kernel<false, 4, 0, 4, 2, false>"
+_ASP = "attn_apply_stream64_kernel<false, 4, 0, 2, 2, true>"
+_A128 = {h: "attn_apply_stream128_kernel<%d>" % h for h in (1, 2, 4)}
+EXPECT = {
+    "self-d32-h1-L64": ((_KT32, _AT41), (_K32, _AS32Q)),
+    "self-d32-h4-L64": ((_KT32, _AT41), (_K32, _AT41)),
+    "self-d32-h2-L45": ((_KT32, _AT41), (_KT32, _AT41)),
+    "self-d32-h2-L1": ((_KT32, _AT41), (_KT32, _AT41)),
+    "self-d64-h2-L96": ((_KS_F2, _AT21), (_KS_1W2, _ASQ)),
+    "self-d64-h2-L160": ((_KS_F2, _AT21), (_KS_B2, _ASQ)),
+    "self-d64-h1-L64": ((_KS_F1, _AT21), (_KS_1W1, _ASQ)),
+    "self-d64-h4-L64": ((_KS_F2, _AT21), (_KS_1W2, _ASQ)),
+    "self-d64-h2-L45": ((_KO3, _AT21), (_KO3, _AT21)),
+    "self-d96-h2-L40": ((_KT96, _AT12), (_KT96, _AT12)),
+    "self-d96-h3-L40": ((_KT96, _AT12), (_KT96, _AT12)),
+    "self-d128-h2-L256": ((_KO2, _AT12), (_K128_2, _A128[2])),
+    "self-d128-h4-L512": ((_KO2, _AT12), (_K128_4, _A128[4])),
+    "self-d128-h1-L256": ((_KO2, _AT12), (_KO2B, _A128[1])),
+    "self-d128-h2-L270": ((_KO2, _AT12), (_KO2B, _AT12)),
+    "self-d128-h2-L32": ((_KO2, _AT12), (_KO2, _AT12)),
+    "self-d256-h2-L40": ((_KW2, _AT14), (_KW2, _AT14)),
+    "self-d256-h4-L40": ((_KW2, _AT14), (_KW2, _AT14)),
+    "self-d512-h2-L40": ((_KW3, _AT18), (_KW3, _AT18)),
+    "self-d512-h4-L40": ((_KW2, _AT18), (_KW2, _AT18)),
+    "cross-d64-h2-64x32": ((_KS_F2, _AT21), (_KS_1W2, _ASX)),
+    "cross-d64-h2-33x70": ((_KO3, _AT21), (_KO3, _AT21)),
+    "cross-d32-h2-96x256": ((_KT32, _AT41), (_K32, _AS32)),
+    "cross-d128-h2-64x256": ((_KO2, _AT12), (_K128_2, _AT12)),
+    "cross-d64-h2-32x1": ((_KO3, _AT21), (_KO3, _ASX)),
+    "cross-d64-h1-32x160": ((_KS_F1, _AT21), (_KS_B1, _ASX)),
+    "cross-reversed": ((_KS_F2, _AT21), (_KS_1W2, _ASX)),
+    "cross-gallery-L64": ((_KS_F2, _AT21), (_KS_1W2, _ASX)),
+    "cross-gallery-L33": ((_KS_F2, _AT21), (_KS_1W2, _AT21)),
+    "fp-3-64-64-32-f64": ((_KS_F2, _AT21), (_KS_1W2, _AS3)),
+    "fp-3-64-64-32-f64-ragged": ((_KS_F2, _AT21), (_KS_1W2, _AT21)),
+    "fp-3-64-64-32-f32": ((_KS_F2, _AT21), (_KS_1W2, _AT21)),
+    "fp-32-128-64-64-k128": ((_KO3, _AT21), (_KS_X2, _ASH)),
+    "fp-32-128-64-64-k96": ((_KO3, _AT21), (_KO3, _ASH)),
+    "fp-32-128-64-64-h1": ((_KO3, _AT21), (_KS_X1, _ASH)),
+    "fp-32-128-64-64-f128": ((_KO3, _AT21), (_KS_X2, _ASHF)),
+    "fp-64-128-64-128": ((_KO3, _AT21), (_KS_X2, _ASW)),
+    "fp-64-64-64-64-f128": ((_KS_F2, _AT21), (_KS_1W2, _ASXF)),
+    "fp-64-256-128-128": ((_KO2, _AT12), (_KO2, _AT12)),
+    "fp-3-128-128-64-f64": ((_KO2, _AT12), (_KO2, _AT12)),
+    "fp-32-32-32-160": ((_KT32, _AT42), (_KT32, _AT42)),
+    "fp-64-128-64-160": ((_KO3, _AT22), (_KO3, _AT22)),
+    "fpq-64-64-64-128": ((_KS_F2, _AT21), (_KS_1W2, _AT21)),
+    "fpq-64-64-64-64-f128": ((_KS_F2, _AT21), (_KS_1W2, _ASQF)),
+    # token split (attn_kv_fold_kernel follows the kv kernel), both counts
+    "fp-32-128-64-64-split[splits=2]": ((_KO3, _AT21), (_KO3, _ASH)),
+    "fp-32-128-64-64-split[splits=3]": ((_KO3, _AT21), (_KO3, _ASH)),
+    "cross-d64-h2-33x200[splits=2]": ((_KO3, _AT21), (_KO3, _AT21)),
+    "cross-d64-h2-33x200[splits=3]": ((_KO3, _AT21), (_KO3, _AT21)),
+    # pooled output (None: pcr_attn_apply_pool_ok says no and the launch is refused)
+    "cross-reversed[pooled]": ((_KS_F2, None), (_KS_1W2, _ASP)),
+    "cross-gallery-L64[pooled]": ((_KS_F2, None), (_KS_1W2, _ASP)),
+    "cross-d64-h2-32x32[pooled]": ((_KS_F2, None), (_KS_1W2, _ASP)),
+    # test_more_work_than_workgroups
+    "self-d32-h2-L32": ((_KT32, _AT41), (_K32, _AS32Q)),
+    "cross-d64-h2-32x32": ((_KS_F2, _AT21), (_KS_1W2, _ASX)),
+    "fp-3-64-64-32": ((_KS_F2, _AT21), (_KS_1W2, _AS3)),
+}
 
 
 # ------------------------------------------------------------------------------------------ CPU side --
@@ -333,20 +392,103 @@ def bound(y, case, prec):
     return min(1e-4, 2.0 * y.ysplit + 4.0 * y.y32)
 
 
-def kv_family(case, prec, splits=1):
-    """the dispatcher's kv rule restated: PCR_PREC_* that pcr_last_launch_arith() must report after the kv launch --
-    bf16x3 for the wave-autonomous forms with a split projection, f32 for the tile forms, the f32 unit and d > 128"""
-    _, c2, d, _ = case.dims
-    Sk, nh = case.Sk, case.nhead
-    if prec == "f32" or d > 128 or splits > 1 or Sk % 32:
-        return ARITH["f32"]
-    if d == 64 and (c2 == 64 or (c2 == 128 and Sk >= 128)) and 64 % nh == 0:
-        return ARITH["bf16x3"]
-    if d == 32 and c2 == 32 and 32 % nh == 0:
-        return ARITH["bf16x3"]
-    if d == 128 and c2 == 128 and Sk >= 256 and nh in (2, 4):
-        return ARITH["bf16x3"]
-    return ARITH["f32"]
+# ------------------------------------------------------------------------------- blocks and their forms --
+_DUMMY = 64         # any address that is not NULL: the queries read pointers against NULL only
+
+
+def host_plan(case, device="cpu"):
+    """engine.AttnPlan of the row, built on the CPU as the modules' plan() calls build it on the device"""
+    from pcr_amd import engine
+    m, conv = build_module(case)
+    pos_name, q_pos, k_pos, residual = FLAGS[case.kind]
+    return engine.AttnPlan(m, pos_name, torch.device(device), case.nhead, q_pos=q_pos, k_pos=k_pos, residual=residual,
+                           final=conv)
+
+
+def host_blocks(plan, case, prec, splits=None, pooled=False):
+    """-> (kv block, apply block): the parameter blocks AttnPlan.kv / .apply hand the library for the row, without a
+    device -- AttnPlan._params on empty tensors with a dummy address in every pointer the call would fill, as
+    AttnPlan.live_ok does.  splits: engine.KV_SPLITS (None: the library's suggestion)"""
+    from pcr_amd import _lib, engine
+    lib = _lib.load()
+    e = torch.empty(0)
+    nv = case.n_out if case.n_out is not None else case.B
+    with engine.precision(prec):
+        kv = plan._params(case.Bk or case.B, 1, case.Sk, e, e, e, e, e, e)
+        ap = plan._params(nv, case.Lq, case.Sk, e, e if plan.q_pos else None, e, e, e, None if pooled else e)
+    for p in (kv, ap):
+        p.feat_q = p.feat_k = p.xyz_k = p.kv = _DUMMY
+    kv.xyz_q = kv.out = ap.feat_k = ap.xyz_k = _DUMMY
+    ap.xyz_q = _DUMMY if plan.q_pos else None
+    ns = lib.pcr_attn_kv_splits(kv.B, case.Sk, plan.d) if splits is None else splits
+    if ns > 1:
+        kv.kv_splits, kv.kv_part = ns, _DUMMY
+    if pooled:
+        ap.pool_out = _DUMMY
+    else:
+        ap.out = _DUMMY
+    return kv, ap
+
+
+def reported(p, apply, live=None):
+    """the kernel pcr_attn_launch_form names for a block, spelled as a trace spells it (attn_ref.kernel_name), and the
+    arithmetic it would note; (None, None): the launch would be refused"""
+    import ctypes
+    from pcr_amd import _lib
+    form = (ctypes.c_int * 16)(*([-1] * 16))
+    status = _lib.load().pcr_attn_launch_form(ctypes.byref(p), live, int(apply), form)
+    if status != 0:
+        assert status == 1 and list(form) == [-1] * 16
+        return None, None
+    f = R.from_library(list(form), apply)
+    return R.kernel_name(f), f[0]
+
+
+class launched_blocks:
+    """with launched_blocks() as seen: every parameter block AttnPlan.kv / .apply build inside is kept, seen["kv"] and
+    seen["apply"] in launch order -- a wrapper around AttnPlan._params on the test's side; the engine's call path is as it was"""
+
+    def __enter__(self):
+        from pcr_amd import engine
+        self.real = {k: getattr(engine.AttnPlan, k) for k in ("_params", "kv", "apply")}
+        self.seen, side = {"kv": [], "apply": []}, []
+
+        def params(plan, *a, **kw):
+            p = self.real["_params"](plan, *a, **kw)
+            if side:
+                self.seen[side[-1]].append(p)
+            return p
+
+        def sided(name):
+            def call(plan, *a, **kw):
+                side.append(name)
+                try:
+                    return self.real[name](plan, *a, **kw)
+                finally:
+                    side.pop()
+            return call
+        engine.AttnPlan._params, engine.AttnPlan.kv, engine.AttnPlan.apply = params, sided("kv"), sided("apply")
+        return self.seen
+
+    def __exit__(self, *exc):
+        from pcr_amd import engine
+        for k, v in self.real.items():
+            setattr(engine.AttnPlan, k, v)
+
+
+def table_rows():
+    """(table key, case, mode, splits, pooled) of every entry of EXPECT in both modes"""
+    cases = dict(BY_NAME, **{c.name: c for c in SPLIT_CASES + list(MANY.values())})
+    for key in EXPECT:
+        name, _, what = key.partition("[")
+        splits = int(what[7:-1]) if what.startswith("splits=") else None
+        for prec in ("f32", "bf16x3"):
+            yield key, cases[name], prec, splits, what == "pooled]"
+
+
+def expect(name, prec, what=""):
+    """the table's (kv kernel, apply kernel) of a row in a mode; what: "[splits=2]" | "[pooled]" """
+    return EXPECT[name + what][0 if prec == "f32" else 1]
 
 
 # ------------------------------------------------------------------------------------------ GPU side --
@@ -406,6 +548,17 @@ def kv_arith(case, m, dev_args):
     return _lib.load().pcr_last_launch_arith()
 
 
+def check_forms(seen, kv_seen, arith, want, splits=None):
+    """the blocks a run launched (`seen`) and the block of the kv launch after which `arith` was read (`kv_seen`): the
+    library reports the table's kernels for them, and the arithmetic it reports for the kv block is the one noted"""
+    assert len(seen["kv"]) == 1 and len(seen["apply"]) == 1
+    assert (reported(seen["kv"][0], 0)[0], reported(seen["apply"][0], 1)[0]) == want
+    kernel, noted = reported(kv_seen["kv"][-1], 0)       # (kv_arith's own launch is the last one)
+    assert kernel == want[0] and arith == noted, (kernel, arith, noted)
+    if splits is not None:
+        assert kv_seen["kv"][-1].kv_splits == splits
+
+
 def check(case, prec, y, got, tag=""):
     err = float((got.double() - y.ref).abs().max())
     lim = bound(y, case, prec)
@@ -426,14 +579,16 @@ def test_launch_form_against_float64(name, prec):
     args = _dev(y.data)
     nv = case.n_out if case.n_out is not None else case.B
     with engine.precision(prec):
-        got = run(case, m, args)
+        with launched_blocks() as seen:
+            got = run(case, m, args)
         again = run(case, m, args)
         first, last = run(case, m, args, only=0), run(case, m, args, only=nv - 1)
-        arith = kv_arith(case, m, args)
+        with launched_blocks() as kv_seen:
+            arith = kv_arith(case, m, args)
     check(case, prec, y, got)
     assert torch.equal(got, again)                                      # fixed reduction orders
     assert torch.equal(first[0], got[0]) and torch.equal(last[0], got[nv - 1])
-    assert arith == kv_family(case, prec), (arith, kv_family(case, prec))
+    check_forms(seen, kv_seen, arith, expect(name, prec))
 
 
 @pytest.mark.gpu
@@ -493,7 +648,9 @@ def test_pooled_forms(name):
         assert ok == (name in POOL_CASES)
         if not ok:
             return
-        got = run(case, m, args, pooled=True)
+        with launched_blocks() as seen:
+            got = run(case, m, args, pooled=True)
+        assert (reported(seen["kv"][0], 0)[0], reported(seen["apply"][0], 1)[0]) == expect(name, "bf16x3", "[pooled]")
         again = run(case, m, args, pooled=True)
         nv = case.n_out if case.n_out is not None else case.B
         first, last = run(case, m, args, only=0, pooled=True), run(case, m, args, only=nv - 1, pooled=True)
@@ -522,11 +679,14 @@ def test_token_split_is_held_to_the_same_bound(case, prec):
         with engine.precision(prec):
             for ns in (2, 3):
                 engine.KV_SPLITS = ns
-                got, again = run(case, m, args), run(case, m, args)
-                arith = kv_arith(case, m, args)
+                with launched_blocks() as seen:
+                    got = run(case, m, args)
+                again = run(case, m, args)
+                with launched_blocks() as kv_seen:
+                    arith = kv_arith(case, m, args)
                 check(case, prec, y, got, tag="[splits=%d]" % ns)
                 assert torch.equal(got, again)
-                assert arith == kv_family(case, prec, splits=ns)
+                check_forms(seen, kv_seen, arith, expect(case.name, prec, "[splits=%d]" % ns), splits=ns)
     finally:
         engine.KV_SPLITS = prev
 
@@ -560,9 +720,13 @@ def test_more_work_than_workgroups(kind):
     args = _dev(y.data, rep)
     big = case._replace(B=B)
     with engine.precision("bf16x3"):
-        got = run(big, m, args)
+        with launched_blocks() as seen:
+            got = run(big, m, args)
+        assert (reported(seen["kv"][0], 0)[0], reported(seen["apply"][0], 1)[0]) == expect(case.name, "bf16x3")
         assert kv_arith(big, m, args) == ARITH["bf16x3"]
-        pooled = run(big, m, args, pooled=True) if kind == "cross" else None
+        with launched_blocks() as seen:
+            pooled = run(big, m, args, pooled=True) if kind == "cross" else None
+        assert kind != "cross" or reported(seen["apply"][0], 1)[0] == expect(case.name, "bf16x3", "[pooled]")[1]
     check(case, "bf16x3", y, got[:5], tag="[B=%d]" % B)
     assert torch.equal(got, got[:5][rep])
     if pooled is not None:

@@ -19,6 +19,8 @@ import torch
 from pcr_amd import _lib as L
 from pcr_amd import engine, testing as T
 
+import test_gpu_attn_forms as G
+
 pytestmark = pytest.mark.gpu
 
 PERIOD = 11
@@ -26,6 +28,36 @@ COUNTS = [0, 1, 5, 11, 12]
 OFFSETS = [0, 3]
 SENTINEL = -12345.0
 NOBJ = 6                      # real clouds; cloud NOBJ is the poison cloud
+
+
+# ---- which gated kernels run here, spelled as attn_ref.kernel_name spells a gated twin: (kv, apply, pooled apply or None).
+# tests/test_attn_ref_cpu.py holds every entry to what the library reports for the block, and every gated instantiation the
+# dispatch can reach to an entry.  GATED: (Ln, mode) of test_gated_attention_launches (corss_attention(64, 2)); TWINS:
+# (kind, heads, trailing conv, Ln, mode) of test_gated_twins_beyond_the_matching_stages, kinds as tests/test_gpu_attn_forms.py's.
+_KS_F, _KS_1W, _KS_B = ("attn_kv_stream64_kernel<%s, true>" % a for a in ("%s, false, 4, false", "%s, true, 4, true", "%s, true, 4, false"))
+_KO3_G, _AT_G = "attn_kv_kernel_o3_live<2, 1, 1, 1>", "attn_apply_kernel<2, 1, true>"
+_AS_G = "attn_apply_stream64_kernel<%s, 4, %d, 2, 2, %s, true>"
+_ASX_G, _ASP_G = _AS_G % ("false", 0, "false"), _AS_G % ("false", 0, "true")
+GATED = {
+    (32, "bf16x3"): (_KS_1W % "true", _ASX_G, _ASP_G), (128, "bf16x3"): (_KS_1W % "true", _ASX_G, _ASP_G),
+    (256, "bf16x3"): (_KS_B % "true", _ASX_G, _ASP_G), (48, "bf16x3"): (_KO3_G, _AT_G, None),
+    (32, "f32"): (_KS_F % "true", _AT_G, None), (128, "f32"): (_KS_F % "true", _AT_G, None),
+    (256, "f32"): (_KS_F % "true", _AT_G, None), (48, "f32"): (_KO3_G, _AT_G, None),
+}
+TWINS = {
+    ("cross", 1, 0, 32, "bf16x3"): (_KS_1W % "false", _ASX_G, None),
+    ("cross", 1, 0, 160, "bf16x3"): (_KS_B % "false", _ASX_G, None),
+    ("cross", 1, 0, 32, "f32"): (_KS_F % "false", _AT_G, None),
+    ("fpq", 2, 0, 32, "bf16x3"): (_KS_1W % "true", _AS_G % ("true", 0, "false"), None),
+    ("fpq", 2, 128, 32, "bf16x3"): (_KS_1W % "true", _AS_G % ("true", 4, "false"), None),
+    ("fp", 2, 128, 32, "bf16x3"): (_KS_1W % "true", _AS_G % ("false", 4, "false"), None),
+}
+
+
+def gated_case(kind, nhead, cfinal, Ln):
+    """the d = c1 = c2 = cout = 64 block of a GATED / TWINS row as a row of tests/test_gpu_attn_forms.py"""
+    import test_gpu_attn_forms as G
+    return G.Case("gated-%s-h%d-f%d-L%d" % (kind, nhead, cfinal, Ln), kind, (64, 64, 64, 64), nhead, 2 * PERIOD, Ln, Ln, cfinal)
 
 
 def live_pairs(count, offset, period=PERIOD):
@@ -107,6 +139,51 @@ def test_gated_attention_launches(cross_block, Ln, prec):
             assert torch.equal(got[alive], ref_pool[alive]) and bool((got[~alive] == 0).all())
         # live=None is the un-gated call
         assert torch.equal(plan.kv(featv, xyzv, live=None), ref_kv)
+        # the blocks of gated launches get the table's gated twins
+        live = (dev_count(5), PERIOD, 3)
+        with G.launched_blocks() as seen:
+            plan.kv(featv, xyzv, live=live, out=torch.full_like(ref_kv, SENTINEL))
+            plan.apply(feat, None, kv_obj, Ln, kv_index=k_idx, q_index=q_idx, n_out=B, live=live, out=torch.full_like(ref_out, SENTINEL))
+            if pooled:
+                plan.apply(feat, None, kv_obj, Ln, kv_index=k_idx, q_index=q_idx, n_out=B, pooled=True, live=live)
+        assert gated_kernels(seen, live) == GATED[Ln, prec]
+
+
+def gated_kernels(seen, live):
+    """(kv, apply, pooled apply or None) the library reports for the gated blocks in `seen` (launched_blocks)"""
+    lv = ctypes.byref(engine._live_block(live))
+    names = [G.reported(seen["kv"][0], 0, lv)[0]] + [G.reported(p, 1, lv)[0] for p in seen["apply"]]
+    return tuple(names + [None] * (3 - len(names)))
+
+
+@pytest.mark.parametrize("row", sorted(TWINS), ids=lambda r: "%s-h%d-f%d-L%d-%s" % r)
+def test_gated_twins_beyond_the_matching_stages(row):
+    """the gated instantiations the matching stages' corss_attention(64, 2) does not reach -- one head, q_pos, a trailing
+    conv -- through engine.AttnPlan itself: a live cloud gets the un-gated launch's bits, a dead cloud (NaN features) is
+    neither read nor written.  B = 22 clouds of 32 tokens (160: the multi-wave kv form)."""
+    kind, nhead, cfinal, Ln, prec = row
+    case = gated_case(kind, nhead, cfinal, Ln)
+    plan = G.host_plan(case, "cuda")
+    g = torch.Generator().manual_seed(2000 + Ln + nhead)
+    B = case.B
+    feat, xyz = torch.randn(B, 64, Ln, generator=g).cuda(), torch.randn(B, Ln, 3, generator=g).cuda()
+    xq = lambda x: x if plan.q_pos else None      # noqa: E731
+    with engine.precision(prec), torch.no_grad():
+        assert plan.live_ok()
+        ref_kv = plan.kv(feat, xyz)
+        ref_out = plan.apply(feat, xq(xyz), ref_kv, Ln)
+        assert not torch.isnan(ref_kv).any() and not torch.isnan(ref_out).any()
+        for count, offset in ((5, 3), (12, 0), (0, 0)):
+            what = "%s count=%d offset=%d" % (case.name, count, offset)
+            alive, live = live_mask(count, offset, B), (dev_count(count), PERIOD, offset)
+            fv, xv = feat.clone(), xyz.clone()
+            fv[~alive], xv[~alive] = float("nan"), float("nan")
+            with G.launched_blocks() as seen:
+                got = plan.kv(fv, xv, live=live, out=torch.full_like(ref_kv, SENTINEL))
+                assert_gated(got, ref_kv, alive, what + " kv")
+                got = plan.apply(fv, xq(xv), ref_kv, Ln, live=live, out=torch.full_like(ref_out, SENTINEL))
+                assert_gated(got, ref_out, alive, what + " apply")
+            assert gated_kernels(seen, live) == TWINS[row]
 
 
 # ---- 2. head --------------------------------------------------------------------------------------------------------------

@@ -8,7 +8,7 @@ device assembly with the build's own flags for that file (pcr_amd.build.compile_
 two compiles of an unchanged file; the include directory's path does not enter the text.  One verdict per file, the first
 differing kernel where two files differ; exit status 1 on any difference, added and removed files included.
 
-The three set-abstraction units (BY_SYMBOL) instantiate their kernels from host code, and the compiler emits templates in the
+The set-abstraction and attention units (BY_SYMBOL) instantiate their kernels from host code, and the compiler emits templates in the
 order the host code first names them: a change of the dispatcher alone reorders the text.  Where the texts of one of those
 files differ, it is compared symbol by symbol instead: the same set of function symbols, each body identical once the
 function-index numbers in local labels (.LBB12_3, .Lfunc_end12) and the comments are taken out, each kernel's
@@ -32,7 +32,7 @@ def assemble(src, root, out):
     return open(out).read()
 
 
-BY_SYMBOL = ("sa_kernels.hip", "sa_kernels_bf1.hip", "sa_kernels_bf3.hip")
+BY_SYMBOL = ("sa_kernels.hip", "sa_kernels_bf1.hip", "sa_kernels_bf3.hip", "attn_kernels.hip", "attn_kernels_bf3.hip")
 
 
 def symbols(text):

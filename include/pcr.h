@@ -1152,6 +1152,83 @@ int pcr_rank_scatter_f32(const float *logits, const int *pairs, const int *count
                          int col0, int width, pcr_stream_t stream);
 int pcr_rank_wide_f32(const pcr_rank *p, pcr_stream_t stream);
 
+/* ------------------------------------------------------------ A13. scoring a validation split -------- */
+
+/* `val_match_acc` and the reference's MatchingEval tables (datasets/reidentification_base.py:87-199, datasets/utils.py:
+ * 254-533) kept as ONE table of 64-bit integer counters on the device (additive to ABI 17): a batch of validation pairs is
+ * added by one fixed-shape launch without a host read, an allocation or a float accumulate.  Every add is an integer
+ * atomic (32-bit in LDS, 64-bit in memory), so the table does not depend on the order of the adds and is the same bits on
+ * every run.  The result is DEFINED by the rules below (tests/match_ref.py restates them; the kernels equal it bit for bit).
+ * Pointers are checked against NULL only.  pcr_match_ok: 0 <= P, M <= PCR_MATCH_MAX_ROWS, 1 <= C <= PCR_MATCH_MAX_CLASSES.
+ *
+ * pcr_match_record_i64.  Row i is one pair: logit[i], gt[i] (float), cls[i][2], num_points[i][2], vis[i][2] (int32).
+ *   rows      count (1, device) or NULL: only the rows i < clamp(count[0], 0, P) take part; NULL = all P.  A row beyond
+ *             the count reads nothing and contributes nothing.
+ *   gt        g = 0 for gt == 1, 1 for gt == 0, 2 for gt == -1 (a pair with a false-positive detection).  Any other value,
+ *             a NaN included: info |= PCR_MATCH_INFO_GT and the row contributes nothing.
+ *   decision  pred = logit > 0 (the float compare).  A NaN logit gives pred = 0 and info |= PCR_MATCH_INFO_NAN.  This is
+ *             the rule of the training log (ReIDNet._log_match); `sigmoid(logit) > 0.5` evaluated in binary32, the host
+ *             route's, differs from it for logits in about (0, 2e-7], where the sigmoid rounds to 0.5.
+ *   cell      c = 2 g + pred, 0 <= c < PCR_MATCH_CELLS; a subset key k owns the counters table[base + k * 6 + c].
+ *   ALL       key 0: every row.
+ *   CLS0      key cls[i][0] + 1;  CLSMAX  key max(cls[i][0], cls[i][1]) + 1.  Both values must lie in [-1, 62];
+ *             otherwise info |= PCR_MATCH_INFO_CLS and the row is left out of both tables.
+ *   PTS       key 32 * bin(lo) + bin(hi), lo / hi the smaller / larger of num_points[i]; bin(0) = 0, bin(n) = 1 +
+ *             floor(log2 n) for n >= 1 (31 for 2^31 - 1).  A negative value: info |= PCR_MATCH_INFO_PTS, left out.
+ *   VIS       key 64 * (lo + 1) + (hi + 1), lo / hi the smaller / larger of vis[i].  Both values must lie in [-1, 62];
+ *             otherwise info |= PCR_MATCH_INFO_VIS, left out.  (The reference feeds its distance and its visibility
+ *             table from this one column; 5-unit distance buckets are sums over the raw values.)
+ * The launch: workgroups of 256 rows-at-a-time threads, strided over the rows; ALL, CLS0, CLSMAX and PTS are counted in an
+ * LDS histogram and the non-zero counters added to the table once per workgroup; VIS is added in memory directly.
+ * Nothing to do: P == 0.
+ *
+ * pcr_match_record_objects_i64: the per-object heads.  Object m is counted iff count == NULL or
+ * (m % period) < clamp(count[0], 0, period): the M = 2 b objects of b pairs, side 1 then side 2, with period = b follow
+ * the pairs' count; period = M is a flat list.  objects (PCR_MATCH_OBJECTS counters, usually table + PCR_MATCH_OBJ):
+ *   cls       (cls_logits (M,C) and cls_gt (M) both given) CLS_TOTAL += 1; CLS_CORRECT += 1 iff the argmax of the row --
+ *             the LOWEST index of the largest value, a NaN being larger than any number, as torch.argmax -- equals cls_gt[m].
+ *             A NaN in the row: info |= PCR_MATCH_INFO_NAN.
+ *   fp        (fp_logits (M) and fp_gt (M) both given) FP_TOTAL += 1; FP_CORRECT += 1 iff (fp_logits[m] > 0 ? 1.0f : 0.0f)
+ *             == fp_gt[m].  A NaN logit: pred 0 and info |= PCR_MATCH_INFO_NAN.
+ * Nothing to do: M == 0, or neither head given.
+ * (The block is a tagged struct followed by its typedef, as in A10; the layout is the plain C one.) */
+#define PCR_MATCH_MAX_ROWS 1073741824                        /* 2^30 */
+#define PCR_MATCH_MAX_CLASSES 4096
+#define PCR_MATCH_CELLS 6
+#define PCR_MATCH_KEY_BINS 64                                /* cls and vis values -1 .. 62 */
+#define PCR_MATCH_PTS_BINS 32
+#define PCR_MATCH_ALL 0                                      /* bases, in counters */
+#define PCR_MATCH_CLS0 6
+#define PCR_MATCH_CLSMAX 390
+#define PCR_MATCH_PTS 774
+#define PCR_MATCH_VIS 6918
+#define PCR_MATCH_OBJ 31494
+#define PCR_MATCH_OBJECTS 4
+#define PCR_MATCH_CLS_CORRECT 0
+#define PCR_MATCH_CLS_TOTAL 1
+#define PCR_MATCH_FP_CORRECT 2
+#define PCR_MATCH_FP_TOTAL 3
+#define PCR_MATCH_TABLE 31498
+#define PCR_MATCH_INFO_NAN 1
+#define PCR_MATCH_INFO_GT 2
+#define PCR_MATCH_INFO_CLS 4
+#define PCR_MATCH_INFO_PTS 8
+#define PCR_MATCH_INFO_VIS 16
+struct pcr_match {
+  int P;
+  const float *logit, *gt;                                   /* (P) */
+  const int *cls, *num_points, *vis;                         /* (P,2) */
+  const int *count;                                          /* (1) device, or NULL */
+  long long *table;                                          /* (PCR_MATCH_TABLE), added to */
+  int *info;                                                 /* (1), or-ed into */
+};
+typedef struct pcr_match pcr_match;
+int pcr_match_ok(int P, int M, int C);
+int pcr_match_record_i64(const pcr_match *p, pcr_stream_t stream);
+int pcr_match_record_objects_i64(const float *cls_logits, const int *cls_gt, const float *fp_logits, const float *fp_gt,
+                                 const int *count, long long *objects, int *info, int M, int C, int period,
+                                 pcr_stream_t stream);
+
 /* ------------------------------------------------- B. fused model kernels ------------ */
 
 /* Neighbour search of the "Point-Transformer" set-abstraction layers: centres are the first S

@@ -872,6 +872,36 @@ class ReIDNet(nn.Module):
         results["val_vis_gt_all"] = torch.cat([vis_1.unsqueeze(1), vis_2.unsqueeze(1)], dim=1)
         return [results]
 
+    def validate_step(self, batch, book, count=None):
+        """forward_test's scoring half for a device-side book (pcr_amd.matchbook.MatchBook): the same inputs, the same
+        encode + match launches and so the same logits, but the batch's pairs go into the book's table by one launch
+        (`book.add`; the per-object heads, when their losses are on, by `book.add_objects`) instead of coming back as
+        tensors.  No host tensor is built and nothing is returned that forces a read, so a step can be captured in a HIP
+        graph and replayed (the split-bf16 guard measures nothing inside a capture: calibrate before, as for every
+        captured entry point).  count: a (1,) int32 device tensor -- only the first count pairs of a padded batch are
+        scored.  The validation losses stay with forward_test."""
+        self._check_losses()
+        if not self.losses_to_use["match"]:
+            raise L.PcrError("validate_step scores the match logits; losses_to_use['match'] is off")
+        keys = ("sparse_1", "sparse_2", "dense_1", "dense_2", "label_1", "label_2", "id_1", "id_2", "size_1", "size_2",
+                "vis_1", "vis_2")
+        (sparse_1, sparse_2, _, _, label_1, label_2, id_1, id_2, size_1, size_2, vis_1,
+         vis_2) = self.preprocess_inputs_size_vis(*(batch[k] for k in keys))
+        xyz1, xyz2, h1, h2 = self.siamese_forward(sparse_1, sparse_2)
+        h1, h2, xyz1, xyz2, match = self.get_match_supervision(h1, h2, xyz1, xyz2, id_1, id_2)
+        with self._at_level(self.precision_level()):
+            match_preds, _ = self._match_logits(h1, h2, xyz1, xyz2)
+        if self._aux_on():
+            from pcr_amd import train_graph
+            preds = self.object_heads(train_graph._joined(h1, h2))
+            labels = torch.cat([label_1, label_2], dim=0)
+            if preds["cls"] is not None or preds["fp"] is not None:
+                book.add_objects(cls_logits=preds["cls"], cls_gt=None if preds["cls"] is None else labels,
+                                 fp_logits=preds["fp"], fp_gt=None if preds["fp"] is None else (labels > 9).float(),
+                                 count=count, period=h1.shape[0])
+        book.add(logit=match_preds, gt=match, cls=torch.stack([label_1, label_2], dim=1),
+                 num_points=torch.stack([size_1, size_2], dim=1), vis=torch.stack([vis_1, vis_2], dim=1), count=count)
+
     @staticmethod
     def _parse_losses(losses):
         """mmdet BaseDetector._parse_losses: mean every entry, sum those whose key contains 'loss',

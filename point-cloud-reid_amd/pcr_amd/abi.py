@@ -106,6 +106,10 @@ SceneLogParams = _block("SceneLogParams", """
     int rows_max R W; iptr in_valid in_ids in_labels; fptr in_scores in_boxes; iptr in_flags;
     iptr frame id label flags; fptr score box; iptr cursor dropped frame_no""")
 
+# ---- section A13 (pcr_match) ----
+MatchParams = _block("MatchParams", """
+    int P; fptr logit gt; iptr cls num_points vis count; lptr table; iptr info""")
+
 # ---- section A6 (pcr_store_tables) ----
 StoreTables = _block("StoreTables", """
     int num_objects num_classes;
@@ -289,6 +293,10 @@ SIGNATURES = {
     "pcr_rank_fill_f32": "s FiiS",
     "pcr_rank_scatter_f32": "s FIIFiiiiiS",
     "pcr_rank_wide_f32": "s <RankParams>S",
+    # A13. scoring a validation split (the block is passed as a plain pointer, as A10: byref(MatchParams))
+    "pcr_match_ok": "i iii",
+    "pcr_match_record_i64": "s PS",
+    "pcr_match_record_objects_i64": "s FIFFIPIiiiS",
     # B. fused model kernels
     "pcr_knn_prefix_f32": "s FIiiiiS",
     "pcr_knn_prefix2_f32": "s FIIiiiiiiS",

@@ -26,6 +26,7 @@ FLAGS = {
     "truth_kernels.hip": ["-ffp-contract=off"],      # the ground-truth matching cost is compared bit for bit
     "rank_kernels.hip": ["-ffp-contract=off"],       # the binary64 average-precision sums are compared bit for bit
     "ident_kernels.hip": ["-ffp-contract=off"],      # the binary64 match-distance sums are compared bit for bit
+    "match_kernels.hip": ["-ffp-contract=off"],      # the validation table is compared bit for bit (integer adds, float compares)
 }
 
 

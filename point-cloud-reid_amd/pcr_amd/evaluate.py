@@ -133,8 +133,13 @@ def _head_width(model, name):
     return int(head[-1].out_features) if isinstance(head, torch.nn.Sequential) and hasattr(head[-1], "out_features") else 0
 
 
+def _padded(batch, size):
+    """a short last batch brought to `size` samples by repeating its last one (the rows beyond the count are not scored)"""
+    return {k: list(v) + [v[-1]] * (size - len(v)) for k, v in batch.items()}
+
+
 def evaluate_model(model, dataset, batch_size, seed=0, device="cuda", rank=None, world=None, cls_to_idx=None,
-                   num_classes=None, on_batch=None, store=None):
+                   num_classes=None, on_batch=None, store=None, book=None, keep_logits=False):
     """multi_gpu_test + dataset.evaluate for one model over one ValPairs: this rank's contiguous shard of the pairs in
     batches of `batch_size` through forward_test, logits gathered in pair order on every rank, metrics from the gathered
     set.  -> dict(val_match_acc, f1 / precision / recall, per-class and per-bucket accuracies, `tables`, `logits`,
@@ -143,7 +148,17 @@ def evaluate_model(model, dataset, batch_size, seed=0, device="cuda", rank=None,
     store: a pcr_amd.store.CropStore over the dataset's crops -- the batches then come from `store.val_batch` (two
     launches, no host read; the dataset's pair list is uploaded once if the store holds none), keyed by the GLOBAL pair
     index, so a pair's clouds are the same bits on any number of ranks and at any batch size.  Its samples are another
-    stream than numpy's; None keeps the host path and its results."""
+    stream than numpy's; None keeps the host path and its results.
+    book: a pcr_amd.matchbook.MatchBook on the model's device -- the split is then scored on the device: the book is reset,
+    every batch goes through `model.validate_step` (one more launch per batch, no host read; the last batch of a shard of
+    several batches is padded to `batch_size` and carries a device-side count, so every step has one shape), nothing
+    per-pair is kept or gathered, and `book.reduce()` is the one collective.  The dict then holds the book's metrics and
+    tables, `num_pairs` and `world`, and no `logits` / `targets` -- unless keep_logits, which sends the batches through
+    forward_test as before (the book is fed from its result dict) and gathers those two columns.  `on_batch` gets None as
+    its third argument where there is no result dict.  The book decides by `logit > 0`; see INTEGRATION.md, "validation on
+    the device".  Without book= the call does what it always did."""
+    if book is None and keep_logits:
+        raise ValueError("keep_logits belongs to book=: without a book the logits are always returned")
     if rank is None:
         rank, _, world = shard.env_world()
         if not shard.is_dist():
@@ -160,6 +175,12 @@ def evaluate_model(model, dataset, batch_size, seed=0, device="cuda", rank=None,
             store.set_val_pairs(dataset.pairs, (), dataset.visibility)
         if store.val["num_pairs"] != n:
             raise ValueError("the store holds %d validation pairs, the dataset %d" % (store.val["num_pairs"], n))
+    if book is not None:
+        book.reset()
+        if book.cls_to_idx is None:
+            book.cls_to_idx = {k: v for k, v in (cls_to_idx or {}).items() if v != -1} or None
+        if book.num_classes is None:
+            book.num_classes = num_classes
     with torch.no_grad():
         for b0 in range(lo, hi, batch_size):
             if store is not None:
@@ -170,9 +191,29 @@ def evaluate_model(model, dataset, batch_size, seed=0, device="cuda", rank=None,
                     np.random.seed(seed_of(seed, i))
                     items.append(dataset[i])
                 batch = D.collate_pairs(items, device=device)
+            if book is not None and not keep_logits:
+                count, real = None, min(hi, b0 + batch_size) - b0
+                if real < batch_size < hi - lo:
+                    batch = _padded(batch, batch_size)
+                    count = torch.tensor([real], dtype=torch.int32).to(device, non_blocking=True)
+                model.validate_step(batch, book, count)
+                if on_batch is not None:
+                    on_batch(b0, batch, None)
+                continue
             (res,) = model(return_loss=False, **batch)
+            if book is not None:
+                book.add(res)
+                if res.get("val_cls_preds") is not None or res.get("val_fp_preds") is not None:
+                    cls_on, fp_on = res.get("val_cls_preds") is not None, res.get("val_fp_preds") is not None
+                    book.add_objects(cls_logits=res["val_cls_preds"] if cls_on else None,
+                                     cls_gt=res["val_cls_gt"] if cls_on else None,
+                                     fp_logits=res["val_fp_preds"] if fp_on else None,
+                                     fp_gt=res["val_fp_gt"] if fp_on else None)
             if on_batch is not None:
                 on_batch(b0, batch, res)
+            if book is not None:
+                local.append({k: res[k].detach() for k in ("val_match_preds", "val_match_gt")})
+                continue
             row = {k: res[k].detach() for k in ("val_match_preds",) + keep}
             # the per-object heads, when their losses are on: forward_test returns cat(side 1, side 2) rows; kept per PAIR
             # (b, 2 * width) so that they shard and gather like every other per-pair tensor
@@ -193,6 +234,15 @@ def evaluate_model(model, dataset, batch_size, seed=0, device="cuda", rank=None,
             mine = mine.cpu()                               # (the CPU rehearsal backend; RCCL gathers device tensors)
         cols = [shard.gather_logits(mine[:, c].contiguous(), n) for c in range(width)]
         return torch.stack(cols, 1)
+    if book is not None:
+        book.reduce()
+        out, tables = book.results()
+        out["tables"] = tables
+        out.update(num_pairs=n, world=world)
+        if keep_logits:
+            out.update(logits=gathered("val_match_preds", 1, torch.float32)[:, 0].cpu(),
+                       targets=gathered("val_match_gt", 1, torch.float32)[:, 0].cpu())
+        return out
     # forward_test's per-pair tensors in pair order on every rank (collect_results): float logits / targets, integer
     # classes / sizes / visibility
     full = {"val_match_preds": gathered("val_match_preds", 1, torch.float32)[:, 0],
@@ -221,12 +271,15 @@ def evaluate_model(model, dataset, batch_size, seed=0, device="cuda", rank=None,
 
 
 def evaluate_checkpoint(cfg_path, ckpt_path, crop_root, max_combinations=None, seed=None, meta=None, batch_size=None,
-                        device="cuda", cfg_options=None, literal_exclusion=False, num_classes=None, device_store=False):
+                        device="cuda", cfg_options=None, literal_exclusion=False, num_classes=None, device_store=False,
+                        device_book=False):
     """(config file, mmcv-layout checkpoint, crop directory) -> `val_match_acc` and everything else
     `ReIDDatasetBase.evaluate` logs, on however many ranks torch.distributed is running (one process per GPU; no
     data-path collective -- BatchNorm statistics are broadcast once before, the per-pair results gathered once after).
     device_store: read the crop directory once into a pcr_amd.store.CropStore on this rank's device and assemble the
-    batches there (see evaluate_model)."""
+    batches there (see evaluate_model).
+    device_book: score the split in a pcr_amd.matchbook.MatchBook on this rank's device (evaluate_model's book=): one small
+    table is reduced instead of the per-pair results being gathered, and the dict has no `logits` / `targets`."""
     cfg = Config.fromfile(cfg_path)
     if cfg_options:
         cfg.merge_from_dict(cfg_options)
@@ -247,8 +300,12 @@ def evaluate_checkpoint(cfg_path, ckpt_path, crop_root, max_combinations=None, s
         sl = dict(val_cfg.get("sparse_loader") or {})
         store = CropStore.from_directory(crop_root, table, device=device,
                                          load_fraction=float(sl.get("load_fraction", 1.0) or 1.0), pair_rule=False)
+    book = None
+    if device_book:
+        from .matchbook import MatchBook
+        book = MatchBook(device)
     out = evaluate_model(model, ds, bs, seed=seed, device=device, cls_to_idx=val_cfg.get("cls_to_idx"),
-                         num_classes=table.num_classes, store=store)
+                         num_classes=table.num_classes, store=store, book=book)
     out["checkpoint_meta"] = ck_meta
     out["config"] = os.path.abspath(cfg_path)
     guard = getattr(model, "guard_state", lambda: None)()

@@ -279,9 +279,11 @@ class EpochLoader:
             yield D.collate_pairs(samples, device=self.device)
 
 
-def run_epochs(trainer, loader, epochs, start_epoch=0, on_step=None):
+def run_epochs(trainer, loader, epochs, start_epoch=0, on_step=None, on_epoch=None):
     """mmcv's EpochBasedRunner loop for this path: per epoch the sampler is re-seeded (DistSamplerSeedHook), every batch
-    is one Trainer.step (forward + backward + bucket exchange + clip + AdamW); -> list of per-step losses (lazy)"""
+    is one Trainer.step (forward + backward + bucket exchange + clip + AdamW); -> list of per-step losses (lazy).
+    on_epoch(ep, trainer) runs after the last step of epoch ep (trainer.epoch is then ep + 1): the place of a per-epoch
+    validation, mmcv's EvalHook.after_train_epoch (evaluate.evaluate_model with book= makes no host read per batch)."""
     outs = []
     for ep in range(start_epoch, start_epoch + epochs):
         trainer.epoch = ep
@@ -291,4 +293,6 @@ def run_epochs(trainer, loader, epochs, start_epoch=0, on_step=None):
             if on_step is not None:
                 on_step(ep, out)
         trainer.epoch = ep + 1
+        if on_epoch is not None:
+            on_epoch(ep, trainer)
     return outs

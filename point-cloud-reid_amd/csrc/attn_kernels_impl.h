@@ -13,6 +13,7 @@
 #include <stdio.h>
 
 #include <initializer_list>
+#include <type_traits>
 #include <vector>
 
 namespace {
@@ -20,7 +21,8 @@ constexpr int kAPrec = PCR_ATTN_PREC;
 // -------------------------------------------------------------- linear attention ----
 struct AttnArgs {
   pcr_attn_params p;
-  int dbg;   // diagnostics (trace builds): 256 = stamp the shader clock
+  int dbg;   // diagnostics (tuning builds): 256 = stamp the shader clock; 512 = attn_kv_stream64_kernel multiplies an all-zero
+             // key-position block too (PCR_ATTN_KV_FULL)
   int wpc;   // attn_kv_stream128_kernel: waves per cloud (1, 2, 4), a function of Sk only
   // gated launches only (pcr_live, the GATE instantiations below); the un-gated kernels never read these
   const int *live_count;
@@ -442,14 +444,35 @@ void attn_kv_stream64_kernel(AttnArgs a) {
     lw = live_walk(a);
     if ((long)blockIdx.x * (kKvsWaves / (ONEW ? 1 : 4)) >= lw.total) return;   // (cpg >= this: no round for this workgroup)
   }
+  // The K rows x hidden columns of the image are all zeros in every block built without k_pos (FP_SA, both
+  // corss_attention stages: wkv = [[Wk, 0], [Wv, Wv W2]]).  The staging copy looks: it ORs the magnitude bits (a -0.0 is a
+  // zero) of the units of that block -- bf16 image: steps s2 >= XS, cout blocks 0 and 1, both parts; f32 image: k-blocks
+  // kb >= 8, couts < 64 -- into s_kz.  kfull, one scalar per wave: the block holds a nonzero (or dbg 512 asks), and the
+  // block loop runs the K half of the hidden steps too.
+  // s_kz is the pad word of s_wm's last row, element [D - 1][D]: the rows are LD = D + 1 floats apart against bank conflicts
+  // and hold D weights, so neither the staging below nor a fold (columns < D) touches it, and the plans' LDS size has it.
+  static_assert(LD > D, "s_kz takes the pad column of s_wm's last row");
+  unsigned *s_kz = reinterpret_cast<unsigned *>(s_wm + (D - 1) * LD + D);
+  if (tid == 0) *s_kz = 0u;
+  __syncthreads();
   {
-    const f32x4 *src = reinterpret_cast<const f32x4 *>(BF ? p.wkv_bf : p.wkv);   // (both images are 4096 16-byte units)
-    for (int e = tid; e < WU; e += 64 * kKvsWaves) s_w[e] = src[e];
+    const f32x4 *src = reinterpret_cast<const f32x4 *>(BF ? p.wkv_bf : p.wkv);   // (WU 16-byte units: 4096, or 6144 at XS = 8)
+    unsigned nz = 0u;
+    for (int e = tid; e < WU; e += 64 * kKvsWaves) {
+      const f32x4 u = src[e];
+      s_w[e] = u;
+      const bool kz = BF ? ((e >> 9) >= XS && ((e >> 7) & 3) < 2) : ((e >> 8) >= 8 && ((e >> 1) & 127) < D);
+      typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+      const u32x4 ub = __builtin_bit_cast(u32x4, u);
+      if (kz) nz |= (ub[0] | ub[1] | ub[2] | ub[3]) & (BF ? 0x7FFF7FFFu : 0x7FFFFFFFu);
+    }
+    if (nz) atomicOr(s_kz, 1u);
     for (int e = tid; e < D * D; e += 64 * kKvsWaves) s_wm[(e >> 6) * LD + (e & 63)] = p.wmerge[e];
     if (tid < D) s_p0[tid] = f32x4{p.pos0_w[3 * tid], p.pos0_w[3 * tid + 1], p.pos0_w[3 * tid + 2], p.pos0_b[tid]};
     if (tid < 2 * D) s_bkv[tid] = p.bkv[tid];
   }
   __syncthreads();
+  const bool kfull = __builtin_amdgcn_readfirstlane((int)*s_kz) != 0 || (a.dbg & 512) != 0;
   const int nblk = p.Sk >> 5;
   // waves per cloud: min(4, Sk / 32) rounded down to a power of two, at least MINW -- i.e. two or four clouds per workgroup
   // round.  (Until round 6 a cloud took up to EIGHT waves: at Sk = 1024 the eight partial KV tiles then met in eight
@@ -521,16 +544,27 @@ void attn_kv_stream64_kernel(AttnArgs a) {
           for (int cb = 0; cb < 4; cb++)
 #pragma unroll
             for (int r = 0; r < 16; r++) acc[cb][r] = 0.f;   // (the bias joins in the epilogue: seeded, 64 registers of copies were live through the load phase)
-#pragma unroll
-          for (int kb = 0; kb < 16; kb++) {
+          // cout blocks CB0 .. 3 of k-block kb: CB0 = 2 leaves out the K rows (their weight reads too)
+          auto project = [&](auto first, int kb) {
+            constexpr int CB0 = decltype(first)::value;
             f32x4 w[4];
 #pragma unroll
-            for (int cb = 0; cb < 4; cb++) w[cb] = s_w[((kb * 128 + cb * 32 + j) << 1) + h];
+            for (int cb = CB0; cb < 4; cb++) w[cb] = s_w[((kb * 128 + cb * 32 + j) << 1) + h];
 #pragma unroll
             for (int i = 0; i < 4; i++)
 #pragma unroll
-              for (int cb = 0; cb < 4; cb++)
+              for (int cb = CB0; cb < 4; cb++)
                 acc[cb] = __builtin_amdgcn_mfma_f32_32x32x2f32(xr[4 * kb + i], w[cb][i], acc[cb], 0, 0, 0);
+          };
+#pragma unroll
+          for (int kb = 0; kb < 8; kb++) project(std::integral_constant<int, 0>{}, kb);
+          // the hidden channels: the K rows only where their weights are not all zeros (kfull: wave-uniform, a scalar branch)
+          if (kfull) {
+#pragma unroll
+            for (int kb = 8; kb < 16; kb++) project(std::integral_constant<int, 0>{}, kb);
+          } else {
+#pragma unroll
+            for (int kb = 8; kb < 16; kb++) project(std::integral_constant<int, 2>{}, kb);
           }
         } else {
           float xf[8 * XS];
@@ -542,9 +576,37 @@ void attn_kv_stream64_kernel(AttnArgs a) {
               xf[e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rfeat, vo, ch * p.Sk * 4, 0));
             }
           }
-          bf16x8 ah[XS + 4], al[XS + 4];
+          // (measured and dropped: the NEXT block's loads requested behind this block's, into the registers its split frees.
+          // At XS = 4 it fits without scratch (231 registers against 194) and measured no gain -- +1.7 % at Sk = 1024; at
+          // XS = 8 it spills 144 bytes: profiles/r16_kv64_skip_ab.txt, r16_kv64_skip_kres.txt)
 #pragma unroll
-          for (int s2 = 0; s2 < 4; s2++) {   // hidden channels 16 s2 + bf_kpos(h, .): the steps after the features'' 
+          for (int e = 0; e < 8 * XS; e++) asm volatile("" : "+v"(xf[e]));   // (the loads land here, see the f32 form)
+#pragma unroll
+          for (int cb = 0; cb < 4; cb++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) acc[cb][r] = 0.f;
+          trace.mark(1);
+          const bf16x8 *wb = reinterpret_cast<const bf16x8 *>(s_w) + lane;
+          // cout blocks CB0 .. 3 of step s2 with the A operand (xh, xl): CB0 = 2 leaves out the K rows (their weight reads too)
+          auto project = [&](auto first, int s2, const bf16x8 xh, const bf16x8 xl) {
+            constexpr int CB0 = decltype(first)::value;
+            bf16x8 wh[4], wl[4];
+#pragma unroll
+            for (int cb = CB0; cb < 4; cb++) {
+              wh[cb] = wb[((s2 * 4 + cb) * 2) * 64];
+              wl[cb] = wb[((s2 * 4 + cb) * 2 + 1) * 64];
+            }
+#pragma unroll
+            for (int cb = CB0; cb < 4; cb++) acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xh, wh[cb], acc[cb], 0, 0, 0);
+#pragma unroll
+            for (int cb = CB0; cb < 4; cb++) acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xl, wh[cb], acc[cb], 0, 0, 0);
+#pragma unroll
+            for (int cb = CB0; cb < 4; cb++) acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xh, wl[cb], acc[cb], 0, 0, 0);
+          };
+          // hidden channels 16 s2 + bf_kpos(h, .), the steps after the features': the operand of a step is formed right
+          // before the step's MFMAs (all four ahead of the feature phase, they held 32 registers through it for nothing)
+          auto hidden = [&](auto first, int s2) {
+            asm volatile("" ::: "memory");   // (... and stays there: the hidden layer's rows are not read ahead)
             float hv[8];
 #pragma unroll
             for (int e = 0; e < 8; e++) {
@@ -552,37 +614,26 @@ void attn_kv_stream64_kernel(AttnArgs a) {
               const float v = w[0] * px + w[1] * py + w[2] * pz + w[3];
               hv[e] = relu_i(v);
             }
-            bf_split8(hv, ah[XS + s2], al[XS + s2], true);
-          }
+            bf16x8 hh, hl;
+            bf_split8(hv, hh, hl, true);
+            project(first, XS + s2, hh, hl);
+          };
 #pragma unroll
-          for (int e = 0; e < 8 * XS; e++) asm volatile("" : "+v"(xf[e]));   // (the loads land here, see the f32 form)
-#pragma unroll
-          for (int s2 = 0; s2 < XS; s2++) {
+          for (int s2 = 0; s2 < XS; s2++) {   // the feature steps, split one at a time: eight registers of operands, not 8 XS
             float xv[8];
 #pragma unroll
             for (int e = 0; e < 8; e++) xv[e] = xf[8 * s2 + e];
-            bf_split8(xv, ah[s2], al[s2], true);
+            bf16x8 xh, xl;
+            bf_split8(xv, xh, xl, true);
+            project(std::integral_constant<int, 0>{}, s2, xh, xl);
           }
+          // the K rows of the hidden steps only where their weights are not all zeros (kfull: wave-uniform, a scalar branch)
+          if (kfull) {
 #pragma unroll
-          for (int cb = 0; cb < 4; cb++)
+            for (int s2 = 0; s2 < 4; s2++) hidden(std::integral_constant<int, 0>{}, s2);
+          } else {
 #pragma unroll
-            for (int r = 0; r < 16; r++) acc[cb][r] = 0.f;
-          trace.mark(1);
-          const bf16x8 *wb = reinterpret_cast<const bf16x8 *>(s_w) + lane;
-#pragma unroll
-          for (int s2 = 0; s2 < XS + 4; s2++) {
-            bf16x8 wh[4], wl[4];
-#pragma unroll
-            for (int cb = 0; cb < 4; cb++) {
-              wh[cb] = wb[((s2 * 4 + cb) * 2) * 64];
-              wl[cb] = wb[((s2 * 4 + cb) * 2 + 1) * 64];
-            }
-#pragma unroll
-            for (int cb = 0; cb < 4; cb++) acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[s2], wh[cb], acc[cb], 0, 0, 0);
-#pragma unroll
-            for (int cb = 0; cb < 4; cb++) acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[s2], wh[cb], acc[cb], 0, 0, 0);
-#pragma unroll
-            for (int cb = 0; cb < 4; cb++) acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[s2], wl[cb], acc[cb], 0, 0, 0);
+            for (int s2 = 0; s2 < 4; s2++) hidden(std::integral_constant<int, 2>{}, s2);
           }
         }
         trace.mark(2);
@@ -2223,7 +2274,8 @@ static void attn_dump_trace(const char *path, const char *tag, int wgs, int B, i
 // neither the device nor the chip's size; one launcher per family turns a plan into the launch.  The f32 unit also holds the
 // order of the units (attn_bf), the gate, the exported queries and the C-ABI entry points.
 
-// tuning builds' knobs (0 / null in production builds: pcr_common.h), gathered once per process and unit
+// tuning builds' knobs (0 / null in production builds: pcr_common.h), gathered once per process and unit.  One more,
+// PCR_ATTN_KV_FULL (attn_kv_stream64_kernel runs the full form whatever the weights hold), is read per launch: attn_unit.
 struct AttnTune {
   int no_onew;         // PCR_ATTN_NO_ONEW: short key sets keep several waves per cloud
   int no_kv128;        // PCR_ATTN_NO_KV128: the d = 128 stream kv shapes back to the tile kernel
@@ -2611,7 +2663,9 @@ static int attn_unit(const pcr_attn_params &p, const pcr_live *live, bool apply,
   if (rc != PCR_OK) return rc;
   AttnArgs a;
   a.p = p;
-  a.dbg = pl->trace ? 256 : 0;
+  // PCR_ATTN_KV_FULL (tuning builds; for the skip test and the A/B, not for users) is read at every launch, not once per
+  // process like AttnTune: a test flips it between two launches of one process
+  a.dbg = (pl->trace ? 256 : 0) | (pcr_tune_int("PCR_ATTN_KV_FULL") ? 512 : 0);
   a.wpc = pl->wpc;
   // gated launches (pcr_live): the caller's count, period and offset travel in AttnArgs
   a.live_count = live ? live->count : nullptr;

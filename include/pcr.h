@@ -1835,6 +1835,19 @@ int pcr_sa_l1_fwd_f32(const float *xyz, const int *idx, const float *tab, const 
 int pcr_sa_l1_bwd_f32(const float *xyz, const int *idx, const float *g, const float *y, const float *ka,
                       const float *kb, const float *kc, float *dtab, float *dwa, int B, int N, int S, int K, int c1,
                       pcr_stream_t stream);
+/* The same pair for a ball-query group (QueryAndGroup with use_xyz: rows [dxyz, f_i]) whose centres are sampled points:
+ * centre (B,S) int32 holds every centre's point index, tab (B,c1,N) or NULL is P alone (no centre half), bias may be
+ * NULL:  y[b][c][s K + k] = wa[c] . (xyz[idx] - xyz[centre[b][s]]) + tab[b][c][idx] (+ bias[c]);  stats as above.
+ * Backward: dtab (B,c1,N) = sum of dy over the rows that gathered each point (a row repeated in idx counts once per
+ * copy), dwa as above.  Same kernels, same ownership rule: no atomics, bit-reproducible.  PCR_ERR_INVALID, before any
+ * launch, for a NULL centre, N > 8192 (one channel's table row must fit the 32 KiB LDS slice) or K, S < 1; S may
+ * exceed N.  The VALUES of idx and centre are the caller's to guarantee, as for pcr_sa_l1_*: every one must lie in
+ * [0, N) -- the kernels index the cloud and the table slice in LDS with them unchecked. */
+int pcr_sa_l1c_fwd_f32(const float *xyz, const int *idx, const int *centre, const float *tab, const float *wa,
+                       const float *bias, float *y, float *stats, int B, int N, int S, int K, int c1, pcr_stream_t stream);
+int pcr_sa_l1c_bwd_f32(const float *xyz, const int *idx, const int *centre, const float *g, const float *y,
+                       const float *ka, const float *kb, const float *kc, float *dtab, float *dwa, int B, int N, int S,
+                       int K, int c1, pcr_stream_t stream);
 /* pooled[b][c][s] = max_k relu(scale[c] y[b][c][s K + k] + shift[c]), argmax = the first k attaining it, ymax (optional)
  * = the raw y at that row (what the backward's BatchNorm sums need) */
 int pcr_sa_pool_fwd_f32(const float *y, const float *scale, const float *shift, float *pooled, int *argmax, float *ymax,

@@ -7,6 +7,10 @@
 // backward sends dy1 back to the tables: dP[i] = sum of dy1 over the rows that gathered point i, dQ[c] = sum over
 // the K rows of centre c -- a scatter, done here WITHOUT float atomics: every (channel, point) accumulator has one
 // owner thread that adds its rows in row order, so the gradients are bit-reproducible.
+//
+// The same two kernels serve a ball-query group (QueryAndGroup with use_xyz: rows [dxyz, f_i], centres at arbitrary
+// point indices, rows k >= cnt copies of row 0) through the CEN flag: centre s is point centre[b][s], there is no Q
+// half, y1 = Wa (xyz[i] - xyz[centre]) + P[i] (+ b) and the backward's dP counts a copy once per copy.
 #include <type_traits>
 
 #include "tile_dense.h"
@@ -27,23 +31,25 @@ struct L1Args {
   float *y;                // (B,c1,S*K)
   float *stats;            // partials [B * chunks][2][ceil32(CS)]... see l1_fwd: [b][chunk][2][CS]
   int N, S, K, c1, CS;
+  const int *centre;       // CEN: (B,S) point index of every centre; tab is then (B,c1,N) = P alone
 };
 
 // one workgroup per (cloud, chunk of CS channels); rows r = s*K + k across the lanes (coalesced idx reads / y writes)
-template <int CS>
+template <int CS, bool CEN>
 __global__ __launch_bounds__(kThreads) void sa_l1_fwd_kernel(L1Args a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int N = a.N, S = a.S, K = a.K, c1 = a.c1, L = S * K;
   float *Pl = smem;                                   // [CS][N]
   float *Ql = Pl + (a.tab ? CS * N : 0);              // [CS][S]: the centres' columns of Q (a row's 32 loads of it sat
                                                       // in front of its stores: one L2 round trip per row iteration)
-  float *xl = Ql + (a.tab ? CS * S : 0);              // [N][3]
+  float *xl = Ql + (a.tab && !CEN ? CS * S : 0);      // [N][3]
   float *wl = xl + 3 * N;                             // [CS][4]: wa, bias
   float *red = wl + 4 * CS;                           // [4 waves][2][CS]
+  int *cenl = reinterpret_cast<int *>(red + 8 * CS);  // CEN: [S] the centres' point indices
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const size_t b = blockIdx.y;
   const int c0 = blockIdx.x * CS;
-  const float *tab = a.tab ? a.tab + b * 2 * c1 * N : nullptr;
+  const float *tab = a.tab ? a.tab + b * (CEN ? 1 : 2) * c1 * N : nullptr;
   if (tab) {   // (batches of eight loads in flight: a load -> LDS-store loop pays the full latency per element)
     constexpr int U = 8;
     for (int e0 = tid; e0 < CS * N; e0 += U * kThreads) {
@@ -61,7 +67,7 @@ __global__ __launch_bounds__(kThreads) void sa_l1_fwd_kernel(L1Args a) {
       }
     }
   }
-  if (tab) {
+  if (!CEN && tab) {
     const float *Qg = tab + (size_t)(c1 + c0) * N;
     constexpr int U = 8;
     for (int e0 = tid; e0 < CS * S; e0 += U * kThreads) {
@@ -80,6 +86,8 @@ __global__ __launch_bounds__(kThreads) void sa_l1_fwd_kernel(L1Args a) {
     }
   }
   for (int e = tid; e < 3 * N; e += kThreads) xl[e] = a.xyz[b * N * 3 + e];
+  if constexpr (CEN)
+    for (int e = tid; e < S; e += kThreads) cenl[e] = a.centre[b * S + e];
   for (int e = tid; e < CS; e += kThreads) {
     const int c = c0 + e;
     const bool ok = c < c1;
@@ -101,14 +109,16 @@ __global__ __launch_bounds__(kThreads) void sa_l1_fwd_kernel(L1Args a) {
     for (int r = tid; r < L; r += kThreads) {
       const int s = r / K, i = inext;
       if (r + kThreads < L) inext = idx[r + kThreads];   // (the next row's index travels while this row is written)
-      const float dx = xl[3 * i] - xl[3 * s], dy = xl[3 * i + 1] - xl[3 * s + 1], dz = xl[3 * i + 2] - xl[3 * s + 2];
+      const int sc = CEN ? cenl[s] : s;                  // the centre's point
+      const float dx = xl[3 * i] - xl[3 * sc], dy = xl[3 * i + 1] - xl[3 * sc + 1], dz = xl[3 * i + 2] - xl[3 * sc + 2];
       // the centre's table column first, all CS loads in flight: read inside the store loop each one waits behind the
       // previous store to y (the compiler cannot rule out that y aliases the table)
 #pragma unroll
       for (int c = 0; c < CS; c++) {
         if (c0 + c < c1) {
           float v = fmaf(wl[4 * c + 2], dz, fmaf(wl[4 * c + 1], dy, fmaf(wl[4 * c], dx, wl[4 * c + 3])));
-          if constexpr (TAB) v += Pl[c * N + i] + Ql[c * S + s];
+          if constexpr (TAB && CEN) v += Pl[c * N + i];
+          if constexpr (TAB && !CEN) v += Pl[c * N + i] + Ql[c * S + s];
           y[(size_t)c * L + r] = v;
           ssum[c] += v;
           ssq[c] += v * v;
@@ -152,11 +162,12 @@ struct L1BwdArgs {
   float *dtab;                 // (B,2*c1,N) or null
   float *dwa;                  // partials [B][c1][4]: d wa (3), d bias
   int N, S, K, c1, CS;
+  const int *centre;           // CEN: (B,S) point index of every centre; dtab is then (B,c1,N) = dP alone
 };
 
 // thread (cl = tid % CS, part = tid / CS): owner of channel cl's accumulators for the points / centres / rows
 // congruent to `part` modulo the number of parts; rows are visited in increasing order by every owner
-template <int CS>
+template <int CS, bool CEN>
 __global__ __launch_bounds__(kThreads) void sa_l1_bwd_kernel(L1BwdArgs a) {
   constexpr int PARTS = kThreads / CS, TR = kL1Tr;   // rows per staged tile
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -164,7 +175,7 @@ __global__ __launch_bounds__(kThreads) void sa_l1_bwd_kernel(L1BwdArgs a) {
   const int NP = N | 1, SP = S | 1;            // odd pitches: the lanes of a wave differ in cl, not in i / s
   float *dP = smem;                            // [CS][NP]
   float *dQ = dP + (a.dtab ? CS * NP : 0);     // [CS][SP]
-  float *xl = dQ + (a.dtab ? CS * SP : 0);     // [N][3]
+  float *xl = dQ + (a.dtab && !CEN ? CS * SP : 0);   // [N][3]
   float *dyt = xl + 3 * N;                     // [CS][TR + 1]
   float *dxt = dyt + CS * (TR + 1);            // [TR][3]
   int *it = reinterpret_cast<int *>(dxt + 3 * TR);   // [TR] neighbour index, [TR] centre
@@ -178,7 +189,7 @@ __global__ __launch_bounds__(kThreads) void sa_l1_bwd_kernel(L1BwdArgs a) {
   const int c0 = blockIdx.x * CS;
   const bool live = c0 + cl < c1;
   if (a.dtab)
-    for (int e = tid; e < CS * NP + CS * SP; e += kThreads) dP[e] = 0.f;   // (dQ follows dP)
+    for (int e = tid; e < CS * NP + (CEN ? 0 : CS * SP); e += kThreads) dP[e] = 0.f;   // (dQ follows dP)
   for (int e = tid; e < 3 * N; e += kThreads) xl[e] = a.xyz[b * N * 3 + e];
   const int *idx = a.idx + b * L;
   const float *g = a.g + (b * c1 + c0) * L, *y = a.y + (b * c1 + c0) * L;
@@ -187,10 +198,12 @@ __global__ __launch_bounds__(kThreads) void sa_l1_bwd_kernel(L1BwdArgs a) {
   // registers before the current tile is scanned, so the global round trip hides behind the scan
   constexpr int NE = (CS * TR + kThreads - 1) / kThreads;
   float pg[NE], py[NE];
-  int pi = 0;
+  int pi = 0, pc = 0;
   auto fetch = [&](int t0) {
     const int nr = L - t0 < TR ? L - t0 : TR;
     if (tid < nr) pi = idx[t0 + tid];
+    if constexpr (CEN)
+      if (tid < nr) pc = a.centre[b * S + (t0 + tid) / K];
 #pragma unroll
     for (int u = 0; u < NE; u++) {
       const int e = tid + u * kThreads;
@@ -207,11 +220,12 @@ __global__ __launch_bounds__(kThreads) void sa_l1_bwd_kernel(L1BwdArgs a) {
     const int nr = L - t0 < TR ? L - t0 : TR;
     if (tid < nr) {
       const int r = t0 + tid, i = pi, s = r / K;
+      const int sc = CEN ? pc : s;                 // the centre's point
       it[tid] = i;
       st[tid] = s;
-      dxt[3 * tid] = xl[3 * i] - xl[3 * s];
-      dxt[3 * tid + 1] = xl[3 * i + 1] - xl[3 * s + 1];
-      dxt[3 * tid + 2] = xl[3 * i + 2] - xl[3 * s + 2];
+      dxt[3 * tid] = xl[3 * i] - xl[3 * sc];
+      dxt[3 * tid + 1] = xl[3 * i + 1] - xl[3 * sc + 1];
+      dxt[3 * tid + 2] = xl[3 * i + 2] - xl[3 * sc + 2];
     }
 #pragma unroll
     for (int u = 0; u < NE; u++) {
@@ -259,13 +273,15 @@ __global__ __launch_bounds__(kThreads) void sa_l1_bwd_kernel(L1BwdArgs a) {
         // owner class j mod PARTS adds segment j's rows in a register (independent LDS reads) and touches dQ once.
         // (Scattering them row by row like the points above put all K rows of a centre on ONE owner: a chain of K
         // dependent LDS read-modify-writes per tile, ~14 k cycles at K = 48, with the other seven owners idle.)
-        const int s_first = st[0], nseg = st[nr - 1] - s_first + 1;
-        for (int j = part; j < nseg; j += PARTS) {
-          const int s = s_first + j;
-          const int lo = s * K - t0 > 0 ? s * K - t0 : 0, hi = (s + 1) * K - t0 < nr ? (s + 1) * K - t0 : nr;
-          float acc = 0.f;
-          for (int rr = lo; rr < hi; rr++) acc += row[rr];
-          dQ[cl * SP + s] += acc;
+        if constexpr (!CEN) {
+          const int s_first = st[0], nseg = st[nr - 1] - s_first + 1;
+          for (int j = part; j < nseg; j += PARTS) {
+            const int s = s_first + j;
+            const int lo = s * K - t0 > 0 ? s * K - t0 : 0, hi = (s + 1) * K - t0 < nr ? (s + 1) * K - t0 : nr;
+            float acc = 0.f;
+            for (int rr = lo; rr < hi; rr++) acc += row[rr];
+            dQ[cl * SP + s] += acc;
+          }
         }
       }
     }
@@ -283,12 +299,12 @@ __global__ __launch_bounds__(kThreads) void sa_l1_bwd_kernel(L1BwdArgs a) {
     if (c0 + c < c1) a.dwa[(b * c1 + c0 + c) * 4 + j] = s;
   }
   if (a.dtab) {
-    float *dt = a.dtab + b * 2 * c1 * N;
+    float *dt = a.dtab + b * (CEN ? 1 : 2) * c1 * N;
     for (int e = tid; e < CS * N; e += kThreads) {
       const int c = e / N, i = e - c * N;
       if (c0 + c < c1) {
         dt[(size_t)(c0 + c) * N + i] = dP[c * NP + i];
-        dt[(size_t)(c1 + c0 + c) * N + i] = i < S ? dQ[c * SP + i] : 0.f;
+        if constexpr (!CEN) dt[(size_t)(c1 + c0 + c) * N + i] = i < S ? dQ[c * SP + i] : 0.f;
       }
     }
   }
@@ -429,45 +445,74 @@ static int l1_pow2(int cs) {
   return p;
 }
 
-PCR_EXPORT int pcr_sa_l1_fwd_f32(const float *xyz, const int *idx, const float *tab, const float *wa, const float *bias,
-                                 float *y, float *stats, int B, int N, int S, int K, int c1, pcr_stream_t stream) {
-  if (!xyz || !idx || !wa || !y || B < 0 || N < 1 || S < 1 || S > N || K < 1 || c1 < 1) return PCR_ERR_INVALID;
+// the one launcher of each direction: centre NULL = the first-S-points grouping with its [P ; Q] table, else the
+// indexed-centre grouping (P alone).  Every argument is checked before anything touches the device.
+template <bool CEN>
+static int l1_fwd_launch(const float *xyz, const int *idx, const int *centre, const float *tab, const float *wa,
+                         const float *bias, float *y, float *stats, int B, int N, int S, int K, int c1, pcr_stream_t stream) {
+  if (!xyz || !idx || !wa || !y || B < 0 || N < 1 || S < 1 || (!CEN && S > N) || K < 1 || c1 < 1) return PCR_ERR_INVALID;
+  if (CEN && (!centre || (size_t)N * 4 > 32 * 1024)) return PCR_ERR_INVALID;   // (l1_chunk: one channel's table row in 32 KiB)
   if (B == 0) return PCR_OK;
   if (B > 65535) return PCR_ERR_INVALID;
   const int cs = l1_pow2(l1_chunk(N, c1));
-  L1Args a{xyz, idx, tab, wa, bias, y, stats, N, S, K, c1, cs};
-  const size_t lds = ((tab ? (size_t)cs * (N + S) : 0) + 3 * (size_t)N + 4 * cs + 8 * cs) * sizeof(float);
+  L1Args a{xyz, idx, tab, wa, bias, y, stats, N, S, K, c1, cs, centre};
+  const size_t lds = ((tab ? (size_t)cs * (N + (CEN ? 0 : S)) : 0) + 3 * (size_t)N + 4 * cs + 8 * cs + (CEN ? (size_t)S : 0)) * sizeof(float);
   if (lds > (size_t)kMaxDynLds) return PCR_ERR_INVALID;
   const dim3 grid((c1 + cs - 1) / cs, B);
   int rc = PCR_OK;
   l1_dispatch(cs, [&](auto tag) {
     constexpr int CS = decltype(tag)::value;
-    rc = pcr_launch_lds<sa_l1_fwd_kernel<CS>>(grid, dim3(kThreads), lds, pcr_s(stream), a);
+    rc = pcr_launch_lds<sa_l1_fwd_kernel<CS, CEN>>(grid, dim3(kThreads), lds, pcr_s(stream), a);
   });
   return rc;
 }
 
-PCR_EXPORT int pcr_sa_l1_bwd_f32(const float *xyz, const int *idx, const float *g, const float *y, const float *ka,
-                                 const float *kb, const float *kc, float *dtab, float *dwa, int B, int N, int S, int K,
-                                 int c1, pcr_stream_t stream) {
-  if (!xyz || !idx || !g || !y || !ka || !kb || !kc || !dwa || B < 0 || N < 1 || S < 1 || S > N || K < 1 || c1 < 1)
+template <bool CEN>
+static int l1_bwd_launch(const float *xyz, const int *idx, const int *centre, const float *g, const float *y, const float *ka,
+                         const float *kb, const float *kc, float *dtab, float *dwa, int B, int N, int S, int K, int c1,
+                         pcr_stream_t stream) {
+  if (!xyz || !idx || !g || !y || !ka || !kb || !kc || !dwa || B < 0 || N < 1 || S < 1 || (!CEN && S > N) || K < 1 || c1 < 1)
     return PCR_ERR_INVALID;
+  if (CEN && (!centre || (size_t)N * 4 > 32 * 1024)) return PCR_ERR_INVALID;
   if (B == 0) return PCR_OK;
   if (B > 65535) return PCR_ERR_INVALID;
   int cs = l1_pow2(l1_chunk(N, c1));
   if (cs > 32) cs = 32;
-  L1BwdArgs a{xyz, idx, g, y, ka, kb, kc, dtab, dwa, N, S, K, c1, cs};
+  L1BwdArgs a{xyz, idx, g, y, ka, kb, kc, dtab, dwa, N, S, K, c1, cs, centre};
   const int parts = kThreads / cs;
-  const size_t lds = ((dtab ? (size_t)cs * ((N | 1) + (S | 1)) : 0) + 3 * (size_t)N + (size_t)cs * (kL1Tr + 1) + 3 * kL1Tr + 2 * kL1Tr +
+  const size_t lds = ((dtab ? (size_t)cs * ((N | 1) + (CEN ? 0 : (S | 1))) : 0) + 3 * (size_t)N + (size_t)cs * (kL1Tr + 1) + 3 * kL1Tr + 2 * kL1Tr +
                       (size_t)parts * cs * 4 + 4 * (size_t)parts + 2) * sizeof(float);
   if (lds > (size_t)kMaxDynLds) return PCR_ERR_INVALID;
   const dim3 grid((c1 + cs - 1) / cs, B);
   int rc = PCR_OK;
   l1_dispatch(cs, [&](auto tag) {
     constexpr int CS = decltype(tag)::value;
-    rc = pcr_launch_lds<sa_l1_bwd_kernel<CS>>(grid, dim3(kThreads), lds, pcr_s(stream), a);
+    rc = pcr_launch_lds<sa_l1_bwd_kernel<CS, CEN>>(grid, dim3(kThreads), lds, pcr_s(stream), a);
   });
   return rc;
+}
+
+PCR_EXPORT int pcr_sa_l1_fwd_f32(const float *xyz, const int *idx, const float *tab, const float *wa, const float *bias,
+                                 float *y, float *stats, int B, int N, int S, int K, int c1, pcr_stream_t stream) {
+  return l1_fwd_launch<false>(xyz, idx, nullptr, tab, wa, bias, y, stats, B, N, S, K, c1, stream);
+}
+
+PCR_EXPORT int pcr_sa_l1_bwd_f32(const float *xyz, const int *idx, const float *g, const float *y, const float *ka,
+                                 const float *kb, const float *kc, float *dtab, float *dwa, int B, int N, int S, int K,
+                                 int c1, pcr_stream_t stream) {
+  return l1_bwd_launch<false>(xyz, idx, nullptr, g, y, ka, kb, kc, dtab, dwa, B, N, S, K, c1, stream);
+}
+
+PCR_EXPORT int pcr_sa_l1c_fwd_f32(const float *xyz, const int *idx, const int *centre, const float *tab, const float *wa,
+                                  const float *bias, float *y, float *stats, int B, int N, int S, int K, int c1,
+                                  pcr_stream_t stream) {
+  return l1_fwd_launch<true>(xyz, idx, centre, tab, wa, bias, y, stats, B, N, S, K, c1, stream);
+}
+
+PCR_EXPORT int pcr_sa_l1c_bwd_f32(const float *xyz, const int *idx, const int *centre, const float *g, const float *y,
+                                  const float *ka, const float *kb, const float *kc, float *dtab, float *dwa, int B, int N,
+                                  int S, int K, int c1, pcr_stream_t stream) {
+  return l1_bwd_launch<true>(xyz, idx, centre, g, y, ka, kb, kc, dtab, dwa, B, N, S, K, c1, stream);
 }
 
 PCR_EXPORT int pcr_sa_pool_fwd_f32(const float *y, const float *scale, const float *shift, float *pooled, int *argmax,

@@ -14,6 +14,10 @@ mmcv's ConvModule (1x1 Conv2d, bias off when a norm follows, BatchNorm2d, ReLU) 
 Eval-mode forward of a 3-layer SA scale is ONE fused launch (pcr_sa_mlp_f32, mode 1) after FPS and
 ball query; nothing of shape (B,C,S,K) is materialised.  `QueryAndGroup` / `grouping_operation`
 remain available as stand-alone ops for callers that want the grouped tensor.
+
+Train mode is refused unless `hip_training` is set on the module (PointNet2SSG(trainable=True) sets it): then a single
+ball-query scale runs the HIP training graph, BatchNorm with batch statistics over all B S K rows
+(pcr_amd.train_ops.SaGroupTrain; BasePointSAModule._forward_train).
 """
 import os
 
@@ -200,6 +204,10 @@ class BasePointSAModule(nn.Module):
         self.points_sampler = Points_Sampler(self.num_point, self.fps_mod_list, self.fps_sample_range_list)
         # evaluate the shared MLP only on the distinct rows of a ball-query group (identical output)
         self.skip_repeats = True
+        # opt-in: in train mode run the HIP training graph of a single ball-query scale (_forward_train) instead of
+        # refusing; set after construction, like skip_repeats (PointNet2SSG(trainable=True) does)
+        self.hip_training = False
+        self.dilated_group = dilated_group
         for i in range(len(radii)):
             if num_point is not None:
                 min_radius = radii[i - 1] if dilated_group and i != 0 else 0
@@ -271,8 +279,54 @@ class BasePointSAModule(nn.Module):
         return plan.run(points_xyz, features, idx, centre_idx=indices.contiguous(),
                         cnt=cnt if self.skip_repeats else None, out_point_major=len(self.groupers) == 1)
 
+    def _training_refusal(self):
+        """why this module has no HIP training graph, or None: one ball-query scale [dxyz, f_i] -> three ConvModules ->
+        max over K is what pcr_amd.train_ops.SaGroupTrain runs"""
+        if len(self.groupers) != 1:
+            return "multi-scale grouping (MSG: %d scales)" % len(self.groupers)
+        if not isinstance(self.groupers[0], QueryAndGroup):
+            return "GroupAll"
+        if self.pool_mod != "max":
+            return "pool_mod=%r" % self.pool_mod
+        if self.normalize_xyz:
+            return "normalize_xyz"
+        if not self.use_xyz:
+            return "use_xyz=False"
+        if self.dilated_group or self.groupers[0].min_radius:
+            return "dilated_group"
+        layers = list(self.mlps[0].children())
+        if len(layers) != 3:
+            return "an MLP of %d layers (three are covered)" % len(layers)
+        for l in layers:
+            if not (isinstance(getattr(l, "conv", None), nn.Conv2d) and isinstance(getattr(l, "bn", None), nn.BatchNorm2d)
+                    and isinstance(getattr(l, "activate", None), nn.ReLU)):
+                return "a layer that is not Conv2d + BatchNorm2d + ReLU"
+        if any(l.bn.momentum is None for l in layers):
+            return "BatchNorm(momentum=None)"
+        return None
+
+    def _forward_train(self, points_xyz, features, indices, target_xyz):
+        """train mode under hip_training: sampler (indices only) -> gather_points -> ball query -> the grouped MLP with
+        BatchNorm batch statistics (train_ops.sa_group_train); same returns as eval, xyz carries no gradient"""
+        why = self._training_refusal()
+        if why is not None:
+            raise L.PcrError("PointSAModule: the HIP training graph covers one ball-query scale with use_xyz, max "
+                             "pooling and three ConvModules; this module has " + why)
+        from pcr_amd import train_ops as TO
+        points_xyz = points_xyz.detach().contiguous()
+        with torch.no_grad():
+            new_xyz, indices = self._sample_points(points_xyz, None if features is None else features.detach(), indices,
+                                                   target_xyz)
+            if indices is None:
+                raise L.PcrError("the HIP training graph gathers centres by index; pass `indices` or let the sampler run")
+            idx = self.groupers[0].query(points_xyz, new_xyz)
+        centre = indices.to(torch.int32).contiguous()
+        return new_xyz, TO.sa_group_train(self.mlps[0], points_xyz, features, idx, centre), indices
+
     def forward(self, points_xyz, features=None, indices=None, target_xyz=None):
         """points_xyz (B,N,3), features (B,C,N) -> new_xyz (B,M,3), new_features (B,sum C',M), indices (B,M)"""
+        if self.hip_training and self.training:
+            return self._forward_train(points_xyz, features, indices, target_xyz)
         points_xyz = points_xyz.contiguous()
         fused = self._fused_sample_and_query(points_xyz, features, indices, target_xyz)
         if fused is not None:

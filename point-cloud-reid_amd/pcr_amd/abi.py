@@ -363,6 +363,8 @@ SIGNATURES = {
     "pcr_bn_bwd_finalize_f32": "s <_BnBwd>S",
     "pcr_sa_l1_fwd_f32": "s FIFFFFFiiiiiS",
     "pcr_sa_l1_bwd_f32": "s FIFFFFFFFiiiiiS",
+    "pcr_sa_l1c_fwd_f32": "s FIIFFFFFiiiiiS",
+    "pcr_sa_l1c_bwd_f32": "s FIIFFFFFFFiiiiiS",
     "pcr_sa_pool_fwd_f32": "s FFFFIFiiiiS",
     "pcr_sa_pool_bwd_stats_f32": "s FFFFFiiiS",
     "pcr_tnorm_fwd_f32": "s FFFFFFFiiiifiS",

@@ -321,6 +321,104 @@ def dense(x, W, bias=None, x2=None, res=None, relu=False):
     return outs[0] if len(outs) == 1 else torch.cat(outs, dim=1)
 
 
+def _sa_mlp_fwd(ctx, xyz, idx, centre, tab, wa, b1, g1, be1, w2, b2, g2, be2, w3, b3, g3, be3, bns):
+    """The one forward of the grouped MLP in training mode (SaEdgeTrain and SaGroupTrain): layer 1 from the per-point
+    table, three (conv, BatchNorm over the B S K rows, ReLU) layers, max over K.  centre None: the first S points are the
+    centres and tab is [P ; Q] (pcr_sa_l1_fwd_f32); centre (B,S) int32: indexed centres, tab = P (pcr_sa_l1c_fwd_f32).
+    A bias may be None (a conv built without one)."""
+    xyz, idx = _dev(xyz), idx.contiguous()
+    L.require_i32(idx)
+    B, N, _ = xyz.shape
+    _, S, K = idx.shape
+    Ln = S * K
+    R = B * Ln
+    c1, c2, c3 = wa.shape[0], w2.shape[0], w3.shape[0]
+    dev = xyz.device
+    tab = None if tab is None else _dev(tab)
+    _bn_refuse(*bns)                                  # (all three, before the first layer's statistics are tracked)
+    y1 = _f32(B, c1, Ln, device=dev)
+    st1 = _f32(B, 2, _c32(c1), device=dev)
+    b1d = None if b1 is None else b1.detach()
+    if centre is None:
+        with _prof("sa_l1_fwd[c1=%d,N=%d,S=%d,K=%d]" % (c1, N, S, K), 8.0 * B * Ln * c1, 4.0 * B * (Ln * (c1 + 1) + 2 * c1 * N)):
+            L.run.pcr_sa_l1_fwd_f32(xyz, idx, tab, _dev(wa.detach()), b1d, y1, st1, B, N, S, K, c1, L.stream_ptr())
+    else:
+        centre = centre.contiguous()
+        L.require_i32(centre)
+        if tuple(centre.shape) != (B, S):
+            raise L.PcrError("centre indices must be (B, S) = (%d, %d), got %s" % (B, S, tuple(centre.shape)))
+        with _prof("sa_l1c_fwd[c1=%d,N=%d,S=%d,K=%d]" % (c1, N, S, K), 8.0 * B * Ln * c1, 4.0 * B * (Ln * (c1 + 1) + c1 * N)):
+            L.run.pcr_sa_l1c_fwd_f32(xyz, idx, centre, tab, _dev(wa.detach()), b1d, y1, st1, B, N, S, K, c1,
+                                     L.stream_ptr())
+    n1 = _bn_batch_step(st1, B, c1, R, g1, be1, bns[0])
+    y2, st2 = tdense_fwd(y1, pack_dev(w2), c2, isc=n1["scale"], ish=n1["shift"], in_relu=True, bias=b2, want_stats=True)
+    n2 = _bn_batch_step(st2, st2.shape[0], c2, R, g2, be2, bns[1])
+    # the last layer's launch also finds every centre's winning row where it can (max of the raw output for
+    # gamma >= 0, min otherwise: relu(scale y + shift) is monotone in y); the pooled activation is then one affine +
+    # ReLU over the (B,c3,S) winners instead of a second pass over the (B,c3,S K) tensor
+    y3, st3, *won = tdense_fwd(y2, pack_dev(w3), c3, isc=n2["scale"], ish=n2["shift"], in_relu=True, bias=b3,
+                               want_stats=True, pool=(K, g3) if FUSE_POOL else None)
+    won = won[0] if won else None                     # (tdense_fwd returns the third value only where it was asked)
+    n3 = _bn_batch_step(st3, st3.shape[0], c3, R, g3, be3, bns[2])
+    pooled = _f32(B, c3, S, device=dev)
+    if won is not None:
+        ymax, argmax = won
+        L.run.pcr_bn_affine_f32(ymax, None, n3["scale"], n3["shift"], None, None, None, None, 1, 0.0, pooled, B,
+                                c3, S, L.stream_ptr())
+    else:
+        argmax = torch.empty((B, c3, S), dtype=torch.int32, device=dev)
+        ymax = _f32(B, c3, S, device=dev)
+        with _prof("sa_pool_fwd[c=%d,S=%d,K=%d]" % (c3, S, K), 2.0 * B * Ln * c3, 4.0 * B * c3 * (Ln + 2 * S)):
+            L.run.pcr_sa_pool_fwd_f32(y3, n3["scale"], n3["shift"], pooled, argmax, ymax, B, c3, S, K,
+                                      L.stream_ptr())
+    ctx.save_for_backward(xyz, idx, y1, y2, y3, pooled, argmax, w2, w3, g1, g2, g3, ymax, centre)
+    ctx.norms = (n1, n2, n3)
+    ctx.has_tab = tab is not None
+    ctx.has_bias = (b1 is not None, b2 is not None, b3 is not None)
+    ctx.dims = (B, N, S, K, c1, c2, c3)
+    ctx.mark_non_differentiable(argmax)
+    return pooled
+
+
+def _sa_mlp_bwd(ctx, gp):
+    """-> (dtab, dwa, db1, dg1, dbe1, dW2, db2, dg2, dbe2, dW3, db3, dg3, dbe3); a bias that was None gets None"""
+    xyz, idx, y1, y2, y3, pooled, argmax, w2, w3, g1, g2, g3, ymax, centre = ctx.saved_tensors
+    n1, n2, n3 = ctx.norms
+    B, N, S, K, c1, c2, c3 = ctx.dims
+    Ln, R, dev = S * K, B * S * K, xyz.device
+    gp = gp.contiguous()
+    part3 = _f32(B, 2, _c32(c3), device=dev)
+    gz = _f32(B, c3, S, device=dev)          # the pooled gradient where the ReLU is open, zero elsewhere
+    L.run.pcr_sa_pool_bwd_stats_f32(gp, pooled, ymax, part3, gz, B, c3, S, L.stream_ptr())
+    k3 = bn_bwd_finalize(part3, B, c3, R, g3, n3["mean"], n3["invstd"])
+    # (128 x 128 layers: dx and dW on the bf16 matrix core when TRAIN_PRECISION says so)
+    bf3 = pack_bf_T(w3) if (_bwd_bf() and c3 == 128 and c2 == 128) else None
+    bf2 = pack_bf_T(w2) if (_bwd_bf() and c2 == 128 and c1 == 128) else None
+    r3 = tdense_bwd(gz, y2, c3, dy_mode=3, y=y3, k=k3, argmax=argmax, pooled=None, K=K, S=S,
+                    isc=n2["scale"], ish=n2["shift"], iinv=n2["inv_scale"], in_relu=True,
+                    wpT=pack_dev(w3, transpose=True), want_dstats=True, wpT_bf=bf3)
+    k2 = bn_bwd_finalize(r3["dstats"], r3["dstats"].shape[0], c2, R, g2, n2["mean"], n2["invstd"])
+    r2 = tdense_bwd(r3["dx"], y1, c2, dy_mode=1, y=y2, k=k2, isc=n1["scale"], ish=n1["shift"], iinv=n1["inv_scale"],
+                    in_relu=True, wpT=pack_dev(w2, transpose=True), want_dstats=True, wpT_bf=bf2)
+    k1 = bn_bwd_finalize(r2["dstats"], r2["dstats"].shape[0], c1, R, g1, n1["mean"], n1["invstd"])
+    dwa_p = _f32(B, c1, 4, device=dev)
+    if centre is None:
+        dtab = _f32(B, 2 * c1, N, device=dev) if ctx.has_tab else None
+        with _prof("sa_l1_bwd[c1=%d,N=%d,S=%d,K=%d]" % (c1, N, S, K), 10.0 * B * Ln * c1, 4.0 * B * (Ln * (2 * c1 + 1) + 2 * c1 * N)):
+            L.run.pcr_sa_l1_bwd_f32(xyz, idx, r2["dx"], y1, k1["ka"], k1["kb"], k1["kc"], dtab, dwa_p, B, N, S, K, c1,
+                                    L.stream_ptr())
+    else:
+        dtab = _f32(B, c1, N, device=dev) if ctx.has_tab else None
+        with _prof("sa_l1c_bwd[c1=%d,N=%d,S=%d,K=%d]" % (c1, N, S, K), 10.0 * B * Ln * c1, 4.0 * B * (Ln * (2 * c1 + 1) + c1 * N)):
+            L.run.pcr_sa_l1c_bwd_f32(xyz, idx, centre, r2["dx"], y1, k1["ka"], k1["kb"], k1["kc"], dtab, dwa_p, B, N, S,
+                                     K, c1, L.stream_ptr())
+    dwa4 = reduce_parts(dwa_p, B, c1 * 4, c1, 4, 4)
+    hb = ctx.has_bias
+    return (dtab, dwa4[:, :3].contiguous(), dwa4[:, 3].contiguous() if hb[0] else None, k1["dgamma"], k1["dbeta"],
+            r2["dW"], r2["db"] if hb[1] else None, k2["dgamma"], k2["dbeta"],
+            r3["dW"], r3["db"] if hb[2] else None, k3["dgamma"], k3["dbeta"])
+
+
 class SaEdgeTrain(Function):
     """Grouped edge MLP of one set-abstraction layer in TRAINING mode: layer 1 from per-point tables, three
     (conv, BatchNorm over the batch, ReLU) layers, max over K.  Inputs: xyz (B,N,3), idx (B,S,K) int32, tab (B,2c1,N)
@@ -329,78 +427,29 @@ class SaEdgeTrain(Function):
 
     @staticmethod
     def forward(ctx, xyz, idx, tab, wa, b1, g1, be1, w2, b2, g2, be2, w3, b3, g3, be3, bns):
-        xyz, idx = _dev(xyz), idx.contiguous()
-        L.require_i32(idx)
-        B, N, _ = xyz.shape
-        _, S, K = idx.shape
-        Ln = S * K
-        R = B * Ln
-        c1, c2, c3 = wa.shape[0], w2.shape[0], w3.shape[0]
-        dev = xyz.device
-        tab = None if tab is None else _dev(tab)
-        _bn_refuse(*bns)                                  # (all three, before the first layer's statistics are tracked)
-        y1 = _f32(B, c1, Ln, device=dev)
-        st1 = _f32(B, 2, _c32(c1), device=dev)
-        with _prof("sa_l1_fwd[c1=%d,N=%d,S=%d,K=%d]" % (c1, N, S, K), 8.0 * B * Ln * c1, 4.0 * B * (Ln * (c1 + 1) + 2 * c1 * N)):
-            L.run.pcr_sa_l1_fwd_f32(xyz, idx, tab, _dev(wa.detach()), b1.detach(), y1, st1, B, N, S, K, c1,
-                                    L.stream_ptr())
-        n1 = _bn_batch_step(st1, B, c1, R, g1, be1, bns[0])
-        y2, st2 = tdense_fwd(y1, pack_dev(w2), c2, isc=n1["scale"], ish=n1["shift"], in_relu=True, bias=b2, want_stats=True)
-        n2 = _bn_batch_step(st2, st2.shape[0], c2, R, g2, be2, bns[1])
-        # the last layer's launch also finds every centre's winning row where it can (max of the raw output for
-        # gamma >= 0, min otherwise: relu(scale y + shift) is monotone in y); the pooled activation is then one affine +
-        # ReLU over the (B,c3,S) winners instead of a second pass over the (B,c3,S K) tensor
-        y3, st3, *won = tdense_fwd(y2, pack_dev(w3), c3, isc=n2["scale"], ish=n2["shift"], in_relu=True, bias=b3,
-                                   want_stats=True, pool=(K, g3) if FUSE_POOL else None)
-        won = won[0] if won else None                     # (tdense_fwd returns the third value only where it was asked)
-        n3 = _bn_batch_step(st3, st3.shape[0], c3, R, g3, be3, bns[2])
-        pooled = _f32(B, c3, S, device=dev)
-        if won is not None:
-            ymax, argmax = won
-            L.run.pcr_bn_affine_f32(ymax, None, n3["scale"], n3["shift"], None, None, None, None, 1, 0.0, pooled, B,
-                                    c3, S, L.stream_ptr())
-        else:
-            argmax = torch.empty((B, c3, S), dtype=torch.int32, device=dev)
-            ymax = _f32(B, c3, S, device=dev)
-            with _prof("sa_pool_fwd[c=%d,S=%d,K=%d]" % (c3, S, K), 2.0 * B * Ln * c3, 4.0 * B * c3 * (Ln + 2 * S)):
-                L.run.pcr_sa_pool_fwd_f32(y3, n3["scale"], n3["shift"], pooled, argmax, ymax, B, c3, S, K,
-                                          L.stream_ptr())
-        ctx.save_for_backward(xyz, idx, y1, y2, y3, pooled, argmax, w2, w3, g1, g2, g3, ymax)
-        ctx.norms = (n1, n2, n3)
-        ctx.has_tab = tab is not None
-        ctx.dims = (B, N, S, K, c1, c2, c3)
-        ctx.mark_non_differentiable(argmax)
-        return pooled
+        return _sa_mlp_fwd(ctx, xyz, idx, None, tab, wa, b1, g1, be1, w2, b2, g2, be2, w3, b3, g3, be3, bns)
 
     @staticmethod
     def backward(ctx, gp):
-        xyz, idx, y1, y2, y3, pooled, argmax, w2, w3, g1, g2, g3, ymax = ctx.saved_tensors
-        n1, n2, n3 = ctx.norms
-        B, N, S, K, c1, c2, c3 = ctx.dims
-        Ln, R, dev = S * K, B * S * K, xyz.device
-        gp = gp.contiguous()
-        part3 = _f32(B, 2, _c32(c3), device=dev)
-        gz = _f32(B, c3, S, device=dev)          # the pooled gradient where the ReLU is open, zero elsewhere
-        L.run.pcr_sa_pool_bwd_stats_f32(gp, pooled, ymax, part3, gz, B, c3, S, L.stream_ptr())
-        k3 = bn_bwd_finalize(part3, B, c3, R, g3, n3["mean"], n3["invstd"])
-        # (128 x 128 layers: dx and dW on the bf16 matrix core when TRAIN_PRECISION says so)
-        bf3 = pack_bf_T(w3) if (_bwd_bf() and c3 == 128 and c2 == 128) else None
-        bf2 = pack_bf_T(w2) if (_bwd_bf() and c2 == 128 and c1 == 128) else None
-        r3 = tdense_bwd(gz, y2, c3, dy_mode=3, y=y3, k=k3, argmax=argmax, pooled=None, K=K, S=S,
-                        isc=n2["scale"], ish=n2["shift"], iinv=n2["inv_scale"], in_relu=True,
-                        wpT=pack_dev(w3, transpose=True), want_dstats=True, wpT_bf=bf3)
-        k2 = bn_bwd_finalize(r3["dstats"], r3["dstats"].shape[0], c2, R, g2, n2["mean"], n2["invstd"])
-        r2 = tdense_bwd(r3["dx"], y1, c2, dy_mode=1, y=y2, k=k2, isc=n1["scale"], ish=n1["shift"], iinv=n1["inv_scale"],
-                        in_relu=True, wpT=pack_dev(w2, transpose=True), want_dstats=True, wpT_bf=bf2)
-        k1 = bn_bwd_finalize(r2["dstats"], r2["dstats"].shape[0], c1, R, g1, n1["mean"], n1["invstd"])
-        dtab = _f32(B, 2 * c1, N, device=dev) if ctx.has_tab else None
-        dwa_p = _f32(B, c1, 4, device=dev)
-        with _prof("sa_l1_bwd[c1=%d,N=%d,S=%d,K=%d]" % (c1, N, S, K), 10.0 * B * Ln * c1, 4.0 * B * (Ln * (2 * c1 + 1) + 2 * c1 * N)):
-            L.run.pcr_sa_l1_bwd_f32(xyz, idx, r2["dx"], y1, k1["ka"], k1["kb"], k1["kc"], dtab, dwa_p, B, N, S, K, c1,
-                                    L.stream_ptr())
-        dwa4 = reduce_parts(dwa_p, B, c1 * 4, c1, 4, 4)
-        return (None, None, dtab, dwa4[:, :3].contiguous(), dwa4[:, 3].contiguous(), k1["dgamma"], k1["dbeta"],
-                r2["dW"], r2["db"], k2["dgamma"], k2["dbeta"], r3["dW"], r3["db"], k3["dgamma"], k3["dbeta"], None)
+        return (None, None) + _sa_mlp_bwd(ctx, gp) + (None,)
+
+
+class SaGroupTrain(Function):
+    """Grouped MLP of one ball-query scale of a PointSAModule in TRAINING mode (QueryAndGroup with use_xyz + three
+    ConvModules + max over K).  Rows are [xyz_i - xyz_centre, f_i]; centre (B,S) int32 holds the sampled centres' point
+    indices; rows k >= cnt of a centre are the ball query's copies of its row 0 and count in the batch statistics and
+    in every gradient, as they do in nn.BatchNorm2d over (B,C,S,K).  tab (B,c1,N) = Wf f or None; a conv bias may be
+    None.  -> pooled (B,c3,S).  Same body as SaEdgeTrain; the first-layer launches are pcr_sa_l1c_*."""
+
+    @staticmethod
+    def forward(ctx, xyz, idx, centre, tab, wa, b1, g1, be1, w2, b2, g2, be2, w3, b3, g3, be3, bns):
+        if centre is None:
+            raise L.PcrError("SaGroupTrain needs the centres' point indices")
+        return _sa_mlp_fwd(ctx, xyz, idx, centre, tab, wa, b1, g1, be1, w2, b2, g2, be2, w3, b3, g3, be3, bns)
+
+    @staticmethod
+    def backward(ctx, gp):
+        return (None, None, None) + _sa_mlp_bwd(ctx, gp) + (None,)
 
 
 def sa_edge_train(sa, xyz, feats, idx):
@@ -420,6 +469,25 @@ def sa_edge_train(sa, xyz, feats, idx):
     for l in (1, 2):
         args += [convs[l].weight.view(convs[l].weight.shape[0], -1), convs[l].bias, bns[l].weight, bns[l].bias]
     return SaEdgeTrain.apply(*args, bns)
+
+
+def sa_group_train(mlp, xyz, feats, idx, centre):
+    """One ball-query scale of a PointSAModule in training mode: mlp = its nn.Sequential of three ConvModules (conv, bn,
+    ReLU), xyz (B,N,3) (no gradient), feats (B,D,N) or None, idx (B,S,K) int32 from ball_query, centre (B,S) int32 the
+    sampled centres -> (B,c3,S).  The first conv's weight [Wa | Wf] is split here and P = Wf f is one dense layer over
+    the N points; the gradient reaches feats and Wf through dtab."""
+    layers = list(mlp.children())
+    convs, bns = [l.conv for l in layers], [l.bn for l in layers]
+    c1 = convs[0].weight.shape[0]
+    w1 = convs[0].weight.view(c1, -1)
+    D = 0 if feats is None else feats.shape[1]
+    if w1.shape[1] != 3 + D:
+        raise L.PcrError("the first conv takes %d channels; the rows [dxyz, f] have 3 + %d" % (w1.shape[1], D))
+    tab = dense(feats.contiguous(), w1[:, 3:].contiguous()) if D else None     # (B, c1, N): P
+    args = [xyz.detach(), idx, centre, tab, w1[:, :3], convs[0].bias, bns[0].weight, bns[0].bias]
+    for l in (1, 2):
+        args += [convs[l].weight.view(convs[l].weight.shape[0], -1), convs[l].bias, bns[l].weight, bns[l].bias]
+    return SaGroupTrain.apply(*args, bns)
 
 
 # ---------------------------------------------------------------- attention / norm / pooling Functions --
